@@ -4,6 +4,15 @@ configuration: 3D Poisson 500^3 (125 M dof, 7-pt stencil) CSR fp64,
 smoothed-aggregation hierarchy, Chebyshev(2) pre/post smoother, V(1,1) cycles.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--grid 500] [--smoother chebyshev]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times exactly K steps and prints the line: `metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` (+ the configuration, setup times and residuals it already has).
+`--full` adds the extras described below (`roofline`: per-kernel timings, the step with 8-byte level-0 values;
+`cpu_baseline`: the C oracle timed on the host and the full-size parity check); without it both are null.
+`--dump-outputs DIR` writes what the last timed step computed (single-rank runs): DIR/residuals.npy (the residual
+norms of the timed solve), DIR/x_sample.npy and DIR/x_sample_index.npy (a fixed, seeded sample of at most 2^21 entries
+of the iterate, float64; the whole iterate when it is smaller).
 
 --config selects the BASELINE.json configuration (default C3 = the metric's: 500^3, SA, Chebyshev(2)):
   C1  2D Poisson 500^2, ruge_stuben_solver, symmetric Gauss-Seidel (the README example)
@@ -13,8 +22,8 @@ smoothed-aggregation hierarchy, Chebyshev(2) pre/post smoother, V(1,1) cycles.
   C5  anisotropic diffusion, P1 on a jittered Kuhn tetrahedral mesh, --grid 360 -> 46.7 M unknowns (the largest cube
       whose BSR 3x3 data array stays below 2^31 values: int32 addressing, as in the reference), block-SA, symmetric
       block Gauss-Seidel
-Every line carries `roofline` (dominant kernel, bytes / live HIP-event time) and `cpu_baseline` (the C oracle timed
-on this box's host cores, with the CPU model) and checks the first iterate against the oracle at the full size.
+With --full every line carries `roofline` (dominant kernel, bytes / live HIP-event time) and `cpu_baseline` (the C
+oracle timed on the host cores, with the CPU model) and checks the first iterate against the oracle at the full size.
 
 One "step" = one multilevel_solver.solve() iteration: a V-cycle + the residual
 norm (pyamg/multilevel.py:454-461).  The hierarchy is resident in HBM before the
@@ -64,6 +73,27 @@ def setup_seconds(t_gen, t_setup):
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_SAMPLE = 1 << 21      # entries of the iterate written by --dump-outputs (x_sample + its index: 32 MB in float64)
+
+
+def dump_outputs(ddir, L, h, n, residuals):
+    """--dump-outputs DIR: what the last timed step computed, as a caller of the solve receives it -- the residual
+    norms of the timed solve and the iterate x (downloaded from HBM; a fixed, seeded sample when it is larger than
+    DUMP_SAMPLE entries).  Runs right after the timed region, before anything else touches the device vectors."""
+    from pyamg_amd import _lib
+    x = np.empty(n)
+    _lib.check(L.amg_dev_copy(x.ctypes.data, L.amg_hier_dev_x(h), n, 1, L.amg_hier_stream(h)))   # 1 = device -> host
+    if n <= DUMP_SAMPLE:
+        idx = np.arange(n)
+    else:
+        idx = np.unique(np.random.default_rng(20240601).integers(0, n, DUMP_SAMPLE))
+    os.makedirs(ddir, exist_ok=True)
+    np.save(os.path.join(ddir, "residuals.npy"), np.asarray(residuals, dtype=np.float64))
+    np.save(os.path.join(ddir, "x_sample.npy"), x[idx])
+    np.save(os.path.join(ddir, "x_sample_index.npy"), idx.astype(np.float64))
+    log("[bench] outputs written to %s: %d residual norms, %d of %d iterate entries" % (ddir, len(residuals), len(idx), n))
 
 
 def build_hierarchy(grid, smoother, cache=None):
@@ -304,9 +334,11 @@ def partitioned_main(args, rank, local_rank, world, torch, dist):
         _lib.check(Lb.amg_hier_comm_check(h))
         timed = res[:nres.value].copy()
         r0 = float(warm[0])
-        ms_resid = C.c_double(0.0)
-        _lib.check(Lb.amg_hier_time_spmv(h, 0, 0, 1, 20, C.byref(ms_resid)))
-        ms_resid = ms_resid.value
+        ms_resid = None
+        if args.full:
+            ms_resid = C.c_double(0.0)
+            _lib.check(Lb.amg_hier_time_spmv(h, 0, 0, 1, 20, C.byref(ms_resid)))
+            ms_resid = ms_resid.value
         form = Lb.amg_hier_operator_form(h, 0)
         moved = Lb.amg_hier_operator_bytes(h, 0, 1)
         coded0 = Lb.amg_hier_value_index(h, 0, -1)
@@ -321,13 +353,15 @@ def partitioned_main(args, rank, local_rank, world, torch, dist):
         sync_all()
         wall = time.perf_counter() - t0
         lv = S.lv[0]
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        S.be.apply(lv.A, 2, lv.x, lv.b, None, lv.r, None, 0.0)
-        e0.record()
-        for _ in range(20):
+        ms_resid = None
+        if args.full:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             S.be.apply(lv.A, 2, lv.x, lv.b, None, lv.r, None, 0.0)
-        e1.record(); torch.cuda.synchronize()
-        ms_resid = e0.elapsed_time(e1) / 20
+            e0.record()
+            for _ in range(20):
+                S.be.apply(lv.A, 2, lv.x, lv.b, None, lv.r, None, 0.0)
+            e1.record(); torch.cuda.synchronize()
+            ms_resid = e0.elapsed_time(e1) / 20
         form = S.operator_form(0)
         moved = None
         coded0 = 0
@@ -341,7 +375,18 @@ def partitioned_main(args, rank, local_rank, world, torch, dist):
         spmv_bytes = 12.0 * lv.nnzA + 4.0 * (n_own + 1) + 24.0 * n_own
         if moved is None:
             moved = spmv_bytes
-        ach = moved / (ms_resid * 1e-3) / 1e9
+        roofline = None
+        if ms_resid is not None:
+            ach = moved / (ms_resid * 1e-3) / 1e9
+            roofline = {"bound": "hbm",
+                        "kernel": {0: "csr_stream_kernel", 1: "csr_pattern_kernel", 2: "stencil_coded_kernel (one-byte value codes)" if coded0 else "stencil2_kernel"}.get(form, "csr_stream_kernel") +
+                                  " (level-0 A-application on rank 0's row block)",
+                        "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None,
+                        "traffic_source": "not measured in this run (PMC passes need rocprofv3 around a single rank)",
+                        "bytes_per_launch": moved, "ms_per_launch": round(ms_resid, 4),
+                        "csr_equivalent_bytes_per_launch": spmv_bytes,
+                        "csr_equivalent_GBs": round(spmv_bytes / (ms_resid * 1e-3) / 1e9, 1)}
         out = {
             "metric": "V-cycle iterations/sec (3D Poisson %d^3 fp64, SA-AMG, %s smoother)" % (args.grid, args.smoother),
             "value": round(args.steps / wall, 4), "unit": "V-cycle iterations/s", "n_gpus": world,
@@ -358,16 +403,7 @@ def partitioned_main(args, rank, local_rank, world, torch, dist):
                        "replicated_from_level": S.first_rep,
                        "setup_seconds": setup_seconds(t_gen, t_setup),
                        "residuals": [r0, float(warm[-1]), float(timed[-1])]},
-            "roofline": {"bound": "hbm",
-                         "kernel": {0: "csr_stream_kernel", 1: "csr_pattern_kernel", 2: "stencil_coded_kernel (one-byte value codes)" if coded0 else "stencil2_kernel"}.get(form, "csr_stream_kernel") +
-                                   " (level-0 A-application on rank 0's row block)",
-                         "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None,
-                         "traffic_source": "not measured in this run (PMC passes need rocprofv3 around a single rank)",
-                         "bytes_per_launch": moved, "ms_per_launch": round(ms_resid, 4),
-                         "csr_equivalent_bytes_per_launch": spmv_bytes,
-                         "csr_equivalent_GBs": round(spmv_bytes / (ms_resid * 1e-3) / 1e9, 1)},
-            "cpu_baseline": cpu,
+            "roofline": roofline, "cpu_baseline": cpu,
         }
         print(json.dumps(out), flush=True)
     S.close()
@@ -468,7 +504,10 @@ def config_main(args, rank, local_rank, world, torch, dist, L):
         tw = torch.tensor([wall], dtype=torch.float64)
         dist.all_reduce(tw, op=dist.ReduceOp.MAX)
         wall = float(tw.item())
-    if rank == 0:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, L, h, n, timed_res)
+    roofline = cpu = None
+    if rank == 0 and args.full:
         A0 = ml.levels[0].A
         if kind == "block_gs":
             bs = A0.blocksize[0]
@@ -507,7 +546,6 @@ def config_main(args, rank, local_rank, world, torch, dist, L):
             moved = L.amg_hier_operator_bytes(h, 0, 1)
             roofline["level0_residual_bytes_moved"] = moved
             roofline["level0_residual_moved_GBs"] = round(moved / (ms_resid * 1e-3) / 1e9, 1)
-        cpu = None
         if not args.no_cpu_baseline:
             def gpu_first():
                 xg = np.zeros(n)
@@ -515,6 +553,7 @@ def config_main(args, rank, local_rank, world, torch, dist, L):
                 _lib.check(L.amg_hier_solve(h, b.ctypes.data, xg.ctypes.data, 0.0, 1, 0, _lib.dp(r1), C.byref(n1), NO_EARLY_STOP | X0_ZERO))
                 return xg, float(r1[1])
             cpu = cpu_baseline_of(ml, b, gpu_first)
+    if rank == 0:
         out = {
             "metric": "V-cycle iterations/sec (BASELINE configuration %s)" % cfg,
             "value": round(world * args.steps / wall, 4), "unit": "V-cycle iterations/s", "n_gpus": world,
@@ -554,6 +593,11 @@ def main():
     ap.add_argument("--tile-target", type=int, default=None)
     ap.add_argument("--replicas", action="store_true", help="N>1: independent replicas instead of partitioning")
     ap.add_argument("--cache", default=None, help="directory of saved hierarchies: skip the setup on reruns")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the extras: roofline / per-kernel timings, the step with 8-byte level-0 values, "
+                         "the CPU oracle baseline and the full-size parity check (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/*.npy (single-rank runs)")
     args = ap.parse_args()
     if args.grid is None:
         args.grid = {"C1": 500, "C2": 2000, "C3": 500, "C4": 500, "C5": 360}[args.config]
@@ -561,6 +605,10 @@ def main():
         args.smoother = "hybrid_gs" if args.config == "C4" else "chebyshev"
     if args.steps is None:
         args.steps = {"C1": 200, "C2": 500}.get(args.config, 50)
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.dump_outputs and args.gpus > 1 and not args.replicas:
+        raise SystemExit("--dump-outputs: single-rank runs only (the partitioned solve keeps its iterate split over the ranks)")
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args)           # before anything touches the GPU
@@ -653,13 +701,16 @@ def main():
         tw = torch.tensor([wall], dtype=torch.float64)
         dist.all_reduce(tw, op=dist.ReduceOp.MAX)
         wall = float(tw.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, L, h, n, timed_res)
 
-    cycle_bytes = dev.cycle_bytes("V")
     cycles_per_s = world * args.steps / wall
 
     out = None
-    if rank == 0:
-        A0 = ml.levels[0].A
+    A0 = ml.levels[0].A
+    roofline = cpu = None
+    if rank == 0 and args.full:
+        cycle_bytes = dev.cycle_bytes("V")
         reps = 20
         NAMES = {0: "csr_stream_kernel", 1: "csr_pattern_kernel", 2: "stencil2_kernel", 3: "sell_kernel"}
         PMC_KEYS = {"sell_kernel": "level1_residual", "stencil_coded_kernel": "level0_coded", "stencil2_kernel": "level0_values"}
@@ -761,7 +812,6 @@ def main():
             ent2 = ents.get(PMC_KEYS.get(other["kernel"].split("<")[0])) if other is not None else None
             if ent2 is not None:
                 other["traffic"] = ent2["traffic_bytes"]
-        cpu = None
         if not args.no_cpu_baseline:
             def gpu_first():
                 xg = np.zeros(n)
@@ -770,6 +820,7 @@ def main():
                                             NO_EARLY_STOP | X0_ZERO))
                 return xg, float(r1[1])
             cpu = cpu_baseline_of(ml, b, gpu_first)
+    if rank == 0:
         out = {
             "metric": "V-cycle iterations/sec (3D Poisson %d^3 fp64, SA-AMG, %s smoother)" % (args.grid, args.smoother),
             "value": round(cycles_per_s, 4), "unit": "V-cycle iterations/s", "n_gpus": world,

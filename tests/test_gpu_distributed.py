@@ -369,7 +369,7 @@ def test_bench_config_c4_runs_partitioned_hybrid_gauss_seidel(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "AMG_DIST_TRANSPORT")}
     for extra in (["--gpus", "2"], ["--smoother", "hybrid_gs_lex"]):
         p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "C4", "--grid", "40", "--steps", "3",
-                            "--warmup", "2"] + extra, env=env, capture_output=True, text=True, timeout=900)
+                            "--warmup", "2", "--full"] + extra, env=env, capture_output=True, text=True, timeout=900)
         assert p.returncode == 0, p.stderr[-3000:]
         line = json.loads(p.stdout.strip().splitlines()[-1])
         assert line["steps"] == 3 and line["roofline"]["frac"] > 0
@@ -390,7 +390,7 @@ def test_bench_gpus_2_runs_two_ranks(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "AMG_DIST_TRANSPORT")}
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--grid", "48", "--steps", "3",
-                        "--warmup", "2"], env=env, capture_output=True, text=True, timeout=900)
+                        "--warmup", "2", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["steps"] == 3

@@ -5,7 +5,7 @@ set -o pipefail
 export TMPDIR=/tmp
 O=gpurun_out
 mkdir -p $O
-python bench.py > $O/r02_bench500.json 2> $O/r02_bench500.err && tail -c 600 $O/r02_bench500.json && \
+python bench.py --full > $O/r02_bench500.json 2> $O/r02_bench500.err && tail -c 600 $O/r02_bench500.json && \
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_r02 -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-value-index > $O/r02_bench500_under_rocprof.json 2> $O/r02_rocprof.err && \
 python tools/trace_cycle.py $(ls $O/prof_r02/*/*kernel_trace.csv | head -1) 10 > $O/r02_bench500_timed_region.txt && \
 cp $(ls $O/prof_r02/*/*kernel_stats.csv | head -1) $O/r02_bench500_kernel_stats.csv && \
