@@ -5,8 +5,8 @@
  * multigrid hierarchy that runs multilevel_solver.solve() entirely in HBM.
  *
  * C ABI only: plain pointers, ints and doubles; no C++/torch types.  fp64
- * values, int32 indices (the reference instantiates `int` indices only,
- * pyamg/amg_core/amg_core.i:108).  Every function returns 0 on success or a
+ * values (section 1 also float32, complex64, complex128), int32 indices (the
+ * reference instantiates `int` indices only, pyamg/amg_core/amg_core.i:108).  Every function returns 0 on success or a
  * negative AMG_E* code; amg_last_error() gives the message.  Nothing here
  * falls back to the CPU: without a usable HIP device every compute entry
  * point fails with AMG_ENODEV.
@@ -119,6 +119,66 @@ int amgcore_bsr_matvec_f64(int n_brow, int n_bcol, int R, int C, const int Ap[],
                            const double Ax[], const double x[], double y[]);
 /* pyamg/util/linalg.py:17-53 norm(x) (2-norm) */
 int amgcore_norm2_f64(const double x[], long n, double *result);
+
+/* The same thirteen entries for the reference's other value types (amg_core.i:139-144): suffix _f32
+ * (float), _c64 (complex<float>) and _c128 (complex<double>), with the argument lists of the _f64
+ * entries.  Complex values are interleaved (re, im) pairs, numpy's layout; every *_size counts
+ * elements of the value type.  F is the real type of the value type: the omega of gauss_seidel_ne /
+ * gauss_seidel_nr.  Rounding follows the reference's compiled kernels bit for bit. */
+typedef struct { float re, im; } amg_c64;
+typedef struct { double re, im; } amg_c128;
+
+#define AMGCORE_TYPED_ENTRIES(SUF, T, F)                                                                       \
+int amgcore_gauss_seidel_##SUF(const int Ap[], int Ap_size, const int Aj[], int Aj_size, const T Ax[],         \
+                               int Ax_size, T x[], int x_size, const T b[], int b_size,                       \
+                               int row_start, int row_stop, int row_step);                                    \
+int amgcore_bsr_gauss_seidel_##SUF(const int Ap[], int Ap_size, const int Aj[], int Aj_size, const T Ax[],     \
+                                   int Ax_size, T x[], int x_size, const T b[], int b_size,                   \
+                                   int row_start, int row_stop, int row_step, int blocksize);                 \
+int amgcore_jacobi_##SUF(const int Ap[], int Ap_size, const int Aj[], int Aj_size, const T Ax[], int Ax_size,  \
+                         T x[], int x_size, const T b[], int b_size, T temp[], int temp_size,                 \
+                         int row_start, int row_stop, int row_step, const T omega[], int omega_size);         \
+int amgcore_bsr_jacobi_##SUF(const int Ap[], int Ap_size, const int Aj[], int Aj_size, const T Ax[],           \
+                             int Ax_size, T x[], int x_size, const T b[], int b_size, T temp[],               \
+                             int temp_size, int row_start, int row_stop, int row_step, int blocksize,         \
+                             const T omega[], int omega_size);                                                \
+int amgcore_gauss_seidel_indexed_##SUF(const int Ap[], int Ap_size, const int Aj[], int Aj_size,               \
+                                       const T Ax[], int Ax_size, T x[], int x_size, const T b[],             \
+                                       int b_size, const int Id[], int Id_size,                               \
+                                       int row_start, int row_stop, int row_step);                            \
+int amgcore_jacobi_ne_##SUF(const int Ap[], int Ap_size, const int Aj[], int Aj_size, const T Ax[],            \
+                            int Ax_size, T x[], int x_size, const T b[], int b_size, const T Tx[],            \
+                            int Tx_size, T temp[], int temp_size, int row_start, int row_stop,                \
+                            int row_step, const T omega[], int omega_size);                                   \
+int amgcore_overlapping_schwarz_csr_##SUF(const int Ap[], int Ap_size, const int Aj[], int Aj_size,            \
+                                          const T Ax[], int Ax_size, T x[], int x_size, const T b[],          \
+                                          int b_size, const T Tx[], int Tx_size, const int Tp[],              \
+                                          int Tp_size, const int Sj[], int Sj_size, const int Sp[],           \
+                                          int Sp_size, int nsdomains, int nrows,                              \
+                                          int row_start, int row_stop, int row_step);                         \
+int amgcore_gauss_seidel_ne_##SUF(const int Ap[], int Ap_size, const int Aj[], int Aj_size, const T Ax[],      \
+                                  int Ax_size, T x[], int x_size, const T b[], int b_size,                    \
+                                  int row_start, int row_stop, int row_step, const T Tx[], int Tx_size,       \
+                                  F omega);                                                                   \
+int amgcore_gauss_seidel_nr_##SUF(const int Ap[], int Ap_size, const int Aj[], int Aj_size, const T Ax[],      \
+                                  int Ax_size, T x[], int x_size, T z[], int z_size,                          \
+                                  int col_start, int col_stop, int col_step, const T Tx[], int Tx_size,       \
+                                  F omega);                                                                   \
+int amgcore_block_jacobi_##SUF(const int Ap[], int Ap_size, const int Aj[], int Aj_size, const T Ax[],         \
+                               int Ax_size, T x[], int x_size, const T b[], int b_size, const T Tx[],         \
+                               int Tx_size, T temp[], int temp_size, int row_start, int row_stop,             \
+                               int row_step, const T omega[], int omega_size, int blocksize);                 \
+int amgcore_block_gauss_seidel_##SUF(const int Ap[], int Ap_size, const int Aj[], int Aj_size, const T Ax[],   \
+                                     int Ax_size, T x[], int x_size, const T b[], int b_size, const T Tx[],   \
+                                     int Tx_size, int row_start, int row_stop, int row_step, int blocksize);  \
+int amgcore_csr_matvec_##SUF(int n_row, int n_col, const int Ap[], const int Aj[], const T Ax[],               \
+                             const T x[], T y[]);                                                             \
+int amgcore_bsr_matvec_##SUF(int n_brow, int n_bcol, int R, int C, const int Ap[], const int Aj[],             \
+                             const T Ax[], const T x[], T y[]);
+
+AMGCORE_TYPED_ENTRIES(f32, float, float)
+AMGCORE_TYPED_ENTRIES(c64, amg_c64, float)
+AMGCORE_TYPED_ENTRIES(c128, amg_c128, double)
 
 /* ------------------------------------------------------------------------ */
 /* 2. Device-resident hierarchy: multilevel_solver.solve()/__solve()         */

@@ -38,6 +38,44 @@ class SmootherDesc(C.Structure):
                 ("Sj", c_int_p), ("Sp", c_int_p), ("Tp", c_int_p), ("Tx", c_dbl_p), ("nsdomains", C.c_int)]
 
 
+# The flat amg_core table (include/amgcore_hip.h section 1): each entry's arguments in the SWIG call order.
+# "I" int32 array, "V" value array, "i" int, "F" real scalar (the real type of the values); a `sized` entry
+# passes every array followed by its length, as the C++ prototypes of amg_core do.
+FLAT_TABLE = {
+    "gauss_seidel": ("IIVVViii", True),
+    "bsr_gauss_seidel": ("IIVVViiii", True),
+    "jacobi": ("IIVVVViiiV", True),
+    "bsr_jacobi": ("IIVVVViiiiV", True),
+    "gauss_seidel_indexed": ("IIVVVIiii", True),
+    "jacobi_ne": ("IIVVVVViiiV", True),
+    "overlapping_schwarz_csr": ("IIVVVVIIIiiiii", True),
+    "gauss_seidel_ne": ("IIVVViiiVF", True),
+    "gauss_seidel_nr": ("IIVVViiiVF", True),
+    "block_jacobi": ("IIVVVVViiiVi", True),
+    "block_gauss_seidel": ("IIVVVViiii", True),
+    "csr_matvec": ("iiIIVVV", False),
+    "bsr_matvec": ("iiiiIIVVV", False),
+}
+# value dtype -> symbol suffix, and per suffix the C types of a value pointer and of the real scalar F
+VALUE_SUFFIX = {np.dtype(np.float64): "f64", np.dtype(np.float32): "f32",
+                np.dtype(np.complex64): "c64", np.dtype(np.complex128): "c128"}
+VALUE_CTYPES = {"f64": (c_dbl_p, C.c_double), "f32": (C.POINTER(C.c_float), C.c_float),
+                "c64": (C.c_void_p, C.c_float), "c128": (C.c_void_p, C.c_double)}
+
+
+def flat_argtypes(kinds, sized, suffix):
+    vptr, real = VALUE_CTYPES[suffix]
+    out = []
+    for k in kinds:
+        if k in "IV":
+            out.append(c_int_p if k == "I" else vptr)
+            if sized:
+                out.append(C.c_int)
+        else:
+            out.append(C.c_int if k == "i" else real)
+    return out
+
+
 def build_library():
     """Compile the HIP sources in-tree (hipcc cross-compiles gfx950 without a GPU)."""
     import subprocess
@@ -64,23 +102,7 @@ def lib():
         pass
     L = C.CDLL(LIB_PATH)
     I, D, V = C.c_int, C.c_double, C.c_void_p
-    arr = [c_int_p, I, c_int_p, I, c_dbl_p, I]          # Ap, Aj, Ax with sizes
-    xb = [c_dbl_p, I, c_dbl_p, I]                       # x, b with sizes
     sig = {
-        "amgcore_gauss_seidel_f64": arr + xb + [I, I, I],
-        "amgcore_bsr_gauss_seidel_f64": arr + xb + [I, I, I, I],
-        "amgcore_jacobi_f64": arr + xb + [c_dbl_p, I, I, I, I, c_dbl_p, I],
-        "amgcore_bsr_jacobi_f64": arr + xb + [c_dbl_p, I, I, I, I, I, c_dbl_p, I],
-        "amgcore_gauss_seidel_indexed_f64": arr + xb + [c_int_p, I, I, I, I],
-        "amgcore_jacobi_ne_f64": arr + xb + [c_dbl_p, I, c_dbl_p, I, I, I, I, c_dbl_p, I],
-        "amgcore_overlapping_schwarz_csr_f64": arr + xb + [c_dbl_p, I, c_int_p, I, c_int_p, I, c_int_p, I,
-                                                           I, I, I, I, I],
-        "amgcore_gauss_seidel_ne_f64": arr + xb + [I, I, I, c_dbl_p, I, D],
-        "amgcore_gauss_seidel_nr_f64": arr + xb + [I, I, I, c_dbl_p, I, D],
-        "amgcore_block_jacobi_f64": arr + xb + [c_dbl_p, I, c_dbl_p, I, I, I, I, c_dbl_p, I, I],
-        "amgcore_block_gauss_seidel_f64": arr + xb + [c_dbl_p, I, I, I, I, I],
-        "amgcore_csr_matvec_f64": [I, I, c_int_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p],
-        "amgcore_bsr_matvec_f64": [I, I, I, I, c_int_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p],
         "amgcore_norm2_f64": [c_dbl_p, C.c_long, c_dbl_p],
         "amg_hier_set_matrix": [V, I, I, I, I, I, I, I, V, V, V, I],
         "amg_hier_set_smoother": [V, I, I, C.POINTER(SmootherDesc)],
@@ -139,6 +161,9 @@ def lib():
         "amg_galerkin_fetch": [V, V, V],
         "amg_csr_matmat_device": [I, I, I, V, V, V, V, V, V, V, C.POINTER(C.c_void_p)],
     }
+    for name, (kinds, sized) in FLAT_TABLE.items():
+        for suffix in VALUE_SUFFIX.values():
+            sig["amgcore_%s_%s" % (name, suffix)] = flat_argtypes(kinds, sized, suffix)
     for name, args in sig.items():
         f = getattr(L, name)
         f.argtypes = args

@@ -24,6 +24,7 @@ import numpy as np
 import scipy.sparse as sparse
 from scipy.sparse import bsr_matrix, csr_matrix, isspmatrix_bsr, isspmatrix_csr
 
+from ._lib import VALUE_CTYPES
 from .multilevel import multilevel_solver
 from .smoothing import change_smoothers
 from .util import (approximate_spectral_radius, approximate_spectral_radius_device, get_diagonal,
@@ -92,6 +93,11 @@ def host_lib():
         L.amgsetup_pattern_symmetric.restype = C.c_int
         L.amgsetup_extract_subblocks.argtypes = [ip, ip, dp, dp, ip, ip, ip, C.c_int, C.c_int]
         L.amgsetup_extract_subblocks.restype = None
+        for suffix in ("f32", "c64", "c128"):
+            f = getattr(L, "amgsetup_extract_subblocks_" + suffix)
+            vp = VALUE_CTYPES[suffix][0]
+            f.argtypes = [ip, ip, vp, vp, ip, ip, ip, C.c_int, C.c_int]
+            f.restype = None
         L.amgsetup_num_threads.restype = C.c_int
         L.amgsetup_set_num_threads.argtypes = [C.c_int]
         L.amgsetup_set_num_threads.restype = None

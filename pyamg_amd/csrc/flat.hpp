@@ -1,0 +1,89 @@
+// Host-side helpers of the flat amg_core entries (include/amgcore_hip.h, section 1), shared by
+// capi.hip (float64) and typed.hip (float32 / complex64 / complex128): argument checks, the row list
+// of a sweep, and an owning device buffer.
+#pragma once
+#include "amg_dev.hpp"
+#include "../../include/amgcore_hip.h"
+
+#include <vector>
+
+#ifndef CHK
+#define CHK(call)                   \
+    do {                            \
+        int rc__ = (call);          \
+        if (rc__ != 0) return rc__; \
+    } while (0)
+#endif
+
+namespace amg {
+namespace {
+
+// RAII device buffer
+struct DBuf {
+    void *p = nullptr;
+    ~DBuf() { if (p) hipFree(p); }
+    int alloc(size_t bytes)
+    {
+        hipError_t e = hipMalloc(&p, bytes + 128);
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc", __FILE__, __LINE__);
+        return 0;
+    }
+    int from_host(const void *src, size_t bytes)
+    {
+        CHK(alloc(bytes));
+        if (bytes) AMG_HIP(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
+        return 0;
+    }
+    int to_host(void *dst, size_t bytes) const
+    {
+        if (bytes) AMG_HIP(hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    double *d() const { return (double *)p; }
+    int *i() const { return (int *)p; }
+};
+
+int require_device()
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
+        set_error("no HIP device available (amgcore_hip has no CPU fallback)");
+        return AMG_ENODEV;
+    }
+    return 0;
+}
+
+// the rows visited by for(i = start; i != stop; i += step)
+int sweep_rows(int start, int stop, int step, int limit, std::vector<int> &rows)
+{
+    rows.clear();
+    if (step == 0) { set_error("row_step == 0"); return AMG_EINVAL; }
+    long span = (long)stop - start;
+    if (span == 0) return 0;
+    if (span % step != 0 || span / step < 0) {
+        set_error("row_start/row_stop/row_step never terminate");
+        return AMG_EINVAL;
+    }
+    long cnt = span / step;
+    rows.resize((size_t)cnt);
+    for (long t = 0; t < cnt; ++t) {
+        long i = start + t * step;
+        if (i < 0 || i >= limit) { set_error("sweep leaves the matrix"); return AMG_EINVAL; }
+        rows[(size_t)t] = (int)i;
+    }
+    return 0;
+}
+
+int check_csr(const int *Ap, int Ap_size, int Aj_size, int Ax_size, int per_entry)
+{
+    if (!Ap || Ap_size < 1) { set_error("bad Ap"); return AMG_EINVAL; }
+    long nnz = Ap[Ap_size - 1];
+    if (nnz < 0 || nnz > Aj_size || nnz * per_entry > Ax_size) {
+        set_error("Aj/Ax shorter than Ap[-1]");
+        return AMG_EINVAL;
+    }
+    return 0;
+}
+
+}  // namespace
+}  // namespace amg

@@ -3,6 +3,7 @@
 // these routines exist so that the build travels to the GPU box without the
 // reference: they restate the setup kernels the BASELINE configurations need.
 // All reference paths relative to /root/reference.
+#include <complex>
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -1164,20 +1165,22 @@ int amgsetup_num_threads(void)
 // Dense diagonal block of A for every subdomain (sorted index lists Sj[Sp[d]..Sp[d+1])), row-major into
 // Tx[Tp[d]..]: the input of the Schwarz smoother's block inversion (pyamg/amg_core/relaxation.h:836-899).
 // Rows of A and subdomains are both sorted, so a merge per row finds the common columns.
-void amgsetup_extract_subblocks(const int *Ap, const int *Aj, const double *Ax, double *Tx, const int *Tp,
-                                const int *Sj, const int *Sp, int nsdomains, int nrows)
+}  // extern "C"
+
+template <class T>
+static void extract_subblocks(const int *Ap, const int *Aj, const T *Ax, T *Tx, const int *Tp, const int *Sj,
+                              const int *Sp, int nsdomains)
 {
-    (void)nrows;
     const long total = nsdomains > 0 ? Tp[nsdomains] : 0;
 #pragma omp parallel for schedule(static)
-    for (long k = 0; k < total; ++k) Tx[k] = 0.0;
+    for (long k = 0; k < total; ++k) Tx[k] = T(0);
 #pragma omp parallel for schedule(dynamic, 256)
     for (int d = 0; d < nsdomains; ++d) {
         const int m = Sp[d + 1] - Sp[d];
         const int *S = Sj + Sp[d];
         for (int li = 0; li < m; ++li) {
             const int row = S[li];
-            double *Trow = Tx + Tp[d] + (long)li * m;
+            T *Trow = Tx + Tp[d] + (long)li * m;
             int lc = 0;
             for (int k = Ap[row]; k < Ap[row + 1] && lc < m; ++k) {
                 const int col = Aj[k];
@@ -1186,6 +1189,34 @@ void amgsetup_extract_subblocks(const int *Ap, const int *Aj, const double *Ax, 
             }
         }
     }
+}
+
+extern "C" {
+
+void amgsetup_extract_subblocks(const int *Ap, const int *Aj, const double *Ax, double *Tx, const int *Tp,
+                                const int *Sj, const int *Sp, int nsdomains, int nrows)
+{
+    (void)nrows;
+    extract_subblocks(Ap, Aj, Ax, Tx, Tp, Sj, Sp, nsdomains);
+}
+// the same for the other value types of the flat table (complex values as interleaved pairs)
+void amgsetup_extract_subblocks_f32(const int *Ap, const int *Aj, const float *Ax, float *Tx, const int *Tp,
+                                    const int *Sj, const int *Sp, int nsdomains, int nrows)
+{
+    (void)nrows;
+    extract_subblocks(Ap, Aj, Ax, Tx, Tp, Sj, Sp, nsdomains);
+}
+void amgsetup_extract_subblocks_c64(const int *Ap, const int *Aj, const void *Ax, void *Tx, const int *Tp,
+                                    const int *Sj, const int *Sp, int nsdomains, int nrows)
+{
+    (void)nrows;
+    extract_subblocks(Ap, Aj, (const std::complex<float> *)Ax, (std::complex<float> *)Tx, Tp, Sj, Sp, nsdomains);
+}
+void amgsetup_extract_subblocks_c128(const int *Ap, const int *Aj, const void *Ax, void *Tx, const int *Tp,
+                                     const int *Sj, const int *Sp, int nsdomains, int nrows)
+{
+    (void)nrows;
+    extract_subblocks(Ap, Aj, (const std::complex<double> *)Ax, (std::complex<double> *)Tx, Tp, Sj, Sp, nsdomains);
 }
 
 }  // extern "C"

@@ -74,18 +74,19 @@ def _ptr(A):
 
 
 def _spmv(A, x):
-    """``A * x`` (scipy csr/bsr matvec arithmetic) on the device."""
-    y = np.zeros(A.shape[0], dtype=np.float64)
+    """``A * x`` (scipy csr/bsr matvec arithmetic) on the device, in scipy's upcast dtype of A and x."""
+    dtype = np.result_type(A.dtype, x.dtype)
+    y = np.zeros(A.shape[0], dtype=dtype)
     Ap, Aj = _ptr(A)
-    x = np.ascontiguousarray(np.ravel(x), dtype=np.float64)
+    x = np.ascontiguousarray(np.ravel(x), dtype=dtype)
     if sparse.isspmatrix_bsr(A):
         R, C = A.blocksize
         amg_core.bsr_matvec(A.shape[0] // R, A.shape[1] // C, R, C, Ap, Aj,
-                            np.ascontiguousarray(np.ravel(A.data)), x, y)
+                            np.ascontiguousarray(np.ravel(A.data), dtype=dtype), x, y)
     else:
         A = sparse.csr_matrix(A)
         Ap, Aj = _ptr(A)
-        amg_core.csr_matvec(A.shape[0], A.shape[1], Ap, Aj, np.ascontiguousarray(A.data), x, y)
+        amg_core.csr_matvec(A.shape[0], A.shape[1], Ap, Aj, np.ascontiguousarray(A.data, dtype=dtype), x, y)
     return y
 
 
@@ -259,7 +260,7 @@ def gauss_seidel_ne(A, x, b, iterations=1, sweep="forward", omega=1.0, Dinv=None
     Ap, Aj = _ptr(A)
     b = _bvec(b)
     Ax = np.ascontiguousarray(A.data)
-    Dinv = np.ascontiguousarray(Dinv, dtype=np.float64)
+    Dinv = np.ascontiguousarray(Dinv, dtype=A.dtype)
     for _ in range(iterations):
         for start, stop, step in ranges:
             amg_core.gauss_seidel_ne(Ap, Aj, Ax, x, b, start, stop, step, Dinv, omega)
@@ -281,7 +282,7 @@ def gauss_seidel_nr(A, x, b, iterations=1, sweep="forward", omega=1.0, Dinv=None
     Acsr.sort_indices()
     Ap, Aj = _ptr(A)
     Ax = np.ascontiguousarray(A.data)
-    Dinv = np.ascontiguousarray(Dinv, dtype=np.float64)
+    Dinv = np.ascontiguousarray(Dinv, dtype=A.dtype)
 
     def residual():
         return np.ascontiguousarray(b - _spmv(Acsr, x))
@@ -320,7 +321,7 @@ def schwarz_parameters(A, subdomain=None, subdomain_ptr=None, inv_subblock=None,
     """relaxation.py:1011-1083: subdomains (default: A's sparsity pattern) and the pseudo-inverses of
     their diagonal blocks, cached on A as ``A.schwarz_parameters``.  The reference inverts block by
     block with LAPACK gelss (cond = eps*1e6); here the blocks of equal size are inverted together
-    with numpy's batched SVD pseudo-inverse and the same cut-off."""
+    with numpy's batched SVD pseudo-inverse and the same cut-off, in A's dtype."""
     if hasattr(A, "schwarz_parameters"):
         if subdomain is not None and subdomain_ptr is not None:
             if np.array(A.schwarz_parameters[0] == subdomain).all() and \
@@ -341,11 +342,13 @@ def schwarz_parameters(A, subdomain=None, subdomain_ptr=None, inv_subblock=None,
         if ptr64[-1] > np.iinfo(np.intc).max:
             raise ValueError("subdomain blocks need more than 2^31-1 entries")
         inv_subblock_ptr = ptr64.astype(np.intc)
-        inv_subblock = np.zeros((int(ptr64[-1]),), dtype=np.float64)
+        inv_subblock = np.zeros((int(ptr64[-1]),), dtype=A.dtype)
         Ap, Aj = _ptr(A)
-        amg_core.extract_subblocks(Ap, Aj, np.ascontiguousarray(A.data, dtype=np.float64), inv_subblock,
+        amg_core.extract_subblocks(Ap, Aj, np.ascontiguousarray(A.data), inv_subblock,
                                    inv_subblock_ptr, subdomain, subdomain_ptr, nsd, A.shape[0])
-        cond = np.finfo(np.float64).eps * 1e6
+        # the reference's cut-off per precision: single eps * 1e3, double eps * 1e6
+        single = A.dtype in (np.float32, np.complex64)
+        cond = np.finfo(np.float32).eps * 1e3 if single else np.finfo(np.float64).eps * 1e6
         for m in np.unique(blocksize):
             m = int(m)
             if m == 0:
@@ -355,7 +358,7 @@ def schwarz_parameters(A, subdomain=None, subdomain_ptr=None, inv_subblock=None,
             blocks = inv_subblock[idx].reshape(len(which), m, m)
             inv_subblock[idx] = np.linalg.pinv(blocks, rcond=cond).reshape(len(which), m * m)
     else:
-        inv_subblock = np.ascontiguousarray(inv_subblock, dtype=np.float64)
+        inv_subblock = np.ascontiguousarray(inv_subblock, dtype=A.dtype)
         inv_subblock_ptr = np.ascontiguousarray(inv_subblock_ptr, dtype=np.intc)
     A.schwarz_parameters = (subdomain, subdomain_ptr, inv_subblock, inv_subblock_ptr)
     return A.schwarz_parameters

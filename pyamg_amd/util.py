@@ -87,7 +87,7 @@ def get_block_diag(A, blocksize, inv_flag=True):
         A = bsr_matrix(A, blocksize=(blocksize, blocksize))
     if A.blocksize != (blocksize, blocksize):
         A = A.tobsr(blocksize=(blocksize, blocksize))
-    if A.dtype != np.float64:
+    if A.dtype not in (np.float32, np.float64, np.complex64, np.complex128):
         A = A.astype(np.float64)
     nb = A.shape[0] // blocksize
     # the diagonal block of every block row (the last stored one if a row holds duplicates, as the
