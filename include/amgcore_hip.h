@@ -519,6 +519,64 @@ int amg_galerkin_fetch(amg_galerkin *g, int *Cj, double *Cx);
 int amg_csr_matmat_device(int n_row, int n_inner, int n_col, const int64_t *Ap, const int *Aj, const double *Ax,
                           const int64_t *Bp, const int *Bj, const double *Bx, int64_t *Cp, amg_galerkin **out);
 
+/* ------------------------------------------------------------------------ */
+/* 5. Resident hierarchies of other value types: the cycle of section 2      */
+/*    (multilevel.py:316-556) for a hierarchy whose A_l, P_l, R_l hold       */
+/*    complex128 values.  Eager launches on plain CSR / BSR forms.           */
+/* ------------------------------------------------------------------------ */
+/* Value types of a hierarchy.  Only AMG_VALUE_C128 is implemented; the others return AMG_ENOTIMPL.
+ * complex128 values are pairs of doubles (real, imaginary), like amg_c128 and numpy's complex128. */
+#define AMG_VALUE_F64  0
+#define AMG_VALUE_F32  1
+#define AMG_VALUE_C64  2
+#define AMG_VALUE_C128 3
+
+typedef struct amg_hierx amg_hierx;
+
+/* kind: the amg_smoother_desc kinds 0 (none), 1 (jacobi), 2 (gauss_seidel), 3 (sor), 4 (polynomial),
+ * 5 (block_jacobi), 6 (block_gauss_seidel); any other kind returns AMG_ENOTIMPL.  omega and Dinv hold values
+ * of the hierarchy's type (jacobi's omega as type_prep makes it; sor's omega must be real), the polynomial
+ * coefficients are doubles. */
+typedef struct {
+    int kind;
+    int iterations;
+    int sweep;                 /* AMG_SWEEP_* */
+    const void *omega;         /* one value */
+    int ncoef;
+    const double *coef;
+    int blocksize;
+    const void *Dinv;          /* n/blocksize blocks of blocksize^2 values, row-major */
+} amg_smoother_desc_x;
+
+/* A coarse solver supplied by the caller, with HOST vectors of the hierarchy's type; x is zero on entry. */
+typedef int (*amg_coarse_callback_x)(void *user, int n, const void *b_host, void *x_host);
+
+/* *out receives the handle; AMG_ENOTIMPL (and *out = NULL) for value types other than AMG_VALUE_C128 */
+int amg_hierx_create(int value_type, int nlevels, int device, amg_hierx **out);
+void amg_hierx_destroy(amg_hierx *h);
+/* as amg_hier_set_matrix (HOST arrays, copied); A must be square (BSR: square blocks) */
+int amg_hierx_set_matrix(amg_hierx *h, int lvl, int which, int fmt, int nrows, int ncols, int R, int C,
+                         const int *Ap, const int *Aj, const void *Ax);
+/* which = AMG_PRE / AMG_POST, or 2 for the coarse solver of the last level */
+int amg_hierx_set_smoother(amg_hierx *h, int lvl, int which, const amg_smoother_desc_x *d);
+/* as amg_hier_set_block_matrix: A re-blocked for a block smoother, passed after amg_hierx_set_smoother */
+int amg_hierx_set_block_matrix(amg_hierx *h, int lvl, int which, int nbrows, int bs, const int *Ap,
+                               const int *Aj, const void *Ax);
+/* coarse solve = the dense n x n operator M (row-major), applied with sequential row sums */
+int amg_hierx_set_coarse_dense(amg_hierx *h, const void *M, int n);
+int amg_hierx_set_coarse_callback(amg_hierx *h, amg_coarse_callback_x fn, void *user);
+/* builds the schedules and work vectors and seals the handle: setters called after it return AMG_ESTATE, and
+ * calling it again returns 0 without doing anything.  One coarse solver per handle. */
+int amg_hierx_finalize(amg_hierx *h);
+/* amg_hier_solve for HOST vectors of the hierarchy's type; flags AMG_SOLVE_X0_ZERO, AMG_SOLVE_NO_EARLY_STOP;
+ * residuals (maxiter + 1 doubles) receive the residual norms, *nres their count */
+int amg_hierx_solve(amg_hierx *h, const void *b, void *x, double tol, int maxiter, int cycle, double *residuals,
+                    int *nres, int flags);
+/* one cycle of x for the right-hand side b (HOST vectors); AMG_SOLVE_X0_ZERO: start from zero */
+int amg_hierx_cycle(amg_hierx *h, const void *b, void *x, int cycle, int flags);
+long amg_hierx_device_bytes(amg_hierx *h);
+double amg_hierx_last_solve_ms(amg_hierx *h);
+
 #ifdef __cplusplus
 }
 #endif

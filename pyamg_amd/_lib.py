@@ -38,6 +38,16 @@ class SmootherDesc(C.Structure):
                 ("Sj", c_int_p), ("Sp", c_int_p), ("Tp", c_int_p), ("Tx", c_dbl_p), ("nsdomains", C.c_int)]
 
 
+# include/amgcore_hip.h section 5: resident hierarchies of other value types (complex128)
+AMG_VALUE_F64, AMG_VALUE_F32, AMG_VALUE_C64, AMG_VALUE_C128 = 0, 1, 2, 3
+COARSE_CALLBACK_X = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p)
+
+
+class SmootherDescX(C.Structure):
+    _fields_ = [("kind", C.c_int), ("iterations", C.c_int), ("sweep", C.c_int), ("omega", C.c_void_p),
+                ("ncoef", C.c_int), ("coef", c_dbl_p), ("blocksize", C.c_int), ("Dinv", C.c_void_p)]
+
+
 # The flat amg_core table (include/amgcore_hip.h section 1): each entry's arguments in the SWIG call order.
 # "I" int32 array, "V" value array, "i" int, "F" real scalar (the real type of the values); a `sized` entry
 # passes every array followed by its length, as the C++ prototypes of amg_core do.
@@ -160,6 +170,15 @@ def lib():
         "amg_hier_galerkin": [V, I, I, V, V, V, V, V, V, V, C.POINTER(C.c_void_p)],
         "amg_galerkin_fetch": [V, V, V],
         "amg_csr_matmat_device": [I, I, I, V, V, V, V, V, V, V, C.POINTER(C.c_void_p)],
+        "amg_hierx_create": [I, I, I, C.POINTER(C.c_void_p)],
+        "amg_hierx_set_matrix": [V, I, I, I, I, I, I, I, V, V, V],
+        "amg_hierx_set_smoother": [V, I, I, C.POINTER(SmootherDescX)],
+        "amg_hierx_set_block_matrix": [V, I, I, I, I, V, V, V],
+        "amg_hierx_set_coarse_dense": [V, V, I],
+        "amg_hierx_set_coarse_callback": [V, COARSE_CALLBACK_X, V],
+        "amg_hierx_finalize": [V],
+        "amg_hierx_solve": [V, V, V, D, I, I, c_dbl_p, c_int_p, I],
+        "amg_hierx_cycle": [V, V, V, I, I],
     }
     for name, (kinds, sized) in FLAT_TABLE.items():
         for suffix in VALUE_SUFFIX.values():
@@ -176,6 +195,12 @@ def lib():
     L.amg_hier_create.restype = V
     L.amg_hier_destroy.argtypes = [V]
     L.amg_hier_destroy.restype = None
+    L.amg_hierx_destroy.argtypes = [V]
+    L.amg_hierx_destroy.restype = None
+    L.amg_hierx_device_bytes.argtypes = [V]
+    L.amg_hierx_device_bytes.restype = C.c_long
+    L.amg_hierx_last_solve_ms.argtypes = [V]
+    L.amg_hierx_last_solve_ms.restype = D
     L.amg_hier_cycle_bytes.argtypes = [V, I]
     L.amg_hier_cycle_bytes.restype = D
     L.amg_hier_value_index.argtypes = [V, I, I]

@@ -54,7 +54,7 @@ int require_device()
 }
 
 // the rows visited by for(i = start; i != stop; i += step)
-int sweep_rows(int start, int stop, int step, int limit, std::vector<int> &rows)
+[[maybe_unused]] int sweep_rows(int start, int stop, int step, int limit, std::vector<int> &rows)
 {
     rows.clear();
     if (step == 0) { set_error("row_step == 0"); return AMG_EINVAL; }
@@ -74,7 +74,7 @@ int sweep_rows(int start, int stop, int step, int limit, std::vector<int> &rows)
     return 0;
 }
 
-int check_csr(const int *Ap, int Ap_size, int Aj_size, int Ax_size, int per_entry)
+[[maybe_unused]] int check_csr(const int *Ap, int Ap_size, int Aj_size, int Ax_size, int per_entry)
 {
     if (!Ap || Ap_size < 1) { set_error("bad Ap"); return AMG_EINVAL; }
     long nnz = Ap[Ap_size - 1];

@@ -271,6 +271,7 @@ class DistributedSolver(object):
 
     def __init__(self, levels, coarse_dense, backend, rank, world, group=None, host_group=None,
                  replicate_below=500000, owners=None):
+        _refuse_complex([L.get(k) for L in levels for k in ("A", "P", "R")])
         import torch
         import torch.distributed as dist
         self.torch, self.dist = torch, dist
@@ -930,8 +931,19 @@ class DistributedSolver(object):
         return [float(v) for v in np.sqrt(self.be.to_host(hist, steps))]
 
 
+def _refuse_complex(mats):
+    """the partitioned path is float64: a complex operator would lose its imaginary parts in local_rows"""
+    for M in mats:
+        if M is None:
+            continue
+        dt = M.dtype if hasattr(M, "dtype") else M.data.dtype          # scipy matrices, _Lazy arrays
+        if np.dtype(dt).kind == "c":
+            raise NotImplementedError("the partitioned path supports float64 hierarchies only")
+
+
 def levels_from_ml(ml):
     """global level dicts (+ dense coarse operator) from a pyamg_amd.multilevel_solver"""
+    _refuse_complex([getattr(lvl, k, None) for lvl in ml.levels for k in ("A", "P", "R")])
     levels = []
     for lvl in ml.levels:
         L = {"A": lvl.A}

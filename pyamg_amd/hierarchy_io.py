@@ -40,12 +40,20 @@ def _put_matrix(path, tag, M):
     return info
 
 
+def _refuse_complex(mats):
+    """the format stores float64 hierarchies: a complex operator would lose its imaginary parts on the way"""
+    for M in mats:
+        if M is not None and np.dtype(M.dtype).kind == "c":
+            raise NotImplementedError("save / load: complex hierarchies are not supported (float64 only)")
+
+
 def _get_matrix(path, tag, info, mmap):
     mode = "r" if mmap else None
     indptr = np.load(os.path.join(path, tag + "_indptr.npy"), mmap_mode=mode)
     indices = np.load(os.path.join(path, tag + "_indices.npy"), mmap_mode=mode)
     data = np.load(os.path.join(path, tag + "_data.npy"), mmap_mode=mode)
     shape = tuple(info["shape"])
+    _refuse_complex([data])
     if info["format"] == "bsr":
         M = sparse.bsr_matrix((data, indices, indptr), shape=shape, blocksize=tuple(info["blocksize"]), copy=False)
     else:
@@ -86,6 +94,7 @@ def _get_descriptor(path, tag, info):
 
 def save_hierarchy(ml, path):
     """Write `ml` (a pyamg_amd.multilevel_solver) to the directory `path`."""
+    _refuse_complex((getattr(lvl, k, None) for lvl in ml.levels for k in ("A", "P", "R")))
     os.makedirs(path, exist_ok=True)
     meta = {"format": FORMAT, "nlevels": len(ml.levels), "levels": []}
     for l, lvl in enumerate(ml.levels):

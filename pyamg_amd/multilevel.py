@@ -305,6 +305,197 @@ class _DeviceHierarchy(object):
             pass
 
 
+_C128_KIND = {None: 0, "None": 0, "jacobi": 1, "gauss_seidel": 2, "sor": 3, "polynomial": 4, "block_jacobi": 5,
+              "block_gauss_seidel": 6}
+
+
+_SCIPY_ONLY_COARSE = ("cgs", "qmr", "minres", "bicg")     # coarse Krylov names run by scipy on complex128 vectors
+
+
+def _c128(a):
+    return np.ascontiguousarray(np.ravel(a), dtype=np.complex128)
+
+
+class _DeviceHierarchyC128(object):
+    """A complex128 hierarchy in HBM: an amg_hierx handle (include/amgcore_hip.h section 5).  Plain CSR / BSR
+    operators, eager launches; the cycle gives the reference's bits."""
+
+    def __init__(self, ml, device=0):
+        L = _lib.lib()
+        self.L = L
+        self.n = ml.levels[0].A.shape[0]
+        self._callbacks = []
+        self._callback_error = None
+        self._keep = []
+        h = _lib.C.c_void_p()
+        _lib.check(L.amg_hierx_create(_lib.AMG_VALUE_C128, len(ml.levels), int(device), _lib.C.byref(h)))
+        self.h = h.value
+        try:
+            self._build(ml)
+        except Exception:
+            self.close()
+            raise
+        self._keep = []
+
+    @staticmethod
+    def check_levels(ml):
+        """the refusals that need no device: every A complex128 and square, smoothers the engine implements"""
+        for i, lvl in enumerate(ml.levels):
+            if lvl.A.dtype != np.complex128:
+                raise NotImplementedError("complex hierarchy: level %d operator A is %s, not complex128" % (i, lvl.A.dtype))
+            if i < len(ml.levels) - 1:
+                for side in ("presmoother", "postsmoother"):
+                    _DeviceHierarchyC128._desc_of(i, getattr(lvl, side, None))
+        s = ml.coarse_solver.solver
+        from . import krylov
+        if (isinstance(s, str) and s in krylov.METHODS) or any(s is f for f in krylov.METHODS.values()):
+            # pyamg_amd.krylov runs float64 on the device: it would drop the imaginary parts of the coarse problem
+            raise NotImplementedError(
+                "coarse solver %r: the device Krylov methods are float64 only; for a complex128 hierarchy use a dense "
+                "or relaxation coarse solver, a name only scipy has ('cgs', 'qmr', 'minres', 'bicg'), or a callable"
+                % (getattr(s, "__name__", s),))
+        if isinstance(s, str) and s not in _CoarseSolver._DENSE + _CoarseSolver._RELAX + _SCIPY_ONLY_COARSE:
+            raise NotImplementedError("coarse solver %r has no complex128 device implementation" % (s,))
+        kind, payload = ml.coarse_solver.device_form(ml.levels[-1].A)
+        if kind == "smoother":
+            _DeviceHierarchyC128._desc_of(len(ml.levels) - 1, payload)
+        return kind, payload
+
+    @staticmethod
+    def _desc_of(lvl, fn):
+        desc = getattr(fn, "desc", None)
+        if fn is not None and desc is None:
+            raise NotImplementedError(
+                "level %d: smoother %r carries no device descriptor; use pyamg_amd.smoothing."
+                "change_smoothers with one of the device smoothers" % (lvl, fn))
+        name = None if desc is None else desc.get("name")
+        if name not in _C128_KIND:
+            raise NotImplementedError("smoother %r has no complex128 device implementation" % (name,))
+        return desc
+
+    def _set_matrix(self, lvl, which, M):
+        if sparse.isspmatrix_bsr(M):
+            fmt, (R, C) = 1, M.blocksize
+        else:
+            M = sparse.csr_matrix(M)
+            fmt, R, C = 0, 1, 1
+        data = _c128(M.data)       # a real P / R: astype(complex128), as scipy converts it inside a mixed product
+        Ap = np.ascontiguousarray(M.indptr, dtype=np.intc)
+        Aj = np.ascontiguousarray(M.indices, dtype=np.intc)
+        _lib.check(self.L.amg_hierx_set_matrix(self.h, lvl, which, fmt, M.shape[0], M.shape[1], R, C,
+                                               Ap.ctypes.data, Aj.ctypes.data, data.ctypes.data))
+
+    def _set_smoother(self, lvl, which, fn, A):
+        desc = self._desc_of(lvl, fn)
+        d = _lib.SmootherDescX()
+        name = None if desc is None else desc.get("name")
+        d.kind = _C128_KIND[name]
+        if d.kind:
+            d.iterations = int(desc.get("iterations", 1))
+            sweep = desc.get("sweep", "forward")
+            if sweep not in _SWEEP:
+                raise ValueError("valid sweep directions are 'forward', 'backward', and 'symmetric'")
+            d.sweep = _SWEEP[sweep]
+            omega = _c128([desc.get("omega", 1.0)])     # type_prep(A.dtype, [omega])
+            co = desc.get("coefficients")
+            co = np.ascontiguousarray([0.0] if co is None else co, dtype=np.float64)
+            d.omega, d.ncoef, d.coef = omega.ctypes.data, len(co), _lib.dp(co)
+            d.blocksize = int(desc.get("blocksize", 1) or 1)
+            self._keep.extend([omega, co])
+            if desc.get("Dinv") is not None:
+                Dinv = _c128(desc["Dinv"])
+                self._keep.append(Dinv)
+                d.Dinv = Dinv.ctypes.data
+        _lib.check(self.L.amg_hierx_set_smoother(self.h, lvl, which, d))
+        if d.kind in (5, 6):
+            # relaxation.py:471,563: A.tobsr(blocksize=(bs, bs))
+            bs = d.blocksize
+            if not (sparse.isspmatrix_bsr(A) and A.blocksize == (bs, bs)):
+                Ab = A.tobsr(blocksize=(bs, bs))
+                Ap = np.ascontiguousarray(Ab.indptr, dtype=np.intc)
+                Aj = np.ascontiguousarray(Ab.indices, dtype=np.intc)
+                Ax = _c128(Ab.data)
+                _lib.check(self.L.amg_hierx_set_block_matrix(self.h, lvl, which, Ab.shape[0] // bs, bs,
+                                                             Ap.ctypes.data, Aj.ctypes.data, Ax.ctypes.data))
+
+    def _set_coarse_callback(self, fn, Ac):
+        owner = self
+
+        def solve(user, n, b_ptr, x_ptr):
+            try:
+                b = np.frombuffer((_lib.C.c_double * (2 * n)).from_address(b_ptr), dtype=np.complex128).copy()
+                x = np.asarray(fn(Ac, b), dtype=np.complex128).ravel()
+                np.frombuffer((_lib.C.c_double * (2 * n)).from_address(x_ptr), dtype=np.complex128)[:] = x
+                return 0
+            except Exception as e:          # noqa: BLE001 -- must not propagate through the C frames
+                owner._callback_error = e
+                return 1
+        cb = _lib.COARSE_CALLBACK_X(solve)
+        self._callbacks.append(cb)
+        _lib.check(self.L.amg_hierx_set_coarse_callback(self.h, cb, None))
+
+    def _build(self, ml):
+        levels = ml.levels
+        kind, payload = self.check_levels(ml)
+        for i, lvl in enumerate(levels):
+            self._set_matrix(i, 0, lvl.A)
+            if i < len(levels) - 1:
+                self._set_matrix(i, 1, lvl.P)
+                self._set_matrix(i, 2, lvl.R)
+                self._set_smoother(i, 0, getattr(lvl, "presmoother", None), lvl.A)
+                self._set_smoother(i, 1, getattr(lvl, "postsmoother", None), lvl.A)
+        Ac = levels[-1].A
+        if kind == "dense":
+            M = np.ascontiguousarray(payload, dtype=np.complex128)
+            _lib.check(self.L.amg_hierx_set_coarse_dense(self.h, M.ctypes.data, M.shape[0]))
+        elif kind == "smoother":
+            self._set_smoother(len(levels) - 1, 2, payload, Ac)
+        elif kind == "callback":
+            self._set_coarse_callback(payload, Ac)
+        elif kind != "none":
+            raise NotImplementedError("coarse solver %s has no device implementation" % ml.coarse_solver.name())
+        _lib.check(self.L.amg_hierx_finalize(self.h))
+
+    def _check(self, rc):
+        err, self._callback_error = self._callback_error, None
+        if err is not None:
+            raise err
+        _lib.check(rc)
+
+    def solve(self, b, x, tol, maxiter, cycle, x0_zero=False, fixed=False):
+        res = np.zeros(maxiter + 2, dtype=np.float64)
+        nres = _lib.C.c_int(0)
+        flags = (_X0_ZERO if x0_zero else 0) | (_NO_EARLY_STOP if fixed else 0)
+        self._check(self.L.amg_hierx_solve(self.h, b.ctypes.data, x.ctypes.data, float(tol), int(maxiter),
+                                           _CYCLE[cycle], _lib.dp(res), _lib.C.byref(nres), flags))
+        return res[:nres.value]
+
+    def cycle(self, b, x, cycle, x0_zero=False):
+        self._check(self.L.amg_hierx_cycle(self.h, b.ctypes.data, x.ctypes.data, _CYCLE[cycle],
+                                           _X0_ZERO if x0_zero else 0))
+
+    def last_solve_ms(self):
+        return self.L.amg_hierx_last_solve_ms(self.h)
+
+    def device_bytes(self):
+        return self.L.amg_hierx_device_bytes(self.h)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.amg_hierx_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _is_c128(ml):
+    return ml.levels[0].A.dtype == np.complex128
+
+
 class multilevel_solver:
     """Stores multigrid hierarchy and implements the multigrid cycle
     (multilevel.py:14-548).  Same attributes and methods as the reference."""
@@ -412,7 +603,10 @@ class multilevel_solver:
     def device_hierarchy(self):
         """The HBM-resident mirror of this hierarchy (built on first use)."""
         if self._dev is None:
-            self._dev = _DeviceHierarchy(self, self.device)
+            if _is_c128(self):
+                self._dev = _DeviceHierarchyC128(self, self.device)
+            else:
+                self._dev = _DeviceHierarchy(self, self.device)
         return self._dev
 
     # ------------------------------------------------------------------ solve
@@ -438,6 +632,8 @@ class multilevel_solver:
         cycling and accel='cg' (the device PCG); same iterates and history as with host vectors."""
         if _is_device_tensor(b):
             return self._solve_device_tensors(b, x0, tol, maxiter, cycle, accel, callback, residuals)
+        if _is_c128(self):
+            return self._solve_c128(b, x0, tol, maxiter, cycle, accel, callback, residuals, return_residuals)
         b = np.asarray(b)
         if x0 is None:
             x = np.zeros_like(b)
@@ -495,8 +691,67 @@ class multilevel_solver:
             return xout, residuals
         return xout
 
+    def _solve_c128(self, b, x0, tol, maxiter, cycle, accel, callback, residuals, return_residuals):
+        """solve() of a complex128 hierarchy (multilevel.py:316-471): V, W and F cycles on the device, scipy's Krylov
+        methods around it; the complex cycle gives the reference's bits"""
+        b = np.asarray(b)
+        x = np.zeros_like(b) if x0 is None else np.array(x0)
+        cycle = str(cycle).upper()
+        if cycle not in _CYCLE:
+            raise TypeError("Unrecognized cycle type (%s)" % cycle)
+        if cycle == "AMLI":
+            raise NotImplementedError("AMLI cycles are not implemented for complex128 hierarchies")
+        if accel is not None:
+            from . import krylov
+            name = accel if isinstance(accel, str) else getattr(accel, "__name__", None)
+            if name in krylov.METHODS and (isinstance(accel, str) or accel is krylov.METHODS[name]):
+                raise NotImplementedError(
+                    "the device Krylov methods are float64 only; for a complex128 hierarchy pass a scipy.sparse.linalg "
+                    "callable as accel, or use aspreconditioner() as M")
+            _DeviceHierarchyC128.check_levels(self)
+            return self._solve_accel(b, x0, tol, maxiter, cycle, accel, callback, residuals)
+        if return_residuals:
+            warn("return_residuals is deprecated.  Use residuals instead")
+            residuals = []
+        if residuals is None:
+            residuals = []
+        else:
+            residuals[:] = []
+        n = self.levels[0].A.shape[0]
+        if b.size != n or x.size != n:
+            raise ValueError("b and x0 must have %d entries" % n)
+        tp = np.result_type(b.dtype, x.dtype, self.levels[0].A.dtype)     # upcast(b, x, A)
+        if tp != np.complex128:
+            raise NotImplementedError("complex128 hierarchy: b and x0 of type %s" % tp)
+        shape = b.shape
+        b1, x1 = _c128(b), _c128(x)
+        x0_zero = not np.any(x1)
+        if self._dev is None:
+            _DeviceHierarchyC128.check_levels(self)          # refusals before any device work
+        dev = self.device_hierarchy()
+        if callback is None:
+            res = dev.solve(b1, x1, tol, maxiter, cycle, x0_zero=x0_zero)
+            residuals.extend(float(r) for r in res)
+        else:
+            # one cycle per call so that callback(x) sees every iterate (multilevel.py:454-466)
+            normb = float(np.sqrt(np.vdot(b1, b1).real))
+            atol = tol * normb if normb != 0 else tol
+            res = dev.solve(b1, x1, 0.0, 0, cycle, x0_zero=x0_zero)
+            residuals.append(float(res[0]))
+            while len(residuals) <= maxiter and residuals[-1] > atol:
+                res = dev.solve(b1, x1, 0.0, 1, cycle, x0_zero=x0_zero, fixed=True)
+                x0_zero = False
+                residuals.append(float(res[-1]))
+                callback(x1.reshape(shape))
+        xout = x1.reshape(shape)
+        if return_residuals:
+            return xout, residuals
+        return xout
+
     def _solve_device_tensors(self, b, x0, tol, maxiter, cycle, accel, callback, residuals):
         import torch
+        if _is_c128(self):
+            raise NotImplementedError("device tensors: float64 hierarchies only; pass host arrays to a complex128 one")
         cycle = str(cycle).upper()
         if cycle not in _CYCLE:
             raise TypeError("Unrecognized cycle type (%s)" % cycle)
@@ -639,7 +894,7 @@ class _CoarseSolver(object):
         if s in self._DENSE:
             if not hasattr(self, "P"):
                 if s == "dense":
-                    self.P = np.asarray(self.kwargs["M"], dtype=np.float64)
+                    self.P = np.asarray(self.kwargs["M"], dtype=np.complex128 if A.dtype == np.complex128 else np.float64)
                 elif A.nnz == 0:
                     self.P = np.zeros(A.shape)
                 elif s in ("pinv", "pinv2"):
@@ -685,8 +940,9 @@ class _CoarseSolver(object):
         if kind == "callback":
             return np.asarray(payload(lvl.A, np.ravel(b))).reshape(b.shape)
         ml = multilevel_solver([lvl], coarse_solver=self)
-        x = np.zeros(A.shape[0])
-        ml.device_hierarchy().cycle(np.ascontiguousarray(np.ravel(b), dtype=np.float64), x, "V", x0_zero=True)
+        dt = np.complex128 if lvl.A.dtype == np.complex128 else np.float64
+        x = np.zeros(A.shape[0], dtype=dt)
+        ml.device_hierarchy().cycle(np.ascontiguousarray(np.ravel(b), dtype=dt), x, "V", x0_zero=True)
         ml._invalidate_device()
         return x.reshape(b.shape)
 

@@ -340,7 +340,9 @@ def spec_from_descriptor(desc):
         return name, {"iterations": it, "coefficients": np.asarray(desc["coefficients"], dtype=float)}
     if name in ("block_jacobi", "block_gauss_seidel"):
         bs = int(desc["blocksize"])
-        kw = {"iterations": it, "blocksize": bs, "Dinv": np.asarray(desc["Dinv"], dtype=float).reshape(-1, bs, bs)}
+        Dinv = np.asarray(desc["Dinv"])
+        Dinv = Dinv.astype(np.result_type(Dinv.dtype, float), copy=False)       # complex block inverses stay complex
+        kw = {"iterations": it, "blocksize": bs, "Dinv": Dinv.reshape(-1, bs, bs)}
         if name == "block_jacobi":
             kw.update(omega=desc["omega"], withrho=False)
         else:

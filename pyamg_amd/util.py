@@ -328,6 +328,8 @@ def galerkin_device(A, R, P, n_coarse):
 def use_device_for(A):
     if A.shape[0] < DEVICE_RHO_MIN_ROWS:
         return False
+    if np.dtype(getattr(A, "dtype", np.float64)).kind == "c":
+        return False                    # the device Arnoldi is float64: complex operators are estimated on the host
     from . import _lib
     return _lib.device_count() > 0
 
