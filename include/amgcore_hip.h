@@ -312,6 +312,14 @@ int amg_hier_operator_form(amg_hier *h, int lvl);
 int amg_hier_value_index(amg_hier *h, int lvl, int on);
 void amg_set_value_index(int on);       /* process-wide default for operators set afterwards */
 int amg_value_index_enabled(void);
+/* Fused level-0 smoother chains: when level 0's A is the coded 7-point stencil of a box grid
+ * whose couplings stay inside the box, the hierarchy is not partitioned and both smoothers are Chebyshev of degree 2
+ * (two coefficients, one iteration), the pre-smoother and the restriction's residual run as one tiled sweep, and the
+ * post-smoother and the next residual norm's residual as another.  Same bits as the separate passes.
+ * amg_set_level0_fusion(0) selects the separate passes (process-wide; tests); amg_hier_level0_fused says whether a
+ * finalised hierarchy takes the fused path now (1) or not (0). */
+void amg_set_level0_fusion(int on);
+int amg_hier_level0_fused(amg_hier *h);
 /* Setup-side (replaces the host sweeps behind pyamg/aggregation/aggregation.py:313-320 `relaxation_as_linear_operator(
  * ('gauss_seidel', ...), A, 0) * B`, i.e. amg_core gauss_seidel of relaxation.h:34-62 on A x = 0): nsweeps Gauss-Seidel
  * sweeps over level lvl's operator in its own row order, from the CSR arrays in HBM; dirs[k] != 0 = descending rows;

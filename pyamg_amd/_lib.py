@@ -207,6 +207,10 @@ def lib():
     L.amg_hier_value_index.restype = I
     L.amg_set_value_index.argtypes = [I]
     L.amg_set_value_index.restype = None
+    L.amg_set_level0_fusion.argtypes = [I]
+    L.amg_set_level0_fusion.restype = None
+    L.amg_hier_level0_fused.argtypes = [V]
+    L.amg_hier_level0_fused.restype = I
     L.amg_value_index_enabled.argtypes = []
     L.amg_value_index_enabled.restype = I
     L.amg_hier_gs_natural.argtypes = [V, I, V, V, V, I]

@@ -97,6 +97,11 @@ struct DevCsr {
     double i16_frac = 0.0;             // fraction of the entries that are coded
     int st_u0 = -1;                // slot of offset 0 (the diagonal), -1 if absent
     int st_off[32] = {0};          // U, increasing
+    // Fused level-0 smoother chains (launch_level0_chain): decided once per operator (hier.hip level0_chain_check).
+    // 1 when the coded stencil is the 7-point one of an (nz, ny, nx) box, U = (-P, -L, -1, 0, 1, L, P) with L = nx,
+    // P = nx * ny, and no stored coupling leaves the box; 0 otherwise.
+    int l0_ok = 0;
+    int l0_nx = 0, l0_ny = 0, l0_nz = 0;
 };
 constexpr int STENCIL_MAX = 31;
 constexpr int STENCIL_RANGES = 8;
@@ -179,6 +184,27 @@ int launch_sell(StreamMode mode, const StreamArgs &a, const DevCsr &M, hipStream
 int build_sell(DevCsr &M, long *acct, int row_lo = 0, int row_hi = -1);   // from the CSR arrays already in HBM (rows [lo, hi), default all); leaves M untouched if not worth it
 void free_sell(DevCsr &M);
 int stencil_blocks(const StreamArgs &a, const DevCsr &M);   // workgroups (= SM_RESIDUAL_SUMSQ partials) of launch_stencil
+// Fused level-0 chains (DevCsr::l0_ok operators, polynomial smoothers with two coefficients):
+//   [r = b - A g0] -> x' = x + (c_last * r + A (c_gs * r)) -> [r' = b - A x'],
+// g0 = x with the leading residual, else the residual r itself (b when x == 0).  x' -> xout, r' -> rout.
+struct Level0ChainArgs {
+    const unsigned long long *codes;   // one code word per row (DevCsr::st_codes, st_nu <= 7)
+    const double *dict;
+    int ndict;
+    int nx, ny, nz;                    // row = (z * ny + y) * nx + x
+    const double *g0;                  // the first stage's gathered vector
+    const double *x;                   // the iterate (read only without the leading residual)
+    const double *b;
+    double *xout, *rout;               // never an input of the same launch
+    double c_gs, c_last;               // polynomial coefficients 0 and 1
+    int zc;                            // planes per workgroup
+    int tiles_x, tiles_y;              // (set by the launcher)
+};
+int launch_level0_chain(bool first_res, bool last_res, const Level0ChainArgs &a, hipStream_t st);
+int level0_chain_tile(int stages, int axis);   // interior tile extent (axis 0: x, 1: y) of a chain of that many stages
+int level0_chain_lanes(int axis);              // the tile's extent in lanes
+int launch_sumsq_partials(const double *r, int n, double *out2, hipStream_t st);   // the SM_RESIDUAL_SUMSQ partials of a stored r
+int launch_level0_box_scan(const unsigned char *codes, int nx, int ny, int nz, int *bad, hipStream_t st);
 int launch_stencil_build(const DevCsr &M, const int *dict_slot, const unsigned *pat_mask, hipStream_t st);
 // value index: distinct values of st_vals into a 1024-slot table (EMPTY = all ones), then the byte codes
 int launch_value_scan(const double *vals, long count, unsigned long long *table, int *overflow, hipStream_t st);

@@ -1321,6 +1321,91 @@ static int coarse_solve(amg_hier *h, const double *b, double *&x, double *&xalt)
     return relax(h, L, h->coarse_sm, x, xalt, b, true);
 }
 
+// ------------------------------------------------------------------ fused level-0 chains (launch_level0_chain)
+static int g_level0_fusion = 1;
+#ifndef L0_ZCHUNK_PLANES                        // (A/B builds: -DL0_ZCHUNK_PLANES=32 / 64)
+#define L0_ZCHUNK_PLANES 128
+#endif
+constexpr int L0_ZCHUNK = L0_ZCHUNK_PLANES;           // planes per workgroup of a chain
+
+// Decided once per operator, when its value index is built (amg_hier_set_matrix): the coded stencil is the 7-point one of
+// an (nz, ny, nx) box -- U = (-P, -L, -1, 0, 1, L, P), P % L == 0, n % P == 0 -- and one device scan of the codes finds
+// no stored coupling that leaves the box (a row at the end of a line storing its +1 slot, ...).
+static int level0_chain_check(amg_hier *h, DevCsr &M)
+{
+    M.l0_ok = 0;
+    if (!M.st_vals || !M.st_codes || M.st_nu != 7 || M.st_nranges != 0 || M.nrows != M.ncols || M.nrows < 1) return 0;
+    const int *o = M.st_off;
+    const long n = M.nrows, Lx = o[5], P = o[6];
+    if (!(o[0] == -P && o[1] == -Lx && o[2] == -1 && o[3] == 0 && o[4] == 1)) return 0;
+    if (!(Lx > 1 && P > Lx && P % Lx == 0 && n % P == 0)) return 0;
+    int *bad = nullptr;
+    if (dev_alloc(&bad, 1, nullptr) != 0) return AMG_ENOMEM;
+    int found = 1;
+    int rc = 0;
+    if (hipMemsetAsync(bad, 0, sizeof(int), h->stream) != hipSuccess) rc = AMG_ESTATE;
+    if (rc == 0) rc = launch_level0_box_scan(M.st_codes, (int)Lx, (int)(P / Lx), (int)(n / P), bad, h->stream);
+    if (rc == 0 && (hipMemcpyAsync(&found, bad, sizeof(int), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+                    hipStreamSynchronize(h->stream) != hipSuccess)) rc = AMG_ESTATE;
+    hipFree(bad);
+    if (rc != 0) return rc;
+    if (found) return 0;
+    M.l0_nx = (int)Lx; M.l0_ny = (int)(P / Lx); M.l0_nz = (int)(n / P);
+    M.l0_ok = 1;
+    return 0;
+}
+
+// level 0 runs its smoothers as fused chains: an eligible operator applied through its coded stencil form, one rank,
+// Chebyshev of degree 2 (two coefficients, one iteration) before and after
+static bool level0_fused(amg_hier *h)
+{
+    if (!g_level0_fusion || h->comm || h->nlevels < 2) return false;
+    const Level &L = h->lv[0];
+    const DevCsr &M = L.A;
+    if (!M.l0_ok || !M.st_vi_on || !M.st_codes || (M.blk && M.blk->Ap) || !(stencil_enabled() || !M.Ap)) return false;
+    for (int w = 0; w < 2; ++w) {
+        const Smoother &s = L.sm[w];
+        if (s.kind != AMG_SM_POLYNOMIAL || s.coef.size() != 2 || s.iterations != 1) return false;
+    }
+    return true;
+}
+
+// one chain: x' -> xalt (then swapped with x), r' -> rout
+static int level0_chain(amg_hier *h, const Smoother &s, bool first_res, bool last_res, const double *g0, double *&x,
+                        double *&xalt, const double *b, double *rout)
+{
+    const DevCsr &M = h->lv[0].A;
+    Level0ChainArgs a{};
+    a.codes = reinterpret_cast<const unsigned long long *>(M.st_codes);
+    a.dict = M.st_dict; a.ndict = M.st_ndict;
+    a.nx = M.l0_nx; a.ny = M.l0_ny; a.nz = M.l0_nz;
+    a.g0 = g0; a.x = x; a.b = b; a.xout = xalt; a.rout = rout;
+    a.c_gs = s.coef[0]; a.c_last = s.coef[1];
+    a.zc = std::min(L0_ZCHUNK, M.l0_nz);
+    CHK(launch_level0_chain(first_res, last_res, a, h->stream));
+    std::swap(x, xalt);
+    return 0;
+}
+
+// relax(AMG_PRE) + the residual for the restriction (cycle :494-496): r' -> L.h, which the restriction reads
+static int level0_pre_chain(amg_hier *h, double *&x, double *&xalt, const double *b, bool x_zero, bool r_ready)
+{
+    Level &L = h->lv[0];
+    if (x_zero) return level0_chain(h, L.sm[AMG_PRE], false, true, b, x, xalt, b, L.h);          // r = b
+    if (r_ready) return level0_chain(h, L.sm[AMG_PRE], false, true, L.r, x, xalt, b, L.h);       // kept b - A x
+    return level0_chain(h, L.sm[AMG_PRE], true, true, x, x, xalt, b, L.h);
+}
+
+// relax(AMG_POST) (cycle :545), plus the residual of the norm that follows (residual_norm_to), left in L.r
+static int level0_post_chain(amg_hier *h, double *&x, double *&xalt, const double *b)
+{
+    Level &L = h->lv[0];
+    const bool norm = h->norm_next;
+    CHK(level0_chain(h, L.sm[AMG_POST], true, norm, x, x, xalt, b, norm ? L.r : nullptr));
+    h->r_fresh = norm;
+    return 0;
+}
+
 // multilevel_solver.__solve (multilevel.py:473-548)
 static int cycle(amg_hier *h, int lvl, double *&x, double *&xalt, const double *b, int cyc, bool x_zero,
                  bool r_ready = false)
@@ -1329,17 +1414,24 @@ static int cycle(amg_hier *h, int lvl, double *&x, double *&xalt, const double *
     Level &Lc = h->lv[lvl + 1];
     hipStream_t st = h->stream;
     const int nc = Lc.A.nrows;
+    const bool fused = lvl == 0 && level0_fused(h);
 
-    CHK(relax(h, L, L.sm[AMG_PRE], x, xalt, b, x_zero, r_ready));                          // :494
-    CHK(level_apply(h, L, SM_RESIDUAL, x, 0.0, b, nullptr, L.r, 0.0));                     // :496
-    CHK(exchange(h, L, L.r));                                                              // R gathers fine residuals
+    double *rr = L.r;                                                                      // what R restricts
+    if (fused) {
+        CHK(level0_pre_chain(h, x, xalt, b, x_zero, r_ready));                             // :494-496
+        rr = L.h;
+    } else {
+        CHK(relax(h, L, L.sm[AMG_PRE], x, xalt, b, x_zero, r_ready));                      // :494
+        CHK(level_apply(h, L, SM_RESIDUAL, x, 0.0, b, nullptr, L.r, 0.0));                 // :496
+    }
+    CHK(exchange(h, L, rr));                                                               // R gathers fine residuals
     if (h->comm && L.part.gather_channel >= 0) {
         // entering the replicated levels: every rank restricts its slice of the coarse rows, all ranks gather
-        CHK(spmv(L.Rm, SM_MATVEC, L.r, nullptr, nullptr, L.part.rslice, nullptr, 0.0, st));
+        CHK(spmv(L.Rm, SM_MATVEC, rr, nullptr, nullptr, L.part.rslice, nullptr, 0.0, st));
         CHK(comm_exchange_begin(h->comm, L.part.gather_channel, L.part.rslice, L.part.gather_idx, Lc.b, st));
         CHK(comm_exchange_end(h->comm, L.part.gather_channel, Lc.b, st));
     } else {
-        CHK(spmv(L.Rm, SM_MATVEC, L.r, nullptr, nullptr, Lc.b, nullptr, 0.0, st));         // :498
+        CHK(spmv(L.Rm, SM_MATVEC, rr, nullptr, nullptr, Lc.b, nullptr, 0.0, st));          // :498
     }
     AMG_HIP(hipMemsetAsync(Lc.x, 0, sizeof(double) * (size_t)nc, st));                     // :499
 
@@ -1391,7 +1483,8 @@ static int cycle(amg_hier *h, int lvl, double *&x, double *&xalt, const double *
 
     CHK(exchange(h, Lc, Lc.x));                                                            // P gathers coarse corrections
     CHK(spmv(L.P, SM_MATVEC_ACC, Lc.x, nullptr, nullptr, x, nullptr, 0.0, st));            // :544
-    CHK(relax(h, L, L.sm[AMG_POST], x, xalt, b, false));                                   // :545
+    if (fused) CHK(level0_post_chain(h, x, xalt, b));                                      // :545 (+ the norm's residual)
+    else CHK(relax(h, L, L.sm[AMG_POST], x, xalt, b, false));                              // :545
     return 0;
 }
 
@@ -1423,6 +1516,15 @@ static int residual_norm_to(amg_hier *h, double *slot)
     }
     a.out = keep ? L0.r : nullptr;
     h->r_kept = keep;
+    if (h->r_fresh) {
+        // the fused post chain stored r = b - A x in L0.r: only the partial sums are left, from the same rows as the
+        // stencil launch's 256-row blocks, added by the same tree (launch_sumsq_partials)
+        h->r_fresh = false;
+        const int nb = stencil_blocks(a, L0.A);
+        if (nb > h->sumsq_cap) { set_error("sumsq partial buffer too small"); return AMG_ESTATE; }
+        CHK(launch_sumsq_partials(L0.r, L0.A.nrows, h->sumsq_partials, h->stream));
+        return launch_sum_sqrt(h->sumsq_partials, nb, h->sumsq_partials + h->sumsq_cap, slot, h->stream);
+    }
     const bool stencil = L0.A.st_vals && stencil_enabled();
     if (applies_from_blocks(L0.A, SM_RESIDUAL_SUMSQ, a)) {
         const BsrStreamArgs q = block_spmv_args(*L0.A.blk, SM_RESIDUAL_SUMSQ, a);
@@ -1454,7 +1556,11 @@ static int iteration_with_norm(amg_hier *h, int cyc, bool x_zero, double *slot)
 {
     const bool r_ready = h->r_kept;
     h->r_kept = false;
-    CHK(one_iteration(h, cyc, x_zero, r_ready));
+    h->r_fresh = false;
+    h->norm_next = true;
+    const int rc = one_iteration(h, cyc, x_zero, r_ready);
+    h->norm_next = false;
+    if (rc != 0) { h->r_fresh = false; return rc; }
     return residual_norm_to(h, slot);
 }
 
@@ -1667,6 +1773,7 @@ static int value_index_build(amg_hier *h, DevCsr &M)
     AMG_HIP(hipStreamSynchronize(h->stream));
     if (rc != 0) return AMG_ESTATE;
     M.st_vi_on = true;
+    CHK(level0_chain_check(h, M));                 // (the codes never change afterwards)
     return M.st_ndict;
 }
 
@@ -2540,6 +2647,23 @@ static double cycle_bytes_impl(amg_hier *h, int cyc, bool moved)
         // each pair of visits -- counted as zero-start for all coarse presmooths of a V cycle
         double k = smoother_apps(L.sm[0], l > 0) + 1.0 + smoother_apps(L.sm[1], false);
         double extra = 0.0;
+        if (l == 0 && moved && level0_fused(h)) {
+            // the two chains: per interior row, 8 B per loaded vector, code word and output; the first stage's operand is
+            // loaded on the whole tile, the row operands on the tile less its outer ring, both over the chunk's planes
+            // plus the halo planes; + the partial sums' pass over the stored residual
+            const double zc = std::min(L0_ZCHUNK, L.A.l0_nz);
+            const double tx = level0_chain_lanes(0), ty = level0_chain_lanes(1);
+            auto chain = [&](int S, int row_operands, int outputs) {
+                const double in = (double)level0_chain_tile(S, 0) * level0_chain_tile(S, 1);
+                const double zf = (zc + 2.0 * S) / zc;
+                return 8.0 * n * (tx * ty / in * zf + row_operands * (tx - 2.0) * (ty - 2.0) / in * zf + outputs);
+            };
+            const bool kept = h->keep_residual != 0;
+            const double pre = kept ? chain(2, 3, 2) : chain(3, 2, 2);     // r | x; codes, x, b | b; x', r'
+            const double post = chain(3, 2, 2) + 8.0 * n;                 // x; codes, b; x', r'; partials
+            total += visits[l] * (pre + post + bytes_spmv(L.Rm) + bytes_spmv(L.P) + 8.0 * n);
+            continue;
+        }
         if (l == 0) {
             k += 1.0;   // outer residual norm (multilevel.py:461)
             if (moved && h->keep_residual && L.sm[0].kind == AMG_SM_POLYNOMIAL && L.sm[0].iterations >= 1) {
@@ -2899,5 +3023,7 @@ void amg_set_index16(int on) { amg::set_index16(on); }
 void amg_set_tile_target(int t) { amg::set_tile_target(t); }
 void amg_hier_use_graphs(amg_hier *h, int on) { if (h) { h->use_graphs = on; if (!on) drop_graphs(h); } }
 void amg_hier_keep_residual(amg_hier *h, int on) { if (h) { h->keep_residual = on; h->r_kept = false; drop_graphs(h); } }
+void amg_set_level0_fusion(int on) { g_level0_fusion = on ? 1 : 0; amg::bump_config_epoch(); }
+int amg_hier_level0_fused(amg_hier *h) { return (h && h->finalized && level0_fused(h)) ? 1 : 0; }
 
 }  // extern "C"

@@ -205,6 +205,8 @@ struct amg_hier {
     int graph_epoch = 0;                         // amg::config_epoch() the cached graphs were captured under
     int keep_residual = 1;                       // hand the outer residual to the next pre-smoother
     bool r_kept = false;                         // lv[0].r == lv[0].b - A*lv[0].x right now (solve loop only)
+    bool norm_next = false;                      // a residual norm follows the cycle being issued (iteration_with_norm)
+    bool r_fresh = false;                        // the fused level-0 post chain left b - A*lv[0].x in lv[0].r
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double last_ms = 0.0;
     long dev_bytes = 0;

@@ -1565,6 +1565,15 @@ struct StencilArgs {
     int off[STENCIL_MAX];
 };
 
+// row results of the residual and the last polynomial step (shared by the stencil kernels and the fused level-0 chains)
+__device__ __forceinline__ double residual_row(double bval, double acc) { return bval - acc; }
+__device__ __forceinline__ double poly_last_row(double c0, double bval, double acc, double pre2)
+{
+    double cr = c0 * bval;
+    double h = cr + acc;
+    return pre2 + h;
+}
+
 // what a stencil application does with a row's sum (shared by the 8-byte-value and the coded-value kernels)
 template <int MODE>
 __device__ __forceinline__ void stencil_epilogue(const StreamArgs &a, const StencilArgs &E, int i, int blk, int t, bool covered,
@@ -1573,7 +1582,7 @@ __device__ __forceinline__ void stencil_epilogue(const StreamArgs &a, const Sten
     if (MODE == SM_RESIDUAL_SUMSQ) {
         double sq = 0.0;
         if (covered) {
-            double rr = bval - acc;
+            double rr = residual_row(bval, acc);
             sq = rr * rr;
             if (a.out) store_out(&a.out[i], rr);
         }
@@ -1587,14 +1596,12 @@ __device__ __forceinline__ void stencil_epilogue(const StreamArgs &a, const Sten
     } else if (MODE == SM_MATVEC_ACC) {
         store_out(&a.out[i], pre2 + acc);
     } else if (MODE == SM_RESIDUAL) {
-        store_out(&a.out[i], bval - acc);
+        store_out(&a.out[i], residual_row(bval, acc));
     } else if (MODE == SM_POLY_STEP) {
         double cr = a.c0 * bval;
         a.out[i] = cr + acc;
     } else if (MODE == SM_POLY_LAST) {
-        double cr = a.c0 * bval;
-        double h = cr + acc;
-        store_out(&a.out[i], pre2 + h);
+        store_out(&a.out[i], poly_last_row(a.c0, bval, acc, pre2));
     } else if (MODE == SM_JACOBI) {
         double told = pre2;
         if (diag != 0.0) {
@@ -1615,6 +1622,36 @@ __device__ __forceinline__ void stencil_epilogue(const StreamArgs &a, const Sten
             a.out[i] = told;
         }
     }
+}
+
+// The row sum of a coded row (stencils of up to 7 offsets): slot u holds dictionary entry (cw >> 8u) & 255, code 255 = the
+// row does not store the slot (also every slot >= nu).  Terms v[u] * (gscale * xv[u]) in increasing slot order, skipped by
+// selects.  Shared by stencil_coded_kernel and the fused level-0 chains (level0_chain_kernel): the same bits in both.
+template <int MODE>
+__device__ __forceinline__ double coded_row_sum(unsigned long long cw, const double *sdict, const double (&xv)[7], double gscale,
+                                                bool covered, double bval, int u0, double &diag)
+{
+    using MT = ModeTraits<MODE>;
+    double v[7];
+#pragma unroll
+    for (int u = 0; u < 7; ++u) v[u] = sdict[(unsigned)(cw >> (8 * u)) & 0xFFu];
+    double acc = MT::sub ? bval : 0.0;
+#pragma unroll
+    for (int u = 0; u < 7; ++u) {
+        const bool on = covered && ((unsigned)(cw >> (8 * u)) & 0xFFu) != 255u;      // (slots >= nu and unstored slots: 255)
+        if (MT::jac) {
+            const bool isd = u == u0;
+            diag = (on && isd) ? v[u] : diag;
+            const double pr = v[u] * (gscale * xv[u]);
+            const double nx = MT::sub ? (acc - pr) : (acc + pr);
+            acc = (on && !isd) ? nx : acc;
+        } else {
+            const double pr = v[u] * (gscale * xv[u]);
+            const double nx = MT::sub ? (acc - pr) : (acc + pr);
+            acc = on ? nx : acc;
+        }
+    }
+    return acc;
 }
 
 // ---------------------------------------------------------------------------
@@ -1666,26 +1703,8 @@ __global__ __launch_bounds__(WG) void stencil_coded_kernel(StreamArgs a, Stencil
     if (t < E.ndict) sdict[t] = dv;
     const bool covered = live && !(m & 0x80u);
     __syncthreads();                                              // dictionary in LDS
-    double v[7];
-#pragma unroll
-    for (int u = 0; u < 7; ++u) v[u] = sdict[(unsigned)(cw >> (8 * u)) & 0xFFu];
-    const double gscale = a.gscale;
-    double acc = MT::sub ? bval : 0.0, diag = 0.0;
-#pragma unroll
-    for (int u = 0; u < 7; ++u) {
-        const bool on = covered && ((unsigned)(cw >> (8 * u)) & 0xFFu) != 255u;      // (slots >= nu and unstored slots: 255)
-        if (MT::jac) {
-            const bool isd = u == E.u0;
-            diag = (on && isd) ? v[u] : diag;
-            const double pr = v[u] * (gscale * xv[u]);
-            const double nx = MT::sub ? (acc - pr) : (acc + pr);
-            acc = (on && !isd) ? nx : acc;
-        } else {
-            const double pr = v[u] * (gscale * xv[u]);
-            const double nx = MT::sub ? (acc - pr) : (acc + pr);
-            acc = on ? nx : acc;
-        }
-    }
+    double diag = 0.0;
+    const double acc = coded_row_sum<MODE>(cw, sdict, xv, a.gscale, covered, bval, E.u0, diag);
     stencil_epilogue<MODE>(a, E, i, blk, t, covered, acc, diag, bval, pre2, red);
 }
 
@@ -2142,6 +2161,180 @@ int launch_stencil(StreamMode mode, const StreamArgs &a, const DevCsr &M, hipStr
     }
     set_error("launch_stencil: mode not supported");
     return -1;
+}
+
+// ---------------------------------------------------------------------------
+// Fused level-0 smoother chains (hier.hip cycle): [RESIDUAL] -> POLY_LAST -> [RESIDUAL] over a 3-D box
+// grid whose operator is the coded 7-point stencil (offsets -P, -L, -1, 0, 1, L, P = slots 0..6).  A workgroup owns a
+// 32 x 32 column tile (interior 32 - 2S, S = stages) and marches along z over a chunk of planes; stage s runs one plane
+// behind stage s - 1 and is valid on the tile shrunk by s rows, so its halo rows are recomputed, never exchanged.  Each
+// lane keeps its column's last three planes of every stage in registers (the +-P operands), the middle plane of the stage
+// being consumed goes through LDS (the +-1, +-L operands).  Every row's sum is coded_row_sum over the same slots in the
+// same order with the same gscale products, and residual_row / poly_last_row are the unfused epilogues: the same bits as
+// the separate stencil_coded_kernel passes.  The first stage's operand is loaded one iteration ahead, the row operands
+// (codes, b, x) too; no workgroup waits for another.
+// ---------------------------------------------------------------------------
+#ifndef L0C_TY                                  // (A/B builds: -DL0C_TY=24 / 32)
+#define L0C_TY 16
+#endif
+constexpr int L0C_TX = 32;                      // tile extent in lanes along x (a wave: two line segments) ...
+constexpr int L0C_WG = L0C_TX * L0C_TY;         // ... and along y
+constexpr int L0C_PAD = L0C_TX;                 // LDS padding: lanes of the tile's edge read past the plane (results discarded)
+
+template <int FR, int LR>
+__global__ __launch_bounds__(L0C_WG) void level0_chain_kernel(Level0ChainArgs a)
+{
+    constexpr int S = FR + 1 + LR;              // stages = halo depth in rows and planes
+    constexpr int SP = FR + 1;                  // the POLY_LAST stage
+    constexpr int INX = L0C_TX - 2 * S, INY = L0C_TY - 2 * S;      // interior of the tile
+    __shared__ double sdict[256];
+    __shared__ double pl[S][L0C_WG + 2 * L0C_PAD];
+    const int t = threadIdx.x, tx = t % L0C_TX, ty = t / L0C_TX;
+    const int bid = remap_block(blockIdx.x, gridDim.x, 16);
+    const int tiles = a.tiles_x * a.tiles_y;
+    const int zb = bid / tiles, rem = bid - zb * tiles;
+    const int tyi = rem / a.tiles_x, txi = rem - tyi * a.tiles_x;
+    const int gx = txi * INX - S + tx, gy = tyi * INY - S + ty;
+    const bool inxy = gx >= 0 && gx < a.nx && gy >= 0 && gy < a.ny;
+    const bool ring1 = inxy && tx >= 1 && tx < L0C_TX - 1 && ty >= 1 && ty < L0C_TY - 1;   // where stage 1 can be valid
+    const bool inner = inxy && tx >= S && tx < L0C_TX - S && ty >= S && ty < L0C_TY - S;
+    const long P = (long)a.nx * a.ny;
+    const long col = inxy ? (long)gy * a.nx + gx : 0;
+    const int z0 = zb * a.zc, z1 = min(z0 + a.zc, a.nz);
+    if (t < a.ndict) sdict[t] = a.dict[t];      // (read after the first barrier below)
+
+    double w[S + 1][3];                         // stage s: planes k-s-2, k-s-1, k-s (stage 0 = the loaded operand)
+    unsigned long long cq[S];                   // codes of planes k-1 .. k-S
+    double bq[S];                               // right-hand side of planes k-1 .. k-S
+#pragma unroll
+    for (int s = 0; s <= S; ++s) w[s][0] = w[s][1] = w[s][2] = 0.0;
+#pragma unroll
+    for (int s = 0; s < S; ++s) { cq[s] = ~0ULL; bq[s] = 0.0; }
+    double xq = 0.0;                            // (no leading residual) the iterate of plane k-1
+    int k = z0 - S;
+    double g_next = (inxy && k >= 0) ? a.g0[(long)k * P + col] : 0.0;
+    unsigned long long c_next = ~0ULL;
+    double b_next = 0.0, x_next = 0.0;
+    const int iters = (z1 - z0) + 2 * S;
+    for (int j = 0; j < iters; ++j, ++k) {
+        w[0][0] = w[0][1]; w[0][1] = w[0][2]; w[0][2] = g_next;
+#pragma unroll
+        for (int s = S - 1; s > 0; --s) { cq[s] = cq[s - 1]; bq[s] = bq[s - 1]; }
+        cq[0] = c_next; bq[0] = b_next; xq = x_next;
+        {   // the next iteration's loads: the operand of plane k+1, the row operands of plane k
+            const int kn = k + 1;
+            g_next = (inxy && kn >= 0 && kn < a.nz) ? a.g0[(long)kn * P + col] : 0.0;
+            const bool rowk = ring1 && k >= 0 && k < a.nz;
+            const long ik = (long)k * P + col;
+            c_next = rowk ? a.codes[ik] : ~0ULL;               // (all slots absent)
+            b_next = rowk ? a.b[ik] : 0.0;
+            if (!FR) x_next = rowk ? a.x[ik] : 0.0;
+        }
+#pragma unroll
+        for (int s = 1; s <= S; ++s) {          // stage s at plane k - s
+            pl[s - 1][L0C_PAD + t] = w[s - 1][1];
+            __syncthreads();
+            const double *q = &pl[s - 1][L0C_PAD + t];
+            const double xv[7] = {w[s - 1][0], q[-L0C_TX], q[-1], w[s - 1][1], q[1], q[L0C_TX], w[s - 1][2]};
+            double diag = 0.0, val;
+            if (s == SP) {
+                const double acc = coded_row_sum<SM_POLY_LAST>(cq[s - 1], sdict, xv, a.c_gs, true, 0.0, -1, diag);
+                val = poly_last_row(a.c_last, w[s - 1][1], acc, FR ? w[0][0] : xq);
+            } else {
+                const double acc = coded_row_sum<SM_RESIDUAL>(cq[s - 1], sdict, xv, 1.0, true, 0.0, -1, diag);
+                val = residual_row(bq[s - 1], acc);
+            }
+            w[s][0] = w[s][1]; w[s][1] = w[s][2]; w[s][2] = val;
+        }
+        const int p = k - S;                    // the chain's output plane
+        if (inner && p >= z0 && p < z1) {
+            const long i = (long)p * P + col;
+            if (LR) store_out(&a.rout[i], w[S][2]);
+            store_out(&a.xout[i], w[SP][2 - (S - SP)]);
+        }
+    }
+}
+
+int level0_chain_tile(int stages, int axis) { return (axis == 0 ? L0C_TX : L0C_TY) - 2 * stages; }
+int level0_chain_lanes(int axis) { return axis == 0 ? L0C_TX : L0C_TY; }
+
+int launch_level0_chain(bool first_res, bool last_res, const Level0ChainArgs &a0, hipStream_t st)
+{
+    Level0ChainArgs a = a0;
+    const int S = 1 + (first_res ? 1 : 0) + (last_res ? 1 : 0);
+    if (S < 2 || a.nx < 1 || a.ny < 1 || a.nz < 1 || a.zc < 1) { set_error("launch_level0_chain: bad chain"); return -1; }
+    const int inx = level0_chain_tile(S, 0), iny = level0_chain_tile(S, 1);
+    a.tiles_x = (a.nx + inx - 1) / inx;
+    a.tiles_y = (a.ny + iny - 1) / iny;
+    const long grid = (long)a.tiles_x * a.tiles_y * ((a.nz + a.zc - 1) / a.zc);
+    if (grid > 2147483647L) { set_error("launch_level0_chain: grid too large"); return -1; }
+    if (first_res && last_res) hipLaunchKernelGGL((level0_chain_kernel<1, 1>), dim3(grid), dim3(L0C_WG), 0, st, a);
+    else if (first_res) hipLaunchKernelGGL((level0_chain_kernel<1, 0>), dim3(grid), dim3(L0C_WG), 0, st, a);
+    else hipLaunchKernelGGL((level0_chain_kernel<0, 1>), dim3(grid), dim3(L0C_WG), 0, st, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "level-0 chain launch", __FILE__, __LINE__);
+    return 0;
+}
+
+// the partial sums of SM_RESIDUAL_SUMSQ from a stored residual: same 256-row blocks, same block_reduce_sum tree, and
+// r * r of the stored r is the square the fused pass forms from the same double.  A workgroup takes SSQ_BLOCKS blocks,
+// every load requested before the first reduction (500^3: 0.32 ms per pass, as with one block per workgroup)
+constexpr int SSQ_BLOCKS = 8;
+__global__ __launch_bounds__(WG) void sumsq_partials_kernel(const double *r, int n, int nb, double *out2)
+{
+    __shared__ double red[SSQ_BLOCKS][8];
+    const int t = threadIdx.x, b0 = blockIdx.x * SSQ_BLOCKS;
+    double sq[SSQ_BLOCKS];
+#pragma unroll
+    for (int q = 0; q < SSQ_BLOCKS; ++q) {
+        const long i = (long)(b0 + q) * WG + t;
+        sq[q] = 0.0;
+        if (i < n) {
+            const double rr = r[i];
+            sq[q] = rr * rr;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < SSQ_BLOCKS; ++q) {
+        const double tot = block_reduce_sum(sq[q], red[q]);
+        if (t == 0 && b0 + q < nb) out2[b0 + q] = tot;
+    }
+}
+
+int launch_sumsq_partials(const double *r, int n, double *out2, hipStream_t st)
+{
+    if (n <= 0) return 0;
+    const int nb = (n + WG - 1) / WG;
+    hipLaunchKernelGGL(sumsq_partials_kernel, dim3((nb + SSQ_BLOCKS - 1) / SSQ_BLOCKS), dim3(WG), 0, st, r, n, nb, out2);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "sumsq partials launch", __FILE__, __LINE__);
+    return 0;
+}
+
+// eligibility of the fused chains: every stored coupling of the coded 7-point rows stays inside the (nz, ny, nx) box
+__global__ void level0_box_scan_kernel(const unsigned long long *codes, int nx, int ny, int nz, int *bad)
+{
+    const long n = (long)nx * ny * nz;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const unsigned long long cw = codes[i];
+        const int x = (int)(i % nx);
+        const long r = i / nx;
+        const int y = (int)(r % ny), z = (int)(r / ny);
+        const bool ok[7] = {z > 0, y > 0, x > 0, true, x < nx - 1, y < ny - 1, z < nz - 1};
+        bool fail = false;
+#pragma unroll
+        for (int u = 0; u < 7; ++u) fail |= ((unsigned)(cw >> (8 * u)) & 0xFFu) != 255u && !ok[u];
+        if (fail) *bad = 1;
+    }
+}
+
+int launch_level0_box_scan(const unsigned char *codes, int nx, int ny, int nz, int *bad, hipStream_t st)
+{
+    hipLaunchKernelGGL(level0_box_scan_kernel, dim3(4096), dim3(256), 0, st, reinterpret_cast<const unsigned long long *>(codes),
+                       nx, ny, nz, bad);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "level-0 box scan launch", __FILE__, __LINE__);
+    return 0;
 }
 
 // 16-bit column codes (DevCsr::Aj16): one workgroup per row block of the stream kernel
