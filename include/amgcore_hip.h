@@ -585,6 +585,45 @@ int amg_hierx_cycle(amg_hierx *h, const void *b, void *x, int cycle, int flags);
 long amg_hierx_device_bytes(amg_hierx *h);
 double amg_hierx_last_solve_ms(amg_hierx *h);
 
+/* ------------------------------------------------------------------------ */
+/* 6. Resident float64 hierarchies for SEVERAL right-hand sides: the cycle   */
+/*    of section 2 (multilevel.py:316-548) for k vectors at once.  Every     */
+/*    operator entry is read once per application and applied to all columns,*/
+/*    every Gauss-Seidel dependency level is one launch for all columns.     */
+/*    Per column the iterates have the bits of amg_hier_solve; a column's    */
+/*    iterates and residual history do not depend on k, on its position or   */
+/*    on the other columns.  Plain CSR operators, eager launches.            */
+/* ------------------------------------------------------------------------ */
+typedef struct amg_hierm amg_hierm;
+
+/* kmax in 1 .. 8: the most columns one call will carry (work vectors are n x {1, 2, 4, 8} doubles, the next width) */
+int amg_hierm_create(int nlevels, int device, int kmax, amg_hierm **out);
+void amg_hierm_destroy(amg_hierm *h);
+/* as amg_hier_set_matrix (HOST arrays, copied): CSR, or BSR with 1 x 1 blocks (larger blocks: AMG_ENOTIMPL), which
+ * multiplies like CSR and relaxes with the rounding of bsr_jacobi / bsr_gauss_seidel */
+int amg_hierm_set_matrix(amg_hierm *h, int lvl, int which, int fmt, int nrows, int ncols, int R, int C,
+                         const int *Ap, const int *Aj, const double *Ax);
+/* kinds AMG_SM_NONE, _JACOBI, _GAUSS_SEIDEL, _SOR, _POLYNOMIAL; any other kind returns AMG_ENOTIMPL */
+int amg_hierm_set_smoother(amg_hierm *h, int lvl, int which, const amg_smoother_desc *d);
+/* coarse solve = the dense n x n operator M (row-major), sequential row sums per column */
+int amg_hierm_set_coarse_dense(amg_hierm *h, const double *M, int n);
+/* coarse solve = x = 0, then the smoother (same kinds) */
+int amg_hierm_set_coarse_smoother(amg_hierm *h, const amg_smoother_desc *d);
+/* builds the schedules and work vectors and seals the handle: setters called after it return AMG_ESTATE, and
+ * calling it again returns 0 without doing anything */
+int amg_hierm_finalize(amg_hierm *h);
+/* multilevel_solver.solve for each of the k (1 .. kmax) columns of B; B and X are HOST arrays, row-major (n, k); X holds
+ * the starting guesses on entry.  Column j stops by its own tol * ||b_j|| (tol when ||b_j|| = 0); what X receives for
+ * it is the iterate at which it stopped, although the engine keeps cycling it while other columns are active.
+ * residuals: k rows of maxiter + 1 doubles (column j's history), nres: k counts.  flags AMG_SOLVE_X0_ZERO and
+ * AMG_SOLVE_NO_EARLY_STOP as for amg_hier_solve. */
+int amg_hierm_solve(amg_hierm *h, int k, const double *B, double *X, double tol, int maxiter, int cycle,
+                    double *residuals, int *nres, int flags);
+/* one cycle (V, W, F) of every column; AMG_SOLVE_X0_ZERO: start from zero */
+int amg_hierm_cycle(amg_hierm *h, int k, const double *B, double *X, int cycle, int flags);
+long amg_hierm_device_bytes(amg_hierm *h);
+double amg_hierm_last_solve_ms(amg_hierm *h);
+
 #ifdef __cplusplus
 }
 #endif

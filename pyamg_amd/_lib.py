@@ -179,6 +179,15 @@ def lib():
         "amg_hierx_finalize": [V],
         "amg_hierx_solve": [V, V, V, D, I, I, c_dbl_p, c_int_p, I],
         "amg_hierx_cycle": [V, V, V, I, I],
+        # section 6: several right-hand sides
+        "amg_hierm_create": [I, I, I, C.POINTER(C.c_void_p)],
+        "amg_hierm_set_matrix": [V, I, I, I, I, I, I, I, V, V, V],
+        "amg_hierm_set_smoother": [V, I, I, C.POINTER(SmootherDesc)],
+        "amg_hierm_set_coarse_dense": [V, c_dbl_p, I],
+        "amg_hierm_set_coarse_smoother": [V, C.POINTER(SmootherDesc)],
+        "amg_hierm_finalize": [V],
+        "amg_hierm_solve": [V, I, V, V, D, I, I, c_dbl_p, c_int_p, I],
+        "amg_hierm_cycle": [V, I, V, V, I, I],
     }
     for name, (kinds, sized) in FLAT_TABLE.items():
         for suffix in VALUE_SUFFIX.values():
@@ -201,6 +210,12 @@ def lib():
     L.amg_hierx_device_bytes.restype = C.c_long
     L.amg_hierx_last_solve_ms.argtypes = [V]
     L.amg_hierx_last_solve_ms.restype = D
+    L.amg_hierm_destroy.argtypes = [V]
+    L.amg_hierm_destroy.restype = None
+    L.amg_hierm_device_bytes.argtypes = [V]
+    L.amg_hierm_device_bytes.restype = C.c_long
+    L.amg_hierm_last_solve_ms.argtypes = [V]
+    L.amg_hierm_last_solve_ms.restype = D
     L.amg_hier_cycle_bytes.argtypes = [V, I]
     L.amg_hier_cycle_bytes.restype = D
     L.amg_hier_value_index.argtypes = [V, I, I]

@@ -881,6 +881,9 @@ class DistributedSolver(object):
             return np.asarray(self.perm[l][lo:hi], dtype=np.int64)
         return np.arange(lo, hi, dtype=np.int64)
 
+    def solve_many(self, *args, **kwargs):
+        raise NotImplementedError("solve_many: partitioned hierarchies are not implemented; solve() takes one vector")
+
     def solve(self, b_local, x0_local=None, tol=1e-5, maxiter=100, cycle="V", fixed=False):
         """multilevel.py:316-471 on the local slices; returns (x_local, residuals)"""
         cycle = str(cycle).upper()

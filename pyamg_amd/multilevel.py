@@ -492,6 +492,198 @@ class _DeviceHierarchyC128(object):
             pass
 
 
+_MULTI_KIND = {None: 0, "None": 0, "jacobi": 1, "gauss_seidel": 2, "sor": 3, "polynomial": 4}
+_MULTI_KMAX = 8          # widest column layout of the engine; more columns run in groups
+
+
+def _rhs_groups(k, kmax=_MULTI_KMAX):
+    """How k right-hand sides run: a list of (first column, columns, layout width).  Groups of kmax columns, the last
+    one padded with zero columns to the next width of 1, 2, 4, 8."""
+    if k < 1:
+        raise ValueError("at least one right-hand side is needed")
+    groups = []
+    for first in range(0, k, kmax):
+        cols = min(kmax, k - first)
+        width = 1
+        while width < cols:
+            width *= 2
+        groups.append((first, cols, width))
+    return groups
+
+
+# One batched cycle against one cycle per column, measured on SA hierarchies of 3-D Poisson problems with Chebyshev(2)
+# smoothers (profiles/r07_multirhs.txt): (unknowns up to, speed-up of 4 columns, speed-up of 8 columns).  The batched
+# engine runs the next width of 1, 2, 4, 8 columns, streams plain CSR and launches eagerly; the one-vector engine has
+# compressed operator forms, fused level-0 passes, graph replay and dataflow Gauss-Seidel sweeps, so the batch wins
+# where launches dominate (small problems, wide batches) and loses where bytes do.
+_BATCHED_SPEEDUP = [(4096, 2.29, 5.22), (32768, 1.07, 2.58), (262144, 0.77, 1.95), (1000000, 0.66, 1.43),
+                    (4096000, 0.45, 1.06)]
+_BATCHED_MARGIN = 1.1
+
+
+def _batched_cycle_pays(ml, k):
+    """aspreconditioner().matmat: is one batched cycle of k columns faster than k cycles?  Only where it was
+    measured to be, with a margin: never for one or two columns (0.54 and 0.97 at the smallest size), never on
+    hierarchies with Gauss-Seidel / SOR sweeps (a launch per dependency level against the dataflow sweep: 0.62 for 8
+    columns at 128^3), never above the largest size at which eight columns won; a group of k columns in a layout of
+    w costs what w columns cost."""
+    for lvl in ml.levels[:-1]:
+        for side in ("presmoother", "postsmoother"):
+            desc = getattr(getattr(lvl, side, None), "desc", None) or {}
+            if desc.get("name") in ("gauss_seidel", "sor"):
+                return False
+    if k < 3:
+        return False
+    n = ml.levels[0].A.shape[0]
+    k = min(k, _MULTI_KMAX)               # more columns run in groups of 8
+    for nmax, speedup4, speedup8 in _BATCHED_SPEEDUP:
+        if n <= nmax:
+            width, speedup = (4, speedup4) if k <= 4 else (8, speedup8)
+            return speedup * k / width >= _BATCHED_MARGIN
+    return False
+
+
+class _DeviceHierarchyMulti(object):
+    """A float64 hierarchy in HBM for several right-hand sides at once: an amg_hierm handle (include/amgcore_hip.h
+    section 6).  Plain CSR operators, eager launches; per column the cycle gives the bits of the one-vector engine
+    (DESIGN.md section 9c)."""
+
+    def __init__(self, ml, device=0, kmax=_MULTI_KMAX):
+        L = _lib.lib()
+        self.L = L
+        self.n = ml.levels[0].A.shape[0]
+        self.kmax = int(kmax)
+        self._cycles = 0
+        self._keep = []
+        kind, payload = self.check_levels(ml)
+        h = _lib.C.c_void_p()
+        _lib.check(L.amg_hierm_create(len(ml.levels), int(device), self.kmax, _lib.C.byref(h)))
+        self.h = h.value
+        try:
+            self._build(ml, kind, payload)
+        except Exception:
+            self.close()
+            raise
+        self._keep = []
+
+    @staticmethod
+    def check_levels(ml):
+        """the refusals, none of which needs a device: float64 operators in CSR or BSR(1,1), smoothers and a coarse
+        solver the engine implements.  Returns the coarse solver's device form."""
+        for i, lvl in enumerate(ml.levels):
+            ops = [("A", lvl.A)]
+            if i < len(ml.levels) - 1:
+                ops += [("P", lvl.P), ("R", lvl.R)]
+            for name, M in ops:
+                if np.iscomplexobj(M):
+                    raise NotImplementedError("solve_many: complex hierarchies are not implemented (level %d %s)" % (i, name))
+                if M.dtype != np.float64:
+                    raise NotImplementedError("solve_many: float64 operators only (level %d %s is %s)" % (i, name, M.dtype))
+                if sparse.isspmatrix_bsr(M) and tuple(M.blocksize) != (1, 1):
+                    raise NotImplementedError("solve_many: BSR blocks larger than 1 x 1 are not implemented "
+                                              "(level %d %s has %s blocks)" % (i, name, (M.blocksize,)))
+            if i < len(ml.levels) - 1:
+                for side in ("presmoother", "postsmoother"):
+                    _DeviceHierarchyMulti._desc_of(i, getattr(lvl, side, None))
+        s = ml.coarse_solver.solver
+        if callable(s) or (s is not None and s not in _CoarseSolver._DENSE + tuple(
+                n for n in _CoarseSolver._RELAX if not n.startswith("block_"))):
+            raise NotImplementedError("solve_many: coarse solver %r is not implemented (dense solvers, jacobi, "
+                                      "gauss_seidel, sor, richardson, chebyshev or None)" % (getattr(s, "__name__", s),))
+        kind, payload = ml.coarse_solver.device_form(ml.levels[-1].A)
+        if kind == "smoother":
+            _DeviceHierarchyMulti._desc_of(len(ml.levels) - 1, payload)
+        return kind, payload
+
+    @staticmethod
+    def _desc_of(lvl, fn):
+        desc = getattr(fn, "desc", None)
+        if fn is not None and desc is None:
+            raise NotImplementedError(
+                "level %d: smoother %r carries no device descriptor; use pyamg_amd.smoothing."
+                "change_smoothers with one of the device smoothers" % (lvl, fn))
+        name = None if desc is None else desc.get("name")
+        if name not in _MULTI_KIND:
+            raise NotImplementedError("solve_many: smoother %r is not implemented (jacobi, gauss_seidel, sor, "
+                                      "polynomial / chebyshev / richardson, None)" % (name,))
+        return desc
+
+    def _set_matrix(self, lvl, which, M):
+        if sparse.isspmatrix_bsr(M):
+            fmt = 1
+        else:
+            M = sparse.csr_matrix(M)
+            fmt = 0
+        data = np.ascontiguousarray(np.ravel(M.data), dtype=np.float64)
+        Ap = np.ascontiguousarray(M.indptr, dtype=np.intc)
+        Aj = np.ascontiguousarray(M.indices, dtype=np.intc)
+        _lib.check(self.L.amg_hierm_set_matrix(self.h, lvl, which, fmt, M.shape[0], M.shape[1], 1, 1,
+                                               Ap.ctypes.data, Aj.ctypes.data, data.ctypes.data))
+
+    def _set_smoother(self, lvl, which, fn):
+        d = _desc_struct(self._desc_of(lvl, fn), self._keep)
+        if which == 2:
+            _lib.check(self.L.amg_hierm_set_coarse_smoother(self.h, d))
+        else:
+            _lib.check(self.L.amg_hierm_set_smoother(self.h, lvl, which, d))
+
+    def _build(self, ml, kind, payload):
+        levels = ml.levels
+        for i, lvl in enumerate(levels):
+            self._set_matrix(i, 0, lvl.A)
+            if i < len(levels) - 1:
+                self._set_matrix(i, 1, lvl.P)
+                self._set_matrix(i, 2, lvl.R)
+                self._set_smoother(i, 0, getattr(lvl, "presmoother", None))
+                self._set_smoother(i, 1, getattr(lvl, "postsmoother", None))
+        if kind == "dense":
+            M = np.ascontiguousarray(payload, dtype=np.float64)
+            _lib.check(self.L.amg_hierm_set_coarse_dense(self.h, _lib.dp(M), M.shape[0]))
+        elif kind == "smoother":
+            self._set_smoother(len(levels) - 1, 2, payload)
+        elif kind != "none":
+            raise NotImplementedError("coarse solver %s has no implementation for several right-hand sides"
+                                      % ml.coarse_solver.name())
+        _lib.check(self.L.amg_hierm_finalize(self.h))
+
+    def solve(self, B, X, tol, maxiter, cycle, x0_zero=False, fixed=False):
+        """B, X: C-contiguous float64 (n, k), k <= kmax; X is overwritten.  Returns the k residual histories."""
+        k = B.shape[1]
+        res = np.zeros((k, maxiter + 1), dtype=np.float64)
+        nres = np.zeros(k, dtype=np.intc)
+        flags = (_X0_ZERO if x0_zero else 0) | (_NO_EARLY_STOP if fixed else 0)
+        _lib.check(self.L.amg_hierm_solve(self.h, k, B.ctypes.data, X.ctypes.data, float(tol), int(maxiter),
+                                          _CYCLE[cycle], _lib.dp(res), _lib.ip(nres), flags))
+        self._cycles += int(nres.max()) - 1
+        return [res[j, :nres[j]] for j in range(k)]
+
+    def cycle(self, B, X, cycle, x0_zero=False):
+        _lib.check(self.L.amg_hierm_cycle(self.h, B.shape[1], B.ctypes.data, X.ctypes.data, _CYCLE[cycle],
+                                          _X0_ZERO if x0_zero else 0))
+        self._cycles += 1
+
+    def cycles_run(self):
+        """batched cycles this mirror has run (one per cycle of a group of columns)"""
+        return self._cycles
+
+    def last_solve_ms(self):
+        return self.L.amg_hierm_last_solve_ms(self.h)
+
+    def device_bytes(self):
+        return self.L.amg_hierm_device_bytes(self.h)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.amg_hierm_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _is_c128(ml):
     return ml.levels[0].A.dtype == np.complex128
 
@@ -512,6 +704,7 @@ class multilevel_solver:
         self.coarse_solver = coarse_grid_solver(coarse_solver)
         self.device = device
         self._dev = None
+        self._devm = None
         for level in levels[:-1]:
             if not hasattr(level, "R"):
                 level.R = level.P.conj().T.asformat(level.P.format)   # level.P.H (multilevel.py:154-156)
@@ -599,6 +792,9 @@ class multilevel_solver:
         if self._dev is not None:
             self._dev.close()
         self._dev = None
+        if getattr(self, "_devm", None) is not None:
+            self._devm.close()
+        self._devm = None
 
     def device_hierarchy(self):
         """The HBM-resident mirror of this hierarchy (built on first use)."""
@@ -609,19 +805,129 @@ class multilevel_solver:
                 self._dev = _DeviceHierarchy(self, self.device)
         return self._dev
 
+    def device_hierarchy_multi(self):
+        """The HBM-resident mirror that solve_many runs on (built on first use; several right-hand sides at once)."""
+        if getattr(self, "_devm", None) is None:
+            self._devm = _DeviceHierarchyMulti(self, self.device)
+        return self._devm
+
     # ------------------------------------------------------------------ solve
     def psolve(self, b):
         return self.solve(b, maxiter=1)
 
-    def aspreconditioner(self, cycle="V"):
-        """multilevel.py:274-314"""
+    def aspreconditioner(self, cycle="V", batched=None):
+        """multilevel.py:274-314.  The operator also has a matmat: M.matmat(X) is one batched cycle of solve_many
+        for all columns (batched=True, or batched=None where that was measured faster than one cycle per column:
+        _batched_cycle_pays) when the hierarchy is one solve_many takes, and the loop over columns scipy would have
+        made otherwise (batched=False: always).  Either way column j is M.matvec(X[:, j]) bit for bit."""
         from scipy.sparse.linalg import LinearOperator
         shape = self.levels[0].A.shape
         dtype = self.levels[0].A.dtype
 
         def matvec(b):
             return self.solve(b, maxiter=1, cycle=cycle, tol=1e-12)
-        return LinearOperator(shape, matvec, dtype=dtype)
+
+        def matmat(X):
+            X = np.asarray(X)
+            use = batched is not False and not np.iscomplexobj(X)
+            if use and batched is None:
+                use = _batched_cycle_pays(self, X.shape[1])
+            if use:
+                try:
+                    self._check_many(cycle)
+                except NotImplementedError:
+                    use = False
+            if not use:
+                return np.hstack([matvec(X[:, j]).reshape(-1, 1) for j in range(X.shape[1])])
+            return self.solve_many(X, maxiter=1, cycle=cycle, tol=1e-12)
+        return LinearOperator(shape, matvec, matmat=matmat, dtype=dtype)
+
+    def _check_many(self, cycle):
+        """what solve_many refuses about the hierarchy and the cycle, before any device work; returns the cycle's name"""
+        cycle = str(cycle).upper()
+        if cycle not in _CYCLE:
+            raise TypeError("Unrecognized cycle type (%s)" % cycle)
+        if cycle == "AMLI":
+            raise NotImplementedError("solve_many: AMLI cycles are not implemented")
+        if getattr(self, "_devm", None) is None:
+            _DeviceHierarchyMulti.check_levels(self)
+        return cycle
+
+    def solve_many(self, B, X0=None, tol=1e-5, maxiter=100, cycle="V", residuals=None, callback=None, accel=None):
+        """solve() for the k columns of B at once: column j of the result and residuals[j] are what
+        solve(B[:, j], x0=X0[:, j], tol=tol, maxiter=maxiter, cycle=cycle, residuals=r) returns -- the column stops by
+        its own tol * ||b_j||, and what is returned for it is the iterate at which it stopped.  Every operator entry
+        is read once per application for all columns.
+
+        B, X0: real array-likes (n, k), k >= 1, on the host.  Returns a new C-contiguous float64 (n, k) array.
+        residuals, when a list, receives k lists of floats.  callback(j, x_j) is called after every cycle for every
+        column still iterating.  float64 hierarchies with CSR / BSR(1,1) operators, jacobi / gauss_seidel / sor /
+        polynomial smoothers, a dense or relaxation coarse solver, V / W / F cycles; anything else raises
+        NotImplementedError before any device work."""
+        if _is_device_tensor(B) or (X0 is not None and _is_device_tensor(X0)):
+            raise NotImplementedError("solve_many: torch device tensors are not implemented; pass host arrays")
+        if accel is not None:
+            raise NotImplementedError("solve_many: Krylov acceleration (accel) is not implemented")
+        B = np.asarray(B)
+        n = self.levels[0].A.shape[0]
+        if B.ndim != 2:
+            raise ValueError("B must be two-dimensional (n, k); solve() takes one vector")
+        if B.shape[0] != n:
+            raise ValueError("B must have %d rows" % n)
+        k = B.shape[1]
+        if k == 0:
+            raise ValueError("B has no columns")
+        if X0 is not None:
+            X0 = np.asarray(X0)
+            if X0.shape != B.shape:
+                raise ValueError("X0 must have the shape of B, %s" % (B.shape,))
+        cycle = self._check_many(cycle)
+        if np.iscomplexobj(B) or (X0 is not None and np.iscomplexobj(X0)):
+            raise NotImplementedError("solve_many: complex right-hand sides are not implemented")
+        maxiter = int(maxiter)
+        X = np.zeros((n, k), dtype=np.float64) if X0 is None else np.array(X0, dtype=np.float64, order="C")
+        hist = [[] for _ in range(k)]
+        dev = self.device_hierarchy_multi()
+        for first, cols, _width in _rhs_groups(k, dev.kmax):
+            Bg = np.ascontiguousarray(B[:, first:first + cols], dtype=np.float64)
+            Xg = np.ascontiguousarray(X[:, first:first + cols])
+            x0_zero = not np.any(Xg)
+            if callback is None:
+                res = dev.solve(Bg, Xg, tol, maxiter, cycle, x0_zero=x0_zero)
+                for j in range(cols):
+                    hist[first + j] = [float(r) for r in res[j]]
+            else:
+                self._solve_many_callback(dev, Bg, Xg, tol, maxiter, cycle, x0_zero, first, hist, callback)
+            X[:, first:first + cols] = Xg
+        if residuals is not None:
+            residuals[:] = hist
+        return X
+
+    @staticmethod
+    def _solve_many_callback(dev, Bg, Xg, tol, maxiter, cycle, x0_zero, first, hist, callback):
+        """one cycle per engine call so that callback(j, x_j) sees every iterate of an active column
+        (multilevel.py:454-466); a column that stopped keeps the iterate it stopped at"""
+        cols = Bg.shape[1]
+        res = dev.solve(Bg, Xg, 0.0, 0, cycle, x0_zero=x0_zero)
+        normb = [float(r[0]) for r in dev.solve(np.ascontiguousarray(Bg), np.zeros_like(Xg), 0.0, 0, cycle, x0_zero=True)]
+        atol = [tol * nb if nb != 0 else tol for nb in normb]
+        for j in range(cols):
+            hist[first + j] = [float(res[j][0])]
+        active = [j for j in range(cols) if hist[first + j][-1] > atol[j]]
+        work = Xg.copy()
+        it = 0
+        while active and it < maxiter:
+            res = dev.solve(Bg, work, 0.0, 1, cycle, x0_zero=x0_zero, fixed=True)
+            x0_zero = False
+            it += 1
+            still = []
+            for j in active:
+                hist[first + j].append(float(res[j][-1]))
+                Xg[:, j] = work[:, j]
+                callback(first + j, Xg[:, j].copy())
+                if hist[first + j][-1] > atol[j]:
+                    still.append(j)
+            active = still
 
     def solve(self, b, x0=None, tol=1e-5, maxiter=100, cycle="V", accel=None, callback=None,
               residuals=None, return_residuals=False):
