@@ -2168,11 +2168,11 @@ int launch_stencil(StreamMode mode, const StreamArgs &a, const DevCsr &M, hipStr
 // grid whose operator is the coded 7-point stencil (offsets -P, -L, -1, 0, 1, L, P = slots 0..6).  A workgroup owns a
 // 32 x 32 column tile (interior 32 - 2S, S = stages) and marches along z over a chunk of planes; stage s runs one plane
 // behind stage s - 1 and is valid on the tile shrunk by s rows, so its halo rows are recomputed, never exchanged.  Each
-// lane keeps its column's last three planes of every stage in registers (the +-P operands), the middle plane of the stage
-// being consumed goes through LDS (the +-1, +-L operands).  Every row's sum is coded_row_sum over the same slots in the
-// same order with the same gscale products, and residual_row / poly_last_row are the unfused epilogues: the same bits as
-// the separate stencil_coded_kernel passes.  The first stage's operand is loaded one iteration ahead, the row operands
-// (codes, b, x) too; no workgroup waits for another.
+// lane keeps its column's last three planes of every stage in registers (the +-P operands), the middle planes the stages
+// consume go through LDS (the +-1, +-L operands), all S of them behind one barrier per plane.  Every
+// row's sum is coded_row_sum over the same slots in the same order with the same gscale products, and residual_row /
+// poly_last_row are the unfused epilogues: the same bits as the separate stencil_coded_kernel passes.  The first
+// stage's operand is loaded one iteration ahead, the row operands (codes, b, x) too; no workgroup waits for another.
 // ---------------------------------------------------------------------------
 #ifndef L0C_TY                                  // (A/B builds: -DL0C_TY=24 / 32)
 #define L0C_TY 16
@@ -2188,7 +2188,7 @@ __global__ __launch_bounds__(L0C_WG) void level0_chain_kernel(Level0ChainArgs a)
     constexpr int SP = FR + 1;                  // the POLY_LAST stage
     constexpr int INX = L0C_TX - 2 * S, INY = L0C_TY - 2 * S;      // interior of the tile
     __shared__ double sdict[256];
-    __shared__ double pl[S][L0C_WG + 2 * L0C_PAD];
+    __shared__ double pl[2][S][L0C_WG + 2 * L0C_PAD];   // double-buffered by iteration parity: one barrier per plane
     const int t = threadIdx.x, tx = t % L0C_TX, ty = t / L0C_TX;
     const int bid = remap_block(blockIdx.x, gridDim.x, 16);
     const int tiles = a.tiles_x * a.tiles_y;
@@ -2230,11 +2230,17 @@ __global__ __launch_bounds__(L0C_WG) void level0_chain_kernel(Level0ChainArgs a)
             b_next = rowk ? a.b[ik] : 0.0;
             if (!FR) x_next = rowk ? a.x[ik] : 0.0;
         }
+        // Every stage's middle plane is known here: stage 1's is the operand just shifted in, stage s >= 2's is what stage
+        // s - 1 computed in the previous iteration (w[s-1][2], which that stage's shift below moves to w[s-1][1]).  All S
+        // planes are published at once, behind one barrier.  A wave that runs ahead writes the other buffer; it comes
+        // back to this one only behind the next iteration's barrier, which every wave reaches after its reads here.
+        double (*plb)[L0C_WG + 2 * L0C_PAD] = pl[j & 1];
+#pragma unroll
+        for (int s = 1; s <= S; ++s) plb[s - 1][L0C_PAD + t] = s == 1 ? w[0][1] : w[s - 1][2];
+        __syncthreads();
 #pragma unroll
         for (int s = 1; s <= S; ++s) {          // stage s at plane k - s
-            pl[s - 1][L0C_PAD + t] = w[s - 1][1];
-            __syncthreads();
-            const double *q = &pl[s - 1][L0C_PAD + t];
+            const double *q = &plb[s - 1][L0C_PAD + t];
             const double xv[7] = {w[s - 1][0], q[-L0C_TX], q[-1], w[s - 1][1], q[1], q[L0C_TX], w[s - 1][2]};
             double diag = 0.0, val;
             if (s == SP) {
@@ -2276,28 +2282,36 @@ int launch_level0_chain(bool first_res, bool last_res, const Level0ChainArgs &a0
     return 0;
 }
 
-// the partial sums of SM_RESIDUAL_SUMSQ from a stored residual: same 256-row blocks, same block_reduce_sum tree, and
-// r * r of the stored r is the square the fused pass forms from the same double.  A workgroup takes SSQ_BLOCKS blocks,
-// every load requested before the first reduction (500^3: 0.32 ms per pass, as with one block per workgroup)
-constexpr int SSQ_BLOCKS = 8;
+// the partial sums of SM_RESIDUAL_SUMSQ from a stored residual: same 256-row blocks, same additions in the same order as
+// block_reduce_sum, and r * r of the stored r is the square the fused pass forms from the same double.  A wave owns
+// SSQ_BLOCKS whole blocks: lane l holds rows 64 q + l (q = 0..3) of each, which are the rows of lane l of wave q in the
+// stencil launch, so the four butterflies are that launch's four and lane 0 adds their results as its thread 0 adds
+// smem[0..3].  No LDS, no barrier; every load requested before the first reduction.
+constexpr int SSQ_BLOCKS = 2;
 __global__ __launch_bounds__(WG) void sumsq_partials_kernel(const double *r, int n, int nb, double *out2)
 {
-    __shared__ double red[SSQ_BLOCKS][8];
-    const int t = threadIdx.x, b0 = blockIdx.x * SSQ_BLOCKS;
-    double sq[SSQ_BLOCKS];
+    static_assert(WG == 256, "a block of the partials is four wave-sized pieces");
+    const int lane = threadIdx.x & 63;
+    const int b0 = (blockIdx.x * (WG / 64) + (threadIdx.x >> 6)) * SSQ_BLOCKS;
+    double sq[SSQ_BLOCKS][4];
 #pragma unroll
-    for (int q = 0; q < SSQ_BLOCKS; ++q) {
-        const long i = (long)(b0 + q) * WG + t;
-        sq[q] = 0.0;
-        if (i < n) {
-            const double rr = r[i];
-            sq[q] = rr * rr;
+    for (int q = 0; q < SSQ_BLOCKS; ++q)
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const long i = (long)(b0 + q) * WG + 64 * p + lane;
+            const double rr = i < n ? r[i] : 0.0;
+            sq[q][p] = rr * rr;
         }
-    }
 #pragma unroll
     for (int q = 0; q < SSQ_BLOCKS; ++q) {
-        const double tot = block_reduce_sum(sq[q], red[q]);
-        if (t == 0 && b0 + q < nb) out2[b0 + q] = tot;
+        double tot = 0.0;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            double v = sq[q][p];
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+            tot += v;
+        }
+        if (lane == 0 && b0 + q < nb) out2[b0 + q] = tot;
     }
 }
 
@@ -2305,7 +2319,8 @@ int launch_sumsq_partials(const double *r, int n, double *out2, hipStream_t st)
 {
     if (n <= 0) return 0;
     const int nb = (n + WG - 1) / WG;
-    hipLaunchKernelGGL(sumsq_partials_kernel, dim3((nb + SSQ_BLOCKS - 1) / SSQ_BLOCKS), dim3(WG), 0, st, r, n, nb, out2);
+    const int per_wg = SSQ_BLOCKS * (WG / 64);
+    hipLaunchKernelGGL(sumsq_partials_kernel, dim3((nb + per_wg - 1) / per_wg), dim3(WG), 0, st, r, n, nb, out2);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "sumsq partials launch", __FILE__, __LINE__);
     return 0;
