@@ -42,6 +42,21 @@ const char *amg_device_name(int device);
 /*    scheduling, which reproduces the sequential iterates bit for bit.      */
 /* ------------------------------------------------------------------------ */
 
+/* Sweep ranges.  Every sweeping entry visits `for (i = start; i != stop; i += step)` over rows, block rows,
+ * positions of Id or subdomains: step may be negative, start == stop is an empty sweep that touches nothing,
+ * and AMG_EINVAL (with every array untouched) answers step == 0, a range that never reaches stop, one that
+ * leaves the matrix, and an Id entry outside it.  jacobi_ne alone loops `for (i = start; i < stop; i += step)`
+ * and takes a positive step only.
+ * temp and z are the caller's, read and written back:
+ *  - jacobi and block_jacobi copy x into temp on the swept (block) rows only, read temp on every column of a
+ *    swept row, so also the caller's values outside the sweep, and write x on the swept rows;
+ *  - bsr_jacobi copies the prefix temp[0 .. |stop - start| * blocksize) = x[...] from index 0 whatever start
+ *    is, reads the caller's temp beyond it, and takes a step >= 1 only (the reference's copy loop does not
+ *    end for a negative one);
+ *  - jacobi_ne zeroes temp on the swept rows, accumulates every swept row's update onto temp, onto the
+ *    caller's values on columns outside the sweep, then adds temp to x on the swept rows;
+ *  - gauss_seidel_nr keeps z = b - A x up to date: z is the residual going in and coming out. */
+
 /* pyamg/amg_core/relaxation.h:33-62, called from pyamg/relaxation/relaxation.py:349 */
 int amgcore_gauss_seidel_f64(const int Ap[], int Ap_size, const int Aj[], int Aj_size,
                              const double Ax[], int Ax_size, double x[], int x_size,

@@ -13,7 +13,11 @@ oracle/_ref/_amg_core.so, exactly as oracle/gen_golden.py does -- and records in
   tests/golden/relaxation_dtypes.npz  the reference's pyamg.relaxation functions on small CSR and BSR 2x2
                                       systems in each dtype
 
-kernels_dtypes.npz and division_dtypes.npz keep every distinct array once (``pool_<k>``); ``<case>__call`` describes the call
+  tests/golden/ranges_<dtype>.npz     sub-range, strided, single-row and empty sweeps of every sweeping entry with
+                                      random (never zero) temp and z, one file per dtype, float64 included; the
+                                      systems and the list of calls are tests/flat_ranges.py:sweep_calls
+
+kernels_dtypes.npz, division_dtypes.npz and ranges_*.npz keep every distinct array once (``pool_<k>``); ``<case>__call`` describes the call
 and names the pool entries of its inputs and of the arrays it changed (class Recorder).  Usage:  make -C oracle ref && python tools/gen_golden_dtypes.py
 """
 import json
@@ -27,11 +31,14 @@ from scipy.sparse import _sparsetools
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import ref_env  # noqa: E402
+import flat_ranges  # noqa: E402
 from gen_golden import random_system  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden")
 DTYPES = {"f32": np.float32, "c64": np.complex64, "c128": np.complex128}
+CAP = 1000 * 1000          # bytes: no fixture file may reach 1 MB
 
 
 class Recorder:
@@ -266,6 +273,28 @@ def gen_division(core, rec, tag, dt):
              division=True)
 
 
+def gen_ranges(core):
+    """tests/golden/ranges_<dtype>.npz: CSR n = 300 (two 256-row workgroups, three 128-thread level blocks, two
+    1024-entry LDS chunks), BSR 2x2 (150 block rows) and 3x3 (100), 60 Schwarz subdomains; every recorded output
+    is finite, so the tests compare bits with no NaN exemption"""
+    for tag, dt in flat_ranges.DTYPES.items():
+        calls = list(flat_ranges.sweep_calls(dt, 300, ((2, 150), (3, 100)), 60, list(flat_ranges.ranges(300))))
+        path = os.path.join(OUT, "ranges_%s.npz" % tag)
+        while True:
+            rec = Recorder()
+            for name, fn, args in calls:
+                case = "%s@%s" % (name, tag)
+                rec.call(core, case, fn, [(k, v.item() if isinstance(v, np.generic) else v) for k, v in args])
+                out = json.loads(str(rec.out[case + "__call"]))["out"]
+                assert all(np.all(np.isfinite(rec.out[key])) for key in out.values()), case
+                assert bool(out) == ("_empty" not in name), case
+            rec.save(path)
+            if os.path.getsize(path) < CAP:
+                break
+            dropped = calls.pop()                              # the largest file sheds its last cases first
+            print("%s is over the cap: dropping %s" % (os.path.basename(path), dropped[0]))
+
+
 # --------------------------------------------------------------------------- pyamg.relaxation
 def poisson1(n):
     return sps.diags([-np.ones(n - 1), 2 * np.ones(n), -np.ones(n - 1)], [-1, 0, 1], format="csr")
@@ -367,6 +396,7 @@ def main():
             gen_division(core, div, tag, dt)
     rec.save(os.path.join(OUT, "kernels_dtypes.npz"))
     div.save(os.path.join(OUT, "division_dtypes.npz"))
+    gen_ranges(core)
     store = {"cases": [], "arrays": {}}
     for tag, dt in DTYPES.items():
         gen_relaxation(pyamg, tag, dt, store)
