@@ -15,8 +15,7 @@
 //
 // Shapes: CSR rows run in 256-row workgroups that stage their entries' products in LDS (coalesced 16-byte loads)
 // and sum each row in stored order; BSR rows run one thread per point row.  Launches are eager on one stream.
-#include "hier.hpp"
-#include "flat.hpp"
+#include "resident.hpp"
 #include "scalar.hpp"
 #include "typed_kernels.hpp"
 
@@ -36,7 +35,7 @@ constexpr int NORM_WG = 256;
 constexpr int VEC_WG = 256;
 
 enum { SM_NONE = 0, SM_JACOBI = 1, SM_GS = 2, SM_SOR = 3, SM_POLY = 4, SM_BJACOBI = 5, SM_BGS = 6 };
-enum { COARSE_NONE = 0, COARSE_DENSE = 1, COARSE_SMOOTHER = 2, COARSE_CALLBACK = 3 };
+constexpr char FINALIZE[] = "amg_hierx_finalize";
 
 // numpy's product of a complex array with a real scalar c: c is promoted to c + 0i and the full complex product
 // formed, (a.re c - a.im 0, a.re 0 + a.im c); it differs from component-wise scaling in the sign of zeros
@@ -200,42 +199,6 @@ __global__ void __launch_bounds__(NORM_WG) norm_final(const double *__restrict__
 }
 
 // ----------------------------------------------------------------------------------------------- host side
-int blocks_of(long n, int per) { return (int)((n + per - 1) / per); }
-
-int launched(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
-    return 0;
-}
-
-// Ap nondecreasing from 0, every column index in [0, ncols): no kernel can read outside its arrays
-int check_pattern(const int *Ap, int nrows, const int *Aj, int ncols)
-{
-    if (!Ap || Ap[0] != 0) { set_error("bad Ap"); return AMG_EINVAL; }
-    for (int i = 0; i < nrows; ++i)
-        if (Ap[i + 1] < Ap[i]) { set_error("Ap is not nondecreasing"); return AMG_EINVAL; }
-    for (long k = 0; k < Ap[nrows]; ++k)
-        if (Aj[k] < 0 || Aj[k] >= ncols) { set_error("column index out of range"); return AMG_EINVAL; }
-    return 0;
-}
-
-struct Pool {            // device buffers of one hierarchy, counted for device_bytes
-    long bytes = 0;
-    int alloc(DBuf &d, size_t n)
-    {
-        CHK(d.alloc(n));
-        bytes += (long)n;
-        return 0;
-    }
-    int upload(DBuf &d, const void *src, size_t n)
-    {
-        CHK(alloc(d, n));
-        if (n) AMG_HIP(hipMemcpy(d.p, src, n, hipMemcpyHostToDevice));
-        return 0;
-    }
-};
-
 // one operator: CSR (R = C = 1) or BSR with R x C blocks; nb block rows, nrows = nb R point rows
 template <class T>
 struct XMat {
@@ -281,20 +244,6 @@ int apply_rows(const XMat<T> &A, const T *v, Epi epi, hipStream_t st)
     return launched("row kernel");
 }
 
-// dependency levels of a sweep over the block rows of a pattern (rows in level order on the device)
-struct Sweep {
-    std::vector<int> lp;
-    DBuf rows;
-    int build(Pool &pool, int nb, const std::vector<int> &Ap, const std::vector<int> &Aj, bool backward)
-    {
-        std::vector<int> tasks(nb), order, rws(nb);
-        for (int t = 0; t < nb; ++t) tasks[t] = backward ? nb - 1 - t : t;
-        CHK(build_levels(nb, Ap.data(), Aj.data(), tasks.data(), nb, lp, order));
-        for (int k = 0; k < nb; ++k) rws[k] = tasks[order[k]];
-        return pool.upload(rows, rws.data(), sizeof(int) * (size_t)nb);
-    }
-};
-
 template <class T>
 struct XSmoother {
     bool set = false;
@@ -314,30 +263,12 @@ struct XLevel {
 };
 
 template <class T>
-struct Engine {
-    int device = 0, nlev = 0;
-    bool finalized = false;
-    bool sealed = false;                  // finalize has run: the operators, smoothers and coarse solver are fixed
-    hipStream_t st = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+struct Engine : Core {
     std::vector<XLevel<T>> lv;
-    int coarse = COARSE_NONE;
     XSmoother<T> csm;                     // relaxation-named coarse solver
-    DBuf M;
-    int nM = 0;
     amg_coarse_callback_x cb = nullptr;
     void *cb_user = nullptr;
     std::vector<T> hb, hx;
-    DBuf part, res;
-    int nres_cap = 0;
-    double last_ms = 0.0;
-    Pool pool;
-    ~Engine()
-    {
-        if (ev0) hipEventDestroy(ev0);
-        if (ev1) hipEventDestroy(ev1);
-        if (st) hipStreamDestroy(st);
-    }
 };
 
 // ----------------------------------------------------------------------------------------------- smoothers
@@ -502,41 +433,24 @@ int coarse_solve(Engine<T> &E, T *x, const T *b)
     return AMG_ESTATE;
 }
 
-// multilevel.py:473-548 on level l (V, W, F); x_l and b_l live in the level's vectors
+// the steps of a cycle (cycle_level, resident.hpp) on the levels' vectors
 template <class T>
-int cycle_level(Engine<T> &E, int l, int cyc)
-{
-    XLevel<T> &L = E.lv[l], &Lc = E.lv[l + 1];
-    T *x = (T *)L.x.p, *b = (T *)L.b.p, *r = (T *)L.r.p;
-    T *xc = (T *)Lc.x.p, *bc = (T *)Lc.b.p;
-    CHK(relax(E, L, L.sm[0], x, b));
-    CHK(apply_rows(L.A, (const T *)x, EpiResid<T>{b, r}, E.st));                       // residual = b - A x
-    CHK(apply_rows(L.R, (const T *)r, EpiStore<T>{bc}, E.st));                         // coarse_b = R residual
-    if (Lc.A.nrows) AMG_HIP(hipMemsetAsync(xc, 0, sizeof(T) * (size_t)Lc.A.nrows, E.st));
-    if (l == E.nlev - 2) {
-        CHK(coarse_solve(E, xc, bc));
-    } else if (cyc == 0) {
-        CHK(cycle_level(E, l + 1, 0));
-    } else if (cyc == 1) {
-        CHK(cycle_level(E, l + 1, 1));
-        CHK(cycle_level(E, l + 1, 1));
-    } else {
-        CHK(cycle_level(E, l + 1, 2));
-        CHK(cycle_level(E, l + 1, 0));
+struct XCycle {
+    Engine<T> &E;
+    T *x(int l) const { return (T *)E.lv[l].x.p; }
+    T *b(int l) const { return (T *)E.lv[l].b.p; }
+    T *r(int l) const { return (T *)E.lv[l].r.p; }
+    int relax(int l, int w) { return ::relax(E, E.lv[l], E.lv[l].sm[w], x(l), (const T *)b(l)); }
+    int residual(int l) { return apply_rows(E.lv[l].A, (const T *)x(l), EpiResid<T>{b(l), r(l)}, E.st); }
+    int restrict_residual(int l) { return apply_rows(E.lv[l].R, (const T *)r(l), EpiStore<T>{b(l + 1)}, E.st); }
+    int zero_x(int l)
+    {
+        if (E.lv[l].A.nrows) AMG_HIP(hipMemsetAsync(x(l), 0, sizeof(T) * (size_t)E.lv[l].A.nrows, E.st));
+        return 0;
     }
-    CHK(apply_rows(L.P, (const T *)xc, EpiAdd<T>{x}, E.st));                           // x += P coarse_x
-    return relax(E, L, L.sm[1], x, b);
-}
-
-template <class T>
-int one_cycle(Engine<T> &E, int cyc)
-{
-    if (E.nlev == 1) {                      // multilevel.py:456-458: x = coarse_solver(A, b)
-        XLevel<T> &L = E.lv[0];
-        return coarse_solve(E, (T *)L.x.p, (const T *)L.b.p);
-    }
-    return cycle_level(E, 0, cyc);
-}
+    int coarse_solve() { return ::coarse_solve(E, x(E.nlev - 1), (const T *)b(E.nlev - 1)); }
+    int prolong_add(int l) { return apply_rows(E.lv[l].P, (const T *)x(l + 1), EpiAdd<T>{x(l)}, E.st); }
+};
 
 template <class T>
 int device_norm(Engine<T> &E, const T *v, long n, double *out)
@@ -551,9 +465,8 @@ int device_norm(Engine<T> &E, const T *v, long n, double *out)
 template <class T>
 int residual_norm(Engine<T> &E, double *slot)
 {
-    XLevel<T> &L = E.lv[0];
-    CHK(apply_rows(L.A, (const T *)L.x.p, EpiResid<T>{(const T *)L.b.p, (T *)L.r.p}, E.st));
-    return device_norm(E, (const T *)L.r.p, L.A.nrows, slot);
+    CHK(XCycle<T>{E}.residual(0));
+    return device_norm(E, (const T *)E.lv[0].r.p, E.lv[0].A.nrows, slot);
 }
 
 template <class T>
@@ -611,20 +524,13 @@ int build_smoother(Engine<T> &E, XLevel<T> &L, XSmoother<T> &s)
 template <class T>
 int set_smoother(Engine<T> &E, int lvl, int which, const amg_smoother_desc_x *d)
 {
-    if (lvl < 0 || lvl >= E.nlev || which < 0 || which > 2 || !d) { set_error("bad smoother slot"); return AMG_EINVAL; }
-    if (which == 2 && lvl != E.nlev - 1) { set_error("the coarse smoother belongs to the last level"); return AMG_EINVAL; }
-    if (which < 2 && lvl == E.nlev - 1) { set_error("the last level has no pre/post smoother"); return AMG_EINVAL; }
-    if (d->kind < SM_NONE || d->kind > SM_BGS) {
-        set_error("smoother kind " + std::to_string(d->kind) + " has no implementation for this value type");
-        return AMG_ENOTIMPL;
-    }
-    XSmoother<T> &s = which == 2 ? E.csm : E.lv[lvl].sm[which];
-    if (s.set) { set_error("smoother already set"); return AMG_ESTATE; }
-    if (which == 2 && E.coarse != COARSE_NONE) { set_error("coarse solver already set"); return AMG_ESTATE; }
+    XSmoother<T> *slot = nullptr;
+    CHK(smoother_slot(E, lvl, which, d, SM_BGS, "for this value type", slot));
+    XSmoother<T> &s = *slot;
     s.set = true;
     s.kind = d->kind;
     if (s.kind == SM_NONE) return 0;
-    if (d->iterations < 0 || d->sweep < 0 || d->sweep > 2) { set_error("bad iterations / sweep"); return AMG_EINVAL; }
+    CHK(check_sweeps(d));
     s.iterations = d->iterations;
     s.sweep = d->sweep;
     if (s.kind == SM_JACOBI || s.kind == SM_SOR || s.kind == SM_BJACOBI) {
@@ -646,46 +552,30 @@ int set_smoother(Engine<T> &E, int lvl, int which, const amg_smoother_desc_x *d)
     return 0;
 }
 
+// what finalize (resident.hpp) leaves to this engine
 template <class T>
-int finalize(Engine<T> &E)
-{
-    if (E.sealed) {
-        if (E.finalized) return 0;
-        set_error("an earlier amg_hierx_finalize failed; build a new hierarchy");
-        return AMG_ESTATE;
+struct XSetup {
+    Engine<T> &E;
+    int square(const XMat<T> &A)
+    {
+        if (A.nrows != A.ncols || A.R != A.C) { set_error("A must be square with square blocks"); return AMG_EINVAL; }
+        return 0;
     }
-    E.sealed = true;                      // the schedules below consume the host patterns: no setter may follow
-    for (int l = 0; l < E.nlev; ++l) {
+    int build_smoother(XLevel<T> &L, XSmoother<T> &s) { return ::build_smoother(E, L, s); }
+    int level_vectors(int l)
+    {
         XLevel<T> &L = E.lv[l];
-        if (!L.A.set) { set_error("level " + std::to_string(l) + ": A missing"); return AMG_ESTATE; }
-        if (L.A.nrows != L.A.ncols || L.A.R != L.A.C) { set_error("A must be square with square blocks"); return AMG_EINVAL; }
-        const int n = L.A.nrows;
-        if (l < E.nlev - 1) {
-            const XMat<T> &An = E.lv[l + 1].A;
-            if (!L.P.set || !L.R.set) { set_error("level " + std::to_string(l) + ": P or R missing"); return AMG_ESTATE; }
-            if (L.P.nrows != n || L.P.ncols != An.nrows || L.R.nrows != An.nrows || L.R.ncols != n) {
-                set_error("level " + std::to_string(l) + ": P / R shapes do not match A");
-                return AMG_EINVAL;
-            }
-            for (int w = 0; w < 2; ++w) CHK(build_smoother(E, L, L.sm[w]));
-        }
-        const size_t vb = sizeof(T) * (size_t)n;
-        for (DBuf *v : {&L.x, &L.b, &L.r, &L.h1, &L.h2, &L.t})
-            if (!v->p) CHK(E.pool.alloc(*v, vb));
+        for (DBuf *v : {&L.x, &L.b, &L.r, &L.h1, &L.h2, &L.t}) CHK(E.pool.alloc(*v, sizeof(T) * (size_t)L.A.nrows));
+        return 0;
     }
-    XLevel<T> &Lc = E.lv[E.nlev - 1];
-    if (E.coarse == COARSE_SMOOTHER) CHK(build_smoother(E, Lc, E.csm));
-    if (E.coarse == COARSE_DENSE && E.nM != Lc.A.nrows) { set_error("dense coarse operator has the wrong size"); return AMG_EINVAL; }
-    if (!E.part.p) CHK(E.pool.alloc(E.part, sizeof(double) * NORM_BLOCKS));
-    for (int l = 0; l < E.nlev; ++l) {             // the patterns served the schedules
-        for (XMat<T> *M : {&E.lv[l].A, &E.lv[l].P, &E.lv[l].R, &E.lv[l].sm[0].Ab, &E.lv[l].sm[1].Ab}) {
-            std::vector<int>().swap(M->hAp);
-            std::vector<int>().swap(M->hAj);
-        }
+    int finish()
+    {
+        CHK(E.pool.alloc(E.part, sizeof(double) * NORM_BLOCKS));
+        for (XLevel<T> &L : E.lv)
+            for (XSmoother<T> &s : L.sm) drop_pattern(s.Ab);
+        return 0;
     }
-    E.finalized = true;
-    return 0;
-}
+};
 
 template <class T>
 int solve(Engine<T> &E, const void *b, void *x, double tol, int maxiter, int cyc, double *residuals, int *nres,
@@ -696,13 +586,7 @@ int solve(Engine<T> &E, const void *b, void *x, double tol, int maxiter, int cyc
         set_error(cyc == 3 ? "AMLI cycles are not implemented for this value type" : "bad solve arguments");
         return cyc == 3 ? AMG_ENOTIMPL : AMG_EINVAL;
     }
-    if (E.nres_cap < maxiter + 2) {
-        E.pool.bytes -= (long)sizeof(double) * E.nres_cap;
-        if (E.res.p) AMG_HIP(hipFree(E.res.p));
-        E.res.p = nullptr;
-        CHK(E.pool.alloc(E.res, sizeof(double) * (size_t)(maxiter + 2)));
-        E.nres_cap = maxiter + 2;
-    }
+    CHK(E.reserve_history(maxiter, 1));
     double *rd = E.res.d();
     CHK(load_vectors(E, b, x, flags));
     XLevel<T> &L0 = E.lv[0];
@@ -715,25 +599,25 @@ int solve(Engine<T> &E, const void *b, void *x, double tol, int maxiter, int cyc
     if (normb != 0.0) tol = tol * normb;
     const bool fixed = (flags & AMG_SOLVE_NO_EARLY_STOP) != 0;
     int k = 1;
-    AMG_HIP(hipEventRecord(E.ev0, E.st));
-    while (k <= maxiter && (fixed || residuals[k - 1] > tol)) {                       // :454
-        CHK(one_cycle(E, cyc));
-        CHK(residual_norm(E, rd + k));
-        if (!fixed) {
-            AMG_HIP(hipMemcpyAsync(&residuals[k], rd + k, sizeof(double), hipMemcpyDeviceToHost, E.st));
-            AMG_HIP(hipStreamSynchronize(E.st));
-        }
-        ++k;
-    }
-    AMG_HIP(hipEventRecord(E.ev1, E.st));
-    if (fixed && k > 1)
-        AMG_HIP(hipMemcpyAsync(residuals + 1, rd + 1, sizeof(double) * (size_t)(k - 1), hipMemcpyDeviceToHost, E.st));
-    *nres = k;
-    CHK(store_x(E, x));
-    float ms = 0.f;
-    AMG_HIP(hipEventElapsedTime(&ms, E.ev0, E.ev1));
-    E.last_ms = ms;
-    return 0;
+    return E.timed(
+        [&]() -> int {
+            while (k <= maxiter && (fixed || residuals[k - 1] > tol)) {               // :454
+                CHK(one_cycle(XCycle<T>{E}, E.nlev, cyc));
+                CHK(residual_norm(E, rd + k));
+                if (!fixed) {
+                    AMG_HIP(hipMemcpyAsync(&residuals[k], rd + k, sizeof(double), hipMemcpyDeviceToHost, E.st));
+                    AMG_HIP(hipStreamSynchronize(E.st));
+                }
+                ++k;
+            }
+            return 0;
+        },
+        [&]() -> int {
+            if (fixed && k > 1)
+                AMG_HIP(hipMemcpyAsync(residuals + 1, rd + 1, sizeof(double) * (size_t)(k - 1), hipMemcpyDeviceToHost, E.st));
+            *nres = k;
+            return store_x(E, x);
+        });
 }
 
 template <class T>
@@ -745,14 +629,7 @@ int cycle(Engine<T> &E, const void *b, void *x, int cyc, int flags)
         return cyc == 3 ? AMG_ENOTIMPL : AMG_EINVAL;
     }
     CHK(load_vectors(E, b, x, flags));
-    AMG_HIP(hipEventRecord(E.ev0, E.st));
-    CHK(one_cycle(E, cyc));
-    AMG_HIP(hipEventRecord(E.ev1, E.st));
-    CHK(store_x(E, x));
-    float ms = 0.f;
-    AMG_HIP(hipEventElapsedTime(&ms, E.ev0, E.ev1));
-    E.last_ms = ms;
-    return 0;
+    return E.timed([&] { return one_cycle(XCycle<T>{E}, E.nlev, cyc); }, [&] { return store_x(E, x); });
 }
 
 using C128 = Engine<c128>;
@@ -765,16 +642,6 @@ struct amg_hierx {
     C128 e;
 };
 
-#define ENTERX(h)                                                       \
-    if (!(h)) { amg::set_error("null hierarchy"); return AMG_EINVAL; }  \
-    AMG_HIP(hipSetDevice((h)->e.device))
-// setters: only before amg_hierx_finalize
-#define UNSEALED(h)                                                                                       \
-    if ((h)->e.sealed) {                                                                                  \
-        amg::set_error("hierarchy already finalised: operators and solvers are set before amg_hierx_finalize"); \
-        return AMG_ESTATE;                                                                                \
-    }
-
 extern "C" {
 
 int amg_hierx_create(int value_type, int nlevels, int device, amg_hierx **out)
@@ -786,51 +653,27 @@ int amg_hierx_create(int value_type, int nlevels, int device, amg_hierx **out)
         return AMG_ENOTIMPL;
     }
     if (nlevels < 1) { set_error("nlevels < 1"); return AMG_EINVAL; }
-    CHK(require_device());
-    AMG_HIP(hipSetDevice(device));
-    amg_hierx *h = new amg_hierx();
-    C128 &E = h->e;
-    E.device = device;
-    E.nlev = nlevels;
-    E.lv.resize(nlevels);
-    if (hipStreamCreateWithFlags(&E.st, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreate(&E.ev0) != hipSuccess || hipEventCreate(&E.ev1) != hipSuccess) {
-        delete h;
-        set_error("hipStreamCreate / hipEventCreate failed");
-        return AMG_ENODEV;
-    }
-    *out = h;
-    return 0;
+    return open_handle(nlevels, device, out);
 }
 
-void amg_hierx_destroy(amg_hierx *h)
-{
-    if (!h) return;
-    hipSetDevice(h->e.device);
-    hipDeviceSynchronize();
-    delete h;
-}
+void amg_hierx_destroy(amg_hierx *h) { close_handle(h); }
 
 int amg_hierx_set_matrix(amg_hierx *h, int lvl, int which, int fmt, int nrows, int ncols, int R, int C,
                          const int *Ap, const int *Aj, const void *Ax)
 {
-    ENTERX(h);
-    UNSEALED(h);
+    ENTER(h);
+    UNSEALED(h, FINALIZE);
     C128 &E = h->e;
-    if (lvl < 0 || lvl >= E.nlev || which < 0 || which > 2 || (which > 0 && lvl == E.nlev - 1)) {
-        set_error("bad level / operator slot");
-        return AMG_EINVAL;
-    }
-    XLevel<c128> &L = E.lv[lvl];
-    XMat<c128> &M = which == 0 ? L.A : which == 1 ? L.P : L.R;
-    if (M.set) { set_error("operator already set"); return AMG_ESTATE; }
-    return M.load(E.pool, fmt, nrows, ncols, fmt ? R : 1, fmt ? C : 1, Ap, Aj, Ax);
+    XMat<c128> *M = operator_slot(E, lvl, which);
+    if (!M) return AMG_EINVAL;
+    if (M->set) { set_error("operator already set"); return AMG_ESTATE; }
+    return M->load(E.pool, fmt, nrows, ncols, fmt ? R : 1, fmt ? C : 1, Ap, Aj, Ax);
 }
 
 int amg_hierx_set_smoother(amg_hierx *h, int lvl, int which, const amg_smoother_desc_x *d)
 {
-    ENTERX(h);
-    UNSEALED(h);
+    ENTER(h);
+    UNSEALED(h, FINALIZE);
     CHK(set_smoother(h->e, lvl, which, d));
     if (which == 2) h->e.coarse = COARSE_SMOOTHER;
     return 0;
@@ -839,8 +682,8 @@ int amg_hierx_set_smoother(amg_hierx *h, int lvl, int which, const amg_smoother_
 int amg_hierx_set_block_matrix(amg_hierx *h, int lvl, int which, int nbrows, int bs, const int *Ap, const int *Aj,
                                const void *Ax)
 {
-    ENTERX(h);
-    UNSEALED(h);
+    ENTER(h);
+    UNSEALED(h, FINALIZE);
     C128 &E = h->e;
     if (lvl < 0 || lvl >= E.nlev || which < 0 || which > 2 || bs < 1 || nbrows < 0) { set_error("bad slot"); return AMG_EINVAL; }
     XSmoother<c128> &s = which == 2 ? E.csm : E.lv[lvl].sm[which];
@@ -854,21 +697,15 @@ int amg_hierx_set_block_matrix(amg_hierx *h, int lvl, int which, int nbrows, int
 
 int amg_hierx_set_coarse_dense(amg_hierx *h, const void *M, int n)
 {
-    ENTERX(h);
-    UNSEALED(h);
-    C128 &E = h->e;
-    if (n < 0 || (!M && n)) { set_error("bad dense operator"); return AMG_EINVAL; }
-    if (E.coarse != COARSE_NONE) { set_error("coarse solver already set"); return AMG_ESTATE; }
-    CHK(E.pool.upload(E.M, M, sizeof(c128) * (size_t)n * n));
-    E.nM = n;
-    E.coarse = COARSE_DENSE;
-    return 0;
+    ENTER(h);
+    UNSEALED(h, FINALIZE);
+    return set_coarse_dense(h->e, M, n, sizeof(c128));
 }
 
 int amg_hierx_set_coarse_callback(amg_hierx *h, amg_coarse_callback_x fn, void *user)
 {
-    ENTERX(h);
-    UNSEALED(h);
+    ENTER(h);
+    UNSEALED(h, FINALIZE);
     if (!fn) { set_error("null callback"); return AMG_EINVAL; }
     if (h->e.coarse != COARSE_NONE) { set_error("coarse solver already set"); return AMG_ESTATE; }
     h->e.cb = fn;
@@ -879,20 +716,20 @@ int amg_hierx_set_coarse_callback(amg_hierx *h, amg_coarse_callback_x fn, void *
 
 int amg_hierx_finalize(amg_hierx *h)
 {
-    ENTERX(h);
-    return finalize(h->e);
+    ENTER(h);
+    return finalize(h->e, FINALIZE, XSetup<c128>{h->e});
 }
 
 int amg_hierx_solve(amg_hierx *h, const void *b, void *x, double tol, int maxiter, int cyc, double *residuals,
                     int *nres, int flags)
 {
-    ENTERX(h);
+    ENTER(h);
     return solve(h->e, b, x, tol, maxiter, cyc, residuals, nres, flags);
 }
 
 int amg_hierx_cycle(amg_hierx *h, const void *b, void *x, int cyc, int flags)
 {
-    ENTERX(h);
+    ENTER(h);
     return cycle(h->e, b, x, cyc, flags);
 }
 

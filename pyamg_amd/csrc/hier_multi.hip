@@ -11,8 +11,7 @@
 // (the library builds with -ffp-contract=off), epilogues parenthesised as in relaxation.h / relaxation.py.  No
 // kernel mixes columns, so a column's bits do not depend on k, on its position or on its neighbours.  The residual
 // norm of a column is a two-stage reduction over a fixed grid: its tree depends on n only.
-#include "hier.hpp"
-#include "flat.hpp"
+#include "resident.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -32,7 +31,7 @@ constexpr int NORM_BLOCKS = 2048;   // partial sums of a norm: fixed, so the tre
 constexpr int NORM_WG = 256;
 constexpr int VEC_WG = 256;
 
-enum { COARSE_NONE = 0, COARSE_DENSE = 1, COARSE_SMOOTHER = 2 };
+constexpr char FINALIZE[] = "amg_hierm_finalize";
 // how a row is summed: from zero over all entries (products), from zero without the diagonal (jacobi, gauss_seidel),
 // or bsr_jacobi / bsr_gauss_seidel with 1 x 1 blocks: from b[i], every off-diagonal block's product (0 + a x)
 // subtracted in stored order
@@ -423,43 +422,7 @@ __global__ void __launch_bounds__(NORM_WG) norm_final_multi(const double *__rest
 }
 
 // ----------------------------------------------------------------------------------------------- host side
-int blocks_of(long n, int per) { return (int)((n + per - 1) / per); }
-
-int launched(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
-    return 0;
-}
-
 int width_of(int k) { return k <= 1 ? 1 : k <= 2 ? 2 : k <= 4 ? 4 : 8; }
-
-// Ap nondecreasing from 0, every column index in [0, ncols): no kernel can read outside its arrays
-int check_pattern(const int *Ap, int nrows, const int *Aj, int ncols)
-{
-    if (!Ap || Ap[0] != 0) { set_error("bad Ap"); return AMG_EINVAL; }
-    for (int i = 0; i < nrows; ++i)
-        if (Ap[i + 1] < Ap[i]) { set_error("Ap is not nondecreasing"); return AMG_EINVAL; }
-    for (long k = 0; k < Ap[nrows]; ++k)
-        if (Aj[k] < 0 || Aj[k] >= ncols) { set_error("column index out of range"); return AMG_EINVAL; }
-    return 0;
-}
-
-struct Pool {            // device buffers of one hierarchy, counted for device_bytes
-    long bytes = 0;
-    int alloc(DBuf &d, size_t n)
-    {
-        CHK(d.alloc(n));
-        bytes += (long)n;
-        return 0;
-    }
-    int upload(DBuf &d, const void *src, size_t n)
-    {
-        CHK(alloc(d, n));
-        if (n) AMG_HIP(hipMemcpy(d.p, src, n, hipMemcpyHostToDevice));
-        return 0;
-    }
-};
 
 // one operator: CSR, or BSR with 1 x 1 blocks (the same arrays; the flag selects the bsr_* rounding of the relaxations)
 struct MMat {
@@ -486,20 +449,6 @@ struct MMat {
     }
 };
 
-// dependency levels of a sweep over the rows of a pattern (rows in level order on the device)
-struct Sweep {
-    std::vector<int> lp;
-    DBuf rows;
-    int build(Pool &pool, int n, const std::vector<int> &Ap, const std::vector<int> &Aj, bool backward)
-    {
-        std::vector<int> tasks(n), order, rws(n);
-        for (int t = 0; t < n; ++t) tasks[t] = backward ? n - 1 - t : t;
-        CHK(build_levels(n, Ap.data(), Aj.data(), tasks.data(), n, lp, order));
-        for (int k = 0; k < n; ++k) rws[k] = tasks[order[k]];
-        return pool.upload(rows, rws.data(), sizeof(int) * (size_t)n);
-    }
-};
-
 struct MSmoother {
     bool set = false;
     int kind = AMG_SM_NONE, iterations = 1, sweep = 0;
@@ -514,29 +463,12 @@ struct MLevel {
     DBuf x, b, r, h1, h2, t;     // iterate, right-hand side, residual, polynomial ping-pong, jacobi / sor copy
 };
 
-struct Engine {
-    int device = 0, nlev = 0, kmax = 1, kpmax = 1;
-    bool finalized = false;
-    bool sealed = false;                  // finalize has run: the operators, smoothers and coarse solver are fixed
-    hipStream_t st = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+struct Engine : Core {
+    int kmax = 1, kpmax = 1;
     std::vector<MLevel> lv;
-    int coarse = COARSE_NONE;
     MSmoother csm;                        // relaxation-named coarse solver
-    DBuf M;
-    int nM = 0;
     DBuf xs;                              // the iterates of the columns that stopped
-    DBuf part, res;
-    int nres_cap = 0;
     std::vector<double> hb, hx;           // packing of k != KP columns
-    double last_ms = 0.0;
-    Pool pool;
-    ~Engine()
-    {
-        if (ev0) hipEventDestroy(ev0);
-        if (ev1) hipEventDestroy(ev1);
-        if (st) hipStreamDestroy(st);
-    }
 };
 
 // operators of up to DIRECT_MAX_ROW entries per row on average skip the LDS stage (AMG_MULTI_DIRECT=0: never; A/B runs)
@@ -667,41 +599,26 @@ int coarse_solve(Engine &E, double *x, const double *b)
     return AMG_ESTATE;
 }
 
-// multilevel.py:473-548 on level l (V, W, F); x_l and b_l live in the level's vectors
+// the steps of a cycle (cycle_level, resident.hpp) on the levels' vectors, KP columns wide
 template <int KP>
-int cycle_level(Engine &E, int l, int cyc)
-{
-    MLevel &L = E.lv[l], &Lc = E.lv[l + 1];
-    double *x = L.x.d(), *b = L.b.d(), *r = L.r.d();
-    double *xc = Lc.x.d(), *bc = Lc.b.d();
-    CHK(relax<KP>(E, L, L.sm[0], x, b));
-    CHK((apply_rows<KP, ROW_SUM>(L.A, (const double *)x, nullptr, EpiResid<Shape<KP>::CW>{b, r}, E.st)));      // residual = b - A x
-    CHK((apply_rows<KP, ROW_SUM>(L.R, (const double *)r, nullptr, EpiStore<Shape<KP>::CW>{bc}, E.st)));        // coarse_b = R residual
-    if (Lc.A.nrows) AMG_HIP(hipMemsetAsync(xc, 0, sizeof(double) * (size_t)Lc.A.nrows * KP, E.st));
-    if (l == E.nlev - 2) {
-        CHK(coarse_solve<KP>(E, xc, bc));
-    } else if (cyc == AMG_CYCLE_V) {
-        CHK(cycle_level<KP>(E, l + 1, AMG_CYCLE_V));
-    } else if (cyc == AMG_CYCLE_W) {
-        CHK(cycle_level<KP>(E, l + 1, AMG_CYCLE_W));
-        CHK(cycle_level<KP>(E, l + 1, AMG_CYCLE_W));
-    } else {
-        CHK(cycle_level<KP>(E, l + 1, AMG_CYCLE_F));
-        CHK(cycle_level<KP>(E, l + 1, AMG_CYCLE_V));
+struct MCycle {
+    static constexpr int CW = Shape<KP>::CW;
+    Engine &E;
+    double *x(int l) const { return E.lv[l].x.d(); }
+    double *b(int l) const { return E.lv[l].b.d(); }
+    double *r(int l) const { return E.lv[l].r.d(); }
+    template <class Epi> int rows(const MMat &A, const double *v, Epi epi) { return apply_rows<KP, ROW_SUM>(A, v, nullptr, epi, E.st); }
+    int relax(int l, int w) { return ::relax<KP>(E, E.lv[l], E.lv[l].sm[w], x(l), b(l)); }
+    int residual(int l) { return rows(E.lv[l].A, x(l), EpiResid<CW>{b(l), r(l)}); }
+    int restrict_residual(int l) { return rows(E.lv[l].R, r(l), EpiStore<CW>{b(l + 1)}); }
+    int zero_x(int l)
+    {
+        if (E.lv[l].A.nrows) AMG_HIP(hipMemsetAsync(x(l), 0, sizeof(double) * (size_t)E.lv[l].A.nrows * KP, E.st));
+        return 0;
     }
-    CHK((apply_rows<KP, ROW_SUM>(L.P, (const double *)xc, nullptr, EpiAdd<Shape<KP>::CW>{x}, E.st)));          // x += P coarse_x
-    return relax<KP>(E, L, L.sm[1], x, b);
-}
-
-template <int KP>
-int one_cycle(Engine &E, int cyc)
-{
-    if (E.nlev == 1) {                      // multilevel.py:455-457: x = coarse_solver(A, b)
-        MLevel &L = E.lv[0];
-        return coarse_solve<KP>(E, L.x.d(), L.b.d());
-    }
-    return cycle_level<KP>(E, 0, cyc);
-}
+    int coarse_solve() { return ::coarse_solve<KP>(E, x(E.nlev - 1), b(E.nlev - 1)); }
+    int prolong_add(int l) { return rows(E.lv[l].P, x(l + 1), EpiAdd<CW>{x(l)}); }
+};
 
 // out[0..KP) = the columns' norms
 template <int KP>
@@ -717,9 +634,8 @@ int device_norm(Engine &E, const double *v, long n, double *out)
 template <int KP>
 int residual_norm(Engine &E, double *slot)
 {
-    MLevel &L = E.lv[0];
-    CHK((apply_rows<KP, ROW_SUM>(L.A, (const double *)L.x.d(), nullptr, EpiResid<Shape<KP>::CW>{L.b.d(), L.r.d()}, E.st)));
-    return device_norm<KP>(E, L.r.d(), L.A.nrows, slot);
+    CHK(MCycle<KP>{E}.residual(0));
+    return device_norm<KP>(E, E.lv[0].r.d(), E.lv[0].A.nrows, slot);
 }
 
 // host (n, k) row-major -> device [n][KP], padding columns zero
@@ -808,63 +724,54 @@ int solve_kp(Engine &E, int k, const double *B, double *X, double tol, int maxit
         for (int j = 0; j < k; ++j)
             if (!active[j]) { CHK(snapshot<KP>(E, j)); snapped = true; }
     int it = 1;
-    AMG_HIP(hipEventRecord(E.ev0, E.st));
-    while (it <= maxiter && nactive > 0) {
-        CHK(one_cycle<KP>(E, cyc));
-        CHK(residual_norm<KP>(E, rd + (long)it * KMAX));
-        if (!fixed) {
-            AMG_HIP(hipMemcpyAsync(cur, rd + (long)it * KMAX, sizeof(double) * KP, hipMemcpyDeviceToHost, E.st));
-            AMG_HIP(hipStreamSynchronize(E.st));
-            for (int j = 0; j < k; ++j) {
-                if (!active[j]) continue;
-                residuals[(size_t)j * stride + it] = cur[j];
-                nres[j] = it + 1;
-                if (!(cur[j] > tolj[j])) {
-                    active[j] = false;
-                    --nactive;
-                    // the other columns go on: keep this one's iterate (nothing follows when it was the last)
-                    if (nactive > 0 && it < maxiter) { CHK(snapshot<KP>(E, j)); snapped = true; }
+    auto run = [&]() -> int {
+        while (it <= maxiter && nactive > 0) {
+            CHK(one_cycle(MCycle<KP>{E}, E.nlev, cyc));
+            CHK(residual_norm<KP>(E, rd + (long)it * KMAX));
+            if (!fixed) {
+                AMG_HIP(hipMemcpyAsync(cur, rd + (long)it * KMAX, sizeof(double) * KP, hipMemcpyDeviceToHost, E.st));
+                AMG_HIP(hipStreamSynchronize(E.st));
+                for (int j = 0; j < k; ++j) {
+                    if (!active[j]) continue;
+                    residuals[(size_t)j * stride + it] = cur[j];
+                    nres[j] = it + 1;
+                    if (!(cur[j] > tolj[j])) {
+                        active[j] = false;
+                        --nactive;
+                        // the other columns go on: keep this one's iterate (nothing follows when it was the last)
+                        if (nactive > 0 && it < maxiter) { CHK(snapshot<KP>(E, j)); snapped = true; }
+                    }
                 }
             }
+            ++it;
         }
-        ++it;
-    }
-    AMG_HIP(hipEventRecord(E.ev1, E.st));
-    if (fixed && it > 1) {
-        std::vector<double> all((size_t)it * KMAX);
-        AMG_HIP(hipMemcpyAsync(all.data(), rd, sizeof(double) * all.size(), hipMemcpyDeviceToHost, E.st));
-        AMG_HIP(hipStreamSynchronize(E.st));
-        for (int j = 0; j < k; ++j) {
-            for (int q = 1; q < it; ++q) residuals[(size_t)j * stride + q] = all[(size_t)q * KMAX + j];
-            nres[j] = it;
+        return 0;
+    };
+    auto store = [&]() -> int {
+        if (fixed && it > 1) {
+            std::vector<double> all((size_t)it * KMAX);
+            AMG_HIP(hipMemcpyAsync(all.data(), rd, sizeof(double) * all.size(), hipMemcpyDeviceToHost, E.st));
+            AMG_HIP(hipStreamSynchronize(E.st));
+            for (int j = 0; j < k; ++j) {
+                for (int q = 1; q < it; ++q) residuals[(size_t)j * stride + q] = all[(size_t)q * KMAX + j];
+                nres[j] = it;
+            }
         }
-    }
-    if (snapped) {
+        if (!snapped) return store_columns<KP>(E, L0.x.d(), k, X);
         // columns that ran to the end (or stopped in the last cycle run) hold their result in x
         for (int j = 0; j < k; ++j)
             if (nres[j] == it) CHK(snapshot<KP>(E, j));
-        CHK(store_columns<KP>(E, E.xs.d(), k, X));
-    } else {
-        CHK(store_columns<KP>(E, L0.x.d(), k, X));
-    }
-    float ms = 0.f;
-    AMG_HIP(hipEventElapsedTime(&ms, E.ev0, E.ev1));
-    E.last_ms = ms;
-    return 0;
+        return store_columns<KP>(E, E.xs.d(), k, X);
+    };
+    return E.timed(run, store);
 }
 
 template <int KP>
 int cycle_kp(Engine &E, int k, const double *B, double *X, int cyc, int flags)
 {
     CHK(load_vectors<KP>(E, k, B, X, flags));
-    AMG_HIP(hipEventRecord(E.ev0, E.st));
-    CHK(one_cycle<KP>(E, cyc));
-    AMG_HIP(hipEventRecord(E.ev1, E.st));
-    CHK(store_columns<KP>(E, E.lv[0].x.d(), k, X));
-    float ms = 0.f;
-    AMG_HIP(hipEventElapsedTime(&ms, E.ev0, E.ev1));
-    E.last_ms = ms;
-    return 0;
+    return E.timed([&] { return one_cycle(MCycle<KP>{E}, E.nlev, cyc); },
+                   [&] { return store_columns<KP>(E, E.lv[0].x.d(), k, X); });
 }
 
 int check_call(Engine &E, int k, const void *B, const void *X, int cyc)
@@ -889,18 +796,11 @@ int build_smoother(Engine &E, MLevel &L, MSmoother &s)
 
 int set_smoother(Engine &E, int lvl, int which, const amg_smoother_desc *d)
 {
-    if (lvl < 0 || lvl >= E.nlev || which < 0 || which > 2 || !d) { set_error("bad smoother slot"); return AMG_EINVAL; }
-    if (which == 2 && lvl != E.nlev - 1) { set_error("the coarse smoother belongs to the last level"); return AMG_EINVAL; }
-    if (which < 2 && lvl == E.nlev - 1) { set_error("the last level has no pre/post smoother"); return AMG_EINVAL; }
-    if (d->kind < AMG_SM_NONE || d->kind > AMG_SM_POLYNOMIAL) {
-        set_error("smoother kind " + std::to_string(d->kind) + " has no implementation for several right-hand sides");
-        return AMG_ENOTIMPL;
-    }
-    MSmoother &s = which == 2 ? E.csm : E.lv[lvl].sm[which];
-    if (s.set) { set_error("smoother already set"); return AMG_ESTATE; }
-    if (which == 2 && E.coarse != COARSE_NONE) { set_error("coarse solver already set"); return AMG_ESTATE; }
+    MSmoother *slot = nullptr;
+    CHK(smoother_slot(E, lvl, which, d, AMG_SM_POLYNOMIAL, "for several right-hand sides", slot));
+    MSmoother &s = *slot;
     if (d->kind != AMG_SM_NONE) {
-        if (d->iterations < 0 || d->sweep < 0 || d->sweep > 2) { set_error("bad iterations / sweep"); return AMG_EINVAL; }
+        CHK(check_sweeps(d));
         if (d->kind == AMG_SM_POLYNOMIAL && (d->ncoef < 1 || !d->coef)) { set_error("polynomial: no coefficients"); return AMG_EINVAL; }
     }
     s.set = true;
@@ -913,30 +813,20 @@ int set_smoother(Engine &E, int lvl, int which, const amg_smoother_desc *d)
     return 0;
 }
 
-int finalize(Engine &E)
-{
-    if (E.sealed) {
-        if (E.finalized) return 0;
-        set_error("an earlier amg_hierm_finalize failed; build a new hierarchy");
-        return AMG_ESTATE;
+// what finalize (resident.hpp) leaves to this engine
+struct MSetup {
+    Engine &E;
+    int square(const MMat &A)
+    {
+        if (A.nrows != A.ncols) { set_error("A must be square"); return AMG_EINVAL; }
+        return 0;
     }
-    E.sealed = true;                      // the schedules below consume the host patterns: no setter may follow
-    for (int l = 0; l < E.nlev; ++l) {
+    int build_smoother(MLevel &L, MSmoother &s) { return ::build_smoother(E, L, s); }
+    // work vectors by what the level's smoothers use: the polynomial ping-pong, the copy jacobi and sor keep
+    int level_vectors(int l)
+    {
         MLevel &L = E.lv[l];
-        if (!L.A.set) { set_error("level " + std::to_string(l) + ": A missing"); return AMG_ESTATE; }
-        if (L.A.nrows != L.A.ncols) { set_error("A must be square"); return AMG_EINVAL; }
-        const int n = L.A.nrows;
-        if (l < E.nlev - 1) {
-            const MMat &An = E.lv[l + 1].A;
-            if (!L.P.set || !L.R.set) { set_error("level " + std::to_string(l) + ": P or R missing"); return AMG_ESTATE; }
-            if (L.P.nrows != n || L.P.ncols != An.nrows || L.R.nrows != An.nrows || L.R.ncols != n) {
-                set_error("level " + std::to_string(l) + ": P / R shapes do not match A");
-                return AMG_EINVAL;
-            }
-            for (int w = 0; w < 2; ++w) CHK(build_smoother(E, L, L.sm[w]));
-        }
-        // work vectors by what the level's smoothers use: the polynomial ping-pong, the copy jacobi and sor keep
-        const size_t vb = sizeof(double) * (size_t)n * E.kpmax;
+        const size_t vb = sizeof(double) * (size_t)L.A.nrows * E.kpmax;
         bool poly = false, copy = false;
         auto uses = [&](const MSmoother &s) {
             poly = poly || s.kind == AMG_SM_POLYNOMIAL;
@@ -948,33 +838,14 @@ int finalize(Engine &E)
         for (DBuf *v : {&L.x, &L.b, &L.r}) CHK(E.pool.alloc(*v, vb));
         if (poly) for (DBuf *v : {&L.h1, &L.h2}) CHK(E.pool.alloc(*v, vb));
         if (copy) CHK(E.pool.alloc(L.t, vb));
+        return 0;
     }
-    MLevel &Lc = E.lv[E.nlev - 1];
-    if (E.coarse == COARSE_SMOOTHER) CHK(build_smoother(E, Lc, E.csm));
-    if (E.coarse == COARSE_DENSE && E.nM != Lc.A.nrows) { set_error("dense coarse operator has the wrong size"); return AMG_EINVAL; }
-    CHK(E.pool.alloc(E.xs, sizeof(double) * (size_t)E.lv[0].A.nrows * E.kpmax));
-    CHK(E.pool.alloc(E.part, sizeof(double) * NORM_BLOCKS * KMAX));
-    for (int l = 0; l < E.nlev; ++l) {             // the patterns served the schedules
-        for (MMat *M : {&E.lv[l].A, &E.lv[l].P, &E.lv[l].R}) {
-            std::vector<int>().swap(M->hAp);
-            std::vector<int>().swap(M->hAj);
-        }
+    int finish()
+    {
+        CHK(E.pool.alloc(E.xs, sizeof(double) * (size_t)E.lv[0].A.nrows * E.kpmax));
+        return E.pool.alloc(E.part, sizeof(double) * NORM_BLOCKS * KMAX);
     }
-    E.finalized = true;
-    return 0;
-}
-
-int reserve_history(Engine &E, int maxiter)
-{
-    if (E.nres_cap >= maxiter + 2) return 0;
-    E.pool.bytes -= (long)sizeof(double) * E.nres_cap * KMAX;
-    if (E.res.p) AMG_HIP(hipFree(E.res.p));
-    E.res.p = nullptr;
-    E.nres_cap = 0;
-    CHK(E.pool.alloc(E.res, sizeof(double) * (size_t)(maxiter + 2) * KMAX));
-    E.nres_cap = maxiter + 2;
-    return 0;
-}
+};
 
 }  // namespace
 
@@ -982,15 +853,6 @@ struct amg_hierm {
     Engine e;
 };
 
-#define ENTERM(h)                                                       \
-    if (!(h)) { amg::set_error("null hierarchy"); return AMG_EINVAL; }  \
-    AMG_HIP(hipSetDevice((h)->e.device))
-// setters: only before amg_hierm_finalize
-#define UNSEALEDM(h)                                                                                      \
-    if ((h)->e.sealed) {                                                                                  \
-        amg::set_error("hierarchy already finalised: operators and solvers are set before amg_hierm_finalize"); \
-        return AMG_ESTATE;                                                                                \
-    }
 #define BY_WIDTH(kp, fn, ...)                 \
     switch (kp) {                             \
     case 1: return fn<1>(__VA_ARGS__);        \
@@ -1007,79 +869,50 @@ int amg_hierm_create(int nlevels, int device, int kmax, amg_hierm **out)
     *out = nullptr;
     if (nlevels < 1) { set_error("nlevels < 1"); return AMG_EINVAL; }
     if (kmax < 1 || kmax > KMAX) { set_error("kmax must be in 1 .. 8 (more columns run in groups)"); return AMG_EINVAL; }
-    CHK(require_device());
-    AMG_HIP(hipSetDevice(device));
-    amg_hierm *h = new amg_hierm();
-    Engine &E = h->e;
-    E.device = device;
-    E.nlev = nlevels;
-    E.kmax = kmax;
-    E.kpmax = width_of(kmax);
-    E.lv.resize(nlevels);
-    if (hipStreamCreateWithFlags(&E.st, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreate(&E.ev0) != hipSuccess || hipEventCreate(&E.ev1) != hipSuccess) {
-        delete h;
-        set_error("hipStreamCreate / hipEventCreate failed");
-        return AMG_ENODEV;
-    }
-    *out = h;
+    CHK(open_handle(nlevels, device, out));
+    (*out)->e.kmax = kmax;
+    (*out)->e.kpmax = width_of(kmax);
     return 0;
 }
 
-void amg_hierm_destroy(amg_hierm *h)
-{
-    if (!h) return;
-    hipSetDevice(h->e.device);
-    hipDeviceSynchronize();
-    delete h;
-}
+void amg_hierm_destroy(amg_hierm *h) { close_handle(h); }
 
 int amg_hierm_set_matrix(amg_hierm *h, int lvl, int which, int fmt, int nrows, int ncols, int R, int C,
                          const int *Ap, const int *Aj, const double *Ax)
 {
-    ENTERM(h);
-    UNSEALEDM(h);
+    ENTER(h);
+    UNSEALED(h, FINALIZE);
     Engine &E = h->e;
-    if (lvl < 0 || lvl >= E.nlev || which < 0 || which > 2 || (which > 0 && lvl == E.nlev - 1)) {
-        set_error("bad level / operator slot");
-        return AMG_EINVAL;
-    }
+    MMat *M = operator_slot(E, lvl, which);
+    if (!M) return AMG_EINVAL;
     if (fmt != AMG_FMT_CSR && fmt != AMG_FMT_BSR) { set_error("fmt must be 0 (CSR) or 1 (BSR)"); return AMG_EINVAL; }
     if (fmt == AMG_FMT_BSR && (R != 1 || C != 1)) {
         set_error("several right-hand sides: BSR operators with 1 x 1 blocks only");
         return AMG_ENOTIMPL;
     }
-    MLevel &L = E.lv[lvl];
-    MMat &M = which == 0 ? L.A : which == 1 ? L.P : L.R;
-    if (M.set) { set_error("operator already set"); return AMG_ESTATE; }
-    return M.load(E.pool, fmt, nrows, ncols, Ap, Aj, Ax);
+    if (M->set) { set_error("operator already set"); return AMG_ESTATE; }
+    return M->load(E.pool, fmt, nrows, ncols, Ap, Aj, Ax);
 }
 
 int amg_hierm_set_smoother(amg_hierm *h, int lvl, int which, const amg_smoother_desc *d)
 {
-    ENTERM(h);
-    UNSEALEDM(h);
+    ENTER(h);
+    UNSEALED(h, FINALIZE);
     if (which != AMG_PRE && which != AMG_POST) { set_error("which must be AMG_PRE or AMG_POST"); return AMG_EINVAL; }
     return set_smoother(h->e, lvl, which, d);
 }
 
 int amg_hierm_set_coarse_dense(amg_hierm *h, const double *M, int n)
 {
-    ENTERM(h);
-    UNSEALEDM(h);
-    Engine &E = h->e;
-    if (n < 0 || (!M && n)) { set_error("bad dense operator"); return AMG_EINVAL; }
-    if (E.coarse != COARSE_NONE) { set_error("coarse solver already set"); return AMG_ESTATE; }
-    CHK(E.pool.upload(E.M, M, sizeof(double) * (size_t)n * n));
-    E.nM = n;
-    E.coarse = COARSE_DENSE;
-    return 0;
+    ENTER(h);
+    UNSEALED(h, FINALIZE);
+    return set_coarse_dense(h->e, M, n, sizeof(double));
 }
 
 int amg_hierm_set_coarse_smoother(amg_hierm *h, const amg_smoother_desc *d)
 {
-    ENTERM(h);
-    UNSEALEDM(h);
+    ENTER(h);
+    UNSEALED(h, FINALIZE);
     CHK(set_smoother(h->e, h->e.nlev - 1, 2, d));
     h->e.coarse = COARSE_SMOOTHER;
     return 0;
@@ -1087,24 +920,24 @@ int amg_hierm_set_coarse_smoother(amg_hierm *h, const amg_smoother_desc *d)
 
 int amg_hierm_finalize(amg_hierm *h)
 {
-    ENTERM(h);
-    return finalize(h->e);
+    ENTER(h);
+    return finalize(h->e, FINALIZE, MSetup{h->e});
 }
 
 int amg_hierm_solve(amg_hierm *h, int k, const double *B, double *X, double tol, int maxiter, int cyc,
                     double *residuals, int *nres, int flags)
 {
-    ENTERM(h);
+    ENTER(h);
     Engine &E = h->e;
     CHK(check_call(E, k, B, X, cyc));
     if (!residuals || !nres || maxiter < 0) { set_error("bad solve arguments"); return AMG_EINVAL; }
-    CHK(reserve_history(E, maxiter));
+    CHK(E.reserve_history(maxiter, KMAX));
     BY_WIDTH(width_of(k), solve_kp, E, k, B, X, tol, maxiter, cyc, residuals, nres, flags)
 }
 
 int amg_hierm_cycle(amg_hierm *h, int k, const double *B, double *X, int cyc, int flags)
 {
-    ENTERM(h);
+    ENTER(h);
     Engine &E = h->e;
     CHK(check_call(E, k, B, X, cyc));
     BY_WIDTH(width_of(k), cycle_kp, E, k, B, X, cyc, flags)

@@ -1,6 +1,7 @@
 // Value-type templated relaxation kernels shared by the flat float32 / complex64 / complex128 table
-// (typed.hip) and the complex128 resident hierarchy (hier_c128.hip).  Every expression goes through the
-// scalar rules of scalar.hpp, so a kernel gives the reference's bits whichever file launches it.
+// (typed.hip) and the complex128 resident hierarchy (hier_c128.hip, on the host scaffold of resident.hpp).
+// Every expression goes through the scalar rules of scalar.hpp, so a kernel gives the reference's bits
+// whichever file launches it.
 #pragma once
 #include <hip/hip_runtime.h>
 

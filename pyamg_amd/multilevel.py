@@ -316,9 +316,103 @@ def _c128(a):
     return np.ascontiguousarray(np.ravel(a), dtype=np.complex128)
 
 
-class _DeviceHierarchyC128(object):
+class _ResidentHierarchy(object):
+    """What the mirrors of the two plain resident engines share: the handle's lifetime, the descriptor of a smoother
+    and the order in which a hierarchy goes into the engine.  A mirror names its value type, its smoother kinds and
+    its refusals, binds the engine's entries that this base calls (self._entry, before _open), and sets a smoother
+    (_set_smoother(lvl, which, fn, A); which = 2: the coarse solver of the last level; A: the level's operator, for
+    a smoother that needs it in another form) and every other form of coarse solver it has (_COARSE)."""
+    _DTYPE = None           # of the operators' values
+    _KIND = None            # smoother name -> the engine's kind
+    _NO_SMOOTHER = None     # the refusal of any other smoother (% its name)
+    _NO_COARSE = None       # the refusal of a coarse solver form that is not in _COARSE (% the solver's name)
+    _COARSE = None          # form of _CoarseSolver.device_form -> setter(self, payload, Ac); Ac: the coarsest operator
+
+    def _open(self, ml, create, coarse=None):
+        """create(byref(h)) makes the handle; the hierarchy is then built into it (coarse: what check_levels returned,
+        when it has run), and the handle is closed again if that fails"""
+        self._keep = []
+        h = _lib.C.c_void_p()
+        _lib.check(create(_lib.C.byref(h)))
+        self.h = h.value
+        try:
+            self._build(ml, coarse)
+        except Exception:
+            self.close()
+            raise
+        self._keep = []
+
+    @classmethod
+    def _desc_of(cls, lvl, fn):
+        desc = getattr(fn, "desc", None)
+        if fn is not None and desc is None:
+            raise NotImplementedError(
+                "level %d: smoother %r carries no device descriptor; use pyamg_amd.smoothing."
+                "change_smoothers with one of the device smoothers" % (lvl, fn))
+        name = None if desc is None else desc.get("name")
+        if name not in cls._KIND:
+            raise NotImplementedError(cls._NO_SMOOTHER % (name,))
+        return desc
+
+    @staticmethod
+    def _pattern(M):
+        """a BSR operator as it is, any other as CSR: (fmt, M, indptr, indices), the index arrays as C ints"""
+        fmt = 1 if sparse.isspmatrix_bsr(M) else 0
+        if not fmt:
+            M = sparse.csr_matrix(M)
+        return fmt, M, np.ascontiguousarray(M.indptr, dtype=np.intc), np.ascontiguousarray(M.indices, dtype=np.intc)
+
+    def _set_matrix(self, lvl, which, M):
+        fmt, M, Ap, Aj = self._pattern(M)
+        R, C = M.blocksize if fmt else (1, 1)
+        # a real P / R of a complex hierarchy: astype(complex128), as scipy converts it inside a mixed product
+        data = np.ascontiguousarray(np.ravel(M.data), dtype=self._DTYPE)
+        _lib.check(self._entry["set_matrix"](self.h, lvl, which, fmt, M.shape[0], M.shape[1], R, C,
+                                          Ap.ctypes.data, Aj.ctypes.data, data.ctypes.data))
+
+    def _build(self, ml, coarse=None):
+        levels = ml.levels
+        kind, payload = self.check_levels(ml) if coarse is None else coarse
+        for i, lvl in enumerate(levels):
+            self._set_matrix(i, 0, lvl.A)
+            if i < len(levels) - 1:
+                self._set_matrix(i, 1, lvl.P)
+                self._set_matrix(i, 2, lvl.R)
+                self._set_smoother(i, 0, getattr(lvl, "presmoother", None), lvl.A)
+                self._set_smoother(i, 1, getattr(lvl, "postsmoother", None), lvl.A)
+        if kind == "smoother":
+            self._set_smoother(len(levels) - 1, 2, payload, levels[-1].A)
+        elif kind != "none":
+            if kind not in self._COARSE:
+                raise NotImplementedError(self._NO_COARSE % ml.coarse_solver.name())
+            self._COARSE[kind](self, payload, levels[-1].A)
+        _lib.check(self._entry["finalize"](self.h))
+
+    def last_solve_ms(self):
+        return self._entry["last_solve_ms"](self.h)
+
+    def device_bytes(self):
+        return self._entry["device_bytes"](self.h)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._entry["destroy"](self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _DeviceHierarchyC128(_ResidentHierarchy):
     """A complex128 hierarchy in HBM: an amg_hierx handle (include/amgcore_hip.h section 5).  Plain CSR / BSR
     operators, eager launches; the cycle gives the reference's bits."""
+
+    _DTYPE, _KIND = np.complex128, _C128_KIND
+    _NO_SMOOTHER = "smoother %r has no complex128 device implementation"
+    _NO_COARSE = "coarse solver %s has no device implementation"
 
     def __init__(self, ml, device=0):
         L = _lib.lib()
@@ -326,16 +420,10 @@ class _DeviceHierarchyC128(object):
         self.n = ml.levels[0].A.shape[0]
         self._callbacks = []
         self._callback_error = None
-        self._keep = []
-        h = _lib.C.c_void_p()
-        _lib.check(L.amg_hierx_create(_lib.AMG_VALUE_C128, len(ml.levels), int(device), _lib.C.byref(h)))
-        self.h = h.value
-        try:
-            self._build(ml)
-        except Exception:
-            self.close()
-            raise
-        self._keep = []
+        self._entry = {"set_matrix": L.amg_hierx_set_matrix, "finalize": L.amg_hierx_finalize,
+                       "destroy": L.amg_hierx_destroy, "last_solve_ms": L.amg_hierx_last_solve_ms,
+                       "device_bytes": L.amg_hierx_device_bytes}
+        self._open(ml, lambda h: L.amg_hierx_create(_lib.AMG_VALUE_C128, len(ml.levels), int(device), h))
 
     @staticmethod
     def check_levels(ml):
@@ -360,30 +448,6 @@ class _DeviceHierarchyC128(object):
         if kind == "smoother":
             _DeviceHierarchyC128._desc_of(len(ml.levels) - 1, payload)
         return kind, payload
-
-    @staticmethod
-    def _desc_of(lvl, fn):
-        desc = getattr(fn, "desc", None)
-        if fn is not None and desc is None:
-            raise NotImplementedError(
-                "level %d: smoother %r carries no device descriptor; use pyamg_amd.smoothing."
-                "change_smoothers with one of the device smoothers" % (lvl, fn))
-        name = None if desc is None else desc.get("name")
-        if name not in _C128_KIND:
-            raise NotImplementedError("smoother %r has no complex128 device implementation" % (name,))
-        return desc
-
-    def _set_matrix(self, lvl, which, M):
-        if sparse.isspmatrix_bsr(M):
-            fmt, (R, C) = 1, M.blocksize
-        else:
-            M = sparse.csr_matrix(M)
-            fmt, R, C = 0, 1, 1
-        data = _c128(M.data)       # a real P / R: astype(complex128), as scipy converts it inside a mixed product
-        Ap = np.ascontiguousarray(M.indptr, dtype=np.intc)
-        Aj = np.ascontiguousarray(M.indices, dtype=np.intc)
-        _lib.check(self.L.amg_hierx_set_matrix(self.h, lvl, which, fmt, M.shape[0], M.shape[1], R, C,
-                                               Ap.ctypes.data, Aj.ctypes.data, data.ctypes.data))
 
     def _set_smoother(self, lvl, which, fn, A):
         desc = self._desc_of(lvl, fn)
@@ -411,12 +475,14 @@ class _DeviceHierarchyC128(object):
             # relaxation.py:471,563: A.tobsr(blocksize=(bs, bs))
             bs = d.blocksize
             if not (sparse.isspmatrix_bsr(A) and A.blocksize == (bs, bs)):
-                Ab = A.tobsr(blocksize=(bs, bs))
-                Ap = np.ascontiguousarray(Ab.indptr, dtype=np.intc)
-                Aj = np.ascontiguousarray(Ab.indices, dtype=np.intc)
+                _, Ab, Ap, Aj = self._pattern(A.tobsr(blocksize=(bs, bs)))
                 Ax = _c128(Ab.data)
                 _lib.check(self.L.amg_hierx_set_block_matrix(self.h, lvl, which, Ab.shape[0] // bs, bs,
                                                              Ap.ctypes.data, Aj.ctypes.data, Ax.ctypes.data))
+
+    def _set_coarse_dense(self, M, Ac):         # Ac: only the callback form needs it
+        M = np.ascontiguousarray(M, dtype=np.complex128)
+        _lib.check(self.L.amg_hierx_set_coarse_dense(self.h, M.ctypes.data, M.shape[0]))
 
     def _set_coarse_callback(self, fn, Ac):
         owner = self
@@ -434,27 +500,7 @@ class _DeviceHierarchyC128(object):
         self._callbacks.append(cb)
         _lib.check(self.L.amg_hierx_set_coarse_callback(self.h, cb, None))
 
-    def _build(self, ml):
-        levels = ml.levels
-        kind, payload = self.check_levels(ml)
-        for i, lvl in enumerate(levels):
-            self._set_matrix(i, 0, lvl.A)
-            if i < len(levels) - 1:
-                self._set_matrix(i, 1, lvl.P)
-                self._set_matrix(i, 2, lvl.R)
-                self._set_smoother(i, 0, getattr(lvl, "presmoother", None), lvl.A)
-                self._set_smoother(i, 1, getattr(lvl, "postsmoother", None), lvl.A)
-        Ac = levels[-1].A
-        if kind == "dense":
-            M = np.ascontiguousarray(payload, dtype=np.complex128)
-            _lib.check(self.L.amg_hierx_set_coarse_dense(self.h, M.ctypes.data, M.shape[0]))
-        elif kind == "smoother":
-            self._set_smoother(len(levels) - 1, 2, payload, Ac)
-        elif kind == "callback":
-            self._set_coarse_callback(payload, Ac)
-        elif kind != "none":
-            raise NotImplementedError("coarse solver %s has no device implementation" % ml.coarse_solver.name())
-        _lib.check(self.L.amg_hierx_finalize(self.h))
+    _COARSE = {"dense": _set_coarse_dense, "callback": _set_coarse_callback}
 
     def _check(self, rc):
         err, self._callback_error = self._callback_error, None
@@ -473,23 +519,6 @@ class _DeviceHierarchyC128(object):
     def cycle(self, b, x, cycle, x0_zero=False):
         self._check(self.L.amg_hierx_cycle(self.h, b.ctypes.data, x.ctypes.data, _CYCLE[cycle],
                                            _X0_ZERO if x0_zero else 0))
-
-    def last_solve_ms(self):
-        return self.L.amg_hierx_last_solve_ms(self.h)
-
-    def device_bytes(self):
-        return self.L.amg_hierx_device_bytes(self.h)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.amg_hierx_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 _MULTI_KIND = {None: 0, "None": 0, "jacobi": 1, "gauss_seidel": 2, "sor": 3, "polynomial": 4}
@@ -543,10 +572,15 @@ def _batched_cycle_pays(ml, k):
     return False
 
 
-class _DeviceHierarchyMulti(object):
+class _DeviceHierarchyMulti(_ResidentHierarchy):
     """A float64 hierarchy in HBM for several right-hand sides at once: an amg_hierm handle (include/amgcore_hip.h
     section 6).  Plain CSR operators, eager launches; per column the cycle gives the bits of the one-vector engine
     (DESIGN.md section 9c)."""
+
+    _DTYPE, _KIND = np.float64, _MULTI_KIND
+    _NO_SMOOTHER = ("solve_many: smoother %r is not implemented (jacobi, gauss_seidel, sor, "
+                    "polynomial / chebyshev / richardson, None)")
+    _NO_COARSE = "coarse solver %s has no implementation for several right-hand sides"
 
     def __init__(self, ml, device=0, kmax=_MULTI_KMAX):
         L = _lib.lib()
@@ -554,17 +588,11 @@ class _DeviceHierarchyMulti(object):
         self.n = ml.levels[0].A.shape[0]
         self.kmax = int(kmax)
         self._cycles = 0
-        self._keep = []
-        kind, payload = self.check_levels(ml)
-        h = _lib.C.c_void_p()
-        _lib.check(L.amg_hierm_create(len(ml.levels), int(device), self.kmax, _lib.C.byref(h)))
-        self.h = h.value
-        try:
-            self._build(ml, kind, payload)
-        except Exception:
-            self.close()
-            raise
-        self._keep = []
+        coarse = self.check_levels(ml)
+        self._entry = {"set_matrix": L.amg_hierm_set_matrix, "finalize": L.amg_hierm_finalize,
+                       "destroy": L.amg_hierm_destroy, "last_solve_ms": L.amg_hierm_last_solve_ms,
+                       "device_bytes": L.amg_hierm_device_bytes}
+        self._open(ml, lambda h: L.amg_hierm_create(len(ml.levels), int(device), self.kmax, h), coarse)
 
     @staticmethod
     def check_levels(ml):
@@ -595,56 +623,18 @@ class _DeviceHierarchyMulti(object):
             _DeviceHierarchyMulti._desc_of(len(ml.levels) - 1, payload)
         return kind, payload
 
-    @staticmethod
-    def _desc_of(lvl, fn):
-        desc = getattr(fn, "desc", None)
-        if fn is not None and desc is None:
-            raise NotImplementedError(
-                "level %d: smoother %r carries no device descriptor; use pyamg_amd.smoothing."
-                "change_smoothers with one of the device smoothers" % (lvl, fn))
-        name = None if desc is None else desc.get("name")
-        if name not in _MULTI_KIND:
-            raise NotImplementedError("solve_many: smoother %r is not implemented (jacobi, gauss_seidel, sor, "
-                                      "polynomial / chebyshev / richardson, None)" % (name,))
-        return desc
-
-    def _set_matrix(self, lvl, which, M):
-        if sparse.isspmatrix_bsr(M):
-            fmt = 1
-        else:
-            M = sparse.csr_matrix(M)
-            fmt = 0
-        data = np.ascontiguousarray(np.ravel(M.data), dtype=np.float64)
-        Ap = np.ascontiguousarray(M.indptr, dtype=np.intc)
-        Aj = np.ascontiguousarray(M.indices, dtype=np.intc)
-        _lib.check(self.L.amg_hierm_set_matrix(self.h, lvl, which, fmt, M.shape[0], M.shape[1], 1, 1,
-                                               Ap.ctypes.data, Aj.ctypes.data, data.ctypes.data))
-
-    def _set_smoother(self, lvl, which, fn):
+    def _set_smoother(self, lvl, which, fn, A):     # A: unused, no smoother here needs another form of it
         d = _desc_struct(self._desc_of(lvl, fn), self._keep)
         if which == 2:
             _lib.check(self.L.amg_hierm_set_coarse_smoother(self.h, d))
         else:
             _lib.check(self.L.amg_hierm_set_smoother(self.h, lvl, which, d))
 
-    def _build(self, ml, kind, payload):
-        levels = ml.levels
-        for i, lvl in enumerate(levels):
-            self._set_matrix(i, 0, lvl.A)
-            if i < len(levels) - 1:
-                self._set_matrix(i, 1, lvl.P)
-                self._set_matrix(i, 2, lvl.R)
-                self._set_smoother(i, 0, getattr(lvl, "presmoother", None))
-                self._set_smoother(i, 1, getattr(lvl, "postsmoother", None))
-        if kind == "dense":
-            M = np.ascontiguousarray(payload, dtype=np.float64)
-            _lib.check(self.L.amg_hierm_set_coarse_dense(self.h, _lib.dp(M), M.shape[0]))
-        elif kind == "smoother":
-            self._set_smoother(len(levels) - 1, 2, payload)
-        elif kind != "none":
-            raise NotImplementedError("coarse solver %s has no implementation for several right-hand sides"
-                                      % ml.coarse_solver.name())
-        _lib.check(self.L.amg_hierm_finalize(self.h))
+    def _set_coarse_dense(self, M, Ac):             # Ac: unused, part of the setters' common signature
+        M = np.ascontiguousarray(M, dtype=np.float64)
+        _lib.check(self.L.amg_hierm_set_coarse_dense(self.h, _lib.dp(M), M.shape[0]))
+
+    _COARSE = {"dense": _set_coarse_dense}
 
     def solve(self, B, X, tol, maxiter, cycle, x0_zero=False, fixed=False):
         """B, X: C-contiguous float64 (n, k), k <= kmax; X is overwritten.  Returns the k residual histories."""
@@ -665,23 +655,6 @@ class _DeviceHierarchyMulti(object):
     def cycles_run(self):
         """batched cycles this mirror has run (one per cycle of a group of columns)"""
         return self._cycles
-
-    def last_solve_ms(self):
-        return self.L.amg_hierm_last_solve_ms(self.h)
-
-    def device_bytes(self):
-        return self.L.amg_hierm_device_bytes(self.h)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.amg_hierm_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _is_c128(ml):

@@ -150,3 +150,40 @@ def test_handle_is_sealed_after_finalize():
     assert dev.L.amg_hierx_finalize(dev.h) == 0
     x = ml.solve(g["b"], tol=g["meta"]["tol"], maxiter=g["meta"]["maxiter"])
     assert same(x, g["x"])
+
+
+def test_history_reservation_and_timing():
+    """the device history holds maxiter + 2 doubles, is counted in device_bytes and only grows; a history left by a
+    longer solve changes nothing in a shorter one; solve and cycle both time themselves"""
+    g = c128_cycle.load("gs_sym_V_shifted2d")
+    cyc = str(g["meta"]["cycle"]).upper()
+    ml = c128_cycle.build_ml(g)
+    ml.solve(g["b"], tol=0, maxiter=2, cycle=cyc)
+    dev = ml.device_hierarchy()
+    assert dev.last_solve_ms() > 0.0
+    small = dev.device_bytes()
+    ml.solve(g["b"], tol=0, maxiter=20, cycle=cyc)
+    grown = dev.device_bytes()
+    assert grown - small == 8 * (22 - 4)
+    res = []
+    x = ml.solve(g["b"], tol=0, maxiter=5, cycle=cyc, residuals=res)
+    assert dev.device_bytes() == grown
+    fresh = c128_cycle.build_ml(g)
+    res_fresh = []
+    x_fresh = fresh.solve(g["b"], tol=0, maxiter=5, cycle=cyc, residuals=res_fresh)
+    assert fresh.device_hierarchy().device_bytes() == small + 8 * (7 - 4)
+    assert same(x, x_fresh)
+    assert len(res) == len(res_fresh) == 6
+    assert np.array_equal(np.array(res).view(np.int64), np.array(res_fresh).view(np.int64))
+    # the cycle entry, as the first timed call of a handle (no solve has set the time before it); it gives what the
+    # preconditioner gives (one cycle of solve), which leaves the history as it was
+    Mb = ml.aspreconditioner(cycle=cyc) * g["b"]
+    assert dev.device_bytes() == grown
+    cold_ml = c128_cycle.build_ml(g)
+    cold = cold_ml.device_hierarchy()
+    assert cold.last_solve_ms() == 0.0
+    b1 = np.ascontiguousarray(g["b"], dtype=np.complex128)
+    x1 = np.zeros_like(b1)
+    cold.cycle(b1, x1, cyc, x0_zero=True)
+    assert cold.last_solve_ms() > 0.0
+    assert same(x1, Mb)

@@ -311,3 +311,29 @@ def test_poisson_96_cubed(smoother):
         assert len(res[j]) == len(r1) == 3
         golden_io.assert_history(res[j], r1, A, x1, B[:, j])
     assert ml.device_hierarchy_multi().cycles_run() == 2
+
+
+# ------------------------------------------------------------------------------------------ 8. bookkeeping
+def test_history_reservation_is_counted_and_only_grows():
+    """the device history holds maxiter + 2 slots of 8 doubles, is counted in device_bytes and only grows; a history
+    left by a longer solve changes nothing in a shorter one"""
+    g = golden_io.load_hier("rs_gs_2d")
+    ml = golden_io.build_ml(g)
+    B = rhs(g)
+    ml.solve_many(B, tol=0, maxiter=2)
+    dev = ml.device_hierarchy_multi()
+    small = dev.device_bytes()
+    ml.solve_many(B, tol=0, maxiter=20)
+    grown = dev.device_bytes()
+    assert grown - small == 8 * 8 * (22 - 4)
+    res = []
+    X = ml.solve_many(B, tol=0, maxiter=5, residuals=res)
+    assert dev.device_bytes() == grown
+    fresh = golden_io.build_ml(g)
+    res_fresh = []
+    X_fresh = fresh.solve_many(B, tol=0, maxiter=5, residuals=res_fresh)
+    assert fresh.device_hierarchy_multi().device_bytes() == small + 8 * 8 * (7 - 4)
+    assert same_bits(X, X_fresh)
+    for j in range(K):
+        assert len(res[j]) == len(res_fresh[j]) == (1 if j == 5 else 6)
+        assert same_bits(res[j], res_fresh[j])
