@@ -541,6 +541,21 @@ int amg_galerkin_fetch(amg_galerkin *g, int *Cj, double *Cx);
 /* C = A * B for host CSR operands through the same kernels (n_row x n_inner times n_inner x n_col) */
 int amg_csr_matmat_device(int n_row, int n_inner, int n_col, const int64_t *Ap, const int *Aj, const double *Ax,
                           const int64_t *Bp, const int *Bj, const double *Bx, int64_t *Cp, amg_galerkin **out);
+/* The same products for complex128 operands (values as interleaved (real, imaginary) pairs of doubles), scipy's complex
+ * csr_matmat bit for bit: each product is (ar br - ai bi, ar bi + ai br) without contraction, every output entry
+ * accumulates from zero in traversal order, part by part, and is dropped only when BOTH parts are zero of either sign
+ * (an entry whose real part cancels exactly keeps its zero as computed).  Device tables hold 2048 entries per wave
+ * (24 bytes each) where the float64 ones hold 4096; the overflow tiers are the same and end in AMG_EINVAL.
+ * amg_csr_matmat_device_c128: C = A * B.  amg_galerkin_device_c128: (R * A) * P from three host CSR operands
+ * (R n_coarse x n_fine, A n_fine x n_fine, P n_fine x n_coarse); R * A never leaves HBM.  Both fill Cp and leave the
+ * product in *out; amg_galerkin_fetch_c128 copies its columns and values to the host and releases it (the float64
+ * fetch refuses a complex product and the other way round). */
+int amg_csr_matmat_device_c128(int n_row, int n_inner, int n_col, const int64_t *Ap, const int *Aj, const void *Ax,
+                               const int64_t *Bp, const int *Bj, const void *Bx, int64_t *Cp, amg_galerkin **out);
+int amg_galerkin_device_c128(int n_fine, int n_coarse, const int64_t *Rp, const int *Rj, const void *Rx,
+                             const int64_t *Ap, const int *Aj, const void *Ax,
+                             const int64_t *Pp, const int *Pj, const void *Px, int64_t *Cp, amg_galerkin **out);
+int amg_galerkin_fetch_c128(amg_galerkin *g, int *Cj, void *Cx);
 
 /* ------------------------------------------------------------------------ */
 /* 5. Resident hierarchies of other value types: the cycle of section 2      */

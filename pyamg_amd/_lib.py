@@ -170,6 +170,9 @@ def lib():
         "amg_hier_galerkin": [V, I, I, V, V, V, V, V, V, V, C.POINTER(C.c_void_p)],
         "amg_galerkin_fetch": [V, V, V],
         "amg_csr_matmat_device": [I, I, I, V, V, V, V, V, V, V, C.POINTER(C.c_void_p)],
+        "amg_csr_matmat_device_c128": [I, I, I, V, V, V, V, V, V, V, C.POINTER(C.c_void_p)],
+        "amg_galerkin_device_c128": [I, I, V, V, V, V, V, V, V, V, V, V, C.POINTER(C.c_void_p)],
+        "amg_galerkin_fetch_c128": [V, V, V],
         "amg_hierx_create": [I, I, I, C.POINTER(C.c_void_p)],
         "amg_hierx_set_matrix": [V, I, I, I, I, I, I, I, V, V, V],
         "amg_hierx_set_smoother": [V, I, I, C.POINTER(SmootherDescX)],

@@ -51,6 +51,13 @@ def host_lib():
         L.amgsetup_gauss_seidel.restype = None
         L.amgsetup_block_gauss_seidel.argtypes = [ip, ip, dp, dp, dp, dp, C.c_int, C.c_int, C.c_int, C.c_int]
         L.amgsetup_block_gauss_seidel.restype = None
+        L.amgsetup_gauss_seidel_c128.argtypes = [ip, ip, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+        L.amgsetup_gauss_seidel_c128.restype = None
+        L.amgsetup_block_gauss_seidel_c128.argtypes = [ip, ip, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_int, C.c_int, C.c_int, C.c_int]
+        L.amgsetup_block_gauss_seidel_c128.restype = None
+        L.amgsetup_pinv_blocks_c128.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.amgsetup_pinv_blocks_c128.restype = None
         L.amgsetup_csr_diagonal_inv.argtypes = [C.c_int, lp, ip, dp, dp]
         L.amgsetup_csr_diagonal_inv.restype = None
         L.amgsetup_gauss_seidel_pipelined.argtypes = [ip, ip, dp, dp, dp, C.c_int, C.c_int, C.c_int]
@@ -158,8 +165,10 @@ def blocksize(A):
 # --------------------------------------------------------------------------- strength
 def symmetric_strength_of_connection(A, theta=0):
     """pyamg/strength.py:213-318, amg_core/smoothed_aggregation.h:49-99:
-    keep a_ij with |a_ij| >= theta*sqrt(|a_ii a_jj|) (the diagonal always), take
-    magnitudes and scale each row by its largest entry."""
+    keep a_ij with |a_ij|^2 >= theta^2 |a_ii| |a_jj| (the diagonal always), take
+    magnitudes and scale each row by its largest entry.  Complex operators: the
+    diagonal is summed as a complex number, |d| = sqrt(re^2 + im^2) (linalg.h mynorm)
+    and |a_ij|^2 = re^2 + im^2 (mynormsq)."""
     if theta < 0:
         raise ValueError("expected a positive theta")
     if isspmatrix_csr(A):
@@ -167,11 +176,18 @@ def symmetric_strength_of_connection(A, theta=0):
         n = A.shape[0]
         rows = np.repeat(np.arange(n), np.diff(A.indptr))
         isdiag = rows == A.indices
-        d = np.zeros(n)
-        np.add.at(d, rows[isdiag], A.data[isdiag])
-        diags = np.abs(d)
+        if A.dtype.kind == "c":
+            d = np.zeros(n, dtype=A.dtype)
+            np.add.at(d, rows[isdiag], A.data[isdiag])
+            diags = np.sqrt(d.real * d.real + d.imag * d.imag)
+            normsq = A.data.real * A.data.real + A.data.imag * A.data.imag
+        else:
+            d = np.zeros(n)
+            np.add.at(d, rows[isdiag], A.data[isdiag])
+            diags = np.abs(d)
+            normsq = A.data * A.data
         eps = (theta * theta) * diags
-        keep = isdiag | (A.data * A.data >= eps[rows] * diags[A.indices])
+        keep = isdiag | (normsq >= eps[rows] * diags[A.indices])
         Sp = np.concatenate(([0], np.cumsum(np.bincount(rows[keep], minlength=n)))).astype(A.indptr.dtype)
         S = csr_matrix((A.data[keep], A.indices[keep], Sp), shape=A.shape)
     elif isspmatrix_bsr(A):
@@ -233,7 +249,9 @@ def fit_candidates(AggOp, B, tol=1e-10):
     if not isspmatrix_csr(AggOp):
         raise TypeError("expected csr_matrix for argument AggOp")
     B = np.asarray(B)
-    if B.dtype not in ["float32", "float64"]:
+    if B.dtype.kind == "c":
+        B = np.asarray(B, dtype=np.complex128)
+    elif B.dtype not in ["float32", "float64"]:
         B = np.asarray(B, dtype="float64")
     if len(B.shape) != 2:
         raise ValueError("expected 2d array for argument B")
@@ -258,6 +276,8 @@ def fit_candidates(AggOp, B, tol=1e-10):
 def _aggregate_qr(Qx, Ap, N_coarse, K1, K2, tol):
     """Per-aggregate modified Gram-Schmidt of the candidate blocks Qx (one K1 x K2 block per member, members of
     aggregate j at Ap[j]:Ap[j+1]) -> (Q blocks, R (N_coarse, K2, K2)); smoothed_aggregation.h:341-452."""
+    if np.asarray(Qx).dtype.kind == "c":
+        return _aggregate_qr_c128(Qx, Ap, N_coarse, K1, K2, tol)
     Qx = np.array(Qx, dtype=np.float64)
     nnz = Qx.shape[0]
     R = np.zeros((N_coarse, K2, K2), dtype=np.float64)
@@ -305,6 +325,63 @@ def _aggregate_qr(Qx, Ap, N_coarse, K1, K2, tol):
             R[aggs, bj, bj] = np.where(ok, norm_j, 0.0)
             blk[:, :, bj] = blk[:, :, bj] * scale[:, None]
         Qx[pos] = blk.reshape(len(aggs), m, K1, K2)
+    return Qx, R
+
+
+def _aggregate_qr_c128(Qx, Ap, N_coarse, K1, K2, tol):
+    """_aggregate_qr for complex128 candidates (fit_candidates_complex, smoothed_aggregation.h:322-470), batched over
+    the aggregates of equal size, real and imaginary parts in arrays of their own so that every operation is one
+    correctly rounded real ufunc call:
+      norm      sum over the rows of re*re + im*im (complex_norm), a real sum from zero
+      dot       sum over the rows of conj(q_bi) * q_bj (complex_dot conjugates its SECOND argument, the column bi
+                that is already orthonormal), a complex sum from zero
+      update    q_bj -= dot * q_bi, then q_bj *= (1/norm + 0i), both full complex products."""
+    Qx = np.array(Qx, dtype=np.complex128)
+    R = np.zeros((N_coarse, K2, K2), dtype=np.complex128)
+    counts = np.diff(Ap)
+
+    def cmul(ar, ai, br, bi):
+        return ar * br - ai * bi, ar * bi + ai * br
+
+    for m in np.unique(counts):
+        if m == 0:
+            continue
+        aggs = np.nonzero(counts == m)[0]
+        pos = (np.asarray(Ap)[aggs][:, None] + np.arange(m)[None, :]).astype(np.int64)      # (ng, m)
+        blk = Qx[pos].reshape(len(aggs), m * K1, K2)
+        br, bi_ = np.ascontiguousarray(blk.real), np.ascontiguousarray(blk.imag)
+        nrow = m * K1
+
+        def colnorm(bj):
+            acc = np.zeros(len(aggs))
+            for rr in range(nrow):
+                acc = acc + (br[:, rr, bj] * br[:, rr, bj] + bi_[:, rr, bj] * bi_[:, rr, bj])
+            return np.sqrt(acc)
+
+        for bj in range(K2):
+            threshold_j = tol * colnorm(bj)
+            for b2 in range(bj):
+                dr, di = np.zeros(len(aggs)), np.zeros(len(aggs))
+                for rr in range(nrow):
+                    pr, pi = cmul(br[:, rr, b2], -bi_[:, rr, b2], br[:, rr, bj], bi_[:, rr, bj])
+                    dr = dr + pr
+                    di = di + pi
+                pr, pi = cmul(dr[:, None], di[:, None], br[:, :, b2], bi_[:, :, b2])
+                br[:, :, bj] = br[:, :, bj] - pr
+                bi_[:, :, bj] = bi_[:, :, bj] - pi
+                R.real[aggs, b2, bj] = dr
+                R.imag[aggs, b2, bj] = di
+            norm_j = colnorm(bj)
+            ok = norm_j > threshold_j
+            scale = np.zeros(len(aggs))
+            scale[ok] = 1.0 / norm_j[ok]
+            R[aggs, bj, bj] = np.where(ok, norm_j, 0.0)
+            pr, pi = cmul(br[:, :, bj], bi_[:, :, bj], scale[:, None], np.zeros((len(aggs), 1)))
+            br[:, :, bj] = pr
+            bi_[:, :, bj] = pi
+        out = np.empty(blk.shape, dtype=np.complex128)
+        out.real, out.imag = br, bi_
+        Qx[pos] = out.reshape(len(aggs), m, K1, K2)
     return Qx, R
 
 
@@ -379,6 +456,8 @@ def _improve(method, A, B):
     """relaxation_as_linear_operator(method, A, 0) * B  (util/utils.py:1129-1204,
     aggregation.py:313-320): relax A x = 0 from each candidate column.  Setup runs on
     the CPU: Gauss-Seidel sweeps use the host restatement of relaxation.h:34-62."""
+    if A.dtype.kind == "c":
+        return _improve_c128(method, A, B)
     from . import smoothing
     fn, kwargs = unpack_arg(method)
     lvl = multilevel_solver.level()
@@ -489,6 +568,60 @@ def _improve(method, A, B):
     return out
 
 
+def _improve_c128(method, A, B):
+    """_improve for a complex128 operator: the sequential sweeps of csrc/setup_host.cpp on scalar.hpp arithmetic
+    (amgsetup_gauss_seidel_c128 / amgsetup_block_gauss_seidel_c128); at or above util.DEVICE_RHO_MIN_ROWS with a
+    device present, the complex128 entries of the flat table (pyamg_amd.relaxation), which give the same bits."""
+    from . import smoothing, util
+    fn, kwargs = unpack_arg(method)
+    lvl = multilevel_solver.level()
+    lvl.A = A
+    desc = getattr(smoothing, "setup_" + str(fn))(lvl, **kwargs).desc
+    n = A.shape[0]
+    its = int(desc.get("iterations", 1))
+    sw = desc.get("sweep", "forward")
+    if sw not in ("forward", "backward", "symmetric"):
+        raise ValueError("valid sweep directions are 'forward', 'backward', and 'symmetric'")
+    b = np.zeros(n, dtype=np.complex128)
+    out = np.empty((n, B.shape[1]), dtype=np.complex128)
+    L = host_lib()
+    if desc["name"] == "gauss_seidel" and isspmatrix_csr(A):
+        bs, Dinv, M = 1, None, A
+    elif desc["name"] == "block_gauss_seidel":
+        bs = int(desc["blocksize"])
+        M = A.tobsr(blocksize=(bs, bs))                       # relaxation.py:563
+        Dinv = np.ascontiguousarray(np.ravel(desc["Dinv"]), dtype=np.complex128)
+    else:
+        raise NotImplementedError("improve_candidates=%r on this matrix is outside the restated setup" % (fn,))
+    from . import _lib
+    on_device = n >= util.DEVICE_RHO_MIN_ROWS and os.environ.get("AMG_SETUP_DEVICE_GS", "1") != "0" \
+        and _lib.device_count() > 0
+    Ap = np.ascontiguousarray(M.indptr, dtype=np.intc)
+    Aj = np.ascontiguousarray(M.indices, dtype=np.intc)
+    Ax = np.ascontiguousarray(np.ravel(M.data), dtype=np.complex128)
+    nb = n // bs
+    for j in range(B.shape[1]):
+        x = np.array(B[:, j], dtype=np.complex128, order="C")
+        if on_device:
+            from . import relaxation
+            if Dinv is None:
+                relaxation.gauss_seidel(M, x, b, iterations=its, sweep=sw)
+            else:
+                relaxation.block_gauss_seidel(M, x, b, iterations=its, sweep=sw, blocksize=bs,
+                                              Dinv=np.asarray(desc["Dinv"], dtype=np.complex128).reshape(-1, bs, bs))
+        else:
+            for it in range(its):
+                for rng in ([(0, nb, 1)] if sw == "forward" else [(nb - 1, -1, -1)] if sw == "backward"
+                            else [(0, nb, 1), (nb - 1, -1, -1)]):
+                    if Dinv is None:
+                        L.amgsetup_gauss_seidel_c128(_ip(Ap), _ip(Aj), Ax.ctypes.data, x.ctypes.data, b.ctypes.data, *rng)
+                    else:
+                        L.amgsetup_block_gauss_seidel_c128(_ip(Ap), _ip(Aj), Ax.ctypes.data, x.ctypes.data, b.ctypes.data,
+                                                           Dinv.ctypes.data, rng[0], rng[1], rng[2], bs)
+        out[:, j] = x
+    return out
+
+
 def smoothed_aggregation_solver(A, B=None, BH=None, symmetry="hermitian", strength="symmetric",
                                 aggregate="standard", smooth=("jacobi", {"omega": 4.0 / 3.0}),
                                 presmoother=("block_gauss_seidel", {"sweep": "symmetric"}),
@@ -504,7 +637,10 @@ def smoothed_aggregation_solver(A, B=None, BH=None, symmetry="hermitian", streng
             A = csr_matrix(A)
         except Exception:
             raise TypeError("Argument A must have type csr_matrix or bsr_matrix, or be convertible to csr_matrix")
-    A = A.astype(np.float64) if A.dtype != np.float64 else A
+    if A.dtype.kind == "c":
+        A = A.astype(np.complex128) if A.dtype != np.complex128 else A      # complex64 is raised, as float32 is
+    else:
+        A = A.astype(np.float64) if A.dtype != np.float64 else A
     if symmetry not in ("symmetric", "hermitian"):
         raise NotImplementedError("symmetry=%r is outside the restated setup" % (symmetry,))
     if diagonal_dominance:
@@ -601,6 +737,8 @@ def _as_bsr11(arrs, shape):
 
 
 def _scalar_fast_path_ok(A, B, strength_l, aggregate_l, smooth_l):
+    if A.dtype.kind == "c":
+        return False                    # the flat-array fast paths are float64: complex operators take the generic path
     if not (isspmatrix_csr(A) or (isspmatrix_bsr(A) and A.blocksize == (1, 1))):
         return False
     return _default_options(B, strength_l, aggregate_l, smooth_l)
@@ -750,6 +888,8 @@ def _extend_scalar(levels, smooth_l, keep, rho_fn):
 
 def _block_fast_path_ok(A, B, strength_l, aggregate_l, smooth_l):
     """square-block BSR operator (any number of candidates), default strength / aggregation / smoothing"""
+    if A.dtype.kind == "c":
+        return False
     if not (isspmatrix_bsr(A) and A.blocksize[0] == A.blocksize[1] and 1 < A.blocksize[0] <= 16):
         return False
     return _default_options(np.empty((1, 1)), strength_l, aggregate_l, smooth_l)
@@ -867,18 +1007,55 @@ def _rho_D_inv_A_host(A, D_inv):
     return approximate_spectral_radius(scale_rows(A, D_inv, copy=True))
 
 
+def _galerkin_c128_device(R, A, P):
+    """(R*A)*P of a complex128 level on the GPU (util.galerkin_device, csrc/spgemm.hip) as the BSR(1,1) matrix scipy's
+    R * A * P gives, or None: no device, AMG_SETUP_DEVICE_GALERKIN=0, a level below the gates
+    (util.DEVICE_GALERKIN_C128_MIN_ROWS, None = never, and util.DEVICE_RHO_MIN_ROWS), operands with blocks larger
+    than 1 x 1, or a row too long for the device tables -- the caller then uses scipy's products."""
+    from . import util
+    gate = util.DEVICE_GALERKIN_C128_MIN_ROWS
+    if os.environ.get("AMG_SETUP_DEVICE_GALERKIN", "1") == "0" or gate is None \
+            or A.shape[0] < max(gate, util.DEVICE_RHO_MIN_ROWS):
+        return None
+    for M in (R, A, P):
+        if not (isspmatrix_csr(M) or (isspmatrix_bsr(M) and M.blocksize == (1, 1))):
+            return None
+    from . import _lib
+    if _lib.device_count() <= 0:
+        return None
+    def arrays(M):
+        return (np.ascontiguousarray(M.indptr, dtype=np.int64), np.ascontiguousarray(M.indices, dtype=np.intc),
+                np.ascontiguousarray(np.ravel(M.data), dtype=np.complex128))
+    Ac = util.galerkin_device(arrays(A), arrays(R), arrays(P), P.shape[1])
+    if Ac is None:
+        return None
+    return _as_bsr11(Ac, (P.shape[1], P.shape[1]))
+
+
 def extend_hierarchy(levels, strength, aggregate, smooth, improve_candidates, keep=True, rho_fn=None):
     """aggregation.py:293-435"""
     A = levels[-1].A
     B = levels[-1].B
 
     li = len(levels) - 1
+    # stage lines for complex operators only: the generic path of a real operator prints what it printed before
+    verbose = os.environ.get("AMG_SETUP_VERBOSE", "0") != "0" and np.iscomplexobj(A)
+    n_rows, dtype = A.shape[0], A.dtype
+    _t = [time.perf_counter()]
+
+    def lap(what):
+        if verbose:
+            now = time.perf_counter()
+            print("[setup] level %d (%d rows, %s, generic) %-22s %6.2fs" % (li, n_rows, dtype, what, now - _t[0]),
+                  flush=True)
+            _t[0] = now
     fn, kwargs = unpack_arg(improve_candidates[li])
     # (running the candidate improvement beside the aggregation was tried: both are bound by host memory bandwidth and
     # the pair took longer than one after the other)
     if fn is not None:
         B = _improve((fn, kwargs), A, B)
         levels[-1].B = B
+        lap("candidate improvement")
 
     if not keep and _scalar_fast_path_ok(A, B, strength[li], aggregate[li], smooth[li]):
         return _extend_scalar(levels, smooth[li], keep, rho_fn or _rho_D_inv_A_host)
@@ -902,8 +1079,10 @@ def extend_hierarchy(levels, strength, aggregate, smooth, improve_candidates, ke
         AggOp = kwargs["AggOp"].tocsr()
     else:
         raise NotImplementedError("aggregate=%r is outside the restated setup" % (fn,))
+    lap("strength, aggregation")
 
     T, B = fit_candidates(AggOp, B)
+    lap("tentative prolongator")
 
     fn, kwargs = unpack_arg(smooth[len(levels) - 1])
     if fn == "jacobi":
@@ -913,8 +1092,10 @@ def extend_hierarchy(levels, strength, aggregate, smooth, improve_candidates, ke
     else:
         raise NotImplementedError("smooth=%r is outside the restated setup" % (fn,))
 
+    lap("smoothed prolongator")
     symmetry = A.symmetry
     R = P.conj().T.asformat(P.format) if symmetry == "hermitian" else P.T.asformat(P.format)
+    lap("R = P^H" if symmetry == "hermitian" else "R = P^T")
 
     if keep:
         levels[-1].C = Cm
@@ -924,7 +1105,10 @@ def extend_hierarchy(levels, strength, aggregate, smooth, improve_candidates, ke
     levels[-1].R = R
 
     levels.append(multilevel_solver.level())
-    A = R * A * P
+    Ac = _galerkin_c128_device(R, A, P) if A.dtype.kind == "c" else None
+    what = "(R*A)*P by scipy" if Ac is None else "(R*A)*P on the device"
+    A = R * A * P if Ac is None else Ac
+    lap(what)
     A.symmetry = symmetry
     levels[-1].A = A
     levels[-1].B = B

@@ -9,10 +9,13 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <limits>
 #include <vector>
 #ifdef _OPENMP
 #include <omp.h>
 #endif
+
+#include "scalar.hpp"
 
 extern "C" {
 
@@ -114,6 +117,201 @@ void amgsetup_block_gauss_seidel(const int *Ap, const int *Aj, const double *Ax,
             double sacc = 0.0;
             for (int c = 0; c < bs; c++) sacc += D[r * bs + c] * rsum[c];
             x[ib + r] = sacc;
+        }
+    }
+}
+
+// The two sweeps above for complex128 operators (values as interleaved pairs): plain sequential loops on the
+// arithmetic of scalar.hpp -- the product (ar br - ai bi, ar bi + ai br) without contraction, the quotient as the
+// compiler runtime forms it, a diagonal that is zero only when both parts are.
+void amgsetup_gauss_seidel_c128(const int *Ap, const int *Aj, const void *Ax_, void *x_, const void *b_,
+                                int row_start, int row_stop, int row_step)
+{
+    using namespace amg::sc;
+    const c128 *Ax = (const c128 *)Ax_, *b = (const c128 *)b_;
+    c128 *x = (c128 *)x_;
+    for (int i = row_start; i != row_stop; i += row_step) {
+        c128 rsum = from_real<c128>(0.0), diag = from_real<c128>(0.0);
+        for (int jj = Ap[i]; jj < Ap[i + 1]; jj++) {
+            const int j = Aj[jj];
+            if (i == j) diag = Ax[jj];
+            else rsum = add(rsum, mul(Ax[jj], x[j]));
+        }
+        if (nonzero(diag)) x[i] = div(sub(b[i], rsum), diag);
+    }
+}
+
+void amgsetup_block_gauss_seidel_c128(const int *Ap, const int *Aj, const void *Ax_, void *x_, const void *b_,
+                                      const void *Dinv_, int row_start, int row_stop, int row_step, int bs)
+{
+    using namespace amg::sc;
+    const c128 *Ax = (const c128 *)Ax_, *b = (const c128 *)b_, *Dinv = (const c128 *)Dinv_;
+    c128 *x = (c128 *)x_;
+    const int B2 = bs * bs;
+    std::vector<c128> rsum((size_t)bs), v((size_t)bs);
+    for (int i = row_start; i != row_stop; i += row_step) {
+        std::fill(rsum.begin(), rsum.end(), from_real<c128>(0.0));
+        for (int jj = Ap[i]; jj < Ap[i + 1]; jj++) {
+            const int j = Aj[jj];
+            if (i == j) continue;
+            const c128 *blk = Ax + (int64_t)jj * B2;
+            const c128 *xj = x + (int64_t)j * bs;
+            for (int r = 0; r < bs; r++) {
+                c128 sacc = from_real<c128>(0.0);
+                for (int c = 0; c < bs; c++) sacc = add(sacc, mul(blk[r * bs + c], xj[c]));
+                v[r] = sacc;
+            }
+            for (int k = 0; k < bs; k++) rsum[k] = add(rsum[k], v[k]);
+        }
+        const int64_t ib = (int64_t)i * bs;
+        for (int k = 0; k < bs; k++) rsum[k] = sub(b[ib + k], rsum[k]);
+        const c128 *D = Dinv + (int64_t)i * B2;
+        for (int r = 0; r < bs; r++) {
+            c128 sacc = from_real<c128>(0.0);
+            for (int c = 0; c < bs; c++) sacc = add(sacc, mul(D[r * bs + c], rsum[c]));
+            v[r] = sacc;
+        }
+        for (int r = 0; r < bs; r++) x[ib + r] = v[r];
+    }
+}
+
+}  // extern "C"
+
+// Moore-Penrose inverse of small dense complex128 blocks by the one-sided Jacobi method of de Rijk (SIAM J. Sci. Stat.
+// Comput. 10 (1989) 359-371): the columns of the block are turned against each other in cyclic order until they are
+// mutually orthogonal and sorted by length; their lengths are then the singular values, the unit columns the left
+// vectors, and the accumulated turns the right vectors.  The inverted diagonal blocks of a complex operator are the
+// constants of the block smoothers and of the candidate improvement, and the spectral-radius estimates of the next
+// level amplify a last-bit difference in them, so every sum below runs from zero in index order and
+// every turn is the four products and two sums spelled out in `Turn::apply`, which is what the reference's inverse
+// rounds to as well.  LAPACK's pinv agrees with it to rounding only.
+namespace {
+
+typedef std::complex<double> zc;
+
+inline double modulus(const zc &x) { return std::sqrt(x.real() * x.real() + x.imag() * x.imag()); }
+
+// The working array of one block stacks the block (rows 0 .. n-1) on the right vectors (rows n .. 2n-1): a column
+// has 2n entries, and whatever turns two columns of the block turns the same two right vectors in the same pass.
+struct Stacked {
+    zc *w;
+    int n;
+    zc *col(int j) const { return w + (size_t)j * 2 * n; }
+    zc inner(int j, int k) const                      // conj(column j) . column k over the block's rows
+    {
+        const zc *x = col(j), *y = col(k);
+        zc s = 0.0;
+        for (int i = 0; i < n; ++i) s += std::conj(x[i]) * y[i];
+        return s;
+    }
+    double length(int j) const { return std::sqrt(inner(j, j).real()); }
+};
+
+// right multiplication of a column pair (x, y) by [c s; -conj(s) c], or by [0 1; -1 0] when `exchange` is set
+struct Turn {
+    bool exchange;
+    double c;
+    zc s, ncs;
+    void apply(zc *x, zc *y, int len) const
+    {
+        if (exchange) {
+            for (int i = 0; i < len; ++i) { const zc xi = x[i]; x[i] = -y[i]; y[i] = xi; }
+            return;
+        }
+        for (int i = 0; i < len; ++i) {
+            const zc xi = x[i], yi = y[i];
+            x[i] = xi * c + ncs * yi;
+            y[i] = s * xi + yi * c;
+        }
+    }
+};
+
+// Orthogonalises the columns of the block held in W (see Stacked) and leaves in S, per column, the singular value.
+// err[] follows an absolute error bound of each column through the turns: a column shorter than its bound is noise
+// and is left alone.  The sweeps end when one of them turned nothing, or after max(15 n, 30) + 1 of them; a block
+// that has not settled by then is used as it stands, as the reference's pinv_array uses it (it does not look at
+// the status its decomposition returns).
+void orthogonalise(const Stacked &W, double *S, double *err)
+{
+    const int n = W.n;
+    const double eps = std::numeric_limits<double>::epsilon();
+    const double tol = std::sqrt((double)n) * eps;
+    const int last_sweep = std::max(15 * n, 30);
+    for (int j = 0; j < n; ++j) err[j] = eps * W.length(j);
+    bool turned = true;
+    for (int sweep = 0; turned && sweep <= last_sweep; ++sweep) {
+        turned = false;
+        for (int j = 0; j + 1 < n; ++j)
+            for (int k = j + 1; k < n; ++k) {
+                const double a = W.length(j), b = W.length(k);
+                const zc d = W.inner(j, k);
+                const double nd = modulus(d);
+                const bool settled = (nd <= tol * a * b) || a < err[j] || b < err[k];
+                if (a >= b && settled) continue;
+                Turn g;
+                g.exchange = !(a >= b) || (nd == 0.0 && a == b);      // out of order, or two equal null columns
+                const double ej = err[j], ek = err[k];
+                if (g.exchange) {
+                    err[j] = ek;
+                    err[k] = ej;
+                } else {
+                    const double tau = (b * b - a * a) / (2.0 * nd);
+                    const double t = (tau < 0.0 ? -1.0 : 1.0) / (std::fabs(tau) + std::sqrt(1.0 + tau * tau));
+                    g.c = 1.0 / std::sqrt(1.0 + t * t);
+                    g.s = d * (t * g.c / nd);
+                    g.ncs = -std::conj(g.s);
+                    const double ns = modulus(g.s);
+                    err[j] = std::fabs(g.c) * ej + ns * ek;
+                    err[k] = ns * ej + std::fabs(g.c) * ek;
+                }
+                g.apply(W.col(j), W.col(k), 2 * n);
+                turned = true;
+            }
+    }
+    // a column no longer than 50 eps^(3/4) times the first (longest) one carries a zero singular value
+    const double cut = (50.0 / std::sqrt(std::sqrt(eps))) * W.length(0) * eps;
+    for (int j = 0; j < n; ++j) {
+        const double len = W.length(j);
+        zc *u = W.col(j);
+        S[j] = len <= cut ? 0.0 : len;
+        for (int i = 0; i < n; ++i) u[i] = len <= cut ? zc(0.0) : u[i] / len;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+// blocks: count row-major n x n complex128 blocks (interleaved pairs), each replaced by its pseudo-inverse
+// V diag(1/S) U^H (zero singular values stay zero); every entry a row-times-column sum from zero, left to right
+void amgsetup_pinv_blocks_c128(void *blocks_, int count, int n)
+{
+    zc *blocks = (zc *)blocks_;
+    const int nn = n * n;
+#pragma omp parallel
+    {
+        std::vector<zc> work((size_t)2 * nn), SUh((size_t)nn);
+        std::vector<double> S((size_t)n), err((size_t)n);
+        const Stacked W = {work.data(), n};
+#pragma omp for schedule(static)
+        for (int q = 0; q < count; ++q) {
+            zc *M = blocks + (int64_t)q * nn;
+            for (int c = 0; c < n; ++c) {
+                zc *w = W.col(c);
+                for (int r = 0; r < n; ++r) { w[r] = M[r * n + c]; w[n + r] = (r == c) ? 1.0 : 0.0; }
+            }
+            orthogonalise(W, S.data(), err.data());
+            // SUh(k, c) = conj(U(c, k)) / S_k; an all-zero block inverts to zero
+            for (int k = 0; k < n; ++k) {
+                const double inv = S[k] != 0.0 ? 1.0 / S[k] : 0.0;
+                for (int c = 0; c < n; ++c) SUh[k * n + c] = std::conj(W.col(k)[c]) * inv;
+            }
+            for (int r = 0; r < n; ++r)
+                for (int c = 0; c < n; ++c) {
+                    zc acc = 0.0;
+                    for (int k = 0; k < n; ++k) acc += W.col(k)[n + r] * SUh[k * n + c];
+                    M[r * n + c] = acc;
+                }
         }
     }
 }

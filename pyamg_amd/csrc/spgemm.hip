@@ -11,6 +11,7 @@
 // row.  Bit-identical to the host restatement (setup_host.cpp amgsetup_csr_matmat_*) and to scipy: same products, same
 // order, separate multiply and add.
 #include "hier.hpp"
+#include "scalar.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -18,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <numeric>
+#include <type_traits>
 #include <vector>
 
 using namespace amg;
@@ -43,16 +45,35 @@ struct Lap {                 // AMG_SETUP_VERBOSE=1: stage times on stderr
     }
 };
 
-struct DCsr {              // a CSR operand in HBM (row pointer as 64-bit offsets)
+using sc::c128;
+
+// The value type V of a product is double or c128 (interleaved complex128).  The complex product is scalar.hpp's
+// (ar br - ai bi, ar bi + ai br) without contraction, sums add part by part, and a result is dropped only when both of
+// its parts are zero (scipy's complex `!= 0`).  The double overloads are the plain operators the float64 kernels
+// always used.
+template <class V> __device__ __forceinline__ V vzero();
+template <> __device__ __forceinline__ double vzero<double>() { return 0.0; }
+template <> __device__ __forceinline__ c128 vzero<c128>() { return c128{0.0, 0.0}; }
+__device__ __forceinline__ double vmul(double a, double b) { return a * b; }
+__device__ __forceinline__ c128 vmul(c128 a, c128 b) { return sc::mul(a, b); }
+__device__ __forceinline__ double vadd(double a, double b) { return a + b; }
+__device__ __forceinline__ c128 vadd(c128 a, c128 b) { return sc::add(a, b); }
+__device__ __forceinline__ bool vnz(double a) { return a != 0.0; }
+__device__ __forceinline__ bool vnz(c128 a) { return sc::nonzero(a); }
+
+template <class V>
+struct DCsrT {             // a CSR operand in HBM (row pointer as 64-bit offsets)
     int n_row = 0, n_col = 0;
     long nnz = 0;
     long *Ap = nullptr;
     int *Aj = nullptr;
-    double *Ax = nullptr;
+    V *Ax = nullptr;
     bool owned = true;
 };
+using DCsr = DCsrT<double>;
 
-void dcsr_free(DCsr &M)
+template <class V>
+void dcsr_free(DCsrT<V> &M)
 {
     if (M.owned) {
         if (M.Ap) hipFree(M.Ap);
@@ -80,16 +101,16 @@ __global__ void spgemm_upper_kernel(int n_row, const long *Ap, const int *Aj, co
 // threads): every probe a random 64-byte HBM access, 0.77 s per product of the 500^3 level.  The rows' DISTINCT
 // columns are far fewer, so the first launch runs with 256-entry tables (4 KB per thread, 256 MB in all: Infinity
 // Cache / L2) and only rows that outgrow them are redone with the large ones.
-template <bool FILL>
-__global__ __launch_bounds__(256) void spgemm_rows_kernel(int n_work, const int *rows, const long *Ap, const int *Aj, const double *Ax,
-                                                         const long *Bp, const int *Bj, const double *Bx, int cap, int limit,
-                                                         int *keys, double *sums, int *order, int *count, const long *Cp,
-                                                         int *Cj, double *Cx)
+template <class V, bool FILL>
+__global__ __launch_bounds__(256) void spgemm_rows_kernel(int n_work, const int *rows, const long *Ap, const int *Aj, const V *Ax,
+                                                         const long *Bp, const int *Bj, const V *Bx, int cap, int limit,
+                                                         int *keys, V *sums, int *order, int *count, const long *Cp,
+                                                         int *Cj, V *Cx)
 {
     const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long nthreads = (long)gridDim.x * blockDim.x;
     int *key = keys + tid * cap;
-    double *sum = sums + tid * cap;
+    V *sum = sums + tid * cap;
     int *ord = order + tid * cap;
     const unsigned mask = (unsigned)cap - 1u;
     for (long w = tid; w < n_work; w += nthreads) {
@@ -99,7 +120,7 @@ __global__ __launch_bounds__(256) void spgemm_rows_kernel(int n_work, const int 
         bool over = false;
         for (long jj = Ap[i]; jj < Ap[i + 1] && !over; ++jj) {
             const int j = Aj[jj];
-            const double v = Ax[jj];
+            const V v = Ax[jj];
             for (long kk = Bp[j]; kk < Bp[j + 1]; ++kk) {
                 const int c = Bj[kk];
                 unsigned h = ((unsigned)c * 2654435761u) & mask;
@@ -108,14 +129,14 @@ __global__ __launch_bounds__(256) void spgemm_rows_kernel(int n_work, const int 
                     if (k == c) break;
                     if (k == -1) {
                         if (n_ins >= limit) { over = true; break; }
-                        key[h] = c; sum[h] = 0.0; ord[n_ins++] = (int)h;
+                        key[h] = c; sum[h] = vzero<V>(); ord[n_ins++] = (int)h;
                         break;
                     }
                     h = (h + 1u) & mask;
                 }
                 if (over) break;
-                const double p = v * Bx[kk];
-                sum[h] = sum[h] + p;
+                const V p = vmul(v, Bx[kk]);
+                sum[h] = vadd(sum[h], p);
             }
         }
         if (over) {
@@ -127,15 +148,15 @@ __global__ __launch_bounds__(256) void spgemm_rows_kernel(int n_work, const int 
             long at = Cp[i];
             for (int q = n_ins - 1; q >= 0; --q) {
                 const int h = ord[q];
-                const double sv = sum[h];
-                if (sv != 0.0) { Cj[at] = key[h]; Cx[at] = sv; ++at; }
+                const V sv = sum[h];
+                if (vnz(sv)) { Cj[at] = key[h]; Cx[at] = sv; ++at; }
                 key[h] = -1;
             }
         } else {
             int nz = 0;
             for (int q = 0; q < n_ins; ++q) {
                 const int h = ord[q];
-                nz += (sum[h] != 0.0) ? 1 : 0;
+                nz += vnz(sum[h]) ? 1 : 0;
                 key[h] = -1;
             }
             count[i] = nz;
@@ -152,32 +173,37 @@ __global__ __launch_bounds__(256) void spgemm_rows_kernel(int n_work, const int 
 // long rows: the whole wave on one row with 4096 entries).  A row whose distinct columns do not fit its table raises
 // `overflow`: the caller retries with the whole wave per row, then with the one-thread-per-row kernel (tables in HBM),
 // then hands the product back to its host path.
-constexpr int WCAP = 4096;                 // table entries per wave (64 KB of LDS, two waves per compute unit)
+// Table entries per wave.  float64: 4096 (16 B per entry, 64 KB of LDS, two waves per compute unit).  complex128: an
+// entry costs 24 B, so 2048 (48 KB) keep two waves per compute unit; the host picks lane groups one step wider for
+// complex operands, which gives every row the table it has in float64 at all widths below the whole wave.
+template <class V> struct wave_cap { static constexpr int value = 4096; };
+template <> struct wave_cap<c128> { static constexpr int value = 2048; };
 // HBM = true (G = 64 only): the table of the wave's row lives in HBM instead (gcap entries per workgroup, keys preset
 // to -1 by the host) -- rows of tens of thousands of products on small coarse levels, where a few hundred waves with
 // 2 MB tables each are plenty.
-template <bool FILL, int G, bool HBM>
-__global__ __launch_bounds__(64) void spgemm_group_kernel(int n_row, const long *Ap, const int *Aj, const double *Ax,
-                                                         const long *Bp, const int *Bj, const double *Bx, int *count,
-                                                         const long *Cp, int *Cj, double *Cx, int *overflow,
-                                                         int *gkey, double *gsum, int *gord, int gcap)
+template <class V, bool FILL, int G, bool HBM>
+__global__ __launch_bounds__(64) void spgemm_group_kernel(int n_row, const long *Ap, const int *Aj, const V *Ax,
+                                                         const long *Bp, const int *Bj, const V *Bx, int *count,
+                                                         const long *Cp, int *Cj, V *Cx, int *overflow,
+                                                         int *gkey, V *gsum, int *gord, int gcap)
 {
+    constexpr int WCAP = wave_cap<V>::value;
     static_assert(!HBM || G == 64, "tables in HBM: one row per wave");
     constexpr int NG = 64 / G;             // rows per wave
     constexpr int LB = 64;                 // left-hand entries staged per batch and row
     __shared__ int key_s[HBM ? 1 : WCAP];
-    __shared__ double sum_s[HBM ? 1 : WCAP];
+    __shared__ V sum_s[HBM ? 1 : WCAP];
     __shared__ int ord_s[HBM ? 1 : WCAP];
-    __shared__ double stv_s[NG * LB];
+    __shared__ V stv_s[NG * LB];
     __shared__ long stb_s[NG * LB];
     __shared__ int stl_s[NG * LB];
     const int lane = threadIdx.x;
     const int g = lane / G, gl = lane % G;                          // group (row slot) and lane within the group
     const int CAP = HBM ? gcap : WCAP / NG;                         // table entries per row
     int *key = HBM ? gkey + (long)blockIdx.x * gcap : key_s + g * CAP;
-    double *sum = HBM ? gsum + (long)blockIdx.x * gcap : sum_s + g * CAP;
+    V *sum = HBM ? gsum + (long)blockIdx.x * gcap : sum_s + g * CAP;
     int *ord = HBM ? gord + (long)blockIdx.x * gcap : ord_s + g * CAP;
-    double *st_v = stv_s + g * LB;
+    V *st_v = stv_s + g * LB;
     long *st_b0 = stb_s + g * LB;
     int *st_len = stl_s + g * LB;
     const unsigned mask = (unsigned)CAP - 1u;
@@ -216,10 +242,10 @@ __global__ __launch_bounds__(64) void spgemm_group_kernel(int n_row, const long 
             // the first chunks of the next PD entries' right-hand rows are requested ahead of use (a ring of PD
             // register slots, the loop unrolled by PD so that the slot index is a constant)
             constexpr int PD = 4;
-            int pc[PD]; double px[PD];
+            int pc[PD]; V px[PD];
 #pragma unroll
             for (int u = 0; u < PD; ++u) {
-                pc[u] = 0; px[u] = 0.0;
+                pc[u] = 0; px[u] = vzero<V>();
                 const int l = st_len[u];
                 if (gl < l) { const long b = st_b0[u]; pc[u] = Bj[b + gl]; px[u] = Bx[b + gl]; }
             }
@@ -231,10 +257,10 @@ __global__ __launch_bounds__(64) void spgemm_group_kernel(int n_row, const long 
                     const int len = st_len[e];
                     if (__ballot(len >= 0) == 0ULL) { batch_done = true; break; }   // every row of the wave is through its batch
                     const long b0 = len >= 0 ? st_b0[e] : 0;
-                    const int c0 = pc[u]; const double x0 = px[u];
-                    const double v = len >= 0 ? st_v[e] : 0.0;
+                    const int c0 = pc[u]; const V x0 = px[u];
+                    const V v = len >= 0 ? st_v[e] : vzero<V>();
                     // refill this slot with entry e + PD before touching the table
-                    pc[u] = 0; px[u] = 0.0;
+                    pc[u] = 0; px[u] = vzero<V>();
                     if (e + PD < LB) {
                         const int l = st_len[e + PD];
                         if (gl < l) { const long b = st_b0[e + PD]; pc[u] = Bj[b + gl]; px[u] = Bx[b + gl]; }
@@ -248,17 +274,17 @@ __global__ __launch_bounds__(64) void spgemm_group_kernel(int n_row, const long 
                         if (active) {
                             if (n_ins + G > CAP / 2) bad = true;        // keep the table at most half full
                             else if (kb + gl < len) {
-                                int c; double x;
+                                int c; V x;
                                 if (kb == 0) { c = c0; x = x0; } else { c = Bj[b0 + kb + gl]; x = Bx[b0 + kb + gl]; }
                                 h = (int)(((unsigned)c * 2654435761u) & mask);
                                 for (;;) {
                                     const int k = atomicCAS(&key[h], -1, c);
-                                    if (k == -1) { inserted = true; sum[h] = 0.0; break; }
+                                    if (k == -1) { inserted = true; sum[h] = vzero<V>(); break; }
                                     if (k == c) break;
                                     h = (h + 1) & (int)mask;
                                 }
-                                const double p = v * x;
-                                sum[h] = sum[h] + p;
+                                const V p = vmul(v, x);
+                                sum[h] = vadd(sum[h], p);
                             }
                         }
                         const unsigned long long m = __ballot(inserted);
@@ -276,9 +302,9 @@ __global__ __launch_bounds__(64) void spgemm_group_kernel(int n_row, const long 
             for (;;) {                                              // reverse first-touch order, zeros dropped
                 if (__ballot(q0 >= 0) == 0ULL) break;
                 const int q = q0 - gl;
-                double sv = 0.0; int kv = 0;
+                V sv = vzero<V>(); int kv = 0;
                 if (q >= 0) { const int hh = ord[q]; sv = sum[hh]; kv = key[hh]; }
-                const bool keep = (q >= 0) && sv != 0.0 && !bad;
+                const bool keep = (q >= 0) && vnz(sv) && !bad;
                 const unsigned long long m = __ballot(keep);
                 if (keep) { const long w = at + __popcll(m & below); Cj[w] = kv; Cx[w] = sv; }
                 at += __popcll(m & gmask);
@@ -289,7 +315,7 @@ __global__ __launch_bounds__(64) void spgemm_group_kernel(int n_row, const long 
             for (;;) {
                 if (__ballot(q0 < n_ins) == 0ULL) break;
                 const int q = q0 + gl;
-                const bool keep = (q < n_ins) && sum[ord[q]] != 0.0;
+                const bool keep = (q < n_ins) && vnz(sum[ord[q]]);
                 nz += __popcll(__ballot(keep) & gmask);
                 q0 += G;
             }
@@ -301,24 +327,34 @@ __global__ __launch_bounds__(64) void spgemm_group_kernel(int n_row, const long 
     }
 }
 
-int upload_dcsr(DCsr &M, int n_row, int n_col, const long *Ap, const int *Aj, const double *Ax)
+template <class V>
+int upload_dcsr(DCsrT<V> &M, int n_row, int n_col, const long *Ap, const int *Aj, const V *Ax)
 {
     M.n_row = n_row; M.n_col = n_col; M.nnz = Ap[n_row];
     AMG_HIP(hipMalloc((void **)&M.Ap, sizeof(long) * ((size_t)n_row + 1)));
     AMG_HIP(hipMalloc((void **)&M.Aj, sizeof(int) * (size_t)std::max(M.nnz, 1L)));
-    AMG_HIP(hipMalloc((void **)&M.Ax, sizeof(double) * (size_t)std::max(M.nnz, 1L)));
+    AMG_HIP(hipMalloc((void **)&M.Ax, sizeof(V) * (size_t)std::max(M.nnz, 1L)));
     AMG_HIP(hipMemcpy(M.Ap, Ap, sizeof(long) * ((size_t)n_row + 1), hipMemcpyHostToDevice));
     AMG_HIP(hipMemcpy(M.Aj, Aj, sizeof(int) * (size_t)M.nnz, hipMemcpyHostToDevice));
-    AMG_HIP(hipMemcpy(M.Ax, Ax, sizeof(double) * (size_t)M.nnz, hipMemcpyHostToDevice));
+    AMG_HIP(hipMemcpy(M.Ax, Ax, sizeof(V) * (size_t)M.nnz, hipMemcpyHostToDevice));
     return 0;
 }
 
 // C = A * B, both in HBM; C allocated here
-int matmat(const DCsr &A, const DCsr &B, DCsr &C)
+template <class V>
+int matmat(const DCsrT<V> &A, const DCsrT<V> &B, DCsrT<V> &C)
 {
     if (A.n_col != B.n_row) { set_error("spgemm: inner dimensions differ"); return AMG_EINVAL; }
     C.n_row = A.n_row; C.n_col = B.n_col;
     const int n = A.n_row;
+    constexpr bool CPLX = !std::is_same<V, double>::value;
+    constexpr long ENTRY = 8 + (long)sizeof(V);                 // bytes of a table entry: key, place in the order list, sum
+    if (CPLX && n == 0) {                                       // no rows: the empty product (complex entries only)
+        C.nnz = 0; C.Aj = nullptr; C.Ax = nullptr;
+        AMG_HIP(hipMalloc((void **)&C.Ap, sizeof(long)));
+        AMG_HIP(hipMemset(C.Ap, 0, sizeof(long)));
+        return 0;
+    }
     int *upper = nullptr;
     AMG_HIP(hipMalloc((void **)&upper, sizeof(int) * (size_t)std::max(n, 1)));
     hipLaunchKernelGGL(spgemm_upper_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, n, A.Ap, A.Aj, B.Ap, upper);
@@ -331,7 +367,8 @@ int matmat(const DCsr &A, const DCsr &B, DCsr &C)
     // G lanes per row with the tables in LDS; rows whose distinct columns outgrow their table send the whole product to
     // the one-thread-per-row kernel below (tables in HBM), which in turn refuses levels too large for it
     const double avgB = B.n_row > 0 ? (double)B.nnz / (double)B.n_row : 1.0;
-    const int G0 = avgB <= 10.0 ? 8 : (avgB <= 20.0 ? 16 : (avgB <= 40.0 ? 32 : 64));
+    const int G0r = avgB <= 10.0 ? 8 : (avgB <= 20.0 ? 16 : (avgB <= 40.0 ? 32 : 64));
+    const int G0 = CPLX ? std::min(64, 2 * G0r) : G0r;             // complex: one step wider (wave_cap)
     for (int G = G0; G <= 64; G = (G == 64 ? 128 : 64)) {          // the preferred width, then the whole wave per row
         int *count = nullptr, *overflow = nullptr;
         AMG_HIP(hipMalloc((void **)&count, sizeof(int) * (size_t)std::max(n, 1)));
@@ -339,10 +376,10 @@ int matmat(const DCsr &A, const DCsr &B, DCsr &C)
         AMG_HIP(hipMemset(overflow, 0, sizeof(int)));
         const int rows_per_wave = 64 / G;
         const int blocks = (int)std::min<long>(((long)n + rows_per_wave - 1) / rows_per_wave, 256L * 2 * 8);
-#define GROUP_LAUNCH(FILL, GG) hipLaunchKernelGGL((spgemm_group_kernel<FILL, GG, false>), dim3(blocks), dim3(64), 0, nullptr, n, A.Ap, A.Aj, A.Ax, \
+#define GROUP_LAUNCH(FILL, GG) hipLaunchKernelGGL((spgemm_group_kernel<V, FILL, GG, false>), dim3(blocks), dim3(64), 0, nullptr, n, A.Ap, A.Aj, A.Ax, \
                                                   B.Ap, B.Aj, B.Ax, count, (const long *)C.Ap, C.Aj, C.Ax, overflow, (int *)nullptr, \
-                                                  (double *)nullptr, (int *)nullptr, 0)
-#define GROUP_DISPATCH(FILL) do { if (G == 8) GROUP_LAUNCH(FILL, 8); else if (G == 16) GROUP_LAUNCH(FILL, 16); \
+                                                  (V *)nullptr, (int *)nullptr, 0)
+#define GROUP_DISPATCH(FILL) do { if (G == 8) { if constexpr (!CPLX) GROUP_LAUNCH(FILL, 8); } else if (G == 16) GROUP_LAUNCH(FILL, 16); \
                                   else if (G == 32) GROUP_LAUNCH(FILL, 32); else GROUP_LAUNCH(FILL, 64); } while (0)
         C.Ap = nullptr; C.Aj = nullptr; C.Ax = nullptr;
         GROUP_DISPATCH(false);
@@ -351,8 +388,8 @@ int matmat(const DCsr &A, const DCsr &B, DCsr &C)
         int ovf = 0;
         AMG_HIP(hipMemcpy(&ovf, overflow, sizeof(int), hipMemcpyDeviceToHost));
         if (std::getenv("AMG_SETUP_VERBOSE") && std::getenv("AMG_SETUP_VERBOSE")[0] != '0')
-            std::fprintf(stderr, "[setup]     device product %d x %d: %d lanes per row (right-hand rows avg %.1f, longest row %d products)%s\n",
-                         A.n_row, B.n_col, G, avgB, max_upper, ovf ? " -- a row outgrew its LDS table" : "");
+            std::fprintf(stderr, "[setup]     device product %d x %d%s: %d lanes per row (right-hand rows avg %.1f, longest row %d products)%s\n",
+                         A.n_row, B.n_col, CPLX ? " (complex128)" : "", G, avgB, max_upper, ovf ? " -- a row outgrew its LDS table" : "");
         if (!ovf) {
             std::vector<int> hc((size_t)n);
             AMG_HIP(hipMemcpy(hc.data(), count, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
@@ -362,7 +399,7 @@ int matmat(const DCsr &A, const DCsr &B, DCsr &C)
             C.nnz = cp[(size_t)n];
             AMG_HIP(hipMalloc((void **)&C.Ap, sizeof(long) * ((size_t)n + 1)));
             AMG_HIP(hipMalloc((void **)&C.Aj, sizeof(int) * (size_t)std::max(C.nnz, 1L)));
-            AMG_HIP(hipMalloc((void **)&C.Ax, sizeof(double) * (size_t)std::max(C.nnz, 1L)));
+            AMG_HIP(hipMalloc((void **)&C.Ax, sizeof(V) * (size_t)std::max(C.nnz, 1L)));
             AMG_HIP(hipMemcpy(C.Ap, cp.data(), sizeof(long) * ((size_t)n + 1), hipMemcpyHostToDevice));
             GROUP_DISPATCH(true);
             e = hipGetLastError();
@@ -381,19 +418,19 @@ int matmat(const DCsr &A, const DCsr &B, DCsr &C)
         long distinct_bound = std::min<long>(max_upper, (long)B.n_col);
         int gcap = 1024;
         while (gcap < 2 * distinct_bound + 256) gcap <<= 1;
-        const int blocks = (int)std::max<long>(1, std::min<long>(std::min<long>(n, 1024), (4L << 30) / ((long)gcap * 16L)));
+        const int blocks = (int)std::max<long>(1, std::min<long>(std::min<long>(n, 1024), (4L << 30) / ((long)gcap * ENTRY)));
         int *count = nullptr, *overflow = nullptr, *gkey = nullptr, *gord = nullptr;
-        double *gsum = nullptr;
+        V *gsum = nullptr;
         AMG_HIP(hipMalloc((void **)&count, sizeof(int) * (size_t)std::max(n, 1)));
         AMG_HIP(hipMalloc((void **)&overflow, sizeof(int)));
         AMG_HIP(hipMemset(overflow, 0, sizeof(int)));
         AMG_HIP(hipMalloc((void **)&gkey, sizeof(int) * (size_t)blocks * gcap));
         AMG_HIP(hipMalloc((void **)&gord, sizeof(int) * (size_t)blocks * gcap));
-        AMG_HIP(hipMalloc((void **)&gsum, sizeof(double) * (size_t)blocks * gcap));
+        AMG_HIP(hipMalloc((void **)&gsum, sizeof(V) * (size_t)blocks * gcap));
         AMG_HIP(hipMemset(gkey, 0xFF, sizeof(int) * (size_t)blocks * gcap));
         C.Ap = nullptr; C.Aj = nullptr; C.Ax = nullptr;
-        hipLaunchKernelGGL((spgemm_group_kernel<false, 64, true>), dim3(blocks), dim3(64), 0, nullptr, n, A.Ap, A.Aj, A.Ax, B.Ap, B.Aj, B.Ax,
-                           count, (const long *)nullptr, (int *)nullptr, (double *)nullptr, overflow, gkey, gsum, gord, gcap);
+        hipLaunchKernelGGL((spgemm_group_kernel<V, false, 64, true>), dim3(blocks), dim3(64), 0, nullptr, n, A.Ap, A.Aj, A.Ax, B.Ap, B.Aj, B.Ax,
+                           count, (const long *)nullptr, (int *)nullptr, (V *)nullptr, overflow, gkey, gsum, gord, gcap);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return hip_fail(e, "spgemm HBM-table count launch", __FILE__, __LINE__);
         int ovf = 0;
@@ -411,9 +448,9 @@ int matmat(const DCsr &A, const DCsr &B, DCsr &C)
             C.nnz = cp[(size_t)n];
             AMG_HIP(hipMalloc((void **)&C.Ap, sizeof(long) * ((size_t)n + 1)));
             AMG_HIP(hipMalloc((void **)&C.Aj, sizeof(int) * (size_t)std::max(C.nnz, 1L)));
-            AMG_HIP(hipMalloc((void **)&C.Ax, sizeof(double) * (size_t)std::max(C.nnz, 1L)));
+            AMG_HIP(hipMalloc((void **)&C.Ax, sizeof(V) * (size_t)std::max(C.nnz, 1L)));
             AMG_HIP(hipMemcpy(C.Ap, cp.data(), sizeof(long) * ((size_t)n + 1), hipMemcpyHostToDevice));
-            hipLaunchKernelGGL((spgemm_group_kernel<true, 64, true>), dim3(blocks), dim3(64), 0, nullptr, n, A.Ap, A.Aj, A.Ax, B.Ap, B.Aj, B.Ax,
+            hipLaunchKernelGGL((spgemm_group_kernel<V, true, 64, true>), dim3(blocks), dim3(64), 0, nullptr, n, A.Ap, A.Aj, A.Ax, B.Ap, B.Aj, B.Ax,
                                count, (const long *)C.Ap, C.Aj, C.Ax, overflow, gkey, gsum, gord, gcap);
             e = hipGetLastError();
             if (e != hipSuccess) rc = hip_fail(e, "spgemm HBM-table fill launch", __FILE__, __LINE__);
@@ -422,13 +459,13 @@ int matmat(const DCsr &A, const DCsr &B, DCsr &C)
         hipFree(count); hipFree(overflow); hipFree(gkey); hipFree(gord); hipFree(gsum);
         if (!ovf) return rc;
     }
-    if (!(max_upper <= 1024 || (double)n * (double)cap * 16.0 <= 2.0e9)) {
+    if (!(max_upper <= 1024 || (double)n * (double)cap * (double)ENTRY <= 2.0e9)) {
         set_error("spgemm: rows with more distinct columns than the LDS tables hold on a level too large for per-thread tables (host path)");
         return AMG_EINVAL;
     }
     // first tier: 256-entry tables (up to 128 distinct columns per row), 65536 threads
     struct Tables {
-        int *keys = nullptr, *order = nullptr; double *sums = nullptr; int cap = 0; long threads = 0; int blocks = 0;
+        int *keys = nullptr, *order = nullptr; V *sums = nullptr; int cap = 0; long threads = 0; int blocks = 0;
         int make(int cap_, long want_threads)
         {
             cap = cap_;
@@ -436,20 +473,23 @@ int matmat(const DCsr &A, const DCsr &B, DCsr &C)
             threads = (long)blocks * 256;
             AMG_HIP(hipMalloc((void **)&keys, sizeof(int) * (size_t)(threads * cap)));
             AMG_HIP(hipMalloc((void **)&order, sizeof(int) * (size_t)(threads * cap)));
-            AMG_HIP(hipMalloc((void **)&sums, sizeof(double) * (size_t)(threads * cap)));
+            AMG_HIP(hipMalloc((void **)&sums, sizeof(V) * (size_t)(threads * cap)));
             AMG_HIP(hipMemset(keys, 0xFF, sizeof(int) * (size_t)(threads * cap)));
             return 0;
         }
         void drop() { if (keys) hipFree(keys); if (order) hipFree(order); if (sums) hipFree(sums); keys = order = nullptr; sums = nullptr; }
     };
     const int small_cap = std::min(cap, 256);
+    if (std::getenv("AMG_SETUP_VERBOSE") && std::getenv("AMG_SETUP_VERBOSE")[0] != '0')
+        std::fprintf(stderr, "[setup]     device product %d x %d%s: one thread per row, %d-entry tables in HBM (%d-entry ones for rows that outgrow them)\n",
+                     A.n_row, B.n_col, CPLX ? " (complex128)" : "", small_cap, cap);
     Tables T1, T2;
     CHK(T1.make(small_cap, std::min<long>(65536, n)));
     int *count = nullptr, *big_rows = nullptr;
     AMG_HIP(hipMalloc((void **)&count, sizeof(int) * (size_t)std::max(n, 1)));
-    hipLaunchKernelGGL((spgemm_rows_kernel<false>), dim3(T1.blocks), dim3(256), 0, nullptr, n, (const int *)nullptr, A.Ap, A.Aj, A.Ax,
+    hipLaunchKernelGGL((spgemm_rows_kernel<V, false>), dim3(T1.blocks), dim3(256), 0, nullptr, n, (const int *)nullptr, A.Ap, A.Aj, A.Ax,
                        B.Ap, B.Aj, B.Ax, T1.cap, T1.cap / 2, T1.keys, T1.sums, T1.order, count, (const long *)nullptr,
-                       (int *)nullptr, (double *)nullptr);
+                       (int *)nullptr, (V *)nullptr);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "spgemm count launch", __FILE__, __LINE__);
     std::vector<int> hc((size_t)n);
@@ -458,13 +498,13 @@ int matmat(const DCsr &A, const DCsr &B, DCsr &C)
     for (int i = 0; i < n; ++i) if (hc[(size_t)i] < 0) big.push_back(i);
     if (!big.empty()) {
         // second tier: the rows that outgrew the small tables, with tables sized by the longest row's products
-        long threads = std::min<long>(256L * 512L, (3L << 30) / ((long)cap * 16L));
+        long threads = std::min<long>(256L * 512L, (3L << 30) / ((long)cap * ENTRY));
         CHK(T2.make(cap, std::min<long>(threads, (long)big.size())));
         AMG_HIP(hipMalloc((void **)&big_rows, sizeof(int) * big.size()));
         AMG_HIP(hipMemcpy(big_rows, big.data(), sizeof(int) * big.size(), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL((spgemm_rows_kernel<false>), dim3(T2.blocks), dim3(256), 0, nullptr, (int)big.size(), big_rows, A.Ap, A.Aj, A.Ax,
+        hipLaunchKernelGGL((spgemm_rows_kernel<V, false>), dim3(T2.blocks), dim3(256), 0, nullptr, (int)big.size(), big_rows, A.Ap, A.Aj, A.Ax,
                            B.Ap, B.Aj, B.Ax, T2.cap, T2.cap / 2, T2.keys, T2.sums, T2.order, count, (const long *)nullptr,
-                           (int *)nullptr, (double *)nullptr);
+                           (int *)nullptr, (V *)nullptr);
         e = hipGetLastError();
         if (e != hipSuccess) return hip_fail(e, "spgemm count launch (large tables)", __FILE__, __LINE__);
         AMG_HIP(hipMemcpy(hc.data(), count, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
@@ -476,7 +516,7 @@ int matmat(const DCsr &A, const DCsr &B, DCsr &C)
     C.nnz = cp[(size_t)n];
     AMG_HIP(hipMalloc((void **)&C.Ap, sizeof(long) * ((size_t)n + 1)));
     AMG_HIP(hipMalloc((void **)&C.Aj, sizeof(int) * (size_t)std::max(C.nnz, 1L)));
-    AMG_HIP(hipMalloc((void **)&C.Ax, sizeof(double) * (size_t)std::max(C.nnz, 1L)));
+    AMG_HIP(hipMalloc((void **)&C.Ax, sizeof(V) * (size_t)std::max(C.nnz, 1L)));
     AMG_HIP(hipMemcpy(C.Ap, cp.data(), sizeof(long) * ((size_t)n + 1), hipMemcpyHostToDevice));
     if (!big.empty()) {
         // mark the large rows in `count` again (the first-tier fill skips rows with count < 0)
@@ -484,12 +524,12 @@ int matmat(const DCsr &A, const DCsr &B, DCsr &C)
         for (int i : big) mark[(size_t)i] = -1;
         AMG_HIP(hipMemcpy(count, mark.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
     }
-    hipLaunchKernelGGL((spgemm_rows_kernel<true>), dim3(T1.blocks), dim3(256), 0, nullptr, n, (const int *)nullptr, A.Ap, A.Aj, A.Ax,
+    hipLaunchKernelGGL((spgemm_rows_kernel<V, true>), dim3(T1.blocks), dim3(256), 0, nullptr, n, (const int *)nullptr, A.Ap, A.Aj, A.Ax,
                        B.Ap, B.Aj, B.Ax, T1.cap, T1.cap / 2, T1.keys, T1.sums, T1.order, count, C.Ap, C.Aj, C.Ax);
     e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "spgemm fill launch", __FILE__, __LINE__);
     if (!big.empty()) {
-        hipLaunchKernelGGL((spgemm_rows_kernel<true>), dim3(T2.blocks), dim3(256), 0, nullptr, (int)big.size(), big_rows, A.Ap, A.Aj, A.Ax,
+        hipLaunchKernelGGL((spgemm_rows_kernel<V, true>), dim3(T2.blocks), dim3(256), 0, nullptr, (int)big.size(), big_rows, A.Ap, A.Aj, A.Ax,
                            B.Ap, B.Aj, B.Ax, T2.cap, T2.cap / 2, T2.keys, T2.sums, T2.order, count, C.Ap, C.Aj, C.Ax);
         e = hipGetLastError();
         if (e != hipSuccess) return hip_fail(e, "spgemm fill launch (large tables)", __FILE__, __LINE__);
@@ -511,6 +551,8 @@ __global__ void widen_rowptr_kernel(int n, const int *Ap32, long *Ap64)
 
 struct amg_galerkin {
     DCsr C;
+    DCsrT<c128> Cz;             // the product of the complex128 entries (is_c128)
+    bool is_c128 = false;
     std::vector<long> cp;
 };
 
@@ -561,6 +603,7 @@ int amg_hier_galerkin(amg_hier *h, int level, int n_coarse, const int64_t *Rp, c
 int amg_galerkin_fetch(amg_galerkin *g, int *Cj, double *Cx)
 {
     if (!g) return AMG_EINVAL;
+    if (g->is_c128) { set_error("galerkin: a complex128 product is fetched with amg_galerkin_fetch_c128"); return AMG_EINVAL; }
     int rc = 0;
     if (g->C.nnz > 0) {
         if (hipMemcpy(Cj, g->C.Aj, sizeof(int) * (size_t)g->C.nnz, hipMemcpyDeviceToHost) != hipSuccess ||
@@ -593,6 +636,85 @@ int amg_csr_matmat_device(int n_row, int n_inner, int n_col, const int64_t *Ap, 
     }
     *out = g;
     return 0;
+}
+
+// ---- complex128 operands (values as interleaved (re, im) pairs of doubles); the products run through the same
+// kernels instantiated for c128: every output entry accumulates (ar br - ai bi, ar bi + ai br) from zero in traversal
+// order, part by part, comes out in reverse first-touch order and is dropped only when both parts are zero.
+
+// C = A * B for host CSR operands: the complex twin of amg_csr_matmat_device
+int amg_csr_matmat_device_c128(int n_row, int n_inner, int n_col, const int64_t *Ap, const int *Aj, const void *Ax,
+                               const int64_t *Bp, const int *Bj, const void *Bx, int64_t *Cp, amg_galerkin **out)
+{
+    if (!out || !Ap || !Bp || !Cp || n_row < 0 || n_inner < 0 || n_col < 0) { set_error("matmat: bad arguments"); return AMG_EINVAL; }
+    DCsrT<c128> A, B;
+    int rc = upload_dcsr(A, n_row, n_inner, (const long *)Ap, Aj, (const c128 *)Ax);
+    if (rc == 0) rc = upload_dcsr(B, n_inner, n_col, (const long *)Bp, Bj, (const c128 *)Bx);
+    amg_galerkin *g = new amg_galerkin;
+    g->is_c128 = true;
+    if (rc == 0) rc = matmat(A, B, g->Cz);
+    dcsr_free(A); dcsr_free(B);
+    if (rc != 0) { dcsr_free(g->Cz); delete g; return rc; }
+    if (hipMemcpy(Cp, g->Cz.Ap, sizeof(long) * ((size_t)n_row + 1), hipMemcpyDeviceToHost) != hipSuccess) {
+        dcsr_free(g->Cz); delete g;
+        set_error("matmat: row pointer download failed");
+        return AMG_ENODEV;
+    }
+    *out = g;
+    return 0;
+}
+
+// Ac = (R * A) * P from three host CSR operands (64-bit row pointers): R is n_coarse x n_fine, A n_fine x n_fine,
+// P n_fine x n_coarse.  R * A is formed in HBM and stays there.  On return Cp (n_coarse + 1 entries) is filled and
+// *out holds the product for amg_galerkin_fetch_c128.  AMG_EINVAL when a row is too long for the device tables: the
+// caller then uses its host path.
+int amg_galerkin_device_c128(int n_fine, int n_coarse, const int64_t *Rp, const int *Rj, const void *Rx,
+                             const int64_t *Ap, const int *Aj, const void *Ax,
+                             const int64_t *Pp, const int *Pj, const void *Px, int64_t *Cp, amg_galerkin **out)
+{
+    if (!out || !Rp || !Ap || !Pp || !Cp || n_fine < 0 || n_coarse < 0) { set_error("galerkin: bad arguments"); return AMG_EINVAL; }
+    Lap lap;
+    DCsrT<c128> A, R, P, RA;
+    int rc = upload_dcsr(R, n_coarse, n_fine, (const long *)Rp, Rj, (const c128 *)Rx);
+    if (rc == 0) rc = upload_dcsr(A, n_fine, n_fine, (const long *)Ap, Aj, (const c128 *)Ax);
+    lap("R, A to HBM");
+    if (rc == 0) rc = matmat(R, A, RA);
+    lap("R*A");
+    dcsr_free(R); dcsr_free(A);
+    if (rc != 0) { dcsr_free(RA); return rc; }
+    rc = upload_dcsr(P, n_fine, n_coarse, (const long *)Pp, Pj, (const c128 *)Px);
+    lap("P to HBM");
+    amg_galerkin *g = new amg_galerkin;
+    g->is_c128 = true;
+    if (rc == 0) rc = matmat(RA, P, g->Cz);
+    lap("(R*A)*P");
+    dcsr_free(P); dcsr_free(RA);
+    if (rc != 0) { dcsr_free(g->Cz); delete g; return rc; }
+    if (hipMemcpy(Cp, g->Cz.Ap, sizeof(long) * ((size_t)n_coarse + 1), hipMemcpyDeviceToHost) != hipSuccess) {
+        dcsr_free(g->Cz); delete g;
+        set_error("galerkin: row pointer download failed");
+        return AMG_ENODEV;
+    }
+    *out = g;
+    return 0;
+}
+
+// columns and interleaved values (Cp[n] entries each) of a complex128 product to the host; releases it
+int amg_galerkin_fetch_c128(amg_galerkin *g, int *Cj, void *Cx)
+{
+    if (!g) return AMG_EINVAL;
+    if (!g->is_c128) { set_error("galerkin: a float64 product is fetched with amg_galerkin_fetch"); return AMG_EINVAL; }
+    int rc = 0;
+    if (g->Cz.nnz > 0) {
+        if (hipMemcpy(Cj, g->Cz.Aj, sizeof(int) * (size_t)g->Cz.nnz, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(Cx, g->Cz.Ax, sizeof(c128) * (size_t)g->Cz.nnz, hipMemcpyDeviceToHost) != hipSuccess) {
+            set_error("galerkin: download failed");
+            rc = AMG_ENODEV;
+        }
+    }
+    dcsr_free(g->Cz);
+    delete g;
+    return rc;
 }
 
 }   // extern "C"

@@ -9,6 +9,8 @@ import scipy.linalg
 from scipy.sparse import bsr_matrix, csr_matrix, isspmatrix, isspmatrix_bsr, isspmatrix_csc, isspmatrix_csr
 
 DEVICE_RHO_MIN_ROWS = 200000   # spectral-radius estimates of larger operators run on the GPU
+# complex128 levels with at least this many rows form their Galerkin product on the GPU; None: never (scipy's products)
+DEVICE_GALERKIN_C128_MIN_ROWS = None
 
 __all__ = ["type_prep", "to_type", "get_diagonal", "get_block_diag", "scale_rows", "norm",
            "approximate_spectral_radius", "upcast"]
@@ -75,8 +77,9 @@ def get_diagonal(A, norm_eq=False, inv=False):
 
 def get_block_diag(A, blocksize, inv_flag=True):
     """util/utils.py:591-683.  The reference inverts the blocks with its own
-    SVD routine (amg_core.pinv_array); LAPACK's pinv is used here -- the result
-    is a setup constant handed to the smoother as Dinv."""
+    SVD routine (amg_core.pinv_array); LAPACK's pinv is used here for real
+    blocks and a one-sided Jacobi SVD that rounds as that routine does for
+    complex128 ones -- the result is a setup constant handed to the smoother as Dinv."""
     if not isspmatrix(A):
         raise TypeError("Expected sparse matrix")
     if A.shape[0] != A.shape[1]:
@@ -96,7 +99,13 @@ def get_block_diag(A, blocksize, inv_flag=True):
     brow = np.repeat(np.arange(nb, dtype=np.int64), np.diff(A.indptr))
     at = np.nonzero(A.indices == brow)[0]
     block_diag[brow[at]] = A.data[at]
-    if inv_flag:
+    if inv_flag and A.dtype == np.complex128:
+        # complex128: a one-sided Jacobi SVD on the host (csrc/setup_host.cpp) with the reference's rounding -- the
+        # spectral-radius estimate of the next level turns LAPACK's last-bit differences into 1e-10 ones
+        from .aggregation import host_lib
+        block_diag = np.ascontiguousarray(block_diag)
+        host_lib().amgsetup_pinv_blocks_c128(block_diag.ctypes.data, nb, blocksize)
+    elif inv_flag:
         # pseudo-inverse of every block (the reference: amg_core.pinv_array, an SVD per block), batched;
         # LAPACK runs without the GIL, so large inputs are cut into chunks for a few host threads
         step = 1 << 16
@@ -119,17 +128,41 @@ def get_block_diag(A, blocksize, inv_flag=True):
     return block_diag
 
 
+def complex_product(a, b):
+    """a * b for complex arrays as (ar br - ai bi, ar bi + ai br), every multiply, the difference and the sum a
+    real ufunc call of its own: the rounding of the compiled kernels (csrc/scalar.hpp).  numpy's complex array
+    product may be FMA-contracted on AVX-512 hosts."""
+    a = np.asarray(a, dtype=np.complex128)
+    b = np.asarray(b, dtype=np.complex128)
+    ar, ai, br, bi = a.real, a.imag, b.real, b.imag
+    out = np.empty(np.broadcast(a, b).shape, dtype=np.complex128)
+    out.real = np.subtract(np.multiply(ar, br), np.multiply(ai, bi))
+    out.imag = np.add(np.multiply(ar, bi), np.multiply(ai, br))
+    return out
+
+
+def _is_complex(*arrays):
+    return any(np.dtype(getattr(a, "dtype", np.float64)).kind == "c" for a in arrays)
+
+
 def scale_rows(A, v, copy=True):
-    """util/utils.py:133-200 (CSR/BSR(1,1))"""
+    """util/utils.py:133-200 (CSR/BSR(1,1)); complex values through complex_product, as csr_scale_rows /
+    bsr_scale_rows form them"""
     v = np.ravel(v)
     if isspmatrix_bsr(A):
         R, C = A.blocksize
         A = bsr_matrix(A, copy=copy)
         per_block = np.repeat(v.reshape(-1, R), np.diff(A.indptr), axis=0)      # (nblocks, R)
-        A.data = A.data * per_block[:, :, None]
+        if _is_complex(A, v):
+            A.data = complex_product(A.data, per_block[:, :, None])
+        else:
+            A.data = A.data * per_block[:, :, None]
         return A
     A = csr_matrix(A, copy=copy)
-    A.data = A.data * np.repeat(v, np.diff(A.indptr))
+    if _is_complex(A, v):
+        A.data = complex_product(A.data, np.repeat(v, np.diff(A.indptr)))
+    else:
+        A.data = A.data * np.repeat(v, np.diff(A.indptr))
     return A
 
 
@@ -146,6 +179,8 @@ def _approximate_eigenvalues(A, tol, maxiter, symmetric=None, initial_guess=None
     maxiter = min(A.shape[0], maxiter)
     if initial_guess is None:
         v0 = np.random.rand(A.shape[1], 1)
+        if A.dtype == complex:                                  # util/linalg.py:205-206: a second draw
+            v0 = v0 + 1.0j * np.random.rand(A.shape[1], 1)
     else:
         v0 = initial_guess
     v0 = v0 / norm(v0)
@@ -183,7 +218,8 @@ def _check_estimate_arguments(A, maxiter, restart):
 def approximate_spectral_radius(A, tol=0.01, maxiter=15, restart=5, symmetric=None,
                                 initial_guess=None, return_vector=False):
     """util/linalg.py:282-416.  Consumes the global numpy RNG exactly like the
-    reference (one rand(n,1) per call), so seeded runs give the same rho."""
+    reference (one rand(n,1) per call, a second one for the imaginary part when
+    the operator is complex128), so seeded runs give the same rho."""
     if not hasattr(A, "rho") or return_vector:
         _check_estimate_arguments(A, maxiter, restart)
     if (not hasattr(A, "rho")) and (not return_vector) and initial_guess is None and isspmatrix(A) \
@@ -193,6 +229,8 @@ def approximate_spectral_radius(A, tol=0.01, maxiter=15, restart=5, symmetric=No
     if not hasattr(A, "rho") or return_vector:
         if initial_guess is None:
             v0 = np.random.rand(A.shape[1], 1)
+            if A.dtype == complex:                              # util/linalg.py:368-369: a second draw
+                v0 = v0 + 1.0j * np.random.rand(A.shape[1], 1)
         else:
             v0 = np.array(initial_guess.reshape(-1, 1), dtype=A.dtype)
         for j in range(restart + 1):
@@ -304,8 +342,29 @@ def galerkin_device(A, R, P, n_coarse):
     """(R*A)*P on the GPU with scipy's csr_matmat arithmetic and output order (csrc/spgemm.hip), A being the HBM copy
     the spectral-radius estimate left behind (device_operator); R, P = (indptr int64, indices int32, data f64).
     Returns (Cp, Cj, Cx) or None when the device path does not apply (no HBM copy, operator not held as CSR, a row too
-    long for the device tables) -- the caller then runs its host products."""
+    long for the device tables) -- the caller then runs its host products.
+    A complex128 operator is handed in as host arrays, A = (indptr, indices, data) like R and P."""
     import ctypes as C
+    if isinstance(A, tuple):
+        # complex128: A = (indptr int64, indices int32, data complex128) on the host, like R and P; the three operands
+        # go to HBM for the product and R*A stays there (amg_galerkin_device_c128)
+        from . import _lib
+        L = _lib.lib()
+        (Ap, Aj, Ax), (Rp, Rj, Rx), (Pp, Pj, Px) = A, R, P
+        if not all(x.dtype == np.complex128 for x in (Ax, Rx, Px)):
+            raise TypeError("galerkin_device: complex128 values expected")
+        Cp = np.empty(n_coarse + 1, dtype=np.int64)
+        g = C.c_void_p()
+        rc = L.amg_galerkin_device_c128(len(Ap) - 1, int(n_coarse), Rp.ctypes.data, Rj.ctypes.data, Rx.ctypes.data,
+                                        Ap.ctypes.data, Aj.ctypes.data, Ax.ctypes.data,
+                                        Pp.ctypes.data, Pj.ctypes.data, Px.ctypes.data, Cp.ctypes.data, C.byref(g))
+        if rc != 0:
+            return None
+        nnz = int(Cp[n_coarse])
+        Cj = np.empty(nnz, dtype=np.intc)
+        Cx = np.empty(nnz, dtype=np.complex128)
+        _lib.check(L.amg_galerkin_fetch_c128(g, Cj.ctypes.data, Cx.ctypes.data))
+        return Cp, Cj, Cx
     op = getattr(A, "_amg_devop", None)
     if op is None or not getattr(op, "h", None):
         return None

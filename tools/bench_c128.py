@@ -6,6 +6,12 @@ AMG_STENCIL=0 AMG_PATTERN=0 AMG_SELL=0) for a like-for-like ratio.  Prints one J
 Hierarchy: piecewise-constant 2x2x2 aggregation down to <= 1000 unknowns, Galerkin products by scipy, dense coarse
 solve; Chebyshev coefficients from a Gershgorin bound (no estimate).  Device events time `--cycles` V-cycles after
 `--warmup` ones.  Usage:  python tools/bench_c128.py [--n 160] [--cycles 20] [--warmup 3]
+
+--sa builds the hierarchy with pyamg_amd.smoothed_aggregation_solver instead (symmetry='hermitian', max_coarse=1000,
+Chebyshev(2) smoothers from the estimated spectral radius), prints the setup seconds on stderr and in the JSON line
+("setup_s"), and turns AMG_SETUP_VERBOSE on so that the library prints its stage split; AMG_SETUP_DEVICE_GALERKIN=0
+selects scipy's Galerkin products (the library's default for complex levels; the tool lowers
+util.DEVICE_GALERKIN_C128_MIN_ROWS to the float64 row gate so that the device products run).  The float64 counterpart is then the float64 setup of |A|.
 """
 import argparse
 import json
@@ -73,6 +79,21 @@ def hierarchy(A, n):
     return ml
 
 
+def sa_hierarchy(A):
+    import time
+    import pyamg_amd
+    cheb = ("chebyshev", {"degree": 2})
+    # the Galerkin products of the complex levels on the device, from the row gate of the float64 setup on
+    pyamg_amd.util.DEVICE_GALERKIN_C128_MIN_ROWS = pyamg_amd.util.DEVICE_RHO_MIN_ROWS
+    np.random.seed(0)
+    t0 = time.perf_counter()
+    ml = pyamg_amd.smoothed_aggregation_solver(A, symmetry="hermitian", max_coarse=1000, presmoother=cheb, postsmoother=cheb)
+    dt = time.perf_counter() - t0
+    print("[bench_c128] smoothed_aggregation_solver (%s, %d unknowns): %.2f s, levels %s"
+          % (A.dtype, A.shape[0], dt, [lvl.A.shape[0] for lvl in ml.levels]), file=sys.stderr, flush=True)
+    return ml, dt
+
+
 def time_cycles(ml, b, cycles, warmup):
     dev = ml.device_hierarchy()
     x = np.zeros_like(b)
@@ -99,20 +120,34 @@ def main():
     ap.add_argument("--cycles", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--skip-f64", action="store_true")
+    ap.add_argument("--sa", action="store_true", help="build the hierarchy with smoothed_aggregation_solver")
     a = ap.parse_args()
+    if a.sa:
+        os.environ.setdefault("AMG_SETUP_VERBOSE", "1")
     A = magnetic3d(a.n, 0.05, seed=1)
     rng = np.random.RandomState(2)
     b = rng.rand(A.shape[0]) + 1j * rng.rand(A.shape[0])
-    ml = hierarchy(A, a.n)
+    setup_s = None
+    if a.sa:
+        ml, setup_s = sa_hierarchy(A)
+    else:
+        ml = hierarchy(A, a.n)
     ms, dbytes, x = time_cycles(ml, b, a.cycles, a.warmup)
     out = {"metric": "c128_vcycle_ms", "n": a.n, "unknowns": int(A.shape[0]), "levels": len(ml.levels),
            "ms_per_cycle": ms, "device_bytes": dbytes, "level0_bytes_per_cycle": level0_bytes(ml, 16),
            "finite": bool(np.all(np.isfinite(x)))}
     out["level0_TBps"] = out["level0_bytes_per_cycle"] / (ms * 1e-3) / 1e12
+    if a.sa:
+        out["hierarchy"] = "smoothed_aggregation"
+        out["setup_s"] = setup_s
+        out["device_galerkin"] = os.environ.get("AMG_SETUP_DEVICE_GALERKIN", "1") != "0"
     del ml
     if not a.skip_f64:
         Ar = sps.csr_matrix((np.abs(A.data), A.indices, A.indptr), shape=A.shape)
-        mlr = hierarchy(Ar, a.n)
+        if a.sa:
+            mlr, out["f64_setup_s"] = sa_hierarchy(Ar)
+        else:
+            mlr = hierarchy(Ar, a.n)
         ms64, _, _ = time_cycles(mlr, np.ascontiguousarray(b.real), a.cycles, a.warmup)
         out["f64_csr_ms_per_cycle"] = ms64
         out["f64_level0_bytes_per_cycle"] = level0_bytes(mlr, 8)
