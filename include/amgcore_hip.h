@@ -610,10 +610,50 @@ int amg_hierx_finalize(amg_hierx *h);
  * residuals (maxiter + 1 doubles) receive the residual norms, *nres their count */
 int amg_hierx_solve(amg_hierx *h, const void *b, void *x, double tol, int maxiter, int cycle, double *residuals,
                     int *nres, int flags);
-/* one cycle of x for the right-hand side b (HOST vectors); AMG_SOLVE_X0_ZERO: start from zero */
+/* one cycle of x for the right-hand side b; AMG_SOLVE_X0_ZERO: start from zero.  HOST vectors, or with
+ * AMG_SOLVE_DEVICE_VECTORS device vectors: copied in and out on the hierarchy's stream, without synchronising */
 int amg_hierx_cycle(amg_hierx *h, const void *b, void *x, int cycle, int flags);
 long amg_hierx_device_bytes(amg_hierx *h);
 double amg_hierx_last_solve_ms(amg_hierx *h);
+
+/* ---- device-resident vectors for the Krylov methods that wrap the cycle (pyamg_amd/krylov_c128.py): vectors of
+ * the hierarchy's value type live in HBM; only scalars cross PCIe.  All work is ordered on amg_hierx_stream(h). */
+void *amg_hierx_stream(amg_hierx *h);
+int amg_hierx_level_size(amg_hierx *h, int lvl);             /* rows of A_lvl, -1 for a bad level */
+/* y = A_lvl x on DEVICE vectors (x and y distinct): each row summed from zero in stored order, as in the cycle */
+int amg_hierx_apply(amg_hierx *h, int lvl, const void *x_dev, void *y_dev);
+/* a zeroed device vector of n values, counted in amg_hierx_device_bytes until freed with the same n */
+void *amg_hierx_vec_alloc(amg_hierx *h, long n);
+void amg_hierx_vec_free(amg_hierx *h, void *p, long n);
+/* the hierarchy's scratch of the amg_devx_* reductions: AMG_DEVX_PARTIALS partial sums, then AMG_DEVX_SLOTS result
+ * slots (one value of the hierarchy's type each); allocated on first use, NULL on failure */
+#define AMG_DEVX_PARTIALS 512
+#define AMG_DEVX_SLOTS    8
+void *amg_hierx_scratch(amg_hierx *h);
+/* *host = ||v||_2 of n device values (v may point into a vector): the residual norm's two-stage reduction; one
+ * 8-byte read-back, stream synchronised */
+int amg_hierx_norm(amg_hierx *h, const void *v_dev, long n, double *host);
+
+/* complex128 vector kernels on caller-supplied DEVICE pointers and stream (scratch: amg_hierx_scratch).
+ * zdotc: slot <- sum_k conj(x_k) y_k in a fixed order that depends on n alone; host != NULL: also copied there
+ * (two doubles) with the stream synchronised */
+int amg_devx_zdotc(const void *x, const void *y, long n, void *scratch, int slot, double *host, void *stream);
+int amg_devx_axpy(void *y, const void *x, double are, double aim, long n, void *stream);          /* y += a x */
+/* y += (factor * slot) x, the complex scalar read from the result slot on the device */
+int amg_devx_axpy_slot(void *y, const void *x, const void *scratch, int slot, double factor, long n, void *stream);
+int amg_devx_xpby(void *p, double bre, double bim, const void *z, long n, void *stream);          /* p = beta p + z */
+int amg_devx_scale(void *out, const void *x, double cre, double cim, long n, void *stream);       /* out = c x */
+int amg_devx_sub(void *out, const void *a, const void *b, long n, void *stream);                  /* out = a - b */
+int amg_devx_fill(void *x, double vre, double vim, long n, void *stream);
+/* n values; kind: 0 host->device, 1 device->host, 2 device->device; host copies synchronous on return */
+int amg_devx_copy(void *dst, const void *src, long n, int kind, void *stream);
+/* for j = start, start + step, ... (stop excluded): v <- v - 2 <W[j], v> W[j] (amg_core/krylov.h:34-53).  W: HOST
+ * array of nW device vectors.  Every inner product stays on the device (slot 0): no host synchronisation. */
+int amg_devx_householders(void *v, const void *const *W, int nW, long n, int start, int stop, int step,
+                          void *scratch, void *stream);
+/* the same with v[j] += y[j] before reflector j (householder_hornerscheme, krylov.h:97-120); y: DEVICE vector */
+int amg_devx_horner(void *v, const void *const *W, int nW, const void *y, long n, int start, int stop, int step,
+                    void *scratch, void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* 6. Resident float64 hierarchies for SEVERAL right-hand sides: the cycle   */

@@ -4,7 +4,7 @@ relaxation kernels of PyAMG) on AMD MI355X through hand-written HIP.
     from pyamg_amd import ruge_stuben_solver, smoothed_aggregation_solver, solve, multilevel_solver
 """
 from . import _lib
-from . import amg_core, relaxation, smoothing, util
+from . import amg_core, krylov_c128, relaxation, smoothing, util
 from .multilevel import coarse_grid_solver, multilevel_solver
 from .smoothing import change_smoothers
 from .classical import ruge_stuben_solver
@@ -14,7 +14,7 @@ from .blackbox import solve, solver, solver_configuration
 # the package-level names of the reference (pyamg/__init__.py:61-65) that live on this path
 __all__ = ["multilevel_solver", "coarse_grid_solver", "change_smoothers", "ruge_stuben_solver",
            "smoothed_aggregation_solver", "solve", "solver", "solver_configuration", "amg_core", "relaxation",
-           "smoothing", "util", "device_count"]
+           "smoothing", "util", "krylov_c128", "device_count"]
 
 
 def device_count():

@@ -182,6 +182,18 @@ def lib():
         "amg_hierx_finalize": [V],
         "amg_hierx_solve": [V, V, V, D, I, I, c_dbl_p, c_int_p, I],
         "amg_hierx_cycle": [V, V, V, I, I],
+        "amg_hierx_apply": [V, I, V, V],
+        "amg_hierx_norm": [V, V, C.c_long, C.POINTER(C.c_double)],
+        "amg_devx_zdotc": [V, V, C.c_long, V, I, C.POINTER(C.c_double), V],
+        "amg_devx_axpy": [V, V, D, D, C.c_long, V],
+        "amg_devx_axpy_slot": [V, V, V, I, D, C.c_long, V],
+        "amg_devx_xpby": [V, D, D, V, C.c_long, V],
+        "amg_devx_scale": [V, V, D, D, C.c_long, V],
+        "amg_devx_sub": [V, V, V, C.c_long, V],
+        "amg_devx_fill": [V, D, D, C.c_long, V],
+        "amg_devx_copy": [V, V, C.c_long, I, V],
+        "amg_devx_householders": [V, C.POINTER(V), I, C.c_long, I, I, I, V, V],
+        "amg_devx_horner": [V, C.POINTER(V), I, V, C.c_long, I, I, I, V, V],
         # section 6: several right-hand sides
         "amg_hierm_create": [I, I, I, C.POINTER(C.c_void_p)],
         "amg_hierm_set_matrix": [V, I, I, I, I, I, I, I, V, V, V],
@@ -213,6 +225,16 @@ def lib():
     L.amg_hierx_device_bytes.restype = C.c_long
     L.amg_hierx_last_solve_ms.argtypes = [V]
     L.amg_hierx_last_solve_ms.restype = D
+    L.amg_hierx_stream.argtypes = [V]
+    L.amg_hierx_stream.restype = V
+    L.amg_hierx_scratch.argtypes = [V]
+    L.amg_hierx_scratch.restype = V
+    L.amg_hierx_level_size.argtypes = [V, I]
+    L.amg_hierx_level_size.restype = I
+    L.amg_hierx_vec_alloc.argtypes = [V, C.c_long]
+    L.amg_hierx_vec_alloc.restype = V
+    L.amg_hierx_vec_free.argtypes = [V, V, C.c_long]
+    L.amg_hierx_vec_free.restype = None
     L.amg_hierm_destroy.argtypes = [V]
     L.amg_hierm_destroy.restype = None
     L.amg_hierm_device_bytes.argtypes = [V]

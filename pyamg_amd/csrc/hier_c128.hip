@@ -269,6 +269,7 @@ struct Engine : Core {
     amg_coarse_callback_x cb = nullptr;
     void *cb_user = nullptr;
     std::vector<T> hb, hx;
+    DBuf kscr;                            // scratch of the amg_devx_* reductions, then one double for a norm
 };
 
 // ----------------------------------------------------------------------------------------------- smoothers
@@ -628,8 +629,30 @@ int cycle(Engine<T> &E, const void *b, void *x, int cyc, int flags)
         set_error(cyc == 3 ? "AMLI cycles are not implemented for this value type" : "bad cycle arguments");
         return cyc == 3 ? AMG_ENOTIMPL : AMG_EINVAL;
     }
+    if (flags & AMG_SOLVE_DEVICE_VECTORS) {         // b, x in HBM: copies on the stream, nothing waits for them
+        XLevel<T> &L = E.lv[0];
+        const size_t vbytes = sizeof(T) * (size_t)L.A.nrows;
+        if (!vbytes) return 0;
+        AMG_HIP(hipMemcpyAsync(L.b.p, b, vbytes, hipMemcpyDeviceToDevice, E.st));
+        if (flags & AMG_SOLVE_X0_ZERO) AMG_HIP(hipMemsetAsync(L.x.p, 0, vbytes, E.st));
+        else AMG_HIP(hipMemcpyAsync(L.x.p, x, vbytes, hipMemcpyDeviceToDevice, E.st));
+        CHK(one_cycle(XCycle<T>{E}, E.nlev, cyc));
+        AMG_HIP(hipMemcpyAsync(x, L.x.p, vbytes, hipMemcpyDeviceToDevice, E.st));
+        return 0;
+    }
     CHK(load_vectors(E, b, x, flags));
     return E.timed([&] { return one_cycle(XCycle<T>{E}, E.nlev, cyc); }, [&] { return store_x(E, x); });
+}
+
+// the scratch of the device Krylov methods: partial sums and result slots of zdotc, then the slot of a norm
+constexpr size_t KSCR_VALUES = AMG_DEVX_PARTIALS + AMG_DEVX_SLOTS + 1;
+template <class T>
+int krylov_scratch(Engine<T> &E)
+{
+    if (E.kscr.p) return 0;
+    CHK(E.pool.alloc(E.kscr, sizeof(T) * KSCR_VALUES));
+    AMG_HIP(hipMemset(E.kscr.p, 0, sizeof(T) * KSCR_VALUES));
+    return 0;
 }
 
 using C128 = Engine<c128>;
@@ -731,6 +754,67 @@ int amg_hierx_cycle(amg_hierx *h, const void *b, void *x, int cyc, int flags)
 {
     ENTER(h);
     return cycle(h->e, b, x, cyc, flags);
+}
+
+void *amg_hierx_stream(amg_hierx *h) { return h ? (void *)h->e.st : nullptr; }
+
+int amg_hierx_level_size(amg_hierx *h, int lvl)
+{
+    if (!h || lvl < 0 || lvl >= h->e.nlev || !h->e.lv[lvl].A.set) return -1;
+    return h->e.lv[lvl].A.nrows;
+}
+
+int amg_hierx_apply(amg_hierx *h, int lvl, const void *x_dev, void *y_dev)
+{
+    ENTER(h);
+    C128 &E = h->e;
+    if (!E.finalized) { set_error("hierarchy not finalised"); return AMG_ESTATE; }
+    if (lvl < 0 || lvl >= E.nlev || !x_dev || !y_dev || x_dev == y_dev) { set_error("bad apply arguments"); return AMG_EINVAL; }
+    return apply_rows(E.lv[lvl].A, (const c128 *)x_dev, EpiStore<c128>{(c128 *)y_dev}, E.st);
+}
+
+void *amg_hierx_vec_alloc(amg_hierx *h, long n)
+{
+    if (!h || n < 0 || hipSetDevice(h->e.device) != hipSuccess) { set_error("bad vector allocation"); return nullptr; }
+    void *p = nullptr;
+    const size_t bytes = sizeof(c128) * (size_t)n;
+    if (hipMalloc(&p, bytes + 128) != hipSuccess) { set_error("device allocation failed"); return nullptr; }
+    if (hipMemset(p, 0, bytes + 128) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        hipFree(p);
+        set_error("device allocation failed");
+        return nullptr;
+    }
+    h->e.pool.bytes += (long)bytes;
+    return p;
+}
+
+void amg_hierx_vec_free(amg_hierx *h, void *p, long n)
+{
+    if (!h || !p) return;
+    hipSetDevice(h->e.device);
+    hipStreamSynchronize(h->e.st);
+    hipFree(p);
+    h->e.pool.bytes -= (long)(sizeof(c128) * (size_t)n);
+}
+
+void *amg_hierx_scratch(amg_hierx *h)
+{
+    if (!h || hipSetDevice(h->e.device) != hipSuccess || krylov_scratch(h->e) != 0) return nullptr;
+    return h->e.kscr.p;
+}
+
+int amg_hierx_norm(amg_hierx *h, const void *v_dev, long n, double *host)
+{
+    ENTER(h);
+    C128 &E = h->e;
+    if (!E.finalized) { set_error("hierarchy not finalised"); return AMG_ESTATE; }
+    if (!v_dev || !host || n < 0) { set_error("bad norm arguments"); return AMG_EINVAL; }
+    CHK(krylov_scratch(E));
+    double *slot = (double *)((c128 *)E.kscr.p + AMG_DEVX_PARTIALS + AMG_DEVX_SLOTS);
+    CHK(device_norm(E, (const c128 *)v_dev, n, slot));
+    AMG_HIP(hipMemcpyAsync(host, slot, sizeof(double), hipMemcpyDeviceToHost, E.st));
+    AMG_HIP(hipStreamSynchronize(E.st));
+    return 0;
 }
 
 long amg_hierx_device_bytes(amg_hierx *h) { return h ? h->e.pool.bytes : 0; }

@@ -520,6 +520,10 @@ class _DeviceHierarchyC128(_ResidentHierarchy):
         self._check(self.L.amg_hierx_cycle(self.h, b.ctypes.data, x.ctypes.data, _CYCLE[cycle],
                                            _X0_ZERO if x0_zero else 0))
 
+    def cycle_device(self, b_dev, x_dev, cycle):
+        """x = one cycle from a zero guess for the right-hand side b, both device vectors (pyamg_amd.krylov_c128)"""
+        self._check(self.L.amg_hierx_cycle(self.h, b_dev, x_dev, _CYCLE[cycle], _X0_ZERO | _DEVICE_VECTORS))
+
 
 _MULTI_KIND = {None: 0, "None": 0, "jacobi": 1, "gauss_seidel": 2, "sor": 3, "polynomial": 4}
 _MULTI_KMAX = 8          # widest column layout of the engine; more columns run in groups
@@ -813,7 +817,9 @@ class multilevel_solver:
             if not use:
                 return np.hstack([matvec(X[:, j]).reshape(-1, 1) for j in range(X.shape[1])])
             return self.solve_many(X, maxiter=1, cycle=cycle, tol=1e-12)
-        return LinearOperator(shape, matvec, matmat=matmat, dtype=dtype)
+        op = LinearOperator(shape, matvec, matmat=matmat, dtype=dtype)
+        op.hierarchy, op.cycle = self, cycle          # what pyamg_amd.krylov_c128 looks for in its M
+        return op
 
     def _check_many(self, cycle):
         """what solve_many refuses about the hierarchy and the cycle, before any device work; returns the cycle's name"""
@@ -987,6 +993,11 @@ class multilevel_solver:
                 raise NotImplementedError(
                     "the device Krylov methods are float64 only; for a complex128 hierarchy pass a scipy.sparse.linalg "
                     "callable as accel, or use aspreconditioner() as M")
+            from . import krylov_c128
+            if any(accel is f for f in krylov_c128.METHODS.values()):
+                # the complex128 device methods: vectors stay in HBM, the cycle is M
+                return accel(self.levels[0].A, b, x0=x0, tol=tol, maxiter=maxiter, M=self.aspreconditioner(cycle=cycle),
+                             callback=callback, residuals=residuals)[0]
             _DeviceHierarchyC128.check_levels(self)
             return self._solve_accel(b, x0, tol, maxiter, cycle, accel, callback, residuals)
         if return_residuals:
