@@ -1,14 +1,19 @@
-"""Krylov methods around the device-resident cycle -- the methods of /root/reference/pyamg/krylov that
+"""Krylov methods around the device-resident cycle -- the methods of the reference's pyamg/krylov that
 `multilevel_solver.solve(accel=...)` (multilevel.py:381-422), the Krylov smoothers (relaxation/smoothing.py:481-509) and
 the Krylov coarse solvers (multilevel.py:642-660) reach for.
+
+Every method body exists once, here, written against a vector space V (VectorSpace lists what V provides): DeviceSpace
+holds the float64 vectors of one level, krylov_c128.DeviceSpaceC128 the complex128 ones, tests/krylov_numpy.py host
+arrays of either dtype.  cg, bicgstab, gmres and fgmres run in both dtypes and follow the reference line by line --
+conjugated inner products, mysign(x) = x / |x|, the Givens block [[c, s], [-conj(s), c]] -- all of which are the plain
+real formulas on real numbers; cr, steepest_descent, minimal_residual, cgne and cgnr are float64 only.
 
 Every vector lives in HBM: operator applications, preconditioner cycles and BLAS-1 updates are kernels on the hierarchy's
 stream (include/amgcore_hip.h: amg_hier_apply, amg_hier_cycle with device vectors, amg_dev_*); what crosses PCIe per
 iteration is a handful of scalars -- inner products, norms and, for the Householder GMRES variants, the few leading
-entries of one vector that form the next Hessenberg column.  The iteration logic itself (what is computed from what,
-stopping rules, residual-history semantics) follows the reference method by method; inner products are fixed-order device
-reductions where the reference calls BLAS, so histories agree to rounding (pinned against histories the reference itself
-produced: tests/golden/hier_accel_*.npz).
+entries of one vector that form the next Hessenberg column.  Inner products are fixed-order device reductions where the
+reference calls BLAS, so histories agree to rounding (pinned against histories the reference itself produced:
+tests/golden/hier_accel_*.npz, tests/golden/accel_c128/).
 """
 import ctypes as C
 
@@ -17,15 +22,58 @@ import scipy.linalg
 
 from . import _lib
 
-__all__ = ["cg", "fgmres", "gmres", "bicgstab", "cgne", "cgnr", "DeviceSpace"]
+__all__ = ["cg", "fgmres", "gmres", "bicgstab", "cgne", "cgnr", "DeviceSpace", "VectorSpace"]
 
 _H2D, _D2H, _D2D = 0, 1, 2
 
 
-class DeviceSpace(object):
-    """Vectors of one level of a device hierarchy plus the three operators a Krylov method needs:
+class VectorSpace(object):
+    """What the methods below need of a space V, and the parts that are the same in every space.  A space provides n,
+    dtype (np.float64 | np.complex128: the type of H, g and Q, and the key of the Givens arithmetic), new / upload /
+    download / poke / peek, copy / fill / scale / axpy / xpby / sub, dot (sum conj(x_i) y_i) / norm, and the operators
+    A, M and -- cgne / cgnr only -- AH.  dot and peek return the scalars the recurrences then compute with: a Python
+    float (so a zero <Ap, p> raises ZeroDivisionError and the root of a negative <r, z> is a real NaN) or an
+    np.complex128, never a Python complex, whose division rounds differently from numpy's.  A space that allocates
+    lists what it owns in _owned and frees one entry in _free."""
+    dtype = np.float64
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.release()
+
+    def release(self):
+        for p in self._owned:
+            self._free(p)
+        self._owned = []
+
+    def residual(self, out, b, x, tmp):               # out = b - A x
+        self.A(x, tmp)
+        self.sub(out, b, tmp)
+
+    def reflectors(self, limit):
+        """storage for the (up to `limit`) Householder or preconditioned vectors of a restart cycle.  All of it at once
+        here: an allocation synchronises the device, and the Krylov smoothers build a space per application"""
+        return [self.new() for _ in range(limit)]
+
+    def reflect_range(self, v, W, start, stop, step):
+        """for j in range(start, stop, step): v <- v - 2 <W[j], v> W[j]  (amg_core/krylov.h:34-53)"""
+        for j in range(start, stop, step):
+            self.axpy(v, -2.0 * self.dot(W[j], v), W[j])
+
+    def horner(self, v, W, y, inner):
+        """for j = inner .. 0: v[j] += y[j]; v <- v - 2 <W[j], v> W[j]  (amg_core/krylov.h:97-120)"""
+        for j in range(inner, -1, -1):
+            self.poke(v, j, self.peek(v, j) + y[j])
+            self.reflect_range(v, W, j, j - 1, -1)
+
+
+class DeviceSpace(VectorSpace):
+    """float64 vectors of one level of a device hierarchy plus the three operators a Krylov method needs:
     A (the level operator), AH (its transpose, when uploaded as the smoother slot's auxiliary operator) and
-    M (one multigrid cycle from a zero guess -- level 0 only -- or the identity)."""
+    M (one multigrid cycle from a zero guess -- level 0 only -- or the identity).  One inner product per reflector
+    comes to the host (VectorSpace.reflect_range)."""
 
     def __init__(self, dev, lvl=0, cycle=None, aux=None):
         self.L = _lib.lib()
@@ -50,16 +98,8 @@ class DeviceSpace(object):
         self._owned.append(p)
         return p
 
-    def release(self):
-        for p in self._owned:
-            self.L.amg_dev_free(p)
-        self._owned = []
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.release()
+    def _free(self, p):
+        self.L.amg_dev_free(p)
 
     def upload(self, host, dst=None):
         host = np.ascontiguousarray(np.ravel(host), dtype=np.float64)
@@ -129,48 +169,56 @@ class DeviceSpace(object):
         else:
             self.dev.cycle_device(r, out, self.cycle)
 
-    def residual(self, out, b, x, tmp):               # out = b - A x
-        self.A(x, tmp)
-        self.sub(out, b, tmp)
+
+def _mysign(x):
+    """the sign x / |x| (krylov/_fgmres.py:16-21, _gmres_householder.py:16-21)"""
+    return 1.0 if x == 0.0 else x / abs(x)
 
 
-def _sign(v):
-    return 1.0 if v == 0 else float(np.sign(v))
+def _maxiter(maxiter, default):
+    if maxiter is None:
+        return default
+    if maxiter < 1:
+        raise ValueError("Number of iterations must be positive")
+    return maxiter
 
 
-def _finish(V, x, x_host_out):
-    if x_host_out is not None:
-        x_host_out[:] = V.download(x)
+def _start(V, b, normr, tol, residuals, callback=None):
+    """What every method does with its first residual norm: open the history, test tol against ||b||, then make tol
+    relative to that norm.  -> the tolerance of the iteration, or None when the initial guess has converged (only the
+    GMRES pair passes its callback, which the reference calls on that exit: _fgmres.py:179-182)"""
+    if residuals is not None:
+        residuals[:] = [normr]
+    normb = V.norm(b) or 1.0
+    if normr < tol * normb:
+        if callback is not None:
+            callback(normr)
+        return None
+    return tol * normr if normr != 0.0 else tol
 
 
 # --------------------------------------------------------------------------- CG family
 def cg(V, b, x, tol=1e-5, maxiter=None, residuals=None, callback=None):
-    """Preconditioned conjugate gradients (krylov/_cg.py:84-179): history in the preconditioner norm sqrt(<r, M r>),
+    """Preconditioned conjugate gradients (krylov/_cg.py:84-183): history in the preconditioner norm sqrt(<r, M r>),
     true residual every 8th iteration, tolerance relative to the first entry.  b, x: device vectors (x updated).
+    The reference stores the complex scalar sqrt(<r, M r>), whose imaginary part is zero for a Hermitian positive
+    definite M: its real part is stored here, and the curvature tests look at real parts.
     -> info (0 converged, -1 indefinite operator / preconditioner, else the iteration count)"""
-    if maxiter is None:
-        maxiter = int(1.3 * V.n) + 2
-    elif maxiter < 1:
-        raise ValueError("Number of iterations must be positive")
+    maxiter = _maxiter(maxiter, int(1.3 * V.n) + 2)
     r, z, p, Ap = V.new(), V.new(), V.new(), V.new()
     V.residual(r, b, x, Ap)
     V.M(r, z)
     V.copy(p, z)
     rz = V.dot(r, z)
-    normr = np.sqrt(rz)
-    if residuals is not None:
-        residuals[:] = [normr]
-    normb = V.norm(b) or 1.0
-    if normr < tol * normb:
+    tol = _start(V, b, float(np.real(np.sqrt(rz))), tol, residuals)
+    if tol is None:
         return 0
-    if normr != 0.0:
-        tol = tol * normr
     it = 0
     while True:
         V.A(p, Ap)
         rz_old = rz
         pAp = V.dot(Ap, p)
-        if pAp < 0.0:
+        if np.real(pAp) < 0:
             return -1
         alpha = rz / pAp
         V.axpy(x, alpha, p)
@@ -180,11 +228,11 @@ def cg(V, b, x, tol=1e-5, maxiter=None, residuals=None, callback=None):
             V.residual(r, b, x, z)
         V.M(r, z)
         rz = V.dot(r, z)
-        if rz < 0.0:
+        if np.real(rz) < 0:
             return -1
         V.xpby(p, rz / rz_old, z)
         it += 1
-        normr = np.sqrt(rz)
+        normr = float(np.real(np.sqrt(rz)))
         if residuals is not None:
             residuals.append(normr)
         if callback is not None:
@@ -198,25 +246,18 @@ def cg(V, b, x, tol=1e-5, maxiter=None, residuals=None, callback=None):
 
 
 def cr(V, b, x, tol=1e-5, maxiter=None, residuals=None, callback=None):
-    """Preconditioned conjugate residuals (krylov/_cr.py:86-187): history sqrt(<z, z>) with z = M r; the true residual is
+    """Preconditioned conjugate residuals (krylov/_cr.py:86-186): history sqrt(<z, z>) with z = M r; the true residual is
     recomputed at iterations 0, 8, 16, ... (`if mod(iter, 8) and iter > 0: r -= alpha Ap else: r = b - A x`)."""
-    if maxiter is None:
-        maxiter = int(1.3 * V.n) + 2
-    elif maxiter < 1:
-        raise ValueError("Number of iterations must be positive")
+    maxiter = _maxiter(maxiter, int(1.3 * V.n) + 2)
     r, z, p, Ap, Az = V.new(), V.new(), V.new(), V.new(), V.new()
     V.residual(r, b, x, Ap)
     V.M(r, z)
     V.copy(p, z)
     zz = V.dot(z, z)
     normr = np.sqrt(zz)
-    if residuals is not None:
-        residuals[:] = [normr]
-    normb = V.norm(b) or 1.0
-    if normr < tol * normb:
+    tol = _start(V, b, normr, tol, residuals)
+    if tol is None:
         return 0
-    if normr != 0.0:
-        tol = tol * normr
     it = 0
     V.A(z, Az)
     rAz = V.dot(r, Az)
@@ -251,24 +292,17 @@ def cr(V, b, x, tol=1e-5, maxiter=None, residuals=None, callback=None):
 
 
 def steepest_descent(V, b, x, tol=1e-5, maxiter=None, residuals=None, callback=None):
-    """Preconditioned steepest descent (krylov/_steepest_descent.py:83-165): history sqrt(<r, M r>); the reference
+    """Preconditioned steepest descent (krylov/_steepest_descent.py:84-169): history sqrt(<r, M r>); the reference
     recomputes r = b - A x whenever `mod(iter, 50)` is non-zero and updates it only at iterations 50, 100, ..."""
-    if maxiter is None:
-        maxiter = int(V.n)
-    elif maxiter < 1:
-        raise ValueError("Number of iterations must be positive")
+    maxiter = _maxiter(maxiter, int(V.n))
     r, z, q = V.new(), V.new(), V.new()
     V.residual(r, b, x, q)
     V.M(r, z)
     rz = V.dot(r, z)
     normr = np.sqrt(rz)
-    if residuals is not None:
-        residuals[:] = [normr]
-    normb = V.norm(b) or 1.0
-    if normr < tol * normb:
+    tol = _start(V, b, normr, tol, residuals)
+    if tol is None:
         return 0
-    if normr != 0.0:
-        tol = tol * normr
     it = 0
     while True:
         it += 1
@@ -300,23 +334,16 @@ def steepest_descent(V, b, x, tol=1e-5, maxiter=None, residuals=None, callback=N
 
 
 def minimal_residual(V, b, x, tol=1e-5, maxiter=None, residuals=None, callback=None):
-    """Preconditioned minimal residual iteration (krylov/_minimal_residual.py:83-145): r = M (b - A x), p = M A r,
+    """Preconditioned minimal residual iteration (krylov/_minimal_residual.py:84-152): r = M (b - A x), p = M A r,
     alpha = <p, r> / <p, p>; history ||r||_2; same recompute pattern as steepest_descent."""
-    if maxiter is None:
-        maxiter = int(V.n)
-    elif maxiter < 1:
-        raise ValueError("Number of iterations must be positive")
+    maxiter = _maxiter(maxiter, int(V.n))
     r, p, t, u = V.new(), V.new(), V.new(), V.new()
     V.residual(t, b, x, u)
     V.M(t, r)
     normr = V.norm(r)
-    if residuals is not None:
-        residuals[:] = [normr]
-    normb = V.norm(b) or 1.0
-    if normr < tol * normb:
+    tol = _start(V, b, normr, tol, residuals)
+    if tol is None:
         return 0
-    if normr != 0.0:
-        tol = tol * normr
     it = 0
     while True:
         it += 1
@@ -344,18 +371,14 @@ def minimal_residual(V, b, x, tol=1e-5, maxiter=None, residuals=None, callback=N
 
 
 def cgne(V, b, x, tol=1e-5, maxiter=None, residuals=None, callback=None):
-    """CG on A A^H y = b, x = A^H y (krylov/_cgne.py:85-170): 2-norm history."""
+    """CG on A A^H y = b, x = A^H y (krylov/_cgne.py:93-198): 2-norm history."""
     maxiter = _ne_maxiter(V.n, maxiter)
     r, z, p, t = V.new(), V.new(), V.new(), V.new()
     V.residual(r, b, x, t)
     normr = V.norm(r)
-    if residuals is not None:
-        residuals[:] = [normr]
-    normb = V.norm(b) or 1.0
-    if normr < tol * normb:
+    tol = _start(V, b, normr, tol, residuals)
+    if tol is None:
         return 0
-    if normr != 0.0:
-        tol = tol * normr
     V.M(r, z)
     V.AH(z, p)
     old_zr = V.dot(z, r)
@@ -384,19 +407,15 @@ def cgne(V, b, x, tol=1e-5, maxiter=None, residuals=None, callback=None):
 
 
 def cgnr(V, b, x, tol=1e-5, maxiter=None, residuals=None, callback=None):
-    """CG on A^H A x = A^H b (krylov/_cgnr.py:85-178): 2-norm history of r = b - A x."""
+    """CG on A^H A x = A^H b (krylov/_cgnr.py:94-206): 2-norm history of r = b - A x."""
     maxiter = _ne_maxiter(V.n, maxiter)
     r, rhat, z, p, w = V.new(), V.new(), V.new(), V.new(), V.new()
     V.residual(r, b, x, w)
     V.AH(r, rhat)
     normr = V.norm(r)
-    if residuals is not None:
-        residuals[:] = [normr]
-    normb = V.norm(b) or 1.0
-    if normr < tol * normb:
+    tol = _start(V, b, normr, tol, residuals)
+    if tol is None:
         return 0
-    if normr != 0.0:
-        tol = tol * normr
     V.M(rhat, z)
     V.copy(p, z)
     old_zr = V.dot(z, rhat)
@@ -434,21 +453,16 @@ def _ne_maxiter(n, maxiter):
 
 
 def bicgstab(V, b, x, tol=1e-5, maxiter=None, residuals=None, callback=None):
-    """Right-preconditioned BiCGStab (krylov/_bicgstab.py:80-150): 2-norm history."""
-    if maxiter is None:
-        maxiter = V.n + 5
-    elif maxiter < 1:
-        raise ValueError("Number of iterations must be positive")
+    """Right-preconditioned BiCGStab (krylov/_bicgstab.py:80-167): 2-norm history, conjugated inner products."""
+    maxiter = _maxiter(maxiter, V.n + 5)
     r, rstar, p, Mp, AMp, s_, Ms, AMs = (V.new() for _ in range(8))
     V.residual(r, b, x, Mp)
     normr = V.norm(r)
-    if residuals is not None:
-        residuals[:] = [normr]
-    normb = V.norm(b) or 1.0
-    if normr < tol * normb:
+    tol = _start(V, b, normr, tol, residuals)
+    if tol is None:
         return 0
-    if normr != 0.0:
-        tol = tol * normr
+    if V.n == 1:
+        return _solve_1x1(V, b, x)
     V.copy(rstar, r)
     V.copy(p, r)
     rr_old = V.dot(rstar, r)
@@ -485,7 +499,7 @@ def bicgstab(V, b, x, tol=1e-5, maxiter=None, residuals=None, callback=None):
 
 # --------------------------------------------------------------------------- GMRES with Householder reflections
 def _inner_limits(n, restrt, maxiter):
-    """(outer, inner) iteration limits (krylov/_fgmres.py:136-155, _gmres_householder.py:130-149)"""
+    """(outer, inner) iteration limits (krylov/_fgmres.py:139-158, _gmres_householder.py:139-158)"""
     if restrt:
         return (maxiter if maxiter else 1), min(int(restrt), n)
     if maxiter is None:
@@ -494,33 +508,67 @@ def _inner_limits(n, restrt, maxiter):
 
 
 def _solve_1x1(V, b, x):
-    """a 1 x 1 system is solved directly: x = b / A[0, 0] (krylov/_fgmres.py:157-160, _gmres_householder.py:151-154)"""
+    """a 1 x 1 system is solved directly: x = b / A[0, 0] (krylov/_fgmres.py:163-166, _gmres_householder.py:163-166,
+    _bicgstab.py:111-114)"""
     e, a = V.new(), V.new()
     V.fill(e, 1.0)
     V.A(e, a)
-    V.copy(x, b)
-    V.scale(x, x, 1.0 / V.peek(a, 0))
+    V.poke(x, 0, V.peek(b, 0) / V.peek(a, 0))
     return 0
 
 
-def _reflect(V, v, W, j):
-    """v <- (I - 2 w_j w_j^T) v  (amg_core/krylov.h:35-53: alpha = <w_j, v>; alpha *= -2; v += alpha w_j)"""
-    V.axpy(v, -2.0 * V.dot(W[j], v), W[j])
+def _first_reflector(V, w, r, normr):
+    """w = r + mysign(r[0]) ||r|| e_0, normalised (krylov/_fgmres.py:200-203); -> beta"""
+    V.copy(w, r)
+    w0 = V.peek(w, 0)
+    beta = _mysign(w0) * normr
+    V.poke(w, 0, w0 + beta)
+    V.scale(w, w, 1.0 / V.norm(w))
+    return beta
+
+
+def _krylov_vector(V, v, W, inner):
+    """v = P_0 ... P_inner e_inner (krylov/_fgmres.py:226-231)"""
+    w = W[inner]
+    V.scale(v, w, -2.0 * np.conjugate(V.peek(w, inner)))
+    V.poke(v, inner, V.peek(v, inner) + 1.0)
+    V.reflect_range(v, W, inner - 1, -1, -1)
+
+
+def _givens_f64(Q, g, head, inner):
+    c, s = scipy.linalg.blas.drotg(head[inner], head[inner + 1])
+    Q[4 * inner:4 * inner + 4] = (c, s, -s, c)
+    g[inner:inner + 2] = (c * g[inner] + s * g[inner + 1], -s * g[inner] + c * g[inner + 1])
+    head[inner] = c * head[inner] + s * head[inner + 1]
+
+
+def _givens_c128(Q, g, head, inner):
+    c, s = scipy.linalg.blas.zrotg(head[inner], head[inner + 1])
+    Qblock = np.array([[c, s], [-np.conjugate(s), c]], dtype=np.complex128)
+    Q[4 * inner:4 * inner + 4] = np.ravel(Qblock)
+    g[inner:inner + 2] = np.dot(Qblock, g[inner:inner + 2])
+    head[inner] = np.dot(Qblock[0, :], head[inner:inner + 2])
+
+
+# The new rotation [[c, s], [-conj(s), c]] from BLAS rotg, stored in Q and applied to g and to the column
+# (krylov/_fgmres.py:287-298).  Each dtype keeps its own arithmetic: np.dot on two entries goes through BLAS and may
+# contract a multiply-add that the scalar expressions round twice, so one form for both would move last bits of one.
+_GIVENS = {np.float64: _givens_f64, np.complex128: _givens_c128}
 
 
 def _hessenberg_step(V, v, W, inner, max_inner, Q, g, H):
-    """The part of one (F)GMRES inner iteration after the operator has been applied and v holds
-    P_inner ... P_0 (A ...) (krylov/_fgmres.py:219-262): the next reflector, then -- on the host, v has at most
-    inner + 2 non-zero leading entries now -- the accumulated Givens rotations, the new rotation, the Hessenberg column."""
+    """The part of one (F)GMRES inner iteration after v holds P_inner ... P_0 (A ...) (krylov/_fgmres.py:250-303): the
+    next reflector, then -- on the host, v has at most inner + 2 non-zero leading entries now -- the accumulated
+    Givens rotations, the new rotation, the Hessenberg column."""
     n = V.n
     if inner != n - 1:
         if inner < max_inner - 1:
-            # the reference starts every restart cycle from zeroed reflectors (W = zeros(...), _fgmres.py:195): after a
-            # breakdown (alpha == 0) the next step must not find the previous cycle's vector here (ADVICE r2)
+            # the reference starts every restart cycle from zeroed reflectors (W = zeros(...), _fgmres.py:212): after
+            # a breakdown (alpha == 0) the next step must not find the previous cycle's vector here
             V.fill(W[inner + 1], 0.0)
         alpha = V.norm(v, off=inner + 1)
         if alpha != 0:
-            alpha = _sign(V.peek(v, inner + 1)) * alpha
+            alpha = _mysign(V.peek(v, inner + 1)) * alpha
             if inner < max_inner - 1:
                 w = W[inner + 1]
                 V.copy(w, v, off=inner + 1)
@@ -530,22 +578,29 @@ def _hessenberg_step(V, v, W, inner, max_inner, Q, g, H):
             V.fill(v, 0.0, off=inner + 2)
     head = V.download(v, min(n, inner + 2))
     for j in range(inner):                            # amg_core/krylov.h apply_givens: rotations 0 .. inner-1 in order
-        c, s, ms, c2 = Q[4 * j:4 * j + 4]
+        q0, q1, q2, q3 = Q[4 * j:4 * j + 4]
         a, bb = head[j], head[j + 1]
-        head[j] = c * a + s * bb
-        head[j + 1] = ms * a + c2 * bb
+        head[j] = q0 * a + q1 * bb
+        head[j + 1] = q2 * a + q3 * bb
     if inner != n - 1 and head[inner + 1] != 0:
-        c, s = scipy.linalg.blas.drotg(head[inner], head[inner + 1])
-        Q[4 * inner:4 * inner + 4] = (c, s, -s, c)
-        g[inner:inner + 2] = (c * g[inner] + s * g[inner + 1], -s * g[inner] + c * g[inner + 1])
-        head[inner] = c * head[inner] + s * head[inner + 1]
+        _GIVENS[V.dtype](Q, g, head, inner)
         head[inner + 1] = 0.0
     m = min(max_inner, len(head))
     H[:m, inner] = head[:m]
 
 
+def _cycle_arrays(V, max_inner, beta):
+    """the host side of a restart cycle: rotations Q, Hessenberg matrix H and the rotated right-hand side g = -beta e_0
+    (krylov/_fgmres.py:209-221; g is read up to entry max_inner only)"""
+    Q = np.zeros(4 * max_inner, dtype=V.dtype)
+    H = np.zeros((max_inner, max_inner), dtype=V.dtype)
+    g = np.zeros(max_inner + 2, dtype=V.dtype)
+    g[0] = -beta
+    return Q, H, g
+
+
 def fgmres(V, b, x, tol=1e-5, restrt=None, maxiter=None, residuals=None, callback=None):
-    """Flexible GMRES, right preconditioning, Householder orthogonalisation (krylov/_fgmres.py:118-305); history:
+    """Flexible GMRES, right preconditioning, Householder orthogonalisation (krylov/_fgmres.py:114-357); history:
     the 2-norm of the (true) residual, estimated through the rotated right-hand side inside a restart cycle."""
     n = V.n
     if n == 1:
@@ -555,40 +610,22 @@ def fgmres(V, b, x, tol=1e-5, restrt=None, maxiter=None, residuals=None, callbac
     V.residual(r, b, x, t)
     normr = V.norm(r)
     keep = residuals is not None
-    if keep:
-        residuals[:] = [normr]
-    normb = V.norm(b) or 1.0
-    if normr < tol * normb:
+    tol = _start(V, b, normr, tol, residuals, callback)
+    if tol is None:
         return 0
-    if normr != 0.0:
-        tol = tol * normr
-    W = [V.new() for _ in range(max_inner)]
-    Z = [V.new() for _ in range(max_inner)]
+    W, Z = V.reflectors(max_inner), V.reflectors(max_inner)
     niter = 0
     for outer in range(max_outer):
-        w = W[0]
-        V.copy(w, r)
-        beta = _sign(V.peek(w, 0)) * normr
-        V.poke(w, 0, V.peek(w, 0) + beta)
-        V.scale(w, w, 1.0 / V.norm(w))
-        Q = np.zeros(4 * max_inner)
-        H = np.zeros((max_inner, max_inner))
-        g = np.zeros(n if n < 4096 else max_inner + 2)
-        g[0] = -beta
+        Q, H, g = _cycle_arrays(V, max_inner, _first_reflector(V, W[0], r, normr))
         inner = 0
         for inner in range(max_inner):
-            w = W[inner]
-            V.scale(v, w, -2.0 * V.peek(w, inner))                 # v = P_inner e_inner ...
-            V.poke(v, inner, V.peek(v, inner) + 1.0)
-            for j in range(inner - 1, -1, -1):                    # ... = P_0 ... P_inner e_inner
-                _reflect(V, v, W, j)
+            _krylov_vector(V, v, W, inner)
             V.M(v, Z[inner])
             V.A(Z[inner], v)
-            for j in range(0, inner + 1):
-                _reflect(V, v, W, j)
+            V.reflect_range(v, W, 0, inner + 1, 1)
             _hessenberg_step(V, v, W, inner, max_inner, Q, g, H)
             if inner < max_inner - 1:
-                normr = abs(g[inner + 1])
+                normr = float(abs(g[inner + 1]))
                 if normr < tol:
                     break
                 if callback is not None:
@@ -615,7 +652,7 @@ def fgmres(V, b, x, tol=1e-5, restrt=None, maxiter=None, residuals=None, callbac
 
 
 def gmres(V, b, x, tol=1e-5, restrt=None, maxiter=None, residuals=None, callback=None):
-    """GMRES with LEFT preconditioning and Householder orthogonalisation (krylov/_gmres_householder.py:107-268, the
+    """GMRES with LEFT preconditioning and Householder orthogonalisation (krylov/_gmres_householder.py:108-375, the
     reference's default `orthog`); history: the norm of the preconditioned residual M (b - A x)."""
     n = V.n
     if n == 1:
@@ -626,40 +663,23 @@ def gmres(V, b, x, tol=1e-5, restrt=None, maxiter=None, residuals=None, callback
     V.M(t, r)
     normr = V.norm(r)
     keep = residuals is not None
-    if keep:
-        residuals[:] = [normr]
-    normb = V.norm(b) or 1.0
-    if normr < tol * normb:
+    tol = _start(V, b, normr, tol, residuals, callback)
+    if tol is None:
         return 0
-    if normr != 0.0:
-        tol = tol * normr
-    W = [V.new() for _ in range(max_inner + 1)]
+    W = V.reflectors(max_inner + 1)
     niter = 0
     for outer in range(max_outer):
-        w = W[0]
-        V.copy(w, r)
-        beta = _sign(V.peek(w, 0)) * normr
-        V.poke(w, 0, V.peek(w, 0) + beta)
-        V.scale(w, w, 1.0 / V.norm(w))
-        Q = np.zeros(4 * max_inner)
-        H = np.zeros((max_inner, max_inner))
-        g = np.zeros(n if n < 4096 else max_inner + 2)
-        g[0] = -beta
+        Q, H, g = _cycle_arrays(V, max_inner, _first_reflector(V, W[0], r, normr))
         inner = 0
         for inner in range(max_inner):
-            w = W[inner]
-            V.scale(v, w, -2.0 * V.peek(w, inner))
-            V.poke(v, inner, V.peek(v, inner) + 1.0)
-            for j in range(inner - 1, -1, -1):
-                _reflect(V, v, W, j)
+            _krylov_vector(V, v, W, inner)
             V.A(v, t)
             V.M(t, v)
-            for j in range(0, inner + 1):
-                _reflect(V, v, W, j)
+            V.reflect_range(v, W, 0, inner + 1, 1)
             _hessenberg_step(V, v, W, inner, max_inner, Q, g, H)
             niter += 1
             if inner < max_inner - 1:
-                normr = abs(g[inner + 1])
+                normr = float(abs(g[inner + 1]))
                 if normr < tol:
                     break
                 if callback is not None:
@@ -667,11 +687,8 @@ def gmres(V, b, x, tol=1e-5, restrt=None, maxiter=None, residuals=None, callback
                 if keep:
                     residuals.append(normr)
         y = scipy.linalg.solve(H[:inner + 1, :inner + 1], g[:inner + 1])
-        # amg_core/krylov.h householder_hornerscheme: for j = inner .. 0: update[j] += y[j]; update <- P_j update
         V.fill(t, 0.0)
-        for j in range(inner, -1, -1):
-            V.poke(t, j, V.peek(t, j) + y[j])
-            _reflect(V, t, W, j)
+        V.horner(t, W, y, inner)                                   # amg_core/krylov.h householder_hornerscheme
         V.axpy(x, 1.0, t)
         V.residual(v, b, x, r)
         V.M(v, r)
@@ -688,7 +705,7 @@ def gmres(V, b, x, tol=1e-5, restrt=None, maxiter=None, residuals=None, callback
 
 
 def _stagnated(V, update, x):
-    """max |update_i / x_i| over x_i != 0 below 1e-12 (krylov/_fgmres.py:293-297): checked on the host copy of the two
+    """max |update_i / x_i| over x_i != 0 below 1e-12 (krylov/_fgmres.py:343-349): checked on the host copy of the two
     vectors only when the update is tiny in norm to begin with, which is the only way the entrywise test can hold"""
     nu, nx = V.norm(update), V.norm(x)
     if nx == 0.0 or nu > 1e-10 * nx:

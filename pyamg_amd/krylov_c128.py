@@ -12,19 +12,17 @@ Every vector lives in HBM (include/amgcore_hip.h section 5: amg_hierx_apply, amg
 amg_devx_*); what crosses PCIe per iteration is a handful of scalars.  The Householder sequences of the GMRES pair
 (amg_core/krylov.h apply_householders, householder_hornerscheme) run as one chain of launches whose inner products
 never leave the device, so an inner iteration costs a fixed number of host reads whatever its index
-(DeviceSpaceC128.host_reads counts them).  Each method follows the reference line by line -- conjugated inner
-products, mysign(x) = x / |x|, the BLAS rotg Givens block [[c, s], [-conj(s), c]], complex H, g and Q on the host;
-inner products are fixed-order device reductions where the reference calls BLAS, so histories agree to rounding
+(DeviceSpaceC128.host_reads counts them).  The method bodies are krylov.py's, shared with the float64 hierarchies:
+this module holds the complex128 vector space they run on and the public functions with the reference's signature.
+Inner products are fixed-order device reductions where the reference calls BLAS, so histories agree to rounding
 (pinned against the reference's own histories in tests/golden/accel_c128/).
 """
 import ctypes as C
 
 import numpy as np
-import scipy.linalg
 from scipy import sparse
 
-from . import _lib
-from .krylov import _inner_limits
+from . import _lib, krylov
 
 __all__ = ["cg", "bicgstab", "gmres", "fgmres", "DeviceSpaceC128"]
 
@@ -32,15 +30,13 @@ _H2D, _D2H, _D2D = 0, 1, 2
 _SZ = 16          # bytes of a complex128
 
 
-def _c(v):
-    return np.complex128(v)
-
-
-class DeviceSpaceC128(object):
+class DeviceSpaceC128(krylov.VectorSpace):
     """complex128 vectors of level 0 of a device hierarchy plus the two operators a Krylov method needs: A (the level
-    operator) and M (one multigrid cycle from a zero guess).  The method surface of krylov.DeviceSpace; dot returns a
-    Python complex (the conjugated inner product sum conj(x_i) y_i), and reflect_range / horner run the Householder
-    sequences without leaving the device.  host_reads counts the calls that brought a value to the host."""
+    operator) and M (one multigrid cycle from a zero guess).  A krylov.VectorSpace whose dot (the conjugated inner
+    product sum conj(x_i) y_i) and peek return np.complex128, whose reflect_range / horner run the Householder
+    sequences without leaving the device, and whose reflectors are allocated as a restart cycle reaches them.
+    host_reads counts the calls that brought a value to the host."""
+    dtype = np.complex128
 
     def __init__(self, dev, cycle):
         self.L = _lib.lib()
@@ -64,16 +60,11 @@ class DeviceSpaceC128(object):
         self._owned.append((p, count))
         return p
 
-    def release(self):
-        for p, count in self._owned:
-            self.L.amg_hierx_vec_free(self.h, p, count)
-        self._owned = []
+    def _free(self, owned):
+        self.L.amg_hierx_vec_free(self.h, *owned)
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.release()
+    def reflectors(self, limit):
+        return _Reflectors(self, limit)
 
     def upload(self, host, dst=None):
         host = np.ascontiguousarray(np.ravel(host), dtype=np.complex128)
@@ -94,7 +85,7 @@ class DeviceSpaceC128(object):
         _lib.check(self.L.amg_devx_copy(dst + _SZ * offset, values.ctypes.data, len(values), _H2D, self.stream))
 
     def peek(self, src, offset):
-        return _c(self.download(src, 1, offset)[0])
+        return self.download(src, 1, offset)[0]
 
     # -- BLAS-1 on (sub)vectors: `off` skips leading entries
     def copy(self, dst, src, off=0):
@@ -125,7 +116,7 @@ class DeviceSpaceC128(object):
         r = (C.c_double * 2)()
         _lib.check(self.L.amg_devx_zdotc(x, y, self.n, self.scratch, 1, r, self.stream))
         self.host_reads += 1
-        return complex(r[0], r[1])
+        return np.complex128(complex(r[0], r[1]))
 
     def norm(self, x, off=0):
         if self.n - off <= 0:
@@ -159,198 +150,6 @@ class DeviceSpaceC128(object):
     def M(self, r, out):
         self.dev.cycle_device(r, out, self.cycle)
 
-    def residual(self, out, b, x, tmp):               # out = b - A x
-        self.A(x, tmp)
-        self.sub(out, b, tmp)
-
-
-def _mysign(x):
-    """the complex sign x / |x| (krylov/_fgmres.py:16, _gmres_householder.py:16)"""
-    return 1.0 if x == 0.0 else x / abs(x)
-
-
-def _check_maxiter(maxiter):
-    if maxiter is not None and maxiter < 1:
-        raise ValueError("Number of iterations must be positive")
-
-
-# --------------------------------------------------------------------------- the methods on device vectors
-def _cg(V, b, x, tol=1e-5, maxiter=None, residuals=None, callback=None):
-    """Preconditioned conjugate gradients (krylov/_cg.py:84-183) with conjugated inner products.  The history is
-    sqrt(<r, M r>); the reference stores that complex scalar, whose imaginary part is zero for a Hermitian positive
-    definite M -- here its real part is stored, and the curvature tests look at real parts.
-    -> info (0 converged, -1 indefinite operator / preconditioner, else the iteration count)"""
-    if maxiter is None:
-        maxiter = int(1.3 * V.n) + 2
-    r, z, p, Ap = V.new(), V.new(), V.new(), V.new()
-    V.residual(r, b, x, Ap)
-    V.M(r, z)
-    V.copy(p, z)
-    rz = _c(V.dot(r, z))
-    normr = float(np.sqrt(rz).real)
-    if residuals is not None:
-        residuals[:] = [normr]
-    normb = V.norm(b) or 1.0
-    if normr < tol * normb:
-        return 0
-    if normr != 0.0:
-        tol = tol * normr
-    it = 0
-    while True:
-        V.A(p, Ap)
-        rz_old = rz
-        pAp = _c(V.dot(Ap, p))
-        if pAp.real < 0.0:
-            return -1
-        alpha = rz / pAp
-        V.axpy(x, alpha, p)
-        if (it % 8) and it > 0:
-            V.axpy(r, -alpha, Ap)
-        else:
-            V.residual(r, b, x, z)
-        V.M(r, z)
-        rz = _c(V.dot(r, z))
-        if rz.real < 0.0:
-            return -1
-        V.xpby(p, rz / rz_old, z)
-        it += 1
-        normr = float(np.sqrt(rz).real)
-        if residuals is not None:
-            residuals.append(normr)
-        if callback is not None:
-            callback(V.download(x))
-        if normr < tol:
-            return 0
-        if rz == 0.0:
-            return -1
-        if it == maxiter:
-            return it
-
-
-def _bicgstab(V, b, x, tol=1e-5, maxiter=None, residuals=None, callback=None):
-    """Right-preconditioned BiCGStab (krylov/_bicgstab.py:80-167): 2-norm history, conjugated inner products."""
-    if maxiter is None:
-        maxiter = V.n + 5
-    r, rstar, p, Mp, AMp, s_, Ms, AMs = (V.new() for _ in range(8))
-    V.residual(r, b, x, Mp)
-    normr = V.norm(r)
-    if residuals is not None:
-        residuals[:] = [normr]
-    normb = V.norm(b) or 1.0
-    if normr < tol * normb:
-        return 0
-    if normr != 0.0:
-        tol = tol * normr
-    if V.n == 1:
-        return _solve_1x1(V, b, x)
-    V.copy(rstar, r)
-    V.copy(p, r)
-    rr_old = _c(V.dot(rstar, r))
-    it = 0
-    while True:
-        V.M(p, Mp)
-        V.A(Mp, AMp)
-        alpha = rr_old / _c(V.dot(rstar, AMp))
-        V.copy(s_, r)
-        V.axpy(s_, -alpha, AMp)                       # s = r - alpha A M p
-        V.M(s_, Ms)
-        V.A(Ms, AMs)
-        omega = _c(V.dot(AMs, s_)) / _c(V.dot(AMs, AMs))
-        V.axpy(x, alpha, Mp)
-        V.axpy(x, omega, Ms)
-        V.copy(r, s_)
-        V.axpy(r, -omega, AMs)                        # r = s - omega A M s
-        rr_new = _c(V.dot(rstar, r))
-        beta = (rr_new / rr_old) * (alpha / omega)
-        rr_old = rr_new
-        V.axpy(p, -omega, AMp)                        # p = r + beta (p - omega A M p)
-        V.xpby(p, beta, r)
-        it += 1
-        normr = V.norm(r)
-        if residuals is not None:
-            residuals.append(normr)
-        if callback is not None:
-            callback(V.download(x))
-        if normr < tol:
-            return 0
-        if it == maxiter:
-            return it
-
-
-def _solve_1x1(V, b, x):
-    """a 1 x 1 system is solved directly: x = b / A[0, 0] (krylov/_fgmres.py:163-166, _gmres_householder.py:163-166)"""
-    e, a = V.new(), V.new()
-    V.fill(e, 1.0)
-    V.A(e, a)
-    V.poke(x, 0, V.peek(b, 0) / V.peek(a, 0))
-    return 0
-
-
-def _first_reflector(V, w, r, normr):
-    """w = r + mysign(r[0]) ||r|| e_0, normalised (krylov/_fgmres.py:200-203); -> beta"""
-    V.copy(w, r)
-    w0 = V.peek(w, 0)
-    beta = _mysign(w0) * normr
-    V.poke(w, 0, w0 + beta)
-    V.scale(w, w, 1.0 / V.norm(w))
-    return beta
-
-
-def _krylov_vector(V, v, W, inner):
-    """v = P_0 ... P_inner e_inner (krylov/_fgmres.py:226-231)"""
-    w = W[inner]
-    V.scale(v, w, -2.0 * np.conjugate(V.peek(w, inner)))
-    V.poke(v, inner, V.peek(v, inner) + 1.0)
-    V.reflect_range(v, W, inner - 1, -1, -1)
-
-
-def _hessenberg_step(V, v, W, inner, max_inner, Q, g, H):
-    """The part of one (F)GMRES inner iteration after v holds P_inner ... P_0 (A ...) (krylov/_fgmres.py:250-303): the
-    next reflector, then -- on the host, v has at most inner + 2 non-zero leading entries now -- the accumulated
-    Givens rotations, the new rotation, the Hessenberg column."""
-    n = V.n
-    if inner != n - 1:
-        if inner < max_inner - 1:
-            # the reference starts every restart cycle from zeroed reflectors (W = zeros(...), _fgmres.py:212): after
-            # a breakdown (alpha == 0) the next step must not find the previous cycle's vector here
-            V.fill(W[inner + 1], 0.0)
-        alpha = V.norm(v, off=inner + 1)
-        if alpha != 0:
-            alpha = _mysign(V.peek(v, inner + 1)) * alpha
-            if inner < max_inner - 1:
-                w = W[inner + 1]
-                V.copy(w, v, off=inner + 1)
-                V.poke(w, inner + 1, V.peek(w, inner + 1) + alpha)
-                V.scale(w, w, 1.0 / V.norm(w))
-            V.poke(v, inner + 1, -alpha)
-            V.fill(v, 0.0, off=inner + 2)
-    head = V.download(v, min(n, inner + 2))
-    for j in range(inner):                            # amg_core/krylov.h apply_givens: rotations 0 .. inner-1 in order
-        q0, q1, q2, q3 = Q[4 * j:4 * j + 4]
-        a, bb = head[j], head[j + 1]
-        head[j] = q0 * a + q1 * bb
-        head[j + 1] = q2 * a + q3 * bb
-    if inner != n - 1 and head[inner + 1] != 0:
-        c, s = scipy.linalg.blas.zrotg(head[inner], head[inner + 1])
-        Qblock = np.array([[c, s], [-np.conjugate(s), c]], dtype=np.complex128)
-        Q[4 * inner:4 * inner + 4] = np.ravel(Qblock)
-        g[inner:inner + 2] = np.dot(Qblock, g[inner:inner + 2])
-        head[inner] = np.dot(Qblock[0, :], head[inner:inner + 2])
-        head[inner + 1] = 0.0
-    m = min(max_inner, len(head))
-    H[:m, inner] = head[:m]
-
-
-def _stagnated(V, update, x):
-    """max |update_i / x_i| over x_i != 0 below 1e-12 (krylov/_fgmres.py:343-349): checked on the host copy of the two
-    vectors only when the update is tiny in norm to begin with, which is the only way the entrywise test can hold"""
-    nu, nx = V.norm(update), V.norm(x)
-    if nx == 0.0 or nu > 1e-10 * nx:
-        return False
-    u, xx = V.download(update), V.download(x)
-    idx = xx != 0
-    return bool(idx.any() and np.max(np.abs(u[idx] / xx[idx])) < 1e-12)
-
 
 class _Reflectors(object):
     """the Householder vectors of a restart cycle, allocated as the cycle reaches them"""
@@ -368,132 +167,6 @@ class _Reflectors(object):
 
     def __iter__(self):
         return iter(self.vecs)
-
-
-def _fgmres(V, b, x, tol=1e-5, restrt=None, maxiter=None, residuals=None, callback=None):
-    """Flexible GMRES, right preconditioning, Householder orthogonalisation (krylov/_fgmres.py:114-357); history:
-    the 2-norm of the (true) residual, estimated through the rotated right-hand side inside a restart cycle."""
-    n = V.n
-    if n == 1:
-        return _solve_1x1(V, b, x)
-    max_outer, max_inner = _inner_limits(n, restrt, maxiter)
-    r, v, t = V.new(), V.new(), V.new()
-    V.residual(r, b, x, t)
-    normr = V.norm(r)
-    keep = residuals is not None
-    if keep:
-        residuals[:] = [normr]
-    normb = V.norm(b) or 1.0
-    if normr < tol * normb:
-        if callback is not None:
-            callback(normr)
-        return 0
-    if normr != 0.0:
-        tol = tol * normr
-    W = _Reflectors(V, max_inner)
-    Z = _Reflectors(V, max_inner)
-    niter = 0
-    for outer in range(max_outer):
-        beta = _first_reflector(V, W[0], r, normr)
-        Q = np.zeros(4 * max_inner, dtype=np.complex128)
-        H = np.zeros((max_inner, max_inner), dtype=np.complex128)
-        g = np.zeros(max_inner + 2, dtype=np.complex128)
-        g[0] = -beta
-        inner = 0
-        for inner in range(max_inner):
-            _krylov_vector(V, v, W, inner)
-            V.M(v, Z[inner])
-            V.A(Z[inner], v)
-            V.reflect_range(v, W, 0, inner + 1, 1)
-            _hessenberg_step(V, v, W, inner, max_inner, Q, g, H)
-            if inner < max_inner - 1:
-                normr = float(abs(g[inner + 1]))
-                if normr < tol:
-                    break
-                if callback is not None:
-                    callback(normr)
-                if keep:
-                    residuals.append(normr)
-            niter += 1
-        y = scipy.linalg.solve(H[:inner + 1, :inner + 1], g[:inner + 1])
-        V.fill(t, 0.0)                                             # update = Z[:, :inner+1] y
-        for k in range(inner + 1):
-            V.axpy(t, y[k], Z[k])
-        V.axpy(x, 1.0, t)
-        V.residual(r, b, x, v)
-        normr = V.norm(r)
-        if callback is not None:
-            callback(normr)
-        if keep:
-            residuals.append(normr)
-        if _stagnated(V, t, x):
-            return -1
-        if normr < tol:
-            return 0
-    return niter
-
-
-def _gmres(V, b, x, tol=1e-5, restrt=None, maxiter=None, residuals=None, callback=None):
-    """GMRES with LEFT preconditioning and Householder orthogonalisation (krylov/_gmres_householder.py:108-375, the
-    reference's default `orthog`); history: the norm of the preconditioned residual M (b - A x)."""
-    n = V.n
-    if n == 1:
-        return _solve_1x1(V, b, x)
-    max_outer, max_inner = _inner_limits(n, restrt, maxiter)
-    r, v, t = V.new(), V.new(), V.new()
-    V.residual(t, b, x, v)
-    V.M(t, r)
-    normr = V.norm(r)
-    keep = residuals is not None
-    if keep:
-        residuals[:] = [normr]
-    normb = V.norm(b) or 1.0
-    if normr < tol * normb:
-        if callback is not None:
-            callback(normr)
-        return 0
-    if normr != 0.0:
-        tol = tol * normr
-    W = _Reflectors(V, max_inner + 1)
-    niter = 0
-    for outer in range(max_outer):
-        beta = _first_reflector(V, W[0], r, normr)
-        Q = np.zeros(4 * max_inner, dtype=np.complex128)
-        H = np.zeros((max_inner, max_inner), dtype=np.complex128)
-        g = np.zeros(max_inner + 2, dtype=np.complex128)
-        g[0] = -beta
-        inner = 0
-        for inner in range(max_inner):
-            _krylov_vector(V, v, W, inner)
-            V.A(v, t)
-            V.M(t, v)
-            V.reflect_range(v, W, 0, inner + 1, 1)
-            _hessenberg_step(V, v, W, inner, max_inner, Q, g, H)
-            niter += 1
-            if inner < max_inner - 1:
-                normr = float(abs(g[inner + 1]))
-                if normr < tol:
-                    break
-                if callback is not None:
-                    callback(normr)
-                if keep:
-                    residuals.append(normr)
-        y = scipy.linalg.solve(H[:inner + 1, :inner + 1], g[:inner + 1])
-        V.fill(t, 0.0)
-        V.horner(t, W, y, inner)                                   # amg_core/krylov.h householder_hornerscheme
-        V.axpy(x, 1.0, t)
-        V.residual(v, b, x, r)
-        V.M(v, r)
-        normr = V.norm(r)
-        if callback is not None:
-            callback(normr)
-        if keep:
-            residuals.append(normr)
-        if _stagnated(V, t, x):
-            return -1
-        if normr < tol:
-            return 0
-    return niter
 
 
 # --------------------------------------------------------------------------- the public functions: host vectors in and out
@@ -525,7 +198,7 @@ def _resolve(A, M):
 
 
 def _run(method, A, b, x0, M, callback, **kw):
-    _check_maxiter(kw.get("maxiter"))
+    krylov._maxiter(kw.get("maxiter"), None)
     ml, cycle = _resolve(A, M)
     b = np.asarray(b)
     n = ml.levels[0].A.shape[0]
@@ -535,7 +208,7 @@ def _run(method, A, b, x0, M, callback, **kw):
     x1 = np.zeros(n, dtype=np.complex128) if x0 is None else np.ascontiguousarray(np.ravel(x0), dtype=np.complex128)
     with DeviceSpaceC128(ml.device_hierarchy(), cycle) as V:
         bd, xd = V.upload(b1), V.upload(x1)
-        info = method(V, bd, xd, callback=callback, **kw)
+        info = krylov.METHODS[method](V, bd, xd, callback=callback, **kw)
         x = V.download(xd)
     return x.reshape(b.shape), info
 
@@ -543,22 +216,22 @@ def _run(method, A, b, x0, M, callback, **kw):
 def cg(A, b, x0=None, tol=1e-5, restrt=None, maxiter=None, M=None, callback=None, residuals=None):
     """Preconditioned conjugate gradients (krylov/_cg.py); callback(x) after every iteration; info -1: indefinite
     operator or preconditioner (Re <Ap, p> < 0 or Re <r, z> < 0).  restrt is ignored."""
-    return _run(_cg, A, b, x0, M, callback, tol=tol, maxiter=maxiter, residuals=residuals)
+    return _run("cg", A, b, x0, M, callback, tol=tol, maxiter=maxiter, residuals=residuals)
 
 
 def bicgstab(A, b, x0=None, tol=1e-5, restrt=None, maxiter=None, M=None, callback=None, residuals=None):
     """Right-preconditioned BiCGStab (krylov/_bicgstab.py); callback(x) after every iteration.  restrt is ignored."""
-    return _run(_bicgstab, A, b, x0, M, callback, tol=tol, maxiter=maxiter, residuals=residuals)
+    return _run("bicgstab", A, b, x0, M, callback, tol=tol, maxiter=maxiter, residuals=residuals)
 
 
 def gmres(A, b, x0=None, tol=1e-5, restrt=None, maxiter=None, M=None, callback=None, residuals=None):
     """Left-preconditioned Householder GMRES (krylov/_gmres_householder.py); callback(normr) per inner iteration."""
-    return _run(_gmres, A, b, x0, M, callback, tol=tol, restrt=restrt, maxiter=maxiter, residuals=residuals)
+    return _run("gmres", A, b, x0, M, callback, tol=tol, restrt=restrt, maxiter=maxiter, residuals=residuals)
 
 
 def fgmres(A, b, x0=None, tol=1e-5, restrt=None, maxiter=None, M=None, callback=None, residuals=None):
     """Right-preconditioned flexible Householder GMRES (krylov/_fgmres.py); callback(normr) per inner iteration."""
-    return _run(_fgmres, A, b, x0, M, callback, tol=tol, restrt=restrt, maxiter=maxiter, residuals=residuals)
+    return _run("fgmres", A, b, x0, M, callback, tol=tol, restrt=restrt, maxiter=maxiter, residuals=residuals)
 
 
 METHODS = {"cg": cg, "bicgstab": bicgstab, "gmres": gmres, "fgmres": fgmres}

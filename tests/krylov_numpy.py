@@ -1,17 +1,22 @@
-"""A NumPy stand-in for pyamg_amd.krylov's device-vector class (same method names): lets the Krylov drivers' host logic
-(restart bookkeeping, breakdown branches, 1 x 1 systems) run without a GPU.  Handles are indices into a list of arrays."""
+"""A NumPy stand-in for pyamg_amd.krylov's device-vector classes (a krylov.VectorSpace of float64 or complex128 host
+arrays): lets the Krylov drivers' host logic (restart bookkeeping, breakdown branches, 1 x 1 systems) run without a GPU.
+Handles are indices into a list of arrays; the Householder sequences and reflector storage are the base class's."""
 import numpy as np
 
+from pyamg_amd.krylov import VectorSpace
 
-class NumpyVectors(object):
-    def __init__(self, A, M=None):
+
+class NumpyVectors(VectorSpace):
+    def __init__(self, A, M=None, dtype=np.float64):
         self.Amat = A
         self.Mfun = M
         self.n = A.shape[0]
+        self.dtype = np.dtype(dtype).type
+        self.real = self.dtype is np.float64
         self.store = []
 
     def new(self, count=None):
-        self.store.append(np.zeros(self.n if count is None else count))
+        self.store.append(np.zeros(self.n if count is None else count, dtype=self.dtype))
         return len(self.store) - 1
 
     def upload(self, host, dst=None):
@@ -28,7 +33,8 @@ class NumpyVectors(object):
         self.store[dst][offset:offset + len(v)] = v
 
     def peek(self, src, offset):
-        return float(self.store[src][offset])
+        v = self.store[src][offset]
+        return float(v) if self.real else v
 
     def copy(self, dst, src, off=0):
         self.store[dst][off:] = self.store[src][off:]
@@ -49,7 +55,9 @@ class NumpyVectors(object):
         self.store[out][:] = self.store[a] - self.store[b]
 
     def dot(self, x, y):
-        return float(np.dot(self.store[x], self.store[y]))
+        if self.real:
+            return float(np.dot(self.store[x], self.store[y]))
+        return np.complex128(np.vdot(self.store[x], self.store[y]))
 
     def norm(self, x, off=0):
         return float(np.linalg.norm(self.store[x][off:]))
@@ -57,9 +65,8 @@ class NumpyVectors(object):
     def A(self, x, out):
         self.store[out][:] = self.Amat @ self.store[x]
 
+    def AH(self, x, out):
+        self.store[out][:] = self.Amat.conj().T @ self.store[x]
+
     def M(self, r, out):
         self.store[out][:] = self.store[r] if self.Mfun is None else self.Mfun(self.store[r])
-
-    def residual(self, out, b, x, tmp):
-        self.A(x, tmp)
-        self.sub(out, b, tmp)
