@@ -23,6 +23,23 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line);
 constexpr int PAD = 16;
 
 struct DevBsr;
+// Sliced form (DevCsr::sl_*, sell.hip): what a slice's wave reads before its entries.  The record's address depends on
+// the slice number alone, so its fields arrive together (as scalar loads: the slice number is wave-uniform) and the
+// entry stream depends on nothing else.  The first 32 bytes serve every slice; the origins only the 16-bit codes.
+struct alignas(32) SellHdr {
+    long off;        // first entry of the slice in sl_col / sl_val (a multiple of 64)
+    long coff;       // first code word of the slice in sl_code (0 without codes)
+    int w;           // entries of the slice's longest row = entries stored per row
+    int coded;       // 1 = the slice's columns are read from sl_code
+    int pad[2];
+    int org[16];     // window origins of a coded slice (multiples of 4096), else 0
+};
+static_assert(sizeof(SellHdr) == 96, "three 32-byte groups");
+struct SellSlot {
+    int row;         // -1: padding slot
+    int len;
+};
+
 struct DevCsr {
     int nrows = 0, ncols = 0;
     long nnz = 0;
@@ -53,20 +70,16 @@ struct DevCsr {
     // are stored entry-major -- entry k of its 64 rows side by side -- padded to the slice's longest row.  One wave per
     // slice, one lane per row: no row pointer, no LDS, no barrier; every lane sums ITS row's entries in stored
     // order, so results are bit-identical to the CSR kernel's.
-    int *sl_row = nullptr;         // [sl_nslices * 64] row of the slot (-1: padding slot)
-    unsigned short *sl_len = nullptr;  // [sl_nslices * 64] entries of that row
-    long *sl_off = nullptr;        // [sl_nslices + 1] first entry of the slice in sl_col / sl_val (multiples of 64)
+    SellSlot *sl_slot = nullptr;   // [sl_nslices * 64] row of the slot (-1: padding slot) and its entries: one 8-byte load per lane
+    SellHdr *sl_hdr = nullptr;     // [sl_nslices] everything the slice's wave needs before its entries, one 32-byte-aligned record
     int *sl_col = nullptr;
     double *sl_val = nullptr;
     int sl_nslices = 0;
     // 16-bit column codes of the sliced form (lossless): the columns a slice's 64 rows reference fall into a few narrow
     // clusters; when at most 16 aligned windows of 4096 columns cover them, entry k of a row is stored as
     // (window slot << 12) | (column & 4095), two codes per 32-bit word, and the slice's 16 window origins travel in one
-    // 64-byte load: 10 B per entry instead of 12.  Slices that need more windows keep reading sl_col (flag per slice).
-    unsigned *sl_code = nullptr;       // [sl_coff[nslices]] pairs of codes, pair-major per slice: [k / 2][64 lanes]
-    int *sl_org = nullptr;             // [nslices * 16] window origins (multiples of 4096)
-    long *sl_coff = nullptr;           // [nslices + 1] first code word of the slice
-    unsigned char *sl_flag16 = nullptr;// [nslices] 1 = this slice's entries are coded
+    // 64-byte load: 10 B per entry instead of 12.  Slices that need more windows keep reading sl_col (SellHdr::coded).
+    unsigned *sl_code = nullptr;       // [sum of ceil(w / 2) * 64] pairs of codes, pair-major per slice: [k / 2][64 lanes]; slice s starts at sl_hdr[s].coff
     double sl_frac16 = 0.0;            // fraction of the slices that are coded
     long sl_entries = 0;           // padded entries stored
     int sl_lo = 0, sl_hi = 0;      // rows the sliced form covers (all of them; a partitioned level: its interior rows)

@@ -2614,11 +2614,13 @@ static double bytes_spmv_moved(const DevCsr &M)
         return (coded ? 8.0 * (double)((M.st_nu + 7) / 8) : 8.0 * (double)M.st_nu) * 256.0 * (double)((M.nrows + 255) / 256) + mask_bytes * M.nrows +
                8.0 * M.ncols + 8.0 * M.nrows;
     }
-    if (!M.pat && M.sl_val && (sell_enabled() || !M.Ap) && M.sl_lo == 0 && M.sl_hi == M.nrows)    // padded entries, slot bookkeeping (row id + length), slice offsets; no row pointer
+    if (!M.pat && M.sl_val && (sell_enabled() || !M.Ap) && M.sl_lo == 0 && M.sl_hi == M.nrows)    // padded entries, slot bookkeeping (row id + length), slice headers; no row pointer
     {
-        // (16-bit column codes: 2 B instead of 4 B per entry of a coded slice, + its 16 window origins)
-        const double f16 = (M.sl_code && sell_index16_enabled()) ? M.sl_frac16 : 0.0;
-        return (12.0 - 2.0 * f16) * (double)M.sl_entries + (6.0 * 64.0 + 64.0 * f16 + 1.0) * M.sl_nslices + 8.0 * (M.sl_nslices + 1.0) + 8.0 * M.ncols + 8.0 * M.nrows;
+        // (16-bit column codes: 2 B instead of 4 B per entry of a coded slice; every slice's header then comes with its
+        //  16 window origins, 96 B instead of the 32 B of offsets, width and flag)
+        const bool codes = M.sl_code && sell_index16_enabled();
+        const double f16 = codes ? M.sl_frac16 : 0.0;
+        return (12.0 - 2.0 * f16) * (double)M.sl_entries + (8.0 * 64.0 + (codes ? 96.0 : 32.0)) * M.sl_nslices + 8.0 * M.ncols + 8.0 * M.nrows;
     }
     if (!M.pat) {
         double idx = (M.Aj16 && index16_enabled()) ? (2.0 * M.i16_frac + 4.0 * (1.0 - M.i16_frac)) : 4.0;

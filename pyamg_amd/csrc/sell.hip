@@ -5,11 +5,17 @@
 // with barriers in between, and rocprofv3 shows ~80 % of its wave cycles waiting: it is bound
 // by that chain, not by bytes.  Here a wave owns a slice of 64 rows, a lane one row; the slice's entries are stored
 // entry-major (entry k of the 64 rows side by side, padded to the slice's longest row), so a lane's loads are
-// coalesced with its neighbours', need no row pointer and no LDS, and ALL of a row's entries (up to 32 per pass) are
-// requested before any is consumed: two round trips per slice, no barrier.  Rows are sorted by length inside windows
+// coalesced with its neighbours', need no row pointer and no LDS, and a row's entries are requested before any is
+// consumed, no barrier.  Rows are sorted by length inside windows
 // of 256 (restrictions: 64) rows (longest first, ties in row order) so that slices are nearly rectangular.
 // Every lane adds ITS row's products in stored order with separate multiply and add: bit-identical to the CSR kernel
 // (scipy csr_matvec / relaxation.h row loops) in every mode.
+//
+// The dependent round trips of a slice: (1) its header record (SellHdr: entry and code-word offsets, width, coded
+// flag, window origins -- one address that depends on the slice number alone, scalar loads) together with the lane's
+// slot (row and length, one 8-byte load); (2) the entries, up to SL_PASS per row at once, with the epilogue's streamed
+// operands (b[row], v2[row]); (3) the gathered operands; (2) and (3) again for rows of more than SL_PASS entries;
+// (4) the store.
 #include "hier.hpp"
 
 #include <algorithm>
@@ -24,7 +30,8 @@ constexpr int SL_C = 64;            // rows per slice = lanes per wave
 constexpr int SL_SIGMA_SQUARE = 256;   // rows per sorting window: square operators (A_l)
 constexpr int SL_SIGMA_RECT = 64;      //                          restrictions (the gathers reach into the finer level: keep neighbours together)
 constexpr int SL_PASS = 32;         // entries of a row requested at once (16: measured slower)
-constexpr int SL_WG = 256;          // four slices per workgroup
+constexpr int SL_WG = 256;          // four slices per workgroup (one slice per workgroup: measured equal)
+static_assert(SL_PASS % 2 == 0, "code words hold two entries");
 
 __device__ __forceinline__ int remap(int b, int nb, int chunk)       // kernels.hip remap_block: consecutive blocks to one XCD
 {
@@ -42,7 +49,7 @@ __device__ __forceinline__ int remap(int b, int nb, int chunk)       // kernels.
 // cache lines.  2048: A_1 -11 % at 500^3 but +2 % / +10 % at 400^3 / 300^3 against the CSR kernel and R_0 up to +46 %;
 // 256: A_1 -9 .. -12 % at all three sizes; restrictions (which gather from the finer level) want 64.
 template <int SL_SIGMA>
-__global__ __launch_bounds__(1024) void sell_sort_kernel(int row_lo, int n, const int *Ap, int *sl_row, unsigned short *sl_len, int *slice_w)
+__global__ __launch_bounds__(1024) void sell_sort_kernel(int row_lo, int n, const int *Ap, SellSlot *sl_slot, int *slice_w)
 {          // rows row_lo .. row_lo + n - 1
     __shared__ unsigned key[SL_SIGMA];
     static_assert(SL_SIGMA <= 2048 && (SL_SIGMA & (SL_SIGMA - 1)) == 0, "window: a power of two up to 2048 (11-bit position in the sort key)");
@@ -71,22 +78,21 @@ __global__ __launch_bounds__(1024) void sell_sort_kernel(int row_lo, int n, cons
         const int pos = SL_SIGMA - 1 - (int)(kq & 2047u);
         const int len = is_row ? (int)(kq >> 11) - 1 : 0;
         const int slot = w0 + q;
-        sl_row[slot] = is_row ? row_lo + w0 + pos : -1;
-        sl_len[slot] = (unsigned short)len;
+        sl_slot[slot] = SellSlot{is_row ? row_lo + w0 + pos : -1, len};
         if ((q & (SL_C - 1)) == 0) slice_w[slot / SL_C] = len;                    // the slice's longest row comes first
     }
 }
 
 // entries of the slices, entry-major; padding entries: column 0, value 0 (requested, never used)
-__global__ __launch_bounds__(SL_WG) void sell_fill_kernel(int nslices, const int *Ap, const int *Aj, const double *Ax, const int *sl_row,
-                                                         const unsigned short *sl_len, const long *sl_off, int *sl_col, double *sl_val)
+__global__ __launch_bounds__(SL_WG) void sell_fill_kernel(int nslices, const int *Ap, const int *Aj, const double *Ax, const SellSlot *sl_slot,
+                                                               const SellHdr *sl_hdr, int *sl_col, double *sl_val)
 {
     const int s = blockIdx.x * (SL_WG / SL_C) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (s >= nslices) return;
-    const long off = sl_off[s];
-    const int w = (int)((sl_off[s + 1] - off) >> 6);
-    const int slot = s * SL_C + lane;
-    const int row = sl_row[slot], len = sl_len[slot];
+    const long off = sl_hdr[s].off;
+    const int w = sl_hdr[s].w;
+    const SellSlot sl = sl_slot[s * SL_C + lane];
+    const int row = sl.row, len = sl.len;
     const int k0 = row >= 0 ? Ap[row] : 0;
     for (int k = 0; k < w; ++k) {
         const bool have = k < len;
@@ -96,29 +102,24 @@ __global__ __launch_bounds__(SL_WG) void sell_fill_kernel(int nslices, const int
 }
 
 struct SellArgs {
-    const int *row;
-    const unsigned short *len;
-    const long *off;
+    const SellSlot *slot;
+    const SellHdr *hdr;
     const int *col;
     const double *val;
     int nslices;
     const unsigned *code;        // 16-bit column codes (DevCsr::sl_code) or null
-    const int *org;
-    const long *coff;
-    const unsigned char *flag16;
 };
 
 // 16-bit codes of one slice (one wave per slice): the distinct values of column >> 12 over the slice's real entries,
 // in order of first appearance (row of 64 entries by row, lanes in order) -- at most 16, else the slice keeps its
-// 32-bit columns; then the codes, two per word.
-__global__ __launch_bounds__(SL_WG) void sell_code_kernel(int nslices, const unsigned short *sl_len, const long *sl_off, const int *sl_col,
-                                                         const long *sl_coff, unsigned *sl_code, int *sl_org, unsigned char *sl_flag16)
+// 32-bit columns; then the codes, two per word.  Writes the header's origins and coded flag.
+__global__ __launch_bounds__(SL_WG) void sell_code_kernel(int nslices, const SellSlot *sl_slot, SellHdr *sl_hdr, const int *sl_col, unsigned *sl_code)
 {
     const int s = blockIdx.x * (SL_WG / SL_C) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (s >= nslices) return;
-    const long off = sl_off[s];
-    const int w = (int)((sl_off[s + 1] - off) >> 6);
-    const int len = sl_len[s * SL_C + lane];
+    const long off = sl_hdr[s].off;
+    const int w = sl_hdr[s].w;
+    const int len = sl_slot[s * SL_C + lane].len;
     int tab = -1;                                   // lane t < 16 holds window t's value of column >> 12
     int cnt = 0;
     bool ok = true;
@@ -140,10 +141,10 @@ __global__ __launch_bounds__(SL_WG) void sell_code_kernel(int nslices, const uns
             ++cnt;
         }
     }
-    if (lane < 16) sl_org[s * 16 + lane] = (ok && lane < cnt) ? (tab << 12) : 0;
-    if (lane == 0) sl_flag16[s] = ok ? 1 : 0;
+    if (lane < 16) sl_hdr[s].org[lane] = (ok && lane < cnt) ? (tab << 12) : 0;
+    if (lane == 0) sl_hdr[s].coded = ok ? 1 : 0;
     if (!ok) return;
-    const long coff = sl_coff[s];
+    const long coff = sl_hdr[s].coff;
     for (int k = 0; k < w; k += 2) {
         unsigned word = 0;
         for (int h = 0; h < 2; ++h) {
@@ -159,18 +160,85 @@ __global__ __launch_bounds__(SL_WG) void sell_code_kernel(int nslices, const uns
     }
 }
 
+// entries k0 .. k0 + N - 1 of the lane's row, requested: q holds the code words (N / 2, coded slice) or the columns (N);
+// entries at or past the slice's width w are not requested (uniform over the wave) and read as column 0, value 0
+template <int N, bool IDX16>
+__device__ __forceinline__ void sell_request(bool coded, const unsigned *wp, const int *cp, const double *vp, int k0, int w, unsigned (&q)[N], double (&v)[N])
+{
+    if (IDX16 && coded) {
+#pragma unroll
+        for (int u = 0; u < N; u += 2) {
+            q[u / 2] = 0u;
+            if (k0 + u < w) q[u / 2] = __builtin_nontemporal_load(&wp[(long)((k0 + u) >> 1) * SL_C]);
+        }
+#pragma unroll
+        for (int u = 0; u < N; ++u) {
+            v[u] = 0.0;
+            if (k0 + u < w) v[u] = __builtin_nontemporal_load(&vp[(long)(k0 + u) * SL_C]);
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < N; ++u) {
+            q[u] = 0u; v[u] = 0.0;
+            if (k0 + u < w) {                                       // uniform: the whole wave requests or skips
+                q[u] = (unsigned)__builtin_nontemporal_load(&cp[(long)(k0 + u) * SL_C]);
+                v[u] = __builtin_nontemporal_load(&vp[(long)(k0 + u) * SL_C]);
+            }
+        }
+    }
+}
+
+// the columns of what sell_request brought, and the operands gathered (entries past the row's length: not gathered)
+template <int N, bool IDX16>
+__device__ __forceinline__ void sell_gather(bool coded, int org, const unsigned (&q)[N], const double *xg, int k0, int len, double (&xv)[N])
+{
+    int c[N];
+    if (IDX16 && coded) {
+#pragma unroll
+        for (int u = 0; u < N; ++u) {
+            const unsigned code = (q[u / 2] >> (16 * (u & 1))) & 0xffffu;
+            c[u] = __shfl(org, (int)(code >> 12), 64) + (int)(code & 4095u);
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < N; ++u) c[u] = (int)q[u];
+    }
+#pragma unroll
+    for (int u = 0; u < N; ++u) xv[u] = (k0 + u < len) ? xg[c[u]] : 0.0;
+}
+
+template <int N>
+__device__ __forceinline__ double sell_sum(double acc, double gscale, const double (&v)[N], const double (&xv)[N], int k0, int len)
+{
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+        const double pr = v[u] * (gscale * xv[u]);
+        const double nxt = acc + pr;
+        acc = (k0 + u < len) ? nxt : acc;
+    }
+    return acc;
+}
+
 template <int MODE, bool IDX16>
 __global__ __launch_bounds__(SL_WG) void sell_kernel(StreamArgs a, SellArgs S, int xcd_chunk)
 {
     const int blk = remap((int)blockIdx.x, (int)gridDim.x, xcd_chunk);
-    const int s = blk * (SL_WG / SL_C) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    // the slice number is the same in every lane: said to the compiler, so that the header comes in as scalar loads
+    const int s = __builtin_amdgcn_readfirstlane(blk * (SL_WG / SL_C) + (int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     if (s >= S.nslices) return;
-    const long off = S.off[s];
-    const int w = (int)((S.off[s + 1] - off) >> 6);                 // uniform over the wave
-    const int slot = s * SL_C + lane;
-    const int row = S.row[slot];
-    const int len = S.len[slot];
+    const SellHdr *h = S.hdr + s;
+    const long off = h->off;
+    const long coff = h->coff;                                      // fetched with the entry offset, coded or not
+    const int w = h->w;
+    const bool coded = IDX16 && h->coded != 0;
+    const int org = IDX16 ? h->org[lane & 15] : 0;
+    const SellSlot sl = S.slot[s * SL_C + lane];
+    const int row = sl.row, len = sl.len;
     const double gscale = a.gscale;
+    const int *cp = S.col + off + lane;
+    const double *vp = S.val + off + lane;
+    const unsigned *wp = IDX16 ? S.code + coff + lane : nullptr;
+    double acc = 0.0;
     // the epilogue's streamed operands do not depend on the row sum: requested first
     double ep_b = 0.0, ep_v2 = 0.0;
     if (row >= 0) {
@@ -178,57 +246,12 @@ __global__ __launch_bounds__(SL_WG) void sell_kernel(StreamArgs a, SellArgs S, i
         if (MODE == SM_POLY_LAST) ep_v2 = a.v2[row];
         if (MODE == SM_MATVEC_ACC) ep_v2 = a.out[row];
     }
-    const int *cp = S.col + off + lane;
-    const double *vp = S.val + off + lane;
-    bool coded = false;
-    int org = 0;
-    const unsigned *wp = nullptr;
-    if constexpr (IDX16) {
-        coded = S.flag16[s] != 0;                                   // uniform over the wave
-        if (coded) {
-            org = S.org[s * 16 + (lane & 15)];
-            wp = S.code + S.coff[s] + lane;
-        }
-    }
-    double acc = 0.0;
     for (int k0 = 0; k0 < w; k0 += SL_PASS) {
-        int c[SL_PASS];
+        unsigned q[SL_PASS];
         double v[SL_PASS], xv[SL_PASS];
-        if (IDX16 && coded) {
-            unsigned wd[SL_PASS / 2];
-#pragma unroll
-            for (int u = 0; u < SL_PASS; u += 2) {
-                wd[u / 2] = 0u;
-                if (k0 + u < w) wd[u / 2] = __builtin_nontemporal_load(&wp[(long)((k0 + u) >> 1) * SL_C]);
-            }
-#pragma unroll
-            for (int u = 0; u < SL_PASS; ++u) {
-                v[u] = 0.0;
-                if (k0 + u < w) v[u] = __builtin_nontemporal_load(&vp[(long)(k0 + u) * SL_C]);
-            }
-#pragma unroll
-            for (int u = 0; u < SL_PASS; ++u) {
-                const unsigned code = (wd[u / 2] >> (16 * (u & 1))) & 0xffffu;
-                c[u] = __shfl(org, (int)(code >> 12), 64) + (int)(code & 4095u);
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < SL_PASS; ++u) {
-                c[u] = 0; v[u] = 0.0;
-                if (k0 + u < w) {                                       // uniform: the whole wave requests or skips
-                    c[u] = __builtin_nontemporal_load(&cp[(long)(k0 + u) * SL_C]);
-                    v[u] = __builtin_nontemporal_load(&vp[(long)(k0 + u) * SL_C]);
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < SL_PASS; ++u) xv[u] = (k0 + u < len) ? a.xg[c[u]] : 0.0;
-#pragma unroll
-        for (int u = 0; u < SL_PASS; ++u) {
-            const double pr = v[u] * (gscale * xv[u]);
-            const double nxt = acc + pr;
-            acc = (k0 + u < len) ? nxt : acc;
-        }
+        sell_request<SL_PASS, IDX16>(coded, wp, cp, vp, k0, w, q, v);
+        sell_gather<SL_PASS, IDX16>(coded, org, q, a.xg, k0, len, xv);
+        acc = sell_sum<SL_PASS>(acc, gscale, v, xv, k0, len);
     }
     if (row < 0) return;
     if (MODE == SM_MATVEC) {
@@ -246,8 +269,8 @@ __global__ __launch_bounds__(SL_WG) void sell_kernel(StreamArgs a, SellArgs S, i
         a.out[row] = cr + acc;
     } else if (MODE == SM_POLY_LAST) {
         const double cr = a.c0 * ep_b;
-        const double h = cr + acc;
-        __builtin_nontemporal_store(ep_v2 + h, &a.out[row]);
+        const double h2 = cr + acc;
+        __builtin_nontemporal_store(ep_v2 + h2, &a.out[row]);
     }
 }
 
@@ -258,17 +281,13 @@ int g_sell_idx16 = std::getenv("AMG_SELL_IDX16") ? std::atoi(std::getenv("AMG_SE
 
 void free_sell(DevCsr &M)
 {
-    if (M.sl_row) hipFree(M.sl_row);
-    if (M.sl_len) hipFree(M.sl_len);
-    if (M.sl_off) hipFree(M.sl_off);
+    if (M.sl_slot) hipFree(M.sl_slot);
+    if (M.sl_hdr) hipFree(M.sl_hdr);
     if (M.sl_col) hipFree(M.sl_col);
     if (M.sl_val) hipFree(M.sl_val);
     if (M.sl_code) hipFree(M.sl_code);
-    if (M.sl_org) hipFree(M.sl_org);
-    if (M.sl_coff) hipFree(M.sl_coff);
-    if (M.sl_flag16) hipFree(M.sl_flag16);
-    M.sl_row = nullptr; M.sl_len = nullptr; M.sl_off = nullptr; M.sl_col = nullptr; M.sl_val = nullptr;
-    M.sl_code = nullptr; M.sl_org = nullptr; M.sl_coff = nullptr; M.sl_flag16 = nullptr; M.sl_frac16 = 0.0;
+    M.sl_slot = nullptr; M.sl_hdr = nullptr; M.sl_col = nullptr; M.sl_val = nullptr;
+    M.sl_code = nullptr; M.sl_frac16 = 0.0;
     M.sl_nslices = 0; M.sl_entries = 0; M.sl_lo = M.sl_hi = 0;
 }
 
@@ -287,7 +306,7 @@ int launch_sell(StreamMode mode, const StreamArgs &a, const DevCsr &M, hipStream
     StreamArgs b = a;
     if (b.gscale == 0.0) b.gscale = 1.0;
     const bool idx16 = M.sl_code != nullptr && g_sell_idx16 != 0;
-    SellArgs S{M.sl_row, M.sl_len, M.sl_off, M.sl_col, M.sl_val, M.sl_nslices, M.sl_code, M.sl_org, M.sl_coff, M.sl_flag16};
+    SellArgs S{M.sl_slot, M.sl_hdr, M.sl_col, M.sl_val, M.sl_nslices, M.sl_code};
     const int grid = (M.sl_nslices + SL_WG / SL_C - 1) / (SL_WG / SL_C);
     // consecutive workgroups per XCD (speed only).  Measured at 400^3: 8 .. 128 equal within 1 %, 0 (round-robin over
     // the XCDs) 20 % slower, 512 2 % slower.  AMG_SELL_CHUNK overrides for A/B runs.
@@ -325,9 +344,9 @@ int build_sell(DevCsr &M, long *acct, int row_lo, int row_hi)
     const int sigma = (M.ncols >= 2L * M.nrows) ? SL_SIGMA_RECT : SL_SIGMA_SQUARE;
     const int nwin = (n + sigma - 1) / sigma;
     const int nslices = nwin * (sigma / SL_C);
-    int *row = nullptr, *w_dev = nullptr;
-    unsigned short *len = nullptr;
-    // longest row must fit the 11 + 21-bit sort key and the 16-bit length; average row length 8 .. 48 (see above)
+    int *w_dev = nullptr;
+    SellSlot *slot = nullptr;
+    // longest row must fit the 11 + 21-bit sort key; average row length 8 .. 48 (see above)
     long nnz_range = 0;
     {
         std::vector<int> hp((size_t)n + 1);
@@ -338,63 +357,61 @@ int build_sell(DevCsr &M, long *acct, int row_lo, int row_hi)
         nnz_range = (long)hp[(size_t)n] - hp[0];
     }
     if (n < (1 << 16) || nnz_range < 8L * n || nnz_range > 48L * n) return 0;
-    AMG_HIP(hipMalloc((void **)&row, sizeof(int) * (size_t)nslices * SL_C));
-    AMG_HIP(hipMalloc((void **)&len, sizeof(unsigned short) * (size_t)nslices * SL_C));
+    AMG_HIP(hipMalloc((void **)&slot, sizeof(SellSlot) * (size_t)nslices * SL_C));
     AMG_HIP(hipMalloc((void **)&w_dev, sizeof(int) * (size_t)nslices));
-    if (sigma == SL_SIGMA_RECT) hipLaunchKernelGGL((sell_sort_kernel<SL_SIGMA_RECT>), dim3(nwin), dim3(64), 0, nullptr, row_lo, n, M.Ap, row, len, w_dev);
-    else hipLaunchKernelGGL((sell_sort_kernel<SL_SIGMA_SQUARE>), dim3(nwin), dim3(256), 0, nullptr, row_lo, n, M.Ap, row, len, w_dev);
+    if (sigma == SL_SIGMA_RECT) hipLaunchKernelGGL((sell_sort_kernel<SL_SIGMA_RECT>), dim3(nwin), dim3(64), 0, nullptr, row_lo, n, M.Ap, slot, w_dev);
+    else hipLaunchKernelGGL((sell_sort_kernel<SL_SIGMA_SQUARE>), dim3(nwin), dim3(256), 0, nullptr, row_lo, n, M.Ap, slot, w_dev);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "sell sort launch", __FILE__, __LINE__);
     std::vector<int> hw((size_t)nslices);
     AMG_HIP(hipMemcpy(hw.data(), w_dev, sizeof(int) * (size_t)nslices, hipMemcpyDeviceToHost));
     hipFree(w_dev);
-    std::vector<long> off((size_t)nslices + 1);
-    off[0] = 0;
-    for (int s = 0; s < nslices; ++s) off[(size_t)s + 1] = off[(size_t)s] + (long)hw[(size_t)s] * SL_C;
-    const long entries = off[(size_t)nslices];
-    if ((double)entries > 1.15 * (double)nnz_range) { hipFree(row); hipFree(len); return 0; }
-    long *off_dev = nullptr;
+    // headers: entry offsets now; code-word offsets, origins and flags when the codes are built
+    std::vector<SellHdr> hdr((size_t)nslices);
+    long entries = 0;
+    for (int s = 0; s < nslices; ++s) {
+        hdr[(size_t)s] = SellHdr{};
+        hdr[(size_t)s].off = entries;
+        hdr[(size_t)s].w = hw[(size_t)s];
+        entries += (long)hw[(size_t)s] * SL_C;
+    }
+    if ((double)entries > 1.15 * (double)nnz_range) { hipFree(slot); return 0; }
+    const bool want16 = g_sell_idx16 && M.ncols >= 4096;
+    long words = 0;
+    if (want16)           // 16-bit column codes, two per word: ceil(width / 2) rows of 64 words per slice
+        for (int s = 0; s < nslices; ++s) { hdr[(size_t)s].coff = words; words += (long)((hw[(size_t)s] + 1) / 2) * SL_C; }
+    SellHdr *hdr_dev = nullptr;
     int *col = nullptr;
     double *val = nullptr;
-    AMG_HIP(hipMalloc((void **)&off_dev, sizeof(long) * ((size_t)nslices + 1)));
+    AMG_HIP(hipMalloc((void **)&hdr_dev, sizeof(SellHdr) * (size_t)nslices));
     AMG_HIP(hipMalloc((void **)&col, sizeof(int) * (size_t)std::max(entries, 1L)));
     AMG_HIP(hipMalloc((void **)&val, sizeof(double) * (size_t)std::max(entries, 1L)));
-    AMG_HIP(hipMemcpy(off_dev, off.data(), sizeof(long) * ((size_t)nslices + 1), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(sell_fill_kernel, dim3((nslices + SL_WG / SL_C - 1) / (SL_WG / SL_C)), dim3(SL_WG), 0, nullptr, nslices, M.Ap, M.Aj, M.Ax,
-                       row, len, off_dev, col, val);
+    AMG_HIP(hipMemcpy(hdr_dev, hdr.data(), sizeof(SellHdr) * (size_t)nslices, hipMemcpyHostToDevice));
+    const int bgrid = (nslices + SL_WG / SL_C - 1) / (SL_WG / SL_C);
+    hipLaunchKernelGGL(sell_fill_kernel, dim3(bgrid), dim3(SL_WG), 0, nullptr, nslices, M.Ap, M.Aj, M.Ax, slot, hdr_dev, col, val);
     e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "sell fill launch", __FILE__, __LINE__);
     AMG_HIP(hipDeviceSynchronize());
-    M.sl_row = row; M.sl_len = len; M.sl_off = off_dev; M.sl_col = col; M.sl_val = val;
+    M.sl_slot = slot; M.sl_hdr = hdr_dev; M.sl_col = col; M.sl_val = val;
     M.sl_nslices = nslices; M.sl_entries = entries; M.sl_lo = row_lo; M.sl_hi = row_hi;
-    if (g_sell_idx16 && M.ncols >= 4096) {
-        // 16-bit column codes, two per word: code words of slice s start at coff[s] (ceil(width / 2) rows of 64 words)
-        std::vector<long> coff((size_t)nslices + 1);
-        coff[0] = 0;
-        for (int s = 0; s < nslices; ++s) coff[(size_t)s + 1] = coff[(size_t)s] + (long)((hw[(size_t)s] + 1) / 2) * SL_C;
-        AMG_HIP(hipMalloc((void **)&M.sl_coff, sizeof(long) * ((size_t)nslices + 1)));
-        AMG_HIP(hipMalloc((void **)&M.sl_code, sizeof(unsigned) * (size_t)std::max(coff[(size_t)nslices], 1L)));
-        AMG_HIP(hipMalloc((void **)&M.sl_org, sizeof(int) * (size_t)nslices * 16));
-        AMG_HIP(hipMalloc((void **)&M.sl_flag16, (size_t)nslices));
-        AMG_HIP(hipMemcpy(M.sl_coff, coff.data(), sizeof(long) * ((size_t)nslices + 1), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(sell_code_kernel, dim3((nslices + SL_WG / SL_C - 1) / (SL_WG / SL_C)), dim3(SL_WG), 0, nullptr, nslices, len, off_dev, col,
-                           M.sl_coff, M.sl_code, M.sl_org, M.sl_flag16);
+    if (want16) {
+        AMG_HIP(hipMalloc((void **)&M.sl_code, sizeof(unsigned) * (size_t)std::max(words, 1L)));
+        hipLaunchKernelGGL(sell_code_kernel, dim3(bgrid), dim3(SL_WG), 0, nullptr, nslices, slot, hdr_dev, col, M.sl_code);
         e = hipGetLastError();
         if (e != hipSuccess) return hip_fail(e, "sell code launch", __FILE__, __LINE__);
-        std::vector<unsigned char> hf((size_t)nslices);
-        AMG_HIP(hipMemcpy(hf.data(), M.sl_flag16, (size_t)nslices, hipMemcpyDeviceToHost));
+        std::vector<SellHdr> back((size_t)nslices);
+        AMG_HIP(hipMemcpy(back.data(), hdr_dev, sizeof(SellHdr) * (size_t)nslices, hipMemcpyDeviceToHost));
         long coded = 0;
-        for (unsigned char f : hf) coded += f ? 1 : 0;
+        for (const SellHdr &r : back) coded += r.coded ? 1 : 0;
         M.sl_frac16 = nslices ? (double)coded / (double)nslices : 0.0;
-        if (acct) *acct += (long)(4L * coff[(size_t)nslices] + 65L * nslices + 8L * (nslices + 1));
         if (M.sl_frac16 < 0.5) {                                    // mostly fall-back slices: not worth the second array
-            if (acct) *acct -= (long)(4L * coff[(size_t)nslices] + 65L * nslices + 8L * (nslices + 1));
-            hipFree(M.sl_code); hipFree(M.sl_org); hipFree(M.sl_coff); hipFree(M.sl_flag16);
-            M.sl_code = nullptr; M.sl_org = nullptr; M.sl_coff = nullptr; M.sl_flag16 = nullptr; M.sl_frac16 = 0.0;
-        }
+            hipFree(M.sl_code);
+            M.sl_code = nullptr; M.sl_frac16 = 0.0;
+            for (SellHdr &r : hdr) r.coff = 0;                       // headers as of an operator without codes
+            AMG_HIP(hipMemcpy(hdr_dev, hdr.data(), sizeof(SellHdr) * (size_t)nslices, hipMemcpyHostToDevice));
+        } else if (acct) *acct += 4L * words;
     }
-    if (acct) *acct += (long)(sizeof(int) * (size_t)nslices * SL_C + sizeof(unsigned short) * (size_t)nslices * SL_C +
-                              sizeof(long) * ((size_t)nslices + 1) + 12L * entries);
+    if (acct) *acct += (long)(sizeof(SellSlot) * (size_t)nslices * SL_C + sizeof(SellHdr) * (size_t)nslices + 12L * entries);
     return 0;
 }
 
