@@ -335,6 +335,12 @@ int amg_value_index_enabled(void);
  * finalised hierarchy takes the fused path now (1) or not (0). */
 void amg_set_level0_fusion(int on);
 int amg_hier_level0_fused(amg_hier *h);
+/* r12: a setup-time scan flags the planes of that box on which every column's code word equals the one on the plane
+ * below; on those planes the chains keep the word in a register instead of loading it (the first plane of a z chunk
+ * always loads).  Same bits.  amg_set_level0_plane_reuse(0) makes every plane load (process-wide; tests, default 1);
+ * amg_hier_level0_plane_reuse returns the number of flagged planes, 0 when the chains are not taken or the switch is off. */
+void amg_set_level0_plane_reuse(int on);
+int amg_hier_level0_plane_reuse(amg_hier *h);
 /* Setup-side (replaces the host sweeps behind pyamg/aggregation/aggregation.py:313-320 `relaxation_as_linear_operator(
  * ('gauss_seidel', ...), A, 0) * B`, i.e. amg_core gauss_seidel of relaxation.h:34-62 on A x = 0): nsweeps Gauss-Seidel
  * sweeps over level lvl's operator in its own row order, from the CSR arrays in HBM; dirs[k] != 0 = descending rows;

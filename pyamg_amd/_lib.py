@@ -251,6 +251,10 @@ def lib():
     L.amg_set_level0_fusion.restype = None
     L.amg_hier_level0_fused.argtypes = [V]
     L.amg_hier_level0_fused.restype = I
+    L.amg_set_level0_plane_reuse.argtypes = [I]
+    L.amg_set_level0_plane_reuse.restype = None
+    L.amg_hier_level0_plane_reuse.argtypes = [V]
+    L.amg_hier_level0_plane_reuse.restype = I
     L.amg_value_index_enabled.argtypes = []
     L.amg_value_index_enabled.restype = I
     L.amg_hier_gs_natural.argtypes = [V, I, V, V, V, I]

@@ -115,6 +115,11 @@ struct DevCsr {
     // P = nx * ny, and no stored coupling leaves the box; 0 otherwise.
     int l0_ok = 0;
     int l0_nx = 0, l0_ny = 0, l0_nz = 0;
+    // Plane flags of an l0_ok operator (launch_level0_plane_scan): l0_same[z] = 1 iff every column's
+    // code word on plane z equals the one on plane z - 1 (l0_same[0] = 0); the chains then keep the word in a register.
+    unsigned char *l0_same = nullptr;    // [l0_nz], read as 32-bit words
+    int l0_nsame = 0;                    // planes whose flag is set
+    long l0_code_planes[2] = {0, 0};     // planes on which a chain of 2 / 3 stages loads code words, summed over the z chunks
 };
 constexpr int STENCIL_MAX = 31;
 constexpr int STENCIL_RANGES = 8;
@@ -211,6 +216,7 @@ struct Level0ChainArgs {
     double *xout, *rout;               // never an input of the same launch
     double c_gs, c_last;               // polynomial coefficients 0 and 1
     int zc;                            // planes per workgroup
+    const unsigned char *same;         // plane flags (DevCsr::l0_same) or null: every plane loads its code words
     int tiles_x, tiles_y;              // (set by the launcher)
 };
 int launch_level0_chain(bool first_res, bool last_res, const Level0ChainArgs &a, hipStream_t st);
@@ -218,6 +224,7 @@ int level0_chain_tile(int stages, int axis);   // interior tile extent (axis 0: 
 int level0_chain_lanes(int axis);              // the tile's extent in lanes
 int launch_sumsq_partials(const double *r, int n, double *out2, hipStream_t st);   // the SM_RESIDUAL_SUMSQ partials of a stored r
 int launch_level0_box_scan(const unsigned char *codes, int nx, int ny, int nz, int *bad, hipStream_t st);
+int launch_level0_plane_scan(const unsigned char *codes, long plane, int nz, unsigned char *same, hipStream_t st);
 int launch_stencil_build(const DevCsr &M, const int *dict_slot, const unsigned *pat_mask, hipStream_t st);
 // value index: distinct values of st_vals into a 1024-slot table (EMPTY = all ones), then the byte codes
 int launch_value_scan(const double *vals, long count, unsigned long long *table, int *overflow, hipStream_t st);

@@ -57,6 +57,7 @@ void free_csr(DevCsr &M)
     if (M.st_mask) hipFree(M.st_mask);
     if (M.st_codes) hipFree(M.st_codes);
     if (M.st_dict) hipFree(M.st_dict);
+    if (M.l0_same) hipFree(M.l0_same);
     if (M.Aj16) hipFree(M.Aj16);
     if (M.wg_base) hipFree(M.wg_base);
     if (M.wg_flag) hipFree(M.wg_flag);
@@ -1323,6 +1324,7 @@ static int coarse_solve(amg_hier *h, const double *b, double *&x, double *&xalt)
 
 // ------------------------------------------------------------------ fused level-0 chains (launch_level0_chain)
 static int g_level0_fusion = 1;
+static int g_level0_plane_reuse = 1;
 #ifndef L0_ZCHUNK_PLANES                        // (A/B builds: -DL0_ZCHUNK_PLANES=32 / 64)
 #define L0_ZCHUNK_PLANES 128
 #endif
@@ -1330,10 +1332,14 @@ constexpr int L0_ZCHUNK = L0_ZCHUNK_PLANES;           // planes per workgroup of
 
 // Decided once per operator, when its value index is built (amg_hier_set_matrix): the coded stencil is the 7-point one of
 // an (nz, ny, nx) box -- U = (-P, -L, -1, 0, 1, L, P), P % L == 0, n % P == 0 -- and one device scan of the codes finds
-// no stored coupling that leaves the box (a row at the end of a line storing its +1 slot, ...).
+// no stored coupling that leaves the box (a row at the end of a line storing its +1 slot, ...).  A second scan then
+// flags the planes whose code words all equal those of the plane below (DevCsr::l0_same): there the chains keep a
+// column's word in a register.
 static int level0_chain_check(amg_hier *h, DevCsr &M)
 {
     M.l0_ok = 0;
+    if (M.l0_same) { hipFree(M.l0_same); M.l0_same = nullptr; }
+    M.l0_nsame = 0; M.l0_code_planes[0] = M.l0_code_planes[1] = 0;
     if (!M.st_vals || !M.st_codes || M.st_nu != 7 || M.st_nranges != 0 || M.nrows != M.ncols || M.nrows < 1) return 0;
     const int *o = M.st_off;
     const long n = M.nrows, Lx = o[5], P = o[6];
@@ -1351,6 +1357,21 @@ static int level0_chain_check(amg_hier *h, DevCsr &M)
     if (rc != 0) return rc;
     if (found) return 0;
     M.l0_nx = (int)Lx; M.l0_ny = (int)(P / Lx); M.l0_nz = (int)(n / P);
+    const int nz = M.l0_nz;
+    std::vector<unsigned char> same((size_t)nz, 0);
+    if (dev_alloc(&M.l0_same, (nz + 3) / 4 * 4, &h->dev_bytes) != 0) return AMG_ENOMEM;
+    CHK(launch_level0_plane_scan(M.st_codes, P, nz, M.l0_same, h->stream));
+    AMG_HIP(hipMemcpyAsync(same.data(), M.l0_same, (size_t)nz, hipMemcpyDeviceToHost, h->stream));
+    AMG_HIP(hipStreamSynchronize(h->stream));
+    for (int z = 0; z < nz; ++z) M.l0_nsame += same[z] ? 1 : 0;
+    // what the chains load (cycle_bytes_moved): per z chunk the first plane in range, then the planes with a clear flag
+    const int zc = std::min(L0_ZCHUNK, nz);
+    for (int S = 2; S <= 3; ++S)
+        for (int z0 = 0; z0 < nz; z0 += zc) {
+            const int lo = std::max(z0 - S, 0), hi = std::min(std::min(z0 + zc, nz) + S, nz);
+            M.l0_code_planes[S - 2] += 1;
+            for (int z = lo + 1; z < hi; ++z) M.l0_code_planes[S - 2] += same[z] ? 0 : 1;
+        }
     M.l0_ok = 1;
     return 0;
 }
@@ -1382,6 +1403,7 @@ static int level0_chain(amg_hier *h, const Smoother &s, bool first_res, bool las
     a.g0 = g0; a.x = x; a.b = b; a.xout = xalt; a.rout = rout;
     a.c_gs = s.coef[0]; a.c_last = s.coef[1];
     a.zc = std::min(L0_ZCHUNK, M.l0_nz);
+    a.same = g_level0_plane_reuse ? M.l0_same : nullptr;
     CHK(launch_level0_chain(first_res, last_res, a, h->stream));
     std::swap(x, xalt);
     return 0;
@@ -2651,18 +2673,22 @@ static double cycle_bytes_impl(amg_hier *h, int cyc, bool moved)
         double extra = 0.0;
         if (l == 0 && moved && level0_fused(h)) {
             // the two chains: per interior row, 8 B per loaded vector, code word and output; the first stage's operand is
-            // loaded on the whole tile, the row operands on the tile less its outer ring, both over the chunk's planes
-            // plus the halo planes; + the partial sums' pass over the stored residual
+            // loaded on the whole tile, the row operands on the tile less its outer ring (b of the chain without a leading
+            // residual: on the interior), both over the chunk's planes plus the halo planes; the code words only on the
+            // planes that load them (DevCsr::l0_code_planes); + the partial sums' pass over the stored residual
             const double zc = std::min(L0_ZCHUNK, L.A.l0_nz);
             const double tx = level0_chain_lanes(0), ty = level0_chain_lanes(1);
-            auto chain = [&](int S, int row_operands, int outputs) {
+            const bool reuse = g_level0_plane_reuse && L.A.l0_same;
+            auto chain = [&](int S, int ring_operands, int inner_operands, int outputs) {
                 const double in = (double)level0_chain_tile(S, 0) * level0_chain_tile(S, 1);
                 const double zf = (zc + 2.0 * S) / zc;
-                return 8.0 * n * (tx * ty / in * zf + row_operands * (tx - 2.0) * (ty - 2.0) / in * zf + outputs);
+                const double ring = (tx - 2.0) * (ty - 2.0) / in;
+                const double zcodes = reuse ? (double)L.A.l0_code_planes[S - 2] / L.A.l0_nz : zf;
+                return 8.0 * n * (tx * ty / in * zf + ring * zcodes + ring_operands * ring * zf + inner_operands * zf + outputs);
             };
             const bool kept = h->keep_residual != 0;
-            const double pre = kept ? chain(2, 3, 2) : chain(3, 2, 2);     // r | x; codes, x, b | b; x', r'
-            const double post = chain(3, 2, 2) + 8.0 * n;                 // x; codes, b; x', r'; partials
+            const double pre = kept ? chain(2, 1, 1, 2) : chain(3, 1, 0, 2);   // r | x; codes; x | b; b |; x', r'
+            const double post = chain(3, 1, 0, 2) + 8.0 * n;                   // x; codes; b; x', r'; partials
             total += visits[l] * (pre + post + bytes_spmv(L.Rm) + bytes_spmv(L.P) + 8.0 * n);
             continue;
         }
@@ -3027,5 +3053,11 @@ void amg_hier_use_graphs(amg_hier *h, int on) { if (h) { h->use_graphs = on; if 
 void amg_hier_keep_residual(amg_hier *h, int on) { if (h) { h->keep_residual = on; h->r_kept = false; drop_graphs(h); } }
 void amg_set_level0_fusion(int on) { g_level0_fusion = on ? 1 : 0; amg::bump_config_epoch(); }
 int amg_hier_level0_fused(amg_hier *h) { return (h && h->finalized && level0_fused(h)) ? 1 : 0; }
+void amg_set_level0_plane_reuse(int on) { g_level0_plane_reuse = on ? 1 : 0; amg::bump_config_epoch(); }
+int amg_hier_level0_plane_reuse(amg_hier *h)
+{
+    if (!h || !h->finalized || !g_level0_plane_reuse || !level0_fused(h) || !h->lv[0].A.l0_same) return 0;
+    return h->lv[0].A.l0_nsame;
+}
 
 }  // extern "C"

@@ -2173,6 +2173,9 @@ int launch_stencil(StreamMode mode, const StreamArgs &a, const DevCsr &M, hipStr
 // row's sum is coded_row_sum over the same slots in the same order with the same gscale products, and residual_row /
 // poly_last_row are the unfused epilogues: the same bits as the separate stencil_coded_kernel passes.  The first
 // stage's operand is loaded one iteration ahead, the row operands (codes, b, x) too; no workgroup waits for another.
+// Where the operator does not change from plane k - 1 to plane k (Level0ChainArgs::same, a setup-time scan; DESIGN.md
+// §4 r12) a lane takes its column's code word from cq[0], the word it holds for plane k - 1, instead of loading it;
+// the first plane of a chunk always loads.  The flag is uniform over the workgroup and requested one iteration ahead.
 // ---------------------------------------------------------------------------
 #ifndef L0C_TY                                  // (A/B builds: -DL0C_TY=24 / 32)
 #define L0C_TY 16
@@ -2215,6 +2218,11 @@ __global__ __launch_bounds__(L0C_WG) void level0_chain_kernel(Level0ChainArgs a)
     double g_next = (inxy && k >= 0) ? a.g0[(long)k * P + col] : 0.0;
     unsigned long long c_next = ~0ULL;
     double b_next = 0.0, x_next = 0.0;
+    // (read-only for the whole launch and indexed uniformly: the constant address space makes the flag a scalar load)
+    typedef const unsigned __attribute__((address_space(4))) *const_words;
+    const const_words same32 = (const_words)a.same;
+    const int kfirst = max(z0 - S, 0);          // the chunk's first plane in range: its words are always loaded
+    unsigned same_next = 0;                     // the word that holds plane k's flag; 0 up to kfirst and outside [0, nz)
     const int iters = (z1 - z0) + 2 * S;
     for (int j = 0; j < iters; ++j, ++k) {
         w[0][0] = w[0][1]; w[0][1] = w[0][2]; w[0][2] = g_next;
@@ -2226,8 +2234,11 @@ __global__ __launch_bounds__(L0C_WG) void level0_chain_kernel(Level0ChainArgs a)
             g_next = (inxy && kn >= 0 && kn < a.nz) ? a.g0[(long)kn * P + col] : 0.0;
             const bool rowk = ring1 && k >= 0 && k < a.nz;
             const long ik = (long)k * P + col;
-            c_next = rowk ? a.codes[ik] : ~0ULL;               // (all slots absent)
-            b_next = rowk ? a.b[ik] : 0.0;
+            const bool reuse = ((same_next >> (8 * (k & 3))) & 0xFFu) != 0;   // then this workgroup had plane k - 1: cq[0] holds its word
+            same_next = (same32 && kn > kfirst && kn < a.nz) ? same32[kn >> 2] : 0u;
+            c_next = reuse ? cq[0] : (rowk ? a.codes[ik] : ~0ULL);   // (all slots absent; cq[0] is that outside ring 1)
+            if (FR) b_next = rowk ? a.b[ik] : 0.0;
+            else b_next = (inner && k >= 0 && k < a.nz) ? a.b[ik] : 0.0;   // only the trailing residual reads b, valid on the interior
             if (!FR) x_next = rowk ? a.x[ik] : 0.0;
         }
         // Every stage's middle plane is known here: stage 1's is the operand just shifted in, stage s >= 2's is what stage
@@ -2349,6 +2360,29 @@ int launch_level0_box_scan(const unsigned char *codes, int nx, int ny, int nz, i
                        nx, ny, nz, bad);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "level-0 box scan launch", __FILE__, __LINE__);
+    return 0;
+}
+
+// plane flags of the fused chains (DevCsr::l0_same): same[z] = 1 iff every column's code word on plane z is the one on
+// plane z - 1.  One workgroup per plane, one store per flag.
+__global__ __launch_bounds__(1024) void level0_plane_scan_kernel(const unsigned long long *codes, long plane, unsigned char *same)
+{
+    const int z = blockIdx.x;
+    int differs = z == 0;
+    if (z > 0) {
+        const unsigned long long *cur = codes + (long)z * plane, *below = cur - plane;
+        for (long c = threadIdx.x; c < plane; c += blockDim.x) differs |= cur[c] != below[c];
+    }
+    differs = __syncthreads_or(differs);
+    if (threadIdx.x == 0) same[z] = differs ? 0 : 1;
+}
+
+int launch_level0_plane_scan(const unsigned char *codes, long plane, int nz, unsigned char *same, hipStream_t st)
+{
+    hipLaunchKernelGGL(level0_plane_scan_kernel, dim3(nz), dim3(1024), 0, st, reinterpret_cast<const unsigned long long *>(codes),
+                       plane, same);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "level-0 plane scan launch", __FILE__, __LINE__);
     return 0;
 }
 
