@@ -132,6 +132,24 @@ int amgcore_csr_matvec_f64(int n_row, int n_col, const int Ap[], const int Aj[],
                            const double Ax[], const double x[], double y[]);
 int amgcore_bsr_matvec_f64(int n_brow, int n_bcol, int R, int C, const int Ap[], const int Aj[],
                            const double Ax[], const double x[], double y[]);
+
+/* pyamg/amg_core/evolution_strength.h (called by pyamg/strength.py:658-662, 781-782, 802-803).  float64 only: the
+ * measure they serve is real by the time they run.  Each is the reference's loop, operation for operation:
+ * incomplete_mat_mult_csr (:675-699): Sx[ptr] = <A[row, :], B[:, col]> on the pattern of S, A and S sorted CSR,
+ *   B sorted CSC; every sum starts from 0.0, takes its products in index order, multiply and add round separately.
+ * apply_distance_filter (:135-167): per row, threshold = epsilon * min(off-diagonal values, from DBL_MAX); the
+ *   diagonal becomes 1.0, off-diagonal values >= threshold 0.0.  apply_absolute_distance_filter (:60-83): threshold
+ *   = epsilon.
+ * min_blocks (:212-237): Tx[i] = smallest non-zero value of block i (blocksize values), DBL_MAX when it has none. */
+int amgcore_incomplete_mat_mult_csr_f64(const int Ap[], int Ap_size, const int Aj[], int Aj_size, const double Ax[], int Ax_size,
+                                        const int Bp[], int Bp_size, const int Bj[], int Bj_size, const double Bx[], int Bx_size,
+                                        const int Sp[], int Sp_size, const int Sj[], int Sj_size, double Sx[], int Sx_size,
+                                        int num_rows);
+int amgcore_apply_distance_filter_f64(int n_row, double epsilon, const int Sp[], int Sp_size, const int Sj[], int Sj_size,
+                                      double Sx[], int Sx_size);
+int amgcore_apply_absolute_distance_filter_f64(int n_row, double epsilon, const int Sp[], int Sp_size, const int Sj[],
+                                               int Sj_size, double Sx[], int Sx_size);
+int amgcore_min_blocks_f64(int n_blocks, int blocksize, const double Sx[], int Sx_size, double Tx[], int Tx_size);
 /* pyamg/util/linalg.py:17-53 norm(x) (2-norm) */
 int amgcore_norm2_f64(const double x[], long n, double *result);
 
@@ -562,6 +580,18 @@ int amg_galerkin_device_c128(int n_fine, int n_coarse, const int64_t *Rp, const 
                              const int64_t *Ap, const int *Aj, const void *Ax,
                              const int64_t *Pp, const int *Pj, const void *Px, int64_t *Cp, amg_galerkin **out);
 int amg_galerkin_fetch_c128(amg_galerkin *g, int *Cj, void *Cx);
+
+/* Evolution strength of connection (pyamg/strength.py:433-816) for a real operator and ONE candidate vector, every
+ * stage in HBM (csrc/strength.hip).  A: n x n CSR on the host with sorted rows, no duplicates and
+ * no stored zeros (64-bit offsets); b: the candidate; rho: the spectral-radius estimate of Dinv A; k = 1, 2, 4, ...
+ * (AMG_ENOTIMPL otherwise); symmetrize: 0.5 (S + S^T) before the unit diagonal.  On return Cp (n + 1 offsets) is
+ * filled and *out holds the measure; amg_strength_fetch copies its columns and values (Cp[n] each) to the host and
+ * releases it.  Same bits and stored order as the reference's sequence given the same rho.  times_ms (or NULL)
+ * receives the milliseconds of the upload [0] and of the stages [1]. */
+typedef struct amg_strength amg_strength;
+int amg_evolution_strength_device(int n, const int64_t *Ap, const int *Aj, const double *Ax, const double *b, double rho,
+                                  double epsilon, int k, int symmetrize, int64_t *Cp, amg_strength **out, double *times_ms);
+int amg_strength_fetch(amg_strength *s, int *Cj, double *Cx);
 
 /* ------------------------------------------------------------------------ */
 /* 5. Resident hierarchies of other value types: the cycle of section 2      */

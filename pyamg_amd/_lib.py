@@ -65,7 +65,15 @@ FLAT_TABLE = {
     "block_gauss_seidel": ("IIVVVViiii", True),
     "csr_matvec": ("iiIIVVV", False),
     "bsr_matvec": ("iiiiIIVVV", False),
+    # amg_core/evolution_strength.h (csrc/strength.hip)
+    "incomplete_mat_mult_csr": ("IIVIIVIIVi", True),
+    "apply_distance_filter": ("iFIIV", True),
+    "apply_absolute_distance_filter": ("iFIIV", True),
+    "min_blocks": ("iiVV", True),
 }
+# entries whose values are float64 only: another value dtype is the table's overload error
+FLAT_F64_ONLY = frozenset(["incomplete_mat_mult_csr", "apply_distance_filter", "apply_absolute_distance_filter",
+                           "min_blocks"])
 # value dtype -> symbol suffix, and per suffix the C types of a value pointer and of the real scalar F
 VALUE_SUFFIX = {np.dtype(np.float64): "f64", np.dtype(np.float32): "f32",
                 np.dtype(np.complex64): "c64", np.dtype(np.complex128): "c128"}
@@ -173,6 +181,8 @@ def lib():
         "amg_csr_matmat_device_c128": [I, I, I, V, V, V, V, V, V, V, C.POINTER(C.c_void_p)],
         "amg_galerkin_device_c128": [I, I, V, V, V, V, V, V, V, V, V, V, C.POINTER(C.c_void_p)],
         "amg_galerkin_fetch_c128": [V, V, V],
+        "amg_evolution_strength_device": [I, V, V, V, V, D, D, I, I, V, C.POINTER(C.c_void_p), c_dbl_p],
+        "amg_strength_fetch": [V, V, V],
         "amg_hierx_create": [I, I, I, C.POINTER(C.c_void_p)],
         "amg_hierx_set_matrix": [V, I, I, I, I, I, I, I, V, V, V],
         "amg_hierx_set_smoother": [V, I, I, C.POINTER(SmootherDescX)],
@@ -206,6 +216,8 @@ def lib():
     }
     for name, (kinds, sized) in FLAT_TABLE.items():
         for suffix in VALUE_SUFFIX.values():
+            if name in FLAT_F64_ONLY and suffix != "f64":
+                continue
             sig["amgcore_%s_%s" % (name, suffix)] = flat_argtypes(kinds, sized, suffix)
     for name, args in sig.items():
         f = getattr(L, name)

@@ -5,7 +5,8 @@ travel (the GPU box).  The hierarchy is built ONCE on the host and shipped to
 HBM by ``multilevel_solver``; nothing here runs inside the cycle.
 
 Supported subset (anything else raises NotImplementedError):
-  strength   'symmetric' (any theta) | None | ('predefined', {'C': csr})
+  strength   'symmetric' (any theta) | 'evolution' / 'ode' (one candidate, strength.py) | None |
+             ('predefined', {'C': csr})
   aggregate  'standard' | ('predefined', {'AggOp': csr})
   smooth     ('jacobi', {'omega', 'degree'}) | None
   symmetry   'hermitian' | 'symmetric'
@@ -105,6 +106,10 @@ def host_lib():
             vp = VALUE_CTYPES[suffix][0]
             f.argtypes = [ip, ip, vp, vp, ip, ip, ip, C.c_int, C.c_int]
             f.restype = None
+        L.amgsetup_incomplete_mat_mult_csr.argtypes = [ip, ip, dp, ip, ip, dp, ip, ip, dp, C.c_int]
+        L.amgsetup_incomplete_mat_mult_csr.restype = None
+        L.amgsetup_apply_distance_filter.argtypes = [C.c_int, C.c_double, ip, ip, dp, C.c_int]
+        L.amgsetup_apply_distance_filter.restype = None
         L.amgsetup_num_threads.restype = C.c_int
         L.amgsetup_set_num_threads.argtypes = [C.c_int]
         L.amgsetup_set_num_threads.restype = None
@@ -1065,6 +1070,12 @@ def extend_hierarchy(levels, strength, aggregate, smooth, improve_candidates, ke
     fn, kwargs = unpack_arg(strength[len(levels) - 1])
     if fn == "symmetric":
         Cm = symmetric_strength_of_connection(A, **kwargs)
+    elif fn in ("ode", "evolution"):
+        from .strength import evolution_strength_of_connection
+        if "B" in kwargs:
+            Cm = evolution_strength_of_connection(A, **kwargs)
+        else:
+            Cm = evolution_strength_of_connection(A, B, **kwargs)
     elif fn == "predefined":
         Cm = kwargs["C"].tocsr()
     elif fn is None:

@@ -17,7 +17,8 @@ from . import _lib
 
 __all__ = ["gauss_seidel", "bsr_gauss_seidel", "jacobi", "bsr_jacobi", "gauss_seidel_indexed",
            "jacobi_ne", "gauss_seidel_ne", "gauss_seidel_nr", "block_jacobi", "block_gauss_seidel",
-           "csr_matvec", "bsr_matvec", "overlapping_schwarz_csr", "extract_subblocks"]
+           "csr_matvec", "bsr_matvec", "overlapping_schwarz_csr", "extract_subblocks",
+           "incomplete_mat_mult_csr", "apply_distance_filter", "apply_absolute_distance_filter", "min_blocks"]
 
 _INDEX = np.dtype(np.intc)
 
@@ -58,6 +59,8 @@ def _call(name, *args):
     if len(args) != len(kinds):
         raise TypeError("%s: %d arguments expected" % (name, len(kinds)))
     suffix = _check_arrays(name, kinds, args)
+    if name in _lib.FLAT_F64_ONLY and suffix != "f64":
+        raise _overload_error(name)
     vptr, real = _lib.VALUE_CTYPES[suffix]
     cargs = []
     for kind, a in zip(kinds, args):
@@ -126,6 +129,29 @@ def overlapping_schwarz_csr(Ap, Aj, Ax, x, b, Tx, Tp, Sj, Sp, nsdomains, nrows, 
     """relaxation.h:935-1007: one sweep of multiplicative overlapping Schwarz (HIP, by dependency levels)"""
     _call("overlapping_schwarz_csr", Ap, Aj, Ax, x, b, Tx, Tp, Sj, Sp, nsdomains, nrows, row_start, row_stop,
           row_step)
+
+
+def incomplete_mat_mult_csr(Ap, Aj, Ax, Bp, Bj, Bx, Sp, Sj, Sx, dimen):
+    """evolution_strength.h:575-699: Sx[ptr] = <A[row, :], B[:, col]> on the pattern of S (A, S sorted CSR; B sorted
+    CSC); float64"""
+    _call("incomplete_mat_mult_csr", Ap, Aj, Ax, Bp, Bj, Bx, Sp, Sj, Sx, dimen)
+
+
+def apply_distance_filter(n_row, epsilon, Sp, Sj, Sx):
+    """evolution_strength.h:136-167: per row, off-diagonal values >= epsilon * (smallest off-diagonal value) become
+    0.0 and the diagonal 1.0, in place; float64"""
+    _call("apply_distance_filter", n_row, epsilon, Sp, Sj, Sx)
+
+
+def apply_absolute_distance_filter(n_row, epsilon, Sp, Sj, Sx):
+    """evolution_strength.h:61-83: off-diagonal values >= epsilon become 0.0 and the diagonal 1.0, in place; float64"""
+    _call("apply_absolute_distance_filter", n_row, epsilon, Sp, Sj, Sx)
+
+
+def min_blocks(n_blocks, blocksize, Sx, Tx):
+    """evolution_strength.h:213-237: Tx[i] = the smallest non-zero value of block i of Sx (DBL_MAX when it has
+    none); float64"""
+    _call("min_blocks", n_blocks, blocksize, Sx, Tx)
 
 
 def extract_subblocks(Ap, Aj, Ax, Tx, Tp, Sj, Sp, nsdomains, nrows):

@@ -1418,3 +1418,52 @@ void amgsetup_extract_subblocks_c128(const int *Ap, const int *Aj, const void *A
 }
 
 }  // extern "C"
+
+// ---- evolution strength of connection (pyamg/strength.py:433-816): the two native steps of the host path, stated as
+// evolution_strength.h states them and row-parallel (rows are independent).
+extern "C" {
+
+// Sx[ptr] = <A[row, :], B[:, col]> on the pattern of S; A and S sorted CSR, B sorted CSC.  Every sum starts from 0.0
+// and takes its products in index order.
+void amgsetup_incomplete_mat_mult_csr(const int *Ap, const int *Aj, const double *Ax, const int *Bp, const int *Bj,
+                                      const double *Bx, const int *Sp, const int *Sj, double *Sx, int num_rows)
+{
+#pragma omp parallel for schedule(dynamic, 256)
+    for (int row = 0; row < num_rows; ++row) {
+        for (int ptr = Sp[row]; ptr < Sp[row + 1]; ++ptr) {
+            const int col = Sj[ptr];
+            double sum = 0.0;
+            int a = Ap[row], b = Bp[col];
+            const int a_end = Ap[row + 1], b_end = Bp[col + 1];
+            while (a < a_end && b < b_end) {
+                const int ja = Aj[a], jb = Bj[b];
+                if (ja == jb) { sum += Ax[a] * Bx[b]; ++a; ++b; }
+                else if (ja < jb) ++a;
+                else ++b;
+            }
+            Sx[ptr] = sum;
+        }
+    }
+}
+
+// per row: threshold = epsilon * (smallest off-diagonal value, from DBL_MAX); the diagonal becomes 1.0, off-diagonal
+// values >= threshold become 0.0 (absolute != 0: the threshold is epsilon itself)
+void amgsetup_apply_distance_filter(int n_row, double epsilon, const int *Sp, const int *Sj, double *Sx, int absolute)
+{
+#pragma omp parallel for schedule(static)
+    for (int i = 0; i < n_row; ++i) {
+        double threshold = epsilon;
+        if (!absolute) {
+            double m = std::numeric_limits<double>::max();
+            for (int jj = Sp[i]; jj < Sp[i + 1]; ++jj)
+                if (Sj[jj] != i) m = std::min(m, Sx[jj]);
+            threshold = epsilon * m;
+        }
+        for (int jj = Sp[i]; jj < Sp[i + 1]; ++jj) {
+            if (Sj[jj] == i) Sx[jj] = 1.0;
+            else if (Sx[jj] >= threshold) Sx[jj] = 0.0;
+        }
+    }
+}
+
+}  // extern "C"

@@ -549,6 +549,20 @@ __global__ void widen_rowptr_kernel(int n, const int *Ap32, long *Ap64)
 
 }   // namespace
 
+namespace amg {
+// C = A * A for a square operand already in HBM (the squarings of the evolution strength measure, strength.hip); the
+// arrays of C are allocated here and belong to the caller
+int spgemm_square_device(int n, long nnz, long *Ap, int *Aj, double *Ax, long *Cnnz, long **Cp, int **Cj, double **Cx)
+{
+    DCsr A, C;
+    A.n_row = n; A.n_col = n; A.nnz = nnz; A.Ap = Ap; A.Aj = Aj; A.Ax = Ax; A.owned = false;
+    const int rc = matmat(A, A, C);
+    if (rc != 0) { dcsr_free(C); return rc; }
+    *Cnnz = C.nnz; *Cp = C.Ap; *Cj = C.Aj; *Cx = C.Ax;
+    return 0;
+}
+}   // namespace amg
+
 struct amg_galerkin {
     DCsr C;
     DCsrT<c128> Cz;             // the product of the complex128 entries (is_c128)
