@@ -7,7 +7,7 @@ import scipy.sparse as sps
 import evolution_io as eio
 import golden_io
 import pyamg_amd
-from pyamg_amd import amg_core
+from pyamg_amd import amg_core, strength, util
 from pyamg_amd.gallery import poisson
 from pyamg_amd.strength import evolution_strength_of_connection
 
@@ -202,6 +202,162 @@ def test_pipeline_products_that_cancel_exactly():
             H = evolution_strength_of_connection(A, device=False, **kw)
             D = evolution_strength_of_connection(A, device=True, **kw)
             eio.same_bits(D, H)
+
+
+# ---------------------------------------------------------------------------------------------- working size
+# evolution_io.large_grid / large_unsym hold more than 2^20 entries and more than 65 536 rows (asserted where they are
+# built; the rocPRIM limits they are chosen against are named there, read from rocprim/device/device_radix_sort.hpp and
+# device_radix_sort_config.hpp).  Every transpose and row sort of their Jacobi step (and the k = 4 square of about
+# 5.7 M entries on the grid) is therefore sorted by onesweep over all 64 key bits with row bits above bit 48 set, and
+# every count/scan/fill stage scans n + 1 > 150 000 counts with the multi-block look-back scan.
+_host_large = {}
+
+
+def host_large(name, k, sym=True, eps=eio.LARGE_EPSILON):
+    """the host result, pinned to the reference's digests by tests/test_strength_evolution_host.py; computed once"""
+    key = (name, k, sym, eps)
+    if key not in _host_large:
+        A, B = eio.large_problem(name)
+        _host_large[key] = evolution_strength_of_connection(A, B, epsilon=eps, k=k, symmetrize_measure=sym, device=False,
+                                                            rho=eio.large_digests()[name][k]["rho"])
+    return _host_large[key]
+
+
+@pytest.mark.parametrize("k", eio.KS)
+@pytest.mark.parametrize("name", eio.LARGE)
+def test_pipeline_reproduces_the_reference_digests_at_working_size(name, k):
+    A, B = eio.large_problem(name)
+    d = eio.large_digests()[name]
+    assert eio.digests(A) == d["A"] and eio.sha(B, "<f8") == d["B"], "the builder did not rebuild the recorded input"
+    D = evolution_strength_of_connection(A, B, epsilon=eio.LARGE_EPSILON, k=k, device=True, rho=d[k]["rho"])
+    try:
+        eio.assert_large_digests(D, d[k], "%s k=%d, device pipeline" % (name, k))
+    except AssertionError:
+        eio.same_bits(D, host_large(name, k))               # names the first array and position that differ
+        raise
+
+
+@pytest.mark.parametrize("sym,eps", VARIANTS)
+def test_pipeline_variants_equal_the_host_path_at_working_size(sym, eps):
+    A, B = eio.large_grid()
+    H = host_large("large_grid", 2, sym, eps)
+    if (sym, eps) in ((True, 4.0), (False, np.inf)):        # 1 151 520 and 1 610 398 entries: the later sorts are onesweep too
+        assert H.nnz > eio.SORT_MERGE_LIMIT
+    D = evolution_strength_of_connection(A, B, epsilon=eps, k=2, symmetrize_measure=sym, device=True,
+                                         rho=eio.large_digests()["large_grid"][2]["rho"])
+    eio.same_bits(D, H)
+
+
+def test_incomplete_product_at_working_size_on_sampled_entries():
+    """the flat entry on the large unsymmetric operator, its CSC form and its own pattern, against the sequential model on
+    4096 entries: every entry of the 3000-entry row 23, every entry of column 23, the rest drawn"""
+    A, _ = eio.large_unsym()
+    Bc = A.tocsc()
+    Bc.sort_indices()
+    Sx = np.full(A.nnz, np.nan)
+    amg_core.incomplete_mat_mult_csr(ic(A.indptr), ic(A.indices), A.data, ic(Bc.indptr), ic(Bc.indices), Bc.data,
+                                     ic(A.indptr), ic(A.indices), Sx, A.shape[0])
+    rows = np.repeat(np.arange(A.shape[0]), np.diff(A.indptr))
+    special = np.flatnonzero((rows == 23) | (A.indices == 23))
+    assert 3000 <= special.size < 4096 and np.count_nonzero(A.indices[special] == 23) > 1
+    rest = np.setdiff1d(np.arange(A.nnz), special)
+    pick = np.sort(np.concatenate([special, np.random.RandomState(0).choice(rest, 4096 - special.size, replace=False)]))
+    model = eio.model_incomplete_entries(A.indptr, A.indices, A.data, Bc.indptr, Bc.indices, Bc.data, rows[pick], A.indices[pick])
+    assert not np.any(np.isnan(Sx))
+    assert np.array_equal(Sx[pick], model), np.flatnonzero(Sx[pick] != model)[:5]
+
+
+# ---------------------------------------------------------------------------------------------- block boundaries
+def boundary_operator(n, seed, entries=None):
+    """random unsymmetric n x n operator, about 7 entries per row, with the row kinds of unsym_400: row 7 stores no
+    diagonal, row 11 a stored zero diagonal, row 19 is empty.  entries: every row keeps a non-zero diagonal instead and
+    the operator holds exactly that many entries, none zero (its Jacobi step then holds as many: 1 - x / rho and
+    0 - x / rho are not zero for the rho of the test)."""
+    rng = np.random.RandomState(seed)
+    M = sps.random(n, n, density=6.0 / n, random_state=rng, format="lil", data_rvs=lambda s: rng.uniform(-1.0, 1.0, s))
+    for i in range(n):
+        M[i, i] = 4.0 + rng.rand()
+    if entries is None:
+        M[19, :] = 0.0
+        M[7, 7] = 0.0
+    A = sps.csr_matrix(M)
+    A.eliminate_zeros()
+    A.sort_indices()
+    if entries is None:
+        A[11, 11] = 0.0                                     # stays stored
+        assert A.nnz == np.count_nonzero(A.data) + 1 and A.indptr[20] == A.indptr[19] and A[7, 7] == 0.0
+    else:
+        off = np.flatnonzero(A.indices != np.repeat(np.arange(n), np.diff(A.indptr)))
+        A.data[rng.choice(off, A.nnz - entries, replace=False)] = 0.0
+        A.eliminate_zeros()
+        assert A.nnz == entries and np.all(A.diagonal() != 0.0)
+    B = rng.uniform(0.5, 1.5, n)
+    B[::9] *= -1.0
+    B[[3, 23, 50]] = 0.0
+    return A, B
+
+
+# n or n + 1 a multiple of the 256-thread block: the lane i == n that writes count[n] = 0 is the last of a full block
+# (n = 255, 511), the first of a block of its own (n = 256, 512) or the second (257).  1024 = 256 x 4 items is the
+# largest array rocPRIM's radix_sort_pairs sorts with one block; 1025 is the smallest it merge-sorts.
+BOUNDARY = [(255, None), (256, None), (257, None), (511, None), (512, None), (160, eio.SORT_ONE_BLOCK),
+            (160, eio.SORT_ONE_BLOCK + 1)]
+BOUNDARY_RHO = 1.3
+
+
+@pytest.mark.parametrize("k", eio.KS)
+@pytest.mark.parametrize("n,entries", BOUNDARY)
+def test_pipeline_equals_host_path_at_block_boundaries(n, entries, k):
+    A, B = boundary_operator(n, n + (entries or 0), entries)
+    for sym, eps in VARIANTS:
+        kw = dict(epsilon=eps, k=k, symmetrize_measure=sym, rho=BOUNDARY_RHO)
+        H = evolution_strength_of_connection(A, B, device=False, **kw)
+        D = evolution_strength_of_connection(A, B, device=True, **kw)
+        eio.same_bits(D, H)
+
+
+@pytest.mark.parametrize("k", (1, 2))
+@pytest.mark.parametrize("case", ["one_by_one", "one_by_one_cancelled", "empty_rows", "diagonal_only"])
+def test_pipeline_equals_host_path_on_degenerate_operators(case, k):
+    rho = 2.0
+    if case.startswith("one_by_one"):
+        A = sps.csr_matrix(np.array([[3.0]]))
+        rho = 1.0 if case.endswith("cancelled") else 2.0        # rho = 1: the Jacobi step 1 - 1 / rho stores nothing
+    elif case == "empty_rows":
+        A = sps.csr_matrix((5, 5), dtype=np.float64)
+    else:
+        A = sps.diags([np.arange(2.0, 9.0)], [0], format="csr")
+    for sym, eps in VARIANTS:
+        kw = dict(epsilon=eps, k=k, symmetrize_measure=sym, rho=rho)
+        H = evolution_strength_of_connection(A, device=False, **kw)
+        D = evolution_strength_of_connection(A, device=True, **kw)
+        eio.same_bits(D, H)
+    if case == "empty_rows":
+        eio.same_bits(H, sps.identity(5, format="csr"))
+
+
+# ---------------------------------------------------------------------------------------------- the gate
+def test_device_none_above_the_gate_takes_the_device_path(monkeypatch):
+    monkeypatch.setattr(strength, "DEVICE_AUTO", True)
+    monkeypatch.setattr(util, "DEVICE_RHO_MIN_ROWS", 1000)
+    taken = []
+    real = strength._device_measure
+
+    def wrapped(A, b, rho, epsilon, k, symmetrize_measure, *more):
+        taken.append(k)
+        return real(A, b, rho, epsilon, k, symmetrize_measure, *more)
+    monkeypatch.setattr(strength, "_device_measure", wrapped)
+    p = eio.problem("aniso_40x40")
+    C = evolution_strength_of_connection(p["A"], p["B"], epsilon=p["epsilon"], k=2, rho=p[2]["rho"])
+    assert taken == [2]
+    eio.same_bits(C, evolution_strength_of_connection(p["A"], p["B"], epsilon=p["epsilon"], k=2, rho=p[2]["rho"], device=False))
+    eio.same_bits(C, p[2]["C"])
+    # k = 3 is no power of two: the host path, not a refusal
+    with pytest.warns(UserWarning):
+        C3 = evolution_strength_of_connection(p["A"], p["B"], epsilon=p["epsilon"], k=3, rho=p[2]["rho"])
+    assert taken == [2]
+    with pytest.warns(UserWarning):
+        eio.same_bits(C3, evolution_strength_of_connection(p["A"], p["B"], epsilon=p["epsilon"], k=3, rho=p[2]["rho"], device=False))
 
 
 def test_pipeline_refuses_what_the_entry_cannot_take():

@@ -291,6 +291,7 @@ def test_pipelined_candidate_improvement_is_the_sequential_sweep(monkeypatch):
     other chunk by chunk (setup_host.cpp: pipelined_sweep): bit for bit the one-thread sweeps, point and block"""
     import scipy.sparse as sp
     from pyamg_amd import aggregation
+    monkeypatch.setenv("AMG_SETUP_DEVICE_GS", "0")            # the host sweeps, also where a GPU would take this size
     A = aggregation.poisson((60, 60, 60))                     # 216 000 rows, bandwidth 3 600
     A.symmetry = "hermitian"
     rng = np.random.RandomState(3)

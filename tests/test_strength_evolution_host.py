@@ -77,6 +77,30 @@ def test_host_path_with_recorded_rho_is_the_reference_bit_for_bit(name, k):
 
 
 @pytest.mark.parametrize("k", eio.KS)
+@pytest.mark.parametrize("name", eio.LARGE)
+def test_host_path_reproduces_the_reference_digests_at_working_size(name, k):
+    """large_digests.npz: the reference on the two problems of evolution_io above 2^20 entries and 65 536 rows.  With
+    this the host path is a reference-pinned oracle for the device pipeline at the size it is meant for."""
+    A, B = eio.large_problem(name)
+    d = eio.large_digests()[name]
+    assert eio.digests(A) == d["A"] and eio.sha(B, "<f8") == d["B"], "the builder did not rebuild the recorded input"
+    C = evolution_strength_of_connection(A, B, epsilon=eio.LARGE_EPSILON, k=k, device=False, rho=d[k]["rho"])
+    eio.assert_large_digests(C, d[k], "%s k=%d, host path" % (name, k))
+
+
+def test_sampled_model_of_the_incomplete_product_is_the_sequential_model():
+    p = eio.problem("unsym_400")
+    A = p["A"].copy()
+    A.eliminate_zeros()
+    B = A.tocsc()
+    B.sort_indices()
+    full = eio.model_incomplete_mat_mult(A.indptr, A.indices, A.data, B.indptr, B.indices, B.data, A.indptr, A.indices, 400)
+    rows = np.repeat(np.arange(400), np.diff(A.indptr))
+    assert np.array_equal(eio.model_incomplete_entries(A.indptr, A.indices, A.data, B.indptr, B.indices, B.data, rows,
+                                                       A.indices), full)
+
+
+@pytest.mark.parametrize("k", eio.KS)
 @pytest.mark.parametrize("name", eio.PROBLEMS)
 def test_host_path_bsr_1x1_input(name, k):
     p = eio.problem(name)

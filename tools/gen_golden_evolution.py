@@ -11,6 +11,10 @@ golden_io._all_cases() lists the hier_*.npz files of tests/golden/ itself):
   flat_kernels.npz     direct calls of min_blocks and apply_absolute_distance_filter, which the measure itself never
                        reaches with blocks larger than one entry
   hier_sa_evolution_2d.npz   one SA hierarchy and its solve in the hier_*.npz layout of oracle/gen_golden.py
+  large_digests.npz    the two problems of working size built by tests/evolution_io.py (large_grid, large_unsym; the same
+                       builders the tests call), k = 1, 2, 4: rho, nnz of C, SHA-256 of C's three arrays, of A's three
+                       arrays and of B, rows 0-31 and the last 32 rows of C verbatim.  Results of this size do not fit a
+                       committed file; only the distance filter's input is kept while recording, for the check below.
 
 Problems (built here from seeds): rotated anisotropic diffusion, Q1 finite elements on an nx x ny grid (9-point
 stencil from the reference's gallery.diffusion_stencil_2d), and one structurally unsymmetric random operator with
@@ -20,7 +24,7 @@ No drop decision may sit on a knife edge: for every problem and k the generator 
 every value from the threshold it is compared with (distance filter, |ratio| < 1e-4, angle, sqrt(eps)), asserts it is
 at least 1e-6 and prints the smallest.  The ratios are recomputed here with scipy products (rounding-level
 differences from the reference's values do not matter at 1e-6).
-Usage:  make -C oracle ref && python tools/gen_golden_evolution.py
+Usage:  make -C oracle ref && python tools/gen_golden_evolution.py [large]
 """
 import os
 import sys
@@ -30,8 +34,10 @@ import scipy.sparse as sps
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import ref_env  # noqa: E402
 import gen_golden  # noqa: E402
+import evolution_io as eio  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden", "evolution")
 KS = (1, 2, 4)
@@ -102,13 +108,14 @@ class Recorder(object):
     NAMES = ("incomplete_mat_mult_csr", "apply_distance_filter", "min_blocks", "apply_absolute_distance_filter",
              "evolution_strength_helper")
 
-    def __init__(self, core):
+    def __init__(self, core, keep=NAMES):
         self._core = core
+        self.keep = keep
         self.calls = []
 
     def __getattr__(self, name):
         fn = getattr(self._core, name)
-        if name not in self.NAMES:
+        if name not in self.NAMES or name not in self.keep:
             return fn
 
         def wrapped(*args):
@@ -134,17 +141,25 @@ def put_call(out, prefix, name, before, after):
     out["%s__%s_out" % (prefix, o)] = np.asarray(after[ARGS[name].index(o)])
 
 
-def gaps(A, B, rho, k, epsilon, filter_call):
+def gaps(A, B, rho, k, epsilon, filter_call, core=None):
     """smallest relative distance of a compared value from its threshold: (distance filter, 1e-4 rule, angle rule,
-    sqrt(eps) rule); the ratios from scipy products"""
+    sqrt(eps) rule); the ratios from scipy products.  core: the reference's native module, for operators whose full
+    k-th power does not fit memory: the last squaring is then its product on the pattern of A."""
     n = A.shape[0]
     Ac = A.copy(); Ac.eliminate_zeros(); Ac.sort_indices()
     D = A.diagonal(); Dinv = np.where(D != 0, 1.0 / np.where(D != 0, D, 1.0), 1.0)
     M = (sps.eye(n, format="csr") - (1.0 / rho) * sps.diags(Dinv) * A).T.tocsr()
     At = M
-    for _ in range(int(np.log2(k))):
+    for _ in range(int(np.log2(k)) - (1 if core is not None else 0)):
         At = At * At
-    if k > 1:
+    if k > 1 and core is not None:
+        At.sort_indices()
+        Bc = At.tocsc(); Bc.sort_indices()
+        pat = Ac.copy()
+        core.incomplete_mat_mult_csr(At.indptr, At.indices, At.data, Bc.indptr, Bc.indices, Bc.data, pat.indptr, pat.indices,
+                                     pat.data, n)
+        At = pat
+    elif k > 1:
         pat = Ac.copy(); pat.data[:] = 1.0
         At = At.multiply(pat).tocsr()
     At.eliminate_zeros(); At.sort_indices()
@@ -167,12 +182,12 @@ def gaps(A, B, rho, k, epsilon, filter_call):
     if filter_call is not None:
         _, before, _ = filter_call
         n_row, eps_, Sp, Sj, Sx = before
-        for i in range(n_row):
-            j = Sj[Sp[i]:Sp[i + 1]]; x = Sx[Sp[i]:Sp[i + 1]]
-            x = x[j != i]
-            if x.size:
-                thr = eps_ * x.min()
-                g_filter = min(g_filter, np.min(np.abs(x - thr) / thr))
+        r = np.repeat(np.arange(n_row), np.diff(Sp))
+        offd = Sj != r
+        rowmin = np.full(n_row, np.inf); np.minimum.at(rowmin, r[offd], Sx[offd])
+        if offd.any():
+            thr = eps_ * rowmin[r[offd]]
+            g_filter = np.min(np.abs(Sx[offd] - thr) / thr)
     return g_filter, g_ratio, g_angle, g_sqrt
 
 
@@ -222,6 +237,51 @@ def gen_problem(pyamg, name, A, B=None, epsilon=4.0):
     print("%-18s %6.0f KB, smallest gaps %s" % (name, os.path.getsize(path) / 1024, ", ".join("%.2e" % w for w in worst)))
 
 
+def gen_large(pyamg, core, epsilon=eio.LARGE_EPSILON):
+    """digests of the reference's results on the two problems of working size"""
+    import pyamg.strength as rs
+    out = {"epsilon": np.array(epsilon)}
+    U = lambda text: np.array(text, dtype="U64")
+    for name in eio.LARGE:
+        A, B = eio.large_problem(name)
+        for arr, d in zip(("indptr", "indices", "data"), eio.digests(A)):
+            out["%s__A_%s_sha" % (name, arr)] = U(d)
+        out["%s__B_sha" % name] = U(eio.sha(B, "<f8"))
+        worst = [np.inf] * 4
+        for k in KS:
+            rec = Recorder(rs.amg_core, keep=("apply_distance_filter",))
+            keep = rs.amg_core
+            rs.amg_core = rec
+            try:
+                np.random.seed(0)
+                Cm = rs.evolution_strength_of_connection(A.copy(), B.copy().reshape(-1, 1), epsilon=epsilon, k=k)
+            finally:
+                rs.amg_core = keep
+            np.random.seed(0)
+            D = A.diagonal(); Dinv = np.zeros_like(D); Dinv[D != 0] = 1.0 / D[D != 0]; Dinv[D == 0] = 1.0
+            rho = float(pyamg.util.linalg.approximate_spectral_radius(pyamg.util.utils.scale_rows(A, Dinv, copy=True)))
+            Cm = sps.csr_matrix(Cm)
+            pre = "%s__k%d_" % (name, k)
+            out[pre + "rho"] = np.array(rho)
+            out[pre + "nnz"] = np.array(Cm.nnz, dtype=np.int64)
+            for arr, d in zip(("indptr", "indices", "data"), eio.digests(Cm)):
+                out[pre + arr + "_sha"] = U(d)
+            n = Cm.shape[0]
+            for part, lo, hi in (("head", 0, 32), ("tail", n - 32, n)):
+                for arr, v in zip(("indptr", "indices", "data"), eio.rows_of(Cm, lo, hi)):
+                    out[pre + part + "_" + arr] = v
+            (filt,) = rec.calls
+            g = gaps(A, B, rho, k, epsilon, filt, core=core)
+            assert min(g) >= MIN_GAP, "%s k=%d: a drop decision within %g of its threshold: %r" % (name, k, MIN_GAP, g)
+            worst = [min(a, b_) for a, b_ in zip(worst, g)]
+            print("%-18s k=%d rho=%.15g nnz(C)=%d gaps: filter %.2e ratio %.2e angle %.2e sqrt(eps) %.2e"
+                  % (name, k, rho, Cm.nnz, g[0], g[1], g[2], g[3]))
+        print("%-18s smallest gaps %s" % (name, ", ".join("%.2e" % w for w in worst)))
+    path = os.path.join(OUT, "large_digests.npz")
+    np.savez_compressed(path, **out)
+    print("large_digests.npz  %6.0f KB" % (os.path.getsize(path) / 1024))
+
+
 def gen_flat(core):
     """direct calls of the two entries the measure never reaches with real blocks"""
     rng = np.random.RandomState(3)
@@ -249,6 +309,9 @@ def main():
     pyamg = ref_env.stage()
     sys.path.insert(0, os.path.join(ROOT, "oracle", "_ref"))
     import _amg_core as core
+    if sys.argv[1:] == ["large"]:                           # only large_digests.npz
+        gen_large(pyamg, core)
+        return
     gen_problem(pyamg, "aniso_40x40", anisotropic(pyamg, 40, 40, 0.01, np.pi / 6))
     gen_problem(pyamg, "aniso_17x23", anisotropic(pyamg, 17, 23, 0.001, np.pi / 4))
     gen_problem(pyamg, "aniso_9x31", anisotropic(pyamg, 9, 31, 0.1, 1.0))
@@ -263,6 +326,7 @@ def main():
                         lambda A, **kw: pyamg.smoothed_aggregation_solver(
                             A, strength=("evolution", {"k": 2, "epsilon": 4.0}), max_coarse=20, **kw),
                         gs, gs, dict(tol=1e-8))
+    gen_large(pyamg, core)
 
 
 if __name__ == "__main__":
