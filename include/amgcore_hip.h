@@ -150,6 +150,31 @@ int amgcore_apply_distance_filter_f64(int n_row, double epsilon, const int Sp[],
 int amgcore_apply_absolute_distance_filter_f64(int n_row, double epsilon, const int Sp[], int Sp_size, const int Sj[],
                                                int Sj_size, double Sx[], int Sx_size);
 int amgcore_min_blocks_f64(int n_blocks, int blocksize, const double Sx[], int Sx_size, double Tx[], int Tx_size);
+
+/* pyamg/amg_core/smoothed_aggregation.h, the three helpers of energy_prolongation_smoother (smooth.py:21-64, 283-457;
+ * util/utils.py:1617-1707; csrc/energy.hip).  float64 only.  One lane owns one scalar of the output and adds that
+ * scalar's products in the order the reference's loops reach them, multiply and add rounded separately, no atomics.
+ * incomplete_mat_mult_bsr (:797-869): Sx += A * B on the block pattern of S.  A: n_brow block rows of brow_A x bcol_A
+ *   blocks; B: Bp_size - 1 block rows of bcol_A x bcol_B blocks; S: brow_A x bcol_B blocks in n_bcol block columns.
+ *   Rows of A, B and S in any order.  An entry of S takes jj ascending through row i of A, kk ascending through row
+ *   Aj[jj] of B, the block product's inner index ascending.  A row of S that stores a column twice is reproduced as
+ *   the reference has it: the later slot receives everything, the earlier slot keeps what it held.
+ * satisfy_constraints_helper (:556-605): x = conj(B_c) (ColsPerBlock * NullDim values per block column), y = U * B_c
+ *   (RowsPerBlock * NullDim per block row), z = BtBinv (NullDim^2 per block row); every block of S loses
+ *   y_i * (z_i * x_j^T), both products from 0.0 with the inner index ascending.
+ * calc_BtB (:656-734): b = the products of the candidates' columns (BsqCols = NullDim (NullDim + 1) / 2 per row of
+ *   B_c); x[i] = B_i^T B_i over the scalar columns of block row i of S in stored order, from 0.0.
+ * Bad offsets, columns outside the matrix, null arrays and arrays shorter than the block sizes ask for are
+ * AMG_EINVAL before any launch. */
+int amgcore_incomplete_mat_mult_bsr_f64(const int Ap[], int Ap_size, const int Aj[], int Aj_size, const double Ax[], int Ax_size,
+                                        const int Bp[], int Bp_size, const int Bj[], int Bj_size, const double Bx[], int Bx_size,
+                                        const int Sp[], int Sp_size, const int Sj[], int Sj_size, double Sx[], int Sx_size,
+                                        int n_brow, int n_bcol, int brow_A, int bcol_A, int bcol_B);
+int amgcore_satisfy_constraints_helper_f64(int RowsPerBlock, int ColsPerBlock, int num_block_rows, int NullDim, const double x[],
+                                           int x_size, const double y[], int y_size, const double z[], int z_size, const int Sp[],
+                                           int Sp_size, const int Sj[], int Sj_size, double Sx[], int Sx_size);
+int amgcore_calc_BtB_f64(int NullDim, int Nnodes, int ColsPerBlock, const double b[], int b_size, int BsqCols, double x[], int x_size,
+                         const int Sp[], int Sp_size, const int Sj[], int Sj_size);
 /* pyamg/util/linalg.py:17-53 norm(x) (2-norm) */
 int amgcore_norm2_f64(const double x[], long n, double *result);
 
@@ -592,6 +617,21 @@ typedef struct amg_strength amg_strength;
 int amg_evolution_strength_device(int n, const int64_t *Ap, const int *Aj, const double *Ax, const double *b, double rho,
                                   double epsilon, int k, int symmetrize, int64_t *Cp, amg_strength **out, double *times_ms);
 int amg_strength_fetch(amg_strength *s, int *Cj, double *Cx);
+
+/* CG energy minimisation of a tentative prolongator (smooth.py:283-457) for a real operator, the whole iteration in HBM
+ * (csrc/energy.hip).  A: n_brow x n_brow blocks of R x R (BSR on the host).  Sp/Sj: the fixed
+ * pattern, n_brow x n_bcol blocks of R x Cc, rows sorted and unique (AMG_EINVAL otherwise).  Tx: the tentative
+ * prolongator's values on that pattern; Bc: the coarse candidates (n_bcol * Cc rows of ND values); BtBinv: ND x ND per
+ * block row; Dinv: one weight per scalar row.  Up to maxiter iterations; stops when <R, Z> < tol or R holds no
+ * non-zero.  *out then holds the result: amg_energy_fetch copies its values (on the pattern) to the host and releases
+ * it.  *iterations (or NULL): finished iterations.  trace (or NULL, else 2 * maxiter doubles): <R, Z> and <P, AP> of
+ * every started iteration.  times_ms (or NULL): milliseconds of the upload [0] and of the iterations [1]. */
+typedef struct amg_energy amg_energy;
+int amg_energy_smooth_device(int n_brow, int n_bcol, int R, int Cc, int ND, const int *Ap, const int *Aj, const double *Ax,
+                             const int *Sp, const int *Sj, const double *Tx, const double *Bc, const double *BtBinv,
+                             const double *Dinv, int maxiter, double tol, amg_energy **out, int *iterations, double *trace,
+                             double *times_ms);
+int amg_energy_fetch(amg_energy *h, double *Tx);
 
 /* ------------------------------------------------------------------------ */
 /* 5. Resident hierarchies of other value types: the cycle of section 2      */

@@ -70,10 +70,14 @@ FLAT_TABLE = {
     "apply_distance_filter": ("iFIIV", True),
     "apply_absolute_distance_filter": ("iFIIV", True),
     "min_blocks": ("iiVV", True),
+    # amg_core/smoothed_aggregation.h, the helpers of energy smoothing (csrc/energy.hip)
+    "incomplete_mat_mult_bsr": ("IIVIIVIIViiiii", True),
+    "satisfy_constraints_helper": ("iiiiVVVIIV", True),
+    "calc_BtB": ("iiiViVII", True),
 }
 # entries whose values are float64 only: another value dtype is the table's overload error
 FLAT_F64_ONLY = frozenset(["incomplete_mat_mult_csr", "apply_distance_filter", "apply_absolute_distance_filter",
-                           "min_blocks"])
+                           "min_blocks", "incomplete_mat_mult_bsr", "satisfy_constraints_helper", "calc_BtB"])
 # value dtype -> symbol suffix, and per suffix the C types of a value pointer and of the real scalar F
 VALUE_SUFFIX = {np.dtype(np.float64): "f64", np.dtype(np.float32): "f32",
                 np.dtype(np.complex64): "c64", np.dtype(np.complex128): "c128"}
@@ -183,6 +187,8 @@ def lib():
         "amg_galerkin_fetch_c128": [V, V, V],
         "amg_evolution_strength_device": [I, V, V, V, V, D, D, I, I, V, C.POINTER(C.c_void_p), c_dbl_p],
         "amg_strength_fetch": [V, V, V],
+        "amg_energy_smooth_device": [I, I, I, I, I, V, V, V, V, V, V, V, V, V, I, D, C.POINTER(C.c_void_p), c_int_p, V, c_dbl_p],
+        "amg_energy_fetch": [V, V],
         "amg_hierx_create": [I, I, I, C.POINTER(C.c_void_p)],
         "amg_hierx_set_matrix": [V, I, I, I, I, I, I, I, V, V, V],
         "amg_hierx_set_smoother": [V, I, I, C.POINTER(SmootherDescX)],

@@ -8,7 +8,8 @@ Supported subset (anything else raises NotImplementedError):
   strength   'symmetric' (any theta) | 'evolution' / 'ode' (one candidate, strength.py) | None |
              ('predefined', {'C': csr})
   aggregate  'standard' | ('predefined', {'AggOp': csr})
-  smooth     ('jacobi', {'omega', 'degree'}) | None
+  smooth     ('jacobi', {'omega', 'degree'}) | ('energy', {'krylov': 'cg', 'maxiter', 'tol', 'degree',
+             'weighting': 'local' | 'diagonal', 'device'}) (smooth.py) | None
   symmetry   'hermitian' | 'symmetric'
   improve_candidates  relaxation descriptors (run on the device) | None
 
@@ -32,7 +33,7 @@ from .util import (approximate_spectral_radius, approximate_spectral_radius_devi
                    release_device_operator, scale_rows, use_device_for)
 
 __all__ = ["smoothed_aggregation_solver", "standard_aggregation", "fit_candidates",
-           "symmetric_strength_of_connection", "jacobi_prolongation_smoother"]
+           "symmetric_strength_of_connection", "jacobi_prolongation_smoother", "energy_prolongation_smoother"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _host = None
@@ -110,6 +111,16 @@ def host_lib():
         L.amgsetup_incomplete_mat_mult_csr.restype = None
         L.amgsetup_apply_distance_filter.argtypes = [C.c_int, C.c_double, ip, ip, dp, C.c_int]
         L.amgsetup_apply_distance_filter.restype = None
+        L.amgsetup_incomplete_mat_mult_bsr.argtypes = [ip, ip, dp, ip, ip, dp, ip, ip, dp] + [C.c_int] * 5
+        L.amgsetup_incomplete_mat_mult_bsr.restype = None
+        L.amgsetup_satisfy_constraints_helper.argtypes = [C.c_int] * 4 + [dp, dp, dp, ip, ip, dp]
+        L.amgsetup_satisfy_constraints_helper.restype = None
+        L.amgsetup_calc_BtB.argtypes = [C.c_int, C.c_int, C.c_int, dp, C.c_int, dp, ip, ip]
+        L.amgsetup_calc_BtB.restype = None
+        L.amgsetup_energy_block_row_product.argtypes = [C.c_int] * 4 + [ip, ip, dp, dp, dp]
+        L.amgsetup_energy_block_row_product.restype = None
+        L.amgsetup_energy_inner_product.argtypes = [C.c_int, C.c_int, ip, dp, dp, dp]
+        L.amgsetup_energy_inner_product.restype = None
         L.amgsetup_num_threads.restype = C.c_int
         L.amgsetup_set_num_threads.argtypes = [C.c_int]
         L.amgsetup_set_num_threads.restype = None
@@ -1098,6 +1109,9 @@ def extend_hierarchy(levels, strength, aggregate, smooth, improve_candidates, ke
     fn, kwargs = unpack_arg(smooth[len(levels) - 1])
     if fn == "jacobi":
         P = jacobi_prolongation_smoother(A, T, Cm, B, **kwargs)
+    elif fn == "energy":
+        from .smooth import energy_prolongation_smoother
+        P = energy_prolongation_smoother(A, T, Cm, B, None, (False, {}), **kwargs)
     elif fn is None:
         P = T
     else:
@@ -1123,3 +1137,6 @@ def extend_hierarchy(levels, strength, aggregate, smooth, improve_candidates, ke
     A.symmetry = symmetry
     levels[-1].A = A
     levels[-1].B = B
+
+
+from .smooth import energy_prolongation_smoother  # noqa: E402  (smooth.py needs host_lib from this module)

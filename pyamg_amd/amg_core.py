@@ -18,7 +18,8 @@ from . import _lib
 __all__ = ["gauss_seidel", "bsr_gauss_seidel", "jacobi", "bsr_jacobi", "gauss_seidel_indexed",
            "jacobi_ne", "gauss_seidel_ne", "gauss_seidel_nr", "block_jacobi", "block_gauss_seidel",
            "csr_matvec", "bsr_matvec", "overlapping_schwarz_csr", "extract_subblocks",
-           "incomplete_mat_mult_csr", "apply_distance_filter", "apply_absolute_distance_filter", "min_blocks"]
+           "incomplete_mat_mult_csr", "apply_distance_filter", "apply_absolute_distance_filter", "min_blocks",
+           "incomplete_mat_mult_bsr", "satisfy_constraints_helper", "calc_BtB"]
 
 _INDEX = np.dtype(np.intc)
 
@@ -152,6 +153,24 @@ def min_blocks(n_blocks, blocksize, Sx, Tx):
     """evolution_strength.h:213-237: Tx[i] = the smallest non-zero value of block i of Sx (DBL_MAX when it has
     none); float64"""
     _call("min_blocks", n_blocks, blocksize, Sx, Tx)
+
+
+def incomplete_mat_mult_bsr(Ap, Aj, Ax, Bp, Bj, Bx, Sp, Sj, Sx, n_brow, n_bcol, brow_A, bcol_A, bcol_B):
+    """smoothed_aggregation.h:797-869: Sx += A * B on the block pattern of S (BSR, rows in any order; of two slots of
+    one row with the same column the later receives everything); float64"""
+    _call("incomplete_mat_mult_bsr", Ap, Aj, Ax, Bp, Bj, Bx, Sp, Sj, Sx, n_brow, n_bcol, brow_A, bcol_A, bcol_B)
+
+
+def satisfy_constraints_helper(RowsPerBlock, ColsPerBlock, num_block_rows, NullDim, x, y, z, Sp, Sj, Sx):
+    """smoothed_aggregation.h:556-605: x = conj(B_c), y = U * B_c, z = BtBinv, all raveled; every block (i, j) of S
+    loses y_i * (z_i * x_j^T), in place; float64"""
+    _call("satisfy_constraints_helper", RowsPerBlock, ColsPerBlock, num_block_rows, NullDim, x, y, z, Sp, Sj, Sx)
+
+
+def calc_BtB(NullDim, Nnodes, ColsPerBlock, b, BsqCols, x, Sp, Sj):
+    """smoothed_aggregation.h:656-734: x[i] = B_i^T B_i over the columns of block row i of S, from the products b of
+    the candidates' columns; float64"""
+    _call("calc_BtB", NullDim, Nnodes, ColsPerBlock, b, BsqCols, x, Sp, Sj)
 
 
 def extract_subblocks(Ap, Aj, Ax, Tx, Tp, Sj, Sp, nsdomains, nrows):

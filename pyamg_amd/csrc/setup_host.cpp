@@ -1467,3 +1467,168 @@ void amgsetup_apply_distance_filter(int n_row, double epsilon, const int *Sp, co
 }
 
 }  // extern "C"
+
+// ---- energy-minimisation prolongation smoothing (pyamg/aggregation/smooth.py:283-457): the native steps of the host
+// route.  The first three are amg_core/smoothed_aggregation.h:797-869, :556-605 and :656-734 stated as they stand
+// there: every scalar of the output takes its products in the reference's traversal order (its gemm, linalg.h:360-449,
+// for the transpose flags of each call site), multiply and add rounded separately.  Block rows are independent, so
+// they are shared among threads without changing any scalar's order.  float64.
+extern "C" {
+
+// Sx += A * B on the block pattern of S; A: brow_A x bcol_A blocks, B: bcol_A x bcol_B, S: brow_A x bcol_B, rows in any
+// order.  One slot per block column, set by the row's slots in order: of two slots with one column the later receives
+// everything.
+void amgsetup_incomplete_mat_mult_bsr(const int *Ap, const int *Aj, const double *Ax, const int *Bp, const int *Bj,
+                                      const double *Bx, const int *Sp, const int *Sj, double *Sx, int n_brow, int n_bcol,
+                                      int brow_A, int bcol_A, int bcol_B)
+{
+    const long bsA = (long)brow_A * bcol_A, bsB = (long)bcol_A * bcol_B, bsS = (long)brow_A * bcol_B;
+#pragma omp parallel
+    {
+        std::vector<long> slot((size_t)std::max(n_bcol, 0), -1);
+#pragma omp for schedule(dynamic, 256)
+        for (int i = 0; i < n_brow; ++i) {
+            for (int jj = Sp[i]; jj < Sp[i + 1]; ++jj) slot[(size_t)Sj[jj]] = jj;
+            for (int jj = Ap[i]; jj < Ap[i + 1]; ++jj) {
+                const int j = Aj[jj];
+                const double *a = Ax + jj * bsA;
+                for (int kk = Bp[j]; kk < Bp[j + 1]; ++kk) {
+                    const long at = slot[(size_t)Bj[kk]];
+                    if (at < 0) continue;
+                    double *s = Sx + at * bsS;
+                    const double *b = Bx + kk * bsB;
+                    // gemm(A row major, B row major, S row major, accumulate): rows of A, then its columns, then B's columns
+                    for (int r = 0; r < brow_A; ++r)
+                        for (int m = 0; m < bcol_A; ++m)
+                            for (int c = 0; c < bcol_B; ++c) s[r * bcol_B + c] += a[r * bcol_A + m] * b[m * bcol_B + c];
+                }
+            }
+            for (int jj = Sp[i]; jj < Sp[i + 1]; ++jj) slot[(size_t)Sj[jj]] = -1;
+        }
+    }
+}
+
+// x = conj(B_c), y = U * B_c, z = BtBinv: every block of S loses y_i * (z_i * x_j^T)
+void amgsetup_satisfy_constraints_helper(int RowsPerBlock, int ColsPerBlock, int num_block_rows, int NullDim, const double *x,
+                                         const double *y, const double *z, const int *Sp, const int *Sj, double *Sx)
+{
+    const int R = RowsPerBlock, Cc = ColsPerBlock, ND = NullDim;
+#pragma omp parallel
+    {
+        std::vector<double> Cm((size_t)ND * Cc), update((size_t)R * Cc);
+#pragma omp for schedule(dynamic, 256)
+        for (int i = 0; i < num_block_rows; ++i) {
+            const double *binv = z + (long)i * ND * ND, *ub = y + (long)i * R * ND;
+            for (int j = Sp[i]; j < Sp[i + 1]; ++j) {
+                const double *bt = x + (long)Sj[j] * Cc * ND;
+                // Cm(d, c) = sum_k BtBinv_i(d, k) * B_c[column c of the block, k], kept column by column
+                for (int d = 0; d < ND; ++d)
+                    for (int c = 0; c < Cc; ++c) {
+                        double s = 0.0;
+                        for (int k = 0; k < ND; ++k) s += binv[d * ND + k] * bt[c * ND + k];
+                        Cm[(size_t)c * ND + d] = s;
+                    }
+                for (int r = 0; r < R; ++r)
+                    for (int c = 0; c < Cc; ++c) {
+                        double s = 0.0;
+                        for (int d = 0; d < ND; ++d) s += ub[r * ND + d] * Cm[(size_t)c * ND + d];
+                        update[(size_t)r * Cc + c] = s;
+                    }
+                double *s = Sx + (long)j * R * Cc;
+                for (int q = 0; q < R * Cc; ++q) s[q] -= update[(size_t)q];
+            }
+        }
+    }
+}
+
+// b = Bsq (BsqCols = NullDim (NullDim + 1) / 2 products per row of B_c); x[i] = B_i^T B_i over the scalar columns of
+// block row i of S in stored order
+void amgsetup_calc_BtB(int NullDim, int Nnodes, int ColsPerBlock, const double *b, int BsqCols, double *x, const int *Sp,
+                       const int *Sj)
+{
+    const int ND = NullDim;
+#pragma omp parallel
+    {
+        std::vector<double> loc((size_t)ND * ND);
+#pragma omp for schedule(dynamic, 256)
+        for (int i = 0; i < Nnodes; ++i) {
+            std::fill(loc.begin(), loc.end(), 0.0);
+            for (int j = Sp[i]; j < Sp[i + 1]; ++j) {
+                const long first = (long)Sj[j] * ColsPerBlock;
+                for (long k = first; k < first + ColsPerBlock; ++k) {
+                    const double *row = b + k * BsqCols;
+                    int at = 0;
+                    for (int m = 0; m < ND; ++m) {
+                        loc[(size_t)m * ND + m] += row[at];
+                        for (int n = m + 1; n < ND; ++n) {
+                            const double v = row[at + (n - m)];
+                            loc[(size_t)m * ND + n] += v;
+                            loc[(size_t)n * ND + m] += v;
+                        }
+                        at += ND - m;
+                    }
+                }
+            }
+            std::copy(loc.begin(), loc.end(), x + (long)i * ND * ND);
+        }
+    }
+}
+
+// UB = U * B for BSR U (R x Cc blocks) and dense row-major B with ND columns: per scalar row and candidate from 0.0,
+// blocks left to right, the columns of a block left to right
+void amgsetup_energy_block_row_product(int n_brow, int R, int Cc, int ND, const int *Sp, const int *Sj, const double *Ux,
+                                       const double *B, double *UB)
+{
+#pragma omp parallel for schedule(dynamic, 256)
+    for (int i = 0; i < n_brow; ++i)
+        for (int r = 0; r < R; ++r)
+            for (int d = 0; d < ND; ++d) {
+                double s = 0.0;
+                for (int jj = Sp[i]; jj < Sp[i + 1]; ++jj) {
+                    const double *u = Ux + ((long)jj * R + r) * Cc;
+                    const double *b = B + (long)Sj[jj] * Cc * ND + d;
+                    for (int c = 0; c < Cc; ++c) s += u[c] * b[(long)c * ND];
+                }
+                UB[((long)i * R + r) * ND + d] = s;
+            }
+}
+
+// out[0] = the Frobenius inner product <X, Y> of two value arrays on one pattern (bs scalars per block), out[1] = the
+// number of non-zero scalars of X.  A block row's products are added in stored order from 0.0; then 256 consecutive
+// values (0.0 past the end) are added by halving (v[t] += v[t + 128], ... v[0] += v[1]), level after level until one
+// value is left: the order depends on the number of block rows alone, never on the thread count.
+void amgsetup_energy_inner_product(int n_brow, int bs, const int *Sp, const double *X, const double *Y, double *out)
+{
+    const long chunks = ((long)std::max(n_brow, 1) + 255) / 256;
+    std::vector<double> v((size_t)chunks * 256, 0.0), w((size_t)chunks * 256, 0.0);
+#pragma omp parallel for schedule(static)
+    for (int i = 0; i < n_brow; ++i) {
+        double s = 0.0, nz = 0.0;
+        for (long q = (long)Sp[i] * bs; q < (long)Sp[i + 1] * bs; ++q) {
+            s += X[q] * Y[q];
+            if (X[q] != 0.0) nz += 1.0;
+        }
+        v[(size_t)i] = s;
+        w[(size_t)i] = nz;
+    }
+    long n = chunks * 256;
+    for (;;) {
+        const long groups = n / 256;
+#pragma omp parallel for schedule(static)
+        for (long g = 0; g < groups; ++g) {
+            double *a = v.data() + g * 256, *c = w.data() + g * 256;
+            for (int stride = 128; stride >= 1; stride /= 2)
+                for (int t = 0; t < stride; ++t) { a[t] += a[t + stride]; c[t] += c[t + stride]; }
+        }
+        if (groups == 1) break;
+        const long next = (groups + 255) / 256 * 256;
+        // group g's result sits at v[256 g] with g >= 1 ahead of slot g: moving them down in ascending order is safe
+        for (long g = 0; g < groups; ++g) { v[(size_t)g] = v[(size_t)g * 256]; w[(size_t)g] = w[(size_t)g * 256]; }
+        for (long g = groups; g < next; ++g) { v[(size_t)g] = 0.0; w[(size_t)g] = 0.0; }
+        n = next;
+    }
+    out[0] = v[0];
+    out[1] = w[0];
+}
+
+}  // extern "C"
