@@ -175,6 +175,11 @@ int amgcore_satisfy_constraints_helper_f64(int RowsPerBlock, int ColsPerBlock, i
                                            int Sp_size, const int Sj[], int Sj_size, double Sx[], int Sx_size);
 int amgcore_calc_BtB_f64(int NullDim, int Nnodes, int ColsPerBlock, const double b[], int b_size, int BsqCols, double x[], int x_size,
                          const int Sp[], int Sp_size, const int Sj[], int Sj_size);
+/* truncate_rows_csr (smoothed_aggregation.h:898-960), float64 only, in place: every row longer than k is permuted by the
+ * reference's quicksort on magnitudes (middle element to the left as pivot, strict <, column indices carried along) and
+ * its first len - k entries are set to 0.0, so that among equal magnitudes the reference's choice survives.  One lane
+ * per row, an explicit stack of at most 32 ranges, no per-row buffer: rows of any length. */
+int amgcore_truncate_rows_csr_f64(int n_row, int k, const int Sp[], int Sp_size, int Sj[], int Sj_size, double Sx[], int Sx_size);
 /* pyamg/util/linalg.py:17-53 norm(x) (2-norm) */
 int amgcore_norm2_f64(const double x[], long n, double *result);
 
@@ -631,6 +636,16 @@ int amg_energy_smooth_device(int n_brow, int n_bcol, int R, int Cc, int ND, cons
                              const int *Sp, const int *Sj, const double *Tx, const double *Bc, const double *BtBinv,
                              const double *Dinv, int maxiter, double tol, amg_energy **out, int *iterations, double *trace,
                              double *times_ms);
+/* The same iteration with the root-node rules (smooth.py:1129-1146 and :443-445).  root_row:
+ * n_bcol entries, the block row of column j's root node; the roots must be distinct and in range, R == Cc, and the
+ * pattern's row at each root must hold exactly one block, column j (AMG_EINVAL otherwise, before any launch).  Bf (or
+ * NULL: no initial fit): the fine candidates, n_brow * R rows of ND values; with it T <- T - (T B_c - B_f) BtBinv B_c^T
+ * runs on the pattern first.  The root blocks of T are set to the identity after the fit and after every
+ * T += alpha P; R, Z, P and AP are not masked.  Result handle and amg_energy_fetch as above. */
+int amg_energy_smooth_rootnode_device(int n_brow, int n_bcol, int R, int Cc, int ND, const int *Ap, const int *Aj, const double *Ax,
+                                      const int *Sp, const int *Sj, const double *Tx, const double *Bc, const double *BtBinv,
+                                      const double *Dinv, const int *root_row, const double *Bf, int maxiter, double tol,
+                                      amg_energy **out, int *iterations, double *trace, double *times_ms);
 int amg_energy_fetch(amg_energy *h, double *Tx);
 
 /* ------------------------------------------------------------------------ */

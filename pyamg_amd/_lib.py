@@ -74,10 +74,12 @@ FLAT_TABLE = {
     "incomplete_mat_mult_bsr": ("IIVIIVIIViiiii", True),
     "satisfy_constraints_helper": ("iiiiVVVIIV", True),
     "calc_BtB": ("iiiViVII", True),
+    "truncate_rows_csr": ("iiIIV", True),
 }
 # entries whose values are float64 only: another value dtype is the table's overload error
 FLAT_F64_ONLY = frozenset(["incomplete_mat_mult_csr", "apply_distance_filter", "apply_absolute_distance_filter",
-                           "min_blocks", "incomplete_mat_mult_bsr", "satisfy_constraints_helper", "calc_BtB"])
+                           "min_blocks", "incomplete_mat_mult_bsr", "satisfy_constraints_helper", "calc_BtB",
+                           "truncate_rows_csr"])
 # value dtype -> symbol suffix, and per suffix the C types of a value pointer and of the real scalar F
 VALUE_SUFFIX = {np.dtype(np.float64): "f64", np.dtype(np.float32): "f32",
                 np.dtype(np.complex64): "c64", np.dtype(np.complex128): "c128"}
@@ -188,6 +190,8 @@ def lib():
         "amg_evolution_strength_device": [I, V, V, V, V, D, D, I, I, V, C.POINTER(C.c_void_p), c_dbl_p],
         "amg_strength_fetch": [V, V, V],
         "amg_energy_smooth_device": [I, I, I, I, I, V, V, V, V, V, V, V, V, V, I, D, C.POINTER(C.c_void_p), c_int_p, V, c_dbl_p],
+        "amg_energy_smooth_rootnode_device": [I, I, I, I, I, V, V, V, V, V, V, V, V, V, V, V, I, D, C.POINTER(C.c_void_p), c_int_p, V,
+                                              c_dbl_p],
         "amg_energy_fetch": [V, V],
         "amg_hierx_create": [I, I, I, C.POINTER(C.c_void_p)],
         "amg_hierx_set_matrix": [V, I, I, I, I, I, I, I, V, V, V],

@@ -121,6 +121,8 @@ def host_lib():
         L.amgsetup_energy_block_row_product.restype = None
         L.amgsetup_energy_inner_product.argtypes = [C.c_int, C.c_int, ip, dp, dp, dp]
         L.amgsetup_energy_inner_product.restype = None
+        L.amgsetup_truncate_rows_csr.argtypes = [C.c_int, C.c_int, ip, ip, dp]
+        L.amgsetup_truncate_rows_csr.restype = None
         L.amgsetup_num_threads.restype = C.c_int
         L.amgsetup_set_num_threads.argtypes = [C.c_int]
         L.amgsetup_set_num_threads.restype = None

@@ -19,7 +19,7 @@ __all__ = ["gauss_seidel", "bsr_gauss_seidel", "jacobi", "bsr_jacobi", "gauss_se
            "jacobi_ne", "gauss_seidel_ne", "gauss_seidel_nr", "block_jacobi", "block_gauss_seidel",
            "csr_matvec", "bsr_matvec", "overlapping_schwarz_csr", "extract_subblocks",
            "incomplete_mat_mult_csr", "apply_distance_filter", "apply_absolute_distance_filter", "min_blocks",
-           "incomplete_mat_mult_bsr", "satisfy_constraints_helper", "calc_BtB"]
+           "incomplete_mat_mult_bsr", "satisfy_constraints_helper", "calc_BtB", "truncate_rows_csr"]
 
 _INDEX = np.dtype(np.intc)
 
@@ -171,6 +171,12 @@ def calc_BtB(NullDim, Nnodes, ColsPerBlock, b, BsqCols, x, Sp, Sj):
     """smoothed_aggregation.h:656-734: x[i] = B_i^T B_i over the columns of block row i of S, from the products b of
     the candidates' columns; float64"""
     _call("calc_BtB", NullDim, Nnodes, ColsPerBlock, b, BsqCols, x, Sp, Sj)
+
+
+def truncate_rows_csr(n_row, k, Sp, Sj, Sx):
+    """smoothed_aggregation.h:898-960: every row longer than k keeps its k entries of largest magnitude, chosen and
+    ordered as the reference's quicksort leaves them; the other entries become 0.0; Sj and Sx in place; float64"""
+    _call("truncate_rows_csr", n_row, k, Sp, Sj, Sx)
 
 
 def extract_subblocks(Ap, Aj, Ax, Tx, Tp, Sj, Sp, nsdomains, nrows):

@@ -9,6 +9,12 @@
 // Part 2: the whole CG iteration in HBM (amg_energy_smooth_device / amg_energy_fetch): R, Z, P, AP and T are value
 // arrays on ONE fixed block pattern with sorted, unique rows.  Per iteration two reads come back to the host:
 // (<R, Z>, the number of non-zero scalars of R) and <P, AP>.  DESIGN.md section 8f states the arithmetic.
+// Root-node smoothing (amg_energy_smooth_rootnode_device) is that iteration with two additions:
+// an initial fit T <- T - (T B_c - B_f) BtBinv B_c^T, and the single block of every root row set to the identity after
+// the fit and after every update of T.
+//
+// Part 3: the flat entry truncate_rows_csr (smoothed_aggregation.h:898-960): one lane per row runs the reference's
+// quicksort sequence on an explicit stack.
 #include "flat.hpp"
 
 #include <algorithm>
@@ -88,9 +94,11 @@ __global__ __launch_bounds__(TB) void imm_bsr_kernel(const int *Ap, const int *A
 }
 
 // UB = U * B for a BSR matrix U on the pattern and a dense row-major B (n_bcol * Cc rows, ND columns): lane = (scalar
-// row, candidate d); from 0.0, blocks left to right, the columns of a block left to right
+// row, candidate d); from 0.0, blocks left to right, the columns of a block left to right.  FIT: the finished sum loses
+// sub[t] in one subtraction (diff = T B_c - B_f of the initial fit).
+template <bool FIT>
 __global__ __launch_bounds__(TB) void block_row_product_kernel(const int *Sp, const int *Sj, const double *Ux, const double *B, double *UB,
-                                                                int R, int Cc, int ND, long n_out)
+                                                                const double *sub, int R, int Cc, int ND, long n_out)
 {
     const long t = (long)blockIdx.x * TB + threadIdx.x;
     if (t >= n_out) return;
@@ -103,7 +111,62 @@ __global__ __launch_bounds__(TB) void block_row_product_kernel(const int *Sp, co
         const double *b = B + (long)Sj[jj] * Cc * ND + d;
         for (int c = 0; c < Cc; ++c) sum += u[c] * b[(long)c * ND];
     }
-    UB[t] = sum;
+    UB[t] = FIT ? sum - sub[t] : sum;
+}
+
+// The single block of every root row becomes the identity (T = I_F * T + P_I on the fixed pattern): lane = one scalar
+// of the n_bcol root blocks, root_at[j] being the block of column j's root row.  Square blocks of R x R.
+__global__ __launch_bounds__(TB) void root_identity_kernel(const int *root_at, double *Tx, int R, long n)
+{
+    const long t = (long)blockIdx.x * TB + threadIdx.x;
+    if (t >= n) return;
+    const int bs = R * R;
+    const int j = (int)(t / bs), within = (int)(t % bs);
+    Tx[(long)root_at[j] * bs + within] = (within / R == within % R) ? 1.0 : 0.0;
+}
+
+// smoothed_aggregation.h:898-960.  Lane = row.  A row longer than k goes through the reference's quicksort on
+// magnitudes: the middle element is moved to the left as pivot, entries strictly smaller than it are collected behind
+// it, the pivot is put after them; the column indices move with the values.  The two parts are independent, so the
+// recursion is a stack of ranges: the larger part is pushed and the smaller one is taken next, which bounds the stack
+// by log2(len) + 1 <= 32 ranges for any row an int can index.  Then the first len - k entries become 0.0.
+__global__ __launch_bounds__(TB) void truncate_rows_kernel(int n_row, int k, const int *Sp, int *Sj, double *Sx)
+{
+    const long row = (long)blockIdx.x * TB + threadIdx.x;
+    if (row >= n_row) return;
+    const int rowstart = Sp[row], rowend = Sp[row + 1];
+    if (rowend - rowstart <= k) return;
+    int stack_lo[32], stack_hi[32], top = 0;
+    int left = rowstart, right = rowend - 1;
+    for (;;) {
+        while (left < right) {
+            const int mid = (int)(((long)left + right) / 2);
+            double tx = Sx[left]; Sx[left] = Sx[mid]; Sx[mid] = tx;
+            int tj = Sj[left]; Sj[left] = Sj[mid]; Sj[mid] = tj;
+            const double pivot = fabs(Sx[left]);
+            int last = left;
+            for (int i = left + 1; i <= right; ++i) {
+                if (fabs(Sx[i]) < pivot) {
+                    ++last;
+                    tx = Sx[last]; Sx[last] = Sx[i]; Sx[i] = tx;
+                    tj = Sj[last]; Sj[last] = Sj[i]; Sj[i] = tj;
+                }
+            }
+            tx = Sx[left]; Sx[left] = Sx[last]; Sx[last] = tx;
+            tj = Sj[left]; Sj[left] = Sj[last]; Sj[last] = tj;
+            if (last - left < right - last) {
+                if (top < 32) { stack_lo[top] = last + 1; stack_hi[top] = right; ++top; }
+                right = last - 1;
+            } else {
+                if (top < 32) { stack_lo[top] = left; stack_hi[top] = last - 1; ++top; }
+                left = last + 1;
+            }
+        }
+        if (top == 0) break;
+        --top;
+        left = stack_lo[top]; right = stack_hi[top];
+    }
+    for (int jj = rowstart; jj < rowend - k; ++jj) Sx[jj] = 0.0;
 }
 
 // smoothed_aggregation.h:556-605.  Lane = scalar (r, c) of block e in block row i:
@@ -299,6 +362,8 @@ struct Smoother {
     int n_brow, n_bcol, R, Cc, ND, n_block;
     long n_scalar;
     DArr Ap, Aj, Ax, Sp, Sj, Srow, Bc, BtBinv, Dinv, Rx, Zx, Px, APx, UB, part0, part1;
+    DArr RootAt, Bf;                // root-node smoothing: the root block of every column; the fine candidates of the fit
+    bool rooted = false, fit = false;
 
     // <X, Y> and the count of non-zero scalars of X to the host: one read of two doubles
     int inner_product(const double *X, const double *Y, double host[2])
@@ -324,13 +389,36 @@ struct Smoother {
     int project(double *Ux)
     {
         const long n_ub = (long)n_brow * R * ND;
-        hipLaunchKernelGGL(block_row_product_kernel, grid_for(n_ub), dim3(TB), 0, nullptr, (const int *)Sp.i(), (const int *)Sj.i(),
-                           (const double *)Ux, (const double *)Bc.d(), UB.d(), R, Cc, ND, n_ub);
+        hipLaunchKernelGGL(block_row_product_kernel<false>, grid_for(n_ub), dim3(TB), 0, nullptr, (const int *)Sp.i(), (const int *)Sj.i(),
+                           (const double *)Ux, (const double *)Bc.d(), UB.d(), (const double *)nullptr, R, Cc, ND, n_ub);
         LAUNCH_CHECK("energy smoothing: block-row product launch");
         hipLaunchKernelGGL(satisfy_constraints_kernel, grid_for(n_scalar), dim3(TB), 0, nullptr, R, Cc, n_brow, ND, (const double *)Bc.d(),
                            (const double *)UB.d(), (const double *)BtBinv.d(), (const int *)Sp.i(), (const int *)Sj.i(),
                            (const int *)Srow.i(), Ux, n_scalar);
         LAUNCH_CHECK("energy smoothing: constraint launch");
+        return 0;
+    }
+
+    // the single block of every root row of T becomes the identity
+    int root_identity(double *Tx)
+    {
+        const long n = (long)n_bcol * R * R;
+        hipLaunchKernelGGL(root_identity_kernel, grid_for(n), dim3(TB), 0, nullptr, (const int *)RootAt.i(), Tx, R, n);
+        LAUNCH_CHECK("energy smoothing: root identity launch");
+        return 0;
+    }
+
+    // the initial fit of smooth.py:1142-1146 on the pattern: diff = T B_c - B_f, T <- T - diff BtBinv B_c^T
+    int initial_fit(double *Tx)
+    {
+        const long n_ub = (long)n_brow * R * ND;
+        hipLaunchKernelGGL(block_row_product_kernel<true>, grid_for(n_ub), dim3(TB), 0, nullptr, (const int *)Sp.i(), (const int *)Sj.i(),
+                           (const double *)Tx, (const double *)Bc.d(), UB.d(), (const double *)Bf.d(), R, Cc, ND, n_ub);
+        LAUNCH_CHECK("energy smoothing: fit difference launch");
+        hipLaunchKernelGGL(satisfy_constraints_kernel, grid_for(n_scalar), dim3(TB), 0, nullptr, R, Cc, n_brow, ND, (const double *)Bc.d(),
+                           (const double *)UB.d(), (const double *)BtBinv.d(), (const int *)Sp.i(), (const int *)Sj.i(),
+                           (const int *)Srow.i(), Tx, n_scalar);
+        LAUNCH_CHECK("energy smoothing: fit constraint launch");
         return 0;
     }
 
@@ -348,6 +436,10 @@ struct Smoother {
     int run(double *Tx, int maxiter, double tol, int *iterations, double *trace)
     {
         const size_t bytes = sizeof(double) * (size_t)n_scalar;
+        if (fit) {
+            CHK(initial_fit(Tx));
+            if (rooted) CHK(root_identity(Tx));
+        }
         AMG_HIP(hipMemset(Rx.p, 0, bytes));
         CHK(product(Tx, Rx.d()));
         hipLaunchKernelGGL(negate_kernel, grid_for(n_scalar), dim3(TB), 0, nullptr, Rx.d(), n_scalar);
@@ -381,6 +473,8 @@ struct Smoother {
             if (trace) trace[2 * it + 1] = pap[0];
             const double alpha = newsum / pap[0];
             hipLaunchKernelGGL(axpy_kernel, grid_for(n_scalar), dim3(TB), 0, nullptr, alpha, (const double *)Px.d(), Tx, 0, n_scalar);
+            LAUNCH_CHECK("energy smoothing: update launch");
+            if (rooted) CHK(root_identity(Tx));     // R, Z, P and AP keep what the arithmetic leaves in the root rows
             hipLaunchKernelGGL(axpy_kernel, grid_for(n_scalar), dim3(TB), 0, nullptr, alpha, (const double *)APx.d(), Rx.d(), 1, n_scalar);
             LAUNCH_CHECK("energy smoothing: update launch");
             ++it;
@@ -507,9 +601,15 @@ int amgcore_calc_BtB_f64(int NullDim, int Nnodes, int ColsPerBlock, const double
 // non-zero.  *out then holds the smoothed values for amg_energy_fetch; *iterations the finished iterations; trace (or
 // null, else 2 * maxiter doubles): <R, Z> and <P, AP> of every started iteration; times_ms (or null): [0] upload,
 // [1] the iterations.
-int amg_energy_smooth_device(int n_brow, int n_bcol, int R, int Cc, int ND, const int *Ap, const int *Aj, const double *Ax, const int *Sp,
-                             const int *Sj, const double *Tx, const double *Bc, const double *BtBinv, const double *Dinv, int maxiter,
-                             double tol, amg_energy **out, int *iterations, double *trace, double *times_ms)
+// amg_energy_smooth_rootnode_device: the same with the root-node rules.  root_row: n_bcol entries, the block row of
+// column j's root node -- distinct, in range, and the pattern's row there holds exactly one block, column j (AMG_EINVAL
+// otherwise, before any launch); R == Cc.  Bf (or null: no initial fit): the fine candidates, n_brow * R rows of ND
+// values; with it T <- T - (T B_c - B_f) BtBinv B_c^T runs first.  The root blocks are set to the identity after the fit
+// and after every T += alpha P.
+static int energy_smooth(int n_brow, int n_bcol, int R, int Cc, int ND, const int *Ap, const int *Aj, const double *Ax, const int *Sp,
+                         const int *Sj, const double *Tx, const double *Bc, const double *BtBinv, const double *Dinv,
+                         const int *root_row, const double *Bf, int maxiter, double tol, amg_energy **out, int *iterations,
+                         double *trace, double *times_ms)
 {
     const std::string name = "energy smoothing";
     if (!out || n_brow < 1 || n_bcol < 1 || R < 1 || Cc < 1 || ND < 1 || maxiter < 0) { set_error(name + ": bad arguments"); return AMG_EINVAL; }
@@ -520,6 +620,26 @@ int amg_energy_smooth_device(int n_brow, int n_bcol, int R, int Cc, int ND, cons
     if (Sp[n_brow] == 0) { set_error(name + ": empty pattern"); return AMG_EINVAL; }
     if (!rows_sorted_unique(Sp, Sj, n_brow)) { set_error(name + ": the pattern's rows must hold sorted, unique columns"); return AMG_EINVAL; }
     if (!Ax || !Tx || !Bc || !BtBinv || !Dinv) { set_error(name + ": null array"); return AMG_EINVAL; }
+    std::vector<int> root_at;
+    if (root_row) {
+        if (R != Cc) { set_error(name + ": root-node smoothing needs square blocks (R == Cc)"); return AMG_EINVAL; }
+        std::vector<char> taken((size_t)n_brow, 0);
+        root_at.resize((size_t)n_bcol);
+        for (int j = 0; j < n_bcol; ++j) {
+            const int i = root_row[j];
+            if (i < 0 || i >= n_brow) { set_error(name + ": root row outside the matrix"); return AMG_EINVAL; }
+            if (taken[(size_t)i]) { set_error(name + ": two columns share a root row"); return AMG_EINVAL; }
+            taken[(size_t)i] = 1;
+            if (Sp[i + 1] - Sp[i] != 1 || Sj[Sp[i]] != j) {
+                set_error(name + ": the pattern's row at a root must hold exactly one block, the root's own column");
+                return AMG_EINVAL;
+            }
+            root_at[(size_t)j] = Sp[i];
+        }
+    } else if (Bf) {
+        set_error(name + ": an initial fit needs root rows");
+        return AMG_EINVAL;
+    }
     Smoother s;
     s.n_brow = n_brow; s.n_bcol = n_bcol; s.R = R; s.Cc = Cc; s.ND = ND; s.n_block = Sp[n_brow];
     s.n_scalar = (long)s.n_block * R * Cc;
@@ -537,6 +657,8 @@ int amg_energy_smooth_device(int n_brow, int n_bcol, int R, int Cc, int ND, cons
     CHK(s.Bc.upload(Bc, sizeof(double) * (size_t)n_bcol * Cc * ND));
     CHK(s.BtBinv.upload(BtBinv, sizeof(double) * (size_t)n_brow * ND * ND));
     CHK(s.Dinv.upload(Dinv, sizeof(double) * (size_t)n_brow * R));
+    if (root_row) { CHK(s.RootAt.upload(root_at.data(), sizeof(int) * (size_t)n_bcol)); s.rooted = true; }
+    if (Bf) { CHK(s.Bf.upload(Bf, sizeof(double) * (size_t)n_brow * R * ND)); s.fit = true; }
     amg_energy *h = new amg_energy;
     h->n_scalar = s.n_scalar;
     int rc = h->T.upload(Tx, vbytes);
@@ -556,6 +678,46 @@ int amg_energy_smooth_device(int n_brow, int n_bcol, int R, int Cc, int ND, cons
     if (rc != 0) { delete h; return rc; }
     *out = h;
     return 0;
+}
+
+int amg_energy_smooth_device(int n_brow, int n_bcol, int R, int Cc, int ND, const int *Ap, const int *Aj, const double *Ax, const int *Sp,
+                             const int *Sj, const double *Tx, const double *Bc, const double *BtBinv, const double *Dinv, int maxiter,
+                             double tol, amg_energy **out, int *iterations, double *trace, double *times_ms)
+{
+    return energy_smooth(n_brow, n_bcol, R, Cc, ND, Ap, Aj, Ax, Sp, Sj, Tx, Bc, BtBinv, Dinv, nullptr, nullptr, maxiter, tol, out,
+                         iterations, trace, times_ms);
+}
+
+int amg_energy_smooth_rootnode_device(int n_brow, int n_bcol, int R, int Cc, int ND, const int *Ap, const int *Aj, const double *Ax,
+                                      const int *Sp, const int *Sj, const double *Tx, const double *Bc, const double *BtBinv,
+                                      const double *Dinv, const int *root_row, const double *Bf, int maxiter, double tol,
+                                      amg_energy **out, int *iterations, double *trace, double *times_ms)
+{
+    if (!root_row) { set_error("energy smoothing: null root_row"); return AMG_EINVAL; }
+    return energy_smooth(n_brow, n_bcol, R, Cc, ND, Ap, Aj, Ax, Sp, Sj, Tx, Bc, BtBinv, Dinv, root_row, Bf, maxiter, tol, out, iterations,
+                         trace, times_ms);
+}
+
+// Sx, Sj: the CSR arrays of n_row rows; every row longer than k keeps its k entries of largest magnitude as the
+// reference's quicksort leaves them (entries permuted within the row, the others 0.0), in place
+int amgcore_truncate_rows_csr_f64(int n_row, int k, const int Sp[], int Sp_size, int Sj[], int Sj_size, double Sx[], int Sx_size)
+{
+    const std::string name = "truncate_rows_csr";
+    CHK(require_device());
+    if (n_row < 0 || k < 0) { set_error(name + ": bad sizes"); return AMG_EINVAL; }
+    CHK(check_offsets(name + ": S", Sp, Sp_size, n_row, std::min(Sj_size, Sx_size), -1, 0));
+    if (n_row == 0 || Sp[n_row] == 0) return 0;
+    if (!Sj || !Sx) { set_error(name + ": null array"); return AMG_EINVAL; }
+    const size_t nnz = (size_t)Sp[n_row];
+    DBuf dSp, dSj, dSx;
+    CHK(dSp.from_host(Sp, sizeof(int) * ((size_t)n_row + 1)));
+    CHK(dSj.from_host(Sj, sizeof(int) * nnz));
+    CHK(dSx.from_host(Sx, sizeof(double) * nnz));
+    hipLaunchKernelGGL(truncate_rows_kernel, grid_for(n_row), dim3(TB), 0, nullptr, n_row, k, (const int *)dSp.i(), dSj.i(), dSx.d());
+    LAUNCH_CHECK("truncate_rows_csr launch");
+    AMG_HIP(hipDeviceSynchronize());
+    CHK(dSj.to_host(Sj, sizeof(int) * nnz));
+    return dSx.to_host(Sx, sizeof(double) * nnz);
 }
 
 // the smoothed values on the pattern to the host; releases the result

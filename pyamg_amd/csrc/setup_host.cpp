@@ -1631,4 +1631,44 @@ void amgsetup_energy_inner_product(int n_brow, int bs, const int *Sp, const doub
     out[1] = w[0];
 }
 
+// smoothed_aggregation.h:898-960: every row longer than k is put through the reference's quicksort on magnitudes (the
+// middle element moved to the left as pivot, strict <, the column indices permuted with the values), then the first
+// len - k entries of the permuted row become 0.0.  Which of several equal magnitudes survives depends on this very
+// sequence of swaps.  The two parts left of and right of the pivot are independent: they are kept on an explicit stack,
+// the larger part pushed and the smaller part taken next, so the stack holds at most log2(len) + 1 ranges.
+void amgsetup_truncate_rows_csr(int n_row, int k, const int *Sp, int *Sj, double *Sx)
+{
+#pragma omp parallel for schedule(dynamic, 256)
+    for (int row = 0; row < n_row; ++row) {
+        const int rowstart = Sp[row], rowend = Sp[row + 1];
+        if (rowend - rowstart <= k) continue;
+        int stack_lo[40], stack_hi[40], top = 0;
+        int left = rowstart, right = rowend - 1;
+        for (;;) {
+            while (left < right) {
+                const int mid = (int)(((long)left + right) / 2);
+                std::swap(Sx[left], Sx[mid]); std::swap(Sj[left], Sj[mid]);
+                int last = left;
+                for (int i = left + 1; i <= right; ++i)
+                    if (std::fabs(Sx[i]) < std::fabs(Sx[left])) {
+                        ++last;
+                        std::swap(Sx[last], Sx[i]); std::swap(Sj[last], Sj[i]);
+                    }
+                std::swap(Sx[left], Sx[last]); std::swap(Sj[left], Sj[last]);
+                if (last - left < right - last) {           // the left part is the smaller one
+                    stack_lo[top] = last + 1; stack_hi[top] = right; ++top;
+                    right = last - 1;
+                } else {
+                    stack_lo[top] = left; stack_hi[top] = last - 1; ++top;
+                    left = last + 1;
+                }
+            }
+            if (top == 0) break;
+            --top;
+            left = stack_lo[top]; right = stack_hi[top];
+        }
+        for (int jj = rowstart; jj < rowend - (k < 0 ? 0 : k); ++jj) Sx[jj] = 0.0;
+    }
+}
+
 }  // extern "C"

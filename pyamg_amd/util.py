@@ -13,7 +13,8 @@ DEVICE_RHO_MIN_ROWS = 200000   # spectral-radius estimates of larger operators r
 DEVICE_GALERKIN_C128_MIN_ROWS = None
 
 __all__ = ["type_prep", "to_type", "get_diagonal", "get_block_diag", "scale_rows", "norm",
-           "approximate_spectral_radius", "upcast"]
+           "approximate_spectral_radius", "upcast", "get_Cpt_params", "scale_T", "filter_operator",
+           "filter_matrix_rows", "truncate_rows"]
 
 
 def upcast(*args):
@@ -446,3 +447,161 @@ def approximate_spectral_radius_device(A, dinv=None, tol=0.01, maxiter=15, resta
         print("[setup]   spectral radius (%d rows): operator in HBM %.2fs, random start %.2fs, %d Arnoldi pass(es) %.2fs"
               % (n, t1 - t0, t2 - t1, j + 1, time.perf_counter() - t2), flush=True)
     return float(np.abs(ev[max_index]))
+
+
+# --------------------------------------------------------------------------- root-node helpers
+def get_Cpt_params(A, Cnodes, AggOp, T):
+    """util/utils.py:1469-1614: the operators that separate root (C) from non-root (F) degrees of freedom.
+    Cnodes holds the root NODE of every aggregate; for a BSR operator every node expands to its blocksize dofs.
+    -> {'P_I': injection of the coarse dofs onto the root dofs (bsr, T's blocks, column j at row Cpts[j]),
+        'I_F', 'I_C': the identity restricted to F / C dofs (bsr, A's blocks), 'Cpts', 'Fpts': the dof lists}.
+    A coarse grid without root nodes (the single empty aggregate of standard_aggregation) gives an empty P_I."""
+    if not (isspmatrix_bsr(A) or isspmatrix_csr(A)):
+        raise TypeError("Expected BSR or CSR matrix A")
+    if not isspmatrix_csr(AggOp):
+        raise TypeError("Expected CSR matrix AggOp")
+    if not isspmatrix_bsr(T):
+        raise TypeError("Expected BSR matrix T")
+    if T.blocksize[0] != T.blocksize[1]:
+        raise TypeError("Expected square blocksize for BSR matrix T")
+    if A.shape[0] != A.shape[1]:
+        raise TypeError("Expected square matrix A")
+    if T.shape[0] != A.shape[0]:
+        raise TypeError("Expected compatible dimensions for T and A, T.shape[0] = A.shape[0]")
+    Cnodes = np.asarray(Cnodes)
+    if Cnodes.shape[0] != AggOp.shape[1] and AggOp.shape[1] > 1:
+        raise TypeError("Number of columns in AggOp must equal number of Cnodes")
+    bs = A.blocksize[0] if (isspmatrix_bsr(A) and A.blocksize[0] > 1) else 1
+    Cpts = np.array((bs * Cnodes.reshape(-1, 1) + np.arange(bs).reshape(1, -1)).ravel(), dtype=int)
+    if Cpts.shape[0] != T.shape[1] and T.shape[1] > bs:
+        raise ValueError("Expected number of Cpts to match T.shape[1]")
+    if bs != T.blocksize[0]:
+        raise ValueError("Expected identical blocksize in A and T")
+    if AggOp.shape[0] != T.shape[0] // bs:
+        raise ValueError("Number of rows in AggOp must equal number of fine-grid nodes")
+    n, ncoarse = A.shape[0], T.shape[1]
+    is_root = np.zeros(n, dtype=bool)
+    is_root[Cpts] = True
+
+    def restricted_identity(keep):
+        idx = np.nonzero(keep)[0].astype(np.int32)
+        ptr = np.concatenate(([0], np.cumsum(keep))).astype(np.int32)
+        return csr_matrix((np.ones(len(idx), dtype=np.float64), idx, ptr), shape=(n, n))
+    I_F, I_C = restricted_identity(~is_root), restricted_identity(is_root)
+    Fpts = I_F.indices.copy()
+    from scipy.sparse import csc_matrix
+    if I_C.nnz > 0:
+        P_I = csc_matrix((I_C.data.copy(), Cpts.copy(), np.arange(Cpts.shape[0] + 1)), shape=(n, ncoarse))
+    else:
+        P_I = csc_matrix((np.zeros(0), np.zeros(0, dtype=T.indices.dtype), np.zeros(ncoarse + 1, dtype=T.indptr.dtype)),
+                         shape=(n, ncoarse))
+    blocks = A.blocksize if isspmatrix_bsr(A) else (1, 1)
+    return {"P_I": P_I.tobsr(T.blocksize), "I_F": I_F.tobsr(blocks), "I_C": I_C.tobsr(blocks), "Cpts": Cpts, "Fpts": Fpts}
+
+
+def scale_T(T, P_I, I_F):
+    """util/utils.py:1366-1466: T times the block-diagonal D^+, D = P_I^T T being the block T holds at each root node, so
+    that the scaled T is the identity there; then the root rows are replaced by the injection: I_F (T D^+) + P_I."""
+    for M, name in ((T, "T"), (P_I, "P_I"), (I_F, "I_F")):
+        if not isspmatrix_bsr(M):
+            raise TypeError("Expected BSR matrix %s" % name)
+        if M.blocksize[0] != M.blocksize[1]:
+            raise TypeError("Expected BSR matrix %s with square blocks" % name)
+    if not (I_F.blocksize[0] == P_I.blocksize[0] == T.blocksize[0]):
+        raise TypeError("Expected identical blocksize in I_F, P_I and T")
+    if P_I.nnz == 0:                        # the trivial coarse grid: nothing to scale by
+        return T
+    from .smooth import pinv_array
+    D = P_I.T * T
+    if D.nnz > 0:
+        pinv_array(D.data)
+    return I_F * (T * D) + P_I
+
+
+def filter_operator(A, C, B, Bf, BtBinv=None):
+    """util/utils.py:1207-1363: A restricted to the pattern of C (entries of A outside it are dropped, entries of C that
+    A lacks start at 0.0), then corrected row by row so that the result times B is Bf:
+    A_i <- A_i - (A_i B - Bf_i) (B_i^T B_i)^+ B_i^T with B_i the rows of B the pattern of row i reaches.
+    A, C : both csr_matrix or both bsr_matrix with equal blocks, float64.  Returns A's format, sorted rows."""
+    from .aggregation import host_lib
+    from . import smooth
+    if A.shape != C.shape:
+        raise ValueError("A and C must be the same size")
+    if isspmatrix_bsr(C):
+        if not isspmatrix_bsr(A):
+            raise ValueError("A and C must either both be CSR or BSR")
+        if A.blocksize != C.blocksize:
+            raise ValueError("A and C must have same BSR blocksizes")
+        Ab, Cb = A, C
+    elif isspmatrix_csr(C):
+        if not isspmatrix_csr(A):
+            raise ValueError("A and C must either both be CSR or BSR")
+        Ab, Cb = A.tobsr(blocksize=(1, 1)), C.tobsr(blocksize=(1, 1))
+    else:
+        raise ValueError("A and C must either both be CSR or BSR")
+    B, Bf = np.asarray(B), np.asarray(Bf)
+    if Bf.ndim == 1:
+        Bf = Bf.reshape(-1, 1)
+    if B.ndim == 1:
+        B = B.reshape(-1, 1)
+    if Bf.shape[0] != A.shape[0]:
+        raise ValueError("A and Bf must have the same first dimension")
+    if B.shape[0] != A.shape[1]:
+        raise ValueError("A and B must have matching dimensions such that A*B is computable")
+    if B.shape[1] != Bf.shape[1]:
+        raise ValueError("B and Bf must have the same second dimension")
+    if not (Ab.dtype == B.dtype == Bf.dtype == np.float64):
+        raise TypeError("A, B and Bf must be float64")
+    R, Cc = Cb.blocksize
+    n_brow, n_bcol, ND = A.shape[0] // R, A.shape[1] // Cc, B.shape[1]
+    S = csr_matrix((np.ones(len(Cb.indices)), Cb.indices.copy(), Cb.indptr.copy()), shape=(n_brow, n_bcol))
+    S.sum_duplicates()
+    S.sort_indices()
+    Sp, Sj = smooth._ic(S.indptr), smooth._ic(S.indices)
+    Bd, Bfd = smooth._dc(B), smooth._dc(Bf)
+    if BtBinv is None:
+        BtBinv = smooth.compute_BtBinv(Bd, Sp, Sj, n_brow, Cc)
+    Ax, _ = smooth._scatter(Ab, Sp, Sj)
+    Ax = smooth.fit_on_pattern(host_lib(), n_brow, R, Cc, ND, Sp, Sj, Ax, Bd.ravel(), Bfd.ravel(), smooth._dc(BtBinv).ravel())
+    M = bsr_matrix((Ax.reshape(-1, R, Cc), Sj, Sp), shape=A.shape)
+    M.eliminate_zeros()
+    return M if isspmatrix_bsr(A) else M.tocsr()
+
+
+def filter_matrix_rows(A, theta):
+    """util/utils.py:2083-2150: every scalar row of A keeps the entries with |a_ij| >= theta * max_k |a_ik|.  It is the
+    classical strength loop (csrc/setup_host.cpp, ruge_stuben.h:46-99) on column indices shifted past the last row, so
+    that no entry counts as a diagonal.  Sparse input of any format; the result has that format (bsr: its blocks)."""
+    if not isspmatrix(A):
+        raise ValueError("Sparse matrix input needed")
+    if theta < 0 or theta >= 1.0:
+        raise ValueError("theta must be in [0,1)")
+    from .classical import _lib as classical_lib
+    from .aggregation import _dp, _ip
+    M = A.tocsr()
+    n = M.shape[0]
+    Ap = np.ascontiguousarray(M.indptr, dtype=np.intc)
+    Aj = np.ascontiguousarray(M.indices, dtype=np.intc) + np.intc(n)
+    Ax = np.ascontiguousarray(M.data, dtype=np.float64)
+    Sp, Sj, Sx = np.empty_like(Ap), np.empty_like(Aj), np.empty_like(Ax)
+    nnz = classical_lib().amgsetup_classical_strength(n, float(theta), _ip(Ap), _ip(Aj), _dp(Ax), _ip(Sp), _ip(Sj), _dp(Sx))
+    F = csr_matrix((Sx[:nnz], Sj[:nnz] - np.intc(n), Sp), shape=M.shape)
+    return F.tobsr(A.blocksize) if isspmatrix_bsr(A) else F.asformat(A.format)
+
+
+def truncate_rows(A, nz_per_row):
+    """util/utils.py:2153-2205: every scalar row of A keeps its nz_per_row entries of largest magnitude.  Which of
+    several equal magnitudes stay is decided by the reference's row quicksort, restated swap for swap in
+    csrc/setup_host.cpp (amgsetup_truncate_rows_csr), and by the stored order of the row.  A is not changed."""
+    if not isspmatrix(A):
+        raise ValueError("Sparse matrix input needed")
+    from .aggregation import _dp, _ip, host_lib
+    M = A.tocsr()
+    Sp = np.array(M.indptr, dtype=np.intc)          # copies: eliminate_zeros below rewrites all three arrays
+    Sj = np.array(M.indices, dtype=np.intc)
+    Sx = np.array(M.data, dtype=np.float64)
+    host_lib().amgsetup_truncate_rows_csr(M.shape[0], int(nz_per_row), _ip(Sp), _ip(Sj), _dp(Sx))
+    F = csr_matrix((Sx, Sj, Sp), shape=M.shape)
+    F.eliminate_zeros()
+    F.prune()
+    return F.tobsr(A.blocksize) if isspmatrix_bsr(A) else F.asformat(A.format)
