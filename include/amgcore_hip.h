@@ -331,7 +331,12 @@ int amg_hier_set_coarse_callback(amg_hier *h, amg_coarse_callback cb, void *user
  * amg_hier_apply_aux: the auxiliary operator of a smoother slot (amg_hier_set_aux_matrix: A by columns = A^T by rows) */
 int amg_hier_apply(amg_hier *h, int lvl, int which, const double *x_dev, double *y_dev);
 int amg_hier_apply_aux(amg_hier *h, int lvl, int which, int slot, const double *x_dev, double *y_dev);
-/* device scratch of the hierarchy for the reductions of amg_dev_dot_host / amg_dev_norm_host (>= 1040 doubles) */
+/* device scratch of the hierarchy for the amg_dev_* reductions: AMG_DEV_SCRATCH doubles -- AMG_DEV_PARTIALS partial sums
+ * of the first stage, then 8 result slots.  amg_dev_dot_host / amg_dev_norm_host put their result in
+ * scratch[AMG_DEV_HOST_SLOT]; the slots before it are the hierarchy's own (AMLI step lengths, the solve's norms). */
+#define AMG_DEV_PARTIALS  1024
+#define AMG_DEV_SCRATCH   (AMG_DEV_PARTIALS + 8)
+#define AMG_DEV_HOST_SLOT (AMG_DEV_PARTIALS + 6)
 double *amg_hier_scratch(amg_hier *h);
 /* allocate work vectors, build Gauss-Seidel level schedules */
 int amg_hier_finalize(amg_hier *h);
@@ -450,6 +455,8 @@ int amg_mat_gs_sweeps(amg_mat *m, double *x, const double *b, const unsigned cha
 int amg_dev_scale(double *out, const double *in, double c, long n, void *stream);
 int amg_dev_axpy(double *x, const double *h, long n, void *stream);
 int amg_dev_axpy_scaled(double *x, const double *r, double c, long n, void *stream);   /* x += c*r */
+/* result_dev[0] = ||x||_2 / <x, y> by the fixed-order two-stage reduction; scratch: AMG_DEV_PARTIALS doubles that the
+ * first stage overwrites; result_dev: any other device double (n == 0 gives 0.0) */
 int amg_dev_norm2(const double *x, long n, double *scratch, double *result_dev, void *stream);
 int amg_dev_dot(const double *x, const double *y, long n, double *scratch, double *result_dev, void *stream);
 int amg_dev_dense_apply(const double *Mt, const double *b, double *x, int n, void *stream);

@@ -160,7 +160,7 @@ int amg_dev_axpy(double *x, const double *h, long n, void *stream)
 { return launch_axpy_inplace(x, h, n, (hipStream_t)stream); }
 int amg_dev_axpy_scaled(double *x, const double *r, double c, long n, void *stream)
 { return launch_axpy_scaled(x, r, c, n, (hipStream_t)stream); }
-// result_dev[0] = ||x||_2 of the LOCAL part; scratch >= 1040 doubles
+// result_dev[0] = ||x||_2 of the LOCAL part; scratch: the AMG_DEV_PARTIALS partial sums of the first stage
 int amg_dev_norm2(const double *x, long n, double *scratch, double *result_dev, void *stream)
 { return launch_norm2(x, n, scratch, result_dev, (hipStream_t)stream); }
 int amg_dev_dot(const double *x, const double *y, long n, double *scratch, double *result_dev, void *stream)
@@ -196,18 +196,19 @@ int amg_dev_sub(double *out, const double *a, const double *b, long n, void *str
 { return launch_sub(out, a, b, n, (hipStream_t)stream); }
 int amg_dev_divide(double *w, double a, long n, void *stream)                          /* w /= a */
 { return launch_divide(w, a, n, (hipStream_t)stream); }
+static_assert(AMG_DEV_HOST_SLOT < AMG_DEV_SCRATCH, "the host result slot lies inside amg_hier_scratch's allocation");
 /* host scalar = <x, y> / ||x||_2 (deterministic two-stage reductions; one 8-byte read-back, stream synchronised) */
 int amg_dev_dot_host(const double *x, const double *y, long n, double *scratch, double *result, void *stream)
 {
-    CHK(launch_dot(x, y, n, scratch, scratch + 1030, (hipStream_t)stream));
-    AMG_HIP(hipMemcpyAsync(result, scratch + 1030, sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    CHK(launch_dot(x, y, n, scratch, scratch + AMG_DEV_HOST_SLOT, (hipStream_t)stream));
+    AMG_HIP(hipMemcpyAsync(result, scratch + AMG_DEV_HOST_SLOT, sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream));
     AMG_HIP(hipStreamSynchronize((hipStream_t)stream));
     return 0;
 }
 int amg_dev_norm_host(const double *x, long n, double *scratch, double *result, void *stream)
 {
-    CHK(launch_norm2(x, n, scratch, scratch + 1030, (hipStream_t)stream));
-    AMG_HIP(hipMemcpyAsync(result, scratch + 1030, sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    CHK(launch_norm2(x, n, scratch, scratch + AMG_DEV_HOST_SLOT, (hipStream_t)stream));
+    AMG_HIP(hipMemcpyAsync(result, scratch + AMG_DEV_HOST_SLOT, sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream));
     AMG_HIP(hipStreamSynchronize((hipStream_t)stream));
     return 0;
 }

@@ -2151,7 +2151,7 @@ double *amg_hier_scratch(amg_hier *h)
     if (!h) return nullptr;
     if (!h->norm_scratch) {
         hipSetDevice(h->device);
-        if (dev_alloc(&h->norm_scratch, 1024 + 8, &h->dev_bytes) != 0) return nullptr;
+        if (dev_alloc(&h->norm_scratch, AMG_DEV_SCRATCH, &h->dev_bytes) != 0) return nullptr;
     }
     return h->norm_scratch;
 }
@@ -2355,7 +2355,7 @@ int amg_hier_finalize(amg_hier *h)
         set_error("coarse dense operator has the wrong size");
         return AMG_EINVAL;
     }
-    if (!h->norm_scratch) CHK(dev_alloc(&h->norm_scratch, 1024 + 8, &h->dev_bytes));
+    if (!h->norm_scratch) CHK(dev_alloc(&h->norm_scratch, AMG_DEV_SCRATCH, &h->dev_bytes));
     if (h->comm) {
         if (h->reduce_channel < 0) { set_error("partitioned hierarchy without an all-reduce channel"); return AMG_ESTATE; }
         const char *env = getenv("AMG_DIST_OVERLAP");
@@ -2936,7 +2936,7 @@ int amg_arnoldi(amg_hier *h, int lvl, const double *dinv, const double *v0, int 
         h->dev_bytes += h->arn_bytes;                   // counted while it lives (amg_arnoldi_free gives it back)
         h->arn_m = maxiter; h->arn_n = n;
     }
-    if (!h->norm_scratch) CHK(dev_alloc(&h->norm_scratch, 1024 + 8, &h->dev_bytes));
+    if (!h->norm_scratch) CHK(dev_alloc(&h->norm_scratch, AMG_DEV_SCRATCH, &h->dev_bytes));
     double *V = h->arn_V;
     double *slot = h->norm_scratch + 1026;
     if (dinv) AMG_HIP(hipMemcpyAsync(h->arn_dinv, dinv, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));

@@ -185,7 +185,7 @@ struct amg_hier {
     int coarse_n = 0;
     amg::Smoother coarse_sm;
     // scratch
-    double *norm_scratch = nullptr;   // 1024 partials
+    double *norm_scratch = nullptr;   // AMG_DEV_SCRATCH doubles: 1024 partials, 8 result slots
     double *pcg[4] = {nullptr, nullptr, nullptr, nullptr};   // x, r, p, A*p of the device PCG (lazily)
     double *sumsq_partials = nullptr; // one partial per workgroup of the level-0 residual kernel
     long sumsq_cap = 0;

@@ -2767,7 +2767,7 @@ int launch_copy_strided(double *dst, const double *src, int start, int count, in
 // ---------------------------------------------------------------------------
 // 2-norm: deterministic two-stage tree reduction (fixed grid, fixed order)
 // ---------------------------------------------------------------------------
-constexpr int NORM_BLOCKS = 1024;
+constexpr int NORM_BLOCKS = 1024;      // AMG_DEV_PARTIALS of include/amgcore_hip.h: the scratch a caller provides
 
 __global__ __launch_bounds__(256) void sumsq_stage1(const double *x, long n, double *partial)
 {
