@@ -655,6 +655,24 @@ int amg_energy_smooth_rootnode_device(int n_brow, int n_bcol, int R, int Cc, int
                                       amg_energy **out, int *iterations, double *trace, double *times_ms);
 int amg_energy_fetch(amg_energy *h, double *Tx);
 
+/* The parallel C/F splittings of the classical setup (csrc/split.hip); graphs are CSR on the host
+ * with 32-bit offsets from 0 and columns inside the graph (AMG_EINVAL otherwise, before any launch).
+ *
+ * amg_mis_device: Luby's maximal independent set run to completion (amg_core/graph.h:90-156, max_iters == -1) on the
+ * graph as handed in.  x: one state per vertex; entries other than `active` keep their value, an active vertex next to
+ * a C entry becomes F, the others are decided by (y, index), the larger index winning a tie.  On a structurally
+ * symmetric graph the result equals the reference's sweeps.  *rounds (or NULL): rounds run.
+ *
+ * amg_cljp_device: the CLJP selection loop (amg_core/ruge_stuben.h:373-478) on the start weights weight0 (the random
+ * or colour weights plus the in-degree, computed on the host).  T = S^T.  splitting: 1 = C, 0 = F.  *passes (or
+ * NULL): passes run.
+ *
+ * times_ms (or NULL): milliseconds of the upload [0], of the rounds or passes [1] and of the download [2]. */
+int amg_mis_device(int n, const int *Ap, const int *Aj, const double *y, int active, int C, int F, int *x, int *rounds,
+                   double *times_ms);
+int amg_cljp_device(int n, const int *Sp, const int *Sj, const int *Tp, const int *Tj, const double *weight0, int *splitting,
+                    int *passes, double *times_ms);
+
 /* ------------------------------------------------------------------------ */
 /* 5. Resident hierarchies of other value types: the cycle of section 2      */
 /*    (multilevel.py:316-556) for a hierarchy whose A_l, P_l, R_l hold       */

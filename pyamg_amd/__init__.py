@@ -12,11 +12,12 @@ from .aggregation import smoothed_aggregation_solver
 from .rootnode import rootnode_solver
 from .blackbox import solve, solver, solver_configuration
 from . import strength
+from . import classical, graph
 
 # the package-level names of the reference (pyamg/__init__.py:61-65) that live on this path
 __all__ = ["multilevel_solver", "coarse_grid_solver", "change_smoothers", "ruge_stuben_solver",
            "smoothed_aggregation_solver", "rootnode_solver", "solve", "solver", "solver_configuration", "amg_core", "relaxation",
-           "smoothing", "util", "krylov_c128", "strength", "device_count"]
+           "smoothing", "util", "krylov_c128", "strength", "classical", "graph", "device_count"]
 
 
 def device_count():

@@ -193,6 +193,8 @@ def lib():
         "amg_energy_smooth_rootnode_device": [I, I, I, I, I, V, V, V, V, V, V, V, V, V, V, V, I, D, C.POINTER(C.c_void_p), c_int_p, V,
                                               c_dbl_p],
         "amg_energy_fetch": [V, V],
+        "amg_mis_device": [I, V, V, V, I, I, I, V, c_int_p, c_dbl_p],
+        "amg_cljp_device": [I, V, V, V, V, V, V, c_int_p, c_dbl_p],
         "amg_hierx_create": [I, I, I, C.POINTER(C.c_void_p)],
         "amg_hierx_set_matrix": [V, I, I, I, I, I, I, I, V, V, V],
         "amg_hierx_set_smoother": [V, I, I, C.POINTER(SmootherDescX)],

@@ -19,7 +19,8 @@ __all__ = ["gauss_seidel", "bsr_gauss_seidel", "jacobi", "bsr_jacobi", "gauss_se
            "jacobi_ne", "gauss_seidel_ne", "gauss_seidel_nr", "block_jacobi", "block_gauss_seidel",
            "csr_matvec", "bsr_matvec", "overlapping_schwarz_csr", "extract_subblocks",
            "incomplete_mat_mult_csr", "apply_distance_filter", "apply_absolute_distance_filter", "min_blocks",
-           "incomplete_mat_mult_bsr", "satisfy_constraints_helper", "calc_BtB", "truncate_rows_csr"]
+           "incomplete_mat_mult_bsr", "satisfy_constraints_helper", "calc_BtB", "truncate_rows_csr",
+           "maximal_independent_set_parallel", "cljp_naive_splitting"]
 
 _INDEX = np.dtype(np.intc)
 
@@ -191,3 +192,60 @@ def extract_subblocks(Ap, Aj, Ax, Tx, Tp, Sj, Sp, nsdomains, nrows):
     vptr = _lib.VALUE_CTYPES[suffix][0]
     fn(_lib.ip(Ap), _lib.ip(Aj), Ax.ctypes.data_as(vptr), Tx.ctypes.data_as(vptr), _lib.ip(Tp), _lib.ip(Sj),
        _lib.ip(Sp), int(nsdomains), int(nrows))
+
+
+def _graph_arrays(name, n, index_arrays, value_arrays=()):
+    """the typechecks of the two graph entries: int32 index arrays and float64 value arrays, 1-d, contiguous, long
+    enough for n vertices"""
+    for a in tuple(index_arrays) + tuple(value_arrays):
+        if not isinstance(a, np.ndarray):
+            raise TypeError("%s: numpy array expected" % name)
+        if a.ndim != 1:
+            raise ValueError("%s: array must have 1 dimension" % name)
+        if not a.flags.c_contiguous:
+            raise TypeError("%s: array must be contiguous" % name)
+    if any(a.dtype != _INDEX for a in index_arrays) or any(a.dtype != np.float64 for a in value_arrays):
+        raise NotImplementedError("Wrong number or type of arguments for overloaded function '%s' "
+                                  "(indices and states: int32; weights: float64)" % name)
+    if n < 0:
+        raise ValueError("%s: negative size" % name)
+
+
+def maximal_independent_set_parallel(num_rows, Ap, Aj, active, C, F, x, y, max_iters):
+    """graph.h:90-156 run to completion on the device (csrc/split.hip): the active entries of x (int32) become C or F
+    by Luby's rounds on the weights y (float64), the larger index winning a tie; the graph is taken as handed in and is
+    expected to be structurally symmetric.  Returns the number of vertices that became C.  Only max_iters == -1: a
+    limited number of in-place sweeps depends on the sweep order."""
+    import ctypes
+    n = "maximal_independent_set_parallel"
+    num_rows = int(num_rows)
+    _graph_arrays(n, num_rows, (Ap, Aj, x), (y,))
+    if int(max_iters) != -1:
+        raise NotImplementedError("%s: a sweep limit (max_iters=%d) is outside the restated setup" % (n, int(max_iters)))
+    if len(Ap) < num_rows + 1 or len(x) < num_rows or len(y) < num_rows or (num_rows and len(Aj) < Ap[num_rows]):
+        raise ValueError("%s: arrays shorter than the graph" % n)
+    before = int(np.count_nonzero(x[:num_rows] == C))
+    rounds = ctypes.c_int(0)
+    _lib.check(_lib.lib().amg_mis_device(num_rows, Ap.ctypes.data, Aj.ctypes.data, y.ctypes.data, int(active), int(C), int(F),
+                                         x.ctypes.data, ctypes.byref(rounds), None))
+    return int(np.count_nonzero(x[:num_rows] == C)) - before
+
+
+def cljp_naive_splitting(n, Sp, Sj, Tp, Tj, splitting, colorflag):
+    """ruge_stuben.h:316-480: the CLJP splitting (1 = C, 0 = F) of the strength graph S with transpose T into
+    splitting (int32), in place.  The start weights (glibc rand() after srand(2448422), or colour / ncolors for
+    colorflag == 1, plus the in-degree) are computed on the host, the selection loop runs on the device
+    (csrc/split.hip)."""
+    import ctypes
+    from .graph import _host
+    name = "cljp_naive_splitting"
+    n = int(n)
+    _graph_arrays(name, n, (Sp, Sj, Tp, Tj, splitting))
+    if len(Sp) < n + 1 or len(Tp) < n + 1 or len(splitting) < n or (n and (len(Sj) < Sp[n] or len(Tj) < Tp[n])):
+        raise ValueError("%s: arrays shorter than the graph" % name)
+    if n and (Sp[0] != 0 or np.any(np.diff(Sp[:n + 1]) < 0) or (Sp[n] and (Sj[:Sp[n]].min() < 0 or Sj[:Sp[n]].max() >= n))):
+        raise ValueError("%s: S is not a CSR graph of n vertices" % name)
+    weight = np.empty(n, dtype=np.float64)
+    _host().amgsetup_cljp_weights(n, _lib.ip(Sp), _lib.ip(Sj), int(colorflag), _lib.dp(weight))
+    _lib.check(_lib.lib().amg_cljp_device(n, Sp.ctypes.data, Sj.ctypes.data, Tp.ctypes.data, Tj.ctypes.data, weight.ctypes.data,
+                                          splitting.ctypes.data, None, None))

@@ -8,6 +8,7 @@
 #include <atomic>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <vector>
@@ -1255,6 +1256,198 @@ void amgsetup_rs_cf_splitting(int n, const int *Sp, const int *Sj, const int *Tp
             if (splitting[j] == UNDECIDED && wb.weight[j] > 0) wb.lower(j);
         }
     }
+}
+
+// ---- the parallel coarsenings (amg_core/graph.h:34-327, ruge_stuben.h:316-480), restated as sequential host loops.
+// x holds one state per vertex; only vertices equal to `active` are decided, as `C` (in the set) or `F` (next to it).
+
+// graph.h:34-61: greedy in index order.  Returns the number of vertices that joined the set.
+int amgsetup_mis_serial(int n, const int *Ap, const int *Aj, int active, int C, int F, int *x)
+{
+    int joined = 0;
+    for (int i = 0; i < n; ++i) {
+        if (x[i] != active) continue;
+        x[i] = C;
+        ++joined;
+        for (int jj = Ap[i]; jj < Ap[i + 1]; ++jj)
+            if (x[Aj[jj]] == active) x[Aj[jj]] = F;
+    }
+    return joined;
+}
+
+// graph.h:90-156: Luby's rounds as in-place sweeps.  An active vertex next to a C vertex becomes F; one that no active
+// neighbour beats ((y, index) compared, the larger index wins a tie) joins the set and retires its active neighbours.
+// max_iters == -1: until nothing is active.  Returns the number of vertices that joined.
+int amgsetup_mis_parallel(int n, const int *Ap, const int *Aj, int active, int C, int F, int *x, const double *y, int max_iters)
+{
+    int joined = 0;
+    bool any_active = true;
+    for (int sweep = 0; any_active && (max_iters == -1 || sweep < max_iters); ++sweep) {
+        any_active = false;
+        for (int i = 0; i < n; ++i) {
+            if (x[i] != active) continue;
+            const int lo = Ap[i], hi = Ap[i + 1];
+            bool beaten = false;                    // leaves the scan at the first neighbour that settles the question
+            for (int jj = lo; jj < hi && !beaten; ++jj) {
+                const int j = Aj[jj], xj = x[j];
+                if (xj == C) { x[i] = F; beaten = true; }
+                else if (xj == active && (y[j] > y[i] || (y[j] == y[i] && j > i))) beaten = true;
+            }
+            if (beaten) { any_active = true; continue; }
+            for (int jj = lo; jj < hi; ++jj)
+                if (x[Aj[jj]] == active) x[Aj[jj]] = F;
+            x[i] = C;
+            ++joined;
+        }
+    }
+    return joined;
+}
+
+// graph.h:171-188: colour K is a greedy independent set of what colours 0 .. K-1 left.  Returns the number of colours.
+int amgsetup_vertex_coloring_mis(int n, const int *Ap, const int *Aj, int *x)
+{
+    std::fill(x, x + n, -1);
+    int done = 0, K = 0;
+    while (done < n) {
+        done += amgsetup_mis_serial(n, Ap, Aj, -1 - K, K, -2 - K, x);
+        ++K;
+    }
+    return K;
+}
+
+// graph.h:200-218: every vertex of colour K takes the smallest colour none of its coloured neighbours has
+void amgsetup_vertex_coloring_first_fit(int n, const int *Ap, const int *Aj, int *x, int K)
+{
+    std::vector<char> used;
+    for (int i = 0; i < n; ++i) {
+        if (x[i] != K) continue;
+        used.assign((size_t)K, 0);
+        for (int jj = Ap[i]; jj < Ap[i + 1]; ++jj) {
+            const int j = Aj[jj];
+            if (j != i && x[j] >= 0 && x[j] < K) used[(size_t)x[j]] = 1;
+        }
+        int c = 0;
+        while (c < K && used[(size_t)c]) ++c;
+        x[i] = c;
+    }
+}
+
+namespace {
+// the step Jones-Plassmann and largest-degree-first share: ONE Luby sweep over the uncoloured vertices with colour K as
+// the set's mark, the retired vertices uncoloured again, first fit over the new colour
+int colour_one_sweep(int n, const int *Ap, const int *Aj, int *x, const double *w, int K)
+{
+    const int joined = amgsetup_mis_parallel(n, Ap, Aj, -1, K, -2, x, w, 1);
+    for (int i = 0; i < n; ++i)
+        if (x[i] == -2) x[i] = -1;
+    amgsetup_vertex_coloring_first_fit(n, Ap, Aj, x, K);
+    return joined;
+}
+}  // namespace
+
+// graph.h:242-269: z (random values on entry) gains every vertex's row length.  Returns the largest colour.
+int amgsetup_vertex_coloring_jones_plassmann(int n, const int *Ap, const int *Aj, int *x, double *z)
+{
+    std::fill(x, x + n, -1);
+    for (int i = 0; i < n; ++i) z[i] += Ap[i + 1] - Ap[i];
+    for (int done = 0, K = 0; done < n; ++K) done += colour_one_sweep(n, Ap, Aj, x, z, K);
+    return n > 0 ? *std::max_element(x, x + n) : -1;
+}
+
+// graph.h:290-327: the weight of an uncoloured vertex is y plus its number of uncoloured neighbours, counted anew
+// before every sweep.  Returns the largest colour.
+int amgsetup_vertex_coloring_LDF(int n, const int *Ap, const int *Aj, int *x, const double *y)
+{
+    std::fill(x, x + n, -1);
+    std::vector<double> w((size_t)n);
+    for (int done = 0, K = 0; done < n; ++K) {
+        for (int i = 0; i < n; ++i) {
+            if (x[i] != -1) continue;
+            int open = 0;
+            for (int jj = Ap[i]; jj < Ap[i + 1]; ++jj)
+                if (Aj[jj] != i && x[Aj[jj]] == -1) ++open;
+            w[(size_t)i] = y[i] + open;
+        }
+        done += colour_one_sweep(n, Ap, Aj, x, w.data(), K);
+    }
+    return n > 0 ? *std::max_element(x, x + n) : -1;
+}
+
+// ruge_stuben.h:343-371: the CLJP start weights.  colorflag 1: colour / ncolors of vertex_coloring_mis on S; else glibc
+// rand() / RAND_MAX after srand(2448422) (the process's C generator, as in the reference).  Then +1 per vertex that
+// depends on i, one addition at a time.
+void amgsetup_cljp_weights(int n, const int *Sp, const int *Sj, int colorflag, double *weight)
+{
+    if (colorflag == 1) {
+        std::vector<int> colour((size_t)n);
+        amgsetup_vertex_coloring_mis(n, Sp, Sj, colour.data());
+        const int ncolors = n > 0 ? *std::max_element(colour.begin(), colour.end()) + 1 : 1;
+        for (int i = 0; i < n; ++i) weight[i] = double(colour[(size_t)i]) / double(ncolors);
+    } else {
+        srand(2448422);
+        for (int i = 0; i < n; ++i) weight[i] = double(rand()) / RAND_MAX;
+    }
+    for (int i = 0; i < n; ++i)
+        for (int jj = Sp[i]; jj < Sp[i + 1]; ++jj)
+            if (Sj[jj] != i) weight[Sj[jj]]++;
+}
+
+// ruge_stuben.h:373-478: the CLJP selection loop on start weights (changed in place).  S: i depends on Sj[..] of row i;
+// T = S^T.  splitting: 1 = C, 0 = F.  Returns the number of passes.
+int amgsetup_cljp_select(int n, const int *Sp, const int *Sj, const int *Tp, const int *Tj, double *weight, int *splitting)
+{
+    const int F = 0, Cpt = 1, U = 2;
+    std::vector<char> live((size_t)(n > 0 ? Sp[n] : 0), 1);     // edges of S not yet removed
+    std::vector<int> picked, seen_from((size_t)n, -1);
+    std::fill(splitting, splitting + n, U);
+    int open = n, passes = 0;
+    auto undecided_beats = [&](int j, int i) { return splitting[j] == U && weight[j] > weight[i]; };
+    auto lose_edge = [&](int e, int k) {                         // edge e into k goes; k may drop out as F
+        live[(size_t)e] = 0;
+        weight[k]--;
+        if (weight[k] < 1) { splitting[k] = F; --open; }
+    };
+    while (open > 0) {
+        ++passes;
+        // the undecided vertices that no undecided neighbour (either direction) outweighs, all judged on one state
+        picked.clear();
+        for (int i = 0; i < n; ++i) {
+            if (splitting[i] != U) continue;
+            bool top = true;
+            for (int jj = Sp[i]; jj < Sp[i + 1] && top; ++jj) top = !undecided_beats(Sj[jj], i);
+            for (int jj = Tp[i]; jj < Tp[i + 1] && top; ++jj) top = !undecided_beats(Tj[jj], i);
+            if (top) picked.push_back(i);
+        }
+        for (int c : picked) splitting[c] = Cpt;
+        open -= (int)picked.size();
+        // P5: what a new C point depends on is worth less as a C point
+        for (int c : picked)
+            for (int jj = Sp[c]; jj < Sp[c + 1]; ++jj) {
+                const int j = Sj[jj];
+                if (splitting[j] == U && live[(size_t)jj]) lose_edge(jj, j);
+            }
+        // P6: j and k both depend on the new C point c and j depends on k: that dependence no longer counts for k
+        for (int c : picked) {
+            for (int jj = Tp[c]; jj < Tp[c + 1]; ++jj)
+                if (splitting[Tj[jj]] == U) seen_from[(size_t)Tj[jj]] = c;
+            for (int jj = Tp[c]; jj < Tp[c + 1]; ++jj) {
+                const int j = Tj[jj];
+                for (int kk = Sp[j]; kk < Sp[j + 1]; ++kk) {
+                    const int k = Sj[kk];
+                    if (splitting[k] == U && live[(size_t)kk] && seen_from[(size_t)k] == c) lose_edge(kk, k);
+                }
+            }
+        }
+    }
+    return passes;
+}
+
+// ruge_stuben.h:316-480 whole
+void amgsetup_cljp_naive_splitting(int n, const int *Sp, const int *Sj, const int *Tp, const int *Tj, int *splitting, int colorflag)
+{
+    std::vector<double> weight((size_t)n);
+    amgsetup_cljp_weights(n, Sp, Sj, colorflag, weight.data());
+    amgsetup_cljp_select(n, Sp, Sj, Tp, Tj, weight.data(), splitting);
 }
 
 // :497-600 direct interpolation.  pass 1: row pointer of P; pass 2: entries

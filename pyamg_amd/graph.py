@@ -1,0 +1,200 @@
+"""Graph algorithms of the classical setup (pyamg/graph.py of the reference): maximal independent sets and vertex
+colourings, by one of two routes that return the same integers:
+
+  host    the reference's sequential sweeps restated in csrc/setup_host.cpp (amg_core/graph.h:34-327);
+  device  Luby's rounds run to completion in HBM (csrc/split.hip, amg_mis_device).
+
+The device route takes what has ONE answer whatever the sweep order: Luby's algorithm without a
+sweep limit on a structurally symmetric graph, which also covers the greedy serial set (priority -i) and the 'MIS'
+colouring built from it.  The Jones-Plassmann and largest-degree-first colourings call ONE in-place sweep per colour,
+whose result depends on the order of the sweep: they stay on the host.
+
+The global numpy RNG is drawn exactly where the reference draws it: rand(N) for algo='parallel', for 'JP' and for 'LDF'.
+Outside the restated setup (NotImplementedError): the distance-k set (k=).
+"""
+import ctypes as C
+
+import numpy as np
+from scipy import sparse
+
+from .aggregation import _dp, _ip, host_lib
+
+__all__ = ["asgraph", "maximal_independent_set", "vertex_coloring"]
+
+# What device=None does when a GPU is present: the host route until the measurement in profiles/r16_splitting.txt says
+# otherwise.
+DEVICE_AUTO = False
+
+_sig_done = False
+
+
+def _outside(what):
+    return NotImplementedError("%s is outside the restated setup" % what)
+
+
+def _host():
+    global _sig_done
+    L = host_lib()
+    if not _sig_done:
+        I, ip, dp = C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)
+        L.amgsetup_mis_serial.argtypes = [I, ip, ip, I, I, I, ip]
+        L.amgsetup_mis_serial.restype = I
+        L.amgsetup_mis_parallel.argtypes = [I, ip, ip, I, I, I, ip, dp, I]
+        L.amgsetup_mis_parallel.restype = I
+        L.amgsetup_vertex_coloring_mis.argtypes = [I, ip, ip, ip]
+        L.amgsetup_vertex_coloring_mis.restype = I
+        L.amgsetup_vertex_coloring_first_fit.argtypes = [I, ip, ip, ip, I]
+        L.amgsetup_vertex_coloring_first_fit.restype = None
+        L.amgsetup_vertex_coloring_jones_plassmann.argtypes = [I, ip, ip, ip, dp]
+        L.amgsetup_vertex_coloring_jones_plassmann.restype = I
+        L.amgsetup_vertex_coloring_LDF.argtypes = [I, ip, ip, ip, dp]
+        L.amgsetup_vertex_coloring_LDF.restype = I
+        L.amgsetup_cljp_weights.argtypes = [I, ip, ip, I, dp]
+        L.amgsetup_cljp_weights.restype = None
+        L.amgsetup_cljp_select.argtypes = [I, ip, ip, ip, ip, dp, ip]
+        L.amgsetup_cljp_select.restype = I
+        L.amgsetup_cljp_naive_splitting.argtypes = [I, ip, ip, ip, ip, ip, I]
+        L.amgsetup_cljp_naive_splitting.restype = None
+        L.amgsetup_pattern_symmetric.argtypes = [I, ip, ip]
+        L.amgsetup_pattern_symmetric.restype = I
+        _sig_done = True
+    return L
+
+
+def _i32(a):
+    return np.ascontiguousarray(a, dtype=np.intc)
+
+
+def _f64(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _device_present():
+    from . import _lib
+    return _lib.device_count() > 0
+
+
+def _route(device, module_auto):
+    """True: the device entry, its refusals raised.  None: the device entry, its refusals answered by the host route.
+    False: the host route."""
+    if device is None:
+        return None if (module_auto and _device_present()) else False
+    return bool(device)
+
+
+def _pattern_symmetric(n, Ap, Aj):
+    return bool(_host().amgsetup_pattern_symmetric(n, _ip(Ap), _ip(Aj)))
+
+
+def _luby_device(n, Ap, Aj, active, Cval, Fval, x, y, max_iters=-1, times=None):
+    """amg_mis_device on a structurally symmetric graph (checked here, before anything is uploaded); x in place.
+    Returns (vertices that joined, rounds).  times: a list that receives (upload, rounds, fetch) in milliseconds."""
+    if max_iters != -1:
+        raise _outside("the device route of an independent set with a sweep limit")
+    if not _pattern_symmetric(n, Ap, Aj):
+        raise _outside("the device route of an independent set on a structurally unsymmetric graph")
+    from . import _lib
+    before = int(np.count_nonzero(x == Cval))
+    rounds = C.c_int(0)
+    ms = (C.c_double * 3)()
+    _lib.check(_lib.lib().amg_mis_device(n, Ap.ctypes.data, Aj.ctypes.data, y.ctypes.data, int(active), int(Cval), int(Fval),
+                                         x.ctypes.data, C.byref(rounds), ms))
+    if times is not None:
+        times.extend([ms[0], ms[1], ms[2]])
+    return int(np.count_nonzero(x == Cval)) - before, rounds.value
+
+
+def luby(n, Ap, Aj, active, Cval, Fval, x, y, max_iters=-1, device=None, auto=None, times=None):
+    """maximal_independent_set_parallel (graph.h:90-156) on int32 CSR arrays; x (int32) in place.  Returns the number of
+    vertices that joined the set."""
+    route = _route(device, DEVICE_AUTO if auto is None else auto)
+    if route is not False:
+        try:
+            return _luby_device(n, Ap, Aj, active, Cval, Fval, x, y, max_iters, times)[0]
+        except NotImplementedError:
+            if route is True:
+                raise
+    return _host().amgsetup_mis_parallel(n, _ip(Ap), _ip(Aj), int(active), int(Cval), int(Fval), _ip(x), _dp(y), int(max_iters))
+
+
+def asgraph(G):
+    """pyamg/graph.py:23-30"""
+    if not (sparse.isspmatrix_csr(G) or sparse.isspmatrix_csc(G)):
+        G = sparse.csr_matrix(G)
+    if G.shape[0] != G.shape[1]:
+        raise ValueError("expected square matrix")
+    return G
+
+
+def maximal_independent_set(G, algo="serial", k=None, device=None):
+    """Compute a maximal independent vertex set of a graph (pyamg/graph.py:33-81).
+
+    G : symmetric sparse matrix whose non-zeros are the edges; self loops are ignored.
+    algo : 'serial' (greedy in index order) or 'parallel' (Luby's algorithm on rand(N) weights).
+    device : True = the device route (symmetric graphs only), False = the host route, None = the host route unless
+    DEVICE_AUTO and a GPU.
+    Returns an int32 array: 1 for the vertices of the set, 0 for the others."""
+    G = asgraph(G)
+    N = G.shape[0]
+    if k is not None:
+        raise _outside("the distance-k independent set (k=%r)" % (k,))
+    if algo not in ("serial", "parallel"):
+        raise ValueError("unknown algorithm (%s)" % algo)
+    mis = np.full(N, -1, dtype=np.intc)
+    Ap, Aj = _i32(G.indptr), _i32(G.indices)
+    if algo == "parallel":
+        luby(N, Ap, Aj, -1, 1, 0, mis, _f64(np.random.rand(N)), -1, device)
+        return mis
+    route = _route(device, DEVICE_AUTO)
+    if route is not False:
+        # the greedy set in index order is Luby's set for the priorities -i
+        try:
+            _luby_device(N, Ap, Aj, -1, 1, 0, mis, -np.arange(N, dtype=np.float64))
+            return mis
+        except NotImplementedError:
+            if route is True:
+                raise
+            mis[:] = -1
+    _host().amgsetup_mis_serial(N, _ip(Ap), _ip(Aj), -1, 1, 0, _ip(mis))
+    return mis
+
+
+def vertex_coloring(G, method="MIS", device=None):
+    """Compute a vertex colouring of a graph (pyamg/graph.py:84-125).
+
+    method : 'MIS' (colour K is a greedy independent set of what is left), 'JP' (Jones-Plassmann) or 'LDF'
+    (largest degree first); the last two draw rand(N).
+    device : True = 'MIS' by the device route (one Luby run per colour; 'JP' and 'LDF' are refused), False = the host
+    route, None = the host route unless DEVICE_AUTO and a GPU.
+    Returns an int32 array of colours from 0 up."""
+    G = asgraph(G)
+    N = G.shape[0]
+    if method not in ("MIS", "JP", "LDF"):
+        raise ValueError("unknown method (%s)" % method)
+    if device is True and method != "MIS":
+        raise _outside("the device route of the %r colouring" % method)
+    coloring = np.empty(N, dtype=np.intc)
+    Ap, Aj = _i32(G.indptr), _i32(G.indices)
+    L = _host()
+    if method == "MIS":
+        route = _route(device, DEVICE_AUTO)
+        if route is not False:
+            try:
+                coloring[:] = -1
+                y = -np.arange(N, dtype=np.float64)
+                done, K = 0, 0
+                while done < N:
+                    done += _luby_device(N, Ap, Aj, -1 - K, K, -2 - K, coloring, y)[0]
+                    K += 1
+                return coloring
+            except NotImplementedError:
+                if route is True:
+                    raise
+        L.amgsetup_vertex_coloring_mis(N, _ip(Ap), _ip(Aj), _ip(coloring))
+    elif method == "JP":
+        z = _f64(np.random.rand(N))
+        L.amgsetup_vertex_coloring_jones_plassmann(N, _ip(Ap), _ip(Aj), _ip(coloring), _dp(z))
+    else:
+        y = _f64(np.random.rand(N))
+        L.amgsetup_vertex_coloring_LDF(N, _ip(Ap), _ip(Aj), _ip(coloring), _dp(y))
+    return coloring
