@@ -26,129 +26,15 @@ import numpy as np
 import scipy.sparse as sparse
 from scipy.sparse import bsr_matrix, csr_matrix, isspmatrix_bsr, isspmatrix_csr
 
-from ._lib import VALUE_CTYPES
+from ._host import dp as _dp, host_lib, ip as _ip, lp as _lp
 from .multilevel import multilevel_solver
+from .smooth import energy_prolongation_smoother
 from .smoothing import change_smoothers
 from .util import (approximate_spectral_radius, approximate_spectral_radius_device, get_diagonal,
                    release_device_operator, scale_rows, use_device_for)
 
 __all__ = ["smoothed_aggregation_solver", "standard_aggregation", "fit_candidates",
            "symmetric_strength_of_connection", "jacobi_prolongation_smoother", "energy_prolongation_smoother"]
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_host = None
-
-
-def host_lib():
-    global _host
-    if _host is None:
-        path = os.path.join(_HERE, "lib", "libamgsetup_host.so")
-        if not os.path.exists(path):
-            raise ImportError("%s missing: run `make -C pyamg_amd/csrc`" % path)
-        L = C.CDLL(path)
-        ip, lp, dp = C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double)
-        L.amgsetup_standard_aggregation.argtypes = [C.c_int, ip, ip, ip, ip]
-        L.amgsetup_standard_aggregation.restype = C.c_int
-        L.amgsetup_gauss_seidel.argtypes = [ip, ip, dp, dp, dp, C.c_int, C.c_int, C.c_int]
-        L.amgsetup_gauss_seidel.restype = None
-        L.amgsetup_block_gauss_seidel.argtypes = [ip, ip, dp, dp, dp, dp, C.c_int, C.c_int, C.c_int, C.c_int]
-        L.amgsetup_block_gauss_seidel.restype = None
-        L.amgsetup_gauss_seidel_c128.argtypes = [ip, ip, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
-        L.amgsetup_gauss_seidel_c128.restype = None
-        L.amgsetup_block_gauss_seidel_c128.argtypes = [ip, ip, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                       C.c_int, C.c_int, C.c_int, C.c_int]
-        L.amgsetup_block_gauss_seidel_c128.restype = None
-        L.amgsetup_pinv_blocks_c128.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.amgsetup_pinv_blocks_c128.restype = None
-        L.amgsetup_csr_diagonal_inv.argtypes = [C.c_int, lp, ip, dp, dp]
-        L.amgsetup_csr_diagonal_inv.restype = None
-        L.amgsetup_gauss_seidel_pipelined.argtypes = [ip, ip, dp, dp, dp, C.c_int, C.c_int, C.c_int]
-        L.amgsetup_gauss_seidel_pipelined.restype = C.c_int
-        L.amgsetup_block_gauss_seidel_pipelined.argtypes = [ip, ip, dp, dp, dp, dp, C.c_int, C.c_int, C.c_int, C.c_int]
-        L.amgsetup_block_gauss_seidel_pipelined.restype = C.c_int
-        L.amgsetup_csr_matmat_count.argtypes = [C.c_int, C.c_int, lp, ip, lp, ip, lp]
-        L.amgsetup_csr_matmat_count.restype = C.c_int64
-        L.amgsetup_csr_matmat_fill.argtypes = [C.c_int, C.c_int, lp, ip, dp, lp, ip, dp, lp, ip, dp]
-        L.amgsetup_csr_matmat_fill.restype = C.c_int64
-        L.amgsetup_csr_sort_indices.argtypes = [C.c_int, lp, ip, dp]
-        L.amgsetup_csr_sort_indices.restype = None
-        L.amgsetup_csr_transpose.argtypes = [C.c_int, C.c_int, lp, ip, dp, lp, ip, dp]
-        L.amgsetup_csr_transpose.restype = None
-        L.amgsetup_fit_candidates_scalar.argtypes = [C.c_int, ip, ip, dp, dp, dp, C.c_double]
-        L.amgsetup_fit_candidates_scalar.restype = None
-        L.amgsetup_poisson_nnz.argtypes = [C.c_int, C.c_int, C.c_int]
-        L.amgsetup_poisson_nnz.restype = C.c_int64
-        L.amgsetup_poisson.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, lp, ip, dp]
-        L.amgsetup_poisson.restype = None
-        L.amgsetup_tentative_scalar.argtypes = [C.c_int, C.c_int, ip, dp, C.c_double, lp, ip, dp, dp]
-        L.amgsetup_tentative_scalar.restype = C.c_int64
-        L.amgsetup_smooth_prolongator.argtypes = [C.c_int, C.c_int, lp, ip, dp, dp, C.c_double, lp, ip, dp,
-                                                  lp, ip, dp]
-        L.amgsetup_smooth_prolongator.restype = C.c_int64
-        L.amgsetup_bsr_matmat_count.argtypes = [C.c_int, lp, ip, lp, ip, lp]
-        L.amgsetup_bsr_matmat_count.restype = C.c_int64
-        L.amgsetup_bsr_matmat_fill.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, lp, ip, dp, lp, ip, dp, lp, ip, dp]
-        L.amgsetup_bsr_matmat_fill.restype = None
-        L.amgsetup_bsr_transpose.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, lp, ip, dp, lp, ip, dp]
-        L.amgsetup_bsr_transpose.restype = None
-        L.amgsetup_smooth_prolongator_block.argtypes = [C.c_int, C.c_int, C.c_int, lp, ip, dp, dp, C.c_double, ip, dp, lp, ip,
-                                                        dp, ip]
-        L.amgsetup_smooth_prolongator_block.restype = C.c_int64
-        L.amgsetup_kuhn_p1_diffusion.argtypes = [C.c_int, dp, dp, lp, ip, dp]
-        L.amgsetup_kuhn_p1_diffusion.restype = C.c_int64
-        L.amgsetup_greedy_coloring.argtypes = [C.c_int, ip, ip, ip]
-        L.amgsetup_greedy_coloring.restype = C.c_int
-        L.amgsetup_pattern_symmetric.argtypes = [C.c_int, ip, ip]
-        L.amgsetup_pattern_symmetric.restype = C.c_int
-        L.amgsetup_extract_subblocks.argtypes = [ip, ip, dp, dp, ip, ip, ip, C.c_int, C.c_int]
-        L.amgsetup_extract_subblocks.restype = None
-        for suffix in ("f32", "c64", "c128"):
-            f = getattr(L, "amgsetup_extract_subblocks_" + suffix)
-            vp = VALUE_CTYPES[suffix][0]
-            f.argtypes = [ip, ip, vp, vp, ip, ip, ip, C.c_int, C.c_int]
-            f.restype = None
-        L.amgsetup_incomplete_mat_mult_csr.argtypes = [ip, ip, dp, ip, ip, dp, ip, ip, dp, C.c_int]
-        L.amgsetup_incomplete_mat_mult_csr.restype = None
-        L.amgsetup_apply_distance_filter.argtypes = [C.c_int, C.c_double, ip, ip, dp, C.c_int]
-        L.amgsetup_apply_distance_filter.restype = None
-        L.amgsetup_incomplete_mat_mult_bsr.argtypes = [ip, ip, dp, ip, ip, dp, ip, ip, dp] + [C.c_int] * 5
-        L.amgsetup_incomplete_mat_mult_bsr.restype = None
-        L.amgsetup_satisfy_constraints_helper.argtypes = [C.c_int] * 4 + [dp, dp, dp, ip, ip, dp]
-        L.amgsetup_satisfy_constraints_helper.restype = None
-        L.amgsetup_calc_BtB.argtypes = [C.c_int, C.c_int, C.c_int, dp, C.c_int, dp, ip, ip]
-        L.amgsetup_calc_BtB.restype = None
-        L.amgsetup_energy_block_row_product.argtypes = [C.c_int] * 4 + [ip, ip, dp, dp, dp]
-        L.amgsetup_energy_block_row_product.restype = None
-        L.amgsetup_energy_inner_product.argtypes = [C.c_int, C.c_int, ip, dp, dp, dp]
-        L.amgsetup_energy_inner_product.restype = None
-        L.amgsetup_truncate_rows_csr.argtypes = [C.c_int, C.c_int, ip, ip, dp]
-        L.amgsetup_truncate_rows_csr.restype = None
-        L.amgsetup_num_threads.restype = C.c_int
-        L.amgsetup_set_num_threads.argtypes = [C.c_int]
-        L.amgsetup_set_num_threads.restype = None
-        # Row-parallel setup kernels keep O(columns) scratch per thread: cap the team at the CPUs this
-        # process may use (launchers such as torchrun export OMP_NUM_THREADS=1; a bare run on a big
-        # host would otherwise start hundreds of threads).  AMG_SETUP_THREADS overrides.
-        try:
-            avail = len(os.sched_getaffinity(0))
-        except AttributeError:
-            avail = os.cpu_count() or 1
-        want = int(os.environ.get("AMG_SETUP_THREADS", min(32, avail)))
-        L.amgsetup_set_num_threads(max(1, want))
-        _host = L
-    return _host
-
-
-def _ip(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int))
-
-
-def _lp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int64))
-
-
-def _dp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
 def greedy_colouring(A):
@@ -1112,7 +998,6 @@ def extend_hierarchy(levels, strength, aggregate, smooth, improve_candidates, ke
     if fn == "jacobi":
         P = jacobi_prolongation_smoother(A, T, Cm, B, **kwargs)
     elif fn == "energy":
-        from .smooth import energy_prolongation_smoother
         P = energy_prolongation_smoother(A, T, Cm, B, None, (False, {}), **kwargs)
     elif fn is None:
         P = T
@@ -1139,6 +1024,3 @@ def extend_hierarchy(levels, strength, aggregate, smooth, improve_candidates, ke
     A.symmetry = symmetry
     levels[-1].A = A
     levels[-1].B = B
-
-
-from .smooth import energy_prolongation_smoother  # noqa: E402  (smooth.py needs host_lib from this module)

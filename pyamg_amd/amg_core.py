@@ -182,7 +182,7 @@ def truncate_rows_csr(n_row, k, Sp, Sj, Sx):
 
 def extract_subblocks(Ap, Aj, Ax, Tx, Tp, Sj, Sp, nsdomains, nrows):
     """relaxation.h:836-899 (setup helper of the Schwarz smoother; runs on the host)"""
-    from .aggregation import host_lib
+    from ._host import host_lib
     n = "extract_subblocks"
     suffix = _check_arrays(n, "IIVVIII", (Ap, Aj, Ax, Tx, Tp, Sj, Sp))
     if len(Sp) < nsdomains + 1 or len(Tp) < nsdomains + 1 or (nsdomains and len(Tx) < Tp[nsdomains]):

@@ -24,7 +24,8 @@ import numpy as np
 from scipy.sparse import SparseEfficiencyWarning, csr_matrix, isspmatrix_csr
 
 from . import graph
-from .aggregation import _dp, _ip, host_lib, symmetric_strength_of_connection
+from ._host import dp as _dp, host_lib, i32 as _i32, ip as _ip, outside, route
+from .aggregation import symmetric_strength_of_connection
 from .graph import vertex_coloring
 from .multilevel import multilevel_solver
 from .smoothing import change_smoothers
@@ -36,29 +37,7 @@ __all__ = ["ruge_stuben_solver", "classical_strength_of_connection", "RS", "dire
 # otherwise.
 DEVICE_AUTO = False
 
-_sig_done = False
-
-
-def _lib():
-    global _sig_done
-    L = host_lib()
-    if not _sig_done:
-        ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
-        L.amgsetup_classical_strength.argtypes = [C.c_int, C.c_double, ip, ip, dp, ip, ip, dp]
-        L.amgsetup_classical_strength.restype = C.c_int
-        L.amgsetup_rs_cf_splitting.argtypes = [C.c_int, ip, ip, ip, ip, ip]
-        L.amgsetup_rs_cf_splitting.restype = None
-        L.amgsetup_rs_direct_interpolation_pass1.argtypes = [C.c_int, ip, ip, ip, ip]
-        L.amgsetup_rs_direct_interpolation_pass1.restype = C.c_int
-        L.amgsetup_rs_direct_interpolation_pass2.argtypes = [C.c_int, ip, ip, dp, ip, ip, dp, ip, ip, ip, dp]
-        L.amgsetup_rs_direct_interpolation_pass2.restype = None
-        _sig_done = True
-    return L
-
-
-def _i32(a):
-    return np.ascontiguousarray(a, dtype=np.intc)
-
+_lib = host_lib                 # the name tests/test_setup_golden.py imports
 
 def classical_strength_of_connection(A, theta=0.0):
     """pyamg/strength.py:111-210, amg_core/ruge_stuben.h:46-99"""
@@ -69,8 +48,8 @@ def classical_strength_of_connection(A, theta=0.0):
         raise ValueError("expected theta in [0,1]")
     Ap, Aj, Ax = _i32(A.indptr), _i32(A.indices), np.ascontiguousarray(A.data, dtype=np.float64)
     Sp = np.empty_like(Ap); Sj = np.empty_like(Aj); Sx = np.empty_like(Ax)
-    nnz = _lib().amgsetup_classical_strength(A.shape[0], float(theta), _ip(Ap), _ip(Aj), _dp(Ax), _ip(Sp), _ip(Sj),
-                                             _dp(Sx))
+    nnz = host_lib().amgsetup_classical_strength(A.shape[0], float(theta), _ip(Ap), _ip(Aj), _dp(Ax), _ip(Sp), _ip(Sj),
+                                                 _dp(Sx))
     S = csr_matrix((Sx[:nnz], Sj[:nnz], Sp), shape=A.shape)
     S.data = np.abs(S.data)
     # scale_rows_by_largest_entry
@@ -103,8 +82,8 @@ def RS(S):
     S = remove_diagonal(S)
     T = S.T.tocsr()
     splitting = np.empty(S.shape[0], dtype=np.intc)
-    _lib().amgsetup_rs_cf_splitting(S.shape[0], _ip(_i32(S.indptr)), _ip(_i32(S.indices)), _ip(_i32(T.indptr)),
-                                    _ip(_i32(T.indices)), _ip(splitting))
+    host_lib().amgsetup_rs_cf_splitting(S.shape[0], _ip(_i32(S.indptr)), _ip(_i32(S.indices)), _ip(_i32(T.indptr)),
+                                        _ip(_i32(T.indices)), _ip(splitting))
     return splitting
 
 
@@ -148,8 +127,8 @@ def CLJP(S, color=False, device=None):
     n = S.shape[0]
     splitting = np.empty(n, dtype=np.intc)
     Sp, Sj, Tp, Tj = _i32(S.indptr), _i32(S.indices), _i32(T.indptr), _i32(T.indices)
-    L = graph._host()
-    if graph._route(device, DEVICE_AUTO) is not False:
+    L = host_lib()
+    if route(device, DEVICE_AUTO) is not False:
         # the device loop takes every graph: nothing to fall back from
         weight = np.empty(n, dtype=np.float64)
         L.amgsetup_cljp_weights(n, _ip(Sp), _ip(Sj), colorid, _dp(weight))
@@ -174,7 +153,7 @@ def MIS(G, weights, maxiter=None, device=None):
     if maxiter is not None and maxiter < 0:
         raise ValueError("maxiter must be >= 0")
     if maxiter is not None and device is True:
-        raise graph._outside("the device route of an independent set with a sweep limit")
+        raise outside("the device route of an independent set with a sweep limit")
     G = remove_diagonal(G)
     mis = np.full(G.shape[0], -1, dtype=np.intc)
     weights = np.ascontiguousarray(weights, dtype=np.float64)
@@ -220,11 +199,11 @@ def direct_interpolation(A, Cm, splitting):
     Cp, Cj, Cx = _i32(Cm.indptr), _i32(Cm.indices), np.ascontiguousarray(Cm.data, dtype=np.float64)
     Ap, Aj, Ax = _i32(A.indptr), _i32(A.indices), np.ascontiguousarray(A.data, dtype=np.float64)
     Pp = np.empty(n + 1, dtype=np.intc)
-    nnz = _lib().amgsetup_rs_direct_interpolation_pass1(n, _ip(Cp), _ip(Cj), _ip(splitting), _ip(Pp))
+    nnz = host_lib().amgsetup_rs_direct_interpolation_pass1(n, _ip(Cp), _ip(Cj), _ip(splitting), _ip(Pp))
     Pj = np.empty(nnz, dtype=np.intc)
     Px = np.empty(nnz, dtype=np.float64)
-    _lib().amgsetup_rs_direct_interpolation_pass2(n, _ip(Ap), _ip(Aj), _dp(Ax), _ip(Cp), _ip(Cj), _dp(Cx),
-                                                  _ip(splitting), _ip(Pp), _ip(Pj), _dp(Px))
+    host_lib().amgsetup_rs_direct_interpolation_pass2(n, _ip(Ap), _ip(Aj), _dp(Ax), _ip(Cp), _ip(Cj), _dp(Cx),
+                                                      _ip(splitting), _ip(Pp), _ip(Pj), _dp(Px))
     return csr_matrix((Px, Pj, Pp))
 
 

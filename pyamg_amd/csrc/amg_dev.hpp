@@ -15,6 +15,12 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line);
         hipError_t e__ = (call);                                              \
         if (e__ != hipSuccess) return amg::hip_fail(e__, #call, __FILE__, __LINE__); \
     } while (0)
+// an internal call that returns one of the library's own status codes
+#define CHK(call)                   \
+    do {                            \
+        int rc__ = (call);          \
+        if (rc__ != 0) return rc__; \
+    } while (0)
 
 // ---------------------------------------------------------------- device CSR
 // Arrays are over-allocated by PAD entries so that 16-byte vector loads that

@@ -22,12 +22,6 @@ int gs_sweep_csr(const Schedule &S, bool bsr1, double *x, const double *b, bool 
 }
 using namespace amg;
 
-#define CHK(call)                   \
-    do {                            \
-        int rc__ = (call);          \
-        if (rc__ != 0) return rc__; \
-    } while (0)
-
 namespace {
 
 struct CsrHolder {

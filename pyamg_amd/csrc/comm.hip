@@ -1,6 +1,6 @@
 // Inter-GPU exchange of the row-partitioned hierarchy: see comm.hpp.
 #include "comm.hpp"
-#include "amg_dev.hpp"
+#include "driver.hpp"
 #include "../../include/amgcore_hip.h"
 
 #include <dlfcn.h>
@@ -9,12 +9,6 @@
 #include <cstring>
 
 namespace amg {
-
-#define CHK(call)                   \
-    do {                            \
-        int rc__ = (call);          \
-        if (rc__ != 0) return rc__; \
-    } while (0)
 
 // ------------------------------------------------------------------ peer transport kernels
 struct PeerPtrs {
@@ -211,13 +205,6 @@ static bool comm_fused()
     return f != 0;
 }
 
-static int launch_ok(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
-    return 0;
-}
-
 static unsigned partner_mask(const amg_comm *c, const Channel &C)
 {
     unsigned m = 0;
@@ -316,7 +303,7 @@ int comm_exchange_begin(amg_comm *c, int chn, const double *v, const int *send_i
     if (c->transport == 1) {
         if (C.send_total)
             hipLaunchKernelGGL(comm_pack_kernel, dim3(copy_grid(C.send_total)), dim3(256), 0, st, C.rccl_sendbuf, v, send_idx, C.send_total);
-        CHK(launch_ok("comm pack"));
+        CHK(launched("comm pack"));
         NCCL_CHK(g_nccl.GroupStart(), "ncclGroupStart");
         for (int p = 0; p < c->world; ++p) {
             const int ns = C.send_start[p + 1] - C.send_start[p], nr = C.recv_start[p + 1] - C.recv_start[p];
@@ -332,12 +319,12 @@ int comm_exchange_begin(amg_comm *c, int chn, const double *v, const int *send_i
     if (comm_fused()) {
         hipLaunchKernelGGL(comm_push_signal_kernel, dim3(copy_grid(C.send_total)), dim3(256), 0, st, P, v, send_idx, seq_send,
                            c->ticket + 2 * (size_t)chn);
-        return launch_ok("comm push+signal");
+        return launched("comm push+signal");
     }
     if (C.send_total)
         hipLaunchKernelGGL(comm_push_kernel, dim3(copy_grid(C.send_total)), dim3(256), 0, st, P, v, send_idx, seq_send);
     hipLaunchKernelGGL(comm_signal_kernel, dim3(1), dim3(64), 0, st, P, seq_send);
-    return launch_ok("comm push/signal");
+    return launched("comm push/signal");
 }
 
 int comm_exchange_end(amg_comm *c, int chn, double *dst_halo, hipStream_t st)
@@ -352,12 +339,12 @@ int comm_exchange_end(amg_comm *c, int chn, double *dst_halo, hipStream_t st)
         // (tests, rehearsals) the peer's push kernel needs compute units of its own to get there
         hipLaunchKernelGGL(comm_wait_unpack_kernel, dim3(std::min(copy_grid(C.recv_total), wait_grid_cap())), dim3(256), 0, st, P, dst_halo, seq_recv,
                            c->ticket + 2 * (size_t)chn + 1, c->timeout_flag, c->budget_ticks);
-        return launch_ok("comm wait+unpack");
+        return launched("comm wait+unpack");
     }
     hipLaunchKernelGGL(comm_wait_kernel, dim3(1), dim3(64), 0, st, P, seq_recv, c->timeout_flag, c->budget_ticks);
     if (C.recv_total)
         hipLaunchKernelGGL(comm_unpack_kernel, dim3(copy_grid(C.recv_total)), dim3(256), 0, st, P, dst_halo, seq_recv);
-    return launch_ok("comm wait/unpack");
+    return launched("comm wait/unpack");
 }
 
 int comm_allreduce_sqrt(amg_comm *c, int chn, const double *partial, double *result, hipStream_t st)
@@ -366,13 +353,13 @@ int comm_allreduce_sqrt(amg_comm *c, int chn, const double *partial, double *res
     if (c->transport == 1) {
         NCCL_CHK(g_nccl.AllReduce(partial, result, 1, NCCL_FLOAT64, NCCL_SUM, c->nccl_comm, st), "ncclAllReduce");
         hipLaunchKernelGGL(comm_sqrt_kernel, dim3(1), dim3(1), 0, st, result);
-        return launch_ok("comm sqrt");
+        return launched("comm sqrt");
     }
     PeerPtrs Pp = producer_ptrs(c, chn), Pc = consumer_ptrs(c, chn);
     hipLaunchKernelGGL(comm_reduce_push_kernel, dim3(1), dim3(64), 0, st, Pp, partial, c->seq + 2 * (size_t)chn);
     hipLaunchKernelGGL(comm_reduce_wait_kernel, dim3(1), dim3(64), 0, st, Pc, result, c->seq + 2 * (size_t)chn + 1, c->timeout_flag,
                        c->budget_ticks);
-    return launch_ok("comm all-reduce");
+    return launched("comm all-reduce");
 }
 
 int comm_check(amg_comm *c)

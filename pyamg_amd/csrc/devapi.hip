@@ -3,6 +3,7 @@
 // row-partitioned multi-GPU driver (pyamg_amd/distributed.py) is built from: its vectors are
 // torch tensors so that torch.distributed (RCCL) can move the halos.
 #include "hier.hpp"
+#include "driver.hpp"
 
 #include <cstdlib>
 #include <cstring>
@@ -17,12 +18,6 @@ void free_csr(DevCsr &M);
 int build_index16(DevCsr &M, const int *Ap_host, long *acct);
 }
 using namespace amg;
-
-#define CHK(call)                   \
-    do {                            \
-        int rc__ = (call);          \
-        if (rc__ != 0) return rc__; \
-    } while (0)
 
 struct amg_mat {
     int device = 0;
@@ -219,9 +214,7 @@ int amg_dev_gather(double *out, const double *in, const int *idx, long n, void *
     long nb = (n + 255) / 256;
     if (nb > 4096) nb = 4096;
     hipLaunchKernelGGL(gather_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, out, in, idx, n);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "gather", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("gather");
 }
 
 }  // extern "C"

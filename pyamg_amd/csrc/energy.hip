@@ -17,22 +17,11 @@
 // quicksort sequence on an explicit stack.
 #include "flat.hpp"
 
-#include <algorithm>
-#include <chrono>
 #include <string>
 
 using namespace amg;
 
 namespace {
-
-constexpr int TB = 256;
-inline dim3 grid_for(long work) { return dim3((unsigned)std::max<long>(1, (work + TB - 1) / TB)); }
-
-#define LAUNCH_CHECK(what)                                                            \
-    do {                                                                              \
-        hipError_t e__ = hipGetLastError();                                           \
-        if (e__ != hipSuccess) return hip_fail(e__, what, __FILE__, __LINE__);        \
-    } while (0)
 
 // block row of block e: the last row whose offset is <= e (empty rows are stepped over)
 __device__ __forceinline__ int row_of_block(const int *Sp, int n_row, int e)
@@ -321,38 +310,10 @@ __global__ __launch_bounds__(TB) void inner_product_level_kernel(const int *Sp, 
     }
 }
 
-struct DArr {                  // an array in HBM
-    void *p = nullptr;
-    DArr() = default;
-    DArr(const DArr &) = delete;
-    DArr &operator=(const DArr &) = delete;
-    ~DArr() { if (p) hipFree(p); }
-    int alloc(size_t bytes) { AMG_HIP(hipMalloc(&p, std::max<size_t>(bytes, 16))); return 0; }
-    int upload(const void *src, size_t bytes)
-    {
-        CHK(alloc(bytes));
-        if (bytes) AMG_HIP(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
-        return 0;
-    }
-    int zero(size_t bytes)
-    {
-        CHK(alloc(bytes));
-        AMG_HIP(hipMemset(p, 0, std::max<size_t>(bytes, 16)));
-        return 0;
-    }
-    double *d() const { return (double *)p; }
-    int *i() const { return (int *)p; }
-};
-
-double ms_since(std::chrono::steady_clock::time_point t0)
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 }   // namespace
 
 struct amg_energy {
-    DArr T;
+    DBuf T;
     long n_scalar = 0;
 };
 
@@ -361,8 +322,8 @@ namespace {
 struct Smoother {
     int n_brow, n_bcol, R, Cc, ND, n_block;
     long n_scalar;
-    DArr Ap, Aj, Ax, Sp, Sj, Srow, Bc, BtBinv, Dinv, Rx, Zx, Px, APx, UB, part0, part1;
-    DArr RootAt, Bf;                // root-node smoothing: the root block of every column; the fine candidates of the fit
+    DBuf Ap, Aj, Ax, Sp, Sj, Srow, Bc, BtBinv, Dinv, Rx, Zx, Px, APx, UB, part0, part1;
+    DBuf RootAt, Bf;                // root-node smoothing: the root block of every column; the fine candidates of the fit
     bool rooted = false, fit = false;
 
     // <X, Y> and the count of non-zero scalars of X to the host: one read of two doubles
@@ -645,23 +606,23 @@ static int energy_smooth(int n_brow, int n_bcol, int R, int Cc, int ND, const in
     s.n_scalar = (long)s.n_block * R * Cc;
     if (s.n_scalar >= 2147483647L || (long)Ap[n_brow] * R * R >= 2147483647L) { set_error(name + ": exceeds int32 indices"); return AMG_EINVAL; }
     CHK(require_device());
-    const auto t0 = std::chrono::steady_clock::now();
+    LapClock timer;
     std::vector<int> srow((size_t)s.n_block);
     for (int i = 0; i < n_brow; ++i)
         for (int e = Sp[i]; e < Sp[i + 1]; ++e) srow[(size_t)e] = i;
     const size_t np = sizeof(int) * ((size_t)n_brow + 1), vbytes = sizeof(double) * (size_t)s.n_scalar;
-    CHK(s.Ap.upload(Ap, np)); CHK(s.Aj.upload(Aj, sizeof(int) * (size_t)Ap[n_brow]));
-    CHK(s.Ax.upload(Ax, sizeof(double) * (size_t)Ap[n_brow] * R * R));
-    CHK(s.Sp.upload(Sp, np)); CHK(s.Sj.upload(Sj, sizeof(int) * (size_t)s.n_block));
-    CHK(s.Srow.upload(srow.data(), sizeof(int) * (size_t)s.n_block));
-    CHK(s.Bc.upload(Bc, sizeof(double) * (size_t)n_bcol * Cc * ND));
-    CHK(s.BtBinv.upload(BtBinv, sizeof(double) * (size_t)n_brow * ND * ND));
-    CHK(s.Dinv.upload(Dinv, sizeof(double) * (size_t)n_brow * R));
-    if (root_row) { CHK(s.RootAt.upload(root_at.data(), sizeof(int) * (size_t)n_bcol)); s.rooted = true; }
-    if (Bf) { CHK(s.Bf.upload(Bf, sizeof(double) * (size_t)n_brow * R * ND)); s.fit = true; }
+    CHK(s.Ap.from_host(Ap, np)); CHK(s.Aj.from_host(Aj, sizeof(int) * (size_t)Ap[n_brow]));
+    CHK(s.Ax.from_host(Ax, sizeof(double) * (size_t)Ap[n_brow] * R * R));
+    CHK(s.Sp.from_host(Sp, np)); CHK(s.Sj.from_host(Sj, sizeof(int) * (size_t)s.n_block));
+    CHK(s.Srow.from_host(srow.data(), sizeof(int) * (size_t)s.n_block));
+    CHK(s.Bc.from_host(Bc, sizeof(double) * (size_t)n_bcol * Cc * ND));
+    CHK(s.BtBinv.from_host(BtBinv, sizeof(double) * (size_t)n_brow * ND * ND));
+    CHK(s.Dinv.from_host(Dinv, sizeof(double) * (size_t)n_brow * R));
+    if (root_row) { CHK(s.RootAt.from_host(root_at.data(), sizeof(int) * (size_t)n_bcol)); s.rooted = true; }
+    if (Bf) { CHK(s.Bf.from_host(Bf, sizeof(double) * (size_t)n_brow * R * ND)); s.fit = true; }
     amg_energy *h = new amg_energy;
     h->n_scalar = s.n_scalar;
-    int rc = h->T.upload(Tx, vbytes);
+    int rc = h->T.from_host(Tx, vbytes);
     if (rc == 0) rc = s.Rx.alloc(vbytes);
     if (rc == 0) rc = s.Zx.alloc(vbytes);
     if (rc == 0) rc = s.Px.alloc(vbytes);
@@ -671,10 +632,9 @@ static int energy_smooth(int n_brow, int n_bcol, int R, int Cc, int ND, const in
     if (rc == 0) rc = s.part0.alloc(parts);
     if (rc == 0) rc = s.part1.alloc(parts);
     if (rc == 0 && hipDeviceSynchronize() != hipSuccess) { set_error(name + ": upload failed"); rc = AMG_ENODEV; }
-    const auto t1 = std::chrono::steady_clock::now();
-    if (times_ms) times_ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    const double upload_ms = timer.lap();
     if (rc == 0) rc = s.run(h->T.d(), maxiter, tol, iterations, trace);
-    if (times_ms) times_ms[1] = ms_since(t1);
+    if (times_ms) { times_ms[0] = upload_ms; times_ms[1] = timer.lap(); }
     if (rc != 0) { delete h; return rc; }
     *out = h;
     return 0;

@@ -1,47 +1,14 @@
 // Host-side helpers of the flat amg_core entries (include/amgcore_hip.h, section 1), shared by
-// capi.hip (float64) and typed.hip (float32 / complex64 / complex128): argument checks, the row list
-// of a sweep, and an owning device buffer.
+// capi.hip (float64) and typed.hip (float32 / complex64 / complex128): argument checks and the row
+// list of a sweep.  The owning device buffer they stage their operands in is driver.hpp's.
 #pragma once
-#include "amg_dev.hpp"
+#include "driver.hpp"
 #include "../../include/amgcore_hip.h"
 
 #include <vector>
 
-#ifndef CHK
-#define CHK(call)                   \
-    do {                            \
-        int rc__ = (call);          \
-        if (rc__ != 0) return rc__; \
-    } while (0)
-#endif
-
 namespace amg {
 namespace {
-
-// RAII device buffer
-struct DBuf {
-    void *p = nullptr;
-    ~DBuf() { if (p) hipFree(p); }
-    int alloc(size_t bytes)
-    {
-        hipError_t e = hipMalloc(&p, bytes + 128);
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc", __FILE__, __LINE__);
-        return 0;
-    }
-    int from_host(const void *src, size_t bytes)
-    {
-        CHK(alloc(bytes));
-        if (bytes) AMG_HIP(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
-        return 0;
-    }
-    int to_host(void *dst, size_t bytes) const
-    {
-        if (bytes) AMG_HIP(hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost));
-        return 0;
-    }
-    double *d() const { return (double *)p; }
-    int *i() const { return (int *)p; }
-};
 
 int require_device()
 {

@@ -30,6 +30,7 @@
 // spin is bounded by a wall-clock budget measured from the wave's start; a wave that runs out of it raises the
 // status flag and leaves, and so does everybody who waits for it (gs_flow_status()).
 #include "hier.hpp"
+#include "driver.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -773,9 +774,7 @@ int launch_flow(const FlowForm &F, bool bsr1, const FlowArgs &a, hipStream_t st)
     if (a.xcd >= 2 && nw >= 8L * a.xcd) nw -= nw % (8L * a.xcd);
     if (bsr1) hipLaunchKernelGGL((gs_flow_kernel<FLOW_SEG, LPR, true>), dim3((unsigned)nw), dim3(64), 0, st, F.meta, F.col, F.val, F.diag, F.bp, F.rowmap, F.gate_f, F.gate_b, a);
     else hipLaunchKernelGGL((gs_flow_kernel<FLOW_SEG, LPR, false>), dim3((unsigned)nw), dim3(64), 0, st, F.meta, F.col, F.val, F.diag, F.bp, F.rowmap, F.gate_f, F.gate_b, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "dataflow Gauss-Seidel launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("dataflow Gauss-Seidel launch");
 }
 
 template <int BS, int SEG, int LPR>
@@ -798,9 +797,7 @@ int launch_bflow(const BlockFlowForm &F, const BlockFlowArgs &a, hipStream_t st)
     nw = std::min<long>(nw, (long)a.nseq * F.nchunks);
     if (a.xcd >= 2 && nw >= 8L * a.xcd) nw -= nw % (8L * a.xcd);
     hipLaunchKernelGGL((bgs_flow_kernel<BS, SEG, LPR>), dim3((unsigned)nw), dim3(64), 0, st, F.meta, F.col, F.val, F.bp, F.rows, F.gate_f, F.gate_b, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "dataflow block Gauss-Seidel launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("dataflow block Gauss-Seidel launch");
 }
 
 template <int BS>
@@ -956,8 +953,7 @@ int block_flow_sweep(const BlockFlowForm &F, const double *Dinv, double *x, cons
         const long np = (long)(F.nb + 1) * F.bs;
         if (F.bs == 3) hipLaunchKernelGGL((bflow_gather_kernel<3>), dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, F.rows, x, b, (unsigned long long *)F.X, F.bp, F.xstride, F.nb, ns);
         else hipLaunchKernelGGL((bflow_gather_kernel<2>), dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, F.rows, x, b, (unsigned long long *)F.X, F.bp, F.xstride, F.nb, ns);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "dataflow block gather launch", __FILE__, __LINE__);
+        LAUNCH_CHECK("dataflow block gather launch");
         BlockFlowArgs a;
         std::memset(&a, 0, sizeof(a));
         a.X = (unsigned long long *)F.X; a.x_out = x; a.Dinv = Dinv; a.status = status;
@@ -1199,8 +1195,7 @@ int gs_flow_sweep(const FlowForm &F, bool bsr1, double *x, const double *b, cons
         const int ns = std::min(FLOW_MAXSEQ, nseq - s0);
         hipLaunchKernelGGL(flow_gather_kernel, dim3((unsigned)((F.ncols + 1 + 255) / 256)), dim3(256), 0, st, F.rowmap, x, b,
                            (unsigned long long *)F.X, F.bp, F.xstride, F.n, F.ncols, ns);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "dataflow gather launch", __FILE__, __LINE__);
+        LAUNCH_CHECK("dataflow gather launch");
         FlowArgs a;
         std::memset(&a, 0, sizeof(a));
         a.X = (unsigned long long *)F.X; a.x_out = x; a.status = status;

@@ -25,12 +25,6 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line)
     return (e == hipErrorOutOfMemory) ? AMG_ENOMEM : AMG_ENODEV;
 }
 
-#define CHK(call)                 \
-    do {                          \
-        int rc__ = (call);        \
-        if (rc__ != 0) return rc__; \
-    } while (0)
-
 // ------------------------------------------------------------------ memory
 template <class T> static int dev_alloc(T **p, long count, long *acct)
 {

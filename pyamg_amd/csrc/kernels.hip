@@ -14,7 +14,7 @@
 // storage order.  Short rows (7-pt stencil) and long rows (30-60 nnz on coarse
 // SA levels) go through the same path; a slice longer than the tile is
 // processed in several passes with the running sums kept in registers.
-#include "amg_dev.hpp"
+#include "driver.hpp"
 
 namespace amg {
 
@@ -921,9 +921,7 @@ int launch_gs_chain2(const int *lp, const double *val, const int *code, const in
     else { set_error("gs_chain2: unsupported slot count"); return -1; }
 #undef C2_WIDTH
 #undef C2_LAUNCH
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "gs chain2 launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("gs chain2 launch");
 }
 
 // level-order numbering of a scheduled sweep: xp[k] = x[rowmap[k]], bp[k] = b[rowmap[k]] before, x[rowmap[k]] = xp[k] after
@@ -948,17 +946,13 @@ int launch_perm_gather(const int *rowmap, const double *x, const double *b, cons
 {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(perm_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, st, rowmap, x, b, diag, xp, bp, (double2 *)bd, n);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "perm gather launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("perm gather launch");
 }
 int launch_perm_scatter(const int *rowmap, const double *xp, double *x, int n, hipStream_t st)
 {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(perm_scatter_kernel, dim3((n + 255) / 256), dim3(256), 0, st, rowmap, xp, x, n);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "perm scatter launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("perm scatter launch");
 }
 
 static int g_gs_chain = 2;       // 0: a launch per level, 1: chain with operands gathered back from L2, 2 (default): LDS hand-off chain (tools/gs_chain_ab.py)
@@ -987,9 +981,7 @@ int launch_gs_chain(const DevCsr &G, const int *rowmap, const int *diagpos, cons
 #undef C1_WIDTH
 #undef C1_LAUNCH
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "gs chain launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("gs chain launch");
 }
 
 // ---------------------------------------------------------------------------
@@ -1284,9 +1276,7 @@ int launch_gs_chain_long(const DevCsr &G, const int *rowmap, const int *diagpos,
 #undef CL_WIDTH
 #undef CL_LAUNCH
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "gs long-row chain launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("gs long-row chain launch");
 }
 
 // ---------------------------------------------------------------------------
@@ -1507,9 +1497,7 @@ static int launch_pattern_mode(const StreamArgs &a, const PatternArgs &P, int pe
         }
     }
     hipLaunchKernelGGL((csr_pattern_kernel<MODE>), dim3(grid), dim3(WG), 0, st, b, Q, g_xcd_chunk, rpb);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "csr_pattern launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("csr_pattern launch");
 }
 
 int launch_pattern(StreamMode mode, const StreamArgs &a, const DevCsr &M, hipStream_t st)
@@ -1985,9 +1973,7 @@ int launch_stencil_build(const DevCsr &M, const int *dict_slot, const unsigned *
     for (int r = 0; r < STENCIL_RANGES; ++r) { R.range[r][0] = M.st_range[r][0]; R.range[r][1] = M.st_range[r][1]; }
     hipLaunchKernelGGL(stencil_build_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, M.Ap, M.Ax, M.pat,
                        M.dict_ptr, dict_slot, pat_mask, M.st_nu, M.st_vals, M.st_mask, R);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "stencil build launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("stencil build launch");
 }
 
 // ---- value index (DevCsr::st_codes) ----
@@ -2040,17 +2026,13 @@ __global__ void value_encode_kernel(const double *vals, long count, const double
 int launch_value_scan(const double *vals, long count, unsigned long long *table, int *overflow, hipStream_t st)
 {
     hipLaunchKernelGGL(value_scan_kernel, dim3(8192), dim3(256), 0, st, vals, count, table, overflow);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "value scan launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("value scan launch");
 }
 int launch_value_encode(const double *vals, long count, const double *dict_sorted, int ndict, unsigned char *codes, int nu,
                         hipStream_t st, const unsigned char *mask8, long nrows)
 {
     hipLaunchKernelGGL(value_encode_kernel, dim3(8192), dim3(256), 0, st, vals, count, dict_sorted, ndict, codes, nu, mask8, nrows);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "value encode launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("value encode launch");
 }
 
 static int g_stencil_form = 1;
@@ -2128,8 +2110,7 @@ static int launch_stencil_mode(const StreamArgs &a, const DevCsr &M, hipStream_t
         hipLaunchKernelGGL((stencil_kernel<MODE, 16>), dim3(grid), dim3(WG), 0, st, b, E, g_xcd_chunk);
     else
         hipLaunchKernelGGL((stencil_kernel<MODE, 32>), dim3(grid), dim3(WG), 0, st, b, E, g_xcd_chunk);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "stencil launch", __FILE__, __LINE__);
+    LAUNCH_CHECK("stencil launch");
     // rows outside the stencil form
     const int rpb = pattern_rpb(a);
     int done = nb;
@@ -2288,9 +2269,7 @@ int launch_level0_chain(bool first_res, bool last_res, const Level0ChainArgs &a0
     if (first_res && last_res) hipLaunchKernelGGL((level0_chain_kernel<1, 1>), dim3(grid), dim3(L0C_WG), 0, st, a);
     else if (first_res) hipLaunchKernelGGL((level0_chain_kernel<1, 0>), dim3(grid), dim3(L0C_WG), 0, st, a);
     else hipLaunchKernelGGL((level0_chain_kernel<0, 1>), dim3(grid), dim3(L0C_WG), 0, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "level-0 chain launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("level-0 chain launch");
 }
 
 // the partial sums of SM_RESIDUAL_SUMSQ from a stored residual: same 256-row blocks, same additions in the same order as
@@ -2332,9 +2311,7 @@ int launch_sumsq_partials(const double *r, int n, double *out2, hipStream_t st)
     const int nb = (n + WG - 1) / WG;
     const int per_wg = SSQ_BLOCKS * (WG / 64);
     hipLaunchKernelGGL(sumsq_partials_kernel, dim3((nb + per_wg - 1) / per_wg), dim3(WG), 0, st, r, n, nb, out2);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "sumsq partials launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("sumsq partials launch");
 }
 
 // eligibility of the fused chains: every stored coupling of the coded 7-point rows stays inside the (nz, ny, nx) box
@@ -2358,9 +2335,7 @@ int launch_level0_box_scan(const unsigned char *codes, int nx, int ny, int nz, i
 {
     hipLaunchKernelGGL(level0_box_scan_kernel, dim3(4096), dim3(256), 0, st, reinterpret_cast<const unsigned long long *>(codes),
                        nx, ny, nz, bad);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "level-0 box scan launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("level-0 box scan launch");
 }
 
 // plane flags of the fused chains (DevCsr::l0_same): same[z] = 1 iff every column's code word on plane z is the one on
@@ -2381,9 +2356,7 @@ int launch_level0_plane_scan(const unsigned char *codes, long plane, int nz, uns
 {
     hipLaunchKernelGGL(level0_plane_scan_kernel, dim3(nz), dim3(1024), 0, st, reinterpret_cast<const unsigned long long *>(codes),
                        plane, same);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "level-0 plane scan launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("level-0 plane scan launch");
 }
 
 // 16-bit column codes (DevCsr::Aj16): one workgroup per row block of the stream kernel
@@ -2433,9 +2406,7 @@ int launch_index16_build(DevCsr &M, int rpb, hipStream_t st)
     if (nwg <= 0) return 0;
     hipLaunchKernelGGL(index16_build_kernel, dim3(nwg), dim3(WG), 0, st, M.nrows, rpb, M.Ap, M.Aj, M.Aj16, M.wg_base,
                        M.wg_flag);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "index16 build launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("index16 build launch");
 }
 
 template <int MODE>
@@ -2468,18 +2439,14 @@ static int launch_stream_mode(const StreamArgs &a, hipStream_t st)
             G -= G % 8;
             if (G > nb) G = nb;
             hipLaunchKernelGGL((csr_stream_pipe_kernel<MODE>), dim3(G), dim3(WG), 0, st, b, g_xcd_chunk, rpb, nb);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return hip_fail(e, "csr_stream_pipe launch", __FILE__, __LINE__);
-            return 0;
+            LAUNCH_RETURN("csr_stream_pipe launch");
         }
     }
     if (g_stream_variant)
         hipLaunchKernelGGL((csr_stream_kernel<MODE, 1>), dim3(nb), dim3(WG), 0, st, b, g_xcd_chunk, rpb);
     else
         hipLaunchKernelGGL((csr_stream_kernel<MODE, 0>), dim3(nb), dim3(WG), 0, st, b, g_xcd_chunk, rpb);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "csr_stream launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("csr_stream launch");
 }
 
 // ---------------------------------------------------------------------------
@@ -2588,9 +2555,7 @@ int launch_gs_level(const StreamArgs &a, bool bsr1, const int *gp_host, hipStrea
     for (int g = nb + 1; g <= GS_LEVEL_MAXWG; ++g) H.e[g] = H.e[nb];
     if (bsr1) hipLaunchKernelGGL((gs_level_kernel<true>), dim3(nb), dim3(WG), 0, st, a, H, rpb);
     else hipLaunchKernelGGL((gs_level_kernel<false>), dim3(nb), dim3(WG), 0, st, a, H, rpb);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "gs level launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("gs level launch");
 }
 
 int stream_blocks(const StreamArgs &a)
@@ -2651,9 +2616,7 @@ int launch_jacobi_rows(const DevCsr &A, const double *temp, const double *b, dou
     if (count <= 0) return 0;
     hipLaunchKernelGGL(jacobi_rows_kernel, dim3((count + 255) / 256), dim3(256), 0, st, A.Ap, A.Aj,
                        A.Ax, temp, b, x, row_start, count, row_step, omega);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "jacobi_rows launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("jacobi_rows launch");
 }
 
 // ---------------------------------------------------------------------------
@@ -2705,24 +2668,17 @@ __global__ void copy_strided_kernel(double *dst, const double *src, int start, i
     }
 }
 
-#define LAUNCH_CHECK(name)                                                      \
-    do {                                                                        \
-        hipError_t e__ = hipGetLastError();                                     \
-        if (e__ != hipSuccess) return hip_fail(e__, name, __FILE__, __LINE__);  \
-        return 0;                                                               \
-    } while (0)
-
 int launch_scale(double *out, const double *in, double c, long n, hipStream_t st)
 {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(scale_kernel, dim3(vec_grid(n)), dim3(256), 0, st, out, in, c, n);
-    LAUNCH_CHECK("scale");
+    LAUNCH_RETURN("scale");
 }
 int launch_fill(double *out, double v, long n, hipStream_t st)
 {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(fill_kernel, dim3(vec_grid(n)), dim3(256), 0, st, out, v, n);
-    LAUNCH_CHECK("fill");
+    LAUNCH_RETURN("fill");
 }
 __global__ void scale_add_kernel(double *p, double beta, const double *z, long n)
 {
@@ -2736,32 +2692,32 @@ int launch_scale_add(double *p, double beta, const double *z, long n, hipStream_
 {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(scale_add_kernel, dim3(vec_grid(n)), dim3(256), 0, st, p, beta, z, n);
-    LAUNCH_CHECK("scale_add");
+    LAUNCH_RETURN("scale_add");
 }
 int launch_sor_combine(double *x, const double *xold, double omega, long n, hipStream_t st)
 {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(sor_combine_kernel, dim3(vec_grid(n)), dim3(256), 0, st, x, xold, omega, n);
-    LAUNCH_CHECK("sor_combine");
+    LAUNCH_RETURN("sor_combine");
 }
 int launch_axpy_inplace(double *x, const double *h, long n, hipStream_t st)
 {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(axpy_inplace_kernel, dim3(vec_grid(n)), dim3(256), 0, st, x, h, n);
-    LAUNCH_CHECK("axpy_inplace");
+    LAUNCH_RETURN("axpy_inplace");
 }
 int launch_sub(double *out, const double *a, const double *b, long n, hipStream_t st)
 {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(sub_kernel, dim3(vec_grid(n)), dim3(256), 0, st, out, a, b, n);
-    LAUNCH_CHECK("sub");
+    LAUNCH_RETURN("sub");
 }
 int launch_copy_strided(double *dst, const double *src, int start, int count, int step, hipStream_t st)
 {
     if (count <= 0) return 0;
     hipLaunchKernelGGL(copy_strided_kernel, dim3((count + 255) / 256), dim3(256), 0, st, dst, src,
                        start, count, step);
-    LAUNCH_CHECK("copy_strided");
+    LAUNCH_RETURN("copy_strided");
 }
 
 // ---------------------------------------------------------------------------
@@ -2820,7 +2776,7 @@ int launch_sum_sqrt(const double *partial, long np, double *scratch512, double *
     } else {
         hipLaunchKernelGGL(sum_sqrt_kernel, dim3(1), dim3(256), 0, st, partial, np, result_dev);
     }
-    LAUNCH_CHECK("sum_sqrt");
+    LAUNCH_RETURN("sum_sqrt");
 }
 __global__ void axpy_scaled_kernel(double *x, const double *r, double c, long n)
 {
@@ -2834,7 +2790,7 @@ int launch_axpy_scaled(double *x, const double *r, double c, long n, hipStream_t
 {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(axpy_scaled_kernel, dim3(vec_grid(n)), dim3(256), 0, st, x, r, c, n);
-    LAUNCH_CHECK("axpy_scaled");
+    LAUNCH_RETURN("axpy_scaled");
 }
 
 int launch_norm2(const double *x, long n, double *scratch, double *result_dev, hipStream_t st)
@@ -2844,7 +2800,7 @@ int launch_norm2(const double *x, long n, double *scratch, double *result_dev, h
     if (nb < 1) nb = 1;
     hipLaunchKernelGGL(sumsq_stage1, dim3(nb), dim3(256), 0, st, x, n, scratch);
     hipLaunchKernelGGL(sumsq_stage2, dim3(1), dim3(256), 0, st, scratch, nb, result_dev);
-    LAUNCH_CHECK("norm2");
+    LAUNCH_RETURN("norm2");
 }
 
 // dot product, same deterministic two-stage scheme
@@ -2872,7 +2828,7 @@ int launch_dot(const double *x, const double *y, long n, double *scratch, double
     if (nb < 1) nb = 1;
     hipLaunchKernelGGL(dot_stage1, dim3(nb), dim3(256), 0, st, x, y, n, scratch);
     hipLaunchKernelGGL(sum_stage2, dim3(1), dim3(256), 0, st, scratch, nb, result_dev);
-    LAUNCH_CHECK("dot");
+    LAUNCH_RETURN("dot");
 }
 __global__ void axpy_kernel(double *w, const double *v, double a, long n)   // w = w - a*v
 {
@@ -2891,13 +2847,13 @@ int launch_axmy_ratio(double *w, const double *v, const double *num, const doubl
 {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(axpy_ratio_kernel, dim3(vec_grid(n)), dim3(256), 0, st, w, v, num, den, sign, n);
-    LAUNCH_CHECK("axmy ratio");
+    LAUNCH_RETURN("axmy ratio");
 }
 int launch_axmy(double *w, const double *v, double a, long n, hipStream_t st)
 {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(axpy_kernel, dim3(vec_grid(n)), dim3(256), 0, st, w, v, a, n);
-    LAUNCH_CHECK("axmy");
+    LAUNCH_RETURN("axmy");
 }
 __global__ void divide_kernel(double *w, double a, long n)
 {
@@ -2908,7 +2864,7 @@ int launch_divide(double *w, double a, long n, hipStream_t st)
 {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(divide_kernel, dim3(vec_grid(n)), dim3(256), 0, st, w, a, n);
-    LAUNCH_CHECK("divide");
+    LAUNCH_RETURN("divide");
 }
 __global__ void mul_elem_kernel(double *w, const double *d, long n)
 {
@@ -2919,7 +2875,7 @@ int launch_mul_elem(double *w, const double *d, long n, hipStream_t st)
 {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(mul_elem_kernel, dim3(vec_grid(n)), dim3(256), 0, st, w, d, n);
-    LAUNCH_CHECK("mul_elem");
+    LAUNCH_RETURN("mul_elem");
 }
 __global__ void combine_kernel(double *out, const double *V, const double *coef, int m, long n, long ld)
 {
@@ -2933,7 +2889,7 @@ int launch_combine(double *out, const double *V, const double *coef_dev, int m, 
 {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(combine_kernel, dim3(vec_grid(n)), dim3(256), 0, st, out, V, coef_dev, m, n, ld);
-    LAUNCH_CHECK("combine");
+    LAUNCH_RETURN("combine");
 }
 
 // ---------------------------------------------------------------------------
@@ -2961,7 +2917,7 @@ int launch_dense_apply(const double *Mt, const double *b, double *x, int n, hipS
 {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(dense_apply_kernel, dim3((n + 63) / 64), dim3(64), 0, st, Mt, b, x, n);
-    LAUNCH_CHECK("dense_apply");
+    LAUNCH_RETURN("dense_apply");
 }
 
 constexpr int MAXBS = 16;
@@ -3264,7 +3220,7 @@ int launch_bsr_stream(BlockMode m, const BsrStreamArgs &a, long nblocks_hint, hi
     }
 #undef BSR_BY_BS
 #undef BSR_LAUNCH
-    LAUNCH_CHECK("bsr_stream kernel");
+    LAUNCH_RETURN("bsr_stream kernel");
 }
 
 }  // namespace amg

@@ -9,18 +9,12 @@
 // ZDOT_WG sums by a halving tree, one workgroup adds the ZDOT_BLOCKS partial sums the same way.
 //
 // Scratch (amg_hierx_scratch): ZDOT_BLOCKS partial sums followed by AMG_DEVX_SLOTS result slots, all complex128.
-#include "amg_dev.hpp"
+#include "driver.hpp"
 #include "../../include/amgcore_hip.h"
 #include "scalar.hpp"
 
 using namespace amg;
 using namespace amg::sc;
-
-#define CHK(call)                   \
-    do {                            \
-        int rc__ = (call);          \
-        if (rc__ != 0) return rc__; \
-    } while (0)
 
 namespace {
 
@@ -29,13 +23,6 @@ constexpr int ZDOT_WG = 256;
 constexpr int VEC_WG = 256;
 
 int blocks_of(long n, int per) { return (int)((n + per - 1) / per); }
-
-int launched(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
-    return 0;
-}
 
 // the workgroup's ZDOT_WG values added by a halving tree; the sum is s[0]
 __device__ void tree_sum(c128 *s)

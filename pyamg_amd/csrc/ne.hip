@@ -9,34 +9,14 @@
 // jacobi_ne scatters into temp; here each temp entry gathers its contributions
 // through the transposed pattern in the same (row, position) order.
 #include "hier.hpp"
+#include "driver.hpp"
 
 #include <algorithm>
 #include <cstring>
 
 using namespace amg;
 
-#define CHK(call)                   \
-    do {                            \
-        int rc__ = (call);          \
-        if (rc__ != 0) return rc__; \
-    } while (0)
-
 namespace {
-
-struct DB {
-    void *p = nullptr;
-    ~DB() { if (p) hipFree(p); }
-    int put(const void *src, size_t bytes)
-    {
-        hipError_t e = hipMalloc(&p, bytes + 64);
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc", __FILE__, __LINE__);
-        if (bytes) AMG_HIP(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
-        return 0;
-    }
-    int get(void *dst, size_t bytes) { if (bytes) AMG_HIP(hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost)); return 0; }
-    double *d() { return (double *)p; }
-    int *i() { return (int *)p; }
-};
 
 // level(t) = 1 + max level of earlier tasks touching a common entry
 int touch_levels(int nvec, const int *Ap, const int *Aj, const std::vector<int> &tasks,
@@ -144,18 +124,14 @@ int launch_gs_ne_level(const int *Ap, const int *Aj, const double *Ax, double *x
 {
     if (count <= 0) return 0;
     hipLaunchKernelGGL(gs_ne_level, dim3((count + 127) / 128), dim3(128), 0, st, Ap, Aj, Ax, x, b, Dinv, omega, rows, count);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "gs_ne level launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("gs_ne level launch");
 }
 int launch_gs_nr_level(const int *Ap, const int *Aj, const double *Ax, double *x, double *r, const double *Dinv,
                        double omega, const int *cols, int count, hipStream_t st)
 {
     if (count <= 0) return 0;
     hipLaunchKernelGGL(gs_nr_level, dim3((count + 127) / 128), dim3(128), 0, st, Ap, Aj, Ax, x, r, Dinv, omega, cols, count);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "gs_nr level launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("gs_nr level launch");
 }
 // temp[c] = sum over column c of A, rows ascending, of (omega * a) * delta[row]  (relaxation.h:485-495)
 int launch_jacobi_ne_gather(const int *Tp, const int *Trow, const double *Tval, const double *delta, double omega,
@@ -164,9 +140,7 @@ int launch_jacobi_ne_gather(const int *Tp, const int *Trow, const double *Tval, 
     if (n <= 0) return 0;
     hipLaunchKernelGGL(jacobi_ne_gather, dim3((n + 127) / 128), dim3(128), 0, st, Tp, Trow, Tval, delta, omega, temp,
                        (const unsigned char *)nullptr, n);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "jacobi_ne gather launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("jacobi_ne gather launch");
 }
 }  // namespace amg
 
@@ -185,14 +159,14 @@ int amgcore_gauss_seidel_ne_f64(const int Ap[], int Ap_size, const int Aj[], int
     CHK(sweep(row_start, row_stop, row_step, std::min(n, std::min(b_size, Tx_size)), tasks));
     if (tasks.empty()) return 0;
     CHK(touch_levels(x_size, Ap, Aj, tasks, lp, order));
-    DB dAp, dAj, dAx, dx, db, dT, dord;
-    CHK(dAp.put(Ap, sizeof(int) * (size_t)Ap_size));
-    CHK(dAj.put(Aj, sizeof(int) * (size_t)Ap[n]));
-    CHK(dAx.put(Ax, sizeof(double) * (size_t)Ap[n]));
-    CHK(dx.put(x, sizeof(double) * (size_t)x_size));
-    CHK(db.put(b, sizeof(double) * (size_t)b_size));
-    CHK(dT.put(Tx, sizeof(double) * (size_t)Tx_size));
-    CHK(dord.put(order.data(), sizeof(int) * order.size()));
+    DBuf dAp, dAj, dAx, dx, db, dT, dord;
+    CHK(dAp.from_host(Ap, sizeof(int) * (size_t)Ap_size));
+    CHK(dAj.from_host(Aj, sizeof(int) * (size_t)Ap[n]));
+    CHK(dAx.from_host(Ax, sizeof(double) * (size_t)Ap[n]));
+    CHK(dx.from_host(x, sizeof(double) * (size_t)x_size));
+    CHK(db.from_host(b, sizeof(double) * (size_t)b_size));
+    CHK(dT.from_host(Tx, sizeof(double) * (size_t)Tx_size));
+    CHK(dord.from_host(order.data(), sizeof(int) * order.size()));
     for (size_t l = 0; l + 1 < lp.size(); ++l) {
         int cnt = lp[l + 1] - lp[l];
         if (cnt <= 0) continue;
@@ -201,7 +175,7 @@ int amgcore_gauss_seidel_ne_f64(const int Ap[], int Ap_size, const int Aj[], int
     }
     AMG_HIP(hipGetLastError());
     AMG_HIP(hipDeviceSynchronize());
-    return dx.get(x, sizeof(double) * (size_t)x_size);
+    return dx.to_host(x, sizeof(double) * (size_t)x_size);
 }
 
 int amgcore_gauss_seidel_nr_f64(const int Ap[], int Ap_size, const int Aj[], int Aj_size,
@@ -217,14 +191,14 @@ int amgcore_gauss_seidel_nr_f64(const int Ap[], int Ap_size, const int Aj[], int
     CHK(sweep(col_start, col_stop, col_step, std::min(n, std::min(x_size, Tx_size)), tasks));
     if (tasks.empty()) return 0;
     CHK(touch_levels(z_size, Ap, Aj, tasks, lp, order));
-    DB dAp, dAj, dAx, dx, dz, dT, dord;
-    CHK(dAp.put(Ap, sizeof(int) * (size_t)Ap_size));
-    CHK(dAj.put(Aj, sizeof(int) * (size_t)Ap[n]));
-    CHK(dAx.put(Ax, sizeof(double) * (size_t)Ap[n]));
-    CHK(dx.put(x, sizeof(double) * (size_t)x_size));
-    CHK(dz.put(z, sizeof(double) * (size_t)z_size));
-    CHK(dT.put(Tx, sizeof(double) * (size_t)Tx_size));
-    CHK(dord.put(order.data(), sizeof(int) * order.size()));
+    DBuf dAp, dAj, dAx, dx, dz, dT, dord;
+    CHK(dAp.from_host(Ap, sizeof(int) * (size_t)Ap_size));
+    CHK(dAj.from_host(Aj, sizeof(int) * (size_t)Ap[n]));
+    CHK(dAx.from_host(Ax, sizeof(double) * (size_t)Ap[n]));
+    CHK(dx.from_host(x, sizeof(double) * (size_t)x_size));
+    CHK(dz.from_host(z, sizeof(double) * (size_t)z_size));
+    CHK(dT.from_host(Tx, sizeof(double) * (size_t)Tx_size));
+    CHK(dord.from_host(order.data(), sizeof(int) * order.size()));
     for (size_t l = 0; l + 1 < lp.size(); ++l) {
         int cnt = lp[l + 1] - lp[l];
         if (cnt <= 0) continue;
@@ -233,8 +207,8 @@ int amgcore_gauss_seidel_nr_f64(const int Ap[], int Ap_size, const int Aj[], int
     }
     AMG_HIP(hipGetLastError());
     AMG_HIP(hipDeviceSynchronize());
-    CHK(dx.get(x, sizeof(double) * (size_t)x_size));
-    return dz.get(z, sizeof(double) * (size_t)z_size);
+    CHK(dx.to_host(x, sizeof(double) * (size_t)x_size));
+    return dz.to_host(z, sizeof(double) * (size_t)z_size);
 }
 
 int amgcore_jacobi_ne_f64(const int Ap[], int Ap_size, const int Aj[], int Aj_size, const double Ax[],
@@ -275,15 +249,15 @@ int amgcore_jacobi_ne_f64(const int Ap[], int Ap_size, const int Aj[], int Aj_si
             Trow[k] = i;
             Tval[k] = Ax[j];
         }
-    DB dTp, dTr, dTv, dx, dtemp, ddelta, dmask, drows;
-    CHK(dTp.put(Tp.data(), sizeof(int) * Tp.size()));
-    CHK(dTr.put(Trow.data(), sizeof(int) * Trow.size()));
-    CHK(dTv.put(Tval.data(), sizeof(double) * Tval.size()));
-    CHK(dx.put(x, sizeof(double) * (size_t)x_size));
-    CHK(dtemp.put(temp, sizeof(double) * (size_t)temp_size));
-    CHK(ddelta.put(Tx, sizeof(double) * (size_t)Tx_size));
-    CHK(dmask.put(in_range.data(), in_range.size()));
-    CHK(drows.put(rows.data(), sizeof(int) * rows.size()));
+    DBuf dTp, dTr, dTv, dx, dtemp, ddelta, dmask, drows;
+    CHK(dTp.from_host(Tp.data(), sizeof(int) * Tp.size()));
+    CHK(dTr.from_host(Trow.data(), sizeof(int) * Trow.size()));
+    CHK(dTv.from_host(Tval.data(), sizeof(double) * Tval.size()));
+    CHK(dx.from_host(x, sizeof(double) * (size_t)x_size));
+    CHK(dtemp.from_host(temp, sizeof(double) * (size_t)temp_size));
+    CHK(ddelta.from_host(Tx, sizeof(double) * (size_t)Tx_size));
+    CHK(dmask.from_host(in_range.data(), in_range.size()));
+    CHK(drows.from_host(rows.data(), sizeof(int) * rows.size()));
     hipLaunchKernelGGL(jacobi_ne_gather, dim3((temp_size + 127) / 128), dim3(128), 0, nullptr, dTp.i(), dTr.i(),
                        dTv.d(), ddelta.d(), omega[0], dtemp.d(), (const unsigned char *)dmask.p, temp_size);
     int cnt = (int)rows.size();
@@ -291,8 +265,8 @@ int amgcore_jacobi_ne_f64(const int Ap[], int Ap_size, const int Aj[], int Aj_si
                        drows.i(), cnt);
     AMG_HIP(hipGetLastError());
     AMG_HIP(hipDeviceSynchronize());
-    CHK(dx.get(x, sizeof(double) * (size_t)x_size));
-    return dtemp.get(temp, sizeof(double) * (size_t)temp_size);
+    CHK(dx.to_host(x, sizeof(double) * (size_t)x_size));
+    return dtemp.to_host(temp, sizeof(double) * (size_t)temp_size);
 }
 
 }  // extern "C"

@@ -17,13 +17,6 @@ enum { COARSE_NONE = 0, COARSE_DENSE = 1, COARSE_SMOOTHER = 2, COARSE_CALLBACK =
 
 int blocks_of(long n, int per) { return (int)((n + per - 1) / per); }
 
-int launched(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
-    return 0;
-}
-
 // Ap nondecreasing from 0, every column index in [0, ncols): no kernel can read outside its arrays
 int check_pattern(const int *Ap, int nrows, const int *Aj, int ncols)
 {

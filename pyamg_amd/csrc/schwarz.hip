@@ -10,17 +10,12 @@
 // bit-identical to the sequential loop.  The conflict relation is symmetric, so the levels in
 // descending order are the backward sweep.
 #include "hier.hpp"
+#include "driver.hpp"
 
 #include <algorithm>
 #include <cstring>
 
 using namespace amg;
-
-#define CHK(call)                   \
-    do {                            \
-        int rc__ = (call);          \
-        if (rc__ != 0) return rc__; \
-    } while (0)
 
 namespace amg {
 
@@ -96,29 +91,10 @@ int launch_schwarz_level(const int *Ap, const int *Aj, const double *Ax, double 
     if (count <= 0) return 0;
     hipLaunchKernelGGL(schwarz_level_kernel, dim3((count + 63) / 64), dim3(64), 0, st, Ap, Aj, Ax, x, b, Tx, Tp, Sj,
                        Sp, scratch, doms, count);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "schwarz level launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("schwarz level launch");
 }
 
 }  // namespace amg
-
-namespace {
-struct DB {
-    void *p = nullptr;
-    ~DB() { if (p) hipFree(p); }
-    int put(const void *src, size_t bytes)
-    {
-        hipError_t e = hipMalloc(&p, bytes + 64);
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc", __FILE__, __LINE__);
-        if (bytes && src) AMG_HIP(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
-        return 0;
-    }
-    int get(void *dst, size_t bytes) { if (bytes) AMG_HIP(hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost)); return 0; }
-    double *d() { return (double *)p; }
-    int *i() { return (int *)p; }
-};
-}  // namespace
 
 extern "C" {
 
@@ -153,23 +129,23 @@ int amgcore_overlapping_schwarz_csr_f64(const int Ap[], int Ap_size, const int A
         if ((long)(Sp[d + 1] - Sp[d]) * (Sp[d + 1] - Sp[d]) != (long)Tp[d + 1] - Tp[d]) { set_error("inverse block size does not match its subdomain"); return AMG_EINVAL; }
     std::vector<int> lp, order;
     CHK(schwarz_levels(n, Ap, Aj, Sj, Sp, tasks, lp, order));
-    DB dAp, dAj, dAx, dx, db, dT, dTp, dSj, dSp, dord, dscr;
-    CHK(dAp.put(Ap, sizeof(int) * (size_t)Ap_size));
-    CHK(dAj.put(Aj, sizeof(int) * (size_t)Ap[n]));
-    CHK(dAx.put(Ax, sizeof(double) * (size_t)Ap[n]));
-    CHK(dx.put(x, sizeof(double) * (size_t)x_size));
-    CHK(db.put(b, sizeof(double) * (size_t)b_size));
-    CHK(dT.put(Tx, sizeof(double) * (size_t)Tp[nsdomains]));
-    CHK(dTp.put(Tp, sizeof(int) * (size_t)(nsdomains + 1)));
-    CHK(dSj.put(Sj, sizeof(int) * (size_t)Sp[nsdomains]));
-    CHK(dSp.put(Sp, sizeof(int) * (size_t)(nsdomains + 1)));
-    CHK(dord.put(order.data(), sizeof(int) * order.size()));
-    CHK(dscr.put(nullptr, sizeof(double) * (size_t)Sp[nsdomains]));
+    DBuf dAp, dAj, dAx, dx, db, dT, dTp, dSj, dSp, dord, dscr;
+    CHK(dAp.from_host(Ap, sizeof(int) * (size_t)Ap_size));
+    CHK(dAj.from_host(Aj, sizeof(int) * (size_t)Ap[n]));
+    CHK(dAx.from_host(Ax, sizeof(double) * (size_t)Ap[n]));
+    CHK(dx.from_host(x, sizeof(double) * (size_t)x_size));
+    CHK(db.from_host(b, sizeof(double) * (size_t)b_size));
+    CHK(dT.from_host(Tx, sizeof(double) * (size_t)Tp[nsdomains]));
+    CHK(dTp.from_host(Tp, sizeof(int) * (size_t)(nsdomains + 1)));
+    CHK(dSj.from_host(Sj, sizeof(int) * (size_t)Sp[nsdomains]));
+    CHK(dSp.from_host(Sp, sizeof(int) * (size_t)(nsdomains + 1)));
+    CHK(dord.from_host(order.data(), sizeof(int) * order.size()));
+    CHK(dscr.alloc(sizeof(double) * (size_t)Sp[nsdomains]));
     for (size_t l = 0; l + 1 < lp.size(); ++l)
         CHK(launch_schwarz_level(dAp.i(), dAj.i(), dAx.d(), dx.d(), db.d(), dT.d(), dTp.i(), dSj.i(), dSp.i(),
                                  dscr.d(), dord.i() + lp[l], lp[l + 1] - lp[l], nullptr));
     AMG_HIP(hipDeviceSynchronize());
-    return dx.get(x, sizeof(double) * (size_t)x_size);
+    return dx.to_host(x, sizeof(double) * (size_t)x_size);
 }
 
 }  // extern "C"

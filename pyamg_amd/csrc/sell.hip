@@ -17,6 +17,7 @@
 // operands (b[row], v2[row]); (3) the gathered operands; (2) and (3) again for rows of more than SL_PASS entries;
 // (4) the store.
 #include "hier.hpp"
+#include "driver.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -324,9 +325,7 @@ int launch_sell(StreamMode mode, const StreamArgs &a, const DevCsr &M, hipStream
 #undef SELL_CASE
     default: set_error("launch_sell: mode not supported"); return -1;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "sell launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("sell launch");
 }
 
 // Built from the CSR arrays in HBM.  Only where it pays (measured on the 500^3 hierarchy, tools/sell_ab.py and the
@@ -361,8 +360,7 @@ int build_sell(DevCsr &M, long *acct, int row_lo, int row_hi)
     AMG_HIP(hipMalloc((void **)&w_dev, sizeof(int) * (size_t)nslices));
     if (sigma == SL_SIGMA_RECT) hipLaunchKernelGGL((sell_sort_kernel<SL_SIGMA_RECT>), dim3(nwin), dim3(64), 0, nullptr, row_lo, n, M.Ap, slot, w_dev);
     else hipLaunchKernelGGL((sell_sort_kernel<SL_SIGMA_SQUARE>), dim3(nwin), dim3(256), 0, nullptr, row_lo, n, M.Ap, slot, w_dev);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "sell sort launch", __FILE__, __LINE__);
+    LAUNCH_CHECK("sell sort launch");
     std::vector<int> hw((size_t)nslices);
     AMG_HIP(hipMemcpy(hw.data(), w_dev, sizeof(int) * (size_t)nslices, hipMemcpyDeviceToHost));
     hipFree(w_dev);
@@ -389,16 +387,14 @@ int build_sell(DevCsr &M, long *acct, int row_lo, int row_hi)
     AMG_HIP(hipMemcpy(hdr_dev, hdr.data(), sizeof(SellHdr) * (size_t)nslices, hipMemcpyHostToDevice));
     const int bgrid = (nslices + SL_WG / SL_C - 1) / (SL_WG / SL_C);
     hipLaunchKernelGGL(sell_fill_kernel, dim3(bgrid), dim3(SL_WG), 0, nullptr, nslices, M.Ap, M.Aj, M.Ax, slot, hdr_dev, col, val);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "sell fill launch", __FILE__, __LINE__);
+    LAUNCH_CHECK("sell fill launch");
     AMG_HIP(hipDeviceSynchronize());
     M.sl_slot = slot; M.sl_hdr = hdr_dev; M.sl_col = col; M.sl_val = val;
     M.sl_nslices = nslices; M.sl_entries = entries; M.sl_lo = row_lo; M.sl_hi = row_hi;
     if (want16) {
         AMG_HIP(hipMalloc((void **)&M.sl_code, sizeof(unsigned) * (size_t)std::max(words, 1L)));
         hipLaunchKernelGGL(sell_code_kernel, dim3(bgrid), dim3(SL_WG), 0, nullptr, nslices, slot, hdr_dev, col, M.sl_code);
-        e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "sell code launch", __FILE__, __LINE__);
+        LAUNCH_CHECK("sell code launch");
         std::vector<SellHdr> back((size_t)nslices);
         AMG_HIP(hipMemcpy(back.data(), hdr_dev, sizeof(SellHdr) * (size_t)nslices, hipMemcpyDeviceToHost));
         long coded = 0;
@@ -632,8 +628,7 @@ int build_bsell_bs(DevBsr &M, long *acct, const std::vector<int> *level_ptr = nu
     AMG_HIP(hipMalloc((void **)&blen, sizeof(unsigned short) * (size_t)nslices * NBR));
     AMG_HIP(hipMalloc((void **)&w_dev, sizeof(int) * (size_t)nslices));
     hipLaunchKernelGGL((bsell_sort_kernel<NBR>), dim3(nwin), dim3(1024), 0, nullptr, nb, M.Ap, brow, blen, w_dev, (const int *)ws_dev, (const int *)wl_dev);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "bsell sort launch", __FILE__, __LINE__);
+    LAUNCH_CHECK("bsell sort launch");
     std::vector<int> hw((size_t)nslices);
     AMG_HIP(hipMemcpy(hw.data(), w_dev, sizeof(int) * (size_t)nslices, hipMemcpyDeviceToHost));
     hipFree(w_dev);
@@ -649,8 +644,7 @@ int build_bsell_bs(DevBsr &M, long *acct, const std::vector<int> *level_ptr = nu
     AMG_HIP(hipMalloc((void **)&val, sizeof(double) * (size_t)std::max(cols * BS * NBR * BS, 1L)));
     AMG_HIP(hipMemcpy(off_dev, off.data(), sizeof(long) * ((size_t)nslices + 1), hipMemcpyHostToDevice));
     hipLaunchKernelGGL((bsell_fill_kernel<BS>), dim3((nslices + 3) / 4), dim3(256), 0, nullptr, nslices, M.Ap, M.Aj, M.Ax, brow, blen, off_dev, col, val);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "bsell fill launch", __FILE__, __LINE__);
+    LAUNCH_CHECK("bsell fill launch");
     if (rowmap_dev) {                                                // x / b / Dinv are indexed by the ORIGINAL block row
         const int nslots = nslices * NBR;
         hipLaunchKernelGGL(bsell_remap_kernel, dim3((nslots + 255) / 256), dim3(256), 0, nullptr, nslots, rowmap_dev, brow);
@@ -713,9 +707,7 @@ int launch_bsell_level(const DevBsr &M, BlockMode m, const BsrStreamArgs &a, int
     if (M.bs == 3) hipLaunchKernelGGL((bsell_kernel<BM_BLOCK_GS, 3>), dim3(grid), dim3(256), 0, st, a, S, 0, slice_lo, n);
     else if (M.bs == 2) hipLaunchKernelGGL((bsell_kernel<BM_BLOCK_GS, 2>), dim3(grid), dim3(256), 0, st, a, S, 0, slice_lo, n);
     else { set_error("launch_bsell_level: block size not supported"); return -1; }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "bsell level launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("bsell level launch");
 }
 
 bool bsell_level_enabled() { return g_sell != 0; }
@@ -738,9 +730,7 @@ int launch_bsell(const DevBsr &M, BlockMode m, const BsrStreamArgs &a, hipStream
     else if (M.bs == 2 && m == BM_SPMV) hipLaunchKernelGGL((bsell_kernel<BM_SPMV, 2>), dim3(grid), dim3(256), 0, st, a, S, chunk, 0, M.bsl_nslices);
     else if (M.bs == 2) hipLaunchKernelGGL((bsell_kernel<BM_BLOCK_JACOBI, 2>), dim3(grid), dim3(256), 0, st, a, S, chunk, 0, M.bsl_nslices);
     else { set_error("launch_bsell: block size not supported"); return -1; }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "bsell launch", __FILE__, __LINE__);
-    return 0;
+    LAUNCH_RETURN("bsell launch");
 }
 
 }   // namespace amg

@@ -11,6 +11,7 @@
 // row.  Bit-identical to the host restatement (setup_host.cpp amgsetup_csr_matmat_*) and to scipy: same products, same
 // order, separate multiply and add.
 #include "hier.hpp"
+#include "driver.hpp"
 #include "scalar.hpp"
 
 #include <algorithm>
@@ -23,12 +24,6 @@
 #include <vector>
 
 using namespace amg;
-
-#define CHK(call)                   \
-    do {                            \
-        int rc__ = (call);          \
-        if (rc__ != 0) return rc__; \
-    } while (0)
 
 namespace {
 
@@ -383,8 +378,7 @@ int matmat(const DCsrT<V> &A, const DCsrT<V> &B, DCsrT<V> &C)
                                   else if (G == 32) GROUP_LAUNCH(FILL, 32); else GROUP_LAUNCH(FILL, 64); } while (0)
         C.Ap = nullptr; C.Aj = nullptr; C.Ax = nullptr;
         GROUP_DISPATCH(false);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "spgemm group count launch", __FILE__, __LINE__);
+        LAUNCH_CHECK("spgemm group count launch");
         int ovf = 0;
         AMG_HIP(hipMemcpy(&ovf, overflow, sizeof(int), hipMemcpyDeviceToHost));
         if (std::getenv("AMG_SETUP_VERBOSE") && std::getenv("AMG_SETUP_VERBOSE")[0] != '0')
@@ -402,8 +396,7 @@ int matmat(const DCsrT<V> &A, const DCsrT<V> &B, DCsrT<V> &C)
             AMG_HIP(hipMalloc((void **)&C.Ax, sizeof(V) * (size_t)std::max(C.nnz, 1L)));
             AMG_HIP(hipMemcpy(C.Ap, cp.data(), sizeof(long) * ((size_t)n + 1), hipMemcpyHostToDevice));
             GROUP_DISPATCH(true);
-            e = hipGetLastError();
-            if (e != hipSuccess) return hip_fail(e, "spgemm group fill launch", __FILE__, __LINE__);
+            LAUNCH_CHECK("spgemm group fill launch");
             AMG_HIP(hipDeviceSynchronize());
             hipFree(count); hipFree(overflow);
             return 0;
@@ -431,8 +424,7 @@ int matmat(const DCsrT<V> &A, const DCsrT<V> &B, DCsrT<V> &C)
         C.Ap = nullptr; C.Aj = nullptr; C.Ax = nullptr;
         hipLaunchKernelGGL((spgemm_group_kernel<V, false, 64, true>), dim3(blocks), dim3(64), 0, nullptr, n, A.Ap, A.Aj, A.Ax, B.Ap, B.Aj, B.Ax,
                            count, (const long *)nullptr, (int *)nullptr, (V *)nullptr, overflow, gkey, gsum, gord, gcap);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "spgemm HBM-table count launch", __FILE__, __LINE__);
+        LAUNCH_CHECK("spgemm HBM-table count launch");
         int ovf = 0;
         AMG_HIP(hipMemcpy(&ovf, overflow, sizeof(int), hipMemcpyDeviceToHost));
         if (std::getenv("AMG_SETUP_VERBOSE") && std::getenv("AMG_SETUP_VERBOSE")[0] != '0')
@@ -452,8 +444,7 @@ int matmat(const DCsrT<V> &A, const DCsrT<V> &B, DCsrT<V> &C)
             AMG_HIP(hipMemcpy(C.Ap, cp.data(), sizeof(long) * ((size_t)n + 1), hipMemcpyHostToDevice));
             hipLaunchKernelGGL((spgemm_group_kernel<V, true, 64, true>), dim3(blocks), dim3(64), 0, nullptr, n, A.Ap, A.Aj, A.Ax, B.Ap, B.Aj, B.Ax,
                                count, (const long *)C.Ap, C.Aj, C.Ax, overflow, gkey, gsum, gord, gcap);
-            e = hipGetLastError();
-            if (e != hipSuccess) rc = hip_fail(e, "spgemm HBM-table fill launch", __FILE__, __LINE__);
+            rc = launched("spgemm HBM-table fill launch");
             if (hipDeviceSynchronize() != hipSuccess && rc == 0) rc = AMG_ENODEV;
         }
         hipFree(count); hipFree(overflow); hipFree(gkey); hipFree(gord); hipFree(gsum);
@@ -490,8 +481,7 @@ int matmat(const DCsrT<V> &A, const DCsrT<V> &B, DCsrT<V> &C)
     hipLaunchKernelGGL((spgemm_rows_kernel<V, false>), dim3(T1.blocks), dim3(256), 0, nullptr, n, (const int *)nullptr, A.Ap, A.Aj, A.Ax,
                        B.Ap, B.Aj, B.Ax, T1.cap, T1.cap / 2, T1.keys, T1.sums, T1.order, count, (const long *)nullptr,
                        (int *)nullptr, (V *)nullptr);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "spgemm count launch", __FILE__, __LINE__);
+    LAUNCH_CHECK("spgemm count launch");
     std::vector<int> hc((size_t)n);
     AMG_HIP(hipMemcpy(hc.data(), count, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
     std::vector<int> big;
@@ -505,8 +495,7 @@ int matmat(const DCsrT<V> &A, const DCsrT<V> &B, DCsrT<V> &C)
         hipLaunchKernelGGL((spgemm_rows_kernel<V, false>), dim3(T2.blocks), dim3(256), 0, nullptr, (int)big.size(), big_rows, A.Ap, A.Aj, A.Ax,
                            B.Ap, B.Aj, B.Ax, T2.cap, T2.cap / 2, T2.keys, T2.sums, T2.order, count, (const long *)nullptr,
                            (int *)nullptr, (V *)nullptr);
-        e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "spgemm count launch (large tables)", __FILE__, __LINE__);
+        LAUNCH_CHECK("spgemm count launch (large tables)");
         AMG_HIP(hipMemcpy(hc.data(), count, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
         for (int i : big) if (hc[(size_t)i] < 0) { set_error("spgemm: row overflowed the large table"); return AMG_ESTATE; }
     }
@@ -526,13 +515,11 @@ int matmat(const DCsrT<V> &A, const DCsrT<V> &B, DCsrT<V> &C)
     }
     hipLaunchKernelGGL((spgemm_rows_kernel<V, true>), dim3(T1.blocks), dim3(256), 0, nullptr, n, (const int *)nullptr, A.Ap, A.Aj, A.Ax,
                        B.Ap, B.Aj, B.Ax, T1.cap, T1.cap / 2, T1.keys, T1.sums, T1.order, count, C.Ap, C.Aj, C.Ax);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "spgemm fill launch", __FILE__, __LINE__);
+    LAUNCH_CHECK("spgemm fill launch");
     if (!big.empty()) {
         hipLaunchKernelGGL((spgemm_rows_kernel<V, true>), dim3(T2.blocks), dim3(256), 0, nullptr, (int)big.size(), big_rows, A.Ap, A.Aj, A.Ax,
                            B.Ap, B.Aj, B.Ax, T2.cap, T2.cap / 2, T2.keys, T2.sums, T2.order, count, C.Ap, C.Aj, C.Ax);
-        e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "spgemm fill launch (large tables)", __FILE__, __LINE__);
+        LAUNCH_CHECK("spgemm fill launch (large tables)");
     }
     AMG_HIP(hipDeviceSynchronize());
     T1.drop(); T2.drop();

@@ -5,21 +5,11 @@
 // only postpone.  State arrays hold one int per vertex; offsets are widened to 64 bits inside the kernels.
 #include "flat.hpp"
 
-#include <chrono>
 #include <string>
 
 using namespace amg;
 
 namespace {
-
-constexpr int TB = 256;
-inline dim3 grid_for(long work) { return dim3((unsigned)std::max<long>(1, (work + TB - 1) / TB)); }
-
-#define LAUNCH_CHECK(what)                                                            \
-    do {                                                                              \
-        hipError_t e__ = hipGetLastError();                                           \
-        if (e__ != hipSuccess) return hip_fail(e__, what, __FILE__, __LINE__);        \
-    } while (0)
 
 __device__ __forceinline__ int peek(const int *p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
 __device__ __forceinline__ void poke(int *p, int v) { __atomic_store_n(p, v, __ATOMIC_RELAXED); }
@@ -191,9 +181,6 @@ int check_graph(const char *who, int n, const int *p, const int *j)
     return 0;
 }
 
-using clock_type = std::chrono::steady_clock;
-double ms_between(clock_type::time_point a, clock_type::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
-
 }   // namespace
 
 extern "C" {
@@ -208,7 +195,7 @@ int amg_mis_device(int n, const int *Ap, const int *Aj, const double *y, int act
     if (n == 0) return 0;
     CHK(check_graph("mis", n, Ap, Aj));
     CHK(require_device());
-    const auto t0 = clock_type::now();
+    LapClock timer;
     const size_t nnz = (size_t)Ap[n];
     DBuf dp, dj, dy, dx, dflag;
     CHK(dp.from_host(Ap, sizeof(int) * ((size_t)n + 1)));
@@ -217,7 +204,7 @@ int amg_mis_device(int n, const int *Ap, const int *Aj, const double *y, int act
     CHK(dx.from_host(x, sizeof(int) * (size_t)n));
     CHK(dflag.alloc(sizeof(int)));
     AMG_HIP(hipDeviceSynchronize());
-    const auto t1 = clock_type::now();
+    const double upload_ms = timer.lap();
     int done = 0, again = 1;
     while (again) {
         if (done > n) { set_error("mis: no vertex was decided in a round"); return AMG_ESTATE; }    // a round decides >= 1
@@ -230,14 +217,10 @@ int amg_mis_device(int n, const int *Ap, const int *Aj, const double *y, int act
         AMG_HIP(hipMemcpy(&again, dflag.p, sizeof(int), hipMemcpyDeviceToHost));
         ++done;
     }
-    const auto t2 = clock_type::now();
+    const double rounds_ms = timer.lap();
     CHK(dx.to_host(x, sizeof(int) * (size_t)n));
     if (rounds) *rounds = done;
-    if (times_ms) {
-        times_ms[0] = ms_between(t0, t1);
-        times_ms[1] = ms_between(t1, t2);
-        times_ms[2] = ms_between(t2, clock_type::now());
-    }
+    if (times_ms) { times_ms[0] = upload_ms; times_ms[1] = rounds_ms; times_ms[2] = timer.lap(); }
     return 0;
 }
 
@@ -252,7 +235,7 @@ int amg_cljp_device(int n, const int *Sp, const int *Sj, const int *Tp, const in
     CHK(check_graph("cljp: T", n, Tp, Tj));
     if (Sp[n] != Tp[n]) { set_error("cljp: S and its transpose differ in size"); return AMG_EINVAL; }
     CHK(require_device());
-    const auto t0 = clock_type::now();
+    LapClock timer;
     const long nnz = Sp[n];
     const size_t vbytes = sizeof(int) * (size_t)n, ebytes = sizeof(int) * (size_t)nnz;
     DBuf dSp, dSj, dTp, dTj, dSrow, dw, dsplit, dD, dhas, ddec, dmark, dopen;
@@ -265,7 +248,7 @@ int amg_cljp_device(int n, const int *Sp, const int *Sj, const int *Tp, const in
     CHK(dsplit.alloc(vbytes)); CHK(dD.alloc(vbytes)); CHK(dhas.alloc(vbytes)); CHK(ddec.alloc(vbytes));
     CHK(dopen.alloc(sizeof(int)));
     AMG_HIP(hipDeviceSynchronize());
-    const auto t1 = clock_type::now();
+    const double upload_ms = timer.lap();
     hipLaunchKernelGGL(fill_int_kernel, grid_for(n), dim3(TB), 0, nullptr, (long)n, U_NODE, dsplit.i());
     LAUNCH_CHECK("cljp: state launch");
     hipLaunchKernelGGL(fill_int_kernel, grid_for(n), dim3(TB), 0, nullptr, (long)n, 0, ddec.i());
@@ -303,14 +286,10 @@ int amg_cljp_device(int n, const int *Sp, const int *Sj, const int *Tp, const in
         AMG_HIP(hipMemcpy(&open, dopen.p, sizeof(int), hipMemcpyDeviceToHost));
         ++done;
     }
-    const auto t2 = clock_type::now();
+    const double rounds_ms = timer.lap();
     CHK(dsplit.to_host(splitting, vbytes));
     if (passes) *passes = done;
-    if (times_ms) {
-        times_ms[0] = ms_between(t0, t1);
-        times_ms[1] = ms_between(t1, t2);
-        times_ms[2] = ms_between(t2, clock_type::now());
-    }
+    if (times_ms) { times_ms[0] = upload_ms; times_ms[1] = rounds_ms; times_ms[2] = timer.lap(); }
     return 0;
 }
 

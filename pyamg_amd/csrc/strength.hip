@@ -11,7 +11,6 @@
 // scipy's.  Only row counts and offsets travel to the host between upload and fetch.
 #include "flat.hpp"
 
-#include <chrono>
 #include <cfloat>
 #include <cmath>
 #include <cstring>
@@ -29,15 +28,6 @@ int spgemm_square_device(int n, long nnz, long *Ap, int *Aj, double *Ax, long *C
 }
 
 namespace {
-
-constexpr int TB = 256;
-inline dim3 grid_for(long work) { return dim3((unsigned)std::max<long>(1, (work + TB - 1) / TB)); }
-
-#define LAUNCH_CHECK(what)                                                            \
-    do {                                                                              \
-        hipError_t e__ = hipGetLastError();                                           \
-        if (e__ != hipSuccess) return hip_fail(e__, what, __FILE__, __LINE__);        \
-    } while (0)
 
 // row of entry e: the last row whose offset is <= e (empty rows are stepped over)
 template <class P>
@@ -170,19 +160,12 @@ struct DMat {                  // a square CSR matrix in HBM, 64-bit offsets (th
     }
 };
 
-struct DTmp {                  // scratch in HBM
-    void *p = nullptr;
-    ~DTmp() { if (p) hipFree(p); }
-    int alloc(size_t bytes) { AMG_HIP(hipMalloc(&p, std::max<size_t>(bytes, 16))); return 0; }
-    template <class T> T *as() const { return (T *)p; }
-};
-
 // offsets (n + 1) from per-row counts (count[n] = 0) by a device scan; the total comes back to the host
 int offsets_from_counts(int n, const long *count, long *offsets, long *total)
 {
     size_t bytes = 0;
     AMG_HIP(rocprim::exclusive_scan(nullptr, bytes, count, offsets, 0L, (size_t)n + 1, rocprim::plus<long>(), nullptr));
-    DTmp tmp;
+    DBuf tmp;
     CHK(tmp.alloc(bytes));
     AMG_HIP(rocprim::exclusive_scan(tmp.p, bytes, count, offsets, 0L, (size_t)n + 1, rocprim::plus<long>(), nullptr));
     AMG_HIP(hipMemcpy(total, offsets + n, sizeof(long), hipMemcpyDeviceToHost));
@@ -285,12 +268,11 @@ int reorder(const DMat &S, int transposed, DMat &T)
     AMG_HIP(hipMalloc((void **)&T.p, sizeof(long) * ((size_t)n + 1)));
     CHK(T.alloc_entries(S.nnz));
     const long nnz = S.nnz;
-    DTmp keys_in, keys_out, cnt32, cnt64, tmp;
+    DBuf keys_in, keys_out, cnt32, cnt64, tmp;
     CHK(keys_in.alloc(sizeof(unsigned long long) * (size_t)nnz));
     CHK(keys_out.alloc(sizeof(unsigned long long) * (size_t)nnz));
-    CHK(cnt32.alloc(sizeof(int) * ((size_t)n + 1)));
+    CHK(cnt32.zero(sizeof(int) * ((size_t)n + 1)));
     CHK(cnt64.alloc(sizeof(long) * ((size_t)n + 1)));
-    AMG_HIP(hipMemset(cnt32.p, 0, sizeof(int) * ((size_t)n + 1)));
     if (nnz > 0) {
         hipLaunchKernelGGL(entry_keys_kernel, grid_for(nnz), dim3(TB), 0, nullptr, n, nnz, S.p, S.j, transposed, keys_in.as<unsigned long long>());
         LAUNCH_CHECK("strength: sort keys launch");
@@ -316,7 +298,7 @@ int reorder(const DMat &S, int transposed, DMat &T)
 // count / scan / fill around a row kernel: KERNEL<false> fills count (n + 1), KERNEL<true> writes T
 #define COUNT_SCAN_FILL(KCOUNT, KFILL, MAT, NROWS, what, ...)                                                              \
     do {                                                                                                             \
-        DTmp count__;                                                                                                \
+        DBuf count__;                                                                                                \
         CHK(count__.alloc(sizeof(long) * ((size_t)(NROWS) + 1)));                                                        \
         (MAT).release();                                                                                               \
         (MAT).n = (NROWS);                                                                                                 \
@@ -445,11 +427,6 @@ __global__ __launch_bounds__(TB) void invert_scale_kernel(int n, const long *Sp,
     }
     const double s = 1.0 / m;
     for (long jj = lo; jj < hi; ++jj) Sx[jj] = Sx[jj] * s;
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0)
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 }   // namespace
@@ -617,7 +594,7 @@ int amg_evolution_strength_device(int n, const int64_t *Ap, const int *Aj, const
         }
     }
     CHK(require_device());
-    const auto t0 = std::chrono::steady_clock::now();
+    LapClock timer;
     DMat A;
     A.n = n;
     const long nnz = (long)Ap[n];
@@ -628,19 +605,17 @@ int amg_evolution_strength_device(int n, const int64_t *Ap, const int *Aj, const
         AMG_HIP(hipMemcpy(A.j, Aj, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice));
         AMG_HIP(hipMemcpy(A.x, Ax, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice));
     }
-    DTmp bd;
-    CHK(bd.alloc(sizeof(double) * (size_t)n));
-    if (n > 0) AMG_HIP(hipMemcpy(bd.p, b, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+    DBuf bd;
+    CHK(bd.from_host(b, sizeof(double) * (size_t)n));
     AMG_HIP(hipDeviceSynchronize());
-    const auto t1 = std::chrono::steady_clock::now();
-    if (times_ms) times_ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    const double upload_ms = timer.lap();
     amg_strength *s = new amg_strength;
-    int rc = run_pipeline(A, bd.as<double>(), rho, epsilon, k, symmetrize, s->C);
+    int rc = run_pipeline(A, bd.d(), rho, epsilon, k, symmetrize, s->C);
     if (rc == 0 && hipMemcpy(Cp, s->C.p, sizeof(long) * ((size_t)n + 1), hipMemcpyDeviceToHost) != hipSuccess) {
         set_error("evolution strength: offset download failed");
         rc = AMG_ENODEV;
     }
-    if (times_ms) times_ms[1] = ms_since(t1);
+    if (times_ms) { times_ms[0] = upload_ms; times_ms[1] = timer.lap(); }
     if (rc != 0) { delete s; return rc; }
     *out = s;
     return 0;

@@ -107,13 +107,6 @@ __global__ void schwarz_level(const int *Ap, const int *Aj, const T *Ax, T *x, c
 
 // ----------------------------------------------------------------------------------------------- host side
 
-int launched(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
-    return 0;
-}
-
 int blocks_for(long n, int per) { return (int)((n + per - 1) / per); }
 
 // Ap nondecreasing from 0 within Aj/Ax, every index in [0, ncols): nothing a kernel reads can leave its array

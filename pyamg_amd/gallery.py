@@ -138,7 +138,7 @@ def _jittered_vertices(n, jitter, seed):
 
 def _kuhn_native(n, K, jitter, seed):
     import ctypes as C
-    from .aggregation import _dp, _ip, _lp, host_lib
+    from ._host import dp as _dp, host_lib, ip as _ip, lp as _lp
     L = host_lib()
     m = n + 2
     xyz = np.ascontiguousarray(_jittered_vertices(n, jitter, seed))

@@ -17,69 +17,13 @@ import ctypes as C
 import numpy as np
 from scipy import sparse
 
-from .aggregation import _dp, _ip, host_lib
+from ._host import attempt, dp as _dp, f64 as _f64, host_lib as _host, i32 as _i32, ip as _ip, outside as _outside, route
 
 __all__ = ["asgraph", "maximal_independent_set", "vertex_coloring"]
 
 # What device=None does when a GPU is present: the host route until the measurement in profiles/r16_splitting.txt says
 # otherwise.
 DEVICE_AUTO = False
-
-_sig_done = False
-
-
-def _outside(what):
-    return NotImplementedError("%s is outside the restated setup" % what)
-
-
-def _host():
-    global _sig_done
-    L = host_lib()
-    if not _sig_done:
-        I, ip, dp = C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)
-        L.amgsetup_mis_serial.argtypes = [I, ip, ip, I, I, I, ip]
-        L.amgsetup_mis_serial.restype = I
-        L.amgsetup_mis_parallel.argtypes = [I, ip, ip, I, I, I, ip, dp, I]
-        L.amgsetup_mis_parallel.restype = I
-        L.amgsetup_vertex_coloring_mis.argtypes = [I, ip, ip, ip]
-        L.amgsetup_vertex_coloring_mis.restype = I
-        L.amgsetup_vertex_coloring_first_fit.argtypes = [I, ip, ip, ip, I]
-        L.amgsetup_vertex_coloring_first_fit.restype = None
-        L.amgsetup_vertex_coloring_jones_plassmann.argtypes = [I, ip, ip, ip, dp]
-        L.amgsetup_vertex_coloring_jones_plassmann.restype = I
-        L.amgsetup_vertex_coloring_LDF.argtypes = [I, ip, ip, ip, dp]
-        L.amgsetup_vertex_coloring_LDF.restype = I
-        L.amgsetup_cljp_weights.argtypes = [I, ip, ip, I, dp]
-        L.amgsetup_cljp_weights.restype = None
-        L.amgsetup_cljp_select.argtypes = [I, ip, ip, ip, ip, dp, ip]
-        L.amgsetup_cljp_select.restype = I
-        L.amgsetup_cljp_naive_splitting.argtypes = [I, ip, ip, ip, ip, ip, I]
-        L.amgsetup_cljp_naive_splitting.restype = None
-        L.amgsetup_pattern_symmetric.argtypes = [I, ip, ip]
-        L.amgsetup_pattern_symmetric.restype = I
-        _sig_done = True
-    return L
-
-
-def _i32(a):
-    return np.ascontiguousarray(a, dtype=np.intc)
-
-
-def _f64(a):
-    return np.ascontiguousarray(a, dtype=np.float64)
-
-
-def _device_present():
-    from . import _lib
-    return _lib.device_count() > 0
-
-
-def _route(device, module_auto):
-    """True: the device entry, its refusals raised.  None: the device entry, its refusals answered by the host route.
-    False: the host route."""
-    if device is None:
-        return None if (module_auto and _device_present()) else False
-    return bool(device)
 
 
 def _pattern_symmetric(n, Ap, Aj):
@@ -107,14 +51,10 @@ def _luby_device(n, Ap, Aj, active, Cval, Fval, x, y, max_iters=-1, times=None):
 def luby(n, Ap, Aj, active, Cval, Fval, x, y, max_iters=-1, device=None, auto=None, times=None):
     """maximal_independent_set_parallel (graph.h:90-156) on int32 CSR arrays; x (int32) in place.  Returns the number of
     vertices that joined the set."""
-    route = _route(device, DEVICE_AUTO if auto is None else auto)
-    if route is not False:
-        try:
-            return _luby_device(n, Ap, Aj, active, Cval, Fval, x, y, max_iters, times)[0]
-        except NotImplementedError:
-            if route is True:
-                raise
-    return _host().amgsetup_mis_parallel(n, _ip(Ap), _ip(Aj), int(active), int(Cval), int(Fval), _ip(x), _dp(y), int(max_iters))
+    return attempt(route(device, DEVICE_AUTO if auto is None else auto),
+                   lambda: _luby_device(n, Ap, Aj, active, Cval, Fval, x, y, max_iters, times)[0],
+                   lambda: _host().amgsetup_mis_parallel(n, _ip(Ap), _ip(Aj), int(active), int(Cval), int(Fval), _ip(x), _dp(y),
+                                                         int(max_iters)))
 
 
 def asgraph(G):
@@ -145,17 +85,13 @@ def maximal_independent_set(G, algo="serial", k=None, device=None):
     if algo == "parallel":
         luby(N, Ap, Aj, -1, 1, 0, mis, _f64(np.random.rand(N)), -1, device)
         return mis
-    route = _route(device, DEVICE_AUTO)
-    if route is not False:
-        # the greedy set in index order is Luby's set for the priorities -i
-        try:
-            _luby_device(N, Ap, Aj, -1, 1, 0, mis, -np.arange(N, dtype=np.float64))
-            return mis
-        except NotImplementedError:
-            if route is True:
-                raise
-            mis[:] = -1
-    _host().amgsetup_mis_serial(N, _ip(Ap), _ip(Aj), -1, 1, 0, _ip(mis))
+
+    def on_host():
+        mis[:] = -1
+        _host().amgsetup_mis_serial(N, _ip(Ap), _ip(Aj), -1, 1, 0, _ip(mis))
+
+    # the greedy set in index order is Luby's set for the priorities -i
+    attempt(route(device, DEVICE_AUTO), lambda: _luby_device(N, Ap, Aj, -1, 1, 0, mis, -np.arange(N, dtype=np.float64)), on_host)
     return mis
 
 
@@ -177,20 +113,15 @@ def vertex_coloring(G, method="MIS", device=None):
     Ap, Aj = _i32(G.indptr), _i32(G.indices)
     L = _host()
     if method == "MIS":
-        route = _route(device, DEVICE_AUTO)
-        if route is not False:
-            try:
-                coloring[:] = -1
-                y = -np.arange(N, dtype=np.float64)
-                done, K = 0, 0
-                while done < N:
-                    done += _luby_device(N, Ap, Aj, -1 - K, K, -2 - K, coloring, y)[0]
-                    K += 1
-                return coloring
-            except NotImplementedError:
-                if route is True:
-                    raise
-        L.amgsetup_vertex_coloring_mis(N, _ip(Ap), _ip(Aj), _ip(coloring))
+        def on_device():
+            coloring[:] = -1
+            y = -np.arange(N, dtype=np.float64)
+            done, K = 0, 0
+            while done < N:
+                done += _luby_device(N, Ap, Aj, -1 - K, K, -2 - K, coloring, y)[0]
+                K += 1
+
+        attempt(route(device, DEVICE_AUTO), on_device, lambda: L.amgsetup_vertex_coloring_mis(N, _ip(Ap), _ip(Aj), _ip(coloring)))
     elif method == "JP":
         z = _f64(np.random.rand(N))
         L.amgsetup_vertex_coloring_jones_plassmann(N, _ip(Ap), _ip(Aj), _ip(coloring), _dp(z))

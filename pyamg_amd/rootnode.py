@@ -14,6 +14,7 @@ Supported subset (anything else raises NotImplementedError before any level is b
 import numpy as np
 from scipy.sparse import bsr_matrix, csr_matrix, isspmatrix_bsr, isspmatrix_csr
 
+from ._host import outside as _outside
 from .aggregation import (_improve, _levelize_sa, _levelize_smooth, blocksize, fit_candidates, standard_aggregation,
                           symmetric_strength_of_connection, unpack_arg)
 from .multilevel import multilevel_solver
@@ -26,10 +27,6 @@ __all__ = ["rootnode_solver"]
 _STRENGTH = ("symmetric", "evolution", "ode", "predefined", None)
 _AGGREGATE = ("standard", "predefined")
 _SMOOTH = ("energy", None)
-
-
-def _outside(what):
-    return NotImplementedError("%s is outside the restated setup" % what)
 
 
 def _check_options(strength, aggregate, smooth):

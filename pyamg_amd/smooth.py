@@ -30,38 +30,14 @@ import ctypes as C
 import numpy as np
 from scipy.sparse import bsr_matrix, csr_matrix, isspmatrix_bsr, isspmatrix_csr
 
-from .aggregation import host_lib
+from . import _lib
+from ._host import attempt, dp as _dp, f64 as _dc, host_lib, i32 as _ic, ip as _ip, outside as _outside, route
 
 __all__ = ["energy_prolongation_smoother"]
 
 # What device=None does when a GPU is present: decided by the measurement in profiles/r14_energy_smoothing.txt
 # (DESIGN.md section 8f).
 DEVICE_AUTO = False
-
-
-def _outside(what):
-    return NotImplementedError("%s is outside the restated setup" % what)
-
-
-def _ip(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int))
-
-
-def _dp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
-
-
-def _ic(a):
-    return np.ascontiguousarray(a, dtype=np.intc)
-
-
-def _dc(a):
-    return np.ascontiguousarray(a, dtype=np.float64)
-
-
-def _device_present():
-    from . import _lib
-    return _lib.device_count() > 0
 
 
 def _prefiltered(S, prefilter):
@@ -294,7 +270,6 @@ def _cg_host(p, maxiter, tol, trace=None):
 def _cg_device(p, maxiter, tol, trace=None, times=None):
     """the same iteration by csrc/energy.hip; times: a list that receives (upload, iterations, fetch) in milliseconds"""
     import time
-    from . import _lib
     L = _lib.lib()
     handle = C.c_void_p()
     ms = (C.c_double * 2)()
@@ -430,20 +405,10 @@ def energy_prolongation_smoother(A, T, Atilde, B, Bf, Cpt_params, krylov="cg", m
     p.BtBinv = _dc(compute_BtBinv(_dc(B), p.Sp, p.Sj, n_brow, Cc)).ravel()
     p.Dinv = _dc(_weights(A, weighting))
 
-    use_device = device
-    if device is None:
-        use_device = DEVICE_AUTO and _device_present()
-    Tx = None
-    if use_device and inside.all():
-        from . import _lib
-        try:
-            Tx, _ = _cg_device(p, int(maxiter), float(tol), _trace, _times)
-        except (NotImplementedError, ValueError, MemoryError, _lib.AmgError):       # whatever _lib.check raises
-            if device is True:
-                raise
-            Tx = None
-    if Tx is None:
-        Tx, _ = _cg_host(p, int(maxiter), float(tol), _trace)
+    Tx, _ = attempt(route(device, DEVICE_AUTO) if inside.all() else False,
+                    lambda: _cg_device(p, int(maxiter), float(tol), _trace, _times),
+                    lambda: _cg_host(p, int(maxiter), float(tol), _trace),
+                    (NotImplementedError, ValueError, MemoryError, _lib.AmgError))      # whatever _lib.check raises
     P = bsr_matrix((Tx.reshape(-1, R, Cc), p.Sj.copy(), p.Sp.copy()), shape=T.shape)
     if not inside.all():                    # T's blocks outside the pattern are never updated: x + 0.0
         P = P + bsr_matrix((T.data * (~inside)[:, None, None], T.indices, T.indptr), shape=T.shape)

@@ -24,7 +24,8 @@ import scipy.sparse as sparse
 from scipy.sparse import csr_matrix, isspmatrix_bsr, isspmatrix_csr
 
 from . import util
-from .aggregation import host_lib, symmetric_strength_of_connection
+from ._host import dp as _dp, host_lib, ip as _ip, outside as _outside, route
+from .aggregation import symmetric_strength_of_connection
 from .util import approximate_spectral_radius, scale_rows
 
 __all__ = ["symmetric_strength_of_connection", "evolution_strength_of_connection", "ode_strength_of_connection"]
@@ -35,18 +36,6 @@ DEVICE_AUTO = False
 
 _DBL_MAX = np.finfo(np.float64).max
 _DBL_MIN = np.finfo(np.float64).tiny
-
-
-def _outside(what):
-    return NotImplementedError("%s is outside the restated setup" % what)
-
-
-def _ip(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int))
-
-
-def _dp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
 def _power_of_two(k):
@@ -121,10 +110,7 @@ def evolution_strength_of_connection(A, B=None, epsilon=4.0, k=2, proj_type="l2"
         rho = approximate_spectral_radius(Dinv_A)
     rho = float(rho)
 
-    use_device = device
-    if device is None:
-        use_device = DEVICE_AUTO and n >= util.DEVICE_RHO_MIN_ROWS and _power_of_two(k) and _device_present()
-    if use_device:
+    if route(device, DEVICE_AUTO and n >= util.DEVICE_RHO_MIN_ROWS and _power_of_two(k)) is not False:
         Cm = _device_measure(A, b, rho, epsilon, k, symmetrize_measure)
         if Cm is None:
             if device is True:
@@ -135,11 +121,6 @@ def evolution_strength_of_connection(A, B=None, epsilon=4.0, k=2, proj_type="l2"
 
 
 ode_strength_of_connection = evolution_strength_of_connection
-
-
-def _device_present():
-    from . import _lib
-    return _lib.device_count() > 0
 
 
 def _host_measure(A, Dinv_A, b, rho, epsilon, k, symmetrize_measure, csrflag):

@@ -103,7 +103,7 @@ def get_block_diag(A, blocksize, inv_flag=True):
     if inv_flag and A.dtype == np.complex128:
         # complex128: a one-sided Jacobi SVD on the host (csrc/setup_host.cpp) with the reference's rounding -- the
         # spectral-radius estimate of the next level turns LAPACK's last-bit differences into 1e-10 ones
-        from .aggregation import host_lib
+        from ._host import host_lib
         block_diag = np.ascontiguousarray(block_diag)
         host_lib().amgsetup_pinv_blocks_c128(block_diag.ctypes.data, nb, blocksize)
     elif inv_flag:
@@ -523,7 +523,7 @@ def filter_operator(A, C, B, Bf, BtBinv=None):
     A lacks start at 0.0), then corrected row by row so that the result times B is Bf:
     A_i <- A_i - (A_i B - Bf_i) (B_i^T B_i)^+ B_i^T with B_i the rows of B the pattern of row i reaches.
     A, C : both csr_matrix or both bsr_matrix with equal blocks, float64.  Returns A's format, sorted rows."""
-    from .aggregation import host_lib
+    from ._host import host_lib
     from . import smooth
     if A.shape != C.shape:
         raise ValueError("A and C must be the same size")
@@ -576,15 +576,14 @@ def filter_matrix_rows(A, theta):
         raise ValueError("Sparse matrix input needed")
     if theta < 0 or theta >= 1.0:
         raise ValueError("theta must be in [0,1)")
-    from .classical import _lib as classical_lib
-    from .aggregation import _dp, _ip
+    from ._host import dp as _dp, host_lib, ip as _ip
     M = A.tocsr()
     n = M.shape[0]
     Ap = np.ascontiguousarray(M.indptr, dtype=np.intc)
     Aj = np.ascontiguousarray(M.indices, dtype=np.intc) + np.intc(n)
     Ax = np.ascontiguousarray(M.data, dtype=np.float64)
     Sp, Sj, Sx = np.empty_like(Ap), np.empty_like(Aj), np.empty_like(Ax)
-    nnz = classical_lib().amgsetup_classical_strength(n, float(theta), _ip(Ap), _ip(Aj), _dp(Ax), _ip(Sp), _ip(Sj), _dp(Sx))
+    nnz = host_lib().amgsetup_classical_strength(n, float(theta), _ip(Ap), _ip(Aj), _dp(Ax), _ip(Sp), _ip(Sj), _dp(Sx))
     F = csr_matrix((Sx[:nnz], Sj[:nnz] - np.intc(n), Sp), shape=M.shape)
     return F.tobsr(A.blocksize) if isspmatrix_bsr(A) else F.asformat(A.format)
 
@@ -595,7 +594,7 @@ def truncate_rows(A, nz_per_row):
     csrc/setup_host.cpp (amgsetup_truncate_rows_csr), and by the stored order of the row.  A is not changed."""
     if not isspmatrix(A):
         raise ValueError("Sparse matrix input needed")
-    from .aggregation import _dp, _ip, host_lib
+    from ._host import dp as _dp, host_lib, ip as _ip
     M = A.tocsr()
     Sp = np.array(M.indptr, dtype=np.intc)          # copies: eliminate_zeros below rewrites all three arrays
     Sj = np.array(M.indices, dtype=np.intc)

@@ -12,7 +12,7 @@ import energy_io as eio
 import golden_io
 import oracle_lib
 import pyamg_amd
-from pyamg_amd import aggregation, amg_core, smooth
+from pyamg_amd import _host, aggregation, amg_core, smooth
 from pyamg_amd.aggregation import host_lib
 from pyamg_amd.smooth import energy_prolongation_smoother
 
@@ -272,7 +272,7 @@ def test_tentative_prolongator_outside_the_pattern_takes_the_host_route(monkeypa
     Sp, Sj = smooth.sparsity_pattern(sps.bsr_matrix(p["T"]), At, 1)
     assert Sp[6] == Sp[5]
     monkeypatch.setattr(smooth, "DEVICE_AUTO", True)
-    monkeypatch.setattr(smooth, "_device_present", lambda: True)
+    monkeypatch.setattr(_host, "device_present", lambda: True)
     monkeypatch.setattr(_lib, "lib", touched)
     P = energy_prolongation_smoother(p["A"], p["T"], At, p["Bc"], None, (False, {}))
     assert np.abs(P * p["Bc"] - p["B"]).max() <= 1e-12
@@ -291,7 +291,7 @@ def test_device_none_falls_back_when_the_device_entry_refuses(monkeypatch):
         raise NotImplementedError("the device entry refuses: outside the restated setup")
     want = energy_prolongation_smoother(p["A"], p["T"], p["Atilde"], p["Bc"], None, (False, {}), device=False, **s["options"])
     monkeypatch.setattr(smooth, "DEVICE_AUTO", True)
-    monkeypatch.setattr(smooth, "_device_present", lambda: True)
+    monkeypatch.setattr(_host, "device_present", lambda: True)
     monkeypatch.setattr(smooth, "_cg_device", refuses)
     got = energy_prolongation_smoother(p["A"], p["T"], p["Atilde"], p["Bc"], None, (False, {}), **s["options"])
     eio.same_bits(got, want)

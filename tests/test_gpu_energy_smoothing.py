@@ -175,6 +175,19 @@ def test_device_route_maxiter_zero_and_vanishing_residual():
     eio.same_bits(H, sps.bsr_matrix(T, blocksize=(1, 1)))
 
 
+@pytest.mark.parametrize("maxiter", [0, 1])
+@pytest.mark.parametrize("n", [1, 65])
+def test_device_route_on_one_row_and_one_past_a_wave(n, maxiter):
+    # arrays of one or two entries and of one row more than a wave: where an upload or the padding behind it can go wrong
+    A = sps.diags([-np.ones(n - 1), np.linspace(2.0, 3.0, n), -np.ones(n - 1)], [-1, 0, 1], format="csr")
+    B = np.linspace(1.0, 2.0, n).reshape(-1, 1)
+    AggOp = sps.csr_matrix((np.ones(n), (np.arange(n), np.arange(n) // 3)), shape=(n, (n + 2) // 3))
+    T, Bc = fit_candidates(AggOp, B)
+    H, trace = both_routes(A, T, None, Bc, maxiter=maxiter)
+    assert len(trace) == maxiter and H.shape == T.shape
+    assert np.abs(H * Bc - B).max() <= 1e-12
+
+
 def test_device_route_refuses_a_prolongator_outside_the_pattern():
     p = eio.problem("aniso_17x23")
     At = sps.lil_matrix(p["Atilde"])

@@ -144,14 +144,14 @@ def test_four_splittings_on_the_device_equal_the_fixtures(name):
 
 
 # ------------------------------------------------------------------------------------------------ shapes
-@pytest.mark.parametrize("n", [1, 255, 256, 257, 513])
+@pytest.mark.parametrize("n", [0, 1, 65, 255, 256, 257, 513])
 def test_block_edges_for_both_entries(n):
     rng = np.random.RandomState(n)
-    G = sio.random_graph(rng, n, symmetric=True) if n > 1 else sps.csr_matrix((1, 1))
+    G = sio.random_graph(rng, n, symmetric=True) if n > 1 else sps.csr_matrix((n, n))
     for integer in (False, True):
         x, N, rounds = luby_both(G, sio.random_weights(rng, n, integer))
         sio.assert_independent_and_maximal(G, x)
-    S = sio.random_graph(rng, n, symmetric=False) if n > 1 else sps.csr_matrix((1, 1))
+    S = sio.random_graph(rng, n, symmetric=False) if n > 1 else sps.csr_matrix((n, n))
     for integer in (False, True):
         base = sio.random_weights(rng, n, integer) / (4.0 if integer else 1.0)
         cljp_both(S, start_weights(S, base))

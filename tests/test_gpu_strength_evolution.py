@@ -300,7 +300,7 @@ def boundary_operator(n, seed, entries=None):
 # n or n + 1 a multiple of the 256-thread block: the lane i == n that writes count[n] = 0 is the last of a full block
 # (n = 255, 511), the first of a block of its own (n = 256, 512) or the second (257).  1024 = 256 x 4 items is the
 # largest array rocPRIM's radix_sort_pairs sorts with one block; 1025 is the smallest it merge-sorts.
-BOUNDARY = [(255, None), (256, None), (257, None), (511, None), (512, None), (160, eio.SORT_ONE_BLOCK),
+BOUNDARY = [(65, None), (255, None), (256, None), (257, None), (511, None), (512, None), (160, eio.SORT_ONE_BLOCK),
             (160, eio.SORT_ONE_BLOCK + 1)]
 BOUNDARY_RHO = 1.3
 
@@ -317,10 +317,12 @@ def test_pipeline_equals_host_path_at_block_boundaries(n, entries, k):
 
 
 @pytest.mark.parametrize("k", (1, 2))
-@pytest.mark.parametrize("case", ["one_by_one", "one_by_one_cancelled", "empty_rows", "diagonal_only"])
+@pytest.mark.parametrize("case", ["no_rows", "one_by_one", "one_by_one_cancelled", "empty_rows", "diagonal_only"])
 def test_pipeline_equals_host_path_on_degenerate_operators(case, k):
     rho = 2.0
-    if case.startswith("one_by_one"):
+    if case == "no_rows":
+        A = sps.csr_matrix((0, 0), dtype=np.float64)
+    elif case.startswith("one_by_one"):
         A = sps.csr_matrix(np.array([[3.0]]))
         rho = 1.0 if case.endswith("cancelled") else 2.0        # rho = 1: the Jacobi step 1 - 1 / rho stores nothing
     elif case == "empty_rows":

@@ -13,7 +13,7 @@ import golden_io
 import oracle_lib
 import splitting_io as sio
 import pyamg_amd
-from pyamg_amd import classical, graph
+from pyamg_amd import _host, classical, graph
 from pyamg_amd.classical import CLJP, CLJPc, MIS, PMIS, PMISc, preprocess, ruge_stuben_solver
 from pyamg_amd.graph import maximal_independent_set, vertex_coloring
 from test_setup_golden import same
@@ -266,7 +266,7 @@ def test_device_none_falls_back_when_the_device_entry_refuses(monkeypatch):
     _untouchable(monkeypatch)
     monkeypatch.setattr(graph, "DEVICE_AUTO", True)
     monkeypatch.setattr(classical, "DEVICE_AUTO", True)
-    monkeypatch.setattr(graph, "_device_present", lambda: True)
+    monkeypatch.setattr(_host, "device_present", lambda: True)
     assert -1 in want_limit and np.array_equal(MIS(u["G"], y, maxiter=1), want_limit)
     assert np.array_equal(MIS(Gu, y), want_unsym)
     assert np.array_equal(maximal_independent_set(Gu, "serial"), want_serial)
