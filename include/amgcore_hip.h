@@ -33,6 +33,9 @@ const char *amg_last_error(void);
 int amg_device_count(void);
 /* "gfx950:..." of the selected device, or "" */
 const char *amg_device_name(int device);
+/* device allocations the library made and still holds, over the whole process (buffers handed to the caller, such as
+ * amg_dev_alloc's, are not counted): back at its earlier value once everything built since has been destroyed */
+long amg_dev_live_buffers(void);
 
 /* ------------------------------------------------------------------------ */
 /* 1. amg_core drop-ins.  HOST pointers (numpy buffers), results written in  */

@@ -237,6 +237,9 @@ def lib():
         f.restype = I
     L.amg_last_error.restype = C.c_char_p
     L.amg_device_count.restype = I
+    if hasattr(L, "amg_dev_live_buffers"):     # (an older build named by AMGCORE_HIP_LIB for an A/B run has no counter)
+        L.amg_dev_live_buffers.argtypes = []
+        L.amg_dev_live_buffers.restype = C.c_long
     L.amg_device_name.argtypes = [I]
     L.amg_device_name.restype = C.c_char_p
     L.amg_hier_create.argtypes = [I, I]
@@ -388,3 +391,8 @@ def dp(a):
 
 def device_count():
     return lib().amg_device_count()
+
+
+def live_buffers():
+    """Device allocations the library made and still holds (amg_dev_live_buffers)."""
+    return lib().amg_dev_live_buffers()

@@ -1,33 +1,13 @@
 // Internal declarations shared by the translation units of libamgcore_hip.so.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "driver.hpp"
+
 #include <cstdint>
-#include <string>
 #include <vector>
 
 namespace amg {
 
-// ---------------------------------------------------------------- errors
-void set_error(const std::string &msg);
-int hip_fail(hipError_t e, const char *what, const char *file, int line);
-#define AMG_HIP(call)                                                         \
-    do {                                                                      \
-        hipError_t e__ = (call);                                              \
-        if (e__ != hipSuccess) return amg::hip_fail(e__, #call, __FILE__, __LINE__); \
-    } while (0)
-// an internal call that returns one of the library's own status codes
-#define CHK(call)                   \
-    do {                            \
-        int rc__ = (call);          \
-        if (rc__ != 0) return rc__; \
-    } while (0)
-
 // ---------------------------------------------------------------- device CSR
-// Arrays are over-allocated by PAD entries so that 16-byte vector loads that
-// start up to 3 entries before / end up to 3 entries after a row block stay in
-// bounds.
-constexpr int PAD = 16;
-
 struct DevBsr;
 // Sliced form (DevCsr::sl_*, sell.hip): what a slice's wave reads before its entries.  The record's address depends on
 // the slice number alone, so its fields arrive together (as scalar loads: the slice number is wave-uniform) and the
@@ -46,24 +26,24 @@ struct SellSlot {
     int len;
 };
 
+// Every DevArr member below is owned by the struct: move-only, freed with it (driver.hpp).
 struct DevCsr {
     int nrows = 0, ncols = 0;
     long nnz = 0;
-    int *Ap = nullptr;
-    int *Aj = nullptr;
-    double *Ax = nullptr;
-    bool owned = true;
+    DevArr<int> Ap;
+    DevArr<int> Aj;
+    DevArr<double> Ax;
     int longest_row = -1;          // entries of the longest row, found on first need (amg_hier_gs_natural)
-    // The operator's own square blocks (a BSR level of the hierarchy), not owned: when set, applications
+    // The operator's own square blocks (a BSR level of the hierarchy), borrowed from Level::Ab: when set, applications
     // stream 8 B per entry + 4 B per block from there instead of 12 B per entry from the expanded CSR
     const DevBsr *blk = nullptr;
     // Offset-pattern form of the column indices (square operators on structured grids): row i's
     // columns are i + dict_off[dict_ptr[pat[i]] .. ], with a dictionary of a few distinct offset
     // tuples.  When present, the pattern kernel streams 8 B per entry + 4 B per row instead of
     // 12 B per entry; results are identical (same entries, same order).
-    int *pat = nullptr;        // [nrows] pattern id of every row
-    int *dict_ptr = nullptr;   // [npat+1]
-    int *dict_off = nullptr;   // [ndict]
+    DevArr<int> pat;        // [nrows] pattern id of every row
+    DevArr<int> dict_ptr;   // [npat+1]
+    DevArr<int> dict_off;   // [ndict]
     int npat = 0, ndict = 0;
     int period_rows = 0;       // largest |column - row| of the dictionary: the stride of the slowest grid axis
     // Stencil form (a second copy of the values, built on the device when every row's offsets are
@@ -76,21 +56,21 @@ struct DevCsr {
     // are stored entry-major -- entry k of its 64 rows side by side -- padded to the slice's longest row.  One wave per
     // slice, one lane per row: no row pointer, no LDS, no barrier; every lane sums ITS row's entries in stored
     // order, so results are bit-identical to the CSR kernel's.
-    SellSlot *sl_slot = nullptr;   // [sl_nslices * 64] row of the slot (-1: padding slot) and its entries: one 8-byte load per lane
-    SellHdr *sl_hdr = nullptr;     // [sl_nslices] everything the slice's wave needs before its entries, one 32-byte-aligned record
-    int *sl_col = nullptr;
-    double *sl_val = nullptr;
+    DevArr<SellSlot> sl_slot;   // [sl_nslices * 64] row of the slot (-1: padding slot) and its entries: one 8-byte load per lane
+    DevArr<SellHdr> sl_hdr;     // [sl_nslices] everything the slice's wave needs before its entries, one 32-byte-aligned record
+    DevArr<int> sl_col;
+    DevArr<double> sl_val;
     int sl_nslices = 0;
     // 16-bit column codes of the sliced form (lossless): the columns a slice's 64 rows reference fall into a few narrow
     // clusters; when at most 16 aligned windows of 4096 columns cover them, entry k of a row is stored as
     // (window slot << 12) | (column & 4095), two codes per 32-bit word, and the slice's 16 window origins travel in one
     // 64-byte load: 10 B per entry instead of 12.  Slices that need more windows keep reading sl_col (SellHdr::coded).
-    unsigned *sl_code = nullptr;       // [sum of ceil(w / 2) * 64] pairs of codes, pair-major per slice: [k / 2][64 lanes]; slice s starts at sl_hdr[s].coff
+    DevArr<unsigned> sl_code;       // [sum of ceil(w / 2) * 64] pairs of codes, pair-major per slice: [k / 2][64 lanes]; slice s starts at sl_hdr[s].coff
     double sl_frac16 = 0.0;            // fraction of the slices that are coded
     long sl_entries = 0;           // padded entries stored
     int sl_lo = 0, sl_hi = 0;      // rows the sliced form covers (all of them; a partitioned level: its interior rows)
-    double *st_vals = nullptr;     // [nblocks256 * st_nu * 256]
-    void *st_mask = nullptr;       // [nrows] uint8 when |U| <= 7, else uint32; top bit = row not covered
+    DevArr<double> st_vals;     // [nblocks256 * st_nu * 256]
+    DevArr<void> st_mask;       // [nrows] uint8 when |U| <= 7, else uint32; top bit = row not covered
     int st_nu = 0;                 // |U|
     // Rows that use a rare offset (halo columns of a rank-local operator, a few irregular rows) are
     // left out of the stencil form instead of widening U for everybody: up to STENCIL_RANGES
@@ -100,8 +80,8 @@ struct DevCsr {
     // Value index on top of the stencil form (automatic since r3, amg_hier_value_index / amg_set_value_index): when the operator holds at
     // most 255 distinct values (constant-coefficient stencils), slot u of row i stores a one-byte code
     // into a dictionary kept in LDS instead of the 8-byte value -- the product uses the very same double.
-    unsigned char *st_codes = nullptr;   // 8 slots per 64-bit word: [nblocks256][ceil(st_nu / 8)][256] words
-    double *st_dict = nullptr;           // [256]
+    DevArr<unsigned char> st_codes;   // 8 slots per 64-bit word: [nblocks256][ceil(st_nu / 8)][256] words
+    DevArr<double> st_dict;           // [256]
     int st_ndict = 0;
     bool st_vi_on = false;
     // 16-bit column codes for csr_stream_kernel (irregular operators: coarse A_l, P_l, R_l).  The
@@ -109,9 +89,9 @@ struct DevCsr {
     // aligned windows of 4096 columns cover them, entry k is stored as (window slot << 12) | (column
     // & 4095) and the 16 window origins sit in LDS: 2 B per entry instead of 4.  Workgroups that
     // need more windows keep reading Aj (flag per workgroup).  Same columns, same order, same bits.
-    unsigned short *Aj16 = nullptr;    // [nnz]
-    int *wg_base = nullptr;            // [nwg * 16]
-    unsigned char *wg_flag = nullptr;  // [nwg] 1 = this workgroup's entries are coded
+    DevArr<unsigned short> Aj16;    // [nnz]
+    DevArr<int> wg_base;            // [nwg * 16]
+    DevArr<unsigned char> wg_flag;  // [nwg] 1 = this workgroup's entries are coded
     int i16_rpb = 0;                   // rows per workgroup the coding was built for
     double i16_frac = 0.0;             // fraction of the entries that are coded
     int st_u0 = -1;                // slot of offset 0 (the diagonal), -1 if absent
@@ -123,7 +103,7 @@ struct DevCsr {
     int l0_nx = 0, l0_ny = 0, l0_nz = 0;
     // Plane flags of an l0_ok operator (launch_level0_plane_scan): l0_same[z] = 1 iff every column's
     // code word on plane z equals the one on plane z - 1 (l0_same[0] = 0); the chains then keep the word in a register.
-    unsigned char *l0_same = nullptr;    // [l0_nz], read as 32-bit words
+    DevArr<unsigned char> l0_same;    // [l0_nz], read as 32-bit words
     int l0_nsame = 0;                    // planes whose flag is set
     long l0_code_planes[2] = {0, 0};     // planes on which a chain of 2 / 3 stages loads code words, summed over the z chunks
 };
@@ -136,18 +116,18 @@ constexpr int PAT_DICT_MAX = 2048; // total offsets in the dictionary
 struct DevBsr {   // block rows, for the block / point-BSR relaxation kernels
     int nbrows = 0, bs = 1;
     long nblocks = 0;
-    int *Ap = nullptr;
-    int *Aj = nullptr;
-    double *Ax = nullptr;
+    DevArr<int> Ap;
+    DevArr<int> Aj;
+    DevArr<double> Ax;
     // Sliced form of the block operator (sell.hip build_bsell; bs = 2, 3): block rows sorted by block count inside
     // windows, slices of 64 / bs block rows, one lane per SCALAR row; block k of the slice's rows side by side
     // (columns [k][block row], values [k][c][lane]).  Whole passes (operator applications, block Jacobi sweeps) run
     // from it without row pointer, LDS or barrier; same summation order, same bits as bsr_stream_kernel.
-    int *bsl_brow = nullptr;           // [nslices * (64 / bs)] block row of the slot (-1: padding)
-    unsigned short *bsl_len = nullptr; // blocks of that block row
-    long *bsl_off = nullptr;           // [nslices + 1] first block SLOT COLUMN of the slice: slice s holds (off[s+1]-off[s]) blocks per row
-    int *bsl_col = nullptr;            // [off[nslices] * (64 / bs)]
-    double *bsl_val = nullptr;         // [off[nslices] * bs * (64 / bs) * bs]
+    DevArr<int> bsl_brow;           // [nslices * (64 / bs)] block row of the slot (-1: padding)
+    DevArr<unsigned short> bsl_len; // blocks of that block row
+    DevArr<long> bsl_off;           // [nslices + 1] first block SLOT COLUMN of the slice: slice s holds (off[s+1]-off[s]) blocks per row
+    DevArr<int> bsl_col;            // [off[nslices] * (64 / bs)]
+    DevArr<double> bsl_val;         // [off[nslices] * bs * (64 / bs) * bs]
     int bsl_nslices = 0;
 };
 
@@ -206,7 +186,7 @@ void set_sell_index16(int on);
 bool sell_index16_enabled();              // 1 (default): sliced forms built from now on also get 16-bit column codes and the kernel reads those
 int launch_sell(StreamMode mode, const StreamArgs &a, const DevCsr &M, hipStream_t st);
 int build_sell(DevCsr &M, long *acct, int row_lo = 0, int row_hi = -1);   // from the CSR arrays already in HBM (rows [lo, hi), default all); leaves M untouched if not worth it
-void free_sell(DevCsr &M);
+void free_sell(DevCsr &M);                               // drops the sliced form alone
 int stencil_blocks(const StreamArgs &a, const DevCsr &M);   // workgroups (= SM_RESIDUAL_SUMSQ partials) of launch_stencil
 // Fused level-0 chains (DevCsr::l0_ok operators, polynomial smoothers with two coefficients):
 //   [r = b - A g0] -> x' = x + (c_last * r + A (c_gs * r)) -> [r' = b - A x'],
@@ -342,7 +322,6 @@ int launch_bsr_stream(BlockMode m, const BsrStreamArgs &a, long nblocks_hint, hi
 // the sliced block form (DevBsr::bsl_*): whole passes in BM_SPMV (epilogues MATVEC, MATVEC_ACC, RESIDUAL, POLY_STEP,
 // POLY_LAST) and BM_BLOCK_JACOBI
 int build_bsell(DevBsr &M, long *acct);
-void free_bsell(DevBsr &M);
 bool bsell_applies(const DevBsr &M, BlockMode m, const BsrStreamArgs &a);
 int launch_bsell(const DevBsr &M, BlockMode m, const BsrStreamArgs &a, hipStream_t st);
 // level-ordered copy of a block Gauss-Seidel schedule: slices cut at level boundaries, one launch per level
@@ -362,17 +341,16 @@ struct FlowForm {
     bool ready = false;
     int n = 0, ncols = 0, nchunks = 0, nlevels = 0, lpr = 1;    // ncols >= n: columns n .. ncols-1 are frozen operands (a partitioned level's halo); lpr: lanes sharing a row (1 .. 64, by the longest row: 8 slots per lane)
     long slot_rows = 0;                 // rows of 64 (value, column) pairs stored
-    int *rowmap = nullptr;              // [n] original row of level-order position k (rows of a level sorted by length)
-    FlowChunk *meta = nullptr;          // [nchunks]
-    int *col = nullptr;                 // [slot_rows * 64] operand position (n: the permanent 0.0 of padded slots)
-    double *val = nullptr;              // [slot_rows * 64]
-    double *diag = nullptr;             // [n]
-    int *gate_f = nullptr, *gate_b = nullptr;   // [n] forward / backward sweep: the row's latest operand produced at least two levels earlier (n: none)
-    double *bp = nullptr;               // [n] right-hand side in level-order numbering (gathered per application)
-    double *X = nullptr;                // [(FLOW_MAXSEQ + 1) * xstride] iterate buffers, entry n of each = 0.0
+    DevArr<int> rowmap;              // [n] original row of level-order position k (rows of a level sorted by length)
+    DevArr<FlowChunk> meta;          // [nchunks]
+    DevArr<int> col;                 // [slot_rows * 64] operand position (n: the permanent 0.0 of padded slots)
+    DevArr<double> val;              // [slot_rows * 64]
+    DevArr<double> diag;             // [n]
+    DevArr<int> gate_f, gate_b;   // [n] forward / backward sweep: the row's latest operand produced at least two levels earlier (n: none)
+    DevArr<double> bp;               // [n] right-hand side in level-order numbering (gathered per application)
+    DevArr<double> X;                // [(FLOW_MAXSEQ + 1) * xstride] iterate buffers, entry n of each = 0.0
     long xstride = 0;
     long bytes = 0;
-    void release();
 };
 // from the level-ordered copy of a schedule (host arrays): leaves F.ready false when the form does not apply
 int build_flow_form(FlowForm &F, int n, int ntasks, const std::vector<int> &level_ptr, const std::vector<int> &rowmap,
@@ -384,16 +362,15 @@ struct BlockFlowForm {
     bool ready = false;
     int nb = 0, bs = 0, nchunks = 0, nlevels = 0, lpr = 1, seg = 8;     // seg blocks per lane, lpr lanes per scalar row
     long slot_rows = 0;
-    int *rows = nullptr;                // [nb] original block row of position k
-    FlowChunk *meta = nullptr;
-    int *col = nullptr;                 // [slot_rows * (64 / bs)] block position of the slot's operand (nb: the permanent zero block)
-    double *val = nullptr;              // [slot_rows * bs * 64]: slot, column inside the block, lane
-    int *gate_f = nullptr, *gate_b = nullptr;   // [nb]
-    double *bp = nullptr;               // [nb * bs]
-    double *X = nullptr;                // [(FLOW_MAXSEQ + 1) * xstride]
+    DevArr<int> rows;                // [nb] original block row of position k
+    DevArr<FlowChunk> meta;
+    DevArr<int> col;                 // [slot_rows * (64 / bs)] block position of the slot's operand (nb: the permanent zero block)
+    DevArr<double> val;              // [slot_rows * bs * 64]: slot, column inside the block, lane
+    DevArr<int> gate_f, gate_b;   // [nb]
+    DevArr<double> bp;               // [nb * bs]
+    DevArr<double> X;                // [(FLOW_MAXSEQ + 1) * xstride]
     long xstride = 0;
     long bytes = 0;
-    void release();
 };
 int build_block_flow_form(BlockFlowForm &F, int nb, int bs, int ntasks, const std::vector<int> &level_ptr, const std::vector<int> &rows,
                           const std::vector<int> &gp, const std::vector<int> &gj, const std::vector<double> &gx);

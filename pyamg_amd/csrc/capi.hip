@@ -13,7 +13,7 @@ namespace amg {
 int upload_csr(DevCsr &M, int nrows, int ncols, const int *Ap, const int *Aj, const double *Ax, long *acct);
 int upload_bsr(DevBsr &M, int nbrows, int bs, const int *Ap, const int *Aj, const double *Ax, long *acct);
 int spmv(const DevCsr &M, StreamMode mode, const double *xg, const double *b, const double *v2,
-         double *out, double *out2, double c0, hipStream_t st);
+         double *out, double *out2, double c0, hipStream_t st, unsigned skip = 0);
 void expand_bsr(int nbrows, int R, int C, const int *Ap, const int *Aj, const double *Ax,
                 std::vector<int> &cp, std::vector<int> &cj, std::vector<double> &cx);
 }
@@ -23,29 +23,6 @@ int gs_sweep_csr(const Schedule &S, bool bsr1, double *x, const double *b, bool 
 using namespace amg;
 
 namespace {
-
-struct CsrHolder {
-    DevCsr M;
-    ~CsrHolder()
-    {
-        if (M.Ap) hipFree(M.Ap);
-        if (M.Aj) hipFree(M.Aj);
-        if (M.Ax) hipFree(M.Ax);
-    }
-};
-struct BsrHolder {
-    DevBsr M;
-    ~BsrHolder()
-    {
-        if (M.Ap) hipFree(M.Ap);
-        if (M.Aj) hipFree(M.Aj);
-        if (M.Ax) hipFree(M.Ax);
-    }
-};
-struct SchedHolder {
-    Schedule S;
-    ~SchedHolder() { S.release(); }
-};
 
 int run_csr_levels(const Schedule &S, bool bsr1, double *x, const double *b)
 {
@@ -58,12 +35,12 @@ int gs_csr_common(const int *Ap, int Ap_size, const int *Aj, const double *Ax, d
 {
     const int n = Ap_size - 1;
     if (tasks.empty()) return 0;
-    SchedHolder sh;
-    CHK(build_csr_schedule(Ap, Aj, Ax, n, tasks.data(), (int)tasks.size(), sh.S, nullptr));
+    Schedule sched;
+    CHK(build_csr_schedule(Ap, Aj, Ax, n, tasks.data(), (int)tasks.size(), sched, nullptr));
     DBuf dx, db;
     CHK(dx.from_host(x, sizeof(double) * (size_t)x_size));
     CHK(db.from_host(b, sizeof(double) * (size_t)b_size));
-    CHK(run_csr_levels(sh.S, bsr1, dx.d(), db.d()));
+    CHK(run_csr_levels(sched, bsr1, dx.d(), db.d()));
     AMG_HIP(hipDeviceSynchronize());
     if (gs_flow_status() != 0) { set_error("a dataflow Gauss-Seidel sweep ran out of its time budget"); return AMG_ESTATE; }
     return dx.to_host(x, sizeof(double) * (size_t)x_size);
@@ -115,14 +92,14 @@ int amgcore_bsr_gauss_seidel_f64(const int Ap[], int Ap_size, const int Aj[], in
     CHK(sweep_rows(row_start, row_stop, row_step, std::min(nb, std::min(x_size, b_size) / blocksize), tasks));
     if (tasks.empty()) return 0;
     if (blocksize == 1) return gs_csr_common(Ap, Ap_size, Aj, Ax, x, x_size, b, b_size, tasks, true);
-    SchedHolder sh;
-    CHK(build_block_schedule(Ap, Aj, nb, tasks.data(), (int)tasks.size(), sh.S, nullptr, Ax, blocksize));
+    Schedule sched;
+    CHK(build_block_schedule(Ap, Aj, nb, tasks.data(), (int)tasks.size(), sched, nullptr, Ax, blocksize));
     DBuf dx, db;
     CHK(dx.from_host(x, sizeof(double) * (size_t)x_size));
     CHK(db.from_host(b, sizeof(double) * (size_t)b_size));
     // the task list is already in sweep order: levels ascending; a backward sweep reverses the order inside a block
     {
-        Schedule &S = sh.S;
+        Schedule &S = sched;
         BsrStreamArgs a;
         std::memset(&a, 0, sizeof(a));
         a.Ap = S.Gb.Ap; a.Aj = S.Gb.Aj; a.Ax = S.Gb.Ax; a.bs = blocksize; a.rowmap = S.rows;
@@ -149,8 +126,8 @@ int amgcore_jacobi_f64(const int Ap[], int Ap_size, const int Aj[], int Aj_size,
     std::vector<int> rows;
     CHK(sweep_rows(row_start, row_stop, row_step, std::min(n, std::min(std::min(x_size, b_size), temp_size)), rows));
     if (rows.empty()) return 0;
-    CsrHolder ch;
-    CHK(upload_csr(ch.M, n, n, Ap, Aj, Ax, nullptr));
+    DevCsr M;
+    CHK(upload_csr(M, n, n, Ap, Aj, Ax, nullptr));
     DBuf dx, db, dt;
     CHK(dx.from_host(x, sizeof(double) * (size_t)x_size));
     CHK(db.from_host(b, sizeof(double) * (size_t)b_size));
@@ -160,14 +137,14 @@ int amgcore_jacobi_f64(const int Ap[], int Ap_size, const int Aj[], int Aj_size,
     if (row_step == 1 || row_step == -1) {
         StreamArgs a;
         std::memset(&a, 0, sizeof(a));
-        a.Ap = ch.M.Ap; a.Aj = ch.M.Aj; a.Ax = ch.M.Ax; a.nnz_total = ch.M.nnz;
-        a.rows_per_wg = rows_per_wg_for(ch.M.nnz, ch.M.nrows);
+        a.Ap = M.Ap; a.Aj = M.Aj; a.Ax = M.Ax; a.nnz_total = M.nnz;
+        a.rows_per_wg = rows_per_wg_for(M.nnz, M.nrows);
         a.row_lo = (row_step == 1) ? row_start : row_stop + 1;
         a.row_hi = (row_step == 1) ? row_stop : row_start + 1;
         a.xg = dt.d(); a.v2 = dt.d(); a.b = db.d(); a.out = dx.d(); a.c0 = omega[0];
         CHK(launch_stream(SM_JACOBI, a, nullptr));
     } else {
-        CHK(launch_jacobi_rows(ch.M, dt.d(), db.d(), dx.d(), row_start, count, row_step, omega[0], nullptr));
+        CHK(launch_jacobi_rows(M, dt.d(), db.d(), dx.d(), row_start, count, row_step, omega[0], nullptr));
     }
     AMG_HIP(hipDeviceSynchronize());
     CHK(dx.to_host(x, sizeof(double) * (size_t)x_size));
@@ -192,8 +169,8 @@ int amgcore_bsr_jacobi_f64(const int Ap[], int Ap_size, const int Aj[], int Aj_s
     std::vector<int> rows;
     CHK(sweep_rows(row_start, row_stop, row_step, std::min(nb, std::min(std::min(x_size, b_size), temp_size) / blocksize), rows));
     if (rows.empty()) return 0;
-    SchedHolder sh;          // the listed block rows, copied in list order: one streamed slice
-    CHK(build_block_schedule(Ap, Aj, nb, rows.data(), (int)rows.size(), sh.S, nullptr, Ax, blocksize, true));
+    Schedule sched;          // the listed block rows, copied in list order: one streamed slice
+    CHK(build_block_schedule(Ap, Aj, nb, rows.data(), (int)rows.size(), sched, nullptr, Ax, blocksize, true));
     DBuf dx, db, dt;
     CHK(dx.from_host(x, sizeof(double) * (size_t)x_size));
     CHK(db.from_host(b, sizeof(double) * (size_t)b_size));
@@ -201,7 +178,7 @@ int amgcore_bsr_jacobi_f64(const int Ap[], int Ap_size, const int Aj[], int Aj_s
     long ncopy = (long)std::abs(row_stop - row_start) * blocksize;     // relaxation.h:303-305
     if (ncopy > std::min(x_size, temp_size)) { set_error("temp/x too short"); return AMG_EINVAL; }
     AMG_HIP(hipMemcpy(dt.p, dx.p, sizeof(double) * (size_t)ncopy, hipMemcpyDeviceToDevice));
-    CHK(sweep_block_schedule(sh.S, BM_BSR_JACOBI, nullptr, dt.d(), dx.d(), db.d(), omega[0], false, nullptr));
+    CHK(sweep_block_schedule(sched, BM_BSR_JACOBI, nullptr, dt.d(), dx.d(), db.d(), omega[0], false, nullptr));
     AMG_HIP(hipDeviceSynchronize());
     CHK(dx.to_host(x, sizeof(double) * (size_t)x_size));
     return dt.to_host(temp, sizeof(double) * (size_t)temp_size);
@@ -222,8 +199,8 @@ int amgcore_block_jacobi_f64(const int Ap[], int Ap_size, const int Aj[], int Aj
     CHK(sweep_rows(row_start, row_stop, row_step, std::min(nb, std::min(std::min(x_size, b_size), temp_size) / blocksize), rows));
     if (rows.empty()) return 0;
     if ((long)nb * blocksize * blocksize > Tx_size) { set_error("Dinv too short"); return AMG_EINVAL; }
-    SchedHolder sh;
-    CHK(build_block_schedule(Ap, Aj, nb, rows.data(), (int)rows.size(), sh.S, nullptr, Ax, blocksize, true));
+    Schedule sched;
+    CHK(build_block_schedule(Ap, Aj, nb, rows.data(), (int)rows.size(), sched, nullptr, Ax, blocksize, true));
     DBuf dx, db, dt, dd, dr;
     CHK(dx.from_host(x, sizeof(double) * (size_t)x_size));
     CHK(db.from_host(b, sizeof(double) * (size_t)b_size));
@@ -240,7 +217,7 @@ int amgcore_block_jacobi_f64(const int Ap[], int Ap_size, const int Aj[], int Aj
             AMG_HIP(hipMemcpyAsync(dt.d() + (long)r * blocksize, dx.d() + (long)r * blocksize,
                                    sizeof(double) * (size_t)blocksize, hipMemcpyDeviceToDevice, nullptr));
     }
-    CHK(sweep_block_schedule(sh.S, BM_BLOCK_JACOBI, dd.d(), dt.d(), dx.d(), db.d(), omega[0], false, nullptr));
+    CHK(sweep_block_schedule(sched, BM_BLOCK_JACOBI, dd.d(), dt.d(), dx.d(), db.d(), omega[0], false, nullptr));
     AMG_HIP(hipDeviceSynchronize());
     CHK(dx.to_host(x, sizeof(double) * (size_t)x_size));
     return dt.to_host(temp, sizeof(double) * (size_t)temp_size);
@@ -259,14 +236,14 @@ int amgcore_block_gauss_seidel_f64(const int Ap[], int Ap_size, const int Aj[], 
     CHK(sweep_rows(row_start, row_stop, row_step, std::min(nb, std::min(x_size, b_size) / blocksize), tasks));
     if (tasks.empty()) return 0;
     if ((long)nb * blocksize * blocksize > Tx_size) { set_error("Dinv too short"); return AMG_EINVAL; }
-    SchedHolder sh;
-    CHK(build_block_schedule(Ap, Aj, nb, tasks.data(), (int)tasks.size(), sh.S, nullptr, Ax, blocksize, false, true));
+    Schedule sched;
+    CHK(build_block_schedule(Ap, Aj, nb, tasks.data(), (int)tasks.size(), sched, nullptr, Ax, blocksize, false, true));
     DBuf dx, db, dd;
     CHK(dx.from_host(x, sizeof(double) * (size_t)x_size));
     CHK(db.from_host(b, sizeof(double) * (size_t)b_size));
     CHK(dd.from_host(Tx, sizeof(double) * (size_t)Tx_size));
     const unsigned char fwd = 0;
-    CHK(block_gs_sweeps(sh.S, dd.d(), dx.d(), db.d(), &fwd, 1, nullptr));
+    CHK(block_gs_sweeps(sched, dd.d(), dx.d(), db.d(), &fwd, 1, nullptr));
     AMG_HIP(hipDeviceSynchronize());
     if (gs_flow_status() != 0) { set_error("a dataflow block Gauss-Seidel sweep ran out of its time budget"); return AMG_ESTATE; }
     return dx.to_host(x, sizeof(double) * (size_t)x_size);
@@ -277,12 +254,12 @@ int amgcore_csr_matvec_f64(int n_row, int n_col, const int Ap[], const int Aj[],
 {
     CHK(require_device());
     if (n_row < 0 || n_col < 0 || !Ap) { set_error("bad csr_matvec arguments"); return AMG_EINVAL; }
-    CsrHolder ch;
-    CHK(upload_csr(ch.M, n_row, n_col, Ap, Aj, Ax, nullptr));
+    DevCsr M;
+    CHK(upload_csr(M, n_row, n_col, Ap, Aj, Ax, nullptr));
     DBuf dx, dy;
     CHK(dx.from_host(x, sizeof(double) * (size_t)n_col));
     CHK(dy.from_host(y, sizeof(double) * (size_t)n_row));
-    CHK(spmv(ch.M, SM_MATVEC_ACC, dx.d(), nullptr, nullptr, dy.d(), nullptr, 0.0, nullptr));
+    CHK(spmv(M, SM_MATVEC_ACC, dx.d(), nullptr, nullptr, dy.d(), nullptr, 0.0, nullptr));
     AMG_HIP(hipDeviceSynchronize());
     return dy.to_host(y, sizeof(double) * (size_t)n_row);
 }

@@ -3,7 +3,6 @@
 // row-partitioned multi-GPU driver (pyamg_amd/distributed.py) is built from: its vectors are
 // torch tensors so that torch.distributed (RCCL) can move the halos.
 #include "hier.hpp"
-#include "driver.hpp"
 
 #include <cstdlib>
 #include <cstring>
@@ -13,8 +12,7 @@ int upload_csr(DevCsr &M, int nrows, int ncols, const int *Ap, const int *Aj, co
 int gs_sweep_csr(const Schedule &S, bool bsr1, double *x, const double *b, bool reverse, hipStream_t st, bool allow_flow = true);
 int gs_sweep_csr(const Schedule &S, bool bsr1, double *x, const double *b, const unsigned char *seq, int nseq, hipStream_t st, bool allow_flow = true);
 int try_patterns(DevCsr &M, const int *Ap, const int *Aj, long *acct);
-int apply_operator(const DevCsr &M, StreamMode mode, const StreamArgs &a, hipStream_t st);
-void free_csr(DevCsr &M);
+int apply_operator(const DevCsr &M, StreamMode mode, const StreamArgs &a, hipStream_t st, unsigned skip = 0);
 int build_index16(DevCsr &M, const int *Ap_host, long *acct);
 }
 using namespace amg;
@@ -23,7 +21,7 @@ struct amg_mat {
     int device = 0;
     DevCsr M;
     int rpw = 256;
-    Schedule *sched = nullptr;     // Gauss-Seidel over the local rows (amg_mat_build_gs)
+    std::unique_ptr<Schedule> sched;   // Gauss-Seidel over the local rows (amg_mat_build_gs)
 };
 
 __global__ void gather_kernel(double *out, const double *in, const int *idx, long n)
@@ -47,8 +45,8 @@ amg_mat *amg_mat_create(int device, int nrows, int ncols, const int *Ap, const i
     m->device = device;
     if (upload_csr(m->M, nrows, ncols, Ap, Aj, Ax, nullptr) != 0) { delete m; return nullptr; }
     // structured-grid operators (also rank-local ones with a halo) get the pattern / stencil forms
-    if (Aj && try_patterns(m->M, Ap, Aj, nullptr) != 0) { free_csr(m->M); delete m; return nullptr; }
-    if (Aj && build_index16(m->M, Ap, nullptr) != 0) { free_csr(m->M); delete m; return nullptr; }
+    if (Aj && try_patterns(m->M, Ap, Aj, nullptr) != 0) { delete m; return nullptr; }
+    if (Aj && build_index16(m->M, Ap, nullptr) != 0) { delete m; return nullptr; }
     m->rpw = rows_per_wg_for(m->M.nnz, m->M.nrows);
     return m;
 }
@@ -64,8 +62,6 @@ void amg_mat_destroy(amg_mat *m)
 {
     if (!m) return;
     hipSetDevice(m->device);
-    free_csr(m->M);
-    if (m->sched) { m->sched->release(); delete m->sched; }
     delete m;
 }
 
@@ -85,13 +81,13 @@ int amg_mat_build_gs(amg_mat *m, const int *order, int norder)
         AMG_HIP(hipMemcpy(aj.data(), m->M.Aj, sizeof(int) * aj.size(), hipMemcpyDeviceToHost));
         AMG_HIP(hipMemcpy(ax.data(), m->M.Ax, sizeof(double) * ax.size(), hipMemcpyDeviceToHost));
     }
-    if (m->sched) { m->sched->release(); delete m->sched; m->sched = nullptr; }
-    m->sched = new Schedule();
+    m->sched.reset();
+    m->sched.reset(new Schedule());
     // halo columns (ncols > nrows) mean a rank of a partitioned solve: dataflow sweeps only where ranks do not share a device
     const char *df = std::getenv("AMG_DIST_FLOW");
     const bool allow_flow = m->M.ncols == n || (df && std::atoi(df) != 0);
     int rc = build_csr_schedule(ap.data(), aj.data(), ax.data(), n, order, order ? norder : n, *m->sched, nullptr, allow_flow, m->M.ncols);
-    if (rc != 0) { m->sched->release(); delete m->sched; m->sched = nullptr; }
+    if (rc != 0) m->sched.reset();
     return rc;
 }
 

@@ -2,7 +2,7 @@
 // capi.hip (float64) and typed.hip (float32 / complex64 / complex128): argument checks and the row
 // list of a sweep.  The owning device buffer they stage their operands in is driver.hpp's.
 #pragma once
-#include "driver.hpp"
+#include "amg_dev.hpp"
 #include "../../include/amgcore_hip.h"
 
 #include <vector>

@@ -30,7 +30,6 @@
 // spin is bounded by a wall-clock budget measured from the wave's start; a wave that runs out of it raises the
 // status flag and leaves, and so does everybody who waits for it (gs_flow_status()).
 #include "hier.hpp"
-#include "driver.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -78,11 +77,10 @@ constexpr int FLOW_SEG = AMG_FLOW_SEG;          // slots a lane owns at most: a 
         if (rc__ != 0) return rc__; \
     } while (0)
 
-template <class T> int falloc(T **p, long count, long *acct)
+template <class T> int falloc(DevArr<T> &p, long count, long *acct)
 {
-    *p = nullptr;
     if (count <= 0) count = 1;
-    hipError_t e = hipMalloc((void **)p, sizeof(T) * (size_t)count);
+    hipError_t e = p.malloc_bytes(sizeof(T) * (size_t)count);
     if (e != hipSuccess) return hip_fail(e, "hipMalloc (dataflow Gauss-Seidel form)", __FILE__, __LINE__);
     if (acct) *acct += (long)(sizeof(T) * (size_t)count);
     return 0;
@@ -701,7 +699,7 @@ __global__ __launch_bounds__(256) void nat_fill_kernel(unsigned long long *p, lo
 
 int g_flow_mode = std::getenv("AMG_GS_FLOW") ? std::atoi(std::getenv("AMG_GS_FLOW")) : 1;   // A/B runs of tools without a knob of their own
 int g_flow_la = 0;              // look-ahead in levels; 0: default
-int *g_status = nullptr;        // device word, one per process and device (first use)
+int *g_status = nullptr;        // device word, one per process and device (first use); it lives as long as the process
 int g_status_dev = -1;
 
 int flow_status_word(int **out)
@@ -710,8 +708,10 @@ int flow_status_word(int **out)
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return hip_fail(e, "hipGetDevice", __FILE__, __LINE__);
     if (!g_status || g_status_dev != dev) {
-        e = hipMalloc((void **)&g_status, 64);
+        DevArr<int> word;
+        e = word.malloc_bytes(64);
         if (e != hipSuccess) return hip_fail(e, "hipMalloc (dataflow status word)", __FILE__, __LINE__);
+        g_status = word.release();
         e = hipMemset(g_status, 0, 64);
         if (e != hipSuccess) return hip_fail(e, "hipMemset", __FILE__, __LINE__);
         g_status_dev = dev;
@@ -815,21 +815,12 @@ int launch_bflow_bs(const BlockFlowForm &F, const BlockFlowArgs &a, hipStream_t 
 
 }  // namespace
 
-void BlockFlowForm::release()
-{
-    for (void *p : {(void *)rows, (void *)meta, (void *)col, (void *)val, (void *)bp, (void *)X, (void *)gate_f, (void *)gate_b})
-        if (p) hipFree(p);
-    rows = nullptr; meta = nullptr; col = nullptr; val = nullptr; bp = nullptr; X = nullptr; gate_f = gate_b = nullptr;
-    ready = false;
-    bytes = 0;
-}
-
 // rows / gp / gj / gx: the block schedule's level-ordered copy (block row k of it = original block row rows[k], ORIGINAL
 // block columns, blocks row-major)
 int build_block_flow_form(BlockFlowForm &F, int nb, int bs, int ntasks, const std::vector<int> &level_ptr, const std::vector<int> &rows,
                           const std::vector<int> &gp, const std::vector<int> &gj, const std::vector<double> &gx)
 {
-    F.release();
+    F = BlockFlowForm();
     const int nl = (int)level_ptr.size() - 1;
     if (nb <= 0 || ntasks != nb || nl <= 0 || (bs != 2 && bs != 3)) return 0;
     if ((double)nb * bs * (FLOW_MAXSEQ + 1) >= 2.0e9) return 0;
@@ -924,14 +915,14 @@ int build_block_flow_form(BlockFlowForm &F, int nb, int bs, int ntasks, const st
     F.nb = nb; F.nchunks = (int)meta.size(); F.nlevels = nl; F.slot_rows = slot_rows;
     F.xstride = ((long)(nb + 1) * bs + 15) / 16 * 16;
     long acct = 0;
-    FCHK(falloc(&F.rows, nb, &acct));
-    FCHK(falloc(&F.meta, (long)meta.size(), &acct));
-    FCHK(falloc(&F.col, (long)ncol, &acct));
-    FCHK(falloc(&F.val, (long)nval, &acct));
-    FCHK(falloc(&F.bp, (long)nb * bs, &acct));
-    FCHK(falloc(&F.gate_f, nb, &acct));
-    FCHK(falloc(&F.gate_b, nb, &acct));
-    FCHK(falloc(&F.X, (FLOW_MAXSEQ + 1) * F.xstride, &acct));
+    FCHK(falloc(F.rows, nb, &acct));
+    FCHK(falloc(F.meta, (long)meta.size(), &acct));
+    FCHK(falloc(F.col, (long)ncol, &acct));
+    FCHK(falloc(F.val, (long)nval, &acct));
+    FCHK(falloc(F.bp, (long)nb * bs, &acct));
+    FCHK(falloc(F.gate_f, nb, &acct));
+    FCHK(falloc(F.gate_b, nb, &acct));
+    FCHK(falloc(F.X, (FLOW_MAXSEQ + 1) * F.xstride, &acct));
     AMG_HIP(hipMemcpy(F.rows, rmap.data(), sizeof(int) * (size_t)nb, hipMemcpyHostToDevice));
     AMG_HIP(hipMemcpy(F.meta, meta.data(), sizeof(FlowChunk) * meta.size(), hipMemcpyHostToDevice));
     AMG_HIP(hipMemcpy(F.col, col.get(), sizeof(int) * ncol, hipMemcpyHostToDevice));
@@ -951,12 +942,12 @@ int block_flow_sweep(const BlockFlowForm &F, const double *Dinv, double *x, cons
     for (int s0 = 0; s0 < nseq; s0 += FLOW_MAXSEQ) {
         const int ns = std::min(FLOW_MAXSEQ, nseq - s0);
         const long np = (long)(F.nb + 1) * F.bs;
-        if (F.bs == 3) hipLaunchKernelGGL((bflow_gather_kernel<3>), dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, F.rows, x, b, (unsigned long long *)F.X, F.bp, F.xstride, F.nb, ns);
-        else hipLaunchKernelGGL((bflow_gather_kernel<2>), dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, F.rows, x, b, (unsigned long long *)F.X, F.bp, F.xstride, F.nb, ns);
+        if (F.bs == 3) hipLaunchKernelGGL((bflow_gather_kernel<3>), dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, F.rows, x, b, F.X.as<unsigned long long>(), F.bp, F.xstride, F.nb, ns);
+        else hipLaunchKernelGGL((bflow_gather_kernel<2>), dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, F.rows, x, b, F.X.as<unsigned long long>(), F.bp, F.xstride, F.nb, ns);
         LAUNCH_CHECK("dataflow block gather launch");
         BlockFlowArgs a;
         std::memset(&a, 0, sizeof(a));
-        a.X = (unsigned long long *)F.X; a.x_out = x; a.Dinv = Dinv; a.status = status;
+        a.X = F.X.as<unsigned long long>(); a.x_out = x; a.Dinv = Dinv; a.status = status;
         a.xstride = F.xstride; a.budget = 100000000LL * 4;
         a.nchunks = F.nchunks; a.nseq = ns; a.nb = F.nb;
         a.xcd = flow_xcd(true);
@@ -992,8 +983,8 @@ int gs_natural_sweeps(const int *Ap, const int *Aj, const double *Ax, int n, int
         if (std::getenv("AMG_SETUP_VERBOSE") && std::atoi(std::getenv("AMG_SETUP_VERBOSE")))
             std::fprintf(stderr, "[setup]     natural-order Gauss-Seidel: %d one-wave workgroups (occupancy query %d per CU, %d CUs)\n", cap, nb, ncu);
     }
-    double *tmp = nullptr;
-    hipError_t e = hipMalloc((void **)&tmp, sizeof(double) * (size_t)n);
+    DevArr<double> tmp;
+    hipError_t e = tmp.malloc_bytes(sizeof(double) * (size_t)n);
     if (e != hipSuccess) return hip_fail(e, "hipMalloc (natural-order Gauss-Seidel buffer)", __FILE__, __LINE__);
     double *cur = x, *nxt = tmp;
     const int ntasks = (n + 63) / 64;
@@ -1007,25 +998,14 @@ int gs_natural_sweeps(const int *Ap, const int *Aj, const double *Ax, int n, int
         a.ntasks = a.tstart ? (a.reverse ? ntasks_bwd : ntasks_fwd) : ntasks;
         hipLaunchKernelGGL(gs_natural_kernel, dim3((unsigned)std::min(cap, a.ntasks)), dim3(64), 0, st, a);
         e = hipGetLastError();
-        if (e != hipSuccess) { hipFree(tmp); return hip_fail(e, "natural-order Gauss-Seidel launch", __FILE__, __LINE__); }
+        if (e != hipSuccess) return hip_fail(e, "natural-order Gauss-Seidel launch", __FILE__, __LINE__);
         std::swap(cur, nxt);
     }
     if (cur != x) e = hipMemcpyAsync(x, cur, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st);
     hipError_t e2 = hipStreamSynchronize(st);
-    hipFree(tmp);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync", __FILE__, __LINE__);
     if (e2 != hipSuccess) return hip_fail(e2, "hipStreamSynchronize", __FILE__, __LINE__);
     return 0;
-}
-
-void FlowForm::release()
-{
-    for (void *p : {(void *)rowmap, (void *)meta, (void *)col, (void *)val, (void *)diag, (void *)bp, (void *)X, (void *)gate_f, (void *)gate_b})
-        if (p) hipFree(p);
-    gate_f = gate_b = nullptr;
-    rowmap = nullptr; meta = nullptr; col = nullptr; val = nullptr; diag = nullptr; bp = nullptr; X = nullptr;
-    ready = false;
-    bytes = 0;
 }
 
 int gs_flow_mode() { return g_flow_mode; }
@@ -1045,7 +1025,7 @@ int gs_flow_status()
 int build_flow_form(FlowForm &F, int n, int ntasks, const std::vector<int> &level_ptr, const std::vector<int> &rowmap,
                     const std::vector<int> &gp, const std::vector<int> &gj, const std::vector<double> &gx, int ncols)
 {
-    F.release();
+    F = FlowForm();
     const int nl = (int)level_ptr.size() - 1;
     if (ncols < n) ncols = n;
     if (n <= 0 || ntasks != n || nl <= 0) return 0;
@@ -1162,15 +1142,15 @@ int build_flow_form(FlowForm &F, int n, int ntasks, const std::vector<int> &leve
     F.n = n; F.ncols = ncols; F.nchunks = (int)meta.size(); F.nlevels = nl; F.slot_rows = slot_rows;
     F.xstride = ((long)ncols + 1 + 15) / 16 * 16;
     long acct = 0;
-    FCHK(falloc(&F.rowmap, n, &acct));
-    FCHK(falloc(&F.meta, (long)meta.size(), &acct));
-    FCHK(falloc(&F.col, slot_rows * 64, &acct));
-    FCHK(falloc(&F.val, slot_rows * 64, &acct));
-    FCHK(falloc(&F.diag, n, &acct));
-    FCHK(falloc(&F.bp, n, &acct));
-    FCHK(falloc(&F.gate_f, n, &acct));
-    FCHK(falloc(&F.gate_b, n, &acct));
-    FCHK(falloc(&F.X, (FLOW_MAXSEQ + 1) * F.xstride, &acct));
+    FCHK(falloc(F.rowmap, n, &acct));
+    FCHK(falloc(F.meta, (long)meta.size(), &acct));
+    FCHK(falloc(F.col, slot_rows * 64, &acct));
+    FCHK(falloc(F.val, slot_rows * 64, &acct));
+    FCHK(falloc(F.diag, n, &acct));
+    FCHK(falloc(F.bp, n, &acct));
+    FCHK(falloc(F.gate_f, n, &acct));
+    FCHK(falloc(F.gate_b, n, &acct));
+    FCHK(falloc(F.X, (FLOW_MAXSEQ + 1) * F.xstride, &acct));
     AMG_HIP(hipMemcpy(F.rowmap, rmap.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
     AMG_HIP(hipMemcpy(F.meta, meta.data(), sizeof(FlowChunk) * meta.size(), hipMemcpyHostToDevice));
     if (slot_rows > 0) {
@@ -1194,11 +1174,11 @@ int gs_flow_sweep(const FlowForm &F, bool bsr1, double *x, const double *b, cons
     for (int s0 = 0; s0 < nseq; s0 += FLOW_MAXSEQ) {
         const int ns = std::min(FLOW_MAXSEQ, nseq - s0);
         hipLaunchKernelGGL(flow_gather_kernel, dim3((unsigned)((F.ncols + 1 + 255) / 256)), dim3(256), 0, st, F.rowmap, x, b,
-                           (unsigned long long *)F.X, F.bp, F.xstride, F.n, F.ncols, ns);
+                           F.X.as<unsigned long long>(), F.bp, F.xstride, F.n, F.ncols, ns);
         LAUNCH_CHECK("dataflow gather launch");
         FlowArgs a;
         std::memset(&a, 0, sizeof(a));
-        a.X = (unsigned long long *)F.X; a.x_out = x; a.status = status;
+        a.X = F.X.as<unsigned long long>(); a.x_out = x; a.status = status;
         a.xstride = F.xstride; a.budget = 100000000LL * 4;                   // 4 s of the 100 MHz wall clock
         a.nchunks = F.nchunks; a.nseq = ns; a.n = F.ncols;          // position of the permanent 0.0
         a.xcd = flow_xcd(false);

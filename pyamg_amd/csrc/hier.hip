@@ -26,44 +26,18 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line)
 }
 
 // ------------------------------------------------------------------ memory
-template <class T> static int dev_alloc(T **p, long count, long *acct)
+std::atomic<long> dev_live{0};
+
+template <class T> static int dev_alloc(DevArr<T> &p, long count, long *acct)
 {
     size_t bytes = sizeof(T) * (size_t)(count + PAD);
-    AMG_HIP(hipMalloc((void **)p, bytes));
-    AMG_HIP(hipMemset(*p, 0, bytes));
+    AMG_HIP(p.malloc_bytes(bytes));
+    AMG_HIP(hipMemset(p, 0, bytes));
     // the fill runs on the NULL stream and is asynchronous to the host; the hierarchy's stream is
     // non-blocking, so without this wait a later copy/kernel on it could be overtaken by the fill
     AMG_HIP(hipDeviceSynchronize());
     if (acct) *acct += (long)bytes;
     return 0;
-}
-
-void free_csr(DevCsr &M)
-{
-    if (M.Ap) hipFree(M.Ap);
-    if (M.Aj) hipFree(M.Aj);
-    if (M.Ax) hipFree(M.Ax);
-    if (M.pat) hipFree(M.pat);
-    if (M.dict_ptr) hipFree(M.dict_ptr);
-    if (M.dict_off) hipFree(M.dict_off);
-    free_sell(M);
-    if (M.st_vals) hipFree(M.st_vals);
-    if (M.st_mask) hipFree(M.st_mask);
-    if (M.st_codes) hipFree(M.st_codes);
-    if (M.st_dict) hipFree(M.st_dict);
-    if (M.l0_same) hipFree(M.l0_same);
-    if (M.Aj16) hipFree(M.Aj16);
-    if (M.wg_base) hipFree(M.wg_base);
-    if (M.wg_flag) hipFree(M.wg_flag);
-    M = DevCsr();
-}
-static void free_bsr(DevBsr &M)
-{
-    free_bsell(M);
-    if (M.Ap) hipFree(M.Ap);
-    if (M.Aj) hipFree(M.Aj);
-    if (M.Ax) hipFree(M.Ax);
-    M = DevBsr();
 }
 
 int upload_csr(DevCsr &M, int nrows, int ncols, const int *Ap, const int *Aj, const double *Ax,
@@ -72,9 +46,9 @@ int upload_csr(DevCsr &M, int nrows, int ncols, const int *Ap, const int *Aj, co
     long nnz = Ap[nrows];
     if (nnz < 0 || nrows < 0) { set_error("row pointer overflows int32 (more than 2^31-1 stored entries)"); return AMG_EINVAL; }
     M.nrows = nrows; M.ncols = ncols; M.nnz = nnz;
-    CHK(dev_alloc(&M.Ap, nrows + 1, acct));
-    CHK(dev_alloc(&M.Aj, nnz, acct));
-    CHK(dev_alloc(&M.Ax, nnz, acct));
+    CHK(dev_alloc(M.Ap, nrows + 1, acct));
+    CHK(dev_alloc(M.Aj, nnz, acct));
+    CHK(dev_alloc(M.Ax, nnz, acct));
     AMG_HIP(hipMemcpy(M.Ap, Ap, sizeof(int) * (size_t)(nrows + 1), hipMemcpyHostToDevice));
     if (nnz) {
         AMG_HIP(hipMemcpy(M.Aj, Aj, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice));
@@ -93,9 +67,9 @@ int build_index16(DevCsr &M, const int *Ap_host, long *acct)
     const int rpb = rows_per_wg_for(M.nnz, M.nrows);
     const int nwg = (M.nrows + rpb - 1) / rpb;
     long before = acct ? *acct : 0;
-    CHK(dev_alloc(&M.Aj16, M.nnz, acct));
-    CHK(dev_alloc(&M.wg_base, (long)nwg * 16, acct));
-    CHK(dev_alloc(&M.wg_flag, nwg, acct));
+    CHK(dev_alloc(M.Aj16, M.nnz, acct));
+    CHK(dev_alloc(M.wg_base, (long)nwg * 16, acct));
+    CHK(dev_alloc(M.wg_flag, nwg, acct));
     M.i16_rpb = rpb;
     int rc = launch_index16_build(M, rpb, 0);
     AMG_HIP(hipDeviceSynchronize());
@@ -109,8 +83,7 @@ int build_index16(DevCsr &M, const int *Ap_host, long *acct)
         }
     M.i16_frac = M.nnz ? coded / (double)M.nnz : 0.0;
     if (rc != 0 || M.i16_frac < 0.3) {
-        hipFree(M.Aj16); hipFree(M.wg_base); hipFree(M.wg_flag);
-        M.Aj16 = nullptr; M.wg_base = nullptr; M.wg_flag = nullptr; M.i16_rpb = 0; M.i16_frac = 0.0;
+        M.Aj16.reset(); M.wg_base.reset(); M.wg_flag.reset(); M.i16_rpb = 0; M.i16_frac = 0.0;
         if (acct) *acct = before;
     }
     return rc;
@@ -214,22 +187,20 @@ static int try_stencil(DevCsr &M, const std::vector<int> &dptr, const std::vecto
     M.st_nranges = nr;
     for (int r = 0; r < nr; ++r) { M.st_range[r][0] = ranges[r][0]; M.st_range[r][1] = ranges[r][1]; }
     const size_t nblk = ((size_t)M.nrows + 255) / 256;
-    int *dslot = nullptr;
-    unsigned *dmask = nullptr;
-    CHK(dev_alloc(&M.st_vals, nblk * nu * 256, acct));
+    DevArr<int> dslot;
+    DevArr<unsigned> dmask;
+    CHK(dev_alloc(M.st_vals, nblk * nu * 256, acct));
     {
-        unsigned char *mb = nullptr;             // 1 byte per row for |U| <= 7, 4 otherwise
-        CHK(dev_alloc(&mb, (size_t)M.nrows * (nu <= 7 ? 1 : 4) + 16, acct));
-        M.st_mask = mb;
+        DevArr<unsigned char> mb;                // 1 byte per row for |U| <= 7, 4 otherwise
+        CHK(dev_alloc(mb, (size_t)M.nrows * (nu <= 7 ? 1 : 4) + 16, acct));
+        M.st_mask = std::move(mb);
     }
-    CHK(dev_alloc(&dslot, slot.size(), nullptr));
-    CHK(dev_alloc(&dmask, npat, nullptr));
+    CHK(dev_alloc(dslot, slot.size(), nullptr));
+    CHK(dev_alloc(dmask, npat, nullptr));
     AMG_HIP(hipMemcpy(dslot, slot.data(), sizeof(int) * slot.size(), hipMemcpyHostToDevice));
     AMG_HIP(hipMemcpy(dmask, pmask.data(), sizeof(unsigned) * pmask.size(), hipMemcpyHostToDevice));
     int rc = launch_stencil_build(M, dslot, dmask, 0);
     AMG_HIP(hipDeviceSynchronize());
-    hipFree(dslot);
-    hipFree(dmask);
     return rc;
 }
 
@@ -341,9 +312,9 @@ int try_patterns(DevCsr &M, const int *Ap, const int *Aj, long *acct)
         const int top = (int)(std::max_element(pcount.begin(), pcount.end()) - pcount.begin());
         for (int q = dptr[top]; q < dptr[top + 1]; ++q) M.period_rows = std::max(M.period_rows, std::abs(doff[q]));
     }
-    CHK(dev_alloc(&M.pat, n, acct));
-    CHK(dev_alloc(&M.dict_ptr, M.npat + 1, acct));
-    CHK(dev_alloc(&M.dict_off, M.ndict, acct));
+    CHK(dev_alloc(M.pat, n, acct));
+    CHK(dev_alloc(M.dict_ptr, M.npat + 1, acct));
+    CHK(dev_alloc(M.dict_off, M.ndict, acct));
     AMG_HIP(hipMemcpy(M.pat, pat.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
     AMG_HIP(hipMemcpy(M.dict_ptr, dptr.data(), sizeof(int) * dptr.size(), hipMemcpyHostToDevice));
     if (M.ndict) AMG_HIP(hipMemcpy(M.dict_off, doff.data(), sizeof(int) * doff.size(), hipMemcpyHostToDevice));
@@ -355,9 +326,9 @@ int upload_bsr(DevBsr &M, int nbrows, int bs, const int *Ap, const int *Aj, cons
 {
     long nb = Ap[nbrows];
     M.nbrows = nbrows; M.bs = bs; M.nblocks = nb;
-    CHK(dev_alloc(&M.Ap, nbrows + 1, acct));
-    CHK(dev_alloc(&M.Aj, nb, acct));
-    CHK(dev_alloc(&M.Ax, nb * bs * bs, acct));
+    CHK(dev_alloc(M.Ap, nbrows + 1, acct));
+    CHK(dev_alloc(M.Aj, nb, acct));
+    CHK(dev_alloc(M.Ax, nb * bs * bs, acct));
     AMG_HIP(hipMemcpy(M.Ap, Ap, sizeof(int) * (size_t)(nbrows + 1), hipMemcpyHostToDevice));
     if (nb) {
         AMG_HIP(hipMemcpy(M.Aj, Aj, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice));
@@ -410,36 +381,11 @@ template <class F> static void host_parallel(long n, long grain, F fn)
     for (auto &t : th) t.join();
 }
 
-void Schedule::release()
-{
-    free_csr(G);
-    if (rowmap) hipFree(rowmap);
-    if (diagpos) hipFree(diagpos);
-    if (rows) hipFree(rows);
-    if (level_ptr_dev) hipFree(level_ptr_dev);
-    free_bsr(Gb);
-    flow.release();
-    bflow.release();
-    rowmap = diagpos = rows = level_ptr_dev = nullptr;
-    for (int *p : {c2_code_f, c2_code_b, c2_off, perm_Aj, cl_code_f, cl_code_b}) if (p) hipFree(p);
-    cl_code_f = cl_code_b = nullptr;
-    for (double *p : {c2_diag, c2_val, c2_dummy, xp, bp, bd}) if (p) hipFree(p);
-    c2_code_f = c2_code_b = c2_off = perm_Aj = nullptr;
-    c2_diag = c2_val = c2_dummy = xp = bp = bd = nullptr;
-    chain2 = perm = false;
-    gb_level_slice.clear();
-    chains.clear();
-    chain_width.clear();
-}
-
 void Schedule::drop_level_copies()
 {
-    free_csr(G);
     G = DevCsr();
-    for (int *p : {rowmap, diagpos, level_ptr_dev, c2_code_f, c2_code_b, c2_off, perm_Aj, cl_code_f, cl_code_b}) if (p) hipFree(p);
-    for (double *p : {c2_diag, c2_val, c2_dummy, xp, bp, bd}) if (p) hipFree(p);
-    rowmap = diagpos = level_ptr_dev = c2_code_f = c2_code_b = c2_off = perm_Aj = cl_code_f = cl_code_b = nullptr;
-    c2_diag = c2_val = c2_dummy = xp = bp = bd = nullptr;
+    for (DevArr<int> *p : {&rowmap, &diagpos, &level_ptr_dev, &c2_code_f, &c2_code_b, &c2_off, &perm_Aj, &cl_code_f, &cl_code_b}) p->reset();
+    for (DevArr<double> *p : {&c2_diag, &c2_val, &c2_dummy, &xp, &bp, &bd}) p->reset();
     chain2 = perm = chain_long = false;
     chains.clear(); chain_width.clear();
     std::vector<int>().swap(gp_host);
@@ -516,12 +462,12 @@ int build_csr_schedule(const int *Ap, const int *Aj, const double *Ax, int n, co
     });
     CHK(upload_csr(S.G, ntasks, n, gp.data(), gj.data(), gx.data(), nullptr));
     S.gp_host = gp;
-    CHK(dev_alloc(&S.rowmap, ntasks, (long *)nullptr));
-    CHK(dev_alloc(&S.diagpos, ntasks, (long *)nullptr));
+    CHK(dev_alloc(S.rowmap, ntasks, (long *)nullptr));
+    CHK(dev_alloc(S.diagpos, ntasks, (long *)nullptr));
     AMG_HIP(hipMemcpy(S.rowmap, rowmap.data(), sizeof(int) * (size_t)ntasks, hipMemcpyHostToDevice));
     AMG_HIP(hipMemcpy(S.diagpos, dpos.data(), sizeof(int) * (size_t)ntasks, hipMemcpyHostToDevice));
     // runs of narrow levels for the chained sweep
-    CHK(dev_alloc(&S.level_ptr_dev, (long)S.level_ptr.size(), (long *)nullptr));
+    CHK(dev_alloc(S.level_ptr_dev, (long)S.level_ptr.size(), (long *)nullptr));
     AMG_HIP(hipMemcpy(S.level_ptr_dev, S.level_ptr.data(), sizeof(int) * S.level_ptr.size(), hipMemcpyHostToDevice));
     S.chains.clear();
     S.chain_width.clear();
@@ -659,8 +605,8 @@ int build_csr_schedule(const int *Ap, const int *Aj, const double *Ax, int n, co
                 }
             }
             if (ring_ok) {
-                CHK(dev_alloc(&S.cl_code_f, (long)cf.size(), (long *)nullptr));
-                CHK(dev_alloc(&S.cl_code_b, (long)cb.size(), (long *)nullptr));
+                CHK(dev_alloc(S.cl_code_f, (long)cf.size(), (long *)nullptr));
+                CHK(dev_alloc(S.cl_code_b, (long)cb.size(), (long *)nullptr));
                 AMG_HIP(hipMemcpy(S.cl_code_f, cf.data(), sizeof(int) * cf.size(), hipMemcpyHostToDevice));
                 AMG_HIP(hipMemcpy(S.cl_code_b, cb.data(), sizeof(int) * cb.size(), hipMemcpyHostToDevice));
             }
@@ -736,12 +682,12 @@ int build_csr_schedule(const int *Ap, const int *Aj, const double *Ax, int n, co
             }
         }
         if (ok && total > 0) {
-            CHK(dev_alloc(&S.c2_diag, n, (long *)nullptr));
-            CHK(dev_alloc(&S.c2_val, total * PFs, (long *)nullptr));
-            CHK(dev_alloc(&S.c2_code_f, total * PFs, (long *)nullptr));
-            CHK(dev_alloc(&S.c2_code_b, total * PFs, (long *)nullptr));
-            CHK(dev_alloc(&S.c2_off, nl + 1, (long *)nullptr));
-            CHK(dev_alloc(&S.c2_dummy, CHAIN2_WG, (long *)nullptr));
+            CHK(dev_alloc(S.c2_diag, n, (long *)nullptr));
+            CHK(dev_alloc(S.c2_val, total * PFs, (long *)nullptr));
+            CHK(dev_alloc(S.c2_code_f, total * PFs, (long *)nullptr));
+            CHK(dev_alloc(S.c2_code_b, total * PFs, (long *)nullptr));
+            CHK(dev_alloc(S.c2_off, nl + 1, (long *)nullptr));
+            CHK(dev_alloc(S.c2_dummy, CHAIN2_WG, (long *)nullptr));
             AMG_HIP(hipMemcpy(S.c2_diag, cd.data(), sizeof(double) * cd.size(), hipMemcpyHostToDevice));
             AMG_HIP(hipMemcpy(S.c2_val, cv.data(), sizeof(double) * cv.size(), hipMemcpyHostToDevice));
             AMG_HIP(hipMemcpy(S.c2_code_f, cf.data(), sizeof(int) * cf.size(), hipMemcpyHostToDevice));
@@ -751,11 +697,11 @@ int build_csr_schedule(const int *Ap, const int *Aj, const double *Ax, int n, co
             // generation chain of the same sweep) and the gathered x / b the sweep works on
             std::vector<int> pj(gj.size());
             for (size_t q = 0; q < gj.size(); ++q) pj[q] = inv[(size_t)gj[q]];
-            CHK(dev_alloc(&S.perm_Aj, (long)pj.size(), (long *)nullptr));
-            CHK(dev_alloc(&S.xp, (long)n + 1, (long *)nullptr));
+            CHK(dev_alloc(S.perm_Aj, (long)pj.size(), (long *)nullptr));
+            CHK(dev_alloc(S.xp, (long)n + 1, (long *)nullptr));
             AMG_HIP(hipMemset(S.xp, 0, sizeof(double) * ((size_t)n + 1)));       // xp[n] stays 0.0: the operand of padded slots
-            CHK(dev_alloc(&S.bp, n, (long *)nullptr));
-            CHK(dev_alloc(&S.bd, 2 * (long)n, (long *)nullptr));
+            CHK(dev_alloc(S.bp, n, (long *)nullptr));
+            CHK(dev_alloc(S.bd, 2 * (long)n, (long *)nullptr));
             AMG_HIP(hipMemcpy(S.perm_Aj, pj.data(), sizeof(int) * pj.size(), hipMemcpyHostToDevice));
             S.chain2 = true;
             S.perm = true;
@@ -803,7 +749,7 @@ int build_block_schedule(const int *Ap, const int *Aj, int nb, const int *tasks,
     S.ntasks = ntasks;
     std::vector<int> rows((size_t)ntasks);
     for (int k = 0; k < ntasks; ++k) rows[k] = tasks ? tasks[order[k]] : order[k];
-    CHK(dev_alloc(&S.rows, ntasks, (long *)nullptr));
+    CHK(dev_alloc(S.rows, ntasks, (long *)nullptr));
     AMG_HIP(hipMemcpy(S.rows, rows.data(), sizeof(int) * (size_t)ntasks, hipMemcpyHostToDevice));
     if (Ax && bs > 0) {
         // block rows copied in level order so that every level is one contiguous, streamable slice
@@ -869,9 +815,12 @@ static bool applies_from_blocks(const DevCsr &M, StreamMode mode, const StreamAr
     return bsr_spmv_enabled(M.blk->bs) && bsr_spmv_supports(mode) && a.row_lo == 0 && a.row_hi == M.nrows;
 }
 
-int apply_operator(const DevCsr &M, StreamMode mode, const StreamArgs &a, hipStream_t st)
+// forms the dispatch may be told to pass over (amg_hier_time_spmv times the plainer kernels of an operator that has them)
+enum : unsigned { SKIP_BLOCKS = 1, SKIP_STENCIL = 2, SKIP_PATTERN = 4, SKIP_INDEX16 = 8 };
+
+int apply_operator(const DevCsr &M, StreamMode mode, const StreamArgs &a, hipStream_t st, unsigned skip = 0)
 {
-    if (applies_from_blocks(M, mode, a)) {
+    if (!(skip & SKIP_BLOCKS) && applies_from_blocks(M, mode, a)) {
         if (!bsr_spmv_supports(mode) || a.row_lo != 0 || a.row_hi != M.nrows) {
             set_error("this operator is stored by blocks only: the requested application needs its scalar expansion");
             return AMG_ENOTIMPL;
@@ -880,8 +829,8 @@ int apply_operator(const DevCsr &M, StreamMode mode, const StreamArgs &a, hipStr
         if (bsell_applies(*M.blk, BM_SPMV, q)) return launch_bsell(*M.blk, BM_SPMV, q, st);
         return launch_bsr_stream(BM_SPMV, q, M.blk->nblocks, st);
     }
-    if (M.st_vals && (stencil_enabled() || !M.Ap) && pattern_supports(mode)) return launch_stencil(mode, a, M, st);
-    if (M.pat && pattern_supports(mode)) return launch_pattern(mode, a, M, st);
+    if (!(skip & SKIP_STENCIL) && M.st_vals && (stencil_enabled() || !M.Ap) && pattern_supports(mode)) return launch_stencil(mode, a, M, st);
+    if (!(skip & SKIP_PATTERN) && M.pat && pattern_supports(mode)) return launch_pattern(mode, a, M, st);
     if (M.sl_val && (sell_enabled() || !M.Ap) && sell_supports(mode) && a.row_lo == M.sl_lo && a.row_hi == M.sl_hi && !a.rowmap && a.Aj == M.Aj)
         return launch_sell(mode, a, M, st);
     if (!M.Ap || !a.Ap) {
@@ -892,11 +841,12 @@ int apply_operator(const DevCsr &M, StreamMode mode, const StreamArgs &a, hipStr
 }
 
 int spmv(const DevCsr &M, StreamMode mode, const double *xg, const double *b, const double *v2,
-         double *out, double *out2, double c0, hipStream_t st)
+         double *out, double *out2, double c0, hipStream_t st, unsigned skip = 0)
 {
     StreamArgs a = base_args(M);
+    if (skip & SKIP_INDEX16) { a.Aj16 = nullptr; a.wg_base = nullptr; a.wg_flag = nullptr; }
     a.xg = xg; a.b = b; a.v2 = v2; a.out = out; a.out2 = out2; a.c0 = c0;
-    return apply_operator(M, mode, a, st);
+    return apply_operator(M, mode, a, st, skip);
 }
 
 // directional sweeps of a scheduled (CSR flavour) Gauss-Seidel, in the order given (seq[k] != 0: reversed).  With the
@@ -909,16 +859,14 @@ int gs_sweep_csr(const Schedule &S, bool bsr1, double *x, const double *b, const
     if (S.flow.ready && (!S.G.Ap || (allow_flow && (gs_flow_mode() == 2 || (gs_flow_mode() == 1 && S.flow_auto)))))
         return gs_flow_sweep(S.flow, bsr1, x, b, seq, nseq, st);
     const bool perm = S.perm && gs_chain_enabled() && gs_chain_generation() == 2;
-    DevCsr G = S.G;
-    G.owned = false;
     const int *rowmap = S.rowmap;
     double *xs = x;
     const double *bs = b;
+    StreamArgs a = base_args(S.G);
     if (perm) {
         CHK(launch_perm_gather(S.rowmap, x, b, S.c2_diag, S.xp, S.bp, S.bd, S.ntasks, st));
-        G.Aj = S.perm_Aj; rowmap = nullptr; xs = S.xp; bs = S.bp;
+        a.Aj = S.perm_Aj; rowmap = nullptr; xs = S.xp; bs = S.bp;
     }
-    StreamArgs a = base_args(G);
     a.xg = xs; a.b = bs; a.out = xs; a.rowmap = rowmap; a.diagpos = S.diagpos;
     const int nl = S.nlevels();
     for (int k = 0; k < nseq; ++k) {
@@ -945,10 +893,10 @@ int gs_sweep_csr(const Schedule &S, bool bsr1, double *x, const double *b, const
                 CHK(launch_gs_chain2(S.level_ptr_dev, S.c2_val, reverse ? S.c2_code_b : S.c2_code_f, S.c2_off, S.c2_dummy, S.c2_pf,
                                      ch.first, ch.second - ch.first, width, reverse, bsr1, xs, S.bd, S.ntasks, st));
             else if (S.chain_long)
-                CHK(launch_gs_chain_long(G, rowmap, S.diagpos, S.level_ptr_dev, ch.first, ch.second - ch.first, width, reverse, bsr1, xs, bs, st,
+                CHK(launch_gs_chain_long(S.G, rowmap, S.diagpos, S.level_ptr_dev, ch.first, ch.second - ch.first, width, reverse, bsr1, xs, bs, st,
                                          gs_chain_generation() == 2 ? (reverse ? S.cl_code_b : S.cl_code_f) : nullptr));
             else
-                CHK(launch_gs_chain(G, rowmap, S.diagpos, S.level_ptr_dev, ch.first, ch.second - ch.first, width, reverse, bsr1, xs, bs, st));
+                CHK(launch_gs_chain(S.G, rowmap, S.diagpos, S.level_ptr_dev, ch.first, ch.second - ch.first, width, reverse, bsr1, xs, bs, st));
         }
         if (!reverse) CHK(launches(pos, nl));
         else CHK(launches(0, pos));
@@ -1261,7 +1209,7 @@ static int relax(amg_hier *h, Level &L, Smoother &s, double *&x, double *&xalt, 
     }
     case AMG_SM_BLOCK_JACOBI: {
         // relaxation.py:430-506
-        const DevBsr &Ab = s.Ablk_owned ? s.Ablk : L.Ab;
+        const DevBsr &Ab = s.own_blocks() ? s.Ablk : L.Ab;
         for (int it = 0; it < s.iterations; ++it) {
             CHK(bsr_stream_all(Ab, BM_BLOCK_JACOBI, s.Dinv, x, xalt, b, s.omega, st));
             std::swap(x, xalt);
@@ -1332,28 +1280,28 @@ constexpr int L0_ZCHUNK = L0_ZCHUNK_PLANES;           // planes per workgroup of
 static int level0_chain_check(amg_hier *h, DevCsr &M)
 {
     M.l0_ok = 0;
-    if (M.l0_same) { hipFree(M.l0_same); M.l0_same = nullptr; }
+    M.l0_same.reset();
     M.l0_nsame = 0; M.l0_code_planes[0] = M.l0_code_planes[1] = 0;
     if (!M.st_vals || !M.st_codes || M.st_nu != 7 || M.st_nranges != 0 || M.nrows != M.ncols || M.nrows < 1) return 0;
     const int *o = M.st_off;
     const long n = M.nrows, Lx = o[5], P = o[6];
     if (!(o[0] == -P && o[1] == -Lx && o[2] == -1 && o[3] == 0 && o[4] == 1)) return 0;
     if (!(Lx > 1 && P > Lx && P % Lx == 0 && n % P == 0)) return 0;
-    int *bad = nullptr;
-    if (dev_alloc(&bad, 1, nullptr) != 0) return AMG_ENOMEM;
+    DevArr<int> bad;
+    if (dev_alloc(bad, 1, nullptr) != 0) return AMG_ENOMEM;
     int found = 1;
     int rc = 0;
     if (hipMemsetAsync(bad, 0, sizeof(int), h->stream) != hipSuccess) rc = AMG_ESTATE;
     if (rc == 0) rc = launch_level0_box_scan(M.st_codes, (int)Lx, (int)(P / Lx), (int)(n / P), bad, h->stream);
     if (rc == 0 && (hipMemcpyAsync(&found, bad, sizeof(int), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
                     hipStreamSynchronize(h->stream) != hipSuccess)) rc = AMG_ESTATE;
-    hipFree(bad);
+    bad.reset();
     if (rc != 0) return rc;
     if (found) return 0;
     M.l0_nx = (int)Lx; M.l0_ny = (int)(P / Lx); M.l0_nz = (int)(n / P);
     const int nz = M.l0_nz;
     std::vector<unsigned char> same((size_t)nz, 0);
-    if (dev_alloc(&M.l0_same, (nz + 3) / 4 * 4, &h->dev_bytes) != 0) return AMG_ENOMEM;
+    if (dev_alloc(M.l0_same, (nz + 3) / 4 * 4, &h->dev_bytes) != 0) return AMG_ENOMEM;
     CHK(launch_level0_plane_scan(M.st_codes, P, nz, M.l0_same, h->stream));
     AMG_HIP(hipMemcpyAsync(same.data(), M.l0_same, (size_t)nz, hipMemcpyDeviceToHost, h->stream));
     AMG_HIP(hipStreamSynchronize(h->stream));
@@ -1391,7 +1339,7 @@ static int level0_chain(amg_hier *h, const Smoother &s, bool first_res, bool las
 {
     const DevCsr &M = h->lv[0].A;
     Level0ChainArgs a{};
-    a.codes = reinterpret_cast<const unsigned long long *>(M.st_codes);
+    a.codes = M.st_codes.as<const unsigned long long>();
     a.dict = M.st_dict; a.ndict = M.st_ndict;
     a.nx = M.l0_nx; a.ny = M.l0_ny; a.nz = M.l0_nz;
     a.g0 = g0; a.x = x; a.b = b; a.xout = xalt; a.rout = rout;
@@ -1471,7 +1419,7 @@ static int cycle(amg_hier *h, int lvl, double *&x, double *&xalt, const double *
         const int nAMLI = 2;
         const size_t bytes = sizeof(double) * (size_t)nc;
         for (int q = 0; q < 4; ++q)
-            if (!Lc.amli[q]) CHK(dev_alloc(&Lc.amli[q], nc, &h->dev_bytes));
+            if (!Lc.amli[q]) CHK(dev_alloc(Lc.amli[q], nc, &h->dev_bytes));
         double *p[2] = {Lc.amli[0], Lc.amli[1]};
         double *Apk = Lc.amli[2], *Apj = Lc.amli[3];
         double *num = h->norm_scratch + 1027, *den = h->norm_scratch + 1029;
@@ -1653,6 +1601,8 @@ extern "C" {
 
 const char *amg_last_error(void) { return amg::last_error().c_str(); }
 
+long amg_dev_live_buffers(void) { return amg::dev_live.load(std::memory_order_relaxed); }
+
 int amg_device_count(void)
 {
     int n = 0;
@@ -1692,58 +1642,12 @@ amg_hier *amg_hier_create(int nlevels, int device)
     return h;
 }
 
-static void free_smoother(Smoother &s)
-{
-    if (s.sw_Sj) hipFree(s.sw_Sj);
-    if (s.sw_Sp) hipFree(s.sw_Sp);
-    if (s.sw_Tp) hipFree(s.sw_Tp);
-    if (s.sw_order) hipFree(s.sw_order);
-    if (s.sw_Tx) hipFree(s.sw_Tx);
-    if (s.sw_scratch) hipFree(s.sw_scratch);
-    s.sw_Sj = s.sw_Sp = s.sw_Tp = s.sw_order = nullptr;
-    s.sw_Tx = s.sw_scratch = nullptr;
-    free_csr(s.aux[0]);
-    free_csr(s.aux[1]);
-    if (s.Dinv) hipFree(s.Dinv);
-    s.Dinv = nullptr;
-    if (s.Ablk_owned) free_bsr(s.Ablk);
-    if (s.sched && s.sched.use_count() == 1) s.sched->release();
-    s.sched.reset();
-}
-
 void amg_hier_destroy(amg_hier *h)
 {
     if (!h) return;
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
     drop_graphs(h);
-    for (auto &L : h->lv) {
-        free_smoother(L.sm[0]);
-        free_smoother(L.sm[1]);
-        if (L.sched_csr && L.sched_csr.use_count() == 1) L.sched_csr->release();
-        if (L.sched_blk && L.sched_blk.use_count() == 1) L.sched_blk->release();
-        if (L.sched_bgs && L.sched_bgs.use_count() == 1) L.sched_bgs->release();
-        free_csr(L.A); free_csr(L.P); free_csr(L.Rm); free_bsr(L.Ab);
-        if (L.part.send_idx) hipFree(L.part.send_idx);
-        if (L.part.gather_idx) hipFree(L.part.gather_idx);
-        if (L.part.rslice) hipFree(L.part.rslice);
-        for (double *p : {L.x, L.xalt, L.b, L.r, L.h, L.h2, L.amli[0], L.amli[1], L.amli[2], L.amli[3]}) if (p) hipFree(p);
-    }
-    free_smoother(h->coarse_sm);
-    if (h->coarse_Mt) hipFree(h->coarse_Mt);
-    if (h->coarse_gather_idx) hipFree(h->coarse_gather_idx);
-    if (h->coarse_full_b) hipFree(h->coarse_full_b);
-    if (h->coarse_full_x) hipFree(h->coarse_full_x);
-    if (h->arn_V) hipFree(h->arn_V);
-    if (h->arn_dinv) hipFree(h->arn_dinv);
-    if (h->arn_coef) hipFree(h->arn_coef);
-    if (h->norm_scratch) hipFree(h->norm_scratch);
-    if (h->sumsq_partials) hipFree(h->sumsq_partials);
-    for (double *q : h->pcg) if (q) hipFree(q);
-    if (h->res_dev) hipFree(h->res_dev);
-    if (h->ev0) hipEventDestroy(h->ev0);
-    if (h->ev1) hipEventDestroy(h->ev1);
-    if (h->stream) hipStreamDestroy(h->stream);
     delete h;
 }
 
@@ -1759,9 +1663,9 @@ static int value_index_build(amg_hier *h, DevCsr &M)
     if (!M.st_vals) return 0;
     if (M.st_codes) { M.st_vi_on = true; return M.st_ndict; }
     const long count = (long)((M.nrows + 255) / 256) * M.st_nu * 256;
-    unsigned long long *table = nullptr;
-    int *ovf = nullptr;
-    if (dev_alloc(&table, 1024, nullptr) != 0 || dev_alloc(&ovf, 1, nullptr) != 0) return AMG_ENOMEM;
+    DevArr<unsigned long long> table;
+    DevArr<int> ovf;
+    if (dev_alloc(table, 1024, nullptr) != 0 || dev_alloc(ovf, 1, nullptr) != 0) return AMG_ENOMEM;
     AMG_HIP(hipMemset(table, 0xFF, sizeof(unsigned long long) * 1024));
     AMG_HIP(hipDeviceSynchronize());
     int rc = launch_value_scan(M.st_vals, count, table, ovf, h->stream);
@@ -1770,7 +1674,7 @@ static int value_index_build(amg_hier *h, DevCsr &M)
     AMG_HIP(hipStreamSynchronize(h->stream));
     AMG_HIP(hipMemcpy(tb.data(), table, sizeof(unsigned long long) * 1024, hipMemcpyDeviceToHost));
     AMG_HIP(hipMemcpy(&overflow, ovf, sizeof(int), hipMemcpyDeviceToHost));
-    hipFree(table); hipFree(ovf);
+    table.reset(); ovf.reset();
     if (rc != 0) return AMG_ESTATE;
     std::vector<long long> bits;
     for (unsigned long long v : tb) if (v != ~0ULL) bits.push_back((long long)v);
@@ -1778,14 +1682,14 @@ static int value_index_build(amg_hier *h, DevCsr &M)
     std::sort(bits.begin(), bits.end());
     std::vector<double> dict(256, 0.0);
     for (size_t k = 0; k < bits.size(); ++k) std::memcpy(&dict[k], &bits[k], sizeof(double));
-    if (dev_alloc(&M.st_dict, 256, &h->dev_bytes) != 0) return AMG_ENOMEM;
+    if (dev_alloc(M.st_dict, 256, &h->dev_bytes) != 0) return AMG_ENOMEM;
     AMG_HIP(hipMemcpy(M.st_dict, dict.data(), sizeof(double) * 256, hipMemcpyHostToDevice));
     const long code_bytes = (long)((M.nrows + 255) / 256) * ((M.st_nu + 7) / 8) * 256 * 8;
-    if (dev_alloc(&M.st_codes, code_bytes, &h->dev_bytes) != 0) return AMG_ENOMEM;
+    if (dev_alloc(M.st_codes, code_bytes, &h->dev_bytes) != 0) return AMG_ENOMEM;
     M.st_ndict = (int)bits.size();
     AMG_HIP(hipMemsetAsync(M.st_codes, 0xFF, (size_t)code_bytes, h->stream));      // slots the stencil does not have: absent (255)
     rc = launch_value_encode(M.st_vals, count, M.st_dict, M.st_ndict, M.st_codes, M.st_nu, h->stream,
-                             M.st_nu <= 7 ? static_cast<const unsigned char *>(M.st_mask) : nullptr, M.nrows);
+                             M.st_nu <= 7 ? M.st_mask.as<const unsigned char>() : nullptr, M.nrows);
     AMG_HIP(hipStreamSynchronize(h->stream));
     if (rc != 0) return AMG_ESTATE;
     M.st_vi_on = true;
@@ -1808,7 +1712,7 @@ int amg_hier_set_matrix(amg_hier *h, int lvl, int which, int fmt, int nrows, int
     if (R < 1 || C < 1 || nrows % R || ncols % C) { set_error("bad block size"); return AMG_EINVAL; }
     Level &L = h->lv[lvl];
     DevCsr &M = (which == AMG_MAT_A) ? L.A : (which == AMG_MAT_P ? L.P : L.Rm);
-    free_csr(M);
+    M = DevCsr();
     if (on_device) {
         // device-resident source (e.g. an operator assembled on the GPU): copied device-to-device
         if (fmt != AMG_FMT_CSR && !(R == 1 && C == 1)) { set_error("device sources: CSR / BSR(1,1) only"); return AMG_ENOTIMPL; }
@@ -1816,9 +1720,9 @@ int amg_hier_set_matrix(amg_hier *h, int lvl, int which, int fmt, int nrows, int
         AMG_HIP(hipMemcpy(&last, Ap + nrows, sizeof(int), hipMemcpyDeviceToHost));
         if (last < 0) { set_error("bad device row pointer"); return AMG_EINVAL; }
         M.nrows = nrows; M.ncols = ncols; M.nnz = last;
-        CHK(dev_alloc(&M.Ap, nrows + 1, &h->dev_bytes));
-        CHK(dev_alloc(&M.Aj, last, &h->dev_bytes));
-        CHK(dev_alloc(&M.Ax, last, &h->dev_bytes));
+        CHK(dev_alloc(M.Ap, nrows + 1, &h->dev_bytes));
+        CHK(dev_alloc(M.Aj, last, &h->dev_bytes));
+        CHK(dev_alloc(M.Ax, last, &h->dev_bytes));
         AMG_HIP(hipMemcpy(M.Ap, Ap, sizeof(int) * (size_t)(nrows + 1), hipMemcpyDeviceToDevice));
         if (last) {
             AMG_HIP(hipMemcpy(M.Aj, Aj, sizeof(int) * (size_t)last, hipMemcpyDeviceToDevice));
@@ -1860,7 +1764,7 @@ int amg_hier_set_matrix(amg_hier *h, int lvl, int which, int fmt, int nrows, int
     if (which == AMG_MAT_A) {
         if (nrows != ncols && !(h->comm && ncols > nrows)) { set_error("A must be square (row-partitioned: owned rows x [owned | halo] columns)"); return AMG_EINVAL; }
         L.fmt = fmt; L.R = R; L.C = C; L.hasA = true;
-        free_bsr(L.Ab);
+        L.Ab = DevBsr();
         if (fmt == AMG_FMT_BSR && R == C && R > 1) {
             CHK(upload_bsr(L.Ab, nrows / R, R, Ap, Aj, Ax, &h->dev_bytes));
             if (!h->comm) CHK(build_bsell(L.Ab, &h->dev_bytes));        // whole passes run from the sliced block form (sell.hip)
@@ -1877,7 +1781,6 @@ int amg_hier_set_matrix(amg_hier *h, int lvl, int which, int fmt, int nrows, int
 
 static int fill_smoother(amg_hier *h, Smoother &s, const amg_smoother_desc *d, int n)
 {
-    free_smoother(s);
     s = Smoother();
     if (!d) return 0;
     s.kind = d->kind;
@@ -1892,7 +1795,7 @@ static int fill_smoother(amg_hier *h, Smoother &s, const amg_smoother_desc *d, i
         if (d->blocksize < 1 || n % d->blocksize || !d->Dinv) { set_error("block smoother needs blocksize and Dinv"); return AMG_EINVAL; }
         s.bs = d->blocksize;
         long cnt = (long)n * s.bs;
-        CHK(dev_alloc(&s.Dinv, cnt, &h->dev_bytes));
+        CHK(dev_alloc(s.Dinv, cnt, &h->dev_bytes));
         AMG_HIP(hipMemcpy(s.Dinv, d->Dinv, sizeof(double) * (size_t)cnt, hipMemcpyHostToDevice));
     }
     if (d->kind == AMG_SM_GAUSS_SEIDEL_INDEXED) {
@@ -1901,9 +1804,9 @@ static int fill_smoother(amg_hier *h, Smoother &s, const amg_smoother_desc *d, i
     }
     if (d->kind == AMG_SM_GAUSS_SEIDEL_NE || d->kind == AMG_SM_GAUSS_SEIDEL_NR || d->kind == AMG_SM_JACOBI_NE) {
         if (!d->Dinv) { set_error("normal-equation smoother needs the inverse diagonal of A A^H / A^H A"); return AMG_EINVAL; }
-        CHK(dev_alloc(&s.Dinv, n, &h->dev_bytes));
+        CHK(dev_alloc(s.Dinv, n, &h->dev_bytes));
         AMG_HIP(hipMemcpy(s.Dinv, d->Dinv, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-        CHK(dev_alloc(&s.sw_order, n, &h->dev_bytes));
+        CHK(dev_alloc(s.sw_order, n, &h->dev_bytes));
     }
     if (d->kind == AMG_SM_SCHWARZ) {
         const int nsd = d->nsdomains;
@@ -1916,12 +1819,12 @@ static int fill_smoother(amg_hier *h, Smoother &s, const amg_smoother_desc *d, i
         s.hSp.assign(d->Sp, d->Sp + nsd + 1);
         s.hSj.assign(d->Sj, d->Sj + (nsd ? d->Sp[nsd] : 0));
         for (int v : s.hSj) if (v < 0 || v >= n) { set_error("schwarz: subdomain index out of range"); return AMG_EINVAL; }
-        CHK(dev_alloc(&s.sw_Sp, nsd + 1, &h->dev_bytes));
-        CHK(dev_alloc(&s.sw_Tp, nsd + 1, &h->dev_bytes));
-        CHK(dev_alloc(&s.sw_Sj, (long)s.hSj.size(), &h->dev_bytes));
-        CHK(dev_alloc(&s.sw_Tx, nsd ? d->Tp[nsd] : 0, &h->dev_bytes));
-        CHK(dev_alloc(&s.sw_scratch, (long)s.hSj.size(), &h->dev_bytes));
-        CHK(dev_alloc(&s.sw_order, nsd, &h->dev_bytes));
+        CHK(dev_alloc(s.sw_Sp, nsd + 1, &h->dev_bytes));
+        CHK(dev_alloc(s.sw_Tp, nsd + 1, &h->dev_bytes));
+        CHK(dev_alloc(s.sw_Sj, (long)s.hSj.size(), &h->dev_bytes));
+        CHK(dev_alloc(s.sw_Tx, nsd ? d->Tp[nsd] : 0, &h->dev_bytes));
+        CHK(dev_alloc(s.sw_scratch, (long)s.hSj.size(), &h->dev_bytes));
+        CHK(dev_alloc(s.sw_order, nsd, &h->dev_bytes));
         AMG_HIP(hipMemcpy(s.sw_Sp, d->Sp, sizeof(int) * (size_t)(nsd + 1), hipMemcpyHostToDevice));
         AMG_HIP(hipMemcpy(s.sw_Tp, d->Tp, sizeof(int) * (size_t)(nsd + 1), hipMemcpyHostToDevice));
         if (nsd) {
@@ -1949,9 +1852,8 @@ int amg_hier_set_block_matrix(amg_hier *h, int lvl, int which, int nbrows, int b
     ENTER(h);
     if (lvl < 0 || lvl >= h->nlevels || which < 0 || which > 2) { set_error("bad level/which"); return AMG_EINVAL; }
     Smoother &s = (which == 2) ? h->coarse_sm : h->lv[lvl].sm[which];
-    if (s.Ablk_owned) free_bsr(s.Ablk);
+    s.Ablk = DevBsr();
     CHK(upload_bsr(s.Ablk, nbrows, bs, Ap, Aj, Ax, &h->dev_bytes));
-    s.Ablk_owned = true;
     h->finalized = false;
     return 0;
 }
@@ -1963,7 +1865,7 @@ int amg_hier_set_aux_matrix(amg_hier *h, int lvl, int which, int slot, int nmajo
     if (lvl < 0 || lvl >= h->nlevels || which < 0 || which > 2 || slot < 0 || slot > 1) { set_error("bad level/which/slot"); return AMG_EINVAL; }
     if (nmajor < 0 || nminor < 0 || !Ap) { set_error("bad matrix"); return AMG_EINVAL; }
     Smoother &s = (which == 2) ? h->coarse_sm : h->lv[lvl].sm[which];
-    free_csr(s.aux[slot]);
+    s.aux[slot] = DevCsr();
     CHK(upload_csr(s.aux[slot], nmajor, nminor, Ap, Aj, Ax, &h->dev_bytes));
     h->finalized = false;
     return 0;
@@ -1973,12 +1875,11 @@ int amg_hier_set_coarse_dense(amg_hier *h, const double *M, int n)
 {
     ENTER(h);
     if (n < 0 || (n && !M)) { set_error("bad coarse matrix"); return AMG_EINVAL; }
-    if (h->coarse_Mt) hipFree(h->coarse_Mt);
-    h->coarse_Mt = nullptr;
+    h->coarse_Mt.reset();
     std::vector<double> Mt((size_t)n * n);
     for (int i = 0; i < n; ++i)
         for (int k = 0; k < n; ++k) Mt[(size_t)k * n + i] = M[(size_t)i * n + k];
-    CHK(dev_alloc(&h->coarse_Mt, (long)n * n, &h->dev_bytes));
+    CHK(dev_alloc(h->coarse_Mt, (long)n * n, &h->dev_bytes));
     AMG_HIP(hipMemcpy(h->coarse_Mt, Mt.data(), sizeof(double) * Mt.size(), hipMemcpyHostToDevice));
     h->coarse_n = n;
     h->coarse_kind = 1;
@@ -2073,12 +1974,12 @@ static int need_schedule(amg_hier *h, Level &L, Smoother &s)
         CHK(build_csr_schedule(ap.data(), aj.data(), ax.data(), n, s.indices.data(), (int)s.indices.size(), *s.sched, h->stream, flow_allowed(h), L.A.ncols));
         h->dev_bytes += s.sched->level_copy_bytes + s.sched->flow.bytes;
     } else if (s.kind == AMG_SM_BLOCK_GAUSS_SEIDEL || s.kind == AMG_SM_BLOCK_JACOBI) {
-        const DevBsr *Ab = s.Ablk_owned ? &s.Ablk : &L.Ab;
+        const DevBsr *Ab = s.own_blocks() ? &s.Ablk : &L.Ab;
         if (!Ab->Ap || Ab->bs != s.bs) {
             set_error("block smoother: no BSR copy of A with the smoother's blocksize (amg_hier_set_block_matrix)");
             return AMG_ESTATE;
         }
-        if (s.kind == AMG_SM_BLOCK_GAUSS_SEIDEL && !s.Ablk_owned && L.sched_bgs) {
+        if (s.kind == AMG_SM_BLOCK_GAUSS_SEIDEL && !s.own_blocks() && L.sched_bgs) {
             s.sched = L.sched_bgs;                                     // pre- and post-smoother sweep the same blocks
         } else if (s.kind == AMG_SM_BLOCK_GAUSS_SEIDEL) {
             std::vector<int> bp((size_t)Ab->nbrows + 1), bj((size_t)Ab->nblocks);
@@ -2092,7 +1993,7 @@ static int need_schedule(amg_hier *h, Level &L, Smoother &s)
             CHK(build_block_schedule(bp.data(), bj.data(), Ab->nbrows, nullptr, Ab->nbrows, *s.sched, h->stream,
                                      bx.data(), Ab->bs, false, flow_allowed(h)));
             h->dev_bytes += s.sched->level_copy_bytes + s.sched->bflow.bytes;
-            if (!s.Ablk_owned) L.sched_bgs = s.sched;
+            if (!s.own_blocks()) L.sched_bgs = s.sched;
         }
     }
     return 0;
@@ -2103,7 +2004,6 @@ int amg_hier_set_callback_smoother(amg_hier *h, int lvl, int which, amg_relax_ca
     ENTER(h);
     if (lvl < 0 || lvl >= h->nlevels || which < 0 || which > 1 || !cb) { set_error("bad callback smoother"); return AMG_EINVAL; }
     Smoother &s = h->lv[lvl].sm[which];
-    free_smoother(s);
     s = Smoother();
     s.kind = AMG_SM_CALLBACK; s.cb = cb; s.cb_user = user;
     h->has_callbacks = true;
@@ -2145,7 +2045,7 @@ double *amg_hier_scratch(amg_hier *h)
     if (!h) return nullptr;
     if (!h->norm_scratch) {
         hipSetDevice(h->device);
-        if (dev_alloc(&h->norm_scratch, AMG_DEV_SCRATCH, &h->dev_bytes) != 0) return nullptr;
+        if (dev_alloc(h->norm_scratch, AMG_DEV_SCRATCH, &h->dev_bytes) != 0) return nullptr;
     }
     return h->norm_scratch;
 }
@@ -2172,7 +2072,7 @@ int amg_hier_set_partition(amg_hier *h, int lvl, int n_own, int n_halo, int chan
     if (!h->comm) { set_error("amg_hier_set_comm first"); return AMG_ESTATE; }
     if (lvl < 0 || lvl >= h->nlevels || n_own < 0 || n_halo < 0) { set_error("bad partition"); return AMG_EINVAL; }
     Partition &P = h->lv[lvl].part;
-    if (P.send_idx) { hipFree(P.send_idx); P.send_idx = nullptr; }
+    P.send_idx.reset();
     P.n_own = n_own; P.n_halo = n_halo; P.channel = channel;
     if (channel >= 0) {
         if (channel >= (int)h->comm->ch.size()) { set_error("bad channel"); return AMG_EINVAL; }
@@ -2180,7 +2080,7 @@ int amg_hier_set_partition(amg_hier *h, int lvl, int n_own, int n_halo, int chan
         if (C.recv_total != n_halo) { set_error("channel does not deliver this level's halo"); return AMG_EINVAL; }
         for (int k = 0; k < C.send_total; ++k)
             if (send_idx[k] < 0 || send_idx[k] >= n_own) { set_error("send index outside the owned range"); return AMG_EINVAL; }
-        CHK(dev_alloc(&P.send_idx, C.send_total, &h->dev_bytes));
+        CHK(dev_alloc(P.send_idx, C.send_total, &h->dev_bytes));
         if (C.send_total) AMG_HIP(hipMemcpy(P.send_idx, send_idx, sizeof(int) * (size_t)C.send_total, hipMemcpyHostToDevice));
     }
     if (i0 < 0 || i1 > n_own || i1 < i0) { i0 = 0; i1 = 0; }
@@ -2211,14 +2111,13 @@ int amg_hier_set_gather(amg_hier *h, int lvl, int channel, int rows)
     Partition &P = h->lv[lvl].part;
     const Channel &C = h->comm->ch[(size_t)channel];
     if (C.send_total != rows * h->comm->world) { set_error("gather channel does not send this rank's slice to every rank"); return AMG_EINVAL; }
-    if (P.gather_idx) hipFree(P.gather_idx);
-    if (P.rslice) hipFree(P.rslice);
-    P.gather_idx = nullptr; P.rslice = nullptr;
+    P.gather_idx.reset();
+    P.rslice.reset();
     std::vector<int> idx((size_t)C.send_total);
     for (int k = 0; k < C.send_total; ++k) idx[(size_t)k] = rows ? k % rows : 0;
-    CHK(dev_alloc(&P.gather_idx, C.send_total, &h->dev_bytes));
+    CHK(dev_alloc(P.gather_idx, C.send_total, &h->dev_bytes));
     if (C.send_total) AMG_HIP(hipMemcpy(P.gather_idx, idx.data(), sizeof(int) * idx.size(), hipMemcpyHostToDevice));
-    CHK(dev_alloc(&P.rslice, rows, &h->dev_bytes));
+    CHK(dev_alloc(P.rslice, rows, &h->dev_bytes));
     P.gather_channel = channel; P.gather_rows = rows;
     h->finalized = false;
     return 0;
@@ -2234,9 +2133,8 @@ int amg_hier_set_coarse_gather(amg_hier *h, int channel, int lo)
     const int rows = h->comm->world ? C.send_total / h->comm->world : 0;
     std::vector<int> idx((size_t)C.send_total);
     for (int k = 0; k < C.send_total; ++k) idx[(size_t)k] = rows ? k % rows : 0;
-    if (h->coarse_gather_idx) hipFree(h->coarse_gather_idx);
-    h->coarse_gather_idx = nullptr;
-    CHK(dev_alloc(&h->coarse_gather_idx, C.send_total, &h->dev_bytes));
+    h->coarse_gather_idx.reset();
+    CHK(dev_alloc(h->coarse_gather_idx, C.send_total, &h->dev_bytes));
     if (C.send_total) AMG_HIP(hipMemcpy(h->coarse_gather_idx, idx.data(), sizeof(int) * idx.size(), hipMemcpyHostToDevice));
     h->coarse_gather_channel = channel;
     h->coarse_lo = lo;
@@ -2265,17 +2163,14 @@ static bool csr_free_smoother(const Smoother &s, bool jacobi_ok)
 static long release_csr_arrays(DevCsr &M)
 {
     long freed = 0;
-    if (M.Ap) { hipFree(M.Ap); freed += 4L * (M.nrows + 1 + PAD); }
-    if (M.Aj) { hipFree(M.Aj); freed += 4L * (M.nnz + PAD); }
-    if (M.Ax) { hipFree(M.Ax); freed += 8L * (M.nnz + PAD); }
-    if (M.pat) { hipFree(M.pat); freed += 4L * M.nrows; }
-    if (M.dict_ptr) hipFree(M.dict_ptr);
-    if (M.dict_off) hipFree(M.dict_off);
-    if (M.Aj16) { hipFree(M.Aj16); freed += 2L * M.nnz; }
-    if (M.wg_base) hipFree(M.wg_base);
-    if (M.wg_flag) hipFree(M.wg_flag);
-    M.Ap = M.Aj = nullptr; M.Ax = nullptr; M.pat = nullptr; M.dict_ptr = M.dict_off = nullptr; M.npat = M.ndict = 0;
-    M.Aj16 = nullptr; M.wg_base = nullptr; M.wg_flag = nullptr;
+    if (M.Ap) freed += 4L * (M.nrows + 1 + PAD);
+    if (M.Aj) freed += 4L * (M.nnz + PAD);
+    if (M.Ax) freed += 8L * (M.nnz + PAD);
+    if (M.pat) freed += 4L * M.nrows;
+    if (M.Aj16) freed += 2L * M.nnz;
+    for (DevArr<int> *p : {&M.Ap, &M.Aj, &M.pat, &M.dict_ptr, &M.dict_off, &M.wg_base}) p->reset();
+    M.Ax.reset(); M.Aj16.reset(); M.wg_flag.reset();
+    M.npat = M.ndict = 0;
     return freed;
 }
 
@@ -2329,9 +2224,9 @@ int amg_hier_finalize(amg_hier *h)
             return AMG_EINVAL;
         }
         const long n = L.A.ncols;                 // [owned | halo] on a partitioned level, = nrows otherwise
-        double **vecs[] = {&L.x, &L.xalt, &L.b, &L.r, &L.h, &L.h2};
-        for (double **p : vecs)
-            if (!*p) CHK(dev_alloc(p, n, &h->dev_bytes));
+        for (DevArr<double> *p : {&L.xbuf[0], &L.xbuf[1], &L.b, &L.r, &L.h, &L.h2})
+            if (!*p) CHK(dev_alloc(*p, n, &h->dev_bytes));
+        if (!L.x) { L.x = L.xbuf[0]; L.xalt = L.xbuf[1]; }
         if (l < h->nlevels - 1) {
             CHK(need_schedule(h, L, L.sm[0]));
             CHK(need_schedule(h, L, L.sm[1]));
@@ -2339,8 +2234,8 @@ int amg_hier_finalize(amg_hier *h)
     }
     if (h->coarse_kind == 2) CHK(need_schedule(h, h->lv[h->nlevels - 1], h->coarse_sm));
     if (h->coarse_kind == 1 && h->comm && h->coarse_gather_channel >= 0) {
-        if (!h->coarse_full_b) CHK(dev_alloc(&h->coarse_full_b, h->coarse_n, &h->dev_bytes));
-        if (!h->coarse_full_x) CHK(dev_alloc(&h->coarse_full_x, h->coarse_n, &h->dev_bytes));
+        if (!h->coarse_full_b) CHK(dev_alloc(h->coarse_full_b, h->coarse_n, &h->dev_bytes));
+        if (!h->coarse_full_x) CHK(dev_alloc(h->coarse_full_x, h->coarse_n, &h->dev_bytes));
         if (h->coarse_lo < 0 || h->coarse_lo + h->lv[h->nlevels - 1].A.nrows > h->coarse_n) {
             set_error("coarse slice outside the dense operator");
             return AMG_EINVAL;
@@ -2349,7 +2244,7 @@ int amg_hier_finalize(amg_hier *h)
         set_error("coarse dense operator has the wrong size");
         return AMG_EINVAL;
     }
-    if (!h->norm_scratch) CHK(dev_alloc(&h->norm_scratch, AMG_DEV_SCRATCH, &h->dev_bytes));
+    if (!h->norm_scratch) CHK(dev_alloc(h->norm_scratch, AMG_DEV_SCRATCH, &h->dev_bytes));
     if (h->comm) {
         if (h->reduce_channel < 0) { set_error("partitioned hierarchy without an all-reduce channel"); return AMG_ESTATE; }
         const char *env = getenv("AMG_DIST_OVERLAP");
@@ -2361,9 +2256,7 @@ int amg_hier_finalize(amg_hier *h)
         if (h->lv[0].A.blk && h->lv[0].A.blk->Ap)
             need = std::max(need, (long)bsr_stream_blocks(block_spmv_args(*h->lv[0].A.blk, SM_RESIDUAL_SUMSQ, a0), h->lv[0].A.blk->nblocks) + 8);
         if (need > h->sumsq_cap) {
-            if (h->sumsq_partials) hipFree(h->sumsq_partials);
-            h->sumsq_partials = nullptr;
-            CHK(dev_alloc(&h->sumsq_partials, need + 512, &h->dev_bytes));   // + second-stage scratch
+            CHK(dev_alloc(h->sumsq_partials, need + 512, &h->dev_bytes));   // + second-stage scratch
             h->sumsq_cap = need;
         }
     }
@@ -2380,9 +2273,7 @@ int amg_hier_finalize(amg_hier *h)
 static int ensure_res(amg_hier *h, int cap)
 {
     if (cap <= h->res_cap) return 0;
-    if (h->res_dev) hipFree(h->res_dev);
-    h->res_dev = nullptr;
-    CHK(dev_alloc(&h->res_dev, cap, &h->dev_bytes));
+    CHK(dev_alloc(h->res_dev, cap, &h->dev_bytes));
     h->res_cap = cap;
     return 0;
 }
@@ -2472,7 +2363,7 @@ int amg_hier_pcg(amg_hier *h, const double *b, double *x, double tol, int maxite
     const long n = L0.A.nrows;
     const size_t bytes = sizeof(double) * (size_t)n;
     for (int q = 0; q < 4; ++q)
-        if (!h->pcg[q]) CHK(dev_alloc(&h->pcg[q], n, &h->dev_bytes));
+        if (!h->pcg[q]) CHK(dev_alloc(h->pcg[q], n, &h->dev_bytes));
     double *xk = h->pcg[0], *r = h->pcg[1], *p = h->pcg[2], *Ap = h->pcg[3];
     double *slot = h->norm_scratch + 1026;
     hipMemcpyKind in_kind = (flags & AMG_SOLVE_DEVICE_VECTORS) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -2578,16 +2469,15 @@ int amg_hier_matvec(amg_hier *h, int lvl, int which, const double *x, double *y)
     Level &L = h->lv[lvl];
     const DevCsr &M = (which == AMG_MAT_A) ? L.A : (which == AMG_MAT_P ? L.P : L.Rm);
     if (!M.Ap && !(M.blk && M.blk->Ap) && !M.st_vals && !M.sl_val) { set_error("operator not set"); return AMG_ESTATE; }
-    double *dx = nullptr, *dy = nullptr;
-    CHK(dev_alloc(&dx, M.ncols, (long *)nullptr));
-    CHK(dev_alloc(&dy, M.nrows, (long *)nullptr));
+    DevArr<double> dx, dy;
+    CHK(dev_alloc(dx, M.ncols, (long *)nullptr));
+    CHK(dev_alloc(dy, M.nrows, (long *)nullptr));
     AMG_HIP(hipMemcpy(dx, x, sizeof(double) * (size_t)M.ncols, hipMemcpyHostToDevice));
     int rc = spmv(M, SM_MATVEC, dx, nullptr, nullptr, dy, nullptr, 0.0, h->stream);
     if (rc == 0) {
         hipStreamSynchronize(h->stream);
         hipMemcpy(y, dy, sizeof(double) * (size_t)M.nrows, hipMemcpyDeviceToHost);
     }
-    hipFree(dx); hipFree(dy);
     return rc;
 }
 
@@ -2751,13 +2641,12 @@ int amg_hier_time_spmv(amg_hier *h, int lvl, int which, int mode, int reps, doub
     else { in = L.r; out = h->lv[lvl + 1].b; }
     StreamMode sm = ((mode & 1) && which == AMG_MAT_A) ? SM_RESIDUAL : SM_MATVEC;
     if ((mode & 6) && !M.Ap) { set_error("operator is stored by blocks only"); return AMG_ENOTIMPL; }
-    DevCsr Mplain = M;                     // mode bit 1 (value 2): time the plain CSR kernel even if
-    if (mode & 2) { Mplain.pat = nullptr; Mplain.st_vals = nullptr; Mplain.Aj16 = nullptr; Mplain.blk = nullptr; }   // the operator has derived forms;
-    if (mode & 4) Mplain.st_vals = nullptr;                             // bit 2 (value 4): the pattern kernel
-    const DevCsr &Mu = (mode & 6) ? Mplain : M;
-    CHK(spmv(Mu, sm, in, L.b, nullptr, out, nullptr, 0.0, h->stream));   // warm-up
+    unsigned skip = 0;                     // mode bit 1 (value 2): time the plain CSR kernel even if
+    if (mode & 2) skip |= SKIP_PATTERN | SKIP_STENCIL | SKIP_INDEX16 | SKIP_BLOCKS;   // the operator has derived forms;
+    if (mode & 4) skip |= SKIP_STENCIL;                                 // bit 2 (value 4): the pattern kernel
+    CHK(spmv(M, sm, in, L.b, nullptr, out, nullptr, 0.0, h->stream, skip));   // warm-up
     AMG_HIP(hipEventRecord(h->ev0, h->stream));
-    for (int r = 0; r < reps; ++r) CHK(spmv(Mu, sm, in, L.b, nullptr, out, nullptr, 0.0, h->stream));
+    for (int r = 0; r < reps; ++r) CHK(spmv(M, sm, in, L.b, nullptr, out, nullptr, 0.0, h->stream, skip));
     AMG_HIP(hipEventRecord(h->ev1, h->stream));
     AMG_HIP(hipStreamSynchronize(h->stream));
     float t = 0.f;
@@ -2797,14 +2686,13 @@ int amg_hier_gs_natural(amg_hier *h, int lvl, double *x, const double *b, const 
     // rows per task of a structured operator: a task is one chain of hand-offs (0.7 us each at 500^3), a sweep is
     // (tasks per grid line + lines per plane + planes) of them; 32 rows leave about one task per resident wave and level
     constexpr long TASK_ROWS = 32;
-    int *order_dev[2] = {nullptr, nullptr}, *tstart_dev[2] = {nullptr, nullptr};
+    DevArr<int> order_dev[2], tstart_dev[2];
     int ntasks_dir[2] = {0, 0};
     const bool structured = M.st_vals && M.st_nranges == 0 && M.st_nu <= 7;
     if (!structured && ntasks64 > 4096) { set_error("natural-order Gauss-Seidel: large operator without stencil structure"); return AMG_ENOTIMPL; }
     if (structured && ntasks64 > 64) {
         std::vector<unsigned char> mk((size_t)n);
         AMG_HIP(hipMemcpy(mk.data(), M.st_mask, (size_t)n, hipMemcpyDeviceToHost));
-        auto release = [&]() { for (int k = 0; k < 2; ++k) { if (order_dev[k]) hipFree(order_dev[k]); if (tstart_dev[k]) hipFree(tstart_dev[k]); order_dev[k] = tstart_dev[k] = nullptr; } };
         for (int dir = 0; dir < 2; ++dir) {
             bool wanted = false;
             for (int k = 0; k < nsweeps; ++k) wanted |= ((dirs[k] != 0) == (dir == 1));
@@ -2826,7 +2714,7 @@ int amg_hier_gs_natural(amg_hier *h, int lvl, double *x, const double *b, const 
                     dist_u.push_back(u);
                 }
             }
-            if (!supported) { release(); set_error("natural-order Gauss-Seidel: large stencil operator with several short-range offsets"); return AMG_ENOTIMPL; }
+            if (!supported) { set_error("natural-order Gauss-Seidel: large stencil operator with several short-range offsets"); return AMG_ENOTIMPL; }
             auto row_of = [&](long p) { return dir == 0 ? p : (long)n - 1 - p; };
             std::vector<int> ts;
             std::vector<unsigned char> any;                         // per task: the OR of its rows' masks (which offsets occur at all)
@@ -2872,20 +2760,20 @@ int amg_hier_gs_natural(amg_hier *h, int lvl, double *x, const double *b, const 
             for (int q = 0; q < nt; ++q) ++first[(size_t)level[(size_t)q] + 1];
             for (int l = 0; l <= top; ++l) first[(size_t)l + 1] += first[(size_t)l];
             for (int q = 0; q < nt; ++q) order[(size_t)first[(size_t)level[(size_t)q]]++] = q;
-            hipError_t eo = hipMalloc((void **)&order_dev[dir], sizeof(int) * (size_t)nt);
-            if (eo == hipSuccess) eo = hipMalloc((void **)&tstart_dev[dir], sizeof(int) * ((size_t)nt + 1));
+            hipError_t eo = order_dev[dir].malloc_bytes(sizeof(int) * (size_t)nt);
+            if (eo == hipSuccess) eo = tstart_dev[dir].malloc_bytes(sizeof(int) * ((size_t)nt + 1));
             if (eo == hipSuccess) eo = hipMemcpy(order_dev[dir], order.data(), sizeof(int) * (size_t)nt, hipMemcpyHostToDevice);
             if (eo == hipSuccess) eo = hipMemcpy(tstart_dev[dir], ts.data(), sizeof(int) * ((size_t)nt + 1), hipMemcpyHostToDevice);
-            if (eo != hipSuccess) { release(); return hip_fail(eo, "natural-order Gauss-Seidel: task order to the device", __FILE__, __LINE__); }
+            if (eo != hipSuccess) return hip_fail(eo, "natural-order Gauss-Seidel: task order to the device", __FILE__, __LINE__);
             ntasks_dir[dir] = nt;
         }
     }
-    double *dx = nullptr, *db = nullptr;
+    DevArr<double> dx, db;
     int rc = 0;
-    hipError_t e = hipMalloc((void **)&dx, sizeof(double) * (size_t)std::max(n, 1));
+    hipError_t e = dx.malloc_bytes(sizeof(double) * (size_t)std::max(n, 1));
     if (e == hipSuccess) e = hipMemcpy(dx, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice);
     if (e == hipSuccess && b) {
-        e = hipMalloc((void **)&db, sizeof(double) * (size_t)std::max(n, 1));
+        e = db.malloc_bytes(sizeof(double) * (size_t)std::max(n, 1));
         if (e == hipSuccess) e = hipMemcpy(db, b, sizeof(double) * (size_t)n, hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) rc = hip_fail(e, "natural-order Gauss-Seidel: vectors to the device", __FILE__, __LINE__);
@@ -2896,9 +2784,6 @@ int amg_hier_gs_natural(amg_hier *h, int lvl, double *x, const double *b, const 
         e = hipMemcpy(x, dx, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = hip_fail(e, "natural-order Gauss-Seidel: result to the host", __FILE__, __LINE__);
     }
-    if (dx) hipFree(dx);
-    if (db) hipFree(db);
-    for (int k = 0; k < 2; ++k) { if (order_dev[k]) hipFree(order_dev[k]); if (tstart_dev[k]) hipFree(tstart_dev[k]); }
     return rc == -40 ? AMG_ENOTIMPL : rc;
 }
 
@@ -2918,19 +2803,16 @@ int amg_arnoldi(amg_hier *h, int lvl, const double *dinv, const double *v0, int 
     hipStream_t st = h->stream;
     if (maxiter > n) maxiter = (int)n;
     if (h->arn_m < maxiter || h->arn_n != n) {
-        if (h->arn_V) hipFree(h->arn_V);
-        if (h->arn_dinv) hipFree(h->arn_dinv);
-        if (h->arn_coef) hipFree(h->arn_coef);
-        h->arn_V = h->arn_dinv = h->arn_coef = nullptr;
+        h->arn_V.reset(); h->arn_dinv.reset(); h->arn_coef.reset();
         h->dev_bytes -= h->arn_bytes;
         h->arn_bytes = 0;
-        CHK(dev_alloc(&h->arn_V, (long)(maxiter + 1) * n, &h->arn_bytes));
-        CHK(dev_alloc(&h->arn_dinv, n, &h->arn_bytes));
-        CHK(dev_alloc(&h->arn_coef, maxiter + 8, &h->arn_bytes));
+        CHK(dev_alloc(h->arn_V, (long)(maxiter + 1) * n, &h->arn_bytes));
+        CHK(dev_alloc(h->arn_dinv, n, &h->arn_bytes));
+        CHK(dev_alloc(h->arn_coef, maxiter + 8, &h->arn_bytes));
         h->dev_bytes += h->arn_bytes;                   // counted while it lives (amg_arnoldi_free gives it back)
         h->arn_m = maxiter; h->arn_n = n;
     }
-    if (!h->norm_scratch) CHK(dev_alloc(&h->norm_scratch, AMG_DEV_SCRATCH, &h->dev_bytes));
+    if (!h->norm_scratch) CHK(dev_alloc(h->norm_scratch, AMG_DEV_SCRATCH, &h->dev_bytes));
     double *V = h->arn_V;
     double *slot = h->norm_scratch + 1026;
     if (dinv) AMG_HIP(hipMemcpyAsync(h->arn_dinv, dinv, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
@@ -2982,15 +2864,14 @@ int amg_arnoldi_combine(amg_hier *h, const double *coef, int m, double *v)
     ENTER(h);
     if (!h->arn_V || m < 1 || m > h->arn_m || !coef) { set_error("bad combine arguments"); return AMG_EINVAL; }
     const long n = h->arn_n;
-    double *tmp = nullptr;
-    CHK(dev_alloc(&tmp, n, (long *)nullptr));
+    DevArr<double> tmp;
+    CHK(dev_alloc(tmp, n, (long *)nullptr));
     AMG_HIP(hipMemcpyAsync(h->arn_coef, coef, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, h->stream));
     int rc = launch_combine(tmp, h->arn_V, h->arn_coef, m, n, n, h->stream);
     if (rc == 0 && v) {
         hipMemcpyAsync(v, tmp, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream);
     }
     hipStreamSynchronize(h->stream);
-    hipFree(tmp);
     return rc;
 }
 
@@ -2998,10 +2879,7 @@ void amg_arnoldi_free(amg_hier *h)
 {
     if (!h) return;
     hipSetDevice(h->device);
-    if (h->arn_V) hipFree(h->arn_V);
-    if (h->arn_dinv) hipFree(h->arn_dinv);
-    if (h->arn_coef) hipFree(h->arn_coef);
-    h->arn_V = h->arn_dinv = h->arn_coef = nullptr;
+    h->arn_V.reset(); h->arn_dinv.reset(); h->arn_coef.reset();
     h->arn_m = 0; h->arn_n = 0;
     h->dev_bytes -= h->arn_bytes;
     h->arn_bytes = 0;

@@ -15,14 +15,15 @@ namespace amg {
 // (tasks of one level concurrently) reproduces the sequential sweep bit for
 // bit; because the conflict relation is symmetric, running the levels in
 // DESCENDING order reproduces the reversed sweep.
+// A schedule owns its device arrays (DevArr members, the forms' included): it frees them when it goes.
 struct Schedule {
     int ntasks = 0;
     std::vector<int> level_ptr;   // host, size nlevels+1, offsets into the task order
     // CSR flavour: rows copied in level order (coalesced streaming per level)
     DevCsr G;                     // permuted rows, ORIGINAL column indices
-    int *rowmap = nullptr;        // device: original row of permuted row
-    int *diagpos = nullptr;       // device: position of the diagonal entry in G (-1 if none)
-    int *level_ptr_dev = nullptr; // device copy of level_ptr (the chained sweep walks the levels on the GPU)
+    DevArr<int> rowmap;        // device: original row of permuted row
+    DevArr<int> diagpos;       // device: position of the diagonal entry in G (-1 if none)
+    DevArr<int> level_ptr_dev; // device copy of level_ptr (the chained sweep walks the levels on the GPU)
     // maximal runs [first, last) of consecutive levels that are all narrow enough for ONE workgroup:
     // such a run is swept by a single launch (gs_chain_kernel) instead of one launch per level
     std::vector<std::pair<int, int>> chains;
@@ -33,19 +34,19 @@ struct Schedule {
     // final in memory long before it is needed and is prefetched), < 0 a slot of the workgroup's LDS ring (the
     // operand was produced by one of the last CHAIN2_D levels of this very launch).
     std::vector<int> gp_host;          // row pointers of G on the host: a level launch gets its workgroups' entry ranges as kernel arguments
-    int *cl_code_f = nullptr, *cl_code_b = nullptr;   // long-row chain with LDS hand-off: per entry of G the column, or ~(ring slot); forward / backward sweep
+    DevArr<int> cl_code_f, cl_code_b;   // long-row chain with LDS hand-off: per entry of G the column, or ~(ring slot); forward / backward sweep
     bool chain_long = false;           // the chains are runs of levels with few but LONG rows: gs_chainl_kernel (entry-parallel, products through LDS)
     bool chain2 = false;
     int c2_pf = 0;                 // slots per row of the copy: 4, 8 or 12
-    int *c2_code_f = nullptr, *c2_code_b = nullptr, *c2_off = nullptr;
-    double *c2_diag = nullptr, *c2_val = nullptr, *c2_dummy = nullptr;   // diag: by level-order position; dummy: where idle lanes store (512 doubles)
+    DevArr<int> c2_code_f, c2_code_b, c2_off;
+    DevArr<double> c2_diag, c2_val, c2_dummy;   // diag: by level-order position; dummy: where idle lanes store (512 doubles)
     // LEVEL-ORDER numbering (unknown k = k-th row of the schedule; only when the schedule lists every unknown once):
     // the sweeps of the second-generation chain run on xp = x[rowmap], bp = b[rowmap] with G's columns renumbered
     bool perm = false;
-    int *perm_Aj = nullptr;
-    double *xp = nullptr, *bp = nullptr, *bd = nullptr;      // bd: (right-hand side, diagonal) pairs for the chained sweep
+    DevArr<int> perm_Aj;
+    DevArr<double> xp, bp, bd;      // bd: (right-hand side, diagonal) pairs for the chained sweep
     // BSR flavour: block rows listed in level order
-    int *rows = nullptr;          // device
+    DevArr<int> rows;          // device
     DevBsr Gb;                    // BSR flavour with values: block rows copied in level order (streamed)
     std::vector<int> gb_level_slice;   // sliced block form of Gb (sell.hip): first slice of every level (empty: not built)
     // dataflow form (gsflow.hip): the whole sequence of directional sweeps as one persistent launch
@@ -53,7 +54,6 @@ struct Schedule {
     BlockFlowForm bflow;               // the same for block Gauss-Seidel over Gb
     bool flow_auto = false;            // the default picks it for this schedule (wide or long-row levels that would be launches)
     int nlevels() const { return (int)level_ptr.size() - 1; }
-    void release();
     void drop_level_copies();          // the dataflow form serves this schedule: free the level-ordered copies of the other paths
     long level_copy_bytes = 0;         // HBM held by those copies (0 after drop_level_copies)
 };
@@ -86,16 +86,16 @@ struct Smoother {
     double omega = 1.0;
     std::vector<double> coef;
     int bs = 1;
-    double *Dinv = nullptr;          // device
+    DevArr<double> Dinv;          // device
     std::vector<int> indices;        // gauss_seidel_indexed
-    DevBsr Ablk;                     // re-blocked A for block smoothers (owned) ...
-    bool Ablk_owned = false;
-    std::shared_ptr<Schedule> sched; // GS-type smoothers
+    DevBsr Ablk;                     // A re-blocked for this smoother; left empty, the smoother reads the level's own blocks (Level::Ab)
+    bool own_blocks() const { return Ablk.Ap != nullptr; }
+    std::shared_ptr<Schedule> sched; // GS-type smoothers (the natural-order ones are shared with the level)
     // schwarz: subdomains + inverse blocks (device), dependency levels of the subdomain tasks
     int nsd = 0;
     std::vector<int> hSj, hSp;       // host copies for the level analysis at finalize
-    int *sw_Sj = nullptr, *sw_Sp = nullptr, *sw_Tp = nullptr, *sw_order = nullptr;
-    double *sw_Tx = nullptr, *sw_scratch = nullptr;
+    DevArr<int> sw_Sj, sw_Sp, sw_Tp, sw_order;
+    DevArr<double> sw_Tx, sw_scratch;
     std::vector<int> sw_level_ptr;
     // normal-equation family: aux[0] = A by columns (CSC arrays; gauss_seidel_nr sweeps it, jacobi_ne
     // gathers through it), aux[1] = A with sorted rows when the level's own copy is not (the residual
@@ -111,15 +111,15 @@ struct Smoother {
 struct Partition {
     int n_own = 0, n_halo = 0;
     int channel = -1;              // halo exchange plan (comm.hpp); -1: nothing to exchange on this level
-    int *send_idx = nullptr;       // device: owned entries the peers need, grouped by destination rank
+    DevArr<int> send_idx;       // device: owned entries the peers need, grouped by destination rank
     int i0 = 0, i1 = 0;            // rows [i0, i1) of A read no halo entry: they run while the halo is in flight
     bool overlap = false;
     // entering the replicated part of the hierarchy: R computes this rank's slice of the coarse right-hand side,
     // all ranks gather the slices
     int gather_channel = -1;
     int gather_rows = 0;
-    int *gather_idx = nullptr;     // device: (0..gather_rows) repeated once per rank
-    double *rslice = nullptr;
+    DevArr<int> gather_idx;     // device: (0..gather_rows) repeated once per rank
+    DevArr<double> rslice;
 };
 
 struct Level {
@@ -130,8 +130,10 @@ struct Level {
     bool hasA = false, hasP = false, hasR = false;
     Smoother sm[2];
     // work vectors (device), length n
-    double *x = nullptr, *xalt = nullptr, *b = nullptr, *r = nullptr, *h = nullptr, *h2 = nullptr;
-    double *amli[4] = {nullptr, nullptr, nullptr, nullptr};   // p0, p1, A*p, A*p_j (AMLI cycles, lazily)
+    DevArr<double> xbuf[2], b, r, h, h2;
+    double *x = nullptr, *xalt = nullptr;  // the iterate and its alternate: views of xbuf[0..1] that Jacobi-type smoothers
+                                           // swap (the graph cache keys on their values); nothing is freed through them
+    DevArr<double> amli[4];   // p0, p1, A*p, A*p_j (AMLI cycles, lazily)
     std::shared_ptr<Schedule> sched_csr, sched_blk;   // natural-order schedules, shared pre/post
     std::shared_ptr<Schedule> sched_bgs;              // block Gauss-Seidel over the level's own blocks, shared pre/post
 };
@@ -171,6 +173,12 @@ struct GraphEntry {
 }  // namespace amg
 
 struct amg_hier {
+    ~amg_hier()
+    {
+        if (ev0) hipEventDestroy(ev0);
+        if (ev1) hipEventDestroy(ev1);
+        if (stream) hipStreamDestroy(stream);
+    }
     int device = 0;
     int nlevels = 0;
     std::vector<amg::Level> lv;
@@ -181,20 +189,20 @@ struct amg_hier {
     amg_coarse_callback coarse_cb = nullptr;   // x = solve(A_coarse, b) on HOST vectors (Krylov names, callables: <= a few hundred rows)
     void *coarse_cb_user = nullptr;
     std::vector<double> coarse_hb, coarse_hx;
-    double *coarse_Mt = nullptr;
+    amg::DevArr<double> coarse_Mt;
     int coarse_n = 0;
     amg::Smoother coarse_sm;
     // scratch
-    double *norm_scratch = nullptr;   // AMG_DEV_SCRATCH doubles: 1024 partials, 8 result slots
-    double *pcg[4] = {nullptr, nullptr, nullptr, nullptr};   // x, r, p, A*p of the device PCG (lazily)
-    double *sumsq_partials = nullptr; // one partial per workgroup of the level-0 residual kernel
+    amg::DevArr<double> norm_scratch;   // AMG_DEV_SCRATCH doubles: 1024 partials, 8 result slots
+    amg::DevArr<double> pcg[4];   // x, r, p, A*p of the device PCG (lazily)
+    amg::DevArr<double> sumsq_partials; // one partial per workgroup of the level-0 residual kernel
     long sumsq_cap = 0;
-    double *res_dev = nullptr;        // residual history on device
+    amg::DevArr<double> res_dev;        // residual history on device
     int res_cap = 0;
     // Arnoldi workspace for setup-time spectral-radius estimates
-    double *arn_V = nullptr;          // (arn_m + 1) vectors of length arn_n
-    double *arn_dinv = nullptr;
-    double *arn_coef = nullptr;
+    amg::DevArr<double> arn_V;          // (arn_m + 1) vectors of length arn_n
+    amg::DevArr<double> arn_dinv;
+    amg::DevArr<double> arn_coef;
     int arn_m = 0;
     long arn_n = 0;
     long arn_bytes = 0;               // HBM held by the workspace (part of dev_bytes while it lives)
@@ -210,13 +218,13 @@ struct amg_hier {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double last_ms = 0.0;
     long dev_bytes = 0;
-    // row-partitioned mode (amg_hier_set_comm): not owned
+    // row-partitioned mode (amg_hier_set_comm): the caller's communicator, borrowed
     amg_comm *comm = nullptr;
     int reduce_channel = -1;                     // 1 x 1 channel for the residual-norm all-reduce
     // a PARTITIONED coarsest level with a dense coarse solver: all ranks gather the right-hand side, apply the
     // dense operator redundantly (bit-identical everywhere) and keep their slice of the result
     int coarse_gather_channel = -1, coarse_lo = 0;
-    int *coarse_gather_idx = nullptr;
-    double *coarse_full_b = nullptr, *coarse_full_x = nullptr;
+    amg::DevArr<int> coarse_gather_idx;
+    amg::DevArr<double> coarse_full_b, coarse_full_x;
     int overlap = 1;                             // interior rows while the halo is in flight
 };

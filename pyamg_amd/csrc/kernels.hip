@@ -14,7 +14,7 @@
 // storage order.  Short rows (7-pt stencil) and long rows (30-60 nnz on coarse
 // SA levels) go through the same path; a slice longer than the tile is
 // processed in several passes with the running sums kept in registers.
-#include "driver.hpp"
+#include "amg_dev.hpp"
 
 namespace amg {
 

@@ -9,7 +9,6 @@
 // jacobi_ne scatters into temp; here each temp entry gathers its contributions
 // through the transposed pattern in the same (row, position) order.
 #include "hier.hpp"
-#include "driver.hpp"
 
 #include <algorithm>
 #include <cstring>

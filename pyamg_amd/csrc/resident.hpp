@@ -95,8 +95,7 @@ struct Core {
     {
         if (nres_cap >= maxiter + 2) return 0;
         pool.bytes -= (long)sizeof(double) * nres_cap * per_slot;
-        if (res.p) AMG_HIP(hipFree(res.p));
-        res.p = nullptr;
+        res.reset();
         nres_cap = 0;
         CHK(pool.alloc(res, sizeof(double) * (size_t)(maxiter + 2) * per_slot));
         nres_cap = maxiter + 2;

@@ -10,7 +10,6 @@
 // bit-identical to the sequential loop.  The conflict relation is symmetric, so the levels in
 // descending order are the backward sweep.
 #include "hier.hpp"
-#include "driver.hpp"
 
 #include <algorithm>
 #include <cstring>

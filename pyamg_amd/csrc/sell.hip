@@ -17,7 +17,6 @@
 // operands (b[row], v2[row]); (3) the gathered operands; (2) and (3) again for rows of more than SL_PASS entries;
 // (4) the store.
 #include "hier.hpp"
-#include "driver.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -282,13 +281,8 @@ int g_sell_idx16 = std::getenv("AMG_SELL_IDX16") ? std::atoi(std::getenv("AMG_SE
 
 void free_sell(DevCsr &M)
 {
-    if (M.sl_slot) hipFree(M.sl_slot);
-    if (M.sl_hdr) hipFree(M.sl_hdr);
-    if (M.sl_col) hipFree(M.sl_col);
-    if (M.sl_val) hipFree(M.sl_val);
-    if (M.sl_code) hipFree(M.sl_code);
-    M.sl_slot = nullptr; M.sl_hdr = nullptr; M.sl_col = nullptr; M.sl_val = nullptr;
-    M.sl_code = nullptr; M.sl_frac16 = 0.0;
+    M.sl_slot.reset(); M.sl_hdr.reset(); M.sl_col.reset(); M.sl_val.reset();
+    M.sl_code.reset(); M.sl_frac16 = 0.0;
     M.sl_nslices = 0; M.sl_entries = 0; M.sl_lo = M.sl_hi = 0;
 }
 
@@ -343,8 +337,8 @@ int build_sell(DevCsr &M, long *acct, int row_lo, int row_hi)
     const int sigma = (M.ncols >= 2L * M.nrows) ? SL_SIGMA_RECT : SL_SIGMA_SQUARE;
     const int nwin = (n + sigma - 1) / sigma;
     const int nslices = nwin * (sigma / SL_C);
-    int *w_dev = nullptr;
-    SellSlot *slot = nullptr;
+    DevArr<int> w_dev;
+    DevArr<SellSlot> slot;
     // longest row must fit the 11 + 21-bit sort key; average row length 8 .. 48 (see above)
     long nnz_range = 0;
     {
@@ -356,14 +350,14 @@ int build_sell(DevCsr &M, long *acct, int row_lo, int row_hi)
         nnz_range = (long)hp[(size_t)n] - hp[0];
     }
     if (n < (1 << 16) || nnz_range < 8L * n || nnz_range > 48L * n) return 0;
-    AMG_HIP(hipMalloc((void **)&slot, sizeof(SellSlot) * (size_t)nslices * SL_C));
-    AMG_HIP(hipMalloc((void **)&w_dev, sizeof(int) * (size_t)nslices));
+    AMG_HIP(slot.malloc_bytes(sizeof(SellSlot) * (size_t)nslices * SL_C));
+    AMG_HIP(w_dev.malloc_bytes(sizeof(int) * (size_t)nslices));
     if (sigma == SL_SIGMA_RECT) hipLaunchKernelGGL((sell_sort_kernel<SL_SIGMA_RECT>), dim3(nwin), dim3(64), 0, nullptr, row_lo, n, M.Ap, slot, w_dev);
     else hipLaunchKernelGGL((sell_sort_kernel<SL_SIGMA_SQUARE>), dim3(nwin), dim3(256), 0, nullptr, row_lo, n, M.Ap, slot, w_dev);
     LAUNCH_CHECK("sell sort launch");
     std::vector<int> hw((size_t)nslices);
     AMG_HIP(hipMemcpy(hw.data(), w_dev, sizeof(int) * (size_t)nslices, hipMemcpyDeviceToHost));
-    hipFree(w_dev);
+    w_dev.reset();
     // headers: entry offsets now; code-word offsets, origins and flags when the codes are built
     std::vector<SellHdr> hdr((size_t)nslices);
     long entries = 0;
@@ -373,38 +367,37 @@ int build_sell(DevCsr &M, long *acct, int row_lo, int row_hi)
         hdr[(size_t)s].w = hw[(size_t)s];
         entries += (long)hw[(size_t)s] * SL_C;
     }
-    if ((double)entries > 1.15 * (double)nnz_range) { hipFree(slot); return 0; }
+    if ((double)entries > 1.15 * (double)nnz_range) return 0;
     const bool want16 = g_sell_idx16 && M.ncols >= 4096;
     long words = 0;
     if (want16)           // 16-bit column codes, two per word: ceil(width / 2) rows of 64 words per slice
         for (int s = 0; s < nslices; ++s) { hdr[(size_t)s].coff = words; words += (long)((hw[(size_t)s] + 1) / 2) * SL_C; }
-    SellHdr *hdr_dev = nullptr;
-    int *col = nullptr;
-    double *val = nullptr;
-    AMG_HIP(hipMalloc((void **)&hdr_dev, sizeof(SellHdr) * (size_t)nslices));
-    AMG_HIP(hipMalloc((void **)&col, sizeof(int) * (size_t)std::max(entries, 1L)));
-    AMG_HIP(hipMalloc((void **)&val, sizeof(double) * (size_t)std::max(entries, 1L)));
+    DevArr<SellHdr> hdr_dev;
+    DevArr<int> col;
+    DevArr<double> val;
+    AMG_HIP(hdr_dev.malloc_bytes(sizeof(SellHdr) * (size_t)nslices));
+    AMG_HIP(col.malloc_bytes(sizeof(int) * (size_t)std::max(entries, 1L)));
+    AMG_HIP(val.malloc_bytes(sizeof(double) * (size_t)std::max(entries, 1L)));
     AMG_HIP(hipMemcpy(hdr_dev, hdr.data(), sizeof(SellHdr) * (size_t)nslices, hipMemcpyHostToDevice));
     const int bgrid = (nslices + SL_WG / SL_C - 1) / (SL_WG / SL_C);
     hipLaunchKernelGGL(sell_fill_kernel, dim3(bgrid), dim3(SL_WG), 0, nullptr, nslices, M.Ap, M.Aj, M.Ax, slot, hdr_dev, col, val);
     LAUNCH_CHECK("sell fill launch");
     AMG_HIP(hipDeviceSynchronize());
-    M.sl_slot = slot; M.sl_hdr = hdr_dev; M.sl_col = col; M.sl_val = val;
+    M.sl_slot = std::move(slot); M.sl_hdr = std::move(hdr_dev); M.sl_col = std::move(col); M.sl_val = std::move(val);
     M.sl_nslices = nslices; M.sl_entries = entries; M.sl_lo = row_lo; M.sl_hi = row_hi;
     if (want16) {
-        AMG_HIP(hipMalloc((void **)&M.sl_code, sizeof(unsigned) * (size_t)std::max(words, 1L)));
-        hipLaunchKernelGGL(sell_code_kernel, dim3(bgrid), dim3(SL_WG), 0, nullptr, nslices, slot, hdr_dev, col, M.sl_code);
+        AMG_HIP(M.sl_code.malloc_bytes(sizeof(unsigned) * (size_t)std::max(words, 1L)));
+        hipLaunchKernelGGL(sell_code_kernel, dim3(bgrid), dim3(SL_WG), 0, nullptr, nslices, M.sl_slot, M.sl_hdr, M.sl_col, M.sl_code);
         LAUNCH_CHECK("sell code launch");
         std::vector<SellHdr> back((size_t)nslices);
-        AMG_HIP(hipMemcpy(back.data(), hdr_dev, sizeof(SellHdr) * (size_t)nslices, hipMemcpyDeviceToHost));
+        AMG_HIP(hipMemcpy(back.data(), M.sl_hdr, sizeof(SellHdr) * (size_t)nslices, hipMemcpyDeviceToHost));
         long coded = 0;
         for (const SellHdr &r : back) coded += r.coded ? 1 : 0;
         M.sl_frac16 = nslices ? (double)coded / (double)nslices : 0.0;
         if (M.sl_frac16 < 0.5) {                                    // mostly fall-back slices: not worth the second array
-            hipFree(M.sl_code);
-            M.sl_code = nullptr; M.sl_frac16 = 0.0;
+            M.sl_code.reset(); M.sl_frac16 = 0.0;
             for (SellHdr &r : hdr) r.coff = 0;                       // headers as of an operator without codes
-            AMG_HIP(hipMemcpy(hdr_dev, hdr.data(), sizeof(SellHdr) * (size_t)nslices, hipMemcpyHostToDevice));
+            AMG_HIP(hipMemcpy(M.sl_hdr, hdr.data(), sizeof(SellHdr) * (size_t)nslices, hipMemcpyHostToDevice));
         } else if (acct) *acct += 4L * words;
     }
     if (acct) *acct += (long)(sizeof(SellSlot) * (size_t)nslices * SL_C + sizeof(SellHdr) * (size_t)nslices + 12L * entries);
@@ -608,10 +601,10 @@ int build_bsell_bs(DevBsr &M, long *acct, const std::vector<int> *level_ptr = nu
     }
     const int nwin = level_ptr ? (int)ws.size() : (nb + WIN - 1) / WIN;
     const int nslices = nwin * BSL_WIN;
-    int *ws_dev = nullptr, *wl_dev = nullptr;
+    DevArr<int> ws_dev, wl_dev;
     if (level_ptr && nwin > 0) {
-        AMG_HIP(hipMalloc((void **)&ws_dev, sizeof(int) * (size_t)nwin));
-        AMG_HIP(hipMalloc((void **)&wl_dev, sizeof(int) * (size_t)nwin));
+        AMG_HIP(ws_dev.malloc_bytes(sizeof(int) * (size_t)nwin));
+        AMG_HIP(wl_dev.malloc_bytes(sizeof(int) * (size_t)nwin));
         AMG_HIP(hipMemcpy(ws_dev, ws.data(), sizeof(int) * (size_t)nwin, hipMemcpyHostToDevice));
         AMG_HIP(hipMemcpy(wl_dev, wl.data(), sizeof(int) * (size_t)nwin, hipMemcpyHostToDevice));
     }
@@ -622,26 +615,26 @@ int build_bsell_bs(DevBsr &M, long *acct, const std::vector<int> *level_ptr = nu
         for (int i = 0; i < nb; ++i) longest = std::max(longest, hp[(size_t)i + 1] - hp[(size_t)i]);
         if (longest > 60000) return 0;
     }
-    int *brow = nullptr, *w_dev = nullptr;
-    unsigned short *blen = nullptr;
-    AMG_HIP(hipMalloc((void **)&brow, sizeof(int) * (size_t)nslices * NBR));
-    AMG_HIP(hipMalloc((void **)&blen, sizeof(unsigned short) * (size_t)nslices * NBR));
-    AMG_HIP(hipMalloc((void **)&w_dev, sizeof(int) * (size_t)nslices));
+    DevArr<int> brow, w_dev;
+    DevArr<unsigned short> blen;
+    AMG_HIP(brow.malloc_bytes(sizeof(int) * (size_t)nslices * NBR));
+    AMG_HIP(blen.malloc_bytes(sizeof(unsigned short) * (size_t)nslices * NBR));
+    AMG_HIP(w_dev.malloc_bytes(sizeof(int) * (size_t)nslices));
     hipLaunchKernelGGL((bsell_sort_kernel<NBR>), dim3(nwin), dim3(1024), 0, nullptr, nb, M.Ap, brow, blen, w_dev, (const int *)ws_dev, (const int *)wl_dev);
     LAUNCH_CHECK("bsell sort launch");
     std::vector<int> hw((size_t)nslices);
     AMG_HIP(hipMemcpy(hw.data(), w_dev, sizeof(int) * (size_t)nslices, hipMemcpyDeviceToHost));
-    hipFree(w_dev);
+    w_dev.reset();
     std::vector<long> off((size_t)nslices + 1);
     off[0] = 0;
     for (int s = 0; s < nslices; ++s) off[(size_t)s + 1] = off[(size_t)s] + hw[(size_t)s];
     const long cols = off[(size_t)nslices];                          // block slot columns
-    if (ws_dev) { hipFree(ws_dev); hipFree(wl_dev); }
-    if ((double)cols * NBR > (level_ptr ? 1.3 : 1.15) * (double)M.nblocks) { hipFree(brow); hipFree(blen); return 0; }
-    long *off_dev = nullptr; int *col = nullptr; double *val = nullptr;
-    AMG_HIP(hipMalloc((void **)&off_dev, sizeof(long) * ((size_t)nslices + 1)));
-    AMG_HIP(hipMalloc((void **)&col, sizeof(int) * (size_t)std::max(cols * NBR, 1L)));
-    AMG_HIP(hipMalloc((void **)&val, sizeof(double) * (size_t)std::max(cols * BS * NBR * BS, 1L)));
+    ws_dev.reset(); wl_dev.reset();
+    if ((double)cols * NBR > (level_ptr ? 1.3 : 1.15) * (double)M.nblocks) return 0;
+    DevArr<long> off_dev; DevArr<int> col; DevArr<double> val;
+    AMG_HIP(off_dev.malloc_bytes(sizeof(long) * ((size_t)nslices + 1)));
+    AMG_HIP(col.malloc_bytes(sizeof(int) * (size_t)std::max(cols * NBR, 1L)));
+    AMG_HIP(val.malloc_bytes(sizeof(double) * (size_t)std::max(cols * BS * NBR * BS, 1L)));
     AMG_HIP(hipMemcpy(off_dev, off.data(), sizeof(long) * ((size_t)nslices + 1), hipMemcpyHostToDevice));
     hipLaunchKernelGGL((bsell_fill_kernel<BS>), dim3((nslices + 3) / 4), dim3(256), 0, nullptr, nslices, M.Ap, M.Aj, M.Ax, brow, blen, off_dev, col, val);
     LAUNCH_CHECK("bsell fill launch");
@@ -650,22 +643,13 @@ int build_bsell_bs(DevBsr &M, long *acct, const std::vector<int> *level_ptr = nu
         hipLaunchKernelGGL(bsell_remap_kernel, dim3((nslots + 255) / 256), dim3(256), 0, nullptr, nslots, rowmap_dev, brow);
     }
     AMG_HIP(hipDeviceSynchronize());
-    M.bsl_brow = brow; M.bsl_len = blen; M.bsl_off = off_dev; M.bsl_col = col; M.bsl_val = val; M.bsl_nslices = nslices;
+    M.bsl_brow = std::move(brow); M.bsl_len = std::move(blen); M.bsl_off = std::move(off_dev); M.bsl_col = std::move(col); M.bsl_val = std::move(val);
+    M.bsl_nslices = nslices;
     if (acct) *acct += (long)(6L * nslices * NBR + 8L * (nslices + 1) + 4L * cols * NBR + 8L * cols * BS * NBR * BS);
     return 0;
 }
 
 }   // namespace
-
-void free_bsell(DevBsr &M)
-{
-    if (M.bsl_brow) hipFree(M.bsl_brow);
-    if (M.bsl_len) hipFree(M.bsl_len);
-    if (M.bsl_off) hipFree(M.bsl_off);
-    if (M.bsl_col) hipFree(M.bsl_col);
-    if (M.bsl_val) hipFree(M.bsl_val);
-    M.bsl_brow = nullptr; M.bsl_len = nullptr; M.bsl_off = nullptr; M.bsl_col = nullptr; M.bsl_val = nullptr; M.bsl_nslices = 0;
-}
 
 // from the BSR arrays in HBM; blocks of 2x2 and 3x3, at least 2^15 block rows of 4 to 48 blocks on average
 int build_bsell(DevBsr &M, long *acct)

@@ -11,7 +11,6 @@
 // row.  Bit-identical to the host restatement (setup_host.cpp amgsetup_csr_matmat_*) and to scipy: same products, same
 // order, separate multiply and add.
 #include "hier.hpp"
-#include "driver.hpp"
 #include "scalar.hpp"
 
 #include <algorithm>
@@ -57,26 +56,24 @@ __device__ __forceinline__ bool vnz(double a) { return a != 0.0; }
 __device__ __forceinline__ bool vnz(c128 a) { return sc::nonzero(a); }
 
 template <class V>
-struct DCsrT {             // a CSR operand in HBM (row pointer as 64-bit offsets)
+struct DCsrView {          // a CSR operand in HBM that somebody else owns (row pointer as 64-bit offsets)
     int n_row = 0, n_col = 0;
     long nnz = 0;
-    long *Ap = nullptr;
-    int *Aj = nullptr;
-    V *Ax = nullptr;
-    bool owned = true;
+    const long *Ap = nullptr;
+    const int *Aj = nullptr;
+    const V *Ax = nullptr;
+};
+template <class V>
+struct DCsrT {             // the same, owning its arrays
+    int n_row = 0, n_col = 0;
+    long nnz = 0;
+    DevArr<long> Ap;
+    DevArr<int> Aj;
+    DevArr<V> Ax;
+    using View = DCsrView<V>;
+    operator View() const { return View{n_row, n_col, nnz, Ap, Aj, Ax}; }
 };
 using DCsr = DCsrT<double>;
-
-template <class V>
-void dcsr_free(DCsrT<V> &M)
-{
-    if (M.owned) {
-        if (M.Ap) hipFree(M.Ap);
-        if (M.Aj) hipFree(M.Aj);
-        if (M.Ax) hipFree(M.Ax);
-    }
-    M.Ap = nullptr; M.Aj = nullptr; M.Ax = nullptr;
-}
 
 // largest number of products of any output row (sizes the tables)
 __global__ void spgemm_upper_kernel(int n_row, const long *Ap, const int *Aj, const long *Bp, int *row_upper)
@@ -326,9 +323,9 @@ template <class V>
 int upload_dcsr(DCsrT<V> &M, int n_row, int n_col, const long *Ap, const int *Aj, const V *Ax)
 {
     M.n_row = n_row; M.n_col = n_col; M.nnz = Ap[n_row];
-    AMG_HIP(hipMalloc((void **)&M.Ap, sizeof(long) * ((size_t)n_row + 1)));
-    AMG_HIP(hipMalloc((void **)&M.Aj, sizeof(int) * (size_t)std::max(M.nnz, 1L)));
-    AMG_HIP(hipMalloc((void **)&M.Ax, sizeof(V) * (size_t)std::max(M.nnz, 1L)));
+    AMG_HIP(M.Ap.malloc_bytes(sizeof(long) * ((size_t)n_row + 1)));
+    AMG_HIP(M.Aj.malloc_bytes(sizeof(int) * (size_t)std::max(M.nnz, 1L)));
+    AMG_HIP(M.Ax.malloc_bytes(sizeof(V) * (size_t)std::max(M.nnz, 1L)));
     AMG_HIP(hipMemcpy(M.Ap, Ap, sizeof(long) * ((size_t)n_row + 1), hipMemcpyHostToDevice));
     AMG_HIP(hipMemcpy(M.Aj, Aj, sizeof(int) * (size_t)M.nnz, hipMemcpyHostToDevice));
     AMG_HIP(hipMemcpy(M.Ax, Ax, sizeof(V) * (size_t)M.nnz, hipMemcpyHostToDevice));
@@ -337,7 +334,7 @@ int upload_dcsr(DCsrT<V> &M, int n_row, int n_col, const long *Ap, const int *Aj
 
 // C = A * B, both in HBM; C allocated here
 template <class V>
-int matmat(const DCsrT<V> &A, const DCsrT<V> &B, DCsrT<V> &C)
+int matmat(const typename DCsrT<V>::View &A, const typename DCsrT<V>::View &B, DCsrT<V> &C)
 {
     if (A.n_col != B.n_row) { set_error("spgemm: inner dimensions differ"); return AMG_EINVAL; }
     C.n_row = A.n_row; C.n_col = B.n_col;
@@ -345,17 +342,17 @@ int matmat(const DCsrT<V> &A, const DCsrT<V> &B, DCsrT<V> &C)
     constexpr bool CPLX = !std::is_same<V, double>::value;
     constexpr long ENTRY = 8 + (long)sizeof(V);                 // bytes of a table entry: key, place in the order list, sum
     if (CPLX && n == 0) {                                       // no rows: the empty product (complex entries only)
-        C.nnz = 0; C.Aj = nullptr; C.Ax = nullptr;
-        AMG_HIP(hipMalloc((void **)&C.Ap, sizeof(long)));
+        C.nnz = 0; C.Aj.reset(); C.Ax.reset();
+        AMG_HIP(C.Ap.malloc_bytes(sizeof(long)));
         AMG_HIP(hipMemset(C.Ap, 0, sizeof(long)));
         return 0;
     }
-    int *upper = nullptr;
-    AMG_HIP(hipMalloc((void **)&upper, sizeof(int) * (size_t)std::max(n, 1)));
+    DevArr<int> upper;
+    AMG_HIP(upper.malloc_bytes(sizeof(int) * (size_t)std::max(n, 1)));
     hipLaunchKernelGGL(spgemm_upper_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, n, A.Ap, A.Aj, B.Ap, upper);
     std::vector<int> hu((size_t)n);
     AMG_HIP(hipMemcpy(hu.data(), upper, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
-    hipFree(upper);
+    upper.reset();
     const int max_upper = n ? *std::max_element(hu.begin(), hu.end()) : 0;
     int cap = 64;
     while (cap < 2 * max_upper && cap < (1 << 30)) cap <<= 1;
@@ -365,9 +362,9 @@ int matmat(const DCsrT<V> &A, const DCsrT<V> &B, DCsrT<V> &C)
     const int G0r = avgB <= 10.0 ? 8 : (avgB <= 20.0 ? 16 : (avgB <= 40.0 ? 32 : 64));
     const int G0 = CPLX ? std::min(64, 2 * G0r) : G0r;             // complex: one step wider (wave_cap)
     for (int G = G0; G <= 64; G = (G == 64 ? 128 : 64)) {          // the preferred width, then the whole wave per row
-        int *count = nullptr, *overflow = nullptr;
-        AMG_HIP(hipMalloc((void **)&count, sizeof(int) * (size_t)std::max(n, 1)));
-        AMG_HIP(hipMalloc((void **)&overflow, sizeof(int)));
+        DevArr<int> count, overflow;
+        AMG_HIP(count.malloc_bytes(sizeof(int) * (size_t)std::max(n, 1)));
+        AMG_HIP(overflow.malloc_bytes(sizeof(int)));
         AMG_HIP(hipMemset(overflow, 0, sizeof(int)));
         const int rows_per_wave = 64 / G;
         const int blocks = (int)std::min<long>(((long)n + rows_per_wave - 1) / rows_per_wave, 256L * 2 * 8);
@@ -376,7 +373,7 @@ int matmat(const DCsrT<V> &A, const DCsrT<V> &B, DCsrT<V> &C)
                                                   (V *)nullptr, (int *)nullptr, 0)
 #define GROUP_DISPATCH(FILL) do { if (G == 8) { if constexpr (!CPLX) GROUP_LAUNCH(FILL, 8); } else if (G == 16) GROUP_LAUNCH(FILL, 16); \
                                   else if (G == 32) GROUP_LAUNCH(FILL, 32); else GROUP_LAUNCH(FILL, 64); } while (0)
-        C.Ap = nullptr; C.Aj = nullptr; C.Ax = nullptr;
+        C.Ap.reset(); C.Aj.reset(); C.Ax.reset();
         GROUP_DISPATCH(false);
         LAUNCH_CHECK("spgemm group count launch");
         int ovf = 0;
@@ -391,19 +388,17 @@ int matmat(const DCsrT<V> &A, const DCsrT<V> &B, DCsrT<V> &C)
             cp[0] = 0;
             for (int i = 0; i < n; ++i) cp[(size_t)i + 1] = cp[(size_t)i] + hc[(size_t)i];
             C.nnz = cp[(size_t)n];
-            AMG_HIP(hipMalloc((void **)&C.Ap, sizeof(long) * ((size_t)n + 1)));
-            AMG_HIP(hipMalloc((void **)&C.Aj, sizeof(int) * (size_t)std::max(C.nnz, 1L)));
-            AMG_HIP(hipMalloc((void **)&C.Ax, sizeof(V) * (size_t)std::max(C.nnz, 1L)));
+            AMG_HIP(C.Ap.malloc_bytes(sizeof(long) * ((size_t)n + 1)));
+            AMG_HIP(C.Aj.malloc_bytes(sizeof(int) * (size_t)std::max(C.nnz, 1L)));
+            AMG_HIP(C.Ax.malloc_bytes(sizeof(V) * (size_t)std::max(C.nnz, 1L)));
             AMG_HIP(hipMemcpy(C.Ap, cp.data(), sizeof(long) * ((size_t)n + 1), hipMemcpyHostToDevice));
             GROUP_DISPATCH(true);
             LAUNCH_CHECK("spgemm group fill launch");
             AMG_HIP(hipDeviceSynchronize());
-            hipFree(count); hipFree(overflow);
             return 0;
         }
 #undef GROUP_DISPATCH
 #undef GROUP_LAUNCH
-        hipFree(count); hipFree(overflow);
     }
     // whole wave per row with the row's table in HBM: long rows on a small level (a few thousand rows of tens of
     // thousands of products -- the coarse Galerkin products)
@@ -412,16 +407,16 @@ int matmat(const DCsrT<V> &A, const DCsrT<V> &B, DCsrT<V> &C)
         int gcap = 1024;
         while (gcap < 2 * distinct_bound + 256) gcap <<= 1;
         const int blocks = (int)std::max<long>(1, std::min<long>(std::min<long>(n, 1024), (4L << 30) / ((long)gcap * ENTRY)));
-        int *count = nullptr, *overflow = nullptr, *gkey = nullptr, *gord = nullptr;
-        V *gsum = nullptr;
-        AMG_HIP(hipMalloc((void **)&count, sizeof(int) * (size_t)std::max(n, 1)));
-        AMG_HIP(hipMalloc((void **)&overflow, sizeof(int)));
+        DevArr<int> count, overflow, gkey, gord;
+        DevArr<V> gsum;
+        AMG_HIP(count.malloc_bytes(sizeof(int) * (size_t)std::max(n, 1)));
+        AMG_HIP(overflow.malloc_bytes(sizeof(int)));
         AMG_HIP(hipMemset(overflow, 0, sizeof(int)));
-        AMG_HIP(hipMalloc((void **)&gkey, sizeof(int) * (size_t)blocks * gcap));
-        AMG_HIP(hipMalloc((void **)&gord, sizeof(int) * (size_t)blocks * gcap));
-        AMG_HIP(hipMalloc((void **)&gsum, sizeof(V) * (size_t)blocks * gcap));
+        AMG_HIP(gkey.malloc_bytes(sizeof(int) * (size_t)blocks * gcap));
+        AMG_HIP(gord.malloc_bytes(sizeof(int) * (size_t)blocks * gcap));
+        AMG_HIP(gsum.malloc_bytes(sizeof(V) * (size_t)blocks * gcap));
         AMG_HIP(hipMemset(gkey, 0xFF, sizeof(int) * (size_t)blocks * gcap));
-        C.Ap = nullptr; C.Aj = nullptr; C.Ax = nullptr;
+        C.Ap.reset(); C.Aj.reset(); C.Ax.reset();
         hipLaunchKernelGGL((spgemm_group_kernel<V, false, 64, true>), dim3(blocks), dim3(64), 0, nullptr, n, A.Ap, A.Aj, A.Ax, B.Ap, B.Aj, B.Ax,
                            count, (const long *)nullptr, (int *)nullptr, (V *)nullptr, overflow, gkey, gsum, gord, gcap);
         LAUNCH_CHECK("spgemm HBM-table count launch");
@@ -438,16 +433,15 @@ int matmat(const DCsrT<V> &A, const DCsrT<V> &B, DCsrT<V> &C)
             cp[0] = 0;
             for (int i = 0; i < n; ++i) cp[(size_t)i + 1] = cp[(size_t)i] + hc[(size_t)i];
             C.nnz = cp[(size_t)n];
-            AMG_HIP(hipMalloc((void **)&C.Ap, sizeof(long) * ((size_t)n + 1)));
-            AMG_HIP(hipMalloc((void **)&C.Aj, sizeof(int) * (size_t)std::max(C.nnz, 1L)));
-            AMG_HIP(hipMalloc((void **)&C.Ax, sizeof(V) * (size_t)std::max(C.nnz, 1L)));
+            AMG_HIP(C.Ap.malloc_bytes(sizeof(long) * ((size_t)n + 1)));
+            AMG_HIP(C.Aj.malloc_bytes(sizeof(int) * (size_t)std::max(C.nnz, 1L)));
+            AMG_HIP(C.Ax.malloc_bytes(sizeof(V) * (size_t)std::max(C.nnz, 1L)));
             AMG_HIP(hipMemcpy(C.Ap, cp.data(), sizeof(long) * ((size_t)n + 1), hipMemcpyHostToDevice));
             hipLaunchKernelGGL((spgemm_group_kernel<V, true, 64, true>), dim3(blocks), dim3(64), 0, nullptr, n, A.Ap, A.Aj, A.Ax, B.Ap, B.Aj, B.Ax,
                                count, (const long *)C.Ap, C.Aj, C.Ax, overflow, gkey, gsum, gord, gcap);
             rc = launched("spgemm HBM-table fill launch");
             if (hipDeviceSynchronize() != hipSuccess && rc == 0) rc = AMG_ENODEV;
         }
-        hipFree(count); hipFree(overflow); hipFree(gkey); hipFree(gord); hipFree(gsum);
         if (!ovf) return rc;
     }
     if (!(max_upper <= 1024 || (double)n * (double)cap * (double)ENTRY <= 2.0e9)) {
@@ -456,19 +450,18 @@ int matmat(const DCsrT<V> &A, const DCsrT<V> &B, DCsrT<V> &C)
     }
     // first tier: 256-entry tables (up to 128 distinct columns per row), 65536 threads
     struct Tables {
-        int *keys = nullptr, *order = nullptr; V *sums = nullptr; int cap = 0; long threads = 0; int blocks = 0;
+        DevArr<int> keys, order; DevArr<V> sums; int cap = 0; long threads = 0; int blocks = 0;
         int make(int cap_, long want_threads)
         {
             cap = cap_;
             blocks = (int)((std::max<long>(256, want_threads) + 255) / 256);
             threads = (long)blocks * 256;
-            AMG_HIP(hipMalloc((void **)&keys, sizeof(int) * (size_t)(threads * cap)));
-            AMG_HIP(hipMalloc((void **)&order, sizeof(int) * (size_t)(threads * cap)));
-            AMG_HIP(hipMalloc((void **)&sums, sizeof(V) * (size_t)(threads * cap)));
+            AMG_HIP(keys.malloc_bytes(sizeof(int) * (size_t)(threads * cap)));
+            AMG_HIP(order.malloc_bytes(sizeof(int) * (size_t)(threads * cap)));
+            AMG_HIP(sums.malloc_bytes(sizeof(V) * (size_t)(threads * cap)));
             AMG_HIP(hipMemset(keys, 0xFF, sizeof(int) * (size_t)(threads * cap)));
             return 0;
         }
-        void drop() { if (keys) hipFree(keys); if (order) hipFree(order); if (sums) hipFree(sums); keys = order = nullptr; sums = nullptr; }
     };
     const int small_cap = std::min(cap, 256);
     if (std::getenv("AMG_SETUP_VERBOSE") && std::getenv("AMG_SETUP_VERBOSE")[0] != '0')
@@ -476,8 +469,8 @@ int matmat(const DCsrT<V> &A, const DCsrT<V> &B, DCsrT<V> &C)
                      A.n_row, B.n_col, CPLX ? " (complex128)" : "", small_cap, cap);
     Tables T1, T2;
     CHK(T1.make(small_cap, std::min<long>(65536, n)));
-    int *count = nullptr, *big_rows = nullptr;
-    AMG_HIP(hipMalloc((void **)&count, sizeof(int) * (size_t)std::max(n, 1)));
+    DevArr<int> count, big_rows;
+    AMG_HIP(count.malloc_bytes(sizeof(int) * (size_t)std::max(n, 1)));
     hipLaunchKernelGGL((spgemm_rows_kernel<V, false>), dim3(T1.blocks), dim3(256), 0, nullptr, n, (const int *)nullptr, A.Ap, A.Aj, A.Ax,
                        B.Ap, B.Aj, B.Ax, T1.cap, T1.cap / 2, T1.keys, T1.sums, T1.order, count, (const long *)nullptr,
                        (int *)nullptr, (V *)nullptr);
@@ -490,7 +483,7 @@ int matmat(const DCsrT<V> &A, const DCsrT<V> &B, DCsrT<V> &C)
         // second tier: the rows that outgrew the small tables, with tables sized by the longest row's products
         long threads = std::min<long>(256L * 512L, (3L << 30) / ((long)cap * ENTRY));
         CHK(T2.make(cap, std::min<long>(threads, (long)big.size())));
-        AMG_HIP(hipMalloc((void **)&big_rows, sizeof(int) * big.size()));
+        AMG_HIP(big_rows.malloc_bytes(sizeof(int) * big.size()));
         AMG_HIP(hipMemcpy(big_rows, big.data(), sizeof(int) * big.size(), hipMemcpyHostToDevice));
         hipLaunchKernelGGL((spgemm_rows_kernel<V, false>), dim3(T2.blocks), dim3(256), 0, nullptr, (int)big.size(), big_rows, A.Ap, A.Aj, A.Ax,
                            B.Ap, B.Aj, B.Ax, T2.cap, T2.cap / 2, T2.keys, T2.sums, T2.order, count, (const long *)nullptr,
@@ -503,9 +496,9 @@ int matmat(const DCsrT<V> &A, const DCsrT<V> &B, DCsrT<V> &C)
     cp[0] = 0;
     for (int i = 0; i < n; ++i) cp[(size_t)i + 1] = cp[(size_t)i] + hc[(size_t)i];
     C.nnz = cp[(size_t)n];
-    AMG_HIP(hipMalloc((void **)&C.Ap, sizeof(long) * ((size_t)n + 1)));
-    AMG_HIP(hipMalloc((void **)&C.Aj, sizeof(int) * (size_t)std::max(C.nnz, 1L)));
-    AMG_HIP(hipMalloc((void **)&C.Ax, sizeof(V) * (size_t)std::max(C.nnz, 1L)));
+    AMG_HIP(C.Ap.malloc_bytes(sizeof(long) * ((size_t)n + 1)));
+    AMG_HIP(C.Aj.malloc_bytes(sizeof(int) * (size_t)std::max(C.nnz, 1L)));
+    AMG_HIP(C.Ax.malloc_bytes(sizeof(V) * (size_t)std::max(C.nnz, 1L)));
     AMG_HIP(hipMemcpy(C.Ap, cp.data(), sizeof(long) * ((size_t)n + 1), hipMemcpyHostToDevice));
     if (!big.empty()) {
         // mark the large rows in `count` again (the first-tier fill skips rows with count < 0)
@@ -522,9 +515,6 @@ int matmat(const DCsrT<V> &A, const DCsrT<V> &B, DCsrT<V> &C)
         LAUNCH_CHECK("spgemm fill launch (large tables)");
     }
     AMG_HIP(hipDeviceSynchronize());
-    T1.drop(); T2.drop();
-    hipFree(count);
-    if (big_rows) hipFree(big_rows);
     return 0;
 }
 
@@ -538,14 +528,14 @@ __global__ void widen_rowptr_kernel(int n, const int *Ap32, long *Ap64)
 
 namespace amg {
 // C = A * A for a square operand already in HBM (the squarings of the evolution strength measure, strength.hip); the
-// arrays of C are allocated here and belong to the caller
-int spgemm_square_device(int n, long nnz, long *Ap, int *Aj, double *Ax, long *Cnnz, long **Cp, int **Cj, double **Cx)
+// arrays of C are allocated here and move into the caller's owners
+int spgemm_square_device(int n, long nnz, const long *Ap, const int *Aj, const double *Ax, long *Cnnz, DevArr<long> &Cp, DevArr<int> &Cj,
+                         DevArr<double> &Cx)
 {
-    DCsr A, C;
-    A.n_row = n; A.n_col = n; A.nnz = nnz; A.Ap = Ap; A.Aj = Aj; A.Ax = Ax; A.owned = false;
-    const int rc = matmat(A, A, C);
-    if (rc != 0) { dcsr_free(C); return rc; }
-    *Cnnz = C.nnz; *Cp = C.Ap; *Cj = C.Aj; *Cx = C.Ax;
+    const DCsr::View A{n, n, nnz, Ap, Aj, Ax};
+    DCsr C;
+    CHK(matmat(A, A, C));
+    *Cnnz = C.nnz; Cp = std::move(C.Ap); Cj = std::move(C.Aj); Cx = std::move(C.Ax);
     return 0;
 }
 }   // namespace amg
@@ -573,27 +563,28 @@ int amg_hier_galerkin(amg_hier *h, int level, int n_coarse, const int64_t *Rp, c
     AMG_HIP(hipSetDevice(h->device));
     const int n = M.nrows;
     Lap lap;
-    DCsr A, R, P, RA;
-    A.n_row = n; A.n_col = M.ncols; A.nnz = M.nnz; A.Aj = M.Aj; A.Ax = M.Ax; A.owned = false;
-    AMG_HIP(hipMalloc((void **)&A.Ap, sizeof(long) * ((size_t)n + 1)));
-    hipLaunchKernelGGL(widen_rowptr_kernel, dim3((n + 256) / 256), dim3(256), 0, nullptr, n, M.Ap, A.Ap);
+    DCsr R, P, RA;
+    DevArr<long> Ap64;                     // the level's operator as a borrowed operand: its row pointer widened
+    AMG_HIP(Ap64.malloc_bytes(sizeof(long) * ((size_t)n + 1)));
+    hipLaunchKernelGGL(widen_rowptr_kernel, dim3((n + 256) / 256), dim3(256), 0, nullptr, n, M.Ap, Ap64);
+    const DCsr::View A{n, M.ncols, M.nnz, Ap64, M.Aj, M.Ax};
     int rc = upload_dcsr(R, n_coarse, n, (const long *)Rp, Rj, Rx);
     lap("R to HBM");
     if (rc == 0) rc = matmat(R, A, RA);
     lap("R*A");
-    dcsr_free(R);
-    hipFree(A.Ap);
-    if (rc != 0) { dcsr_free(RA); return rc; }
+    R = {};
+    Ap64.reset();
+    if (rc != 0) return rc;
     rc = upload_dcsr(P, n, n_coarse, (const long *)Pp, Pj, Px);
     lap("P to HBM");
     amg_galerkin *g = new amg_galerkin;
     if (rc == 0) rc = matmat(RA, P, g->C);
     lap("(R*A)*P");
-    dcsr_free(P);
-    dcsr_free(RA);
-    if (rc != 0) { dcsr_free(g->C); delete g; return rc; }
+    P = {};
+    RA = {};
+    if (rc != 0) { delete g; return rc; }
     if (hipMemcpy(Cp, g->C.Ap, sizeof(long) * ((size_t)n_coarse + 1), hipMemcpyDeviceToHost) != hipSuccess) {
-        dcsr_free(g->C); delete g;
+        delete g;
         set_error("galerkin: row pointer download failed");
         return AMG_ENODEV;
     }
@@ -613,7 +604,6 @@ int amg_galerkin_fetch(amg_galerkin *g, int *Cj, double *Cx)
             rc = AMG_ENODEV;
         }
     }
-    dcsr_free(g->C);
     delete g;
     return rc;
 }
@@ -628,10 +618,10 @@ int amg_csr_matmat_device(int n_row, int n_inner, int n_col, const int64_t *Ap, 
     if (rc == 0) rc = upload_dcsr(B, n_inner, n_col, (const long *)Bp, Bj, Bx);
     amg_galerkin *g = new amg_galerkin;
     if (rc == 0) rc = matmat(A, B, g->C);
-    dcsr_free(A); dcsr_free(B);
-    if (rc != 0) { dcsr_free(g->C); delete g; return rc; }
+    A = {}; B = {};
+    if (rc != 0) { delete g; return rc; }
     if (hipMemcpy(Cp, g->C.Ap, sizeof(long) * ((size_t)n_row + 1), hipMemcpyDeviceToHost) != hipSuccess) {
-        dcsr_free(g->C); delete g;
+        delete g;
         set_error("matmat: row pointer download failed");
         return AMG_ENODEV;
     }
@@ -654,10 +644,10 @@ int amg_csr_matmat_device_c128(int n_row, int n_inner, int n_col, const int64_t 
     amg_galerkin *g = new amg_galerkin;
     g->is_c128 = true;
     if (rc == 0) rc = matmat(A, B, g->Cz);
-    dcsr_free(A); dcsr_free(B);
-    if (rc != 0) { dcsr_free(g->Cz); delete g; return rc; }
+    A = {}; B = {};
+    if (rc != 0) { delete g; return rc; }
     if (hipMemcpy(Cp, g->Cz.Ap, sizeof(long) * ((size_t)n_row + 1), hipMemcpyDeviceToHost) != hipSuccess) {
-        dcsr_free(g->Cz); delete g;
+        delete g;
         set_error("matmat: row pointer download failed");
         return AMG_ENODEV;
     }
@@ -681,18 +671,18 @@ int amg_galerkin_device_c128(int n_fine, int n_coarse, const int64_t *Rp, const 
     lap("R, A to HBM");
     if (rc == 0) rc = matmat(R, A, RA);
     lap("R*A");
-    dcsr_free(R); dcsr_free(A);
-    if (rc != 0) { dcsr_free(RA); return rc; }
+    R = {}; A = {};
+    if (rc != 0) return rc;
     rc = upload_dcsr(P, n_fine, n_coarse, (const long *)Pp, Pj, (const c128 *)Px);
     lap("P to HBM");
     amg_galerkin *g = new amg_galerkin;
     g->is_c128 = true;
     if (rc == 0) rc = matmat(RA, P, g->Cz);
     lap("(R*A)*P");
-    dcsr_free(P); dcsr_free(RA);
-    if (rc != 0) { dcsr_free(g->Cz); delete g; return rc; }
+    P = {}; RA = {};
+    if (rc != 0) { delete g; return rc; }
     if (hipMemcpy(Cp, g->Cz.Ap, sizeof(long) * ((size_t)n_coarse + 1), hipMemcpyDeviceToHost) != hipSuccess) {
-        dcsr_free(g->Cz); delete g;
+        delete g;
         set_error("galerkin: row pointer download failed");
         return AMG_ENODEV;
     }
@@ -713,7 +703,6 @@ int amg_galerkin_fetch_c128(amg_galerkin *g, int *Cj, void *Cx)
             rc = AMG_ENODEV;
         }
     }
-    dcsr_free(g->Cz);
     delete g;
     return rc;
 }

@@ -23,8 +23,9 @@ using namespace amg;
 
 namespace amg {
 // spgemm.hip: C = A * A for a square CSR operand in HBM with scipy's csr_matmat arithmetic and output order; the
-// arrays of C are allocated with hipMalloc and handed to the caller
-int spgemm_square_device(int n, long nnz, long *Ap, int *Aj, double *Ax, long *Cnnz, long **Cp, int **Cj, double **Cx);
+// arrays of C are allocated there and handed to the caller's owners
+int spgemm_square_device(int n, long nnz, const long *Ap, const int *Aj, const double *Ax, long *Cnnz, DevArr<long> &Cp, DevArr<int> &Cj,
+                         DevArr<double> &Cx);
 }
 
 namespace {
@@ -136,26 +137,15 @@ int filter_entry(int n_row, double epsilon, const int *Sp, int Sp_size, const in
 struct DMat {                  // a square CSR matrix in HBM, 64-bit offsets (the layout of spgemm.hip's operands)
     int n = 0;
     long nnz = 0;
-    long *p = nullptr;
-    int *j = nullptr;
-    double *x = nullptr;
-    DMat() = default;
-    DMat(const DMat &) = delete;
-    DMat &operator=(const DMat &) = delete;
-    ~DMat() { release(); }
-    void release()
-    {
-        if (p) hipFree(p);
-        if (j) hipFree(j);
-        if (x) hipFree(x);
-        p = nullptr; j = nullptr; x = nullptr; nnz = 0;
-    }
-    void swap(DMat &o) { std::swap(n, o.n); std::swap(nnz, o.nnz); std::swap(p, o.p); std::swap(j, o.j); std::swap(x, o.x); }
+    DevArr<long> p;
+    DevArr<int> j;
+    DevArr<double> x;
+    void swap(DMat &o) { std::swap(*this, o); }
     int alloc_entries(long count)
     {
         nnz = count;
-        AMG_HIP(hipMalloc((void **)&j, sizeof(int) * (size_t)std::max(count, 1L)));
-        AMG_HIP(hipMalloc((void **)&x, sizeof(double) * (size_t)std::max(count, 1L)));
+        AMG_HIP(j.malloc_bytes(sizeof(int) * (size_t)std::max(count, 1L)));
+        AMG_HIP(x.malloc_bytes(sizeof(double) * (size_t)std::max(count, 1L)));
         return 0;
     }
 };
@@ -263,9 +253,9 @@ __global__ __launch_bounds__(TB) void minor_kernel(long nnz, const unsigned long
 int reorder(const DMat &S, int transposed, DMat &T)
 {
     const int n = S.n;
-    T.release();
+    T = DMat();
     T.n = n;
-    AMG_HIP(hipMalloc((void **)&T.p, sizeof(long) * ((size_t)n + 1)));
+    AMG_HIP(T.p.malloc_bytes(sizeof(long) * ((size_t)n + 1)));
     CHK(T.alloc_entries(S.nnz));
     const long nnz = S.nnz;
     DBuf keys_in, keys_out, cnt32, cnt64, tmp;
@@ -277,10 +267,10 @@ int reorder(const DMat &S, int transposed, DMat &T)
         hipLaunchKernelGGL(entry_keys_kernel, grid_for(nnz), dim3(TB), 0, nullptr, n, nnz, S.p, S.j, transposed, keys_in.as<unsigned long long>());
         LAUNCH_CHECK("strength: sort keys launch");
         size_t bytes = 0;
-        AMG_HIP(rocprim::radix_sort_pairs(nullptr, bytes, keys_in.as<unsigned long long>(), keys_out.as<unsigned long long>(), S.x, T.x,
+        AMG_HIP(rocprim::radix_sort_pairs(nullptr, bytes, keys_in.as<unsigned long long>(), keys_out.as<unsigned long long>(), (double *)S.x, (double *)T.x,
                                           (size_t)nnz, 0u, 64u, nullptr));
         CHK(tmp.alloc(bytes));
-        AMG_HIP(rocprim::radix_sort_pairs(tmp.p, bytes, keys_in.as<unsigned long long>(), keys_out.as<unsigned long long>(), S.x, T.x,
+        AMG_HIP(rocprim::radix_sort_pairs(tmp.p, bytes, keys_in.as<unsigned long long>(), keys_out.as<unsigned long long>(), (double *)S.x, (double *)T.x,
                                           (size_t)nnz, 0u, 64u, nullptr));
         hipLaunchKernelGGL(major_count_kernel, grid_for(nnz), dim3(TB), 0, nullptr, nnz, keys_out.as<unsigned long long>(), cnt32.as<int>());
         LAUNCH_CHECK("strength: row count launch");
@@ -300,9 +290,9 @@ int reorder(const DMat &S, int transposed, DMat &T)
     do {                                                                                                             \
         DBuf count__;                                                                                                \
         CHK(count__.alloc(sizeof(long) * ((size_t)(NROWS) + 1)));                                                        \
-        (MAT).release();                                                                                               \
+        (MAT) = DMat();                                                                                              \
         (MAT).n = (NROWS);                                                                                                 \
-        AMG_HIP(hipMalloc((void **)&(MAT).p, sizeof(long) * ((size_t)(NROWS) + 1)));                                       \
+        AMG_HIP((MAT).p.malloc_bytes(sizeof(long) * ((size_t)(NROWS) + 1)));                                         \
         hipLaunchKernelGGL(KCOUNT, grid_for((long)(NROWS) + 1), dim3(TB), 0, nullptr, __VA_ARGS__, count__.as<long>(),   \
                            (const long *)nullptr, (int *)nullptr, (double *)nullptr);                               \
         LAUNCH_CHECK(what " (count)");                                                                               \
@@ -454,7 +444,7 @@ int run_pipeline(DMat &A, const double *b_dev, double rho, double epsilon, int k
             for (int s = 0; s < nsquare - 1; ++s) {         // Atilde = Atilde * Atilde, scipy's product and order
                 DMat P;
                 P.n = n;
-                CHK(spgemm_square_device(n, At.nnz, At.p, At.j, At.x, &P.nnz, &P.p, &P.j, &P.x));
+                CHK(spgemm_square_device(n, At.nnz, At.p, At.j, At.x, &P.nnz, P.p, P.j, P.x));
                 At.swap(P);
             }
             CHK(reorder(At, 1, Csc));
@@ -464,10 +454,10 @@ int run_pipeline(DMat &A, const double *b_dev, double rho, double epsilon, int k
         } else {
             Csc.swap(M);                                    // (M^T)^T, already sorted
         }
-        M.release();
+        M = DMat();
         DMat S;                                             // the mask: A's pattern, values overwritten
         S.n = n;
-        AMG_HIP(hipMalloc((void **)&S.p, sizeof(long) * ((size_t)n + 1)));
+        AMG_HIP(S.p.malloc_bytes(sizeof(long) * ((size_t)n + 1)));
         AMG_HIP(hipMemcpy(S.p, A.p, sizeof(long) * ((size_t)n + 1), hipMemcpyDeviceToDevice));
         CHK(S.alloc_entries(A.nnz));
         if (A.nnz > 0) {
@@ -481,8 +471,8 @@ int run_pipeline(DMat &A, const double *b_dev, double rho, double epsilon, int k
         CHK(drop_zeros(S));
         At.swap(S);
     }
-    M.release();
-    A.release();
+    M = DMat();
+    A = DMat();
     // (f) the measure, weak entries dropped
     hipLaunchKernelGGL(measure_kernel, grid_for(n), dim3(TB), 0, nullptr, n, (const long *)At.p, (const int *)At.j, At.x, b_dev);
     LAUNCH_CHECK("strength: measure launch");
@@ -598,7 +588,7 @@ int amg_evolution_strength_device(int n, const int64_t *Ap, const int *Aj, const
     DMat A;
     A.n = n;
     const long nnz = (long)Ap[n];
-    AMG_HIP(hipMalloc((void **)&A.p, sizeof(long) * ((size_t)n + 1)));
+    AMG_HIP(A.p.malloc_bytes(sizeof(long) * ((size_t)n + 1)));
     CHK(A.alloc_entries(nnz));
     AMG_HIP(hipMemcpy(A.p, Ap, sizeof(long) * ((size_t)n + 1), hipMemcpyHostToDevice));
     if (nnz > 0) {
