@@ -437,6 +437,10 @@ typedef struct amg_mat amg_mat;
 amg_mat *amg_mat_create(int device, int nrows, int ncols, const int *Ap, const int *Aj, const double *Ax);
 void amg_mat_destroy(amg_mat *m);
 long amg_mat_nnz(amg_mat *m);
+/* rows per workgroup of the CSR stream kernels for this operator (fixed at creation; amg_set_tile_target) */
+int amg_mat_rows_per_block(amg_mat *m);
+/* fraction of the entries stored with 16-bit column codes (amg_set_index16 before creation); 0 = none kept */
+double amg_mat_index16_fraction(amg_mat *m);
 /* storage form the operator is applied from: 0 CSR, 1 offset-pattern, 2 stencil */
 int amg_mat_form(amg_mat *m);
 /* one csr_stream launch.  mode: 0 out=Mx  1 out+=Mx  2 out=b-Mx  3 out=b-Mx,out2=c0*out

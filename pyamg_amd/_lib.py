@@ -324,6 +324,10 @@ def lib():
     L.amg_mat_form.restype = I
     L.amg_mat_nnz.argtypes = [V]
     L.amg_mat_nnz.restype = C.c_long
+    L.amg_mat_rows_per_block.argtypes = [V]
+    L.amg_mat_rows_per_block.restype = I
+    L.amg_mat_index16_fraction.argtypes = [V]
+    L.amg_mat_index16_fraction.restype = C.c_double
     L.amg_arnoldi_free.argtypes = [V]
     L.amg_arnoldi_free.restype = None
     L.amg_set_stream_variant.argtypes = [I]

@@ -110,6 +110,10 @@ int amg_mat_gs_sweeps(amg_mat *m, double *x, const double *b, const unsigned cha
 }
 
 long amg_mat_nnz(amg_mat *m) { return m ? m->M.nnz : 0; }
+// rows one workgroup of the CSR stream kernels takes (rows_per_wg_for at creation time)
+int amg_mat_rows_per_block(amg_mat *m) { return m ? m->rpw : 0; }
+// fraction of the entries whose row blocks carry 16-bit column codes; 0 when the operator keeps none
+double amg_mat_index16_fraction(amg_mat *m) { return (m && m->M.Aj16) ? m->M.i16_frac : 0.0; }
 
 // mode: 0 MATVEC, 1 MATVEC_ACC, 2 RESIDUAL, 3 POLY_FIRST, 4 POLY_STEP, 5 POLY_LAST, 6 JACOBI, 7 JACOBI_BSR1
 int amg_mat_apply(amg_mat *m, int mode, const double *xg, const double *b, const double *v2, double *out,

@@ -100,7 +100,7 @@ class OracleBackend(object):
         v2c = None if v2 is None else v2.clone()      # in-place modes: read the old values
         self.apply(m, mode, xg, b, v2c, full, full2, c0, gscale)
         out[lo:hi] = full[lo:hi]
-        if out2 is not None:
+        if out2 is not None and mode == POLY_FIRST:       # the only mode that writes out2
             out2[lo:hi] = full2[lo:hi]
 
     def axpy_scaled(self, x, r, c, n):
