@@ -600,13 +600,17 @@ void amg_set_tile_target(int t);
  * A is level `level` of a hierarchy handle that already holds it in HBM as CSR (the handle behind the setup-time
  * spectral-radius estimate); R, P are host CSR arrays with 64-bit row pointers.  Cp receives n_coarse + 1 offsets;
  * amg_galerkin_fetch copies the Cp[n_coarse] columns / values to the host and releases the product.
- * AMG_EINVAL (nothing allocated) when the operator is not held as CSR or a row has more distinct result columns than
- * the device tables hold (2048 for rows of more than 1024 products on large levels). */
+ * AMG_EINVAL (nothing left allocated) when the operator is not held as CSR or the device tables would not fit: a row
+ * that outgrows the tables in LDS and has more than 2^22 products (the memory guard of csrc/spgemm.hip). */
 typedef struct amg_galerkin amg_galerkin;
 int amg_hier_galerkin(amg_hier *h, int level, int n_coarse, const int64_t *Rp, const int *Rj, const double *Rx,
                       const int64_t *Pp, const int *Pj, const double *Px, int64_t *Cp, amg_galerkin **out);
 int amg_galerkin_fetch(amg_galerkin *g, int *Cj, double *Cx);
-/* C = A * B for host CSR operands through the same kernels (n_row x n_inner times n_inner x n_col) */
+/* C = A * B for host CSR operands through the same kernels (n_row x n_inner times n_inner x n_col).
+ * Every product entry of this section requires of its RIGHT-hand operands (B here; A and P of a Galerkin product) that a
+ * row holds each column once: the lanes of a group take the entries of a right-hand row side by side and two entries
+ * with one column would lose a product.  Left-hand rows may repeat columns, and no operand needs sorted rows.  The
+ * callers in the package hand operators they did not build to the host product when they hold duplicates. */
 int amg_csr_matmat_device(int n_row, int n_inner, int n_col, const int64_t *Ap, const int *Aj, const double *Ax,
                           const int64_t *Bp, const int *Bj, const double *Bx, int64_t *Cp, amg_galerkin **out);
 /* The same products for complex128 operands (values as interleaved (real, imaginary) pairs of doubles), scipy's complex
@@ -624,6 +628,19 @@ int amg_galerkin_device_c128(int n_fine, int n_coarse, const int64_t *Rp, const 
                              const int64_t *Ap, const int *Aj, const void *Ax,
                              const int64_t *Pp, const int *Pj, const void *Px, int64_t *Cp, amg_galerkin **out);
 int amg_galerkin_fetch_c128(amg_galerkin *g, int *Cj, void *Cx);
+/* What the calling thread's most recent product (one A * B of the entries above; of a Galerkin product the last one
+ * that ran) did, as AMG_SPGEMM_ROUTE_FIELDS ints; the first min(n, AMG_SPGEMM_ROUTE_FIELDS) are copied to out and the
+ * number of fields is returned:
+ *   0  value type: 0 float64, 1 complex128
+ *   1  lanes per output row first tried (8, 16, 32 or 64; 0 for a product without rows)
+ *   2  lanes per output row that produced the result (1: one thread per row; 0: no kernel ran to the end)
+ *   3  where the tables lived: 0 no kernel (a product without rows), 1 LDS, 2 HBM, a table per wave, 3 HBM, a table per
+ *      thread, 4 refused (AMG_EINVAL: the caller's host product)
+ *   4  table entries per row (per thread: of the first tier; refused: what the longest row's products would have needed)
+ *   5  workgroups of the launches that produced the result (per thread: of the first tier)
+ *   6  rows redone in the second tier of the per-thread tables */
+#define AMG_SPGEMM_ROUTE_FIELDS 7
+int amg_spgemm_last_route(int *out, int n);
 
 /* Evolution strength of connection (pyamg/strength.py:433-816) for a real operator and ONE candidate vector, every
  * stage in HBM (csrc/strength.hip).  A: n x n CSR on the host with sorted rows, no duplicates and

@@ -187,6 +187,7 @@ def lib():
         "amg_csr_matmat_device_c128": [I, I, I, V, V, V, V, V, V, V, C.POINTER(C.c_void_p)],
         "amg_galerkin_device_c128": [I, I, V, V, V, V, V, V, V, V, V, V, C.POINTER(C.c_void_p)],
         "amg_galerkin_fetch_c128": [V, V, V],
+        "amg_spgemm_last_route": [c_int_p, I],
         "amg_evolution_strength_device": [I, V, V, V, V, D, D, I, I, V, C.POINTER(C.c_void_p), c_dbl_p],
         "amg_strength_fetch": [V, V, V],
         "amg_energy_smooth_device": [I, I, I, I, I, V, V, V, V, V, V, V, V, V, I, D, C.POINTER(C.c_void_p), c_int_p, V, c_dbl_p],
@@ -400,3 +401,19 @@ def device_count():
 def live_buffers():
     """Device allocations the library made and still holds (amg_dev_live_buffers)."""
     return lib().amg_dev_live_buffers()
+
+
+SPGEMM_ROUTE_FIELDS = ("complex", "lanes_first", "lanes", "tables", "entries", "blocks", "second_tier_rows")
+SPGEMM_TABLES = ("none", "lds", "hbm_wave", "hbm_thread", "refused")
+
+
+def spgemm_last_route():
+    """What this thread's most recent device product did (amg_spgemm_last_route, csrc/spgemm.hip): a dict of
+    SPGEMM_ROUTE_FIELDS, `tables` as one of SPGEMM_TABLES."""
+    out = (C.c_int * len(SPGEMM_ROUTE_FIELDS))()
+    n = lib().amg_spgemm_last_route(out, len(SPGEMM_ROUTE_FIELDS))
+    if n != len(SPGEMM_ROUTE_FIELDS):
+        raise AmgError("amg_spgemm_last_route: %d fields, %d expected" % (n, len(SPGEMM_ROUTE_FIELDS)))
+    rec = dict(zip(SPGEMM_ROUTE_FIELDS, (int(v) for v in out)))
+    rec["tables"] = SPGEMM_TABLES[rec["tables"]]
+    return rec

@@ -605,6 +605,7 @@ def poisson(grid, format="csr"):
     L.amgsetup_poisson(g3[0], g3[1], g3[2], 2.0 * len(grid), _lp(Ap), _ip(Aj), _dp(Ax))
     A = csr_matrix((Ax, Aj, Ap.astype(np.intc)), shape=(n, n))
     A.has_sorted_indices = True
+    A._amg_columns_once = True              # a stencil's offsets are distinct (_columns_once)
     return A.asformat(format)
 
 
@@ -613,6 +614,20 @@ def _csr_arrays64(M):
     data = M.data.reshape(-1) if isspmatrix_bsr(M) else M.data
     return (np.ascontiguousarray(M.indptr, dtype=np.int64), np.ascontiguousarray(M.indices, dtype=np.intc),
             np.ascontiguousarray(data, dtype=np.float64))
+
+
+def _columns_once(M):
+    """No row of the CSR / BSR(1,1) matrix M holds a column twice: what the device products require of their right-hand
+    operands (csrc/spgemm.hip: the lanes of a group take a right-hand row's entries side by side).  scipy and the host
+    products take such rows as they are, so an operator that fails this stays with them.  Operators this package
+    formed as a product hold each column once by construction and say so (_amg_columns_once)."""
+    if getattr(M, "_amg_columns_once", False):
+        return True
+    if not M.has_sorted_indices:
+        # the pattern alone, sorted in a copy: duplicates are then neighbours, which is what scipy's check looks for
+        M = csr_matrix((np.ones(len(M.indices), dtype=np.int8), M.indices.copy(), M.indptr), shape=M.shape)
+        M.sort_indices()
+    return bool(M.has_canonical_format)
 
 
 def _matmat(Aa, Ba, shape):
@@ -764,8 +779,10 @@ def _extend_scalar(levels, smooth_l, keep, rho_fn):
     lap("R = P^T")
     # Galerkin product (R*A)*P: on the GPU when A already sits in HBM (the spectral-radius estimate uploaded it),
     # else row-parallel on the host -- the same products in the same order either way
+    # (A is the right-hand operand of R*A: an operator with a column twice in a row stays with the host products, which
+    # take it as scipy does; its rows are sorted by now, so this is scipy's own cached check)
     Ac = None
-    if os.environ.get("AMG_SETUP_DEVICE_GALERKIN", "1") != "0":
+    if os.environ.get("AMG_SETUP_DEVICE_GALERKIN", "1") != "0" and _columns_once(A):
         from .util import galerkin_device
         Ac = galerkin_device(A, (Rp, Rj, Rx), (Pp, Pj, Px), n_agg)
         if Ac is not None:
@@ -779,6 +796,7 @@ def _extend_scalar(levels, smooth_l, keep, rho_fn):
     P = _as_bsr11((Pp, Pj, Px), (n, n_agg))
     R = _as_bsr11((Rp, Rj, Rx), (n_agg, n))
     Anew = _as_bsr11(Ac, (n_agg, n_agg))
+    Anew._amg_columns_once = True           # a csr_matmat result, from either path
     if keep:
         levels[-1].AggOp = agg
     levels[-1].P = P
@@ -915,7 +933,8 @@ def _galerkin_c128_device(R, A, P):
     """(R*A)*P of a complex128 level on the GPU (util.galerkin_device, csrc/spgemm.hip) as the BSR(1,1) matrix scipy's
     R * A * P gives, or None: no device, AMG_SETUP_DEVICE_GALERKIN=0, a level below the gates
     (util.DEVICE_GALERKIN_C128_MIN_ROWS, None = never, and util.DEVICE_RHO_MIN_ROWS), operands with blocks larger
-    than 1 x 1, or a row too long for the device tables -- the caller then uses scipy's products."""
+    than 1 x 1, an operator A with a column twice in a row, or a row too long for the device tables --
+    the caller then uses scipy's products."""
     from . import util
     gate = util.DEVICE_GALERKIN_C128_MIN_ROWS
     if os.environ.get("AMG_SETUP_DEVICE_GALERKIN", "1") == "0" or gate is None \
@@ -926,6 +945,8 @@ def _galerkin_c128_device(R, A, P):
             return None
     from . import _lib
     if _lib.device_count() <= 0:
+        return None
+    if not _columns_once(A):                # (P and R*A are this package's own: each column once by construction)
         return None
     def arrays(M):
         return (np.ascontiguousarray(M.indptr, dtype=np.int64), np.ascontiguousarray(M.indices, dtype=np.intc),
@@ -1020,6 +1041,7 @@ def extend_hierarchy(levels, strength, aggregate, smooth, improve_candidates, ke
     Ac = _galerkin_c128_device(R, A, P) if A.dtype.kind == "c" else None
     what = "(R*A)*P by scipy" if Ac is None else "(R*A)*P on the device"
     A = R * A * P if Ac is None else Ac
+    A._amg_columns_once = True              # a csr_matmat result, from either path
     lap(what)
     A.symmetry = symmetry
     levels[-1].A = A

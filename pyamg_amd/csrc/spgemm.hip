@@ -4,12 +4,20 @@
 // output columns come out in REVERSE first-touch order, exact-zero results are dropped.
 //
 // Main kernel (spgemm_group_kernel): G lanes per output row, every row with a table of its own in LDS; left-hand
-// entries strictly in order, the lanes over the right-hand row each entry selects.  Fall-backs for rows whose distinct
-// columns outgrow the LDS table: the whole wave per row, then one thread per row with private tables in HBM
-// (spgemm_rows_kernel, two tiers), then the caller's host path.  Every path runs a count pass (non-zero results per
-// row) and a fill pass (results written at their final places); both do the full arithmetic, neither allocates per
-// row.  Bit-identical to the host restatement (setup_host.cpp amgsetup_csr_matmat_*) and to scipy: same products, same
-// order, separate multiply and add.
+// entries strictly in order, the lanes over the right-hand row each entry selects.  The routes of matmat(), in order:
+//   1. G = 8, 16, 32 or 64 lanes per row from the right-hand operand's mean row length (complex128 one step wider);
+//   2. a row outgrew its table and G < 64: the whole product again with the whole wave per row (64 lanes, LDS);
+//   3. a row outgrew that too and the longest row has more than 1024 and at most 2^22 products: the whole wave per row
+//      with the row's table in HBM, sized so that no row outgrows it;
+//   4. no row has more than 1024 products (complex128 only: its wave table takes fewer distinct columns than that, the
+//      float64 one takes them all): one thread per row with private tables in HBM (spgemm_rows_kernel, two tiers);
+//   5. longer rows than 2^22 products: AMG_EINVAL, the caller's host path -- the per-thread tables would not fit, which
+//      the memory guard decides on the host.
+// A product without rows is the empty product without a launch.  What a product did is kept per thread for
+// amg_spgemm_last_route.  Every path runs a count pass (non-zero results per row) and a fill pass (results written at
+// their final places); both do the full arithmetic, neither allocates per row.  Bit-identical to the host restatement
+// (setup_host.cpp amgsetup_csr_matmat_*) and to scipy: same products, same order, separate multiply and add.
+// Right-hand operands hold each column once per row (amgcore_hip.h); left-hand rows may repeat columns.
 #include "hier.hpp"
 #include "scalar.hpp"
 
@@ -89,10 +97,13 @@ __global__ void spgemm_upper_kernel(int n_row, const long *Ap, const int *Aj, co
 // is left to a launch with larger tables).  FILL = true: write them at Cp[i] .. in reverse first-touch order (rows
 // marked -1 are skipped).  Rows: all (`rows` null) or the listed ones.  Thread t owns table t (cap entries): keys stay
 // -1 between rows (cleared through the order list).
-// Tables sized by the PRODUCTS of the longest row would be 16 KB per thread here and live in HBM (2 GB for 131 k
-// threads): every probe a random 64-byte HBM access, 0.77 s per product of the 500^3 level.  The rows' DISTINCT
-// columns are far fewer, so the first launch runs with 256-entry tables (4 KB per thread, 256 MB in all: Infinity
-// Cache / L2) and only rows that outgrow them are redone with the large ones.
+// Reached by complex128 products only, and only when no row has more than 1024 products: rows of 961 to 1024 distinct
+// columns, which the 2048-entry wave table does not take.  (A float64 row that outgrows its 4096-entry wave table has
+// more than 1024 products and goes to the HBM wave tables; past their gate of 2^22 products the memory guard of
+// matmat() refuses every product, because the second tier here would hold 256 tables of 2^24 entries at the least.)
+// The tables of the second tier are sized by the PRODUCTS of the longest row (2048 entries at most, then); the rows'
+// DISTINCT columns are mostly far fewer, so the first launch runs with 256-entry tables (6 KB per thread: Infinity
+// Cache / L2) and only rows of more than 128 distinct columns are redone with the large ones.
 template <class V, bool FILL>
 __global__ __launch_bounds__(256) void spgemm_rows_kernel(int n_work, const int *rows, const long *Ap, const int *Aj, const V *Ax,
                                                          const long *Bp, const int *Bj, const V *Bx, int cap, int limit,
@@ -163,8 +174,8 @@ __global__ __launch_bounds__(256) void spgemm_rows_kernel(int n_work, const int 
 // numbered in lane (= entry) order by a ballot, which is the sequential first-touch order.  G is chosen from the
 // right-hand operand's average row length (7-point operator: 8 lanes, eight rows per wave with 512-entry tables;
 // long rows: the whole wave on one row with 4096 entries).  A row whose distinct columns do not fit its table raises
-// `overflow`: the caller retries with the whole wave per row, then with the one-thread-per-row kernel (tables in HBM),
-// then hands the product back to its host path.
+// `overflow`: the caller retries with the whole wave per row, then with the row's table in HBM (HBM = true below) or,
+// where no row has more than 1024 products, with the one-thread-per-row kernel; see the routes at the head of the file.
 // Table entries per wave.  float64: 4096 (16 B per entry, 64 KB of LDS, two waves per compute unit).  complex128: an
 // entry costs 24 B, so 2048 (48 KB) keep two waves per compute unit; the host picks lane groups one step wider for
 // complex operands, which gives every row the table it has in float64 at all widths below the whole wave.
@@ -332,16 +343,30 @@ int upload_dcsr(DCsrT<V> &M, int n_row, int n_col, const long *Ap, const int *Aj
     return 0;
 }
 
+// What matmat() did for the calling thread's most recent product (amg_spgemm_last_route, amgcore_hip.h): the tests pin
+// every route below to operands built for it.
+enum { ROUTE_NONE = 0, ROUTE_LDS = 1, ROUTE_HBM_WAVE = 2, ROUTE_HBM_THREAD = 3, ROUTE_REFUSED = 4 };
+struct Route { int cplx = 0, g_first = 0, g_final = 0, where = ROUTE_NONE, cap = 0, blocks = 0, big_rows = 0; };
+thread_local Route last_route;
+
+// threads (= tables) of a per-thread launch that wants `want` of them: whole workgroups of 256, at least one
+inline long table_threads(long want) { return (std::max<long>(256, want) + 255) / 256 * 256; }
+
 // C = A * B, both in HBM; C allocated here
 template <class V>
 int matmat(const typename DCsrT<V>::View &A, const typename DCsrT<V>::View &B, DCsrT<V> &C)
 {
+    constexpr bool CPLX = !std::is_same<V, double>::value;
+    Route &route = last_route;
+    route = Route{};
+    route.cplx = CPLX ? 1 : 0;
+    route.where = ROUTE_REFUSED;                                // until a path below has run to its end
     if (A.n_col != B.n_row) { set_error("spgemm: inner dimensions differ"); return AMG_EINVAL; }
     C.n_row = A.n_row; C.n_col = B.n_col;
     const int n = A.n_row;
-    constexpr bool CPLX = !std::is_same<V, double>::value;
     constexpr long ENTRY = 8 + (long)sizeof(V);                 // bytes of a table entry: key, place in the order list, sum
-    if (CPLX && n == 0) {                                       // no rows: the empty product (complex entries only)
+    if (n == 0) {                                               // no rows: the empty product, without a launch
+        route.where = ROUTE_NONE;
         C.nnz = 0; C.Aj.reset(); C.Ax.reset();
         AMG_HIP(C.Ap.malloc_bytes(sizeof(long)));
         AMG_HIP(hipMemset(C.Ap, 0, sizeof(long)));
@@ -356,11 +381,12 @@ int matmat(const typename DCsrT<V>::View &A, const typename DCsrT<V>::View &B, D
     const int max_upper = n ? *std::max_element(hu.begin(), hu.end()) : 0;
     int cap = 64;
     while (cap < 2 * max_upper && cap < (1 << 30)) cap <<= 1;
-    // G lanes per row with the tables in LDS; rows whose distinct columns outgrow their table send the whole product to
-    // the one-thread-per-row kernel below (tables in HBM), which in turn refuses levels too large for it
+    // G lanes per row with the tables in LDS; a row whose distinct columns outgrow its table sends the whole product on:
+    // to the whole wave per row, then to the paths with tables in HBM below
     const double avgB = B.n_row > 0 ? (double)B.nnz / (double)B.n_row : 1.0;
     const int G0r = avgB <= 10.0 ? 8 : (avgB <= 20.0 ? 16 : (avgB <= 40.0 ? 32 : 64));
     const int G0 = CPLX ? std::min(64, 2 * G0r) : G0r;             // complex: one step wider (wave_cap)
+    route.g_first = G0;
     for (int G = G0; G <= 64; G = (G == 64 ? 128 : 64)) {          // the preferred width, then the whole wave per row
         DevArr<int> count, overflow;
         AMG_HIP(count.malloc_bytes(sizeof(int) * (size_t)std::max(n, 1)));
@@ -395,6 +421,7 @@ int matmat(const typename DCsrT<V>::View &A, const typename DCsrT<V>::View &B, D
             GROUP_DISPATCH(true);
             LAUNCH_CHECK("spgemm group fill launch");
             AMG_HIP(hipDeviceSynchronize());
+            route.g_final = G; route.where = ROUTE_LDS; route.cap = wave_cap<V>::value / rows_per_wave; route.blocks = blocks;
             return 0;
         }
 #undef GROUP_DISPATCH
@@ -441,10 +468,22 @@ int matmat(const typename DCsrT<V>::View &A, const typename DCsrT<V>::View &B, D
                                count, (const long *)C.Ap, C.Aj, C.Ax, overflow, gkey, gsum, gord, gcap);
             rc = launched("spgemm HBM-table fill launch");
             if (hipDeviceSynchronize() != hipSuccess && rc == 0) rc = AMG_ENODEV;
+            if (rc == 0) { route.g_final = 64; route.where = ROUTE_HBM_WAVE; route.cap = gcap; route.blocks = blocks; }
         }
         if (!ovf) return rc;
     }
-    if (!(max_upper <= 1024 || (double)n * (double)cap * (double)ENTRY <= 2.0e9)) {
+    // One thread per row.  The guard counts what Tables::make below would allocate if every row went on to the second
+    // tier -- whole workgroups of 256 tables in either tier, however few rows there are -- against the 4 GB the HBM wave
+    // tables may take.  Rows of at most 1024 products always pass (at most 65536 tables of 256 and of 2048 entries,
+    // 3.6 GB).  Longer rows arrive here only past the gate of the HBM wave tables, 2^22 products: the second tier would
+    // then hold 256 tables of 2^24 entries or more (69 GB in float64), so every such product goes back to the caller's
+    // host path, decided here and not by a failed allocation.
+    const int small_cap = std::min(cap, 256);
+    const long t2_threads = std::min<long>(256L * 512L, (3L << 30) / ((long)cap * ENTRY));
+    const double table_bytes = ((double)table_threads(std::min<long>(65536, n)) * (double)small_cap +
+                                (double)table_threads(std::min<long>(t2_threads, n)) * (double)cap) * (double)ENTRY;
+    if (table_bytes > (double)(4L << 30)) {
+        route.cap = cap;
         set_error("spgemm: rows with more distinct columns than the LDS tables hold on a level too large for per-thread tables (host path)");
         return AMG_EINVAL;
     }
@@ -454,8 +493,8 @@ int matmat(const typename DCsrT<V>::View &A, const typename DCsrT<V>::View &B, D
         int make(int cap_, long want_threads)
         {
             cap = cap_;
-            blocks = (int)((std::max<long>(256, want_threads) + 255) / 256);
-            threads = (long)blocks * 256;
+            threads = table_threads(want_threads);
+            blocks = (int)(threads / 256);
             AMG_HIP(keys.malloc_bytes(sizeof(int) * (size_t)(threads * cap)));
             AMG_HIP(order.malloc_bytes(sizeof(int) * (size_t)(threads * cap)));
             AMG_HIP(sums.malloc_bytes(sizeof(V) * (size_t)(threads * cap)));
@@ -463,7 +502,6 @@ int matmat(const typename DCsrT<V>::View &A, const typename DCsrT<V>::View &B, D
             return 0;
         }
     };
-    const int small_cap = std::min(cap, 256);
     if (std::getenv("AMG_SETUP_VERBOSE") && std::getenv("AMG_SETUP_VERBOSE")[0] != '0')
         std::fprintf(stderr, "[setup]     device product %d x %d%s: one thread per row, %d-entry tables in HBM (%d-entry ones for rows that outgrow them)\n",
                      A.n_row, B.n_col, CPLX ? " (complex128)" : "", small_cap, cap);
@@ -481,8 +519,7 @@ int matmat(const typename DCsrT<V>::View &A, const typename DCsrT<V>::View &B, D
     for (int i = 0; i < n; ++i) if (hc[(size_t)i] < 0) big.push_back(i);
     if (!big.empty()) {
         // second tier: the rows that outgrew the small tables, with tables sized by the longest row's products
-        long threads = std::min<long>(256L * 512L, (3L << 30) / ((long)cap * ENTRY));
-        CHK(T2.make(cap, std::min<long>(threads, (long)big.size())));
+        CHK(T2.make(cap, std::min<long>(t2_threads, (long)big.size())));
         AMG_HIP(big_rows.malloc_bytes(sizeof(int) * big.size()));
         AMG_HIP(hipMemcpy(big_rows, big.data(), sizeof(int) * big.size(), hipMemcpyHostToDevice));
         hipLaunchKernelGGL((spgemm_rows_kernel<V, false>), dim3(T2.blocks), dim3(256), 0, nullptr, (int)big.size(), big_rows, A.Ap, A.Aj, A.Ax,
@@ -515,6 +552,7 @@ int matmat(const typename DCsrT<V>::View &A, const typename DCsrT<V>::View &B, D
         LAUNCH_CHECK("spgemm fill launch (large tables)");
     }
     AMG_HIP(hipDeviceSynchronize());
+    route.g_final = 1; route.where = ROUTE_HBM_THREAD; route.cap = T1.cap; route.blocks = T1.blocks; route.big_rows = (int)big.size();
     return 0;
 }
 
@@ -691,6 +729,14 @@ int amg_galerkin_device_c128(int n_fine, int n_coarse, const int64_t *Rp, const 
 }
 
 // columns and interleaved values (Cp[n] entries each) of a complex128 product to the host; releases it
+int amg_spgemm_last_route(int *out, int n)
+{
+    const int f[AMG_SPGEMM_ROUTE_FIELDS] = {last_route.cplx, last_route.g_first, last_route.g_final, last_route.where,
+                                            last_route.cap, last_route.blocks, last_route.big_rows};
+    for (int q = 0; out && q < n && q < AMG_SPGEMM_ROUTE_FIELDS; ++q) out[q] = f[q];
+    return AMG_SPGEMM_ROUTE_FIELDS;
+}
+
 int amg_galerkin_fetch_c128(amg_galerkin *g, int *Cj, void *Cx)
 {
     if (!g) return AMG_EINVAL;

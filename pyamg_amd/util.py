@@ -344,7 +344,9 @@ def galerkin_device(A, R, P, n_coarse):
     the spectral-radius estimate left behind (device_operator); R, P = (indptr int64, indices int32, data f64).
     Returns (Cp, Cj, Cx) or None when the device path does not apply (no HBM copy, operator not held as CSR, a row too
     long for the device tables) -- the caller then runs its host products.
-    A complex128 operator is handed in as host arrays, A = (indptr, indices, data) like R and P."""
+    A complex128 operator is handed in as host arrays, A = (indptr, indices, data) like R and P.
+    The right-hand operands A and P must hold each column once per row (amgcore_hip.h); the callers in aggregation.py
+    keep an operator that does not with the host products (aggregation._columns_once)."""
     import ctypes as C
     if isinstance(A, tuple):
         # complex128: A = (indptr int64, indices int32, data complex128) on the host, like R and P; the three operands

@@ -1728,9 +1728,12 @@ def _device_matmat(A, B):
 
 @pytest.mark.gpu
 def test_device_csr_matmat_is_scipys_bit_for_bit():
-    """C = A*B on the GPU (one thread per output row, private hash table in HBM): scipy's csr_matmat products in
+    """C = A*B on the GPU (lane groups per output row, the rows' hash tables in LDS): scipy's csr_matmat products in
     scipy's order -- same row pointer, same (unsorted, reverse first-touch) column order, same bits, exact zeros
-    dropped; rectangular, empty rows, cancelling products, unsorted operands"""
+    dropped; rectangular, empty rows, cancelling products, unsorted operands.
+    Routes (the record of amg_spgemm_last_route; tests/test_gpu_spgemm_routes.py asserts the record on small cases):
+    8 lanes per row for all pairs but rnd(1000,50,3) x rnd(50,4000,40) (32 lanes) and the mixed one (16 lanes, a row
+    outgrows its table, redone by the whole wave in LDS).  No float64 product reaches the one-thread-per-row kernel."""
     from pyamg_amd.aggregation import poisson as native
     rng = np.random.RandomState(5)
 
@@ -1748,8 +1751,8 @@ def test_device_csr_matmat_is_scipys_bit_for_bit():
     # unsorted operand (the product of two others, as scipy leaves it)
     U = rnd(400, 300, 6) @ rnd(300, 350, 5)
     cases.append((U, rnd(350, 200, 4)))
-    # rows of 2 products next to rows of ~600 products with ~550 distinct columns: the small first-tier tables (128
-    # distinct columns) overflow for the long rows only, which are redone with the large tables
+    # rows of 2 products next to rows of ~600 products with ~570 distinct columns: the 16-lane tables (1024 entries, at
+    # most 496 distinct columns before a further chunk) are outgrown and the whole product is redone one wave per row
     mixed = sps.vstack([rnd(500, 200, 2), rnd(300, 200, 30), rnd(200, 200, 1)]).tocsr()
     cases.append((mixed, rnd(200, 5000, 20)))
     for A, B in cases:
@@ -1762,9 +1765,10 @@ def test_device_csr_matmat_is_scipys_bit_for_bit():
 
 @pytest.mark.gpu
 def test_device_csr_matmat_long_rows_one_wave_per_row():
-    """rows of ~2000 products on a level too large for per-thread tables go one wave per row with the table in LDS
-    (lanes over the right-hand row, left-hand entries in order): still scipy's bits and order; rows with more distinct
-    columns than the LDS table holds keep their table in HBM instead"""
+    """rows of ~2000 products against right-hand rows of ~50 entries go one wave per row from the start, the table in
+    LDS (lanes over the right-hand row, left-hand entries in order; 4096 workgroups for 40000 rows, so ten rounds of
+    the grid): still scipy's bits and order; rows with more distinct columns than the LDS table holds (~2700 > 1984)
+    keep their table in HBM instead, one of 8192 entries per workgroup, 1024 workgroups for 6000 rows"""
     from pyamg_amd import _lib
     rng = np.random.RandomState(11)
 
@@ -1796,20 +1800,28 @@ def test_device_csr_matmat_long_rows_one_wave_per_row():
 @pytest.mark.gpu
 def test_device_galerkin_product_equals_the_host_products():
     """util.galerkin_device: (R*A)*P from the HBM copy of A that the spectral-radius estimate leaves behind = the host
-    restatement (aggregation._matmat) = scipy, bit for bit, on a smoothed-aggregation level (A in CSR and as BSR(1,1))"""
-    from pyamg_amd import util
+    restatement (aggregation._matmat) = scipy, bit for bit, on a smoothed-aggregation level (A in CSR and as BSR(1,1)).
+    Whether a level is a product or a refusal is what the model of the route policy (tests/spgemm_cases.py) says of its
+    two products, and the route record of the last product that ran says the same."""
+    import spgemm_cases
+    from pyamg_amd import _lib, util
     from pyamg_amd.aggregation import _matmat, _csr_arrays64
     g = golden_io.load_hier("sa_cheb2_3d")
     for l in (0, 1):
         A = g["levels"][l]["A"]; P = sps.csr_matrix(g["levels"][l]["P"]); R = sps.csr_matrix(g["levels"][l]["R"])
         nc = P.shape[1]
+        (rc1, rec1), (rc2, rec2) = (spgemm_cases.route(R, sps.csr_matrix(A), spgemm_cases.F64),
+                                    spgemm_cases.route(R @ sps.csr_matrix(A), P, spgemm_cases.F64))
         util.device_operator(A)
         try:
             Ra, Pa = _csr_arrays64(R), _csr_arrays64(P)
             out = util.galerkin_device(A, Ra, Pa, nc)
-            if l == 1 and out is None:
-                continue              # rows of more than 1024 products stay with the host product (csrc/spgemm.hip)
-            assert out is not None
+            rec = _lib.spgemm_last_route()
+            if rc1 != 0 or rc2 != 0:
+                # the host product's level: refused by the memory guard, and the record says which product was
+                assert out is None and rec["tables"] == "refused" and rec == (rec1 if rc1 != 0 else rec2), (l, rec)
+                continue
+            assert out is not None and rec == rec2 and rec["tables"] in ("lds", "hbm_wave"), (l, rec)
             RA = _matmat(Ra, _csr_arrays64(A), (nc, A.shape[0]))
             ref = _matmat(RA, Pa, (nc, nc))
             for a, b in zip(out, ref):

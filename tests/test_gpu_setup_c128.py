@@ -65,6 +65,7 @@ def test_device_csr_matmat_c128_is_scipys_bit_for_bit():
       long x rnd(100,100000,100)   rows of 1000 products with ~995 distinct columns: more than the wave's table
                                    takes (960) but not over 1024 products, so one thread per row with tables in
                                    HBM -- the short rows in the 256-entry tables, the long ones in the large ones
+    (the routes as amg_spgemm_last_route records them; tests/test_gpu_spgemm_routes.py asserts the record on small cases)
     plus cancellation in the real part only (entry kept, with the zero as computed), in both parts (entry dropped),
     stored (-0.0, 0.0) entries, an empty matrix (5 x 7 without entries), a left operand without rows and empty rows."""
     from pyamg_amd.aggregation import poisson as native
