@@ -183,6 +183,29 @@ int amgcore_calc_BtB_f64(int NullDim, int Nnodes, int ColsPerBlock, const double
  * its first len - k entries are set to 0.0, so that among equal magnitudes the reference's choice survives.  One lane
  * per row, an explicit stack of at most 32 ranges, no per-row buffer: rows of any length. */
 int amgcore_truncate_rows_csr_f64(int n_row, int k, const int Sp[], int Sp_size, int Sj[], int Sj_size, double Sx[], int Sx_size);
+/* The row-parallel stages of the classical setup (amg_core/ruge_stuben.h, csrc/split.hip), float64
+ * only, one lane per row walking it in stored order:
+ * classical_strength_of_connection (:46-93): Sp, Sj[:nnz], Sx[:nnz] as the reference leaves them (count, exclusive scan,
+ *   stable fill).  The row maximum starts at DBL_MIN and a NaN never replaces it; the threshold is theta * max, the test >=;
+ *   every stored diagonal entry is kept at its own position.  Rows in any order, duplicates allowed.
+ * maximum_row_value (:110-130): x[i] = max(DBL_MIN, |a| over row i).
+ * rs_direct_interpolation_pass1 (:497-516): Bp, the last offset being the number of entries of the prolongator.
+ * rs_direct_interpolation_pass2 (:520-595): Bj (renumbered by the exclusive scan of splitting) and Bx; sums from +0.0 in
+ *   stored order, plain divisions, only sum_strong_pos == 0 special-cased, non-finite weights stored as they come.  Bp has
+ *   to be what pass 1 returns for the same S and splitting.
+ * Offsets that do not start at 0 or decrease, a column outside the matrix, a splitting value other than 0 and 1 and arrays
+ * shorter than the offsets ask for are AMG_EINVAL before any launch. */
+int amgcore_classical_strength_of_connection_f64(int n_row, double theta, const int Ap[], int Ap_size, const int Aj[], int Aj_size,
+                                                 const double Ax[], int Ax_size, int Sp[], int Sp_size, int Sj[], int Sj_size, double Sx[],
+                                                 int Sx_size);
+int amgcore_maximum_row_value_f64(int n_row, double x[], int x_size, const int Ap[], int Ap_size, const int Aj[], int Aj_size,
+                                  const double Ax[], int Ax_size);
+int amgcore_rs_direct_interpolation_pass1_f64(int n_nodes, const int Sp[], int Sp_size, const int Sj[], int Sj_size, const int splitting[],
+                                              int splitting_size, int Bp[], int Bp_size);
+int amgcore_rs_direct_interpolation_pass2_f64(int n_nodes, const int Ap[], int Ap_size, const int Aj[], int Aj_size, const double Ax[],
+                                              int Ax_size, const int Sp[], int Sp_size, const int Sj[], int Sj_size, const double Sx[],
+                                              int Sx_size, const int splitting[], int splitting_size, const int Bp[], int Bp_size, int Bj[],
+                                              int Bj_size, double Bx[], int Bx_size);
 /* pyamg/util/linalg.py:17-53 norm(x) (2-norm) */
 int amgcore_norm2_f64(const double x[], long n, double *result);
 
@@ -696,6 +719,24 @@ int amg_mis_device(int n, const int *Ap, const int *Aj, const double *y, int act
                    double *times_ms);
 int amg_cljp_device(int n, const int *Sp, const int *Sj, const int *Tp, const int *Tj, const double *weight0, int *splitting,
                     int *passes, double *times_ms);
+
+/* One level of the classical setup in HBM from one upload of A (csrc/split.hip): classical
+ * strength with theta, the strength graph without its diagonal with its transpose's pattern and the in-degrees, the start
+ * weights, the splitting (kind 0: PMIS, Luby's rounds on S + S^T with double(in-degree) + r; kind 1: CLJP, r then + 1.0 per
+ * dependent), and direct interpolation on S's pattern with the values the strength stage wrote.  A: n x n CSR on the host,
+ * n > 0; r: n start values in [0, 1) from the host.  reversed != 0: interpolation walks every row of S from its last
+ * entry to its first, sums and entries of P alike (the order in which the host route meets S when the rows of A are not
+ * sorted); A's rows are walked as stored either way.  On return *out holds the result, sizes[0] the entries of S, sizes[1]
+ * the entries of P, *rounds (or NULL) the rounds or passes of the splitting.  amg_classical_level_fetch copies splitting (n),
+ * Pp (n + 1), Pj and Px (sizes[1] each, Pj in coarse numbering) and, where Sp is not NULL, Sp (n + 1), Sj and Sx (sizes[0]
+ * each, Sx as |S| with every row divided by its largest entry) to the host and releases the result, also when it fails.
+ * times_ms (or NULL): milliseconds of the upload [0], strength [1], graph and weights [2], splitting [3] and interpolation
+ * [4]; the fetch writes the same five and its own time [5]. */
+typedef struct amg_classical amg_classical;
+int amg_classical_level_device(int n, const int *Ap, const int *Aj, const double *Ax, double theta, int kind, int reversed,
+                               const double *r, amg_classical **out, long *sizes, int *rounds, double *times_ms);
+int amg_classical_level_fetch(amg_classical *h, int *splitting, int *Pp, int *Pj, double *Px, int *Sp, int *Sj, double *Sx,
+                              double *times_ms);
 
 /* ------------------------------------------------------------------------ */
 /* 5. Resident hierarchies of other value types: the cycle of section 2      */

@@ -69,6 +69,7 @@ def _signatures():
         "amgsetup_vertex_coloring_jones_plassmann": (I, [I, i, i, i, d]),
         "amgsetup_vertex_coloring_LDF": (I, [I, i, i, i, d]),
         "amgsetup_cljp_weights": (None, [I, i, i, I, d]),
+        "amgsetup_cljp_random": (None, [I, d]),
         "amgsetup_cljp_select": (I, [I, i, i, i, i, d, i]),
         "amgsetup_cljp_naive_splitting": (None, [I, i, i, i, i, i, I]),
         # the classical setup (classical.py)

@@ -75,11 +75,17 @@ FLAT_TABLE = {
     "satisfy_constraints_helper": ("iiiiVVVIIV", True),
     "calc_BtB": ("iiiViVII", True),
     "truncate_rows_csr": ("iiIIV", True),
+    # amg_core/ruge_stuben.h, the row-parallel stages of the classical setup (csrc/split.hip)
+    "classical_strength_of_connection": ("iFIIVIIV", True),
+    "maximum_row_value": ("iVIIV", True),
+    "rs_direct_interpolation_pass1": ("iIIII", True),
+    "rs_direct_interpolation_pass2": ("iIIVIIVIIIV", True),
 }
 # entries whose values are float64 only: another value dtype is the table's overload error
 FLAT_F64_ONLY = frozenset(["incomplete_mat_mult_csr", "apply_distance_filter", "apply_absolute_distance_filter",
                            "min_blocks", "incomplete_mat_mult_bsr", "satisfy_constraints_helper", "calc_BtB",
-                           "truncate_rows_csr"])
+                           "truncate_rows_csr", "classical_strength_of_connection", "maximum_row_value",
+                           "rs_direct_interpolation_pass1", "rs_direct_interpolation_pass2"])
 # value dtype -> symbol suffix, and per suffix the C types of a value pointer and of the real scalar F
 VALUE_SUFFIX = {np.dtype(np.float64): "f64", np.dtype(np.float32): "f32",
                 np.dtype(np.complex64): "c64", np.dtype(np.complex128): "c128"}
@@ -196,6 +202,8 @@ def lib():
         "amg_energy_fetch": [V, V],
         "amg_mis_device": [I, V, V, V, I, I, I, V, c_int_p, c_dbl_p],
         "amg_cljp_device": [I, V, V, V, V, V, V, c_int_p, c_dbl_p],
+        "amg_classical_level_device": [I, V, V, V, D, I, I, V, C.POINTER(C.c_void_p), C.POINTER(C.c_long), c_int_p, c_dbl_p],
+        "amg_classical_level_fetch": [V, V, V, V, V, V, V, V, c_dbl_p],
         "amg_hierx_create": [I, I, I, C.POINTER(C.c_void_p)],
         "amg_hierx_set_matrix": [V, I, I, I, I, I, I, I, V, V, V],
         "amg_hierx_set_smoother": [V, I, I, C.POINTER(SmootherDescX)],

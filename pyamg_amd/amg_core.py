@@ -20,7 +20,8 @@ __all__ = ["gauss_seidel", "bsr_gauss_seidel", "jacobi", "bsr_jacobi", "gauss_se
            "csr_matvec", "bsr_matvec", "overlapping_schwarz_csr", "extract_subblocks",
            "incomplete_mat_mult_csr", "apply_distance_filter", "apply_absolute_distance_filter", "min_blocks",
            "incomplete_mat_mult_bsr", "satisfy_constraints_helper", "calc_BtB", "truncate_rows_csr",
-           "maximal_independent_set_parallel", "cljp_naive_splitting"]
+           "maximal_independent_set_parallel", "cljp_naive_splitting", "classical_strength_of_connection",
+           "maximum_row_value", "rs_direct_interpolation_pass1", "rs_direct_interpolation_pass2"]
 
 _INDEX = np.dtype(np.intc)
 
@@ -61,6 +62,8 @@ def _call(name, *args):
     if len(args) != len(kinds):
         raise TypeError("%s: %d arguments expected" % (name, len(kinds)))
     suffix = _check_arrays(name, kinds, args)
+    if suffix is None and name in _lib.FLAT_F64_ONLY:
+        suffix = "f64"              # an entry of index arrays alone has the one instantiation
     if name in _lib.FLAT_F64_ONLY and suffix != "f64":
         raise _overload_error(name)
     vptr, real = _lib.VALUE_CTYPES[suffix]
@@ -178,6 +181,29 @@ def truncate_rows_csr(n_row, k, Sp, Sj, Sx):
     """smoothed_aggregation.h:898-960: every row longer than k keeps its k entries of largest magnitude, chosen and
     ordered as the reference's quicksort leaves them; the other entries become 0.0; Sj and Sx in place; float64"""
     _call("truncate_rows_csr", n_row, k, Sp, Sj, Sx)
+
+
+def classical_strength_of_connection(n_row, theta, Ap, Aj, Ax, Sp, Sj, Sx):
+    """ruge_stuben.h:46-93: Sp, Sj and Sx (as long as A's arrays) receive the diagonal of A and the off-diagonals with
+    |a_ij| >= theta * max_k!=i |a_ik|, in A's stored order; float64"""
+    _call("classical_strength_of_connection", n_row, theta, Ap, Aj, Ax, Sp, Sj, Sx)
+
+
+def maximum_row_value(n_row, x, Ap, Aj, Ax):
+    """ruge_stuben.h:110-130: x[i] = the largest magnitude of row i (DBL_MIN for an empty row); float64"""
+    _call("maximum_row_value", n_row, x, Ap, Aj, Ax)
+
+
+def rs_direct_interpolation_pass1(n_nodes, Sp, Sj, splitting, Bp):
+    """ruge_stuben.h:497-516: the row offsets Bp of the direct-interpolation prolongator for the strength matrix S and
+    the C/F splitting (1 = C, 0 = F); Bp[n_nodes] is its number of entries"""
+    _call("rs_direct_interpolation_pass1", n_nodes, Sp, Sj, splitting, Bp)
+
+
+def rs_direct_interpolation_pass2(n_nodes, Ap, Aj, Ax, Sp, Sj, Sx, splitting, Bp, Bj, Bx):
+    """ruge_stuben.h:520-595: the columns Bj (in coarse numbering) and weights Bx of the prolongator whose offsets Bp
+    pass 1 returned; float64"""
+    _call("rs_direct_interpolation_pass2", n_nodes, Ap, Aj, Ax, Sp, Sj, Sx, splitting, Bp, Bj, Bx)
 
 
 def extract_subblocks(Ap, Aj, Ax, Tx, Tp, Sj, Sp, nsdomains, nrows):

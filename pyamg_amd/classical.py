@@ -9,13 +9,19 @@ same integers:
   host    the reference's sweeps restated in csrc/setup_host.cpp;
   device  Luby's rounds / the CLJP selection passes in HBM (csrc/split.hip); weights and colourings come from the host.
 
+Classical strength and direct interpolation have the same two routes with the same bits (csrc/split.hip, DESIGN.md
+section 8i); their device route takes A as canonical CSR (sorted rows, no duplicate columns, no stored zeros, finite
+values).  ``ruge_stuben_solver(..., device=True)`` builds a level with classical strength and ``CF`` 'PMIS' or 'CLJP'
+in HBM from one upload of A (strength, graph, weights, splitting, interpolation); with another ``CF`` strength and
+interpolation take their device routes one by one.  R = P^T and the Galerkin product run on the host.
+
 ``device=True`` takes the device route and raises NotImplementedError for what it cannot take (a sweep limit, a
 structurally unsymmetric graph); ``device=False`` is the host route; ``device=None`` is the host route unless
 ``DEVICE_AUTO`` and a GPU, and then falls back to the host route where the device route refuses.
 
 The global numpy RNG is drawn where the reference draws it: rand(n) once per PMIS / PMISc call, after the colouring's
 own draw.  CLJP's weights come from glibc srand(2448422) / rand(), the process's C generator, as in the reference.
-Strength, interpolation and the Galerkin product run on the host.  Other strength measures raise NotImplementedError.
+Other strength measures raise NotImplementedError.
 """
 import ctypes as C
 from warnings import warn
@@ -24,7 +30,7 @@ import numpy as np
 from scipy.sparse import SparseEfficiencyWarning, csr_matrix, isspmatrix_csr
 
 from . import graph
-from ._host import dp as _dp, host_lib, i32 as _i32, ip as _ip, outside, route
+from ._host import attempt, dp as _dp, host_lib, i32 as _i32, ip as _ip, outside, route
 from .aggregation import symmetric_strength_of_connection
 from .graph import vertex_coloring
 from .multilevel import multilevel_solver
@@ -33,14 +39,65 @@ from .smoothing import change_smoothers
 __all__ = ["ruge_stuben_solver", "classical_strength_of_connection", "RS", "direct_interpolation",
            "PMIS", "PMISc", "CLJP", "CLJPc", "MIS", "preprocess"]
 
-# What device=None does when a GPU is present: the host route until the measurement in profiles/r16_splitting.txt says
-# otherwise.
+# What device=None does when a GPU is present: the host route.  profiles/r16_splitting.txt did not justify the device
+# route of a splitting alone; profiles/r17_classical_level.txt would justify the chained level
+# (section 8i), a switch left to a change of its own.
 DEVICE_AUTO = False
 
 _lib = host_lib                 # the name tests/test_setup_golden.py imports
 
-def classical_strength_of_connection(A, theta=0.0):
-    """pyamg/strength.py:111-210, amg_core/ruge_stuben.h:46-99"""
+
+def _operator_order(A, what, product_order=False):
+    """What the device routes of strength and interpolation take: a square float64 CSR operator without duplicate
+    columns, stored zeros or non-finite values whose rows are sorted (canonical CSR).  Only then are A's values at S's
+    positions, in S's order, what C.multiply(A) returns.  product_order: also rows that are not sorted, as scipy's
+    sparse product leaves the Galerkin operator; the host route then meets every row of S from its last entry to its
+    first (scipy's element-wise product of operands that are not canonical emits a row in reverse).  Returns whether
+    that is the case.  Anything else is a refusal, raised before the device library is touched."""
+    if not isspmatrix_csr(A):
+        raise outside("%s of an operator that is not CSR" % what)
+    if A.shape[0] != A.shape[1] or A.dtype != np.float64 or A.nnz >= 2 ** 31:
+        raise outside("%s of an operator that is not square float64 with fewer than 2^31 entries" % what)
+    if A.nnz and not (np.all(A.data != 0) and np.all(np.isfinite(A.data))):
+        raise outside("%s of an operator with stored zeros or non-finite values" % what)
+    if _sorted_unique_rows(A):
+        if not A.has_canonical_format:
+            raise outside("%s of an operator whose format flags deny its sorted rows" % what)
+        return False
+    if not product_order:
+        raise outside("%s of an operator with unsorted rows or duplicated columns" % what)
+    keys = np.sort(_entry_keys(A))
+    if np.any(keys[1:] == keys[:-1]) or A.has_canonical_format:
+        raise outside("%s of an operator with duplicated columns" % what)
+    return True
+
+
+def _entry_keys(A):
+    return np.repeat(np.arange(A.shape[0], dtype=np.int64), np.diff(A.indptr)) * A.shape[1] + A.indices
+
+
+def _sorted_unique_rows(A):
+    if A.nnz < 2:
+        return True
+    rows = np.repeat(np.arange(A.shape[0]), np.diff(A.indptr))
+    return not np.any((rows[1:] == rows[:-1]) & (np.diff(A.indices.astype(np.int64)) <= 0))
+
+
+def _scaled_strength(Sp, Sj, Sx, shape):
+    """|S| with every row divided by its largest entry (util/utils.py scale_rows_by_largest_entry, by division)"""
+    S = csr_matrix((Sx, Sj, Sp), shape=shape)
+    S.data = np.abs(S.data)
+    counts = np.diff(S.indptr)
+    nz = counts > 0
+    largest = np.ones(S.shape[0])
+    if S.nnz:
+        largest[nz] = np.maximum.reduceat(S.data, S.indptr[:-1][nz])
+    largest[largest == 0] = 1.0
+    S.data = S.data / np.repeat(largest, counts)
+    return S
+
+
+def _strength_host(A, theta):
     if not isspmatrix_csr(A):
         warn("Implicit conversion of A to csr", SparseEfficiencyWarning)
         A = csr_matrix(A)
@@ -50,17 +107,30 @@ def classical_strength_of_connection(A, theta=0.0):
     Sp = np.empty_like(Ap); Sj = np.empty_like(Aj); Sx = np.empty_like(Ax)
     nnz = host_lib().amgsetup_classical_strength(A.shape[0], float(theta), _ip(Ap), _ip(Aj), _dp(Ax), _ip(Sp), _ip(Sj),
                                                  _dp(Sx))
-    S = csr_matrix((Sx[:nnz], Sj[:nnz], Sp), shape=A.shape)
-    S.data = np.abs(S.data)
-    # scale_rows_by_largest_entry
-    counts = np.diff(S.indptr)
-    nz = counts > 0
-    largest = np.ones(S.shape[0])
-    if S.nnz:
-        largest[nz] = np.maximum.reduceat(S.data, S.indptr[:-1][nz])
-    largest[largest == 0] = 1.0
-    S.data = S.data / np.repeat(largest, counts)
-    return S
+    return _scaled_strength(Sp, Sj[:nnz], Sx[:nnz], A.shape)
+
+
+def _strength_device(A, theta, product_order=False):
+    from . import amg_core
+    _operator_order(A, "the device route of classical strength", product_order)
+    if theta < 0 or theta > 1:
+        raise ValueError("expected theta in [0,1]")
+    Ap, Aj, Ax = _i32(A.indptr), _i32(A.indices), np.ascontiguousarray(A.data, dtype=np.float64)
+    Sp = np.empty_like(Ap); Sj = np.empty_like(Aj); Sx = np.empty_like(Ax)
+    amg_core.classical_strength_of_connection(A.shape[0], float(theta), Ap, Aj, Ax, Sp, Sj, Sx)
+    nnz = int(Sp[-1])
+    return _scaled_strength(Sp, Sj[:nnz], Sx[:nnz], A.shape)
+
+
+def _strength(A, theta=0.0, device=None, product_order=False):
+    return attempt(route(device, DEVICE_AUTO), lambda: _strength_device(A, theta, product_order),
+                   lambda: _strength_host(A, theta))
+
+
+def classical_strength_of_connection(A, theta=0.0, device=None):
+    """pyamg/strength.py:111-210, amg_core/ruge_stuben.h:46-99.  device: where the strength kernel runs (module
+    docstring); both routes return the same bits."""
+    return _strength(A, theta, device)
 
 
 def remove_diagonal(S):
@@ -185,8 +255,7 @@ def preprocess(S, coloring_method=None):
     return (weights, G, S, T)
 
 
-def direct_interpolation(A, Cm, splitting):
-    """pyamg/classical/interpolate.py:13-75"""
+def _interpolation_host(A, Cm, splitting):
     if not isspmatrix_csr(A):
         raise TypeError("expected csr_matrix for A")
     if not isspmatrix_csr(Cm):
@@ -207,6 +276,119 @@ def direct_interpolation(A, Cm, splitting):
     return csr_matrix((Px, Pj, Pp))
 
 
+def pattern_values(A, Cm, reverse=False):
+    """C.multiply(A) without the product, for an A without duplicate columns and a C with unique columns per row: the
+    entries of C's pattern that A stores, with A's values.  Sorted rows of both: in C's order.  reverse (rows that are
+    not sorted): every row from C's last entry to its first.  Returns (indptr, indices, data)."""
+    n = A.shape[0]
+    keys_a, keys_c = _entry_keys(A), _entry_keys(Cm)
+    if reverse:                             # rows that are not sorted: search a sorted copy of A's keys
+        order = np.argsort(keys_a, kind="stable")
+        at = np.searchsorted(keys_a[order], keys_c)
+        found = at < len(keys_a)
+        at = order[np.minimum(at, max(len(keys_a) - 1, 0))] if len(keys_a) else at
+    else:
+        at = np.searchsorted(keys_a, keys_c)
+        found = at < len(keys_a)
+    found[found] = keys_a[at[found]] == keys_c[found]
+    rows_c = np.repeat(np.arange(n), np.diff(Cm.indptr))[found]
+    Cp = np.zeros(n + 1, dtype=np.intc)
+    np.cumsum(np.bincount(rows_c, minlength=n), out=Cp[1:])
+    Cj, Cx = _i32(Cm.indices[found]), np.ascontiguousarray(A.data[at[found]], dtype=np.float64)
+    if reverse and len(Cj):
+        back = Cp[rows_c] + Cp[rows_c + 1] - 1 - np.arange(len(Cj))
+        Cj, Cx = np.ascontiguousarray(Cj[back]), np.ascontiguousarray(Cx[back])
+    return Cp, Cj, Cx
+
+
+def _interpolation_device(A, Cm, splitting, product_order=False):
+    from . import amg_core
+    what = "the device route of direct interpolation"
+    reverse = _operator_order(A, what, product_order)
+    if not isspmatrix_csr(Cm) or Cm.shape != A.shape:
+        raise outside("%s on a strength matrix that is not CSR of A's shape" % what)
+    if reverse:
+        keys = np.sort(_entry_keys(Cm))
+        if np.any(keys[1:] == keys[:-1]) or Cm.has_canonical_format:
+            raise outside("%s on a strength matrix with duplicated columns or sorted rows beside an unsorted A" % what)
+    elif not _sorted_unique_rows(Cm) or not Cm.has_canonical_format:
+        raise outside("%s on a strength matrix with unsorted rows or duplicated columns" % what)
+    n = A.shape[0]
+    splitting = _i32(splitting)
+    if splitting.shape != (n,):
+        raise ValueError("expected one splitting value per row")
+    Cp, Cj, Cx = pattern_values(A, Cm, reverse)
+    Ap, Aj, Ax = _i32(A.indptr), _i32(A.indices), np.ascontiguousarray(A.data, dtype=np.float64)
+    Pp = np.empty(n + 1, dtype=np.intc)
+    amg_core.rs_direct_interpolation_pass1(n, Cp, Cj, splitting, Pp)
+    Pj = np.empty(int(Pp[-1]), dtype=np.intc)
+    Px = np.empty(int(Pp[-1]), dtype=np.float64)
+    amg_core.rs_direct_interpolation_pass2(n, Ap, Aj, Ax, Cp, Cj, Cx, splitting, Pp, Pj, Px)
+    return csr_matrix((Px, Pj, Pp))
+
+
+def _interpolation(A, Cm, splitting, device=None, product_order=False):
+    return attempt(route(device, DEVICE_AUTO), lambda: _interpolation_device(A, Cm, splitting, product_order),
+                   lambda: _interpolation_host(A, Cm, splitting))
+
+
+def direct_interpolation(A, Cm, splitting, device=None):
+    """pyamg/classical/interpolate.py:13-75.  device: where the two passes run (module docstring); both routes return
+    the same bits."""
+    return _interpolation(A, Cm, splitting, device)
+
+
+_CHAINED_SPLITTINGS = {"PMIS": 0, "CLJP": 1}
+LEVEL_STAGES = ("upload", "strength", "graph", "splitting", "interpolation", "fetch")
+
+
+def classical_level_device(A, theta, CF, keep=False, times=None, product_order=False):
+    """One level in HBM from one upload of A (amg_classical_level_device): classical strength, the strength graph and
+    its transpose, the start weights, the PMIS or CLJP splitting and direct interpolation.  Returns (splitting, P, S);
+    S, the scaled strength matrix, only with keep (None otherwise).  The random start values are drawn on the host
+    where the host route draws them: rand(n) of the global numpy RNG for PMIS, glibc rand() after srand(2448422) for
+    CLJP.  times: a list that receives the milliseconds of LEVEL_STAGES.  product_order: _operator_order."""
+    from . import _lib
+    reverse = _operator_order(A, "the device route of a classical level", product_order)
+    if theta < 0 or theta > 1:
+        raise ValueError("expected theta in [0,1]")
+    n = A.shape[0]
+    if n == 0:
+        raise outside("the device route of a classical level without rows")
+    kind = _CHAINED_SPLITTINGS[CF]
+    Ap, Aj, Ax = _i32(A.indptr), _i32(A.indices), np.ascontiguousarray(A.data, dtype=np.float64)
+    if kind == 0:
+        r = np.ascontiguousarray(np.random.rand(n))
+    else:
+        r = np.empty(n, dtype=np.float64)
+        host_lib().amgsetup_cljp_random(n, _dp(r))
+    handle = C.c_void_p()
+    sizes = (C.c_long * 2)()
+    ms = (C.c_double * 6)()
+    _lib.check(_lib.lib().amg_classical_level_device(n, Ap.ctypes.data, Aj.ctypes.data, Ax.ctypes.data, float(theta), kind,
+                                                     int(reverse), r.ctypes.data, C.byref(handle), sizes, None, ms))
+    ptr = lambda a: None if a is None else a.ctypes.data
+    try:
+        splitting = np.empty(n, dtype=np.intc)
+        Pp = np.empty(n + 1, dtype=np.intc)
+        Pj = np.empty(sizes[1], dtype=np.intc)
+        Px = np.empty(sizes[1], dtype=np.float64)
+        Sp = Sj = Sx = None
+        if keep:
+            Sp = np.empty(n + 1, dtype=np.intc)
+            Sj = np.empty(sizes[0], dtype=np.intc)
+            Sx = np.empty(sizes[0], dtype=np.float64)
+    except BaseException:
+        _lib.lib().amg_classical_level_fetch(handle, None, None, None, None, None, None, None, None)    # releases the result
+        raise
+    _lib.check(_lib.lib().amg_classical_level_fetch(handle, ptr(splitting), ptr(Pp), ptr(Pj), ptr(Px), ptr(Sp), ptr(Sj), ptr(Sx),
+                                                    ms))
+    if times is not None:
+        times.extend(ms[k] for k in range(6))
+    S = csr_matrix((Sx, Sj, Sp), shape=A.shape) if keep else None
+    return splitting, csr_matrix((Px, Pj, Pp)), S
+
+
 _PARALLEL_SPLITTINGS = {"PMIS": PMIS, "PMISc": PMISc, "CLJP": CLJP, "CLJPc": CLJPc}
 
 
@@ -219,12 +401,14 @@ def unpack_arg(v):
 def ruge_stuben_solver(A, strength=("classical", {"theta": 0.25}), CF="RS",
                        presmoother=("gauss_seidel", {"sweep": "symmetric"}),
                        postsmoother=("gauss_seidel", {"sweep": "symmetric"}),
-                       max_levels=10, max_coarse=500, keep=False, **kwargs):
+                       max_levels=10, max_coarse=500, keep=False, device=None, **kwargs):
     """Create a multilevel solver using Classical AMG (pyamg/classical/classical.py:22-116)
 
     CF : 'RS', 'PMIS', 'PMISc', 'CLJP' or 'CLJPc', or (name, {'device': True | False | None}) for the four parallel
     coarsenings: where their selection loop runs (module docstring).  PMIS and PMISc draw the global numpy RNG once
-    per level."""
+    per level.
+    device : where classical strength and direct interpolation run, and with CF 'PMIS' or 'CLJP' the whole level
+    (module docstring); every route builds the same hierarchy."""
     levels = [multilevel_solver.level()]
     if not isspmatrix_csr(A):
         try:
@@ -237,20 +421,19 @@ def ruge_stuben_solver(A, strength=("classical", {"theta": 0.25}), CF="RS",
         raise ValueError("expected square matrix")
     levels[-1].A = A
     while len(levels) < max_levels and levels[-1].A.shape[0] > max_coarse:
-        extend_hierarchy(levels, strength, CF, keep)
+        extend_hierarchy(levels, strength, CF, keep, device)
     ml = multilevel_solver(levels, **kwargs)
     change_smoothers(ml, presmoother, postsmoother)
     return ml
 
 
-def extend_hierarchy(levels, strength, CF, keep):
-    """classical.py:120-188"""
-    A = levels[-1].A
+def _stages(A, strength, CF, device):
+    """strength, splitting and interpolation one by one -> (C, splitting, P)"""
     fn, kwargs = unpack_arg(strength)
     if fn == "symmetric":
         Cm = symmetric_strength_of_connection(A, **kwargs)
     elif fn == "classical":
-        Cm = classical_strength_of_connection(A, **kwargs)
+        Cm = _strength(A, device=device, product_order=True, **kwargs)
     elif fn is None:
         Cm = A
     else:
@@ -262,7 +445,32 @@ def extend_hierarchy(levels, strength, CF, keep):
         splitting = _PARALLEL_SPLITTINGS[fn](Cm, **kwargs)
     else:
         raise NotImplementedError("C/F splitting %r is outside the restated setup" % (fn,))
-    P = direct_interpolation(A, Cm, splitting)
+    return Cm, splitting, _interpolation(A, Cm, splitting, device, product_order=True)
+
+
+def _chained(A, strength, CF, keep):
+    """the level in HBM where strength is classical with theta alone and CF is PMIS or CLJP not sent to the host;
+    None otherwise"""
+    fn, kwargs = unpack_arg(strength)
+    name, cf_kwargs = unpack_arg(CF)
+    if fn != "classical" or set(kwargs) - {"theta"} or name not in _CHAINED_SPLITTINGS:
+        return None
+    if set(cf_kwargs) - {"device"} or cf_kwargs.get("device", True) is False:
+        return None
+    splitting, P, S = classical_level_device(A, kwargs.get("theta", 0.0), name, keep=keep, product_order=True)
+    return S, splitting, P
+
+
+def extend_hierarchy(levels, strength, CF, keep, device=None):
+    """classical.py:120-188"""
+    A = levels[-1].A
+    way = route(device, DEVICE_AUTO)
+
+    def on_device():
+        built = _chained(A, strength, CF, keep)
+        return built if built is not None else _stages(A, strength, CF, way)
+
+    Cm, splitting, P = attempt(way, on_device, lambda: _stages(A, strength, CF, False))
     R = P.T.tocsr()
     if keep:
         levels[-1].C = Cm

@@ -1373,6 +1373,14 @@ int amgsetup_vertex_coloring_LDF(int n, const int *Ap, const int *Aj, int *x, co
     return n > 0 ? *std::max_element(x, x + n) : -1;
 }
 
+// ruge_stuben.h:357-360: the random part of the CLJP start weights alone, rand() / RAND_MAX after srand(2448422), for a
+// route that adds the in-degrees elsewhere
+void amgsetup_cljp_random(int n, double *r)
+{
+    srand(2448422);
+    for (int i = 0; i < n; ++i) r[i] = double(rand()) / RAND_MAX;
+}
+
 // ruge_stuben.h:343-371: the CLJP start weights.  colorflag 1: colour / ncolors of vertex_coloring_mis on S; else glibc
 // rand() / RAND_MAX after srand(2448422) (the process's C generator, as in the reference).  Then +1 per vertex that
 // depends on i, one addition at a time.

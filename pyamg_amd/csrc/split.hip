@@ -3,8 +3,13 @@
 // (amg_core/ruge_stuben.h:373-478).  Both return the integers of the reference's sequential sweeps (DESIGN.md
 // section 8h): every decision below is a function of the state at a kernel boundary, or is one that a stale read can
 // only postpone.  State arrays hold one int per vertex; offsets are widened to 64 bits inside the kernels.
+// Below them, the stages that turn a splitting into a level: classical strength, direct interpolation and the level
+// chained in HBM, which runs the two loops above on buffers its earlier stages left there.
 #include "flat.hpp"
 
+#include <rocprim/device/device_scan.hpp>
+
+#include <cfloat>
 #include <string>
 
 using namespace amg;
@@ -169,6 +174,75 @@ __global__ __launch_bounds__(TB) void fill_int_kernel(long count, int value, int
     if (e < count) out[e] = value;
 }
 
+// The two selection loops on buffers that are already in HBM: amg_mis_device and amg_cljp_device below run them on what
+// they uploaded, the chained classical level at the end of this file on what its earlier stages left there.
+// mis_rounds_device: x: the states, in place; flag: one int of device memory; *rounds: rounds run.
+// cljp_passes_device: S holds nnz entries, T = S^T in any row order; weight: the start weights, changed in place;
+// splitting: n ints, written (1 = C, 0 = F); *passes: passes run.
+
+int mis_rounds_device(int n, const int *Ap, const int *Aj, const double *y, int active, int C, int F, int *x, int *flag, int *rounds)
+{
+    int done = 0, again = 1;
+    while (again) {
+        if (done > n) { set_error("mis: no vertex was decided in a round"); return AMG_ESTATE; }    // a round decides >= 1
+        hipLaunchKernelGGL(mis_select_kernel, grid_for(n), dim3(TB), 0, nullptr, n, Ap, Aj, y, active, C, x, flag);
+        LAUNCH_CHECK("mis: selection launch");
+        hipLaunchKernelGGL(mis_retire_kernel, grid_for(n), dim3(TB), 0, nullptr, n, Ap, Aj, active, C, F, x, flag);
+        LAUNCH_CHECK("mis: retirement launch");
+        AMG_HIP(hipMemcpy(&again, flag, sizeof(int), hipMemcpyDeviceToHost));
+        ++done;
+    }
+    *rounds = done;
+    return 0;
+}
+
+int cljp_passes_device(int n, long nnz, const int *Sp, const int *Sj, const int *Tp, const int *Tj, double *weight, int *splitting,
+                       int *passes)
+{
+    const size_t vbytes = sizeof(int) * (size_t)n, ebytes = sizeof(int) * (size_t)nnz;
+    DBuf dSrow, dD, dhas, ddec, dmark, dopen;
+    CHK(dSrow.alloc(ebytes)); CHK(dmark.alloc(ebytes));
+    CHK(dD.alloc(vbytes)); CHK(dhas.alloc(vbytes)); CHK(ddec.alloc(vbytes));
+    CHK(dopen.alloc(sizeof(int)));
+    hipLaunchKernelGGL(fill_int_kernel, grid_for(n), dim3(TB), 0, nullptr, (long)n, U_NODE, splitting);
+    LAUNCH_CHECK("cljp: state launch");
+    hipLaunchKernelGGL(fill_int_kernel, grid_for(n), dim3(TB), 0, nullptr, (long)n, 0, ddec.i());
+    LAUNCH_CHECK("cljp: count launch");
+    if (nnz > 0) {
+        hipLaunchKernelGGL(fill_int_kernel, grid_for(nnz), dim3(TB), 0, nullptr, nnz, 1, dmark.i());
+        LAUNCH_CHECK("cljp: edge mark launch");
+        hipLaunchKernelGGL(entry_rows_kernel, grid_for(nnz), dim3(TB), 0, nullptr, n, nnz, Sp, dSrow.i());
+        LAUNCH_CHECK("cljp: edge row launch");
+    }
+    int done = 0, open = n;
+    while (open > 0) {
+        if (done >= n) { set_error("cljp: no vertex was selected in a pass"); return AMG_ESTATE; }  // a pass selects >= 1
+        hipLaunchKernelGGL(cljp_select_kernel, grid_for(n), dim3(TB), 0, nullptr, n, Sp, Sj, Tp, Tj, (const double *)weight,
+                           (const int *)splitting, dD.i(), dhas.i(), dopen.i());
+        LAUNCH_CHECK("cljp: selection launch");
+        if (nnz > 0) {
+            hipLaunchKernelGGL(cljp_p5_kernel, grid_for(nnz), dim3(TB), 0, nullptr, nnz, (const int *)dSrow.i(), Sj, (const int *)dD.i(),
+                               (const int *)splitting, dmark.i(), ddec.i(), dhas.i());
+            LAUNCH_CHECK("cljp: P5 launch");
+        }
+        hipLaunchKernelGGL((cljp_apply_kernel<true, false>), grid_for(n), dim3(TB), 0, nullptr, n, (const int *)dD.i(), weight, splitting,
+                           ddec.i(), dopen.i());
+        LAUNCH_CHECK("cljp: P5 weights launch");
+        if (nnz > 0) {
+            hipLaunchKernelGGL(cljp_p6_kernel, grid_for(nnz), dim3(TB), 0, nullptr, nnz, Sp, (const int *)dSrow.i(), Sj, (const int *)dD.i(),
+                               (const int *)dhas.i(), (const int *)splitting, dmark.i(), ddec.i());
+            LAUNCH_CHECK("cljp: P6 launch");
+        }
+        hipLaunchKernelGGL((cljp_apply_kernel<false, true>), grid_for(n), dim3(TB), 0, nullptr, n, (const int *)dD.i(), weight, splitting,
+                           ddec.i(), dopen.i());
+        LAUNCH_CHECK("cljp: P6 weights launch");
+        AMG_HIP(hipMemcpy(&open, dopen.p, sizeof(int), hipMemcpyDeviceToHost));
+        ++done;
+    }
+    *passes = done;
+    return 0;
+}
+
 // n + 1 offsets from 0 up, never decreasing, every column inside the matrix: nothing is launched on less
 int check_graph(const char *who, int n, const int *p, const int *j)
 {
@@ -205,18 +279,8 @@ int amg_mis_device(int n, const int *Ap, const int *Aj, const double *y, int act
     CHK(dflag.alloc(sizeof(int)));
     AMG_HIP(hipDeviceSynchronize());
     const double upload_ms = timer.lap();
-    int done = 0, again = 1;
-    while (again) {
-        if (done > n) { set_error("mis: no vertex was decided in a round"); return AMG_ESTATE; }    // a round decides >= 1
-        hipLaunchKernelGGL(mis_select_kernel, grid_for(n), dim3(TB), 0, nullptr, n, (const int *)dp.i(), (const int *)dj.i(),
-                           (const double *)dy.d(), active, C, dx.i(), dflag.i());
-        LAUNCH_CHECK("mis: selection launch");
-        hipLaunchKernelGGL(mis_retire_kernel, grid_for(n), dim3(TB), 0, nullptr, n, (const int *)dp.i(), (const int *)dj.i(), active, C, F,
-                           dx.i(), dflag.i());
-        LAUNCH_CHECK("mis: retirement launch");
-        AMG_HIP(hipMemcpy(&again, dflag.p, sizeof(int), hipMemcpyDeviceToHost));
-        ++done;
-    }
+    int done = 0;
+    CHK(mis_rounds_device(n, dp.i(), dj.i(), dy.d(), active, C, F, dx.i(), dflag.i(), &done));
     const double rounds_ms = timer.lap();
     CHK(dx.to_host(x, sizeof(int) * (size_t)n));
     if (rounds) *rounds = done;
@@ -238,58 +302,584 @@ int amg_cljp_device(int n, const int *Sp, const int *Sj, const int *Tp, const in
     LapClock timer;
     const long nnz = Sp[n];
     const size_t vbytes = sizeof(int) * (size_t)n, ebytes = sizeof(int) * (size_t)nnz;
-    DBuf dSp, dSj, dTp, dTj, dSrow, dw, dsplit, dD, dhas, ddec, dmark, dopen;
+    DBuf dSp, dSj, dTp, dTj, dw, dsplit;
     CHK(dSp.from_host(Sp, sizeof(int) * ((size_t)n + 1)));
     CHK(dSj.from_host(Sj, ebytes));
     CHK(dTp.from_host(Tp, sizeof(int) * ((size_t)n + 1)));
     CHK(dTj.from_host(Tj, ebytes));
     CHK(dw.from_host(weight0, sizeof(double) * (size_t)n));
-    CHK(dSrow.alloc(ebytes)); CHK(dmark.alloc(ebytes));
-    CHK(dsplit.alloc(vbytes)); CHK(dD.alloc(vbytes)); CHK(dhas.alloc(vbytes)); CHK(ddec.alloc(vbytes));
-    CHK(dopen.alloc(sizeof(int)));
+    CHK(dsplit.alloc(vbytes));
     AMG_HIP(hipDeviceSynchronize());
     const double upload_ms = timer.lap();
-    hipLaunchKernelGGL(fill_int_kernel, grid_for(n), dim3(TB), 0, nullptr, (long)n, U_NODE, dsplit.i());
-    LAUNCH_CHECK("cljp: state launch");
-    hipLaunchKernelGGL(fill_int_kernel, grid_for(n), dim3(TB), 0, nullptr, (long)n, 0, ddec.i());
-    LAUNCH_CHECK("cljp: count launch");
-    if (nnz > 0) {
-        hipLaunchKernelGGL(fill_int_kernel, grid_for(nnz), dim3(TB), 0, nullptr, nnz, 1, dmark.i());
-        LAUNCH_CHECK("cljp: edge mark launch");
-        hipLaunchKernelGGL(entry_rows_kernel, grid_for(nnz), dim3(TB), 0, nullptr, n, nnz, (const int *)dSp.i(), dSrow.i());
-        LAUNCH_CHECK("cljp: edge row launch");
-    }
-    int done = 0, open = n;
-    while (open > 0) {
-        if (done >= n) { set_error("cljp: no vertex was selected in a pass"); return AMG_ESTATE; }  // a pass selects >= 1
-        hipLaunchKernelGGL(cljp_select_kernel, grid_for(n), dim3(TB), 0, nullptr, n, (const int *)dSp.i(), (const int *)dSj.i(),
-                           (const int *)dTp.i(), (const int *)dTj.i(), (const double *)dw.d(), (const int *)dsplit.i(), dD.i(), dhas.i(),
-                           dopen.i());
-        LAUNCH_CHECK("cljp: selection launch");
-        if (nnz > 0) {
-            hipLaunchKernelGGL(cljp_p5_kernel, grid_for(nnz), dim3(TB), 0, nullptr, nnz, (const int *)dSrow.i(), (const int *)dSj.i(),
-                               (const int *)dD.i(), (const int *)dsplit.i(), dmark.i(), ddec.i(), dhas.i());
-            LAUNCH_CHECK("cljp: P5 launch");
-        }
-        hipLaunchKernelGGL((cljp_apply_kernel<true, false>), grid_for(n), dim3(TB), 0, nullptr, n, (const int *)dD.i(), dw.d(), dsplit.i(),
-                           ddec.i(), dopen.i());
-        LAUNCH_CHECK("cljp: P5 weights launch");
-        if (nnz > 0) {
-            hipLaunchKernelGGL(cljp_p6_kernel, grid_for(nnz), dim3(TB), 0, nullptr, nnz, (const int *)dSp.i(), (const int *)dSrow.i(),
-                               (const int *)dSj.i(), (const int *)dD.i(), (const int *)dhas.i(), (const int *)dsplit.i(), dmark.i(),
-                               ddec.i());
-            LAUNCH_CHECK("cljp: P6 launch");
-        }
-        hipLaunchKernelGGL((cljp_apply_kernel<false, true>), grid_for(n), dim3(TB), 0, nullptr, n, (const int *)dD.i(), dw.d(), dsplit.i(),
-                           ddec.i(), dopen.i());
-        LAUNCH_CHECK("cljp: P6 weights launch");
-        AMG_HIP(hipMemcpy(&open, dopen.p, sizeof(int), hipMemcpyDeviceToHost));
-        ++done;
-    }
+    int done = 0;
+    CHK(cljp_passes_device(n, nnz, dSp.i(), dSj.i(), dTp.i(), dTj.i(), dw.d(), dsplit.i(), &done));
     const double rounds_ms = timer.lap();
     CHK(dsplit.to_host(splitting, vbytes));
     if (passes) *passes = done;
     if (times_ms) { times_ms[0] = upload_ms; times_ms[1] = rounds_ms; times_ms[2] = timer.lap(); }
+    return 0;
+}
+
+}   // extern "C"
+
+// ================================================================================================ classical levels
+// Second part of this file: the row-parallel stages of the classical (Ruge-Stuben) setup on the device (DESIGN.md
+// section 8i): classical strength of connection (amg_core/ruge_stuben.h:46-93), maximum_row_value (:110-130) and the
+// two passes of direct interpolation (:497-595), as flat amg_core entries and chained into one level that stays in HBM from the upload of A
+// to the download of the splitting and P (amg_classical_level_device / amg_classical_level_fetch).
+//
+// Every kernel gives one lane a whole row and walks it in stored order, so each sum is the reference's sequence of
+// additions and the compaction (count, exclusive scan, fill) keeps the reference's entry order.  Nothing is contracted
+// (-ffp-contract=off), nothing is guarded: infinities and NaNs are stored as they come.  Offsets are widened to 64 bits
+// inside the kernels; every count fits an int because nnz < 2^31 is checked before the first launch.
+namespace {
+
+enum { KIND_PMIS = 0, KIND_CLJP = 1 };
+
+// std::max(m, |a|) from numeric_limits<double>::min() over a row, the entries of column `skip` left out: a NaN never
+// replaces the maximum (m < NaN is false)
+__device__ __forceinline__ double row_maximum(const int *Aj, const double *Ax, long lo, long hi, int skip)
+{
+    double m = DBL_MIN;
+    for (long jj = lo; jj < hi; ++jj) {
+        if (Aj[jj] == skip) continue;
+        const double a = fabs(Ax[jj]);
+        if (m < a) m = a;
+    }
+    return m;
+}
+
+// Strength, count pass: threshold[i] = theta * max and the number of entries row i keeps (every stored diagonal entry,
+// and the off-diagonals with |a| >= threshold).  Lane n writes the scan's last addend.
+__global__ __launch_bounds__(TB) void strength_count_kernel(int n, double theta, const int *Ap, const int *Aj, const double *Ax,
+                                                            double *threshold, int *count)
+{
+    const int i = blockIdx.x * TB + threadIdx.x;
+    if (i > n) return;
+    if (i == n) { count[n] = 0; return; }
+    const long lo = Ap[i], hi = Ap[i + 1];
+    const double t = theta * row_maximum(Aj, Ax, lo, hi, i);
+    int kept = 0;
+    for (long jj = lo; jj < hi; ++jj)
+        if (Aj[jj] == i || fabs(Ax[jj]) >= t) ++kept;
+    threshold[i] = t;
+    count[i] = kept;
+}
+
+// Strength, fill pass: the kept entries of row i from Sp[i] on, in stored order
+__global__ __launch_bounds__(TB) void strength_fill_kernel(int n, const int *Ap, const int *Aj, const double *Ax, const double *threshold,
+                                                           const int *Sp, int *Sj, double *Sx)
+{
+    const int i = blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    const long hi = Ap[i + 1];
+    const double t = threshold[i];
+    long at = Sp[i];
+    for (long jj = Ap[i]; jj < hi; ++jj) {
+        const int j = Aj[jj];
+        const double a = Ax[jj];
+        if (j == i || fabs(a) >= t) { Sj[at] = j; Sx[at] = a; ++at; }
+    }
+}
+
+__global__ __launch_bounds__(TB) void maximum_row_value_kernel(int n, const int *Ap, const int *Aj, const double *Ax, double *x)
+{
+    const int i = blockIdx.x * TB + threadIdx.x;
+    if (i < n) x[i] = row_maximum(Aj, Ax, Ap[i], Ap[i + 1], -1);
+}
+
+// Interpolation, pass 1: a C row holds one entry, an F row its strong C neighbours
+__global__ __launch_bounds__(TB) void interpolation_count_kernel(int n, const int *Sp, const int *Sj, const int *splitting, int *count)
+{
+    const int i = blockIdx.x * TB + threadIdx.x;
+    if (i > n) return;
+    if (i == n) { count[n] = 0; return; }
+    int kept = 1;
+    if (splitting[i] != C_NODE) {
+        kept = 0;
+        const long hi = Sp[i + 1];
+        for (long jj = Sp[i]; jj < hi; ++jj) {
+            const int j = Sj[jj];
+            if (splitting[j] == C_NODE && j != i) ++kept;
+        }
+    }
+    count[i] = kept;
+}
+
+// Interpolation, pass 2 (:533-595).  coarse[j]: the exclusive scan of splitting, the coarse number of C point j.
+// step: +1 walks row i of S as stored, -1 from its last entry to its first (the S the caller would have handed in with
+// every row reversed); A's rows are always walked as stored.
+__global__ __launch_bounds__(TB) void interpolation_fill_kernel(int n, const int *Ap, const int *Aj, const double *Ax, const int *Sp,
+                                                                const int *Sj, const double *Sx, const int *splitting, const int *coarse,
+                                                                const int *Bp, int *Bj, double *Bx, int step)
+{
+    const int i = blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    long at = Bp[i];
+    if (splitting[i] == C_NODE) {
+        Bj[at] = coarse[i];
+        Bx[at] = 1.0;
+        return;
+    }
+    const long s_len = (long)Sp[i + 1] - Sp[i], s_first = step > 0 ? Sp[i] : (long)Sp[i + 1] - 1, a_hi = Ap[i + 1];
+    double sum_strong_pos = 0.0, sum_strong_neg = 0.0;
+    for (long k = 0, jj = s_first; k < s_len; ++k, jj += step) {
+        const int j = Sj[jj];
+        if (splitting[j] == C_NODE && j != i) {
+            const double s = Sx[jj];
+            if (s < 0) sum_strong_neg += s; else sum_strong_pos += s;
+        }
+    }
+    double sum_all_pos = 0.0, sum_all_neg = 0.0, diag = 0.0;
+    for (long jj = Ap[i]; jj < a_hi; ++jj) {
+        const double a = Ax[jj];
+        if (Aj[jj] == i) diag += a;
+        else if (a < 0) sum_all_neg += a;
+        else sum_all_pos += a;
+    }
+    const double alpha = sum_all_neg / sum_strong_neg;
+    double beta = sum_all_pos / sum_strong_pos;
+    if (sum_strong_pos == 0) { diag += sum_all_pos; beta = 0.0; }
+    const double neg_coeff = -alpha / diag, pos_coeff = -beta / diag;
+    for (long k = 0, jj = s_first; k < s_len; ++k, jj += step) {
+        const int j = Sj[jj];
+        if (splitting[j] == C_NODE && j != i) {
+            const double s = Sx[jj];
+            Bj[at] = coarse[j];
+            Bx[at] = s < 0 ? neg_coeff * s : pos_coeff * s;
+            ++at;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ the chained level
+// The strength graph without its diagonal, counted: entries per row of G, and per column the rows that depend on it
+__global__ __launch_bounds__(TB) void graph_count_kernel(int n, const int *Sp, const int *Sj, int *count, int *indegree)
+{
+    const int i = blockIdx.x * TB + threadIdx.x;
+    if (i > n) return;
+    if (i == n) { count[n] = 0; return; }
+    const long hi = Sp[i + 1];
+    int kept = 0;
+    for (long jj = Sp[i]; jj < hi; ++jj) {
+        const int j = Sj[jj];
+        if (j != i) { ++kept; atomicAdd(&indegree[j], 1); }
+    }
+    count[i] = kept;
+}
+
+// G's rows in S's order; T's rows in the order the atomics hand out their slots (cursor starts at 0)
+__global__ __launch_bounds__(TB) void graph_fill_kernel(int n, const int *Sp, const int *Sj, const int *Gp, int *Gj, const int *Tp,
+                                                        int *cursor, int *Tj)
+{
+    const int i = blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    const long hi = Sp[i + 1];
+    long at = Gp[i];
+    for (long jj = Sp[i]; jj < hi; ++jj) {
+        const int j = Sj[jj];
+        if (j == i) continue;
+        Gj[at++] = j;
+        Tj[(long)Tp[j] + atomicAdd(&cursor[j], 1)] = i;
+    }
+}
+
+// PMIS: double(in-degree) + r, one addition.  CLJP: r, then + 1.0 once per dependent.
+__global__ __launch_bounds__(TB) void start_weights_kernel(int n, int kind, const int *indegree, const double *r, double *weight)
+{
+    const int i = blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    const int k = indegree[i];
+    double w;
+    if (kind == KIND_PMIS) w = (double)k + r[i];
+    else {
+        w = r[i];
+        for (int t = 0; t < k; ++t) w += 1.0;
+    }
+    weight[i] = w;
+}
+
+// The graph Luby's rounds run on: row i of G followed by row i of T (a neighbour listed twice is only looked at twice)
+__global__ __launch_bounds__(TB) void union_offsets_kernel(int n, const int *Gp, const int *Tp, int *Up)
+{
+    const int i = blockIdx.x * TB + threadIdx.x;
+    if (i <= n) Up[i] = Gp[i] + Tp[i];
+}
+
+__global__ __launch_bounds__(TB) void union_fill_kernel(int n, const int *Gp, const int *Gj, const int *Tp, const int *Tj, const int *Up,
+                                                        int *Uj)
+{
+    const int i = blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    long at = Up[i];
+    for (long jj = Gp[i], hi = Gp[i + 1]; jj < hi; ++jj) Uj[at++] = Gj[jj];
+    for (long jj = Tp[i], hi = Tp[i + 1]; jj < hi; ++jj) Uj[at++] = Tj[jj];
+}
+
+__global__ __launch_bounds__(TB) void fill_kernel(long count, int value, int *out)
+{
+    const long e = (long)blockIdx.x * TB + threadIdx.x;
+    if (e < count) out[e] = value;
+}
+
+// |S| with every row divided by its largest entry (a row whose largest entry is 0 is divided by 1), in place
+__global__ __launch_bounds__(TB) void scale_rows_kernel(int n, const int *Sp, double *Sx)
+{
+    const int i = blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    const long lo = Sp[i], hi = Sp[i + 1];
+    double m = 0.0;
+    for (long jj = lo; jj < hi; ++jj) {
+        const double a = fabs(Sx[jj]);
+        if (m < a) m = a;
+    }
+    if (m == 0.0) m = 1.0;
+    for (long jj = lo; jj < hi; ++jj) Sx[jj] = fabs(Sx[jj]) / m;
+}
+
+// out[k] = in[0] + ... + in[k - 1] for k < count
+int exclusive_scan(const int *in, int *out, size_t count)
+{
+    size_t bytes = 0;
+    AMG_HIP(rocprim::exclusive_scan(nullptr, bytes, in, out, 0, count, rocprim::plus<int>(), nullptr));
+    DBuf tmp;
+    CHK(tmp.alloc(bytes));
+    AMG_HIP(rocprim::exclusive_scan(tmp.p, bytes, in, out, 0, count, rocprim::plus<int>(), nullptr));
+    return 0;
+}
+
+int last_offset(const int *offsets, int n, long *out)
+{
+    int v = 0;
+    AMG_HIP(hipMemcpy(&v, offsets + n, sizeof(int), hipMemcpyDeviceToHost));
+    *out = v;
+    return 0;
+}
+
+int bad(const char *who, const char *what)
+{
+    set_error(std::string(who) + ": " + what);
+    return AMG_EINVAL;
+}
+
+// n + 1 offsets from 0 up that never decrease, every column in [0, n_col), arrays as long as the offsets say.  The last
+// offset is an int, so nnz < 2^31.
+int check_csr_arrays(const char *who, int n, int n_col, const int *p, int p_size, const int *j, int j_size, const void *x, int x_size)
+{
+    if (n < 0) return bad(who, "negative size");
+    if (!p || p_size < n + 1) return bad(who, "offsets shorter than n + 1");
+    if (p[0] != 0) return bad(who, "offsets do not start at 0");
+    for (int i = 0; i < n; ++i)
+        if (p[i + 1] < p[i]) return bad(who, "offsets decrease");
+    const int nnz = p[n];
+    if (nnz > j_size || (x_size >= 0 && nnz > x_size)) return bad(who, "arrays shorter than the last offset");
+    if (nnz > 0 && (!j || (x_size >= 0 && !x))) return bad(who, "null array");
+    for (int e = 0; e < nnz; ++e)
+        if (j[e] < 0 || j[e] >= n_col) return bad(who, "column index outside the matrix");
+    return 0;
+}
+
+int check_splitting(const char *who, int n, const int *splitting, int size)
+{
+    if (size < n || (n > 0 && !splitting)) return bad(who, "splitting shorter than n");
+    for (int i = 0; i < n; ++i)
+        if (splitting[i] != 0 && splitting[i] != 1) return bad(who, "splitting holds a value other than 0 and 1");
+    return 0;
+}
+
+// A on the device
+struct HbmCsr {
+    DBuf p, j, x;
+    int upload(int n, const int *Ap, const int *Aj, const double *Ax)
+    {
+        const size_t nnz = (size_t)Ap[n];
+        CHK(p.from_host(Ap, sizeof(int) * ((size_t)n + 1)));
+        CHK(j.from_host(Aj, sizeof(int) * nnz));
+        if (Ax) CHK(x.from_host(Ax, sizeof(double) * nnz));
+        return 0;
+    }
+};
+
+// strength of A (device) into Sp (n + 1 offsets) and freshly allocated Sj, Sx; *nnz: entries kept
+int strength_device(int n, double theta, const HbmCsr &A, long a_nnz, DBuf &Sp, DBuf &Sj, DBuf &Sx, long *nnz)
+{
+    DBuf threshold, count;
+    CHK(threshold.alloc(sizeof(double) * (size_t)n));
+    CHK(count.alloc(sizeof(int) * ((size_t)n + 1)));
+    CHK(Sp.alloc(sizeof(int) * ((size_t)n + 1)));
+    hipLaunchKernelGGL(strength_count_kernel, grid_for((long)n + 1), dim3(TB), 0, nullptr, n, theta, (const int *)A.p.i(), (const int *)A.j.i(),
+                       (const double *)A.x.d(), threshold.d(), count.i());
+    LAUNCH_CHECK("classical strength: count launch");
+    CHK(exclusive_scan(count.i(), Sp.i(), (size_t)n + 1));
+    CHK(last_offset(Sp.i(), n, nnz));
+    if (*nnz < 0 || *nnz > a_nnz) { set_error("classical strength: the scan left the matrix"); return AMG_ESTATE; }
+    CHK(Sj.alloc(sizeof(int) * (size_t)*nnz));
+    CHK(Sx.alloc(sizeof(double) * (size_t)*nnz));
+    hipLaunchKernelGGL(strength_fill_kernel, grid_for(n), dim3(TB), 0, nullptr, n, (const int *)A.p.i(), (const int *)A.j.i(),
+                       (const double *)A.x.d(), (const double *)threshold.d(), (const int *)Sp.i(), Sj.i(), Sx.d());
+    LAUNCH_CHECK("classical strength: fill launch");
+    AMG_HIP(hipDeviceSynchronize());
+    return 0;
+}
+
+// pass 1 and its scan: Bp (n + 1 offsets, allocated here); *nnz: entries of the prolongator
+int interpolation_offsets_device(int n, const int *Sp, const int *Sj, const int *splitting, DBuf &Bp, long *nnz)
+{
+    DBuf count;
+    CHK(count.alloc(sizeof(int) * ((size_t)n + 1)));
+    CHK(Bp.alloc(sizeof(int) * ((size_t)n + 1)));
+    hipLaunchKernelGGL(interpolation_count_kernel, grid_for((long)n + 1), dim3(TB), 0, nullptr, n, Sp, Sj, splitting, count.i());
+    LAUNCH_CHECK("direct interpolation: count launch");
+    CHK(exclusive_scan(count.i(), Bp.i(), (size_t)n + 1));
+    return last_offset(Bp.i(), n, nnz);
+}
+
+// the scan of splitting and pass 2 into Bj, Bx (device, Bp[n] entries each)
+int interpolation_fill_device(int n, const HbmCsr &A, const int *Sp, const int *Sj, const double *Sx, const int *splitting, const int *Bp,
+                              int *Bj, double *Bx, int step)
+{
+    DBuf coarse;
+    CHK(coarse.alloc(sizeof(int) * (size_t)n));
+    if (n > 0) CHK(exclusive_scan(splitting, coarse.i(), (size_t)n));
+    hipLaunchKernelGGL(interpolation_fill_kernel, grid_for(n), dim3(TB), 0, nullptr, n, (const int *)A.p.i(), (const int *)A.j.i(),
+                       (const double *)A.x.d(), Sp, Sj, Sx, splitting, (const int *)coarse.i(), Bp, Bj, Bx, step);
+    LAUNCH_CHECK("direct interpolation: fill launch");
+    AMG_HIP(hipDeviceSynchronize());
+    return 0;
+}
+
+}   // namespace
+
+// the result of one chained level, held for amg_classical_level_fetch
+struct amg_classical {
+    int n = 0;
+    long s_nnz = 0, p_nnz = 0;
+    DBuf Sp, Sj, Sx, splitting, Pp, Pj, Px;
+    double times_ms[5] = {0, 0, 0, 0, 0};
+};
+
+extern "C" {
+
+int amgcore_classical_strength_of_connection_f64(int n_row, double theta, const int Ap[], int Ap_size, const int Aj[], int Aj_size,
+                                                 const double Ax[], int Ax_size, int Sp[], int Sp_size, int Sj[], int Sj_size, double Sx[],
+                                                 int Sx_size)
+{
+    const char *who = "classical_strength_of_connection";
+    CHK(check_csr_arrays(who, n_row, n_row, Ap, Ap_size, Aj, Aj_size, Ax, Ax_size));
+    if (!Sp || Sp_size < n_row + 1) return bad(who, "Sp shorter than n_row + 1");
+    if (n_row == 0) { Sp[0] = 0; return 0; }
+    CHK(require_device());
+    HbmCsr A;
+    CHK(A.upload(n_row, Ap, Aj, Ax));
+    DBuf dSp, dSj, dSx;
+    long nnz = 0;
+    CHK(strength_device(n_row, theta, A, Ap[n_row], dSp, dSj, dSx, &nnz));
+    if (nnz > Sj_size || nnz > Sx_size || (nnz > 0 && (!Sj || !Sx))) return bad(who, "Sj / Sx shorter than the entries kept");
+    CHK(dSp.to_host(Sp, sizeof(int) * ((size_t)n_row + 1)));
+    CHK(dSj.to_host(Sj, sizeof(int) * (size_t)nnz));
+    return dSx.to_host(Sx, sizeof(double) * (size_t)nnz);
+}
+
+int amgcore_maximum_row_value_f64(int n_row, double x[], int x_size, const int Ap[], int Ap_size, const int Aj[], int Aj_size,
+                                  const double Ax[], int Ax_size)
+{
+    const char *who = "maximum_row_value";
+    if (n_row < 0) return bad(who, "negative size");
+    // the reference never reads Aj here: its columns only have to be there
+    CHK(check_csr_arrays(who, n_row, 0x7fffffff, Ap, Ap_size, Aj, Aj_size, Ax, Ax_size));
+    if (x_size < n_row || (n_row > 0 && !x)) return bad(who, "x shorter than n_row");
+    if (n_row == 0) return 0;
+    CHK(require_device());
+    HbmCsr A;
+    CHK(A.upload(n_row, Ap, Aj, Ax));
+    DBuf dx;
+    CHK(dx.alloc(sizeof(double) * (size_t)n_row));
+    hipLaunchKernelGGL(maximum_row_value_kernel, grid_for(n_row), dim3(TB), 0, nullptr, n_row, (const int *)A.p.i(), (const int *)A.j.i(),
+                       (const double *)A.x.d(), dx.d());
+    LAUNCH_CHECK("maximum_row_value launch");
+    AMG_HIP(hipDeviceSynchronize());
+    return dx.to_host(x, sizeof(double) * (size_t)n_row);
+}
+
+int amgcore_rs_direct_interpolation_pass1_f64(int n_nodes, const int Sp[], int Sp_size, const int Sj[], int Sj_size, const int splitting[],
+                                              int splitting_size, int Bp[], int Bp_size)
+{
+    const char *who = "rs_direct_interpolation_pass1";
+    CHK(check_csr_arrays(who, n_nodes, n_nodes, Sp, Sp_size, Sj, Sj_size, nullptr, -1));
+    CHK(check_splitting(who, n_nodes, splitting, splitting_size));
+    if (!Bp || Bp_size < n_nodes + 1) return bad(who, "Bp shorter than n_nodes + 1");
+    if (n_nodes == 0) { Bp[0] = 0; return 0; }
+    CHK(require_device());
+    HbmCsr S;
+    CHK(S.upload(n_nodes, Sp, Sj, nullptr));
+    DBuf dsplit, dBp;
+    CHK(dsplit.from_host(splitting, sizeof(int) * (size_t)n_nodes));
+    long nnz = 0;
+    CHK(interpolation_offsets_device(n_nodes, S.p.i(), S.j.i(), dsplit.i(), dBp, &nnz));
+    return dBp.to_host(Bp, sizeof(int) * ((size_t)n_nodes + 1));
+}
+
+int amgcore_rs_direct_interpolation_pass2_f64(int n_nodes, const int Ap[], int Ap_size, const int Aj[], int Aj_size, const double Ax[],
+                                              int Ax_size, const int Sp[], int Sp_size, const int Sj[], int Sj_size, const double Sx[],
+                                              int Sx_size, const int splitting[], int splitting_size, const int Bp[], int Bp_size, int Bj[],
+                                              int Bj_size, double Bx[], int Bx_size)
+{
+    const char *who = "rs_direct_interpolation_pass2";
+    CHK(check_csr_arrays(who, n_nodes, n_nodes, Ap, Ap_size, Aj, Aj_size, Ax, Ax_size));
+    CHK(check_csr_arrays(who, n_nodes, n_nodes, Sp, Sp_size, Sj, Sj_size, Sx, Sx_size));
+    CHK(check_splitting(who, n_nodes, splitting, splitting_size));
+    if (!Bp || Bp_size < n_nodes + 1) return bad(who, "Bp shorter than n_nodes + 1");
+    if (Bp[0] != 0) return bad(who, "Bp does not start at 0");
+    // every row writes exactly what pass 1 counted for it: Bp has to be pass 1's answer
+    for (int i = 0; i < n_nodes; ++i) {
+        int kept = 1;
+        if (splitting[i] != C_NODE) {
+            kept = 0;
+            for (int jj = Sp[i]; jj < Sp[i + 1]; ++jj)
+                if (splitting[Sj[jj]] == C_NODE && Sj[jj] != i) ++kept;
+        }
+        if (Bp[i + 1] - Bp[i] != kept) return bad(who, "Bp is not the result of pass 1");
+    }
+    if (n_nodes == 0) return 0;
+    const long nnz = Bp[n_nodes];
+    if (nnz > Bj_size || nnz > Bx_size || (nnz > 0 && (!Bj || !Bx))) return bad(who, "Bj / Bx shorter than Bp[n_nodes]");
+    CHK(require_device());
+    HbmCsr A, S;
+    CHK(A.upload(n_nodes, Ap, Aj, Ax));
+    CHK(S.upload(n_nodes, Sp, Sj, Sx));
+    DBuf dsplit, dBp, dBj, dBx;
+    CHK(dsplit.from_host(splitting, sizeof(int) * (size_t)n_nodes));
+    CHK(dBp.from_host(Bp, sizeof(int) * ((size_t)n_nodes + 1)));
+    CHK(dBj.alloc(sizeof(int) * (size_t)nnz));
+    CHK(dBx.alloc(sizeof(double) * (size_t)nnz));
+    CHK(interpolation_fill_device(n_nodes, A, S.p.i(), S.j.i(), S.x.d(), dsplit.i(), dBp.i(), dBj.i(), dBx.d(), 1));
+    CHK(dBj.to_host(Bj, sizeof(int) * (size_t)nnz));
+    return dBx.to_host(Bx, sizeof(double) * (size_t)nnz);
+}
+
+int amg_classical_level_device(int n, const int *Ap, const int *Aj, const double *Ax, double theta, int kind, int reversed,
+                               const double *r, amg_classical **out, long *sizes, int *rounds, double *times_ms)
+{
+    const char *who = "classical level";
+    if (!out || !sizes) return bad(who, "bad arguments");
+    *out = nullptr;
+    if (kind != KIND_PMIS && kind != KIND_CLJP) return bad(who, "the splitting is 0 (PMIS) or 1 (CLJP)");
+    if (n <= 0 || !r) return bad(who, "an empty operator or no start values");
+    if (!(theta >= 0.0 && theta <= 1.0)) return bad(who, "expected theta in [0, 1]");
+    CHK(check_csr_arrays(who, n, n, Ap, n + 1, Aj, 0x7fffffff, Ax, 0x7fffffff));
+    CHK(require_device());
+    LapClock timer;
+    const size_t vbytes = sizeof(int) * (size_t)n, pbytes = sizeof(int) * ((size_t)n + 1);
+    HbmCsr A;
+    CHK(A.upload(n, Ap, Aj, Ax));
+    DBuf dr;
+    CHK(dr.from_host(r, sizeof(double) * (size_t)n));
+    AMG_HIP(hipDeviceSynchronize());
+    // the handle owns what outlives this call; an early return frees it with everything it holds by then
+    struct Guard {
+        amg_classical *h;
+        ~Guard() { delete h; }
+    } guard{new amg_classical};
+    amg_classical &h = *guard.h;
+    h.n = n;
+    h.times_ms[0] = timer.lap();
+
+    // 1. strength
+    CHK(strength_device(n, theta, A, Ap[n], h.Sp, h.Sj, h.Sx, &h.s_nnz));
+    h.times_ms[1] = timer.lap();
+
+    // 2. G = S without its diagonal, the pattern of T = G^T and the in-degrees
+    DBuf count, indegree, cursor, Gp, Gj, Tp, Tj;
+    CHK(count.alloc(pbytes)); CHK(indegree.zero(pbytes)); CHK(cursor.zero(vbytes));
+    CHK(Gp.alloc(pbytes)); CHK(Tp.alloc(pbytes));
+    hipLaunchKernelGGL(graph_count_kernel, grid_for((long)n + 1), dim3(TB), 0, nullptr, n, (const int *)h.Sp.i(), (const int *)h.Sj.i(),
+                       count.i(), indegree.i());
+    LAUNCH_CHECK("classical level: graph count launch");
+    CHK(exclusive_scan(count.i(), Gp.i(), (size_t)n + 1));
+    CHK(exclusive_scan(indegree.i(), Tp.i(), (size_t)n + 1));
+    long g_nnz = 0, t_nnz = 0;
+    CHK(last_offset(Gp.i(), n, &g_nnz));
+    CHK(last_offset(Tp.i(), n, &t_nnz));
+    if (g_nnz < 0 || g_nnz > h.s_nnz || t_nnz != g_nnz) { set_error("classical level: the graph scans disagree"); return AMG_ESTATE; }
+    CHK(Gj.alloc(sizeof(int) * (size_t)g_nnz)); CHK(Tj.alloc(sizeof(int) * (size_t)g_nnz));
+    hipLaunchKernelGGL(graph_fill_kernel, grid_for(n), dim3(TB), 0, nullptr, n, (const int *)h.Sp.i(), (const int *)h.Sj.i(),
+                       (const int *)Gp.i(), Gj.i(), (const int *)Tp.i(), cursor.i(), Tj.i());
+    LAUNCH_CHECK("classical level: graph fill launch");
+
+    // 3. the start weights
+    DBuf weight;
+    CHK(weight.alloc(sizeof(double) * (size_t)n));
+    hipLaunchKernelGGL(start_weights_kernel, grid_for(n), dim3(TB), 0, nullptr, n, kind, (const int *)indegree.i(), (const double *)dr.d(),
+                       weight.d());
+    LAUNCH_CHECK("classical level: weight launch");
+    AMG_HIP(hipDeviceSynchronize());
+    h.times_ms[2] = timer.lap();
+
+    // 4. the splitting
+    CHK(h.splitting.alloc(vbytes));
+    int done = 0;
+    if (kind == KIND_PMIS) {
+        DBuf Up, Uj, flag;
+        CHK(Up.alloc(pbytes)); CHK(Uj.alloc(sizeof(int) * 2 * (size_t)g_nnz)); CHK(flag.alloc(sizeof(int)));
+        hipLaunchKernelGGL(union_offsets_kernel, grid_for((long)n + 1), dim3(TB), 0, nullptr, n, (const int *)Gp.i(), (const int *)Tp.i(),
+                           Up.i());
+        LAUNCH_CHECK("classical level: union offsets launch");
+        hipLaunchKernelGGL(union_fill_kernel, grid_for(n), dim3(TB), 0, nullptr, n, (const int *)Gp.i(), (const int *)Gj.i(),
+                           (const int *)Tp.i(), (const int *)Tj.i(), (const int *)Up.i(), Uj.i());
+        LAUNCH_CHECK("classical level: union fill launch");
+        hipLaunchKernelGGL(fill_kernel, grid_for(n), dim3(TB), 0, nullptr, (long)n, -1, h.splitting.i());
+        LAUNCH_CHECK("classical level: state launch");
+        CHK(mis_rounds_device(n, Up.i(), Uj.i(), weight.d(), -1, 1, 0, h.splitting.i(), flag.i(), &done));
+    } else {
+        CHK(cljp_passes_device(n, g_nnz, Gp.i(), Gj.i(), Tp.i(), Tj.i(), weight.d(), h.splitting.i(), &done));
+    }
+    AMG_HIP(hipDeviceSynchronize());
+    h.times_ms[3] = timer.lap();
+
+    // 5. direct interpolation on S's pattern with the values the strength kernel wrote
+    CHK(interpolation_offsets_device(n, h.Sp.i(), h.Sj.i(), h.splitting.i(), h.Pp, &h.p_nnz));
+    if (h.p_nnz < 0 || h.p_nnz > h.s_nnz + n) { set_error("classical level: the interpolation scan left the matrix"); return AMG_ESTATE; }
+    CHK(h.Pj.alloc(sizeof(int) * (size_t)h.p_nnz));
+    CHK(h.Px.alloc(sizeof(double) * (size_t)h.p_nnz));
+    CHK(interpolation_fill_device(n, A, h.Sp.i(), h.Sj.i(), h.Sx.d(), h.splitting.i(), h.Pp.i(), h.Pj.i(), h.Px.d(), reversed ? -1 : 1));
+    h.times_ms[4] = timer.lap();
+
+    sizes[0] = h.s_nnz;
+    sizes[1] = h.p_nnz;
+    if (rounds) *rounds = done;
+    if (times_ms) std::copy(h.times_ms, h.times_ms + 5, times_ms);
+    *out = guard.h;
+    guard.h = nullptr;
+    return 0;
+}
+
+int amg_classical_level_fetch(amg_classical *h, int *splitting, int *Pp, int *Pj, double *Px, int *Sp, int *Sj, double *Sx,
+                              double *times_ms)
+{
+    if (!h) return AMG_EINVAL;
+    struct Guard {
+        amg_classical *h;
+        ~Guard() { delete h; }
+    } guard{h};
+    if (!splitting || !Pp || (h->p_nnz > 0 && (!Pj || !Px))) return bad("classical level fetch", "null array");
+    LapClock timer;
+    const size_t pbytes = sizeof(int) * ((size_t)h->n + 1);
+    CHK(h->splitting.to_host(splitting, sizeof(int) * (size_t)h->n));
+    CHK(h->Pp.to_host(Pp, pbytes));
+    CHK(h->Pj.to_host(Pj, sizeof(int) * (size_t)h->p_nnz));
+    CHK(h->Px.to_host(Px, sizeof(double) * (size_t)h->p_nnz));
+    if (Sp) {
+        if (h->s_nnz > 0 && (!Sj || !Sx)) return bad("classical level fetch", "null array");
+        hipLaunchKernelGGL(scale_rows_kernel, grid_for(h->n), dim3(TB), 0, nullptr, h->n, (const int *)h->Sp.i(), h->Sx.d());
+        LAUNCH_CHECK("classical level: scaling launch");
+        CHK(h->Sp.to_host(Sp, pbytes));
+        CHK(h->Sj.to_host(Sj, sizeof(int) * (size_t)h->s_nnz));
+        CHK(h->Sx.to_host(Sx, sizeof(double) * (size_t)h->s_nnz));
+    }
+    if (times_ms) {
+        std::copy(h->times_ms, h->times_ms + 5, times_ms);
+        times_ms[5] = timer.lap();
+    }
     return 0;
 }
 
