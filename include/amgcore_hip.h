@@ -478,6 +478,14 @@ int amg_mat_apply_rows(amg_mat *m, int mode, int row_lo, int row_hi, const doubl
  * gauss_seidel_indexed); columns >= nrows (halo) stay frozen: GS inside a rank, Jacobi across */
 int amg_mat_build_gs(amg_mat *m, const int *order, int norder);
 int amg_mat_gs_levels(amg_mat *m);
+/* read-only view of the schedule amg_mat_build_gs made (the counterpart of amg_mat_form): fills out[0 .. min(nout, 12))
+ * and returns the number written, AMG_ESTATE without a schedule.  Fields: 0 dependency levels, 1 chained launches,
+ * 2 levels inside chains, 3 long-row chains (gs_chainl*), 4 LDS hand-off copy of the short-row chains (gs_chain2),
+ * 5 its slots per row (4 / 8 / 12; 0 when it was not attempted), 6 ring codes of the long-row chains (gs_chainl2),
+ * 7 dataflow form built, 8 its lanes per row, 9 its chunks, 10 the default (amg_set_gs_flow(1)) sweeps it,
+ * 11 the level-ordered copy of the other paths is still held */
+#define AMG_GS_INFO_FIELDS 12
+int amg_mat_gs_info(amg_mat *m, int *out, int nout);
 int amg_mat_gs_sweep(amg_mat *m, double *x, const double *b, int reverse, int bsr1, void *stream);
 /* a whole sequence of directional sweeps (seq[k] != 0: backward) as the in-cycle smoothers issue them: the
  * dataflow form runs up to four of them per launch */

@@ -329,6 +329,8 @@ def lib():
     L.amg_mat_destroy.restype = None
     L.amg_mat_gs_levels.argtypes = [V]
     L.amg_mat_gs_levels.restype = I
+    L.amg_mat_gs_info.argtypes = [V, V, I]
+    L.amg_mat_gs_info.restype = I
     L.amg_mat_form.argtypes = [V]
     L.amg_mat_form.restype = I
     L.amg_mat_nnz.argtypes = [V]

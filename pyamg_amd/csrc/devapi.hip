@@ -93,6 +93,22 @@ int amg_mat_build_gs(amg_mat *m, const int *order, int norder)
 
 int amg_mat_gs_levels(amg_mat *m) { return (m && m->sched) ? m->sched->nlevels() : 0; }
 
+// what the schedule holds and which kernels its sweeps will take (include/amgcore_hip.h lists the fields); reads only
+int amg_mat_gs_info(amg_mat *m, int *out, int nout)
+{
+    if (!m || !m->sched) { set_error("amg_mat_build_gs was not called"); return AMG_ESTATE; }
+    if (!out || nout < 0) { set_error("bad output array"); return AMG_EINVAL; }
+    const Schedule &S = *m->sched;
+    int chained = 0;
+    for (const auto &c : S.chains) chained += c.second - c.first;
+    const int f[AMG_GS_INFO_FIELDS] = {S.nlevels(), (int)S.chains.size(), chained, S.chain_long ? 1 : 0, (S.perm && S.chain2) ? 1 : 0,
+                                       S.c2_pf, S.cl_code_f ? 1 : 0, S.flow.ready ? 1 : 0, S.flow.lpr, S.flow.nchunks,
+                                       S.flow_auto ? 1 : 0, S.G.Ap ? 1 : 0};
+    const int k = std::min(nout, (int)AMG_GS_INFO_FIELDS);
+    for (int q = 0; q < k; ++q) out[q] = f[q];
+    return k;
+}
+
 // one directional sweep (reverse != 0: the reversed order); bsr1 selects bsr_gauss_seidel's rounding
 int amg_mat_gs_sweep(amg_mat *m, double *x, const double *b, int reverse, int bsr1, void *stream)
 {

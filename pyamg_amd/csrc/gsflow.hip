@@ -876,9 +876,13 @@ int build_block_flow_form(BlockFlowForm &F, int nb, int bs, int ntasks, const st
         }
     }
     // (every slot is written exactly once, padding included, by the thread that owns the chunk: no zero-fill pass)
-    const size_t ncol = (size_t)std::max(slot_rows, 1L) * NG, nval = (size_t)std::max(slot_rows, 1L) * bs * 64;
+    // One padding slot row behind the last chunk: a chunk without slots (block rows that hold their diagonal block only)
+    // still issues its loads at its `off`, which for the form's last chunk is slot_rows.
+    const size_t ncol = ((size_t)slot_rows + 1) * NG, nval = ((size_t)slot_rows + 1) * bs * 64;
     std::unique_ptr<int[]> col(new int[ncol]);
     std::unique_ptr<double[]> val(new double[nval]);
+    for (size_t w = (size_t)slot_rows * NG; w < ncol; ++w) col[w] = nb;
+    for (size_t w = (size_t)slot_rows * bs * 64; w < nval; ++w) val[w] = 0.0;
     std::vector<int> rmap((size_t)nb), lev((size_t)nb), gf((size_t)nb, nb), gb((size_t)nb, nb);
     flow_parallel(nl, 64, [&](long llo, long lhi) {
         for (long l = llo; l < lhi; ++l)
@@ -1098,9 +1102,12 @@ int build_flow_form(FlowForm &F, int n, int ntasks, const std::vector<int> &leve
         }
     }
     // (the 12 B per slot are written exactly once, padding included, by the thread that owns the chunk: no zero-fill pass)
-    const size_t nslot = (size_t)std::max(slot_rows, 1L) * 64;
+    // One padding slot row behind the last chunk: a chunk without slots (diagonal-only rows) still issues its loads at its
+    // `off`, which for the form's last chunk is slot_rows; what it reads there is the padding pair and is discarded.
+    const size_t nslot = ((size_t)slot_rows + 1) * 64;
     std::unique_ptr<int[]> col(new int[nslot]);
     std::unique_ptr<double[]> val(new double[nslot]);
+    for (size_t w = (size_t)slot_rows * 64; w < nslot; ++w) { col[w] = ncols; val[w] = 0.0; }
     std::vector<int> rmap((size_t)n), lev((size_t)n), gf((size_t)n, ncols), gb((size_t)n, ncols);
     std::vector<double> dgs((size_t)n);
     flow_parallel(nl, 64, [&](long llo, long lhi) {
@@ -1144,8 +1151,8 @@ int build_flow_form(FlowForm &F, int n, int ntasks, const std::vector<int> &leve
     long acct = 0;
     FCHK(falloc(F.rowmap, n, &acct));
     FCHK(falloc(F.meta, (long)meta.size(), &acct));
-    FCHK(falloc(F.col, slot_rows * 64, &acct));
-    FCHK(falloc(F.val, slot_rows * 64, &acct));
+    FCHK(falloc(F.col, (long)nslot, &acct));
+    FCHK(falloc(F.val, (long)nslot, &acct));
     FCHK(falloc(F.diag, n, &acct));
     FCHK(falloc(F.bp, n, &acct));
     FCHK(falloc(F.gate_f, n, &acct));
@@ -1153,10 +1160,8 @@ int build_flow_form(FlowForm &F, int n, int ntasks, const std::vector<int> &leve
     FCHK(falloc(F.X, (FLOW_MAXSEQ + 1) * F.xstride, &acct));
     AMG_HIP(hipMemcpy(F.rowmap, rmap.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
     AMG_HIP(hipMemcpy(F.meta, meta.data(), sizeof(FlowChunk) * meta.size(), hipMemcpyHostToDevice));
-    if (slot_rows > 0) {
-        AMG_HIP(hipMemcpy(F.col, col.get(), sizeof(int) * (size_t)slot_rows * 64, hipMemcpyHostToDevice));
-        AMG_HIP(hipMemcpy(F.val, val.get(), sizeof(double) * (size_t)slot_rows * 64, hipMemcpyHostToDevice));
-    }
+    AMG_HIP(hipMemcpy(F.col, col.get(), sizeof(int) * nslot, hipMemcpyHostToDevice));
+    AMG_HIP(hipMemcpy(F.val, val.get(), sizeof(double) * nslot, hipMemcpyHostToDevice));
     AMG_HIP(hipMemcpy(F.diag, dgs.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
     AMG_HIP(hipMemcpy(F.gate_f, gf.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
     AMG_HIP(hipMemcpy(F.gate_b, gb.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice));

@@ -436,13 +436,25 @@ int build_csr_schedule(const int *Ap, const int *Aj, const double *Ax, int n, co
     CHK(build_levels(n, Ap, Aj, tasks, ntasks, S.level_ptr, order));
     S.ntasks = ntasks;
     std::vector<int> gp((size_t)ntasks + 1), rowmap((size_t)ntasks), dpos((size_t)ntasks);
+    // The reference leaves EVERY stored a_ii out of the row sum and divides by the last one (relaxation.h:51-52).  The
+    // kernels that sweep the level-ordered copy skip one position per row (dpos), so a row that stores its diagonal more
+    // than once is copied without the overridden ones: dup[k] of them.
+    std::vector<int> dup((size_t)ntasks, 0);
+    host_parallel(ntasks, 1 << 15, [&](long klo, long khi) {
+        for (long k = klo; k < khi; ++k) {
+            const int t = order[(size_t)k];
+            const int i = tasks ? tasks[t] : t;
+            rowmap[(size_t)k] = i;
+            int nd = 0;
+            for (int q = Ap[i]; q < Ap[i + 1]; ++q) nd += (Aj[q] == i) ? 1 : 0;
+            dup[(size_t)k] = nd > 1 ? nd - 1 : 0;
+        }
+    });
     long nnz = 0;
     for (int k = 0; k < ntasks; ++k) {
-        int t = order[k];
-        int i = tasks ? tasks[t] : t;
+        const int i = rowmap[(size_t)k];
         gp[k] = (int)nnz;
-        nnz += Ap[i + 1] - Ap[i];
-        rowmap[k] = i;
+        nnz += Ap[i + 1] - Ap[i] - dup[(size_t)k];
     }
     if (nnz > 2147483647L) { set_error("schedule: nnz exceeds int32"); return AMG_EINVAL; }
     gp[ntasks] = (int)nnz;
@@ -452,11 +464,22 @@ int build_csr_schedule(const int *Ap, const int *Aj, const double *Ax, int n, co
         for (long k = klo; k < khi; ++k) {
             int i = rowmap[(size_t)k];
             int len = Ap[i + 1] - Ap[i];
-            std::memcpy(gj.data() + gp[(size_t)k], Aj + Ap[i], sizeof(int) * (size_t)len);
-            std::memcpy(gx.data() + gp[(size_t)k], Ax + Ap[i], sizeof(double) * (size_t)len);
             int d = -1;
-            for (int q = 0; q < len; ++q)
-                if (Aj[Ap[i] + q] == i) d = gp[(size_t)k] + q;   // last diagonal entry wins, as relaxation.h:51-52
+            if (dup[(size_t)k] == 0) {
+                std::memcpy(gj.data() + gp[(size_t)k], Aj + Ap[i], sizeof(int) * (size_t)len);
+                std::memcpy(gx.data() + gp[(size_t)k], Ax + Ap[i], sizeof(double) * (size_t)len);
+                for (int q = 0; q < len; ++q)
+                    if (Aj[Ap[i] + q] == i) d = gp[(size_t)k] + q;
+            } else {
+                int skip = dup[(size_t)k], w = gp[(size_t)k];       // the last diagonal entry wins, the earlier ones go
+                for (int q = Ap[i]; q < Ap[i + 1]; ++q) {
+                    if (Aj[q] == i) {
+                        if (skip > 0) { --skip; continue; }
+                        d = w;
+                    }
+                    gj[(size_t)w] = Aj[q]; gx[(size_t)w] = Ax[q]; ++w;
+                }
+            }
             dpos[(size_t)k] = d;
         }
     });
