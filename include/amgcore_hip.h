@@ -420,6 +420,12 @@ int amg_hier_level0_fused(amg_hier *h);
  * amg_hier_level0_plane_reuse returns the number of flagged planes, 0 when the chains are not taken or the switch is off. */
 void amg_set_level0_plane_reuse(int on);
 int amg_hier_level0_plane_reuse(amg_hier *h);
+/* The row sums of the chains with a leading residual take a slot a row does not store (code 255) as a stored +0.0 and
+ * drop the per-slot compare and selects: the sum starts at +0.0 and is never -0.0, so adding (+0.0) * operand keeps its
+ * bits for every finite operand.  (The chain without a leading residual keeps the selects: it is not bound by them.)
+ * An Inf or NaN next to an absent slot (a diverged iterate) spreads one row further than under the selects.
+ * amg_set_level0_zero_slots(0) runs the select form (process-wide; tests and A/Bs, default 1); drops captured graphs. */
+void amg_set_level0_zero_slots(int on);
 /* Setup-side (replaces the host sweeps behind pyamg/aggregation/aggregation.py:313-320 `relaxation_as_linear_operator(
  * ('gauss_seidel', ...), A, 0) * B`, i.e. amg_core gauss_seidel of relaxation.h:34-62 on A x = 0): nsweeps Gauss-Seidel
  * sweeps over level lvl's operator in its own row order, from the CSR arrays in HBM; dirs[k] != 0 = descending rows;

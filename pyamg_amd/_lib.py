@@ -291,6 +291,8 @@ def lib():
     L.amg_set_level0_plane_reuse.restype = None
     L.amg_hier_level0_plane_reuse.argtypes = [V]
     L.amg_hier_level0_plane_reuse.restype = I
+    L.amg_set_level0_zero_slots.argtypes = [I]
+    L.amg_set_level0_zero_slots.restype = None
     L.amg_value_index_enabled.argtypes = []
     L.amg_value_index_enabled.restype = I
     L.amg_hier_gs_natural.argtypes = [V, I, V, V, V, I]

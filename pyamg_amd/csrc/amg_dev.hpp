@@ -203,6 +203,7 @@ struct Level0ChainArgs {
     double c_gs, c_last;               // polynomial coefficients 0 and 1
     int zc;                            // planes per workgroup
     const unsigned char *same;         // plane flags (DevCsr::l0_same) or null: every plane loads its code words
+    int zero_slots;                    // absent slots multiply by a stored zero (1) or are skipped by selects (0): same bits
     int tiles_x, tiles_y;              // (set by the launcher)
 };
 int launch_level0_chain(bool first_res, bool last_res, const Level0ChainArgs &a, hipStream_t st);

@@ -1290,6 +1290,7 @@ static int coarse_solve(amg_hier *h, const double *b, double *&x, double *&xalt)
 // ------------------------------------------------------------------ fused level-0 chains (launch_level0_chain)
 static int g_level0_fusion = 1;
 static int g_level0_plane_reuse = 1;
+static int g_level0_zero_slots = 1;
 #ifndef L0_ZCHUNK_PLANES                        // (A/B builds: -DL0_ZCHUNK_PLANES=32 / 64)
 #define L0_ZCHUNK_PLANES 128
 #endif
@@ -1369,6 +1370,7 @@ static int level0_chain(amg_hier *h, const Smoother &s, bool first_res, bool las
     a.c_gs = s.coef[0]; a.c_last = s.coef[1];
     a.zc = std::min(L0_ZCHUNK, M.l0_nz);
     a.same = g_level0_plane_reuse ? M.l0_same : nullptr;
+    a.zero_slots = g_level0_zero_slots;
     CHK(launch_level0_chain(first_res, last_res, a, h->stream));
     std::swap(x, xalt);
     return 0;
@@ -2954,5 +2956,6 @@ int amg_hier_level0_plane_reuse(amg_hier *h)
     if (!h || !h->finalized || !g_level0_plane_reuse || !level0_fused(h) || !h->lv[0].A.l0_same) return 0;
     return h->lv[0].A.l0_nsame;
 }
+void amg_set_level0_zero_slots(int on) { g_level0_zero_slots = on ? 1 : 0; amg::bump_config_epoch(); }
 
 }  // extern "C"

@@ -1615,14 +1615,31 @@ __device__ __forceinline__ void stencil_epilogue(const StreamArgs &a, const Sten
 // The row sum of a coded row (stencils of up to 7 offsets): slot u holds dictionary entry (cw >> 8u) & 255, code 255 = the
 // row does not store the slot (also every slot >= nu).  Terms v[u] * (gscale * xv[u]) in increasing slot order, skipped by
 // selects.  Shared by stencil_coded_kernel and the fused level-0 chains (level0_chain_kernel): the same bits in both.
-template <int MODE>
+//
+// ZERO_SLOTS (level0_chain_kernel): the caller's sdict[255] holds +0.0 and every row is covered, so an
+// absent slot is the term (+0.0) * (gscale * xv[u]) = +-0.0 for a finite operand and the loop is seven unconditional
+// multiply-adds, the same separately rounded products in the same order.  acc keeps its bits: it starts at +0.0 and a
+// round-to-nearest sum is -0.0 only when both addends are, so acc is never -0.0; acc + (+-0.0) is acc when acc != 0
+// and +0.0 when acc is +0.0.  Not for the modes that start from bval (which may be -0.0) or pick the diagonal out
+// through `on`.  A non-finite operand next to an absent slot makes the term NaN where the select form skipped it.
+template <int MODE, bool ZERO_SLOTS = false>
 __device__ __forceinline__ double coded_row_sum(unsigned long long cw, const double *sdict, const double (&xv)[7], double gscale,
                                                 bool covered, double bval, int u0, double &diag)
 {
     using MT = ModeTraits<MODE>;
+    static_assert(!ZERO_SLOTS || !(MT::sub || MT::jac), "zero slots: the sum must start at +0.0 and take every slot alike");
     double v[7];
 #pragma unroll
     for (int u = 0; u < 7; ++u) v[u] = sdict[(unsigned)(cw >> (8 * u)) & 0xFFu];
+    if (ZERO_SLOTS) {
+        double acc = 0.0;
+#pragma unroll
+        for (int u = 0; u < 7; ++u) {
+            const double pr = v[u] * (gscale * xv[u]);
+            acc = acc + pr;
+        }
+        return acc;
+    }
     double acc = MT::sub ? bval : 0.0;
 #pragma unroll
     for (int u = 0; u < 7; ++u) {
@@ -2157,6 +2174,18 @@ int launch_stencil(StreamMode mode, const StreamArgs &a, const DevCsr &M, hipStr
 // Where the operator does not change from plane k - 1 to plane k (Level0ChainArgs::same, a setup-time scan; DESIGN.md
 // §4 r12) a lane takes its column's code word from cq[0], the word it holds for plane k - 1, instead of loading it;
 // the first plane of a chunk always loads.  The flag is uniform over the workgroup and requested one iteration ahead.
+//
+// ZS (Level0ChainArgs::zero_slots, the chains with a leading residual): the row sums take absent
+// slots as a stored zero (coded_row_sum<MODE, true>): sdict[ndict .. 255] is +0.0, code 255 among them.  Same bits for
+// finite operands, and every operand a zero meets here is finite when the vectors are.  In-box lanes: an absent slot's
+// operand is a loaded value, a stage value of a lane inside the box, or -- at a box face -- of a lane outside it.
+// Lanes outside the box or ring 1 carry ~0 code words and now form 0 * operand in every slot where they skipped; their
+// operands are loaded zeros and stage values of their neighbours, so their own stage values are the epilogues of zero
+// sums (0 where b = x = 0), finite.  The only other
+// source is the LDS padding that the tile's edge lanes read: garbage there travels one lane inwards per stage, as it
+// already does through the present slots of in-box edge lanes, which keeps it inside the S-wide rim that is never
+// stored.  The padding is zeroed once per launch all the same (one store per lane), so no lane multiplies
+// uninitialised LDS.  A non-finite iterate (a diverged solve) spreads one row further than under the select form.
 // ---------------------------------------------------------------------------
 #ifndef L0C_TY                                  // (A/B builds: -DL0C_TY=24 / 32)
 #define L0C_TY 16
@@ -2165,7 +2194,7 @@ constexpr int L0C_TX = 32;                      // tile extent in lanes along x 
 constexpr int L0C_WG = L0C_TX * L0C_TY;         // ... and along y
 constexpr int L0C_PAD = L0C_TX;                 // LDS padding: lanes of the tile's edge read past the plane (results discarded)
 
-template <int FR, int LR>
+template <int FR, int LR, bool ZS>
 __global__ __launch_bounds__(L0C_WG) void level0_chain_kernel(Level0ChainArgs a)
 {
     constexpr int S = FR + 1 + LR;              // stages = halo depth in rows and planes
@@ -2185,7 +2214,12 @@ __global__ __launch_bounds__(L0C_WG) void level0_chain_kernel(Level0ChainArgs a)
     const long P = (long)a.nx * a.ny;
     const long col = inxy ? (long)gy * a.nx + gx : 0;
     const int z0 = zb * a.zc, z1 = min(z0 + a.zc, a.nz);
-    if (t < a.ndict) sdict[t] = a.dict[t];      // (read after the first barrier below)
+    if (t < 256) sdict[t] = t < a.ndict ? a.dict[t] : 0.0;   // (read after the first barrier below; 255 = absent: +0.0)
+    static_assert(L0C_WG >= 256 && 2 * S * 2 * L0C_PAD <= L0C_WG, "one lane per dictionary entry and per padding element");
+    if (t < 2 * S * 2 * L0C_PAD) {              // the padding on both sides of every plane buffer, never written again
+        const int r = t / (2 * L0C_PAD), e = t - r * (2 * L0C_PAD);
+        (&pl[0][0][0])[r * (L0C_WG + 2 * L0C_PAD) + (e < L0C_PAD ? e : L0C_WG + e)] = 0.0;
+    }
 
     double w[S + 1][3];                         // stage s: planes k-s-2, k-s-1, k-s (stage 0 = the loaded operand)
     unsigned long long cq[S];                   // codes of planes k-1 .. k-S
@@ -2236,10 +2270,10 @@ __global__ __launch_bounds__(L0C_WG) void level0_chain_kernel(Level0ChainArgs a)
             const double xv[7] = {w[s - 1][0], q[-L0C_TX], q[-1], w[s - 1][1], q[1], q[L0C_TX], w[s - 1][2]};
             double diag = 0.0, val;
             if (s == SP) {
-                const double acc = coded_row_sum<SM_POLY_LAST>(cq[s - 1], sdict, xv, a.c_gs, true, 0.0, -1, diag);
+                const double acc = coded_row_sum<SM_POLY_LAST, ZS>(cq[s - 1], sdict, xv, a.c_gs, true, 0.0, -1, diag);
                 val = poly_last_row(a.c_last, w[s - 1][1], acc, FR ? w[0][0] : xq);
             } else {
-                const double acc = coded_row_sum<SM_RESIDUAL>(cq[s - 1], sdict, xv, 1.0, true, 0.0, -1, diag);
+                const double acc = coded_row_sum<SM_RESIDUAL, ZS>(cq[s - 1], sdict, xv, 1.0, true, 0.0, -1, diag);
                 val = residual_row(bq[s - 1], acc);
             }
             w[s][0] = w[s][1]; w[s][1] = w[s][2]; w[s][2] = val;
@@ -2266,9 +2300,14 @@ int launch_level0_chain(bool first_res, bool last_res, const Level0ChainArgs &a0
     a.tiles_y = (a.ny + iny - 1) / iny;
     const long grid = (long)a.tiles_x * a.tiles_y * ((a.nz + a.zc - 1) / a.zc);
     if (grid > 2147483647L) { set_error("launch_level0_chain: grid too large"); return -1; }
-    if (first_res && last_res) hipLaunchKernelGGL((level0_chain_kernel<1, 1>), dim3(grid), dim3(L0C_WG), 0, st, a);
-    else if (first_res) hipLaunchKernelGGL((level0_chain_kernel<1, 0>), dim3(grid), dim3(L0C_WG), 0, st, a);
-    else hipLaunchKernelGGL((level0_chain_kernel<0, 1>), dim3(grid), dim3(L0C_WG), 0, st, a);
+    // Zero slots go to the chains with a leading residual (S = 3), which the slot loop's issue work bounds.  The chain
+    // without one (<0, 1>, S = 2) runs near the streaming rate either way and keeps the selects: without them it needs
+    // 62 VGPRs instead of 70, a fourth workgroup becomes resident per CU and the launch gets slower.
+    if (a.zero_slots && first_res && last_res) hipLaunchKernelGGL((level0_chain_kernel<1, 1, true>), dim3(grid), dim3(L0C_WG), 0, st, a);
+    else if (a.zero_slots && first_res) hipLaunchKernelGGL((level0_chain_kernel<1, 0, true>), dim3(grid), dim3(L0C_WG), 0, st, a);
+    else if (first_res && last_res) hipLaunchKernelGGL((level0_chain_kernel<1, 1, false>), dim3(grid), dim3(L0C_WG), 0, st, a);
+    else if (first_res) hipLaunchKernelGGL((level0_chain_kernel<1, 0, false>), dim3(grid), dim3(L0C_WG), 0, st, a);
+    else hipLaunchKernelGGL((level0_chain_kernel<0, 1, false>), dim3(grid), dim3(L0C_WG), 0, st, a);
     LAUNCH_RETURN("level-0 chain launch");
 }
 

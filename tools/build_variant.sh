@@ -8,7 +8,7 @@ NAME=$1; FILES=$2; EXTRA=$3
 make -s
 mkdir -p ../../tools/_bin/_obj_$NAME
 OBJS=""
-for f in kernels hier capi ne devapi schwarz comm spgemm sell gsflow typed hier_c128 hier_multi krylov_c128; do
+for f in kernels hier capi ne devapi schwarz comm spgemm sell gsflow typed hier_c128 hier_multi krylov_c128 strength energy split; do
   if [[ " $FILES " == *" $f.hip "* ]]; then
     hipcc -O3 -std=c++17 -fPIC -ffp-contract=off --offload-arch=gfx950 -Wall -Wno-unused-result -Wno-unused-value $EXTRA -c $f.hip -o ../../tools/_bin/_obj_$NAME/$f.o
     OBJS="$OBJS ../../tools/_bin/_obj_$NAME/$f.o"
