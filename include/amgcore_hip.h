@@ -389,6 +389,17 @@ int amg_hier_pcg(amg_hier *h, const double *b, double *x, double tol, int maxite
 int amg_hier_cycle(amg_hier *h, const double *b, double *x, int cycle, int flags);
 /* levels[lvl].presmoother(A, x, b) / postsmoother on host vectors */
 int amg_hier_relax(amg_hier *h, int lvl, int which, const double *b, double *x);
+/* read-only view of what a smoother over square blocks will run (the counterpart of amg_mat_gs_info; which = 0 / 1 for
+ * the level's smoothers, 2 for the coarse smoother): fills out[0 .. min(nout, 12)) and returns the number written,
+ * AMG_ESTATE when the smoother has no block schedule (block_gauss_seidel, and gauss_seidel / sor on a BSR level, after
+ * amg_hier_finalize) or no block operator (block_jacobi, jacobi on a BSR level).  Fields: 0 dependency levels (0 for
+ * the Jacobi kinds), 1 block size, 2 dataflow form built, 3 its blocks per lane (8 or 5), 4 its lanes per scalar row,
+ * 5 its block rows per chunk, 6 its chunks, 7 its slot rows (3 .. 7: 0 without the form), 8 the level-ordered copy
+ * of the streamed levels is held, 9 slices of the sliced form (the schedule's level-cut one, or the operator's for the
+ * Jacobi kinds; 0: none), 10 block rows scheduled (the operator's block rows for the Jacobi kinds), 11 the longest
+ * off-diagonal block count the dataflow form's builder counted (0 where it was not run or declined before counting) */
+#define AMG_BLOCK_INFO_FIELDS 12
+int amg_hier_block_info(amg_hier *h, int lvl, int which, int *out, int nout);
 /* y = M x for a stored operator (host vectors) */
 int amg_hier_matvec(amg_hier *h, int lvl, int which, const double *x, double *y);
 

@@ -362,6 +362,7 @@ int gs_flow_sweep(const FlowForm &F, bool bsr1, double *x, const double *b, cons
 struct BlockFlowForm {
     bool ready = false;
     int nb = 0, bs = 0, nchunks = 0, nlevels = 0, lpr = 1, seg = 8;     // seg blocks per lane, lpr lanes per scalar row
+    int longest = 0;                    // longest off-diagonal block count the builder counted (kept when it then declines)
     long slot_rows = 0;
     DevArr<int> rows;                // [nb] original block row of position k
     DevArr<FlowChunk> meta;

@@ -840,6 +840,7 @@ int build_block_flow_form(BlockFlowForm &F, int nb, int bs, int ntasks, const st
         cnt[(size_t)k] = c;
         longest = std::max(longest, c);
     }
+    F.longest = longest;
     if (longest > FLOW_SEG * 16) return 0;
     int lpr = 1, seg = FLOW_SEG;
     while (lpr * seg < longest) lpr *= 2;

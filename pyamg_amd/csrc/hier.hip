@@ -2487,6 +2487,33 @@ int amg_hier_relax(amg_hier *h, int lvl, int which, const double *b, double *x)
     return 0;
 }
 
+// what a block smoother's schedule holds and which kernels its sweeps will take (include/amgcore_hip.h lists the fields);
+// reads only
+int amg_hier_block_info(amg_hier *h, int lvl, int which, int *out, int nout)
+{
+    if (!h) { set_error("null hierarchy"); return AMG_EINVAL; }
+    if (lvl < 0 || lvl >= h->nlevels || which < 0 || which > 2) { set_error("bad level/which"); return AMG_EINVAL; }
+    if (!out || nout < 0) { set_error("bad output array"); return AMG_EINVAL; }
+    const Level &L = h->lv[lvl];
+    const Smoother &s = (which == 2) ? h->coarse_sm : L.sm[which];
+    const bool block_kind = s.kind == AMG_SM_BLOCK_GAUSS_SEIDEL || s.kind == AMG_SM_BLOCK_JACOBI;
+    const bool point_kind = (s.kind == AMG_SM_GAUSS_SEIDEL || s.kind == AMG_SM_SOR || s.kind == AMG_SM_JACOBI) && L.fmt == AMG_FMT_BSR && L.R > 1;
+    const bool scheduled = s.kind == AMG_SM_BLOCK_GAUSS_SEIDEL || (point_kind && s.kind != AMG_SM_JACOBI);
+    const DevBsr *Ab = block_kind ? (s.own_blocks() ? &s.Ablk : &L.Ab) : (point_kind ? &L.Ab : nullptr);
+    const Schedule *S = (scheduled && s.sched && s.sched->rows) ? s.sched.get() : nullptr;
+    if (!Ab || !Ab->Ap) { set_error("this smoother has no block operator"); return AMG_ESTATE; }
+    if (scheduled && !S) { set_error("this smoother has no block schedule (amg_hier_finalize builds it)"); return AMG_ESTATE; }
+    const bool flow = S && S->bflow.ready;
+    const int f[AMG_BLOCK_INFO_FIELDS] = {S ? S->nlevels() : 0, Ab->bs, flow ? 1 : 0, flow ? S->bflow.seg : 0, flow ? S->bflow.lpr : 0,
+                                          flow ? 64 / (S->bflow.bs * S->bflow.lpr) : 0, flow ? S->bflow.nchunks : 0,
+                                          flow ? (int)S->bflow.slot_rows : 0, (S && S->Gb.Ap) ? 1 : 0,
+                                          S ? (S->gb_level_slice.empty() ? 0 : S->Gb.bsl_nslices) : (Ab->bsl_val ? Ab->bsl_nslices : 0),
+                                          S ? S->ntasks : Ab->nbrows, S ? S->bflow.longest : 0};
+    const int k = std::min(nout, (int)AMG_BLOCK_INFO_FIELDS);
+    for (int q = 0; q < k; ++q) out[q] = f[q];
+    return k;
+}
+
 int amg_hier_matvec(amg_hier *h, int lvl, int which, const double *x, double *y)
 {
     ENTER(h);
