@@ -1,5 +1,5 @@
 """Generic AMG solver -- the ``multilevel_solver`` object API of the reference
-(/root/reference/pyamg/multilevel.py) with the solve phase running on MI355X.
+(pyamg/multilevel.py) with the solve phase running on MI355X.
 
 The object keeps the reference's attributes (``levels[i].A/P/R``,
 ``presmoother``/``postsmoother`` closures, ``coarse_solver``) as host-side
@@ -23,15 +23,37 @@ __all__ = ["multilevel_solver", "coarse_grid_solver"]
 _SM_KIND = {None: 0, "None": 0, "jacobi": 1, "gauss_seidel": 2, "sor": 3, "polynomial": 4,
             "block_jacobi": 5, "block_gauss_seidel": 6, "gauss_seidel_indexed": 7, "schwarz": 8,
             "gauss_seidel_ne": 9, "gauss_seidel_nr": 10, "jacobi_ne": 11}
-# (name "krylov": a callback smoother, registered by _DeviceHierarchy._set_krylov_smoother)
+# The kinds of every engine: the complex128 and the multi-RHS engine implement the subsets _C128_KIND and _MULTI_KIND
+# under the same numbers.  (name "krylov": a callback smoother of the float64 mirror, _set_krylov_smoother)
 _SWEEP = {"forward": 0, "backward": 1, "symmetric": 2}
 _CYCLE = {"V": 0, "W": 1, "F": 2, "AMLI": 3}
 _X0_ZERO, _NO_EARLY_STOP, _DEVICE_VECTORS = 1, 2, 4
 
 
-def _desc_struct(desc, keep):
-    """descriptor dict (smoothing.py closures' .desc) -> amg_smoother_desc"""
-    d = _lib.SmootherDesc()
+def _cycle_name(cycle):
+    cycle = str(cycle).upper()
+    if cycle not in _CYCLE:
+        raise TypeError("Unrecognized cycle type (%s)" % cycle)
+    return cycle
+
+
+def _flags(x0_zero=False, fixed=False, device_vectors=False):
+    return (_X0_ZERO if x0_zero else 0) | (_NO_EARLY_STOP if fixed else 0) | (_DEVICE_VECTORS if device_vectors else 0)
+
+
+def _is_own_krylov(accel):
+    """is accel one of pyamg_amd.krylov's own methods, named or passed as the function itself?"""
+    from . import krylov
+    name = accel if isinstance(accel, str) else getattr(accel, "__name__", None)
+    return name in krylov.METHODS and (isinstance(accel, str) or accel is krylov.METHODS[name])
+
+
+def _desc_struct(desc, keep, struct=_lib.SmootherDesc):
+    """descriptor dict (smoothing.py closures' .desc) -> amg_smoother_desc, or amg_smoother_desc_x (struct =
+    SmootherDescX), whose omega and Dinv are complex128 arrays passed by address; keep receives the arrays the
+    struct points to"""
+    d = struct()
+    cplx = struct is _lib.SmootherDescX
     name = None if desc is None else desc.get("name")
     if name not in _SM_KIND:
         raise NotImplementedError("smoother %r has no device implementation" % (name,))
@@ -43,16 +65,25 @@ def _desc_struct(desc, keep):
     if sweep not in _SWEEP:
         raise ValueError("valid sweep directions are 'forward', 'backward', and 'symmetric'")
     d.sweep = _SWEEP[sweep]
-    d.omega = float(desc.get("omega", 1.0))
-    if desc.get("coefficients") is not None:
-        co = np.ascontiguousarray(desc["coefficients"], dtype=np.float64)
+    co = desc.get("coefficients")
+    if cplx:
+        omega = np.array([desc.get("omega", 1.0)], dtype=np.complex128)     # type_prep(A.dtype, [omega])
+        keep.append(omega)
+        d.omega = omega.ctypes.data
+        co = [0.0] if co is None else co
+    else:
+        d.omega = float(desc.get("omega", 1.0))
+    if co is not None:
+        co = np.ascontiguousarray(co, dtype=np.float64)
         keep.append(co)
         d.ncoef, d.coef = len(co), _lib.dp(co)
     d.blocksize = int(desc.get("blocksize", 1) or 1)
     if desc.get("Dinv") is not None:
-        Dinv = np.ascontiguousarray(np.ravel(desc["Dinv"]), dtype=np.float64)
+        Dinv = np.ascontiguousarray(np.ravel(desc["Dinv"]), dtype=np.complex128 if cplx else np.float64)
         keep.append(Dinv)
-        d.Dinv = _lib.dp(Dinv)
+        d.Dinv = Dinv.ctypes.data if cplx else _lib.dp(Dinv)
+    if cplx:
+        return d                # the complex128 engine has no indexed or Schwarz smoother
     if desc.get("indices") is not None:
         idx = np.ascontiguousarray(desc["indices"], dtype=np.intc)
         keep.append(idx)
@@ -66,71 +97,218 @@ def _desc_struct(desc, keep):
     return d
 
 
-class _DeviceHierarchy(object):
-    """Owns an amg_hier handle (include/amgcore_hip.h section 2)."""
+_C128_KIND = {None: 0, "None": 0, "jacobi": 1, "gauss_seidel": 2, "sor": 3, "polynomial": 4, "block_jacobi": 5,
+              "block_gauss_seidel": 6}
 
-    def __init__(self, ml, device=0):
-        L = _lib.lib()
-        self.L = L
-        levels = ml.levels
-        self.n = levels[0].A.shape[0]
-        self._shapes = {}
+
+_SCIPY_ONLY_COARSE = ("cgs", "qmr", "minres", "bicg")     # coarse Krylov names run by scipy on complex128 vectors
+
+
+class _ResidentHierarchy(object):
+    """What the mirrors of the three resident engines share: the handle's lifetime, the descriptor of a smoother, the
+    order in which a hierarchy goes into the engine, and the calls that cycle on one vector.  A mirror names its
+    engine's entries (_PREFIX), its value type, its smoother kinds and its refusals, and adds to _set_smoother(lvl,
+    which, fn, A) (which = 2: the coarse solver of the last level; A: the level's operator, for a smoother that needs
+    it in another form) and to the forms of coarse solver (_COARSE) what only its engine has."""
+    _PREFIX = None          # of the engine's entries: amg_hier_, amg_hierx_ or amg_hierm_
+    _DTYPE = None           # of the operators' values
+    _DESC = _lib.SmootherDesc       # the engine's smoother descriptor, which _desc_struct fills
+    _KIND = None            # smoother name -> the engine's kind
+    _NO_SMOOTHER = None     # the refusal of any other smoother (% its name)
+    _NO_COARSE = "coarse solver %s has no device implementation"    # a form that is not in _COARSE (% the solver's name)
+    _COARSE_CALLBACK = None     # the ctypes type of a coarse solver callback, where the engine takes one
+
+    def _fn(self, name):
+        return getattr(self.L, self._PREFIX + name)
+
+    def _open(self, ml, coarse, *create):
+        """makes the handle (create: the arguments of the engine's create entry) and builds the hierarchy into it
+        (coarse: what check_levels returned, where the mirror has one); the handle is closed again if that fails"""
+        self.L = _lib.lib()
+        self.n = ml.levels[0].A.shape[0]
+        self._keep = []                  # what the descriptors point to, until the engine has taken it
         self._callbacks = []             # ctypes callbacks must outlive the hierarchy
         self._callback_error = None
-        self.h = L.amg_hier_create(len(levels), int(device))
-        if not self.h:
-            msg = L.amg_last_error().decode()
-            raise _lib.AmgDeviceError(msg)
+        self.h = self._create(*create)
         try:
-            self._build(ml)
+            self._build(ml, coarse)
         except Exception:
-            L.amg_hier_destroy(self.h)
-            self.h = None
+            self.close()
             raise
+        self._keep = []
 
-    def _set_matrix(self, lvl, which, M):
-        if M.dtype != np.float64:
-            raise NotImplementedError("device hierarchy supports float64 operators only")
-        if sparse.isspmatrix_bsr(M):
-            fmt, (R, C) = 1, M.blocksize
-            data = np.ascontiguousarray(np.ravel(M.data), dtype=np.float64)
-        elif sparse.isspmatrix_csr(M):
-            fmt, R, C = 0, 1, 1
-            data = np.ascontiguousarray(M.data, dtype=np.float64)
-        else:
-            M = sparse.csr_matrix(M)
-            fmt, R, C = 0, 1, 1
-            data = np.ascontiguousarray(M.data, dtype=np.float64)
-        Ap = np.ascontiguousarray(M.indptr, dtype=np.intc)
-        Aj = np.ascontiguousarray(M.indices, dtype=np.intc)
-        self._shapes[(lvl, which)] = M.shape
-        _lib.check(self.L.amg_hier_set_matrix(self.h, lvl, which, fmt, M.shape[0], M.shape[1], R, C,
-                                              Ap.ctypes.data, Aj.ctypes.data, data.ctypes.data, 0))
+    def _create(self, *args):
+        h = _lib.C.c_void_p()
+        _lib.check(self._fn("create")(*args, _lib.C.byref(h)))
+        return h.value
 
-    def _set_smoother(self, lvl, which, fn, A):
+    @classmethod
+    def _desc_of(cls, lvl, fn):
         desc = getattr(fn, "desc", None)
         if fn is not None and desc is None:
             raise NotImplementedError(
                 "level %d: smoother %r carries no device descriptor; use pyamg_amd.smoothing."
                 "change_smoothers with one of the device smoothers" % (lvl, fn))
-        if desc is not None and desc.get("name") == "krylov":
-            return self._set_krylov_smoother(lvl, which, desc, A)
-        keep = []
-        d = _desc_struct(desc, keep)
-        if which == 2:
-            _lib.check(self.L.amg_hier_set_coarse_smoother(self.h, d))
-        else:
-            _lib.check(self.L.amg_hier_set_smoother(self.h, lvl, which, d))
+        name = None if desc is None else desc.get("name")
+        if name not in cls._KIND:
+            raise NotImplementedError(cls._NO_SMOOTHER % (name,))
+        return desc
+
+    @staticmethod
+    def _pattern(M):
+        """a BSR operator as it is, any other as CSR: (fmt, M, indptr, indices), the index arrays as C ints"""
+        fmt = 1 if sparse.isspmatrix_bsr(M) else 0
+        if not fmt:
+            M = sparse.csr_matrix(M)
+        return fmt, M, np.ascontiguousarray(M.indptr, dtype=np.intc), np.ascontiguousarray(M.indices, dtype=np.intc)
+
+    def _set_matrix(self, lvl, which, M, *more):
+        fmt, M, Ap, Aj = self._pattern(M)
+        R, C = M.blocksize if fmt else (1, 1)
+        # a real P / R of a complex hierarchy: astype(complex128), as scipy converts it inside a mixed product
+        data = np.ascontiguousarray(np.ravel(M.data), dtype=self._DTYPE)
+        _lib.check(self._fn("set_matrix")(self.h, lvl, which, fmt, M.shape[0], M.shape[1], R, C,
+                                          Ap.ctypes.data, Aj.ctypes.data, data.ctypes.data, *more))
+
+    def _set_smoother(self, lvl, which, fn, A):
+        d = _desc_struct(self._desc_of(lvl, fn), self._keep, self._DESC)
+        self._set_desc(lvl, which, d)
         if d.kind in (5, 6):
-            # the shim re-blocks A (relaxation.py:471,563): A.tobsr(blocksize=(bs, bs))
+            # the block smoothers sweep A in blocks of their own size (relaxation.py:471,563)
             bs = d.blocksize
             if not (sparse.isspmatrix_bsr(A) and A.blocksize == (bs, bs)):
-                Ab = A.tobsr(blocksize=(bs, bs))
-                Ap = np.ascontiguousarray(Ab.indptr, dtype=np.intc)
-                Aj = np.ascontiguousarray(Ab.indices, dtype=np.intc)
-                Ax = np.ascontiguousarray(np.ravel(Ab.data), dtype=np.float64)
-                _lib.check(self.L.amg_hier_set_block_matrix(self.h, lvl, which, Ab.shape[0] // bs, bs,
-                                                            _lib.ip(Ap), _lib.ip(Aj), _lib.dp(Ax)))
+                _, Ab, Ap, Aj = self._pattern(A.tobsr(blocksize=(bs, bs)))
+                Ax = np.ascontiguousarray(np.ravel(Ab.data), dtype=self._DTYPE)
+                _lib.check(self._fn("set_block_matrix")(self.h, lvl, which, Ab.shape[0] // bs, bs,
+                                                        _lib.ip(Ap), _lib.ip(Aj), _lib.dp(Ax)))
+        return d
+
+    def _set_desc(self, lvl, which, d):
+        if which == 2:
+            _lib.check(self._fn("set_coarse_smoother")(self.h, d))
+        else:
+            _lib.check(self._fn("set_smoother")(self.h, lvl, which, d))
+
+    def _set_coarse_dense(self, M, Ac):         # Ac: only the callback form needs it
+        M = np.ascontiguousarray(M, dtype=self._DTYPE)
+        _lib.check(self._fn("set_coarse_dense")(self.h, _lib.dp(M), M.shape[0]))
+
+    def _set_coarse_callback(self, fn, Ac):
+        """multilevel.py:642-692: Krylov names and callables as coarse solver -- host code on the coarsest level's few
+        hundred unknowns, called from inside the cycle"""
+        owner, dtype = self, np.dtype(self._DTYPE)
+
+        def vector(ptr, n):
+            words = (_lib.C.c_double * (n * dtype.itemsize // 8)).from_address(_lib.C.cast(ptr, _lib.C.c_void_p).value)
+            return np.frombuffer(words, dtype=dtype)
+
+        def solve(user, n, b_ptr, x_ptr):
+            try:
+                b = vector(b_ptr, n).copy()
+                vector(x_ptr, n)[:] = np.asarray(fn(Ac, b), dtype=dtype).ravel()
+                return 0
+            except Exception as e:          # noqa: BLE001 -- must not propagate through the C frames
+                owner._callback_error = e
+                return 1
+        cb = self._COARSE_CALLBACK(solve)
+        self._callbacks.append(cb)
+        _lib.check(self._fn("set_coarse_callback")(self.h, cb, None))
+
+    # form of _CoarseSolver.device_form -> setter(self, payload, Ac); Ac: the coarsest operator
+    _COARSE = {"dense": _set_coarse_dense, "callback": _set_coarse_callback}
+
+    def _build(self, ml, coarse=None):
+        levels = ml.levels
+        for i, lvl in enumerate(levels):
+            self._set_matrix(i, 0, lvl.A)
+            if i < len(levels) - 1:
+                self._set_matrix(i, 1, lvl.P)
+                self._set_matrix(i, 2, lvl.R)
+                self._set_smoother(i, 0, getattr(lvl, "presmoother", None), lvl.A)
+                self._set_smoother(i, 1, getattr(lvl, "postsmoother", None), lvl.A)
+        # coarse is None for a mirror without check_levels: its refusals come from here, in this order
+        kind, payload = ml.coarse_solver.device_form(levels[-1].A) if coarse is None else coarse
+        if kind == "smoother":
+            self._set_smoother(len(levels) - 1, 2, payload, levels[-1].A)
+        elif kind != "none":
+            if kind not in self._COARSE:
+                raise NotImplementedError(self._NO_COARSE % ml.coarse_solver.name())
+            self._COARSE[kind](self, payload, levels[-1].A)
+        _lib.check(self._fn("finalize")(self.h))
+
+    def _check(self, rc):
+        """the engine's return code after a call that may have run a callback: the exception a callback parked is
+        raised in place of the engine's report that the callback failed"""
+        err, self._callback_error = self._callback_error, None
+        if err is not None:
+            raise err
+        _lib.check(rc)
+
+    def solve(self, b, x, tol, maxiter, cycle, x0_zero=False, fixed=False, device_vectors=False):
+        """b, x: contiguous host arrays of the engine's value type, or (device_vectors) addresses in HBM; x is
+        overwritten.  Returns the residual history."""
+        res = np.zeros(maxiter + 2, dtype=np.float64)
+        nres = _lib.C.c_int(0)
+        b, x = (b, x) if device_vectors else (b.ctypes.data, x.ctypes.data)
+        self._check(self._fn("solve")(self.h, b, x, float(tol), int(maxiter), _CYCLE[cycle], _lib.dp(res),
+                                      _lib.C.byref(nres), _flags(x0_zero, fixed, device_vectors)))
+        return res[:nres.value]
+
+    def cycle(self, b, x, cycle, x0_zero=False, device_vectors=False):
+        b, x = (b, x) if device_vectors else (b.ctypes.data, x.ctypes.data)
+        self._check(self._fn("cycle")(self.h, b, x, _CYCLE[cycle], _flags(x0_zero, device_vectors=device_vectors)))
+
+    def cycle_device(self, b_dev, x_dev, cycle):
+        """x_dev = one cycle from a zero guess for the right-hand side b_dev (DEVICE pointers): the preconditioner
+        M of multilevel.py:306-314 for the device-resident Krylov methods"""
+        self.cycle(b_dev, x_dev, cycle, x0_zero=True, device_vectors=True)
+
+    def last_solve_ms(self):
+        return self._fn("last_solve_ms")(self.h)
+
+    def device_bytes(self):
+        return self._fn("device_bytes")(self.h)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._fn("destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _DeviceHierarchy(_ResidentHierarchy):
+    """A float64 hierarchy in HBM: an amg_hier handle (include/amgcore_hip.h section 2), the engine of solve()."""
+
+    _PREFIX, _DTYPE, _KIND = "amg_hier_", np.float64, _SM_KIND
+    _NO_SMOOTHER = "smoother %r has no device implementation"
+    _COARSE_CALLBACK = _lib.COARSE_CALLBACK
+
+    def __init__(self, ml, device=0):
+        self._shapes = {}
+        self._open(ml, None, len(ml.levels), int(device))
+
+    def _create(self, *args):           # this engine's create returns the handle
+        h = self.L.amg_hier_create(*args)
+        if not h:
+            raise _lib.AmgDeviceError(self.L.amg_last_error().decode())
+        return h
+
+    def _set_matrix(self, lvl, which, M):
+        if M.dtype != np.float64:
+            raise NotImplementedError("device hierarchy supports float64 operators only")
+        self._shapes[(lvl, which)] = M.shape
+        super()._set_matrix(lvl, which, M, 0)
+
+    def _set_smoother(self, lvl, which, fn, A):
+        desc = getattr(fn, "desc", None)
+        if desc is not None and desc.get("name") == "krylov":
+            return self._set_krylov_smoother(lvl, which, desc, A)
+        d = super()._set_smoother(lvl, which, fn, A)
         if d.kind in (10, 11):
             # gauss_seidel_nr sweeps / jacobi_ne gathers through A by columns (lvl.Acsc, smoothing.py:472-478)
             self._set_aux(lvl, which, 0, A.tocsc())
@@ -165,24 +343,6 @@ class _DeviceHierarchy(object):
         if aux is not None:
             self._set_aux(lvl, which, 0, sparse.csc_matrix(A))        # A by columns = A^T by rows
 
-    def _set_coarse_callback(self, fn, Ac):
-        """multilevel.py:642-692: Krylov names and callables as coarse solver -- host code on the coarsest level's few
-        hundred unknowns, called from inside the cycle"""
-        owner = self
-
-        def solve(user, n, b_ptr, x_ptr):
-            try:
-                b = np.ctypeslib.as_array(b_ptr, shape=(n,)).copy()
-                x = np.asarray(fn(Ac, b), dtype=np.float64).ravel()
-                np.ctypeslib.as_array(x_ptr, shape=(n,))[:] = x
-                return 0
-            except Exception as e:          # noqa: BLE001
-                owner._callback_error = e
-                return 1
-        cb = _lib.COARSE_CALLBACK(solve)
-        self._callbacks.append(cb)
-        _lib.check(self.L.amg_hier_set_coarse_callback(self.h, cb, None))
-
     def _set_aux(self, lvl, which, slot, M):
         M.sort_indices()
         Ap = np.ascontiguousarray(M.indptr, dtype=np.intc)
@@ -193,74 +353,33 @@ class _DeviceHierarchy(object):
         _lib.check(self.L.amg_hier_set_aux_matrix(self.h, lvl, which, slot, nmajor, nminor, _lib.ip(Ap), _lib.ip(Aj),
                                                   _lib.dp(Ax)))
 
-    def _build(self, ml):
-        levels = ml.levels
-        for i, lvl in enumerate(levels):
-            self._set_matrix(i, 0, lvl.A)
-            if i < len(levels) - 1:
-                self._set_matrix(i, 1, lvl.P)
-                self._set_matrix(i, 2, lvl.R)
-                self._set_smoother(i, 0, getattr(lvl, "presmoother", None), lvl.A)
-                self._set_smoother(i, 1, getattr(lvl, "postsmoother", None), lvl.A)
-        cs = ml.coarse_solver
-        Ac = levels[-1].A
-        kind, payload = cs.device_form(Ac)
-        if kind == "dense":
-            M = np.ascontiguousarray(payload, dtype=np.float64)
-            _lib.check(self.L.amg_hier_set_coarse_dense(self.h, _lib.dp(M), M.shape[0]))
-        elif kind == "smoother":
-            self._set_smoother(len(levels) - 1, 2, payload, Ac)
-        elif kind == "callback":
-            self._set_coarse_callback(payload, Ac)
-        elif kind != "none":
-            raise NotImplementedError("coarse solver %s has no device implementation" % cs.name())
-        _lib.check(self.L.amg_hier_finalize(self.h))
+    def _build(self, ml, coarse=None):
+        super()._build(ml, coarse)
         # Large hierarchies: the CSR arrays of operators that are only ever applied from their stencil / sliced form
         # are not kept beside it (500^3 Chebyshev hierarchy: 56.6 -> 34 GB in HBM, same bits).  The host copies stay in
         # ml.levels, so change_smoothers / a rebuilt mirror have everything they need.  AMG_RELEASE_SOURCES=0 keeps
         # them (A/B runs of the other kernels on a live hierarchy), =1 releases at any size.
         rel = os.environ.get("AMG_RELEASE_SOURCES")
-        big = levels[0].A.shape[0] >= 4000000
+        big = ml.levels[0].A.shape[0] >= 4000000
         self.released_bytes = 0
         if rel == "1" or (rel is None and big):
             self.released_bytes = int(self.L.amg_hier_release_sources(self.h))
 
-    def _check(self, rc):
-        err, self._callback_error = self._callback_error, None
-        if err is not None:
-            raise err
-        _lib.check(rc)
-
-    def solve(self, b, x, tol, maxiter, cycle, x0_zero=False, fixed=False):
-        res = np.zeros(maxiter + 2, dtype=np.float64)
-        nres = _lib.C.c_int(0)
-        flags = (_X0_ZERO if x0_zero else 0) | (_NO_EARLY_STOP if fixed else 0)
-        self._check(self.L.amg_hier_solve(self.h, b.ctypes.data, x.ctypes.data, float(tol), int(maxiter),
-                                          _CYCLE[cycle], _lib.dp(res), _lib.C.byref(nres), flags))
-        return res[:nres.value]
-
-    def pcg(self, b, x, tol, maxiter, cycle, x0_zero=False):
+    def pcg(self, b, x, tol, maxiter, cycle, x0_zero=False, device_vectors=False):
+        """preconditioned CG around the cycle, b and x as in solve().  Returns the history and CG's info."""
         res = np.zeros(maxiter + 2, dtype=np.float64)
         nres, info = _lib.C.c_int(0), _lib.C.c_int(0)
-        _lib.check(self.L.amg_hier_pcg(self.h, b.ctypes.data, x.ctypes.data, float(tol), int(maxiter),
-                                       _CYCLE[cycle], _lib.dp(res), _lib.C.byref(nres), _lib.C.byref(info),
-                                       _X0_ZERO if x0_zero else 0))
+        b, x = (b, x) if device_vectors else (b.ctypes.data, x.ctypes.data)
+        self._check(self.L.amg_hier_pcg(self.h, b, x, float(tol), int(maxiter), _CYCLE[cycle], _lib.dp(res),
+                                        _lib.C.byref(nres), _lib.C.byref(info),
+                                        _flags(x0_zero, device_vectors=device_vectors)))
         return res[:nres.value], info.value
-
-    def cycle(self, b, x, cycle, x0_zero=False):
-        self._check(self.L.amg_hier_cycle(self.h, b.ctypes.data, x.ctypes.data, _CYCLE[cycle],
-                                          _X0_ZERO if x0_zero else 0))
-
-    def cycle_device(self, b_dev, x_dev, cycle):
-        """x_dev = one cycle from a zero guess for the right-hand side b_dev (DEVICE pointers): the preconditioner
-        M of multilevel.py:306-314 for the device-resident Krylov methods"""
-        self._check(self.L.amg_hier_cycle(self.h, b_dev, x_dev, _CYCLE[cycle], _X0_ZERO | _DEVICE_VECTORS))
 
     def level_size(self, lvl):
         return self._shapes[(lvl, 0)][0]
 
     def relax(self, lvl, which, b, x):
-        _lib.check(self.L.amg_hier_relax(self.h, lvl, which, _lib.dp(b), _lib.dp(x)))
+        self._check(self.L.amg_hier_relax(self.h, lvl, which, _lib.dp(b), _lib.dp(x)))
 
     def matvec(self, lvl, which, x):
         rows, cols = self._shapes[(lvl, which)]
@@ -277,12 +396,6 @@ class _DeviceHierarchy(object):
     def cycle_bytes_moved(self, cycle="V"):
         return self.L.amg_hier_cycle_bytes_moved(self.h, _CYCLE[cycle])
 
-    def last_solve_ms(self):
-        return self.L.amg_hier_last_solve_ms(self.h)
-
-    def device_bytes(self):
-        return self.L.amg_hier_device_bytes(self.h)
-
     def time_spmv(self, lvl, which, mode=0, reps=10):
         ms = _lib.C.c_double(0.0)
         _lib.check(self.L.amg_hier_time_spmv(self.h, lvl, which, mode, reps, _lib.C.byref(ms)))
@@ -290,140 +403,20 @@ class _DeviceHierarchy(object):
 
     def time_relax(self, lvl, which, reps=5):
         ms = _lib.C.c_double(0.0)
-        _lib.check(self.L.amg_hier_time_relax(self.h, lvl, which, reps, _lib.C.byref(ms)))
+        self._check(self.L.amg_hier_time_relax(self.h, lvl, which, reps, _lib.C.byref(ms)))
         return ms.value
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.amg_hier_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-_C128_KIND = {None: 0, "None": 0, "jacobi": 1, "gauss_seidel": 2, "sor": 3, "polynomial": 4, "block_jacobi": 5,
-              "block_gauss_seidel": 6}
-
-
-_SCIPY_ONLY_COARSE = ("cgs", "qmr", "minres", "bicg")     # coarse Krylov names run by scipy on complex128 vectors
-
-
-def _c128(a):
-    return np.ascontiguousarray(np.ravel(a), dtype=np.complex128)
-
-
-class _ResidentHierarchy(object):
-    """What the mirrors of the two plain resident engines share: the handle's lifetime, the descriptor of a smoother
-    and the order in which a hierarchy goes into the engine.  A mirror names its value type, its smoother kinds and
-    its refusals, binds the engine's entries that this base calls (self._entry, before _open), and sets a smoother
-    (_set_smoother(lvl, which, fn, A); which = 2: the coarse solver of the last level; A: the level's operator, for
-    a smoother that needs it in another form) and every other form of coarse solver it has (_COARSE)."""
-    _DTYPE = None           # of the operators' values
-    _KIND = None            # smoother name -> the engine's kind
-    _NO_SMOOTHER = None     # the refusal of any other smoother (% its name)
-    _NO_COARSE = None       # the refusal of a coarse solver form that is not in _COARSE (% the solver's name)
-    _COARSE = None          # form of _CoarseSolver.device_form -> setter(self, payload, Ac); Ac: the coarsest operator
-
-    def _open(self, ml, create, coarse=None):
-        """create(byref(h)) makes the handle; the hierarchy is then built into it (coarse: what check_levels returned,
-        when it has run), and the handle is closed again if that fails"""
-        self._keep = []
-        h = _lib.C.c_void_p()
-        _lib.check(create(_lib.C.byref(h)))
-        self.h = h.value
-        try:
-            self._build(ml, coarse)
-        except Exception:
-            self.close()
-            raise
-        self._keep = []
-
-    @classmethod
-    def _desc_of(cls, lvl, fn):
-        desc = getattr(fn, "desc", None)
-        if fn is not None and desc is None:
-            raise NotImplementedError(
-                "level %d: smoother %r carries no device descriptor; use pyamg_amd.smoothing."
-                "change_smoothers with one of the device smoothers" % (lvl, fn))
-        name = None if desc is None else desc.get("name")
-        if name not in cls._KIND:
-            raise NotImplementedError(cls._NO_SMOOTHER % (name,))
-        return desc
-
-    @staticmethod
-    def _pattern(M):
-        """a BSR operator as it is, any other as CSR: (fmt, M, indptr, indices), the index arrays as C ints"""
-        fmt = 1 if sparse.isspmatrix_bsr(M) else 0
-        if not fmt:
-            M = sparse.csr_matrix(M)
-        return fmt, M, np.ascontiguousarray(M.indptr, dtype=np.intc), np.ascontiguousarray(M.indices, dtype=np.intc)
-
-    def _set_matrix(self, lvl, which, M):
-        fmt, M, Ap, Aj = self._pattern(M)
-        R, C = M.blocksize if fmt else (1, 1)
-        # a real P / R of a complex hierarchy: astype(complex128), as scipy converts it inside a mixed product
-        data = np.ascontiguousarray(np.ravel(M.data), dtype=self._DTYPE)
-        _lib.check(self._entry["set_matrix"](self.h, lvl, which, fmt, M.shape[0], M.shape[1], R, C,
-                                          Ap.ctypes.data, Aj.ctypes.data, data.ctypes.data))
-
-    def _build(self, ml, coarse=None):
-        levels = ml.levels
-        kind, payload = self.check_levels(ml) if coarse is None else coarse
-        for i, lvl in enumerate(levels):
-            self._set_matrix(i, 0, lvl.A)
-            if i < len(levels) - 1:
-                self._set_matrix(i, 1, lvl.P)
-                self._set_matrix(i, 2, lvl.R)
-                self._set_smoother(i, 0, getattr(lvl, "presmoother", None), lvl.A)
-                self._set_smoother(i, 1, getattr(lvl, "postsmoother", None), lvl.A)
-        if kind == "smoother":
-            self._set_smoother(len(levels) - 1, 2, payload, levels[-1].A)
-        elif kind != "none":
-            if kind not in self._COARSE:
-                raise NotImplementedError(self._NO_COARSE % ml.coarse_solver.name())
-            self._COARSE[kind](self, payload, levels[-1].A)
-        _lib.check(self._entry["finalize"](self.h))
-
-    def last_solve_ms(self):
-        return self._entry["last_solve_ms"](self.h)
-
-    def device_bytes(self):
-        return self._entry["device_bytes"](self.h)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self._entry["destroy"](self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class _DeviceHierarchyC128(_ResidentHierarchy):
     """A complex128 hierarchy in HBM: an amg_hierx handle (include/amgcore_hip.h section 5).  Plain CSR / BSR
     operators, eager launches; the cycle gives the reference's bits."""
 
-    _DTYPE, _KIND = np.complex128, _C128_KIND
+    _PREFIX, _DTYPE, _DESC, _KIND = "amg_hierx_", np.complex128, _lib.SmootherDescX, _C128_KIND
     _NO_SMOOTHER = "smoother %r has no complex128 device implementation"
-    _NO_COARSE = "coarse solver %s has no device implementation"
+    _COARSE_CALLBACK = _lib.COARSE_CALLBACK_X
 
     def __init__(self, ml, device=0):
-        L = _lib.lib()
-        self.L = L
-        self.n = ml.levels[0].A.shape[0]
-        self._callbacks = []
-        self._callback_error = None
-        self._entry = {"set_matrix": L.amg_hierx_set_matrix, "finalize": L.amg_hierx_finalize,
-                       "destroy": L.amg_hierx_destroy, "last_solve_ms": L.amg_hierx_last_solve_ms,
-                       "device_bytes": L.amg_hierx_device_bytes}
-        self._open(ml, lambda h: L.amg_hierx_create(_lib.AMG_VALUE_C128, len(ml.levels), int(device), h))
+        self._open(ml, self.check_levels(ml), _lib.AMG_VALUE_C128, len(ml.levels), int(device))
 
     @staticmethod
     def check_levels(ml):
@@ -435,8 +428,7 @@ class _DeviceHierarchyC128(_ResidentHierarchy):
                 for side in ("presmoother", "postsmoother"):
                     _DeviceHierarchyC128._desc_of(i, getattr(lvl, side, None))
         s = ml.coarse_solver.solver
-        from . import krylov
-        if (isinstance(s, str) and s in krylov.METHODS) or any(s is f for f in krylov.METHODS.values()):
+        if _is_own_krylov(s):
             # pyamg_amd.krylov runs float64 on the device: it would drop the imaginary parts of the coarse problem
             raise NotImplementedError(
                 "coarse solver %r: the device Krylov methods are float64 only; for a complex128 hierarchy use a dense "
@@ -449,80 +441,8 @@ class _DeviceHierarchyC128(_ResidentHierarchy):
             _DeviceHierarchyC128._desc_of(len(ml.levels) - 1, payload)
         return kind, payload
 
-    def _set_smoother(self, lvl, which, fn, A):
-        desc = self._desc_of(lvl, fn)
-        d = _lib.SmootherDescX()
-        name = None if desc is None else desc.get("name")
-        d.kind = _C128_KIND[name]
-        if d.kind:
-            d.iterations = int(desc.get("iterations", 1))
-            sweep = desc.get("sweep", "forward")
-            if sweep not in _SWEEP:
-                raise ValueError("valid sweep directions are 'forward', 'backward', and 'symmetric'")
-            d.sweep = _SWEEP[sweep]
-            omega = _c128([desc.get("omega", 1.0)])     # type_prep(A.dtype, [omega])
-            co = desc.get("coefficients")
-            co = np.ascontiguousarray([0.0] if co is None else co, dtype=np.float64)
-            d.omega, d.ncoef, d.coef = omega.ctypes.data, len(co), _lib.dp(co)
-            d.blocksize = int(desc.get("blocksize", 1) or 1)
-            self._keep.extend([omega, co])
-            if desc.get("Dinv") is not None:
-                Dinv = _c128(desc["Dinv"])
-                self._keep.append(Dinv)
-                d.Dinv = Dinv.ctypes.data
+    def _set_desc(self, lvl, which, d):         # the coarse smoother is slot 2 of the last level
         _lib.check(self.L.amg_hierx_set_smoother(self.h, lvl, which, d))
-        if d.kind in (5, 6):
-            # relaxation.py:471,563: A.tobsr(blocksize=(bs, bs))
-            bs = d.blocksize
-            if not (sparse.isspmatrix_bsr(A) and A.blocksize == (bs, bs)):
-                _, Ab, Ap, Aj = self._pattern(A.tobsr(blocksize=(bs, bs)))
-                Ax = _c128(Ab.data)
-                _lib.check(self.L.amg_hierx_set_block_matrix(self.h, lvl, which, Ab.shape[0] // bs, bs,
-                                                             Ap.ctypes.data, Aj.ctypes.data, Ax.ctypes.data))
-
-    def _set_coarse_dense(self, M, Ac):         # Ac: only the callback form needs it
-        M = np.ascontiguousarray(M, dtype=np.complex128)
-        _lib.check(self.L.amg_hierx_set_coarse_dense(self.h, M.ctypes.data, M.shape[0]))
-
-    def _set_coarse_callback(self, fn, Ac):
-        owner = self
-
-        def solve(user, n, b_ptr, x_ptr):
-            try:
-                b = np.frombuffer((_lib.C.c_double * (2 * n)).from_address(b_ptr), dtype=np.complex128).copy()
-                x = np.asarray(fn(Ac, b), dtype=np.complex128).ravel()
-                np.frombuffer((_lib.C.c_double * (2 * n)).from_address(x_ptr), dtype=np.complex128)[:] = x
-                return 0
-            except Exception as e:          # noqa: BLE001 -- must not propagate through the C frames
-                owner._callback_error = e
-                return 1
-        cb = _lib.COARSE_CALLBACK_X(solve)
-        self._callbacks.append(cb)
-        _lib.check(self.L.amg_hierx_set_coarse_callback(self.h, cb, None))
-
-    _COARSE = {"dense": _set_coarse_dense, "callback": _set_coarse_callback}
-
-    def _check(self, rc):
-        err, self._callback_error = self._callback_error, None
-        if err is not None:
-            raise err
-        _lib.check(rc)
-
-    def solve(self, b, x, tol, maxiter, cycle, x0_zero=False, fixed=False):
-        res = np.zeros(maxiter + 2, dtype=np.float64)
-        nres = _lib.C.c_int(0)
-        flags = (_X0_ZERO if x0_zero else 0) | (_NO_EARLY_STOP if fixed else 0)
-        self._check(self.L.amg_hierx_solve(self.h, b.ctypes.data, x.ctypes.data, float(tol), int(maxiter),
-                                           _CYCLE[cycle], _lib.dp(res), _lib.C.byref(nres), flags))
-        return res[:nres.value]
-
-    def cycle(self, b, x, cycle, x0_zero=False):
-        self._check(self.L.amg_hierx_cycle(self.h, b.ctypes.data, x.ctypes.data, _CYCLE[cycle],
-                                           _X0_ZERO if x0_zero else 0))
-
-    def cycle_device(self, b_dev, x_dev, cycle):
-        """x = one cycle from a zero guess for the right-hand side b, both device vectors (pyamg_amd.krylov_c128)"""
-        self._check(self.L.amg_hierx_cycle(self.h, b_dev, x_dev, _CYCLE[cycle], _X0_ZERO | _DEVICE_VECTORS))
 
 
 _MULTI_KIND = {None: 0, "None": 0, "jacobi": 1, "gauss_seidel": 2, "sor": 3, "polynomial": 4}
@@ -581,22 +501,17 @@ class _DeviceHierarchyMulti(_ResidentHierarchy):
     section 6).  Plain CSR operators, eager launches; per column the cycle gives the bits of the one-vector engine
     (DESIGN.md section 9c)."""
 
-    _DTYPE, _KIND = np.float64, _MULTI_KIND
+    _PREFIX, _DTYPE, _KIND = "amg_hierm_", np.float64, _MULTI_KIND
     _NO_SMOOTHER = ("solve_many: smoother %r is not implemented (jacobi, gauss_seidel, sor, "
                     "polynomial / chebyshev / richardson, None)")
     _NO_COARSE = "coarse solver %s has no implementation for several right-hand sides"
+    _COARSE = {"dense": _ResidentHierarchy._set_coarse_dense}
+    cycle_device = None             # the columns come from the host
 
     def __init__(self, ml, device=0, kmax=_MULTI_KMAX):
-        L = _lib.lib()
-        self.L = L
-        self.n = ml.levels[0].A.shape[0]
         self.kmax = int(kmax)
         self._cycles = 0
-        coarse = self.check_levels(ml)
-        self._entry = {"set_matrix": L.amg_hierm_set_matrix, "finalize": L.amg_hierm_finalize,
-                       "destroy": L.amg_hierm_destroy, "last_solve_ms": L.amg_hierm_last_solve_ms,
-                       "device_bytes": L.amg_hierm_device_bytes}
-        self._open(ml, lambda h: L.amg_hierm_create(len(ml.levels), int(device), self.kmax, h), coarse)
+        self._open(ml, self.check_levels(ml), len(ml.levels), int(device), self.kmax)
 
     @staticmethod
     def check_levels(ml):
@@ -627,33 +542,19 @@ class _DeviceHierarchyMulti(_ResidentHierarchy):
             _DeviceHierarchyMulti._desc_of(len(ml.levels) - 1, payload)
         return kind, payload
 
-    def _set_smoother(self, lvl, which, fn, A):     # A: unused, no smoother here needs another form of it
-        d = _desc_struct(self._desc_of(lvl, fn), self._keep)
-        if which == 2:
-            _lib.check(self.L.amg_hierm_set_coarse_smoother(self.h, d))
-        else:
-            _lib.check(self.L.amg_hierm_set_smoother(self.h, lvl, which, d))
-
-    def _set_coarse_dense(self, M, Ac):             # Ac: unused, part of the setters' common signature
-        M = np.ascontiguousarray(M, dtype=np.float64)
-        _lib.check(self.L.amg_hierm_set_coarse_dense(self.h, _lib.dp(M), M.shape[0]))
-
-    _COARSE = {"dense": _set_coarse_dense}
-
     def solve(self, B, X, tol, maxiter, cycle, x0_zero=False, fixed=False):
         """B, X: C-contiguous float64 (n, k), k <= kmax; X is overwritten.  Returns the k residual histories."""
         k = B.shape[1]
         res = np.zeros((k, maxiter + 1), dtype=np.float64)
         nres = np.zeros(k, dtype=np.intc)
-        flags = (_X0_ZERO if x0_zero else 0) | (_NO_EARLY_STOP if fixed else 0)
         _lib.check(self.L.amg_hierm_solve(self.h, k, B.ctypes.data, X.ctypes.data, float(tol), int(maxiter),
-                                          _CYCLE[cycle], _lib.dp(res), _lib.ip(nres), flags))
+                                          _CYCLE[cycle], _lib.dp(res), _lib.ip(nres), _flags(x0_zero, fixed)))
         self._cycles += int(nres.max()) - 1
         return [res[j, :nres[j]] for j in range(k)]
 
     def cycle(self, B, X, cycle, x0_zero=False):
         _lib.check(self.L.amg_hierm_cycle(self.h, B.shape[1], B.ctypes.data, X.ctypes.data, _CYCLE[cycle],
-                                          _X0_ZERO if x0_zero else 0))
+                                          _flags(x0_zero)))
         self._cycles += 1
 
     def cycles_run(self):
@@ -731,10 +632,7 @@ class multilevel_solver:
         """Entries of the level operators touched by one cycle, relative to the finest operator:
         every arrival at a level costs two passes over A (pre- and post-smoothing), the coarsest
         level one (its solve) -- the values of multilevel.py:178-248."""
-        cycle = str(cycle).upper()
-        kind = {"V": "V", "W": "W", "AMLI": "W", "F": "F"}.get(cycle)
-        if kind is None:
-            raise TypeError("Unrecognized cycle type (%s)" % cycle)
+        kind = {"V": "V", "W": "W", "AMLI": "W", "F": "F"}[_cycle_name(cycle)]
         nnz = self._level_nnz()
         if len(nnz) == 1:
             return 1.0
@@ -823,9 +721,7 @@ class multilevel_solver:
 
     def _check_many(self, cycle):
         """what solve_many refuses about the hierarchy and the cycle, before any device work; returns the cycle's name"""
-        cycle = str(cycle).upper()
-        if cycle not in _CYCLE:
-            raise TypeError("Unrecognized cycle type (%s)" % cycle)
+        cycle = _cycle_name(cycle)
         if cycle == "AMLI":
             raise NotImplementedError("solve_many: AMLI cycles are not implemented")
         if getattr(self, "_devm", None) is None:
@@ -917,18 +813,15 @@ class multilevel_solver:
         cycling and accel='cg' (the device PCG); same iterates and history as with host vectors."""
         if _is_device_tensor(b):
             return self._solve_device_tensors(b, x0, tol, maxiter, cycle, accel, callback, residuals)
-        if _is_c128(self):
-            return self._solve_c128(b, x0, tol, maxiter, cycle, accel, callback, residuals, return_residuals)
+        A = self.levels[0].A
+        c128 = _is_c128(self)       # V, W and F cycles on the complex128 engine: the reference's bits (DESIGN.md section 9b)
         b = np.asarray(b)
-        if x0 is None:
-            x = np.zeros_like(b)
-        else:
-            x = np.array(x0)   # copy
-        cycle = str(cycle).upper()
-        if cycle not in _CYCLE:
-            raise TypeError("Unrecognized cycle type (%s)" % cycle)
-        if (cycle == "AMLI") and hasattr(self.levels[0].A, "symmetry"):
-            if self.levels[0].A.symmetry != "hermitian":
+        x = np.zeros_like(b) if x0 is None else np.array(x0)   # copy
+        cycle = _cycle_name(cycle)
+        if cycle == "AMLI":
+            if c128:
+                raise NotImplementedError("AMLI cycles are not implemented for complex128 hierarchies")
+            if hasattr(A, "symmetry") and A.symmetry != "hermitian":
                 raise ValueError("AMLI cycles require symmetry to be hermitian")
 
         if accel is not None:
@@ -942,18 +835,26 @@ class multilevel_solver:
         else:
             residuals[:] = []
 
-        tp = np.result_type(b.dtype, x.dtype, self.levels[0].A.dtype)
-        if tp != np.float64:
-            if np.issubdtype(tp, np.floating) or np.issubdtype(tp, np.integer):
-                tp = np.float64
-            else:
+        n = A.shape[0]
+
+        def check_size():
+            if b.size != n or x.size != n:
+                raise ValueError("b and x0 must have %d entries" % n)
+        if c128:
+            check_size()
+            tp = np.result_type(b.dtype, x.dtype, A.dtype)     # upcast(b, x, A)
+            if tp != np.complex128:
+                raise NotImplementedError("complex128 hierarchy: b and x0 of type %s" % tp)
+            if self._dev is None:
+                _DeviceHierarchyC128.check_levels(self)          # refusals before any device work
+        else:
+            tp = np.result_type(b.dtype, x.dtype, A.dtype)
+            if tp != np.float64 and not (np.issubdtype(tp, np.floating) or np.issubdtype(tp, np.integer)):
                 raise NotImplementedError("device solve supports real float64 systems only")
+            check_size()
         shape = b.shape
-        n = self.levels[0].A.shape[0]
-        if b.size != n or x.size != n:
-            raise ValueError("b and x0 must have %d entries" % n)
-        b1 = np.ascontiguousarray(np.ravel(b), dtype=np.float64)
-        x1 = np.ascontiguousarray(np.ravel(x), dtype=np.float64)
+        b1 = np.ascontiguousarray(np.ravel(b), dtype=np.complex128 if c128 else np.float64)
+        x1 = np.ascontiguousarray(np.ravel(x), dtype=b1.dtype)
         x0_zero = not np.any(x1)
         dev = self.device_hierarchy()
 
@@ -962,69 +863,7 @@ class multilevel_solver:
             residuals.extend(float(r) for r in res)
         else:
             # one cycle per call so that callback(x) sees every iterate (multilevel.py:454-466)
-            normb = float(np.sqrt(np.inner(b1, b1)))
-            atol = tol * normb if normb != 0 else tol
-            res = dev.solve(b1, x1, 0.0, 0, cycle, x0_zero=x0_zero)
-            residuals.append(float(res[0]))
-            while len(residuals) <= maxiter and residuals[-1] > atol:
-                res = dev.solve(b1, x1, 0.0, 1, cycle, x0_zero=x0_zero, fixed=True)
-                x0_zero = False
-                residuals.append(float(res[-1]))
-                callback(x1.reshape(shape))
-        xout = x1.reshape(shape)
-        if return_residuals:
-            return xout, residuals
-        return xout
-
-    def _solve_c128(self, b, x0, tol, maxiter, cycle, accel, callback, residuals, return_residuals):
-        """solve() of a complex128 hierarchy (multilevel.py:316-471): V, W and F cycles on the device, scipy's Krylov
-        methods around it; the complex cycle gives the reference's bits"""
-        b = np.asarray(b)
-        x = np.zeros_like(b) if x0 is None else np.array(x0)
-        cycle = str(cycle).upper()
-        if cycle not in _CYCLE:
-            raise TypeError("Unrecognized cycle type (%s)" % cycle)
-        if cycle == "AMLI":
-            raise NotImplementedError("AMLI cycles are not implemented for complex128 hierarchies")
-        if accel is not None:
-            from . import krylov
-            name = accel if isinstance(accel, str) else getattr(accel, "__name__", None)
-            if name in krylov.METHODS and (isinstance(accel, str) or accel is krylov.METHODS[name]):
-                raise NotImplementedError(
-                    "the device Krylov methods are float64 only; for a complex128 hierarchy pass a scipy.sparse.linalg "
-                    "callable as accel, or use aspreconditioner() as M")
-            from . import krylov_c128
-            if any(accel is f for f in krylov_c128.METHODS.values()):
-                # the complex128 device methods: vectors stay in HBM, the cycle is M (DESIGN.md section 9d)
-                return accel(self.levels[0].A, b, x0=x0, tol=tol, maxiter=maxiter, M=self.aspreconditioner(cycle=cycle),
-                             callback=callback, residuals=residuals)[0]
-            _DeviceHierarchyC128.check_levels(self)
-            return self._solve_accel(b, x0, tol, maxiter, cycle, accel, callback, residuals)
-        if return_residuals:
-            warn("return_residuals is deprecated.  Use residuals instead")
-            residuals = []
-        if residuals is None:
-            residuals = []
-        else:
-            residuals[:] = []
-        n = self.levels[0].A.shape[0]
-        if b.size != n or x.size != n:
-            raise ValueError("b and x0 must have %d entries" % n)
-        tp = np.result_type(b.dtype, x.dtype, self.levels[0].A.dtype)     # upcast(b, x, A)
-        if tp != np.complex128:
-            raise NotImplementedError("complex128 hierarchy: b and x0 of type %s" % tp)
-        shape = b.shape
-        b1, x1 = _c128(b), _c128(x)
-        x0_zero = not np.any(x1)
-        if self._dev is None:
-            _DeviceHierarchyC128.check_levels(self)          # refusals before any device work
-        dev = self.device_hierarchy()
-        if callback is None:
-            res = dev.solve(b1, x1, tol, maxiter, cycle, x0_zero=x0_zero)
-            residuals.extend(float(r) for r in res)
-        else:
-            # one cycle per call so that callback(x) sees every iterate (multilevel.py:454-466)
-            normb = float(np.sqrt(np.vdot(b1, b1).real))
+            normb = float(np.sqrt(np.vdot(b1, b1).real if c128 else np.inner(b1, b1)))
             atol = tol * normb if normb != 0 else tol
             res = dev.solve(b1, x1, 0.0, 0, cycle, x0_zero=x0_zero)
             residuals.append(float(res[0]))
@@ -1042,9 +881,7 @@ class multilevel_solver:
         import torch
         if _is_c128(self):
             raise NotImplementedError("device tensors: float64 hierarchies only; pass host arrays to a complex128 one")
-        cycle = str(cycle).upper()
-        if cycle not in _CYCLE:
-            raise TypeError("Unrecognized cycle type (%s)" % cycle)
+        cycle = _cycle_name(cycle)
         if callback is not None or accel not in (None, "cg"):
             raise NotImplementedError("device tensors: plain cycling and accel='cg' (no callback); pass host arrays otherwise")
         if accel == "cg" and cycle == "AMLI":
@@ -1055,30 +892,36 @@ class multilevel_solver:
             if not _is_device_tensor(t) or t.dtype != torch.float64 or t.numel() != n or not t.is_contiguous() or t.device.index != self.device:
                 raise ValueError("device tensors must be contiguous float64 CUDA tensors of %d entries on device %d" % (n, self.device))
         x = torch.zeros_like(b) if x0 is None else x0.clone()
-        x0_zero = x0 is None
         torch.cuda.current_stream(b.device).synchronize()          # the library works on its own stream
-        if maxiter is None:
-            maxiter = int(1.3 * n) + 2 if accel == "cg" else 100
-        res = np.zeros(maxiter + 2, dtype=np.float64)
-        nres = _lib.C.c_int(0)
-        flags = _DEVICE_VECTORS | (_X0_ZERO if x0_zero else 0)
         if accel == "cg":
-            info = _lib.C.c_int(0)
-            _lib.check(dev.L.amg_hier_pcg(dev.h, b.data_ptr(), x.data_ptr(), float(tol), int(maxiter), _CYCLE[cycle], _lib.dp(res),
-                                          _lib.C.byref(nres), _lib.C.byref(info), flags))
-            if info.value < 0:
+            if maxiter is None:
+                maxiter = int(1.3 * n) + 2
+            res, info = dev.pcg(b.data_ptr(), x.data_ptr(), tol, maxiter, cycle, x0_zero=x0 is None, device_vectors=True)
+            if info < 0:
                 warn("Indefinite matrix or preconditioner detected in CG, aborting")
         else:
-            dev._check(dev.L.amg_hier_solve(dev.h, b.data_ptr(), x.data_ptr(), float(tol), int(maxiter), _CYCLE[cycle], _lib.dp(res),
-                                            _lib.C.byref(nres), flags))
+            res = dev.solve(b.data_ptr(), x.data_ptr(), tol, 100 if maxiter is None else maxiter, cycle,
+                            x0_zero=x0 is None, device_vectors=True)
         if residuals is not None:
-            residuals[:] = [float(r) for r in res[:nres.value]]
+            residuals[:] = [float(r) for r in res]
         return x
 
     def _solve_accel(self, b, x0, tol, maxiter, cycle, accel, callback, residuals):
         """Krylov acceleration (multilevel.py:381-422): the cycle is the preconditioner M;
         the outer Krylov iteration is scipy's (the reference falls back to the same
         scipy.sparse.linalg interface, :404-422)."""
+        own = _is_own_krylov(accel)
+        if _is_c128(self):
+            if own:
+                raise NotImplementedError(
+                    "the device Krylov methods are float64 only; for a complex128 hierarchy pass a scipy.sparse.linalg "
+                    "callable as accel, or use aspreconditioner() as M")
+            from . import krylov_c128
+            if any(accel is f for f in krylov_c128.METHODS.values()):
+                # the complex128 device methods: vectors stay in HBM, the cycle is M (DESIGN.md section 9d)
+                return accel(self.levels[0].A, b, x0=x0, tol=tol, maxiter=maxiter, M=self.aspreconditioner(cycle=cycle),
+                             callback=callback, residuals=residuals)[0]
+            _DeviceHierarchyC128.check_levels(self)
         if (accel != "fgmres") and (cycle == "AMLI"):
             raise ValueError("AMLI cycles require acceleration (accel) to be fgmres, or no acceleration")
         if accel == "cg" and callback is None:
@@ -1094,10 +937,10 @@ class multilevel_solver:
             if residuals is not None:
                 residuals[:] = [float(r) for r in res]
             return x1.reshape(np.asarray(b).shape)
-        from . import krylov
-        name = accel if isinstance(accel, str) else getattr(accel, "__name__", None)
-        if name in krylov.METHODS and (isinstance(accel, str) or accel is krylov.METHODS[name]):
+        if own:
             # pyamg.krylov's own methods (multilevel.py:390-394), device-resident: vectors stay in HBM, the cycle is M
+            from . import krylov
+            name = accel if isinstance(accel, str) else accel.__name__
             n = self.levels[0].A.shape[0]
             b1 = np.ascontiguousarray(np.ravel(b), dtype=np.float64)
             x1 = np.zeros(n) if x0 is None else np.ascontiguousarray(np.ravel(np.array(x0)), dtype=np.float64)

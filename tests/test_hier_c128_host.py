@@ -151,6 +151,37 @@ def test_real_A_complex_b_refused(no_device):
         ml.solve(np.ones(64, dtype=np.complex128))
 
 
+def _fake_cuda_vector():
+    torch = pytest.importorskip("torch")
+
+    class FakeCuda(object):           # what solve() sees of a CUDA tensor; no device is touched
+        is_cuda = True
+        dtype = torch.float64
+
+        def data_ptr(self):
+            return 0
+    return FakeCuda()
+
+
+@pytest.mark.parametrize("call", ["solve_f64", "solve_c128", "solve_accel", "solve_many", "cycle_complexity",
+                                  "device_tensor"])
+def test_unknown_cycle_name_is_one_message(no_device, monkeypatch, call):
+    """every entry that takes a cycle name upper-cases it and refuses an unknown one with the same TypeError, before
+    any device work"""
+    from pyamg_amd import multilevel
+    monkeypatch.setattr(multilevel._DeviceHierarchyMulti, "__init__", multilevel._DeviceHierarchy.__init__)
+    real = _ml(A=sps.diags([-np.ones(63), 2 * np.ones(64), -np.ones(63)], [-1, 0, 1], format="csr"))
+    calls = {"solve_f64": lambda: real.solve(np.ones(64), cycle="z"),
+             "solve_c128": lambda: _ml().solve(np.ones(64, dtype=np.complex128), cycle="z"),
+             "solve_accel": lambda: real.solve(np.ones(64), cycle="z", accel="cg"),
+             "solve_many": lambda: real.solve_many(np.ones((64, 2)), cycle="z"),
+             "cycle_complexity": lambda: real.cycle_complexity("z"),
+             "device_tensor": lambda: real.solve(_fake_cuda_vector(), cycle="z")}
+    with pytest.raises(TypeError) as err:
+        calls[call]()
+    assert str(err.value) == "Unrecognized cycle type (Z)"
+
+
 def test_change_smoothers_keeps_complex_descriptors():
     import pyamg_amd
     ml = _ml()
