@@ -762,6 +762,29 @@ int amg_classical_level_device(int n, const int *Ap, const int *Aj, const double
                                const double *r, amg_classical **out, long *sizes, int *rounds, double *times_ms);
 int amg_classical_level_fetch(amg_classical *h, int *splitting, int *Pp, int *Pj, double *Px, int *Sp, int *Sj, double *Sx,
                               double *times_ms);
+/* The same level with the interpolation chosen: interpolation 0 is direct interpolation (amg_classical_level_device is this
+ * entry with 0, 0), 1 is extended+i (below) on the pattern of S in the order the strength stage stored it, whatever
+ * `reversed` says, truncated to max_per_row entries per row where that is > 0.  With extended+i a column stored twice in a
+ * row of A is AMG_EINVAL before any launch.  The result is fetched with amg_classical_level_fetch. */
+int amg_classical_level_build(int n, const int *Ap, const int *Aj, const double *Ax, double theta, int kind, int reversed,
+                              const double *r, int interpolation, int max_per_row, amg_classical **out, long *sizes, int *rounds,
+                              double *times_ms);
+
+/* Extended+i (distance-two) interpolation (csrc/split.hip) from a float64 CSR operator A, the
+ * pattern of a strength matrix S of A's shape and a C/F splitting (1 = C, 0 = F), all on the host with 32-bit offsets;
+ * rows in any stored order.  An F row interpolates from C_hat, its strong C neighbours and those of its strong F
+ * neighbours, with the sign-filtered row sums of section 8j; every sum in the order stated there, so the result has the
+ * bits of the host route (amgsetup_extended_interpolation_*).  max_per_row > 0: rows of more finite entries keep the
+ * max_per_row of largest magnitude (ties: the smaller column), rescaled to the row sum; 0: no truncation.  On return Pp
+ * (n + 1 offsets) is filled and *out holds the columns (coarse numbering, ascending per row) and values;
+ * amg_extended_interpolation_fetch copies them (Pp[n] each) to the host and releases the result, also when it fails.
+ * Offsets that do not start at 0 or decrease, a column outside the matrix, a column stored twice in a row of A or S,
+ * a splitting value other than 0 and 1 and a negative max_per_row are AMG_EINVAL before any launch, with Pp untouched.
+ * times_ms (or NULL): milliseconds of the upload [0] and of the stages [1]. */
+typedef struct amg_interpolation amg_interpolation;
+int amg_extended_interpolation_device(int n, const int *Ap, const int *Aj, const double *Ax, const int *Sp, const int *Sj,
+                                      const int *splitting, int max_per_row, int *Pp, amg_interpolation **out, double *times_ms);
+int amg_extended_interpolation_fetch(amg_interpolation *h, int *Pj, double *Px);
 
 /* ------------------------------------------------------------------------ */
 /* 5. Resident hierarchies of other value types: the cycle of section 2      */

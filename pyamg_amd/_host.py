@@ -77,6 +77,9 @@ def _signatures():
         "amgsetup_rs_cf_splitting": (None, [I, i, i, i, i, i]),
         "amgsetup_rs_direct_interpolation_pass1": (I, [I, i, i, i, i]),
         "amgsetup_rs_direct_interpolation_pass2": (None, [I, i, i, d, i, i, d, i, i, i, d]),
+        "amgsetup_extended_interpolation_count": (I, [I, i, i, i, i]),
+        "amgsetup_extended_interpolation_fill": (None, [I, i, i, d, i, i, i, i, i, d]),
+        "amgsetup_truncate_interpolation": (I, [I, I, i, i, d, i, i, d]),
         # the thread team
         "amgsetup_num_threads": (I, []),
         "amgsetup_set_num_threads": (None, [I]),

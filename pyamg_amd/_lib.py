@@ -205,6 +205,9 @@ def lib():
         "amg_cljp_device": [I, V, V, V, V, V, V, c_int_p, c_dbl_p],
         "amg_classical_level_device": [I, V, V, V, D, I, I, V, C.POINTER(C.c_void_p), C.POINTER(C.c_long), c_int_p, c_dbl_p],
         "amg_classical_level_fetch": [V, V, V, V, V, V, V, V, c_dbl_p],
+        "amg_classical_level_build": [I, V, V, V, D, I, I, V, I, I, C.POINTER(C.c_void_p), C.POINTER(C.c_long), c_int_p, c_dbl_p],
+        "amg_extended_interpolation_device": [I, V, V, V, V, V, V, I, V, C.POINTER(C.c_void_p), c_dbl_p],
+        "amg_extended_interpolation_fetch": [V, V, V],
         "amg_hierx_create": [I, I, I, C.POINTER(C.c_void_p)],
         "amg_hierx_set_matrix": [V, I, I, I, I, I, I, I, V, V, V],
         "amg_hierx_set_smoother": [V, I, I, C.POINTER(SmootherDescX)],

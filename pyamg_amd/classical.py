@@ -1,6 +1,13 @@
 """Classical (Ruge-Stuben) AMG setup -- restates pyamg/classical/classical.py:22-188 and pyamg/classical/split.py of
-the reference: classical strength (theta) -> C/F splitting -> direct interpolation -> R = P^T -> Galerkin R*A*P.
+the reference: classical strength (theta) -> C/F splitting -> interpolation -> R = P^T -> Galerkin R*A*P.
 Returns a pyamg_amd.multilevel_solver.
+
+Interpolation is the reference's direct interpolation or, beyond the reference, extended+i (``extended_interpolation``,
+``ruge_stuben_solver(..., interpolation='extended_i')``): the distance-two formula of De Sterck, Falgout, Nolting and
+Yang (2008, eq. 4.10) with BoomerAMG's sign filter, optionally truncated to ``max_per_row`` entries per row.  It is
+what PMIS needs: an F row without a strong C neighbour interpolates from the C neighbours of its strong F neighbours.
+Its arithmetic is DESIGN.md section 8j, and its host route (csrc/setup_host.cpp) and device route (csrc/split.hip)
+return the same bits for an operator and a strength matrix stored in any row order without duplicate columns.
 
 C/F splittings (1 = C, 0 = F): ``RS`` (first pass of Ruge-Stuben, sequential by construction, host only) and the
 reference's parallel coarsenings ``PMIS``, ``PMISc``, ``CLJP`` and ``CLJPc``, each by one of two routes that return the
@@ -12,8 +19,8 @@ same integers:
 Classical strength and direct interpolation have the same two routes with the same bits (csrc/split.hip, DESIGN.md
 section 8i); their device route takes A as canonical CSR (sorted rows, no duplicate columns, no stored zeros, finite
 values).  ``ruge_stuben_solver(..., device=True)`` builds a level with classical strength and ``CF`` 'PMIS' or 'CLJP'
-in HBM from one upload of A (strength, graph, weights, splitting, interpolation); with another ``CF`` strength and
-interpolation take their device routes one by one.  R = P^T and the Galerkin product run on the host.
+in HBM from one upload of A (strength, graph, weights, splitting, either interpolation); with another ``CF`` strength
+and interpolation take their device routes one by one.  R = P^T and the Galerkin product run on the host.
 
 ``device=True`` takes the device route and raises NotImplementedError for what it cannot take (a sweep limit, a
 structurally unsymmetric graph); ``device=False`` is the host route; ``device=None`` is the host route unless
@@ -37,7 +44,7 @@ from .multilevel import multilevel_solver
 from .smoothing import change_smoothers
 
 __all__ = ["ruge_stuben_solver", "classical_strength_of_connection", "RS", "direct_interpolation",
-           "PMIS", "PMISc", "CLJP", "CLJPc", "MIS", "preprocess"]
+           "extended_interpolation", "PMIS", "PMISc", "CLJP", "CLJPc", "MIS", "preprocess"]
 
 # What device=None does when a GPU is present: the host route.  profiles/r16_splitting.txt did not justify the device
 # route of a splitting alone; profiles/r17_classical_level.txt would justify the chained level
@@ -338,17 +345,116 @@ def direct_interpolation(A, Cm, splitting, device=None):
     return _interpolation(A, Cm, splitting, device)
 
 
+def _extended_arguments(A, Cm, splitting, max_per_row):
+    """the checks both routes of extended+i make -> (n, Ap, Aj, Ax, Sp, Sj, splitting, q); q: 0 without truncation"""
+    if not isspmatrix_csr(A):
+        raise TypeError("expected csr_matrix for A")
+    if not isspmatrix_csr(Cm):
+        raise TypeError("expected csr_matrix for C")
+    if A.shape[0] != A.shape[1] or Cm.shape != A.shape:
+        raise ValueError("expected a square operator and a strength matrix of its shape")
+    n = A.shape[0]
+    splitting = _i32(splitting)
+    if splitting.shape != (n,):
+        raise ValueError("expected one splitting value per row")
+    if np.any((splitting != 0) & (splitting != 1)):
+        raise ValueError("expected a splitting of 0 (F) and 1 (C)")
+    if max_per_row is not None and max_per_row < 1:
+        raise ValueError("expected max_per_row >= 1")
+    for M, what in ((A, "A"), (Cm, "C")):
+        if M.nnz >= 2 ** 31:
+            raise ValueError("expected fewer than 2^31 entries in %s" % what)
+        if not _sorted_unique_rows(M):
+            keys = np.sort(_entry_keys(M))
+            if np.any(keys[1:] == keys[:-1]):
+                raise ValueError("duplicated columns in a row of %s" % what)
+    return (n, _i32(A.indptr), _i32(A.indices), np.ascontiguousarray(A.data, dtype=np.float64), _i32(Cm.indptr), _i32(Cm.indices),
+            splitting, 0 if max_per_row is None else int(max_per_row))
+
+
+def _extended_host(n, Ap, Aj, Ax, Sp, Sj, splitting, q):
+    L = host_lib()
+    Pp = np.empty(n + 1, dtype=np.intc)
+    nnz = L.amgsetup_extended_interpolation_count(n, _ip(Sp), _ip(Sj), _ip(splitting), _ip(Pp))
+    if nnz < 0:
+        raise ValueError("the prolongator would hold 2^31 entries or more")
+    Pj = np.empty(nnz, dtype=np.intc)
+    Px = np.empty(nnz, dtype=np.float64)
+    L.amgsetup_extended_interpolation_fill(n, _ip(Ap), _ip(Aj), _dp(Ax), _ip(Sp), _ip(Sj), _ip(splitting), _ip(Pp), _ip(Pj), _dp(Px))
+    if q:
+        Tp, Tj, Tx = np.empty_like(Pp), np.empty_like(Pj), np.empty_like(Px)
+        kept = L.amgsetup_truncate_interpolation(n, q, _ip(Pp), _ip(Pj), _dp(Px), _ip(Tp), _ip(Tj), _dp(Tx))
+        Pp, Pj, Px = Tp, Tj[:kept].copy(), Tx[:kept].copy()
+    return Pp, Pj, Px
+
+
+def _extended_device(n, Ap, Aj, Ax, Sp, Sj, splitting, q, times=None):
+    """amg_extended_interpolation_device and its fetch.  times: a list that receives (upload, stages, fetch) in
+    milliseconds."""
+    import time
+
+    from . import _lib
+    handle = C.c_void_p()
+    ms = (C.c_double * 2)()
+    Pp = np.empty(n + 1, dtype=np.intc)
+    _lib.check(_lib.lib().amg_extended_interpolation_device(n, Ap.ctypes.data, Aj.ctypes.data, Ax.ctypes.data, Sp.ctypes.data,
+                                                            Sj.ctypes.data, splitting.ctypes.data, q, Pp.ctypes.data, C.byref(handle), ms))
+    t0 = time.perf_counter()
+    try:
+        Pj = np.empty(int(Pp[-1]), dtype=np.intc)
+        Px = np.empty(int(Pp[-1]), dtype=np.float64)
+    except BaseException:
+        _lib.lib().amg_extended_interpolation_fetch(handle, None, None)     # releases the result
+        raise
+    _lib.check(_lib.lib().amg_extended_interpolation_fetch(handle, Pj.ctypes.data, Px.ctypes.data))
+    if times is not None:
+        times.extend([ms[0], ms[1], (time.perf_counter() - t0) * 1e3])
+    return Pp, Pj, Px
+
+
+def _extended(A, Cm, splitting, max_per_row=None, device=None):
+    args = _extended_arguments(A, Cm, splitting, max_per_row)
+    Pp, Pj, Px = attempt(route(device, DEVICE_AUTO), lambda: _extended_device(*args), lambda: _extended_host(*args))
+    return csr_matrix((Px, Pj, Pp), shape=(args[0], int(args[6].sum())))
+
+
+def extended_interpolation(A, Cm, splitting, max_per_row=None, device=None):
+    """Extended+i (distance-two) interpolation, DESIGN.md section 8j: an F row interpolates from its strong C neighbours
+    and from those of its strong F neighbours.  Only the pattern of Cm is used; rows of A and Cm in any stored order,
+    without duplicate columns.  max_per_row: keep that many entries of largest magnitude per row, rescaled to the
+    row's sum.  device: where the passes run (module docstring); both routes return the same bits."""
+    return _extended(A, Cm, splitting, max_per_row, device)
+
+
+_INTERPOLATIONS = {"direct": 0, "extended_i": 1}
+
+
+def _interpolation_choice(interpolation):
+    """'direct', 'extended_i' or ('extended_i', {'max_per_row': q}) -> (name, max_per_row or None)"""
+    name, kwargs = unpack_arg(interpolation)
+    if not isinstance(name, str) or name not in _INTERPOLATIONS:
+        raise NotImplementedError("interpolation=%r is outside the restated setup" % (name,))
+    if set(kwargs) - ({"max_per_row"} if name == "extended_i" else set()):
+        raise TypeError("unexpected arguments for %s interpolation: %s" % (name, sorted(kwargs)))
+    q = kwargs.get("max_per_row")
+    if q is not None and q < 1:
+        raise ValueError("expected max_per_row >= 1")
+    return name, q
+
+
 _CHAINED_SPLITTINGS = {"PMIS": 0, "CLJP": 1}
 LEVEL_STAGES = ("upload", "strength", "graph", "splitting", "interpolation", "fetch")
 
 
-def classical_level_device(A, theta, CF, keep=False, times=None, product_order=False):
-    """One level in HBM from one upload of A (amg_classical_level_device): classical strength, the strength graph and
-    its transpose, the start weights, the PMIS or CLJP splitting and direct interpolation.  Returns (splitting, P, S);
+def classical_level_device(A, theta, CF, keep=False, times=None, product_order=False, interpolation="direct"):
+    """One level in HBM from one upload of A (amg_classical_level_build): classical strength, the strength graph and
+    its transpose, the start weights, the PMIS or CLJP splitting and the interpolation chosen (ruge_stuben_solver's
+    ``interpolation``).  Returns (splitting, P, S);
     S, the scaled strength matrix, only with keep (None otherwise).  The random start values are drawn on the host
     where the host route draws them: rand(n) of the global numpy RNG for PMIS, glibc rand() after srand(2448422) for
     CLJP.  times: a list that receives the milliseconds of LEVEL_STAGES.  product_order: _operator_order."""
     from . import _lib
+    name, q = _interpolation_choice(interpolation)
     reverse = _operator_order(A, "the device route of a classical level", product_order)
     if theta < 0 or theta > 1:
         raise ValueError("expected theta in [0,1]")
@@ -365,8 +471,9 @@ def classical_level_device(A, theta, CF, keep=False, times=None, product_order=F
     handle = C.c_void_p()
     sizes = (C.c_long * 2)()
     ms = (C.c_double * 6)()
-    _lib.check(_lib.lib().amg_classical_level_device(n, Ap.ctypes.data, Aj.ctypes.data, Ax.ctypes.data, float(theta), kind,
-                                                     int(reverse), r.ctypes.data, C.byref(handle), sizes, None, ms))
+    _lib.check(_lib.lib().amg_classical_level_build(n, Ap.ctypes.data, Aj.ctypes.data, Ax.ctypes.data, float(theta), kind,
+                                                    int(reverse), r.ctypes.data, _INTERPOLATIONS[name], q or 0, C.byref(handle),
+                                                    sizes, None, ms))
     ptr = lambda a: None if a is None else a.ctypes.data
     try:
         splitting = np.empty(n, dtype=np.intc)
@@ -386,7 +493,8 @@ def classical_level_device(A, theta, CF, keep=False, times=None, product_order=F
     if times is not None:
         times.extend(ms[k] for k in range(6))
     S = csr_matrix((Sx, Sj, Sp), shape=A.shape) if keep else None
-    return splitting, csr_matrix((Px, Pj, Pp)), S
+    shape = None if name == "direct" else (n, int(splitting.sum()))
+    return splitting, csr_matrix((Px, Pj, Pp), shape=shape), S
 
 
 _PARALLEL_SPLITTINGS = {"PMIS": PMIS, "PMISc": PMISc, "CLJP": CLJP, "CLJPc": CLJPc}
@@ -401,14 +509,17 @@ def unpack_arg(v):
 def ruge_stuben_solver(A, strength=("classical", {"theta": 0.25}), CF="RS",
                        presmoother=("gauss_seidel", {"sweep": "symmetric"}),
                        postsmoother=("gauss_seidel", {"sweep": "symmetric"}),
-                       max_levels=10, max_coarse=500, keep=False, device=None, **kwargs):
+                       max_levels=10, max_coarse=500, keep=False, device=None, interpolation="direct", **kwargs):
     """Create a multilevel solver using Classical AMG (pyamg/classical/classical.py:22-116)
 
     CF : 'RS', 'PMIS', 'PMISc', 'CLJP' or 'CLJPc', or (name, {'device': True | False | None}) for the four parallel
     coarsenings: where their selection loop runs (module docstring).  PMIS and PMISc draw the global numpy RNG once
     per level.
-    device : where classical strength and direct interpolation run, and with CF 'PMIS' or 'CLJP' the whole level
-    (module docstring); every route builds the same hierarchy."""
+    device : where classical strength and interpolation run, and with CF 'PMIS' or 'CLJP' the whole level
+    (module docstring); every route builds the same hierarchy.
+    interpolation : 'direct' (the reference's), 'extended_i' or ('extended_i', {'max_per_row': q})
+    (extended_interpolation); another name raises NotImplementedError before a level is built."""
+    _interpolation_choice(interpolation)
     levels = [multilevel_solver.level()]
     if not isspmatrix_csr(A):
         try:
@@ -421,13 +532,13 @@ def ruge_stuben_solver(A, strength=("classical", {"theta": 0.25}), CF="RS",
         raise ValueError("expected square matrix")
     levels[-1].A = A
     while len(levels) < max_levels and levels[-1].A.shape[0] > max_coarse:
-        extend_hierarchy(levels, strength, CF, keep, device)
+        extend_hierarchy(levels, strength, CF, keep, device, interpolation)
     ml = multilevel_solver(levels, **kwargs)
     change_smoothers(ml, presmoother, postsmoother)
     return ml
 
 
-def _stages(A, strength, CF, device):
+def _stages(A, strength, CF, device, interpolation="direct"):
     """strength, splitting and interpolation one by one -> (C, splitting, P)"""
     fn, kwargs = unpack_arg(strength)
     if fn == "symmetric":
@@ -445,10 +556,13 @@ def _stages(A, strength, CF, device):
         splitting = _PARALLEL_SPLITTINGS[fn](Cm, **kwargs)
     else:
         raise NotImplementedError("C/F splitting %r is outside the restated setup" % (fn,))
-    return Cm, splitting, _interpolation(A, Cm, splitting, device, product_order=True)
+    name, q = _interpolation_choice(interpolation)
+    if name == "direct":
+        return Cm, splitting, _interpolation(A, Cm, splitting, device, product_order=True)
+    return Cm, splitting, _extended(A, Cm, splitting, q, device)
 
 
-def _chained(A, strength, CF, keep):
+def _chained(A, strength, CF, keep, interpolation="direct"):
     """the level in HBM where strength is classical with theta alone and CF is PMIS or CLJP not sent to the host;
     None otherwise"""
     fn, kwargs = unpack_arg(strength)
@@ -457,20 +571,21 @@ def _chained(A, strength, CF, keep):
         return None
     if set(cf_kwargs) - {"device"} or cf_kwargs.get("device", True) is False:
         return None
-    splitting, P, S = classical_level_device(A, kwargs.get("theta", 0.0), name, keep=keep, product_order=True)
+    splitting, P, S = classical_level_device(A, kwargs.get("theta", 0.0), name, keep=keep, product_order=True,
+                                             interpolation=interpolation)
     return S, splitting, P
 
 
-def extend_hierarchy(levels, strength, CF, keep, device=None):
+def extend_hierarchy(levels, strength, CF, keep, device=None, interpolation="direct"):
     """classical.py:120-188"""
     A = levels[-1].A
     way = route(device, DEVICE_AUTO)
 
     def on_device():
-        built = _chained(A, strength, CF, keep)
-        return built if built is not None else _stages(A, strength, CF, way)
+        built = _chained(A, strength, CF, keep, interpolation)
+        return built if built is not None else _stages(A, strength, CF, way, interpolation)
 
-    Cm, splitting, P = attempt(way, on_device, lambda: _stages(A, strength, CF, False))
+    Cm, splitting, P = attempt(way, on_device, lambda: _stages(A, strength, CF, False, interpolation))
     R = P.T.tocsr()
     if keep:
         levels[-1].C = Cm

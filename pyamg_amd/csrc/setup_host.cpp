@@ -1873,3 +1873,185 @@ void amgsetup_truncate_rows_csr(int n_row, int k, const int *Sp, int *Sj, double
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------- extended+i interpolation
+// Distance-two interpolation for an F row i: C_hat = the strong C neighbours of i and of its strong F neighbours,
+// ascending; every sum of section 8j in its stated order.  Only S's pattern is read; rows of A and S in any stored
+// order, no duplicate columns.  stamp[l] == i marks the members of C_hat (C points, slot[l] their position) and of
+// Fs_i (F points) alike: a point is one or the other.
+namespace {
+
+inline double sign_filtered(double akk, double v) { return ((akk >= 0 && v < 0) || (akk < 0 && v > 0)) ? v : 0.0; }
+
+struct ExtendedRow {
+    std::vector<int> stamp, slot, chat;
+    std::vector<double> w;
+    explicit ExtendedRow(int n) : stamp((size_t)n, -1), slot((size_t)n, 0) {}
+
+    // C_hat of F row i, sorted, with stamp and slot set
+    void sets(int i, const int *Sp, const int *Sj, const int *splitting)
+    {
+        chat.clear();
+        auto add = [&](int c) {
+            if (stamp[(size_t)c] != i) { stamp[(size_t)c] = i; chat.push_back(c); }
+        };
+        for (int jj = Sp[i]; jj < Sp[i + 1]; ++jj) {
+            const int j = Sj[jj];
+            if (j == i) continue;
+            if (splitting[j] == 1) { add(j); continue; }
+            stamp[(size_t)j] = i;
+            for (int kk = Sp[j]; kk < Sp[j + 1]; ++kk)
+                if (splitting[Sj[kk]] == 1) add(Sj[kk]);
+        }
+        std::sort(chat.begin(), chat.end());
+        for (size_t t = 0; t < chat.size(); ++t) slot[(size_t)chat[t]] = (int)t;
+    }
+};
+
+}   // namespace
+
+extern "C" {
+
+// count pass: Pp (n + 1 offsets): one entry for a C row, |C_hat| for an F row.  Returns the last offset, -1 when it
+// leaves an int.
+int amgsetup_extended_interpolation_count(int n, const int *Sp, const int *Sj, const int *splitting, int *Pp)
+{
+    Pp[0] = 0;
+#pragma omp parallel
+    {
+        ExtendedRow row(n);
+#pragma omp for schedule(dynamic, 256)
+        for (int i = 0; i < n; ++i) {
+            if (splitting[i] == 1) { Pp[i + 1] = 1; continue; }
+            row.sets(i, Sp, Sj, splitting);
+            Pp[i + 1] = (int)row.chat.size();
+        }
+    }
+    long sum = 0;
+    for (int i = 0; i < n; ++i) {
+        sum += Pp[i + 1];
+        if (sum > 0x7fffffffL) return -1;
+        Pp[i + 1] = (int)sum;
+    }
+    return (int)sum;
+}
+
+// fill pass: Pj (coarse numbering, ascending) and Px from Pp[i] on
+void amgsetup_extended_interpolation_fill(int n, const int *Ap, const int *Aj, const double *Ax, const int *Sp, const int *Sj,
+                                          const int *splitting, const int *Pp, int *Pj, double *Px)
+{
+    std::vector<int> coarse((size_t)n);
+    std::vector<double> diag((size_t)n, 0.0);
+    for (int i = 0, sum = 0; i < n; ++i) { coarse[(size_t)i] = sum; sum += splitting[i]; }
+#pragma omp parallel for schedule(static)
+    for (int i = 0; i < n; ++i)
+        for (int jj = Ap[i]; jj < Ap[i + 1]; ++jj)
+            if (Aj[jj] == i) { diag[(size_t)i] = Ax[jj]; break; }
+#pragma omp parallel
+    {
+        ExtendedRow row(n);
+        std::vector<int> &stamp = row.stamp, &slot = row.slot;
+        std::vector<double> &w = row.w;
+#pragma omp for schedule(dynamic, 256)
+        for (int i = 0; i < n; ++i) {
+            const int at = Pp[i];
+            if (splitting[i] == 1) { Pj[at] = coarse[(size_t)i]; Px[at] = 1.0; continue; }
+            row.sets(i, Sp, Sj, splitting);
+            const size_t m = row.chat.size();
+            if (m == 0) continue;
+            w.assign(m, 0.0);
+            double D = diag[(size_t)i];
+            for (int jj = Ap[i]; jj < Ap[i + 1]; ++jj) {
+                const int j = Aj[jj];
+                if (j == i) continue;
+                if (stamp[(size_t)j] != i) D += Ax[jj];
+                else if (splitting[j] == 1) w[(size_t)slot[(size_t)j]] = Ax[jj];
+            }
+            for (int jj = Sp[i]; jj < Sp[i + 1]; ++jj) {
+                const int k = Sj[jj];
+                if (k == i || splitting[k] == 1) continue;
+                double a = 0.0;
+                for (int e = Ap[i]; e < Ap[i + 1]; ++e)
+                    if (Aj[e] == k) { a = Ax[e]; break; }
+                const double akk = diag[(size_t)k];
+                double d = 0.0;
+                for (int e = Ap[k]; e < Ap[k + 1]; ++e) {
+                    const int l = Aj[e];
+                    if (l == i || (splitting[l] == 1 && stamp[(size_t)l] == i)) {
+                        const double b = sign_filtered(akk, Ax[e]);
+                        if (b != 0.0) d += b;
+                    }
+                }
+                if (d == 0.0) { D += a; continue; }
+                for (int e = Ap[k]; e < Ap[k + 1]; ++e) {
+                    const double v = Ax[e];
+                    if (sign_filtered(akk, v) == 0.0) continue;
+                    const int l = Aj[e];
+                    const double c = (a * v) / d;
+                    if (l == i) D += c;
+                    else if (splitting[l] == 1 && stamp[(size_t)l] == i) w[(size_t)slot[(size_t)l]] += c;
+                }
+            }
+            for (size_t t = 0; t < m; ++t) {
+                Pj[(size_t)at + t] = coarse[(size_t)row.chat[t]];
+                Px[(size_t)at + t] = (-w[t]) / D;
+            }
+        }
+    }
+}
+
+// Truncation of the rows of a prolongator with sorted rows to the q entries of largest magnitude (ties: the smaller
+// column), rescaled by sum(all) / sum(kept); rows of at most q entries and rows with a non-finite value stay.  Tp: n + 1
+// offsets; Tj, Tx: as long as Pj, Px.  Returns the entries written.
+namespace {
+inline bool truncation_keeps(const double *x, int m, int t, int q)
+{
+    const double mag = std::fabs(x[t]);
+    int rank = 0;
+    for (int u = 0; u < m; ++u) {
+        const double other = std::fabs(x[u]);
+        rank += (other > mag || (other == mag && u < t)) ? 1 : 0;
+    }
+    return rank < q;
+}
+inline bool truncation_applies(const double *x, int m, int q)
+{
+    if (m <= q) return false;
+    for (int u = 0; u < m; ++u)
+        if (!std::isfinite(x[u])) return false;
+    return true;
+}
+}   // namespace
+
+int amgsetup_truncate_interpolation(int n, int q, const int *Pp, const int *Pj, const double *Px, int *Tp, int *Tj, double *Tx)
+{
+    Tp[0] = 0;
+#pragma omp parallel for schedule(dynamic, 256)
+    for (int i = 0; i < n; ++i) {
+        const int m = Pp[i + 1] - Pp[i];
+        Tp[i + 1] = truncation_applies(Px + Pp[i], m, q) ? q : m;
+    }
+    for (int i = 0; i < n; ++i) Tp[i + 1] += Tp[i];
+#pragma omp parallel for schedule(dynamic, 256)
+    for (int i = 0; i < n; ++i) {
+        const int m = Pp[i + 1] - Pp[i];
+        const int *j = Pj + Pp[i];
+        const double *x = Px + Pp[i];
+        int at = Tp[i];
+        if (Tp[i + 1] - at == m) {
+            for (int t = 0; t < m; ++t, ++at) { Tj[at] = j[t]; Tx[at] = x[t]; }
+            continue;
+        }
+        double s_all = 0.0, s_kept = 0.0;
+        for (int t = 0; t < m; ++t) s_all += x[t];
+        for (int t = 0; t < m; ++t)
+            if (truncation_keeps(x, m, t, q)) { Tj[at] = j[t]; Tx[at] = x[t]; s_kept += x[t]; ++at; }
+        if (s_kept != 0.0) {
+            const double scale = s_all / s_kept;
+            for (int e = Tp[i]; e < Tp[i + 1]; ++e) Tx[e] *= scale;
+        }
+    }
+    return Tp[n];
+}
+
+}  // extern "C"

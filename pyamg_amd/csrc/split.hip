@@ -3,8 +3,9 @@
 // (amg_core/ruge_stuben.h:373-478).  Both return the integers of the reference's sequential sweeps (DESIGN.md
 // section 8h): every decision below is a function of the state at a kernel boundary, or is one that a stale read can
 // only postpone.  State arrays hold one int per vertex; offsets are widened to 64 bits inside the kernels.
-// Below them, the stages that turn a splitting into a level: classical strength, direct interpolation and the level
-// chained in HBM, which runs the two loops above on buffers its earlier stages left there.
+// Below them, the stages that turn a splitting into a level: classical strength, direct and extended+i interpolation
+//  and the level chained in HBM, which runs the two loops above on buffers its earlier stages
+// left there.
 #include "flat.hpp"
 
 #include <rocprim/device/device_scan.hpp>
@@ -335,6 +336,7 @@ int amg_cljp_device(int n, const int *Sp, const int *Sj, const int *Tp, const in
 namespace {
 
 enum { KIND_PMIS = 0, KIND_CLJP = 1 };
+enum { INTERP_DIRECT = 0, INTERP_EXTENDED_I = 1 };
 
 // std::max(m, |a|) from numeric_limits<double>::min() over a row, the entries of column `skip` left out: a NaN never
 // replaces the maximum (m < NaN is false)
@@ -648,7 +650,400 @@ int interpolation_fill_device(int n, const HbmCsr &A, const int *Sp, const int *
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------ extended+i
+// Distance-two interpolation.  A wave owns an F row i.  Its candidates -- row i of S and the rows
+// of S of its strong F neighbours, one slot per stored entry, a slot that holds no C point set to NO_POINT -- are
+// gathered into LDS (up to EXT_CAP slots) or into the row's segment of a workspace in HBM (more), duplicates struck
+// out and the rest ranked into the ascending list C_hat.  Every sum the definition orders is a wave-uniform register
+// that takes its addends in lane order, a chunk of 64 stored entries at a time; w lives beside C_hat, one slot per
+// member, and a strong F neighbour touches each slot at most once (no duplicate columns), the neighbours one after
+// the other.  Lanes of a wave run in lockstep and their LDS and memory operations complete in program order, so a
+// wavefront fence and barrier is all that separates a phase that writes the row's slots from one that reads them.
+constexpr int WAVE = 64, EXT_ROWS = TB / WAVE, EXT_CAP = 256, NO_POINT = 0x7fffffff;
+
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// acc + v of every flagged lane, in lane order; the same value in every lane
+__device__ __forceinline__ double ordered_add(double acc, double v, bool flag)
+{
+    unsigned long long mask = __ballot(flag);
+    while (mask) {
+        acc += __shfl(v, __ffsll((long long)mask) - 1);
+        mask &= mask - 1;
+    }
+    return acc;
+}
+
+// the stored entry of column col in entries [lo, hi), 0.0 where there is none; the same value in every lane
+__device__ __forceinline__ double wave_lookup(const int *Aj, const double *Ax, long lo, long hi, int col, int lane)
+{
+    for (long base = lo; base < hi; base += WAVE) {
+        const long e = base + lane;
+        const bool hit = e < hi && Aj[e] == col;
+        const double x = hit ? Ax[e] : 0.0;
+        const unsigned long long mask = __ballot(hit);
+        if (mask) return __shfl(x, __ffsll((long long)mask) - 1);
+    }
+    return 0.0;
+}
+
+// position of col in the ascending list cs[0, m), -1 where it is not there
+__device__ __forceinline__ int list_find(const int *cs, int m, int col)
+{
+    int lo = 0, hi = m;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (cs[mid] < col) lo = mid + 1; else hi = mid;
+    }
+    return (lo < m && cs[lo] == col) ? lo : -1;
+}
+
+__device__ __forceinline__ double sign_filtered(double akk, double v) { return ((akk >= 0 && v < 0) || (akk < 0 && v > 0)) ? v : 0.0; }
+
+// The slots of F row i (its bound): |row i of S| + the rows of S of its strong F neighbours.  big[i]: the bound where
+// it exceeds EXT_CAP, 0 otherwise; its scan places the workspace segments.
+__global__ __launch_bounds__(TB) void extended_bound_kernel(int n, const int *Sp, const int *Sj, const int *splitting, long *big)
+{
+    const int i = blockIdx.x * TB + threadIdx.x;
+    if (i > n) return;
+    long slots = 0;
+    if (i < n && splitting[i] != C_NODE) {
+        const long lo = Sp[i], hi = Sp[i + 1];
+        slots = hi - lo;
+        for (long jj = lo; jj < hi; ++jj) {
+            const int k = Sj[jj];
+            if (k != i && splitting[k] != C_NODE) slots += (long)Sp[k + 1] - Sp[k];
+        }
+    }
+    big[i] = slots > EXT_CAP ? slots : 0;
+}
+
+// gather and strike out: on return cand[0, slots) holds every member of C_hat once and NO_POINT elsewhere.  A slot is
+// struck out when an earlier slot holds its value; the first slot of a value is never written, so a reader that meets a
+// slot before or after it was struck out decides the same (relaxed accesses, as in Luby's rounds above).
+__device__ __forceinline__ long extended_candidates(int i, const int *Sp, const int *Sj, const int *splitting, int *cand, int lane)
+{
+    const long lo = Sp[i], hi = Sp[i + 1];
+    for (long e = lo + lane; e < hi; e += WAVE) {
+        const int j = Sj[e];
+        cand[e - lo] = (j != i && splitting[j] == C_NODE) ? j : NO_POINT;
+    }
+    long slots = hi - lo;
+    for (long jj = lo; jj < hi; ++jj) {
+        const int k = Sj[jj];
+        if (k == i || splitting[k] == C_NODE) continue;
+        const long klo = Sp[k], khi = Sp[k + 1];
+        for (long e = klo + lane; e < khi; e += WAVE) {
+            const int c = Sj[e];
+            cand[slots + (e - klo)] = splitting[c] == C_NODE ? c : NO_POINT;
+        }
+        slots += khi - klo;
+    }
+    wave_sync();
+    for (long p = lane; p < slots; p += WAVE) {
+        const int v = peek(&cand[p]);
+        if (v == NO_POINT) continue;
+        for (long q = 0; q < p; ++q)
+            if (peek(&cand[q]) == v) { poke(&cand[p], NO_POINT); break; }
+    }
+    wave_sync();
+    return slots;
+}
+
+// count pass: |C_hat| of every F row, 1 for a C row, 0 for the scan's last addend; *total: their sum
+__global__ __launch_bounds__(TB) void extended_count_kernel(int n, const int *Sp, const int *Sj, const int *splitting, const long *Wp,
+                                                            int *wcand, int *count, unsigned long long *total)
+{
+    __shared__ int lds_cand[EXT_ROWS][EXT_CAP];
+    const int lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
+    const long row = (long)blockIdx.x * EXT_ROWS + wave;
+    if (row > n) return;
+    const int i = (int)row;
+    if (i == n || splitting[i] == C_NODE) {
+        if (lane == 0) {
+            count[i] = i < n ? 1 : 0;
+            if (i < n) atomicAdd(total, 1ULL);
+        }
+        return;
+    }
+    int *cand = Wp[i + 1] > Wp[i] ? wcand + Wp[i] : lds_cand[wave];
+    const long slots = extended_candidates(i, Sp, Sj, splitting, cand, lane);
+    int members = 0;
+    for (long base = 0; base < slots; base += WAVE) {
+        const long p = base + lane;
+        members += __popcll(__ballot(p < slots && cand[p] != NO_POINT));
+    }
+    if (lane == 0) {
+        count[i] = members;
+        atomicAdd(total, (unsigned long long)members);
+    }
+}
+
+__global__ __launch_bounds__(TB) void diagonal_kernel(int n, const int *Ap, const int *Aj, const double *Ax, double *diag)
+{
+    const int i = blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    double d = 0.0;
+    for (long jj = Ap[i], hi = Ap[i + 1]; jj < hi; ++jj)
+        if (Aj[jj] == i) { d = Ax[jj]; break; }
+    diag[i] = d;
+}
+
+// fill pass: the row's columns (coarse numbers, ascending) and values from Pp[i] on
+__global__ __launch_bounds__(TB) void extended_fill_kernel(int n, const int *Ap, const int *Aj, const double *Ax, const double *diag,
+                                                           const int *Sp, const int *Sj, const int *splitting, const int *coarse,
+                                                           const long *Wp, int *wcand, int *wlist, double *wsum, const int *Pp, int *Pj,
+                                                           double *Px)
+{
+    __shared__ int lds_cand[EXT_ROWS][EXT_CAP];
+    __shared__ int lds_list[EXT_ROWS][EXT_CAP];
+    __shared__ double lds_sum[EXT_ROWS][EXT_CAP];
+    const int lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
+    const long row = (long)blockIdx.x * EXT_ROWS + wave;
+    if (row >= n) return;
+    const int i = (int)row;
+    const long at = Pp[i];
+    if (splitting[i] == C_NODE) {
+        if (lane == 0) { Pj[at] = coarse[i]; Px[at] = 1.0; }
+        return;
+    }
+    const int m = Pp[i + 1] - Pp[i];
+    if (m == 0) return;
+    const bool wide = Wp[i + 1] > Wp[i];
+    int *cand = wide ? wcand + Wp[i] : lds_cand[wave];
+    int *cs = wide ? wlist + Wp[i] : lds_list[wave];
+    double *w = wide ? wsum + Wp[i] : lds_sum[wave];
+    const long slots = extended_candidates(i, Sp, Sj, splitting, cand, lane);
+    // C_hat: a member's position is the number of members below it
+    for (long p = lane; p < slots; p += WAVE) {
+        const int v = cand[p];
+        if (v == NO_POINT) continue;
+        int below = 0;
+        for (long q = 0; q < slots; ++q) below += cand[q] < v ? 1 : 0;
+        if (below < m) cs[below] = v;
+    }
+    wave_sync();
+    for (int t = lane; t < m; t += WAVE) {
+        w[t] = 0.0;
+        Pj[at + t] = coarse[cs[t]];
+    }
+    wave_sync();
+    // row i of A: step 1 of the weights, and what is neither interpolatory nor a strong F neighbour goes to D
+    const long alo = Ap[i], ahi = Ap[i + 1], slo = Sp[i], shi = Sp[i + 1];
+    double D = diag[i];
+    for (long base = alo; base < ahi; base += WAVE) {
+        const long e = base + lane;
+        bool lump = false;
+        double v = 0.0;
+        if (e < ahi && Aj[e] != i) {
+            const int j = Aj[e];
+            v = Ax[e];
+            if (splitting[j] == C_NODE) {
+                const int t = list_find(cs, m, j);
+                if (t >= 0) w[t] = v; else lump = true;
+            } else {
+                lump = true;
+                for (long jj = slo; jj < shi; ++jj)
+                    if (Sj[jj] == j) { lump = false; break; }
+            }
+        }
+        D = ordered_add(D, v, lump);
+    }
+    wave_sync();
+    // step 2: the strong F neighbours in S's stored order
+    for (long jj = slo; jj < shi; ++jj) {
+        const int k = Sj[jj];
+        if (k == i || splitting[k] == C_NODE) continue;
+        const double a = wave_lookup(Aj, Ax, alo, ahi, k, lane), akk = diag[k];
+        const long klo = Ap[k], khi = Ap[k + 1];
+        double d = 0.0;
+        for (long base = klo; base < khi; base += WAVE) {
+            const long e = base + lane;
+            bool take = false;
+            double v = 0.0;
+            if (e < khi) {
+                const int l = Aj[e];
+                v = Ax[e];
+                take = sign_filtered(akk, v) != 0.0 && (l == i || (splitting[l] == C_NODE && list_find(cs, m, l) >= 0));
+            }
+            d = ordered_add(d, v, take);
+        }
+        if (d == 0.0) { D += a; continue; }
+        for (long base = klo; base < khi; base += WAVE) {
+            const long e = base + lane;
+            bool to_D = false;
+            double c = 0.0;
+            if (e < khi && sign_filtered(akk, Ax[e]) != 0.0) {
+                const int l = Aj[e];
+                c = (a * Ax[e]) / d;
+                if (l == i) to_D = true;
+                else if (splitting[l] == C_NODE) {
+                    const int t = list_find(cs, m, l);
+                    if (t >= 0) w[t] += c;
+                }
+            }
+            D = ordered_add(D, c, to_D);
+        }
+        wave_sync();
+    }
+    for (int t = lane; t < m; t += WAVE) Px[at + t] = (-w[t]) / D;
+}
+
+// Truncation (section 8j): a row of more than q entries, all finite, keeps the q of largest magnitude (ties: the smaller
+// column) times sum(all) / sum(kept).  One lane per row; an entry's rank is counted, nothing is sorted or stored.
+__device__ __forceinline__ bool truncation_applies(const double *x, int m, int q)
+{
+    if (m <= q) return false;
+    for (int u = 0; u < m; ++u)
+        if (!isfinite(x[u])) return false;
+    return true;
+}
+
+__device__ __forceinline__ bool truncation_keeps(const double *x, int m, int t, int q)
+{
+    const double mag = fabs(x[t]);
+    int rank = 0;
+    for (int u = 0; u < m; ++u) {
+        const double other = fabs(x[u]);
+        rank += (other > mag || (other == mag && u < t)) ? 1 : 0;
+    }
+    return rank < q;
+}
+
+__global__ __launch_bounds__(TB) void truncate_count_kernel(int n, int q, const int *Pp, const double *Px, int *count)
+{
+    const int i = blockIdx.x * TB + threadIdx.x;
+    if (i > n) return;
+    if (i == n) { count[n] = 0; return; }
+    const int m = Pp[i + 1] - Pp[i];
+    count[i] = truncation_applies(Px + Pp[i], m, q) ? q : m;
+}
+
+__global__ __launch_bounds__(TB) void truncate_fill_kernel(int n, int q, const int *Pp, const int *Pj, const double *Px, const int *Tp,
+                                                           int *Tj, double *Tx)
+{
+    const int i = blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    const int m = Pp[i + 1] - Pp[i];
+    const int *j = Pj + Pp[i];
+    const double *x = Px + Pp[i];
+    long at = Tp[i];
+    if (Tp[i + 1] - Tp[i] == m) {
+        for (int t = 0; t < m; ++t, ++at) { Tj[at] = j[t]; Tx[at] = x[t]; }
+        return;
+    }
+    double s_all = 0.0, s_kept = 0.0;
+    for (int t = 0; t < m; ++t) s_all += x[t];
+    for (int t = 0; t < m; ++t)
+        if (truncation_keeps(x, m, t, q)) s_kept += x[t];
+    const double scale = s_all / s_kept;
+    for (int t = 0; t < m; ++t)
+        if (truncation_keeps(x, m, t, q)) {
+            Tj[at] = j[t];
+            Tx[at] = s_kept != 0.0 ? x[t] * scale : x[t];
+            ++at;
+        }
+}
+
+int exclusive_scan_long(const long *in, long *out, size_t count)
+{
+    size_t bytes = 0;
+    AMG_HIP(rocprim::exclusive_scan(nullptr, bytes, in, out, 0L, count, rocprim::plus<long>(), nullptr));
+    DBuf tmp;
+    CHK(tmp.alloc(bytes));
+    AMG_HIP(rocprim::exclusive_scan(tmp.p, bytes, in, out, 0L, count, rocprim::plus<long>(), nullptr));
+    return 0;
+}
+
+// no column twice in a row (host arrays that check_csr_arrays has passed)
+int check_unique_columns(const char *who, int n, const int *p, const int *j)
+{
+    std::vector<int> seen((size_t)n, -1);
+    for (int i = 0; i < n; ++i)
+        for (int e = p[i]; e < p[i + 1]; ++e) {
+            if (seen[(size_t)j[e]] == i) return bad(who, "a column is stored twice in a row");
+            seen[(size_t)j[e]] = i;
+        }
+    return 0;
+}
+
+// Extended+i interpolation of A on the pattern of S (all on the device) into Pp (n + 1 offsets) and freshly allocated
+// Pj, Px, truncated to max_per_row entries per row where that is > 0; *nnz: entries of the prolongator
+int extended_interpolation_device(int n, const HbmCsr &A, const int *Sp, const int *Sj, const int *splitting, int max_per_row, DBuf &Pp,
+                                  DBuf &Pj, DBuf &Px, long *nnz)
+{
+    const size_t pbytes = sizeof(int) * ((size_t)n + 1);
+    const int wave_blocks = (int)(((long)n + 1 + EXT_ROWS - 1) / EXT_ROWS);
+    DBuf big, Wp, count, total, coarse, diag, wcand, wlist, wsum;
+    CHK(big.alloc(sizeof(long) * ((size_t)n + 1)));
+    CHK(Wp.alloc(sizeof(long) * ((size_t)n + 1)));
+    CHK(count.alloc(pbytes));
+    CHK(total.zero(sizeof(unsigned long long)));
+    CHK(Pp.alloc(pbytes));
+    hipLaunchKernelGGL(extended_bound_kernel, grid_for((long)n + 1), dim3(TB), 0, nullptr, n, Sp, Sj, splitting, big.as<long>());
+    LAUNCH_CHECK("extended interpolation: bound launch");
+    CHK(exclusive_scan_long(big.as<long>(), Wp.as<long>(), (size_t)n + 1));
+    long wide = 0;
+    AMG_HIP(hipMemcpy(&wide, Wp.as<long>() + n, sizeof(long), hipMemcpyDeviceToHost));
+    if (wide < 0) { set_error("extended interpolation: the workspace scan went negative"); return AMG_ESTATE; }
+    CHK(wcand.alloc(sizeof(int) * (size_t)wide));
+    hipLaunchKernelGGL(extended_count_kernel, dim3(wave_blocks), dim3(TB), 0, nullptr, n, Sp, Sj, splitting, (const long *)Wp.as<long>(),
+                       wcand.i(), count.i(), total.as<unsigned long long>());
+    LAUNCH_CHECK("extended interpolation: count launch");
+    unsigned long long entries = 0;
+    AMG_HIP(hipMemcpy(&entries, total.p, sizeof(entries), hipMemcpyDeviceToHost));
+    if (entries > 0x7fffffffULL) { set_error("extended interpolation: the prolongator has 2^31 entries or more"); return AMG_ENOTIMPL; }
+    CHK(exclusive_scan(count.i(), Pp.i(), (size_t)n + 1));
+    CHK(last_offset(Pp.i(), n, nnz));
+    if (*nnz != (long)entries) { set_error("extended interpolation: the scan and the count disagree"); return AMG_ESTATE; }
+    CHK(Pj.alloc(sizeof(int) * (size_t)*nnz));
+    CHK(Px.alloc(sizeof(double) * (size_t)*nnz));
+    CHK(wlist.alloc(sizeof(int) * (size_t)wide));
+    CHK(wsum.alloc(sizeof(double) * (size_t)wide));
+    CHK(coarse.alloc(sizeof(int) * (size_t)n));
+    CHK(diag.alloc(sizeof(double) * (size_t)n));
+    CHK(exclusive_scan(splitting, coarse.i(), (size_t)n));
+    hipLaunchKernelGGL(diagonal_kernel, grid_for(n), dim3(TB), 0, nullptr, n, (const int *)A.p.i(), (const int *)A.j.i(),
+                       (const double *)A.x.d(), diag.d());
+    LAUNCH_CHECK("extended interpolation: diagonal launch");
+    hipLaunchKernelGGL(extended_fill_kernel, dim3(wave_blocks), dim3(TB), 0, nullptr, n, (const int *)A.p.i(), (const int *)A.j.i(),
+                       (const double *)A.x.d(), (const double *)diag.d(), Sp, Sj, splitting, (const int *)coarse.i(),
+                       (const long *)Wp.as<long>(), wcand.i(), wlist.i(), wsum.d(), (const int *)Pp.i(), Pj.i(), Px.d());
+    LAUNCH_CHECK("extended interpolation: fill launch");
+    if (max_per_row > 0) {
+        DBuf Tp, Tj, Tx;
+        long kept = 0;
+        CHK(Tp.alloc(pbytes));
+        hipLaunchKernelGGL(truncate_count_kernel, grid_for((long)n + 1), dim3(TB), 0, nullptr, n, max_per_row, (const int *)Pp.i(),
+                           (const double *)Px.d(), count.i());
+        LAUNCH_CHECK("extended interpolation: truncation count launch");
+        CHK(exclusive_scan(count.i(), Tp.i(), (size_t)n + 1));
+        CHK(last_offset(Tp.i(), n, &kept));
+        if (kept < 0 || kept > *nnz) { set_error("extended interpolation: the truncation scan left the prolongator"); return AMG_ESTATE; }
+        CHK(Tj.alloc(sizeof(int) * (size_t)kept));
+        CHK(Tx.alloc(sizeof(double) * (size_t)kept));
+        hipLaunchKernelGGL(truncate_fill_kernel, grid_for(n), dim3(TB), 0, nullptr, n, max_per_row, (const int *)Pp.i(), (const int *)Pj.i(),
+                           (const double *)Px.d(), (const int *)Tp.i(), Tj.i(), Tx.d());
+        LAUNCH_CHECK("extended interpolation: truncation fill launch");
+        AMG_HIP(hipDeviceSynchronize());
+        Pp = std::move(Tp); Pj = std::move(Tj); Px = std::move(Tx);
+        *nnz = kept;
+    }
+    AMG_HIP(hipDeviceSynchronize());
+    return 0;
+}
+
 }   // namespace
+
+// the columns and values of a prolongator, held for amg_extended_interpolation_fetch
+struct amg_interpolation {
+    long nnz = 0;
+    DBuf Pj, Px;
+};
 
 // the result of one chained level, held for amg_classical_level_fetch
 struct amg_classical {
@@ -757,16 +1152,81 @@ int amgcore_rs_direct_interpolation_pass2_f64(int n_nodes, const int Ap[], int A
     return dBx.to_host(Bx, sizeof(double) * (size_t)nnz);
 }
 
+int amg_extended_interpolation_device(int n, const int *Ap, const int *Aj, const double *Ax, const int *Sp, const int *Sj,
+                                      const int *splitting, int max_per_row, int *Pp, amg_interpolation **out, double *times_ms)
+{
+    const char *who = "extended interpolation";
+    if (!out || !Pp) return bad(who, "bad arguments");
+    *out = nullptr;
+    if (max_per_row < 0) return bad(who, "max_per_row is 0 (no truncation) or positive");
+    CHK(check_csr_arrays(who, n, n, Ap, n + 1, Aj, 0x7fffffff, Ax, 0x7fffffff));
+    CHK(check_csr_arrays(who, n, n, Sp, n + 1, Sj, 0x7fffffff, nullptr, -1));
+    CHK(check_splitting(who, n, splitting, n));
+    CHK(check_unique_columns(who, n, Ap, Aj));
+    CHK(check_unique_columns(who, n, Sp, Sj));
+    if (times_ms) times_ms[0] = times_ms[1] = 0.0;
+    struct Guard {
+        amg_interpolation *h;
+        ~Guard() { delete h; }
+    } guard{new amg_interpolation};
+    amg_interpolation &h = *guard.h;
+    if (n == 0) {
+        Pp[0] = 0;
+        *out = guard.h;
+        guard.h = nullptr;
+        return 0;
+    }
+    CHK(require_device());
+    LapClock timer;
+    HbmCsr A, S;
+    DBuf dsplit, dPp;
+    CHK(A.upload(n, Ap, Aj, Ax));
+    CHK(S.upload(n, Sp, Sj, nullptr));
+    CHK(dsplit.from_host(splitting, sizeof(int) * (size_t)n));
+    AMG_HIP(hipDeviceSynchronize());
+    const double upload_ms = timer.lap();
+    CHK(extended_interpolation_device(n, A, S.p.i(), S.j.i(), dsplit.i(), max_per_row, dPp, h.Pj, h.Px, &h.nnz));
+    if (times_ms) { times_ms[0] = upload_ms; times_ms[1] = timer.lap(); }
+    CHK(dPp.to_host(Pp, sizeof(int) * ((size_t)n + 1)));
+    *out = guard.h;
+    guard.h = nullptr;
+    return 0;
+}
+
+int amg_extended_interpolation_fetch(amg_interpolation *h, int *Pj, double *Px)
+{
+    if (!h) return AMG_EINVAL;
+    struct Guard {
+        amg_interpolation *h;
+        ~Guard() { delete h; }
+    } guard{h};
+    if (h->nnz > 0 && (!Pj || !Px)) return bad("extended interpolation fetch", "null array");
+    CHK(h->Pj.to_host(Pj, sizeof(int) * (size_t)h->nnz));
+    return h->Px.to_host(Px, sizeof(double) * (size_t)h->nnz);
+}
+
 int amg_classical_level_device(int n, const int *Ap, const int *Aj, const double *Ax, double theta, int kind, int reversed,
                                const double *r, amg_classical **out, long *sizes, int *rounds, double *times_ms)
+{
+    return amg_classical_level_build(n, Ap, Aj, Ax, theta, kind, reversed, r, 0, 0, out, sizes, rounds, times_ms);
+}
+
+int amg_classical_level_build(int n, const int *Ap, const int *Aj, const double *Ax, double theta, int kind, int reversed,
+                              const double *r, int interpolation, int max_per_row, amg_classical **out, long *sizes, int *rounds,
+                              double *times_ms)
 {
     const char *who = "classical level";
     if (!out || !sizes) return bad(who, "bad arguments");
     *out = nullptr;
     if (kind != KIND_PMIS && kind != KIND_CLJP) return bad(who, "the splitting is 0 (PMIS) or 1 (CLJP)");
+    if (interpolation != INTERP_DIRECT && interpolation != INTERP_EXTENDED_I)
+        return bad(who, "the interpolation is 0 (direct) or 1 (extended+i)");
+    if (max_per_row < 0 || (max_per_row > 0 && interpolation == INTERP_DIRECT))
+        return bad(who, "max_per_row is 0, or positive with extended+i");
     if (n <= 0 || !r) return bad(who, "an empty operator or no start values");
     if (!(theta >= 0.0 && theta <= 1.0)) return bad(who, "expected theta in [0, 1]");
     CHK(check_csr_arrays(who, n, n, Ap, n + 1, Aj, 0x7fffffff, Ax, 0x7fffffff));
+    if (interpolation == INTERP_EXTENDED_I) CHK(check_unique_columns(who, n, Ap, Aj));
     CHK(require_device());
     LapClock timer;
     const size_t vbytes = sizeof(int) * (size_t)n, pbytes = sizeof(int) * ((size_t)n + 1);
@@ -836,12 +1296,17 @@ int amg_classical_level_device(int n, const int *Ap, const int *Aj, const double
     AMG_HIP(hipDeviceSynchronize());
     h.times_ms[3] = timer.lap();
 
-    // 5. direct interpolation on S's pattern with the values the strength kernel wrote
-    CHK(interpolation_offsets_device(n, h.Sp.i(), h.Sj.i(), h.splitting.i(), h.Pp, &h.p_nnz));
-    if (h.p_nnz < 0 || h.p_nnz > h.s_nnz + n) { set_error("classical level: the interpolation scan left the matrix"); return AMG_ESTATE; }
-    CHK(h.Pj.alloc(sizeof(int) * (size_t)h.p_nnz));
-    CHK(h.Px.alloc(sizeof(double) * (size_t)h.p_nnz));
-    CHK(interpolation_fill_device(n, A, h.Sp.i(), h.Sj.i(), h.Sx.d(), h.splitting.i(), h.Pp.i(), h.Pj.i(), h.Px.d(), reversed ? -1 : 1));
+    // 5. interpolation on S's pattern: extended+i reads the pattern as the strength kernel stored it, direct
+    // interpolation also the values written beside it
+    if (interpolation == INTERP_EXTENDED_I) {
+        CHK(extended_interpolation_device(n, A, h.Sp.i(), h.Sj.i(), h.splitting.i(), max_per_row, h.Pp, h.Pj, h.Px, &h.p_nnz));
+    } else {
+        CHK(interpolation_offsets_device(n, h.Sp.i(), h.Sj.i(), h.splitting.i(), h.Pp, &h.p_nnz));
+        if (h.p_nnz < 0 || h.p_nnz > h.s_nnz + n) { set_error("classical level: the interpolation scan left the matrix"); return AMG_ESTATE; }
+        CHK(h.Pj.alloc(sizeof(int) * (size_t)h.p_nnz));
+        CHK(h.Px.alloc(sizeof(double) * (size_t)h.p_nnz));
+        CHK(interpolation_fill_device(n, A, h.Sp.i(), h.Sj.i(), h.Sx.d(), h.splitting.i(), h.Pp.i(), h.Pj.i(), h.Px.d(), reversed ? -1 : 1));
+    }
     h.times_ms[4] = timer.lap();
 
     sizes[0] = h.s_nnz;
