@@ -770,6 +770,67 @@ int amg_classical_level_build(int n, const int *Ap, const int *Aj, const double 
                               const double *r, int interpolation, int max_per_row, amg_classical **out, long *sizes, int *rounds,
                               double *times_ms);
 
+/* R = P^T for a float64 CSR matrix P (n_row x n_col, host arrays, 32-bit offsets) with the bits and the order of scipy's
+ * P.T.tocsr() (csr_tocsc, DESIGN.md section 8k, csrc/split.hip): row c of R holds the entries of column c of P in the
+ * order in which a walk over P's stored arrays meets them -- ascending row of P, and within a row of P the stored order.
+ * A column stored twice in a row stays two entries in that order; nothing is summed, dropped or sorted by value; values
+ * are copied bit for bit; an empty column gives repeated offsets; the rows of P may be stored in any order.  On return
+ * Rp (n_col + 1 offsets) is filled and *out holds the columns and values; amg_csr_transpose_fetch copies them (Rp[n_col]
+ * each) to the host and releases the result, also when it fails or is handed NULL arrays.  Offsets that do not start at
+ * 0 or decrease and a column outside [0, n_col) are AMG_EINVAL before any launch, with Rp untouched.  Without rows or
+ * without entries the result is empty and nothing is launched.
+ * amg_transpose_last_route: what the calling thread's most recent transpose (this entry or a chain level) did, as
+ * AMG_TRANSPOSE_ROUTE_FIELDS ints: [0] 1 where kernels ran, [1] the rows of R ordered by one lane each (at most 32
+ * entries, empty rows included), [2] by one wave with the row in LDS (at most 2048), [3] by one workgroup on the row's
+ * keys in HBM (longer).  Returns the number of fields. */
+typedef struct amg_transpose amg_transpose;
+int amg_csr_transpose_device(int n_row, int n_col, const int *Pp, const int *Pj, const double *Px, int *Rp, amg_transpose **out);
+int amg_csr_transpose_fetch(amg_transpose *h, int *Rj, double *Rx);
+#define AMG_TRANSPOSE_ROUTE_FIELDS 4
+int amg_transpose_last_route(int *out, int n);
+
+/* A chain of classical levels that stays in HBM: one upload of A_0, then per level one call that
+ * builds it and one that downloads what the host hierarchy keeps.
+ *
+ * amg_classical_chain_begin validates A_0 (n x n, n > 0, as amg_classical_level_build does, and no column twice in a
+ * row) and uploads it as the chain's resident operator.  reversed: as in amg_classical_level_device.
+ *
+ * amg_classical_chain_level builds the level of the resident operator exactly as amg_classical_level_build does
+ * (theta, kind, r: n start values from the host, interpolation, max_per_row), then R = P^T by the transpose above,
+ * R * A and A_c = (R * A) * P by the routes of amg_csr_matmat_device; R * A is released.  sizes (5 longs): the entries
+ * of S [0], P [1], R [2] and A_c [3] and the coarse size [4].  flags (AMG_CHAIN_FLAG_FIELDS ints): [0] 1 where every
+ * row of A_c is strictly ascending, [1] 1 where every value of A_c is finite -- both from one pass over A_c in HBM --
+ * [2] and [3] the tables (field 3 of amg_spgemm_last_route) of R * A and of (R * A) * P, [4 .. 7] the fields of
+ * amg_transpose_last_route.  *rounds (or NULL): the rounds or passes of the splitting.  times_ms (or NULL, AMG_CHAIN_STAGES
+ * doubles): upload [0] (A_0 with the first level, r with every level), strength [1], graph and weights [2], splitting
+ * [3], interpolation [4], transpose [5], the two products and the pass over A_c [6]; the fetch writes the same seven and
+ * its own time [7].  Returns 0, or AMG_CHAIN_PRODUCT_REFUSED where a product was refused (a row of more than 2^22
+ * products on a level too large for per-thread tables, or 2^31 entries or more): the level then holds its splitting, P
+ * and S only, sizes[3] is 0 and flags[0], flags[1] are 0.  A non-finite value of A_c is no error of this level: it is
+ * reported in flags[1] and the caller decides about the next one.  Any other return is an error and leaves the chain
+ * without a level, its resident operator as it was.
+ *
+ * amg_classical_chain_fetch copies the level just built to the host: splitting (n), Pp (n + 1), Pj, Px (sizes[1]), Rp
+ * (sizes[4] + 1), Rj, Rx (sizes[2]), Cp (sizes[4] + 1), Cj, Cx (sizes[3]) and, where Sp is not NULL, Sp, Sj, Sx as
+ * amg_classical_level_fetch does.  It then makes A_c the resident operator (the next level runs with reversed = 0 where
+ * flags[0] was 1, with 1 otherwise) and releases the level's other buffers.  Rp NULL: R is not copied; Cp NULL: A_c is not
+ * copied (it becomes the resident operator all the same).  After AMG_CHAIN_PRODUCT_REFUSED the R and C
+ * arrays are not read (NULL will do) and the chain is left without an operator: the caller forms the coarse operator on
+ * the host and begins another chain.  A failing fetch, one with a NULL splitting or Pp included, releases the level and keeps the
+ * operator the chain had.
+ *
+ * amg_classical_chain_free releases the chain with everything it holds (NULL: nothing). */
+typedef struct amg_classical_chain amg_classical_chain;
+#define AMG_CHAIN_FLAG_FIELDS 8
+#define AMG_CHAIN_STAGES 8
+#define AMG_CHAIN_PRODUCT_REFUSED 1
+int amg_classical_chain_begin(int n, const int *Ap, const int *Aj, const double *Ax, int reversed, amg_classical_chain **out);
+int amg_classical_chain_level(amg_classical_chain *chain, double theta, int kind, const double *r, int interpolation, int max_per_row,
+                              long *sizes, int *flags, int *rounds, double *times_ms);
+int amg_classical_chain_fetch(amg_classical_chain *chain, int *splitting, int *Pp, int *Pj, double *Px, int *Rp, int *Rj, double *Rx,
+                              int *Cp, int *Cj, double *Cx, int *Sp, int *Sj, double *Sx, double *times_ms);
+void amg_classical_chain_free(amg_classical_chain *chain);
+
 /* Extended+i (distance-two) interpolation (csrc/split.hip) from a float64 CSR operator A, the
  * pattern of a strength matrix S of A's shape and a C/F splitting (1 = C, 0 = F), all on the host with 32-bit offsets;
  * rows in any stored order.  An F row interpolates from C_hat, its strong C neighbours and those of its strong F

@@ -206,6 +206,12 @@ def lib():
         "amg_classical_level_device": [I, V, V, V, D, I, I, V, C.POINTER(C.c_void_p), C.POINTER(C.c_long), c_int_p, c_dbl_p],
         "amg_classical_level_fetch": [V, V, V, V, V, V, V, V, c_dbl_p],
         "amg_classical_level_build": [I, V, V, V, D, I, I, V, I, I, C.POINTER(C.c_void_p), C.POINTER(C.c_long), c_int_p, c_dbl_p],
+        "amg_csr_transpose_device": [I, I, V, V, V, V, C.POINTER(C.c_void_p)],
+        "amg_csr_transpose_fetch": [V, V, V],
+        "amg_transpose_last_route": [c_int_p, I],
+        "amg_classical_chain_begin": [I, V, V, V, I, C.POINTER(C.c_void_p)],
+        "amg_classical_chain_level": [V, D, I, V, I, I, C.POINTER(C.c_long), c_int_p, c_int_p, c_dbl_p],
+        "amg_classical_chain_fetch": [V] * 14 + [c_dbl_p],
         "amg_extended_interpolation_device": [I, V, V, V, V, V, V, I, V, C.POINTER(C.c_void_p), c_dbl_p],
         "amg_extended_interpolation_fetch": [V, V, V],
         "amg_hierx_create": [I, I, I, C.POINTER(C.c_void_p)],
@@ -255,6 +261,8 @@ def lib():
         L.amg_dev_live_buffers.restype = C.c_long
     L.amg_device_name.argtypes = [I]
     L.amg_device_name.restype = C.c_char_p
+    L.amg_classical_chain_free.argtypes = [V]
+    L.amg_classical_chain_free.restype = None
     L.amg_hier_create.argtypes = [I, I]
     L.amg_hier_create.restype = V
     L.amg_hier_destroy.argtypes = [V]
@@ -433,3 +441,21 @@ def spgemm_last_route():
     rec = dict(zip(SPGEMM_ROUTE_FIELDS, (int(v) for v in out)))
     rec["tables"] = SPGEMM_TABLES[rec["tables"]]
     return rec
+
+
+TRANSPOSE_ROUTE_FIELDS = ("launched", "lane_rows", "lds_rows", "hbm_rows")
+# a row of R of at most TRANSPOSE_LANE_MAX entries is ordered by one lane, of at most TRANSPOSE_LDS_MAX by one wave in LDS,
+# a longer one by one workgroup in HBM (TR_LANE_MAX, TR_LDS_MAX of csrc/split.hip)
+TRANSPOSE_LANE_MAX, TRANSPOSE_LDS_MAX = 32, 2048
+CHAIN_PRODUCT_REFUSED = 1
+CHAIN_FLAG_FIELDS = 8
+
+
+def transpose_last_route():
+    """What this thread's most recent device transpose did (amg_transpose_last_route, csrc/split.hip): a dict of
+    TRANSPOSE_ROUTE_FIELDS."""
+    out = (C.c_int * len(TRANSPOSE_ROUTE_FIELDS))()
+    n = lib().amg_transpose_last_route(out, len(TRANSPOSE_ROUTE_FIELDS))
+    if n != len(TRANSPOSE_ROUTE_FIELDS):
+        raise AmgError("amg_transpose_last_route: %d fields, %d expected" % (n, len(TRANSPOSE_ROUTE_FIELDS)))
+    return dict(zip(TRANSPOSE_ROUTE_FIELDS, (int(v) for v in out)))

@@ -18,9 +18,14 @@ same integers:
 
 Classical strength and direct interpolation have the same two routes with the same bits (csrc/split.hip, DESIGN.md
 section 8i); their device route takes A as canonical CSR (sorted rows, no duplicate columns, no stored zeros, finite
-values).  ``ruge_stuben_solver(..., device=True)`` builds a level with classical strength and ``CF`` 'PMIS' or 'CLJP'
-in HBM from one upload of A (strength, graph, weights, splitting, either interpolation); with another ``CF`` strength
-and interpolation take their device routes one by one.  R = P^T and the Galerkin product run on the host.
+values).  ``ruge_stuben_solver(..., device=True)`` with classical strength and ``CF`` 'PMIS' or 'CLJP' builds the whole
+hierarchy in HBM from one upload of A_0: every level's strength, graph, weights, splitting and
+either interpolation, then R = P^T by the device transpose (``transpose``: the order and bits of P.T.tocsr()) and R A P
+by the device sparse product (csrc/spgemm.hip); the coarse operator stays where the product left it for the next
+level, and each level downloads what the host hierarchy keeps.  Where the product refuses a level (a row too long for
+its tables, 2^31 entries) that level's transpose and product run on the host and a new chain begins.  With another
+``CF`` strength and interpolation take their device routes one by one, and R = P^T and the Galerkin product run on the
+host.  ``LAST_BUILD`` records the route of the last build.
 
 ``device=True`` takes the device route and raises NotImplementedError for what it cannot take (a sweep limit, a
 structurally unsymmetric graph); ``device=False`` is the host route; ``device=None`` is the host route unless
@@ -44,7 +49,7 @@ from .multilevel import multilevel_solver
 from .smoothing import change_smoothers
 
 __all__ = ["ruge_stuben_solver", "classical_strength_of_connection", "RS", "direct_interpolation",
-           "extended_interpolation", "PMIS", "PMISc", "CLJP", "CLJPc", "MIS", "preprocess"]
+           "extended_interpolation", "transpose", "PMIS", "PMISc", "CLJP", "CLJPc", "MIS", "preprocess"]
 
 # What device=None does when a GPU is present: the host route.  profiles/r16_splitting.txt did not justify the device
 # route of a splitting alone; profiles/r17_classical_level.txt would justify the chained level
@@ -531,8 +536,14 @@ def ruge_stuben_solver(A, strength=("classical", {"theta": 0.25}), CF="RS",
     if A.shape[0] != A.shape[1]:
         raise ValueError("expected square matrix")
     levels[-1].A = A
-    while len(levels) < max_levels and levels[-1].A.shape[0] > max_coarse:
-        extend_hierarchy(levels, strength, CF, keep, device, interpolation)
+    LAST_BUILD["uploads"] = 0
+    LAST_BUILD["levels"] = []
+    chain = _Chain()
+    try:
+        while len(levels) < max_levels and levels[-1].A.shape[0] > max_coarse:
+            extend_hierarchy(levels, strength, CF, keep, device, interpolation, chain)
+    finally:
+        chain.close()
     ml = multilevel_solver(levels, **kwargs)
     change_smoothers(ml, presmoother, postsmoother)
     return ml
@@ -562,30 +573,215 @@ def _stages(A, strength, CF, device, interpolation="direct"):
     return Cm, splitting, _extended(A, Cm, splitting, q, device)
 
 
-def _chained(A, strength, CF, keep, interpolation="direct"):
-    """the level in HBM where strength is classical with theta alone and CF is PMIS or CLJP not sent to the host;
-    None otherwise"""
+def _chain_options(strength, CF):
+    """(theta, splitting name) where the whole level runs in HBM: strength is classical with theta alone and CF is PMIS
+    or CLJP not sent to the host; None otherwise"""
     fn, kwargs = unpack_arg(strength)
     name, cf_kwargs = unpack_arg(CF)
     if fn != "classical" or set(kwargs) - {"theta"} or name not in _CHAINED_SPLITTINGS:
         return None
     if set(cf_kwargs) - {"device"} or cf_kwargs.get("device", True) is False:
         return None
-    splitting, P, S = classical_level_device(A, kwargs.get("theta", 0.0), name, keep=keep, product_order=True,
+    return kwargs.get("theta", 0.0), name
+
+
+def _chained(A, strength, CF, keep, interpolation="direct"):
+    """the level in HBM from an upload of its own (_chain_options); None otherwise"""
+    options = _chain_options(strength, CF)
+    if options is None:
+        return None
+    times = []
+    LAST_BUILD["uploads"] += 1
+    splitting, P, S = classical_level_device(A, options[0], options[1], keep=keep, times=times, product_order=True,
                                              interpolation=interpolation)
+    _record_level(resident=True, times=dict(zip(LEVEL_STAGES, times)))
     return S, splitting, P
 
 
-def extend_hierarchy(levels, strength, CF, keep, device=None, interpolation="direct"):
-    """classical.py:120-188"""
+# The route of the last ruge_stuben_solver build, for the tests and tools/bench_classical_hierarchy.py.  uploads: operators
+# sent to HBM by the level routes (one per chain, one per level of the per-level route).  levels: one record per level
+# built: chained (its transpose and Galerkin product ran in HBM on the chain's resident operator), resident (the level
+# itself was built in HBM), reversed (what the level entry was told about the row order; None on the host), times
+# (milliseconds by stage: CHAIN_STAGES or LEVEL_STAGES), products (the tables of R * A and (R * A) * P, _lib.SPGEMM_TABLES)
+# and transpose (_lib.TRANSPOSE_ROUTE_FIELDS).
+LAST_BUILD = {"uploads": 0, "levels": []}
+CHAIN_STAGES = ("upload", "strength", "graph", "splitting", "interpolation", "transpose", "galerkin", "fetch")
+# What tools/bench_classical_hierarchy.py turns off to time the per-level route (every level uploads A_l, transposes and
+# multiplies on the host); not an option of the setup.
+_RESIDENT_CHAIN = True
+# a coarse operator of this many entries or more does not fit the host's 32-bit index arrays: the level's product is
+# treated as refused, as the device library itself refuses it
+_PRODUCT_ENTRIES_LIMIT = 2 ** 31
+
+
+def _record_level(chained=False, resident=False, reversed=None, times=None, products=None, transpose=None):
+    LAST_BUILD["levels"].append({"chained": chained, "resident": resident, "reversed": reversed, "times": times or {},
+                                 "products": products, "transpose": transpose})
+
+
+def _transpose_device(P):
+    from . import _lib
+    what = "the device route of a transpose"
+    if P.dtype != np.float64 or P.nnz >= 2 ** 31 or max(P.shape) >= 2 ** 31 - 1:
+        raise outside("%s of a matrix that is not float64 with fewer than 2^31 entries" % what)
+    n_row, n_col = P.shape
+    Pp, Pj, Px = _i32(P.indptr), _i32(P.indices), np.ascontiguousarray(P.data, dtype=np.float64)
+    Rp = np.empty(n_col + 1, dtype=np.intc)
+    handle = C.c_void_p()
+    _lib.check(_lib.lib().amg_csr_transpose_device(n_row, n_col, Pp.ctypes.data, Pj.ctypes.data, Px.ctypes.data, Rp.ctypes.data,
+                                                   C.byref(handle)))
+    try:
+        Rj = np.empty(int(Rp[-1]), dtype=np.intc)
+        Rx = np.empty(int(Rp[-1]), dtype=np.float64)
+    except BaseException:
+        _lib.lib().amg_csr_transpose_fetch(handle, None, None)      # releases the result
+        raise
+    _lib.check(_lib.lib().amg_csr_transpose_fetch(handle, Rj.ctypes.data, Rx.ctypes.data))
+    return _transposed(Rp, Rj, Rx, (n_col, n_row))
+
+
+def _transposed(Rp, Rj, Rx, shape):
+    """the arrays of a device transpose as the object P.T.tocsr() returns: scipy's conversion declares its rows sorted"""
+    R = csr_matrix((Rx, Rj, Rp), shape=shape)
+    R.has_sorted_indices = True
+    return R
+
+
+def transpose(P, device=None):
+    """R = P^T of a CSR matrix exactly as P.T.tocsr() returns it (scipy's csr_tocsc): row c of R holds the entries of
+    column c of P by ascending row of P and, within a row of P, in stored order; duplicates stay, values keep their
+    bits.  device: the host route is P.T.tocsr(), the device route the kernels of csrc/split.hip (DESIGN.md section
+    8k, float64 only); both return the same bits."""
+    if not isspmatrix_csr(P):
+        raise TypeError("expected csr_matrix")
+    return attempt(route(device, DEVICE_AUTO), lambda: _transpose_device(P), lambda: P.T.tocsr())
+
+
+class _Chain:
+    """the resident chain of one ruge_stuben_solver call: the handle of amg_classical_chain_begin and what the last
+    level's flags said about the operator it left in HBM"""
+
+    def __init__(self):
+        self.handle = None
+        self.reversed = 0
+        self.finite = True
+
+    def close(self):
+        if self.handle is not None:
+            from . import _lib
+            handle, self.handle = self.handle, None
+            _lib.lib().amg_classical_chain_free(handle)
+
+
+def _chain_level_call(handle, theta, kind, r, interpolation, q, sizes, flags, ms):
+    """amg_classical_chain_level -> 0 or _lib.CHAIN_PRODUCT_REFUSED (the tests wrap it to see the calls)"""
+    from . import _lib
+    rc = _lib.lib().amg_classical_chain_level(handle, float(theta), kind, r.ctypes.data, interpolation, q, sizes, flags, None, ms)
+    if rc != _lib.CHAIN_PRODUCT_REFUSED:
+        _lib.check(rc)
+    return rc
+
+
+def _chain_level(levels, chain, theta, CF, keep, interpolation):
+    """One level on the chain's resident operator (amg_classical_chain_level / _fetch): strength, splitting and
+    interpolation as classical_level_device builds them, then R = P^T and R A P in HBM; the host hierarchy receives
+    what it keeps.  The first level of a chain vets and uploads A.  Where the product is refused the level is finished
+    on the host from the fetched splitting, P and S, and the chain ends."""
+    from . import _lib
+    A = levels[-1].A
+    name, q = _interpolation_choice(interpolation)
+    what = "the device route of a classical level"
+    if chain.handle is None:
+        reverse = _operator_order(A, what, True)
+    elif not chain.finite:
+        # what _operator_order would say about the operator in HBM, from the flags of the product that left it there
+        raise outside("%s of an operator with stored zeros or non-finite values" % what)
+    else:
+        reverse = bool(chain.reversed)
+    if theta < 0 or theta > 1:
+        raise ValueError("expected theta in [0,1]")
+    n = A.shape[0]
+    if n == 0:
+        raise outside("the device route of a classical level without rows")
+    kind = _CHAINED_SPLITTINGS[CF]
+    if chain.handle is None:
+        Ap, Aj, Ax = _i32(A.indptr), _i32(A.indices), np.ascontiguousarray(A.data, dtype=np.float64)
+        handle = C.c_void_p()
+        _lib.check(_lib.lib().amg_classical_chain_begin(n, Ap.ctypes.data, Aj.ctypes.data, Ax.ctypes.data, int(reverse),
+                                                        C.byref(handle)))
+        chain.handle, chain.reversed, chain.finite = handle, int(reverse), True
+        LAST_BUILD["uploads"] += 1
+    if kind == 0:
+        r = np.ascontiguousarray(np.random.rand(n))
+    else:
+        r = np.empty(n, dtype=np.float64)
+        host_lib().amgsetup_cljp_random(n, _dp(r))
+    sizes = (C.c_long * 5)()
+    flags = (C.c_int * _lib.CHAIN_FLAG_FIELDS)()
+    ms = (C.c_double * len(CHAIN_STAGES))()
+    rc = _chain_level_call(chain.handle, theta, kind, r, _INTERPOLATIONS[name], q or 0, sizes, flags, ms)
+    s_nnz, p_nnz, r_nnz, c_nnz, n_coarse = (int(v) for v in sizes)
+    refused = rc == _lib.CHAIN_PRODUCT_REFUSED or c_nnz >= _PRODUCT_ENTRIES_LIMIT
+    ptr = lambda a: None if a is None else a.ctypes.data
+    splitting = np.empty(n, dtype=np.intc)
+    Pp = np.empty(n + 1, dtype=np.intc)
+    Pj = np.empty(p_nnz, dtype=np.intc)
+    Px = np.empty(p_nnz, dtype=np.float64)
+    Rp = Rj = Rx = Cp = Cj = Cx = Sp = Sj = Sx = None
+    if not refused:
+        Rp, Rj, Rx = np.empty(n_coarse + 1, dtype=np.intc), np.empty(r_nnz, dtype=np.intc), np.empty(r_nnz, dtype=np.float64)
+        Cp, Cj, Cx = np.empty(n_coarse + 1, dtype=np.intc), np.empty(c_nnz, dtype=np.intc), np.empty(c_nnz, dtype=np.float64)
+    if keep:
+        Sp, Sj, Sx = np.empty(n + 1, dtype=np.intc), np.empty(s_nnz, dtype=np.intc), np.empty(s_nnz, dtype=np.float64)
+    _lib.check(_lib.lib().amg_classical_chain_fetch(chain.handle, ptr(splitting), ptr(Pp), ptr(Pj), ptr(Px), ptr(Rp), ptr(Rj), ptr(Rx),
+                                                    ptr(Cp), ptr(Cj), ptr(Cx), ptr(Sp), ptr(Sj), ptr(Sx), ms))
+    _record_level(chained=not refused, resident=True, reversed=int(reverse), times=dict(zip(CHAIN_STAGES, ms)),
+                  products=(_lib.SPGEMM_TABLES[flags[2]], _lib.SPGEMM_TABLES[flags[3]]),
+                  transpose=dict(zip(_lib.TRANSPOSE_ROUTE_FIELDS, (int(v) for v in flags[4:8]))))
+    P = csr_matrix((Px, Pj, Pp), shape=None if name == "direct" else (n, int(splitting.sum())))
+    if refused:
+        chain.close()
+        R = P.T.tocsr()
+        Ac = R * A * P
+    else:
+        chain.reversed, chain.finite = int(not flags[0]), bool(flags[1])
+        R = _transposed(Rp, Rj, Rx, (n_coarse, n))
+        Ac = csr_matrix((Cx, Cj, Cp), shape=(n_coarse, n_coarse))
+    if keep:
+        levels[-1].C = csr_matrix((Sx, Sj, Sp), shape=A.shape)
+        levels[-1].splitting = splitting
+    levels[-1].P = P
+    levels[-1].R = R
+    levels.append(multilevel_solver.level())
+    levels[-1].A = Ac
+
+
+def extend_hierarchy(levels, strength, CF, keep, device=None, interpolation="direct", chain=None):
+    """classical.py:120-188.  chain: the resident chain of the calling ruge_stuben_solver (_Chain); with it, a level that
+    _chain_options takes is built, transposed and multiplied in HBM."""
     A = levels[-1].A
     way = route(device, DEVICE_AUTO)
+    options = _chain_options(strength, CF) if chain is not None and _RESIDENT_CHAIN and way is not False else None
+    if options is not None:
+        try:
+            return _chain_level(levels, chain, options[0], options[1], keep, interpolation)
+        except NotImplementedError:
+            chain.close()
+            if way is True:
+                raise
+        except BaseException:
+            chain.close()
+            raise
+        way = False                         # the refusal is answered by the host route, as attempt() would
 
     def on_device():
         built = _chained(A, strength, CF, keep, interpolation)
         return built if built is not None else _stages(A, strength, CF, way, interpolation)
 
+    recorded = len(LAST_BUILD["levels"])
     Cm, splitting, P = attempt(way, on_device, lambda: _stages(A, strength, CF, False, interpolation))
+    if len(LAST_BUILD["levels"]) == recorded:
+        _record_level()
     R = P.T.tocsr()
     if keep:
         levels[-1].C = Cm

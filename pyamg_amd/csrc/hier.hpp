@@ -141,6 +141,16 @@ struct Level {
 }  // namespace amg
 
 namespace amg {
+// spgemm.hip: products of operands that are already in HBM, with scipy's csr_matmat bits and output order.  The arrays
+// of C are allocated there and move into the caller's owners.  AMG_EINVAL is a refusal (a row of more than 2^22
+// products on a level too large for per-thread tables, or 2^31 entries or more): the caller's host path.
+int spgemm_square_device(int n, long nnz, const long *Ap, const int *Aj, const double *Ax, long *Cnnz, DevArr<long> &Cp, DevArr<int> &Cj,
+                         DevArr<double> &Cx);
+int spgemm_device(int n_row, int n_inner, int n_col, long a_nnz, const long *Ap, const int *Aj, const double *Ax, long b_nnz,
+                  const long *Bp, const int *Bj, const double *Bx, long *Cnnz, DevArr<long> &Cp, DevArr<int> &Cj, DevArr<double> &Cx);
+// between the 32-bit row pointers of the classical setup (split.hip) and the 64-bit ones of the products
+int widen_rowptr_device(int n, const int *p32, DevArr<long> &p64);
+int narrow_rowptr_device(int n, long nnz, const long *p64, int *p32);
 // schwarz.hip
 int schwarz_levels(int nrows, const int *Ap, const int *Aj, const int *Sj, const int *Sp,
                    const std::vector<int> &tasks, std::vector<int> &level_ptr, std::vector<int> &order);

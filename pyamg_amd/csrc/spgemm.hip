@@ -562,6 +562,12 @@ __global__ void widen_rowptr_kernel(int n, const int *Ap32, long *Ap64)
     if (i <= n) Ap64[i] = Ap32[i];
 }
 
+__global__ void narrow_rowptr_kernel(int n, const long *Ap64, int *Ap32)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i <= n) Ap32[i] = (int)Ap64[i];
+}
+
 }   // namespace
 
 namespace amg {
@@ -575,6 +581,36 @@ int spgemm_square_device(int n, long nnz, const long *Ap, const int *Aj, const d
     CHK(matmat(A, A, C));
     *Cnnz = C.nnz; Cp = std::move(C.Ap); Cj = std::move(C.Aj); Cx = std::move(C.Ax);
     return 0;
+}
+
+// C = A * B for operands already in HBM (the Galerkin products of the classical chain, split.hip): A is n_row x n_inner,
+// B n_inner x n_col, both with 64-bit row pointers.  Same ownership rule as above.  AMG_EINVAL, with nothing moved, where
+// matmat() refuses the product or C would hold 2^31 entries or more (C's columns and the callers' offsets are ints).
+int spgemm_device(int n_row, int n_inner, int n_col, long a_nnz, const long *Ap, const int *Aj, const double *Ax, long b_nnz,
+                  const long *Bp, const int *Bj, const double *Bx, long *Cnnz, DevArr<long> &Cp, DevArr<int> &Cj, DevArr<double> &Cx)
+{
+    const DCsr::View A{n_row, n_inner, a_nnz, Ap, Aj, Ax}, B{n_inner, n_col, b_nnz, Bp, Bj, Bx};
+    DCsr C;
+    CHK(matmat(A, B, C));
+    if (C.nnz >= (1L << 31)) { set_error("spgemm: the product holds 2^31 entries or more"); return AMG_EINVAL; }
+    *Cnnz = C.nnz; Cp = std::move(C.Ap); Cj = std::move(C.Aj); Cx = std::move(C.Ax);
+    return 0;
+}
+
+// the n + 1 offsets of a 32-bit row pointer as 64-bit ones (allocated here) and back; both arrays in HBM
+int widen_rowptr_device(int n, const int *p32, DevArr<long> &p64)
+{
+    AMG_HIP(p64.malloc_bytes(sizeof(long) * ((size_t)n + 1)));
+    hipLaunchKernelGGL(widen_rowptr_kernel, dim3((n + 256) / 256), dim3(256), 0, nullptr, n, p32, (long *)p64);
+    LAUNCH_RETURN("spgemm: row pointer widening launch");
+}
+
+// nnz: the last offset, which the caller knows; 2^31 or more does not fit and is AMG_EINVAL
+int narrow_rowptr_device(int n, long nnz, const long *p64, int *p32)
+{
+    if (nnz < 0 || nnz >= (1L << 31)) { set_error("spgemm: offsets of 2^31 or more do not fit 32-bit row pointers"); return AMG_EINVAL; }
+    hipLaunchKernelGGL(narrow_rowptr_kernel, dim3((n + 256) / 256), dim3(256), 0, nullptr, n, p64, p32);
+    LAUNCH_RETURN("spgemm: row pointer narrowing launch");
 }
 }   // namespace amg
 

@@ -7,6 +7,7 @@
 //  and the level chained in HBM, which runs the two loops above on buffers its earlier stages
 // left there.
 #include "flat.hpp"
+#include "hier.hpp"
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -1037,6 +1038,209 @@ int extended_interpolation_device(int n, const HbmCsr &A, const int *Sp, const i
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------ R = P^T
+// The transpose of a CSR matrix with the bits and the order of scipy's csr_tocsc: row c of R
+// holds the entries of column c of P in the order in which a walk over P's stored arrays meets them.  An entry's
+// position k in P's arrays is unique and increases along that walk, so "row c of R ascending by k" is the whole
+// definition.  Columns are counted with integer atomics and scanned; every entry then takes the next free slot of its
+// column (an integer atomic again) and leaves k there.  Which slot an entry gets depends on scheduling; the multiset of
+// keys in a row does not, and ordering every row by key removes the difference.  The row of R and the value follow by
+// gather from the ordered keys: Rj is the row of P that holds position k (bisection of Pp), Rx the 64 bits of Px[k].
+// Three forms order a row, by its length:
+//   lane   at most TR_LANE_MAX entries: one lane per row, insertion sort where the keys lie;
+//   lds    at most TR_LDS_MAX: one wave per row, the row in LDS, a sorting network;
+//   hbm    longer (a hub that is the only C point): one workgroup per row, the same network on the row's keys in HBM.
+// The network is the bitonic one in its flip/disperse form, in which every exchange leaves the smaller key at the
+// smaller index: a row is padded to a power of two by slots that are never touched (they stand for keys larger than
+// all others and no exchange would move them).
+constexpr int TR_LANE_MAX = 32, TR_LDS_MAX = 2048, TR_HBM_THREADS = 256;
+
+__global__ __launch_bounds__(TB) void transpose_count_kernel(long nnz, const int *Pj, int *count)
+{
+    const long e = (long)blockIdx.x * TB + threadIdx.x;
+    if (e < nnz) atomicAdd(&count[Pj[e]], 1);
+}
+
+__global__ __launch_bounds__(TB) void transpose_place_kernel(long nnz, const int *Pj, const int *Rp, int *cursor, int *key)
+{
+    const long e = (long)blockIdx.x * TB + threadIdx.x;
+    if (e >= nnz) return;
+    const int c = Pj[e];
+    key[(long)Rp[c] + atomicAdd(&cursor[c], 1)] = (int)e;
+}
+
+// the rows of the lds and hbm forms, listed in any order (each row is ordered on its own); counts: their numbers
+__global__ __launch_bounds__(TB) void transpose_classify_kernel(int n_col, const int *Rp, int *lds_rows, int *hbm_rows, int *counts)
+{
+    const int c = blockIdx.x * TB + threadIdx.x;
+    if (c >= n_col) return;
+    const int len = Rp[c + 1] - Rp[c];
+    if (len > TR_LDS_MAX) hbm_rows[atomicAdd(&counts[1], 1)] = c;
+    else if (len > TR_LANE_MAX) lds_rows[atomicAdd(&counts[0], 1)] = c;
+}
+
+__global__ __launch_bounds__(TB) void transpose_order_lane_kernel(int n_col, const int *Rp, int *key)
+{
+    const int c = blockIdx.x * TB + threadIdx.x;
+    if (c >= n_col) return;
+    const long lo = Rp[c], hi = Rp[c + 1];
+    if (hi - lo > TR_LANE_MAX) return;
+    for (long a = lo + 1; a < hi; ++a) {
+        const int v = key[a];
+        long b = a;
+        while (b > lo && key[b - 1] > v) { key[b] = key[b - 1]; --b; }
+        key[b] = v;
+    }
+}
+
+// a[0, len) ascending, by the THREADS lanes of one workgroup; every lane of the workgroup calls it
+template <int THREADS>
+__device__ __forceinline__ void order_row(int *a, int len)
+{
+    int padded = 1;
+    while (padded < len) padded <<= 1;
+    const int pairs = padded >> 1;
+    for (int k = 2; k <= padded; k <<= 1) {
+        const int half = k >> 1;                                // flip: i in the lower half of its block of k, mirrored partner
+        for (int t = threadIdx.x; t < pairs; t += THREADS) {
+            const int i = ((t & ~(half - 1)) << 1) | (t & (half - 1)), l = i ^ (k - 1);
+            if (l < len) {
+                const int x = a[i], y = a[l];
+                if (x > y) { a[i] = y; a[l] = x; }
+            }
+        }
+        __syncthreads();
+        for (int j = k >> 2; j >= 1; j >>= 1) {                 // disperse: partner at distance j
+            for (int t = threadIdx.x; t < pairs; t += THREADS) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i + j;
+                if (l < len) {
+                    const int x = a[i], y = a[l];
+                    if (x > y) { a[i] = y; a[l] = x; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__global__ __launch_bounds__(WAVE) void transpose_order_lds_kernel(const int *rows, const int *Rp, int *key)
+{
+    __shared__ int slot[TR_LDS_MAX];
+    const int c = rows[blockIdx.x];
+    const long lo = Rp[c];
+    const int len = Rp[c + 1] - Rp[c];                          // TR_LANE_MAX < len <= TR_LDS_MAX by the classification
+    for (int t = threadIdx.x; t < len; t += WAVE) slot[t] = key[lo + t];
+    __syncthreads();
+    order_row<WAVE>(slot, len);
+    for (int t = threadIdx.x; t < len; t += WAVE) key[lo + t] = slot[t];
+}
+
+__global__ __launch_bounds__(TR_HBM_THREADS) void transpose_order_hbm_kernel(const int *rows, const int *Rp, int *key)
+{
+    const int c = rows[blockIdx.x];
+    order_row<TR_HBM_THREADS>(key + Rp[c], Rp[c + 1] - Rp[c]);
+}
+
+// one lane per entry of R: the row of P that holds position k = key[e], and the value there bit for bit
+__global__ __launch_bounds__(TB) void transpose_gather_kernel(int n_row, long nnz, const int *Pp, const unsigned long long *Px,
+                                                              const int *key, int *Rj, unsigned long long *Rx)
+{
+    const long e = (long)blockIdx.x * TB + threadIdx.x;
+    if (e >= nnz) return;
+    const int k = key[e];
+    int lo = 0, hi = n_row;                 // invariant: Pp[lo] <= k < Pp[hi]
+    while (hi - lo > 1) {
+        const int mid = lo + (hi - lo) / 2;
+        if (Pp[mid] <= k) lo = mid; else hi = mid;
+    }
+    Rj[e] = lo;
+    Rx[e] = Px[k];
+}
+
+// what the calling thread's most recent transpose did (amg_transpose_last_route)
+struct TransposeRoute { int launched = 0, lane_rows = 0, lds_rows = 0, hbm_rows = 0; };
+thread_local TransposeRoute last_transpose;
+
+// R = P^T for P (n_row x n_col, nnz entries, columns inside the matrix) in HBM into Rp (n_col + 1 offsets) and freshly
+// allocated Rj, Rx.  Without entries or rows: the offsets are zeroed and nothing is launched.
+int transpose_device(int n_row, int n_col, long nnz, const int *Pp, const int *Pj, const double *Px, DBuf &Rp, DBuf &Rj, DBuf &Rx)
+{
+    last_transpose = TransposeRoute{};
+    const size_t cbytes = sizeof(int) * ((size_t)n_col + 1);
+    CHK(Rj.alloc(sizeof(int) * (size_t)nnz));
+    CHK(Rx.alloc(sizeof(double) * (size_t)nnz));
+    if (n_row <= 0 || nnz <= 0) return Rp.zero(cbytes);
+    DBuf count, key, lds_rows, hbm_rows, counts;
+    const long lds_most = std::min<long>(n_col, nnz / (TR_LANE_MAX + 1)), hbm_most = std::min<long>(n_col, nnz / (TR_LDS_MAX + 1));
+    CHK(count.zero(cbytes));
+    CHK(Rp.alloc(cbytes));
+    CHK(key.alloc(sizeof(int) * (size_t)nnz));
+    CHK(lds_rows.alloc(sizeof(int) * (size_t)lds_most));
+    CHK(hbm_rows.alloc(sizeof(int) * (size_t)hbm_most));
+    CHK(counts.zero(sizeof(int) * 2));
+    hipLaunchKernelGGL(transpose_count_kernel, grid_for(nnz), dim3(TB), 0, nullptr, nnz, Pj, count.i());
+    LAUNCH_CHECK("transpose: count launch");
+    CHK(exclusive_scan(count.i(), Rp.i(), (size_t)n_col + 1));
+    long total = 0;
+    CHK(last_offset(Rp.i(), n_col, &total));
+    if (total != nnz) { set_error("transpose: the scan and the entries disagree"); return AMG_ESTATE; }
+    AMG_HIP(hipMemsetAsync(count.p, 0, cbytes, nullptr));
+    hipLaunchKernelGGL(transpose_place_kernel, grid_for(nnz), dim3(TB), 0, nullptr, nnz, Pj, (const int *)Rp.i(), count.i(), key.i());
+    LAUNCH_CHECK("transpose: placement launch");
+    hipLaunchKernelGGL(transpose_classify_kernel, grid_for(n_col), dim3(TB), 0, nullptr, n_col, (const int *)Rp.i(), lds_rows.i(),
+                       hbm_rows.i(), counts.i());
+    LAUNCH_CHECK("transpose: classification launch");
+    hipLaunchKernelGGL(transpose_order_lane_kernel, grid_for(n_col), dim3(TB), 0, nullptr, n_col, (const int *)Rp.i(), key.i());
+    LAUNCH_CHECK("transpose: lane form launch");
+    int longer[2] = {0, 0};
+    AMG_HIP(hipMemcpy(longer, counts.p, sizeof(longer), hipMemcpyDeviceToHost));
+    if (longer[0] < 0 || longer[0] > lds_most || longer[1] < 0 || longer[1] > hbm_most) {
+        set_error("transpose: the classification left its lists");
+        return AMG_ESTATE;
+    }
+    if (longer[0] > 0) {
+        hipLaunchKernelGGL(transpose_order_lds_kernel, dim3((unsigned)longer[0]), dim3(WAVE), 0, nullptr, (const int *)lds_rows.i(),
+                           (const int *)Rp.i(), key.i());
+        LAUNCH_CHECK("transpose: LDS form launch");
+    }
+    if (longer[1] > 0) {
+        hipLaunchKernelGGL(transpose_order_hbm_kernel, dim3((unsigned)longer[1]), dim3(TR_HBM_THREADS), 0, nullptr,
+                           (const int *)hbm_rows.i(), (const int *)Rp.i(), key.i());
+        LAUNCH_CHECK("transpose: HBM form launch");
+    }
+    hipLaunchKernelGGL(transpose_gather_kernel, grid_for(nnz), dim3(TB), 0, nullptr, n_row, nnz, Pp, (const unsigned long long *)Px,
+                       (const int *)key.i(), Rj.i(), Rx.as<unsigned long long>());
+    LAUNCH_CHECK("transpose: gather launch");
+    AMG_HIP(hipDeviceSynchronize());
+    last_transpose = TransposeRoute{1, n_col - longer[0] - longer[1], longer[0], longer[1]};
+    return 0;
+}
+
+// One bit per fact about a CSR operator in HBM, by one lane per row: ROWS_UNSORTED where a row is not strictly
+// ascending, VALUE_NOT_FINITE where a value is an infinity or a NaN.  Integer atomics: the result does not depend on order.
+constexpr int ROWS_UNSORTED = 1, VALUE_NOT_FINITE = 2;
+
+__global__ __launch_bounds__(TB) void operator_facts_kernel(int n, const int *Ap, const int *Aj, const double *Ax, int *facts)
+{
+    const int i = blockIdx.x * TB + threadIdx.x;
+    int found = 0;
+    if (i < n) {
+        const long lo = Ap[i], hi = Ap[i + 1];
+        for (long jj = lo; jj < hi; ++jj) {
+            if (jj > lo && Aj[jj] <= Aj[jj - 1]) found |= ROWS_UNSORTED;
+            if (!isfinite(Ax[jj])) found |= VALUE_NOT_FINITE;
+        }
+    }
+    if (found) atomicOr(facts, found);
+}
+
+__global__ __launch_bounds__(TB) void count_ones_kernel(int n, const int *splitting, int *total)
+{
+    const int i = blockIdx.x * TB + threadIdx.x;
+    const int ones = __syncthreads_count(i < n && splitting[i] == 1);
+    if (threadIdx.x == 0 && ones > 0) atomicAdd(total, ones);
+}
+
 }   // namespace
 
 // the columns and values of a prolongator, held for amg_extended_interpolation_fetch
@@ -1052,6 +1256,112 @@ struct amg_classical {
     DBuf Sp, Sj, Sx, splitting, Pp, Pj, Px;
     double times_ms[5] = {0, 0, 0, 0, 0};
 };
+
+// the columns and values of a transpose, held for amg_csr_transpose_fetch
+struct amg_transpose {
+    long nnz = 0;
+    DBuf Rj, Rx;
+};
+
+// A chain of classical levels.  It owns the resident operator A (n x n, nnz entries, `reversed` as the level entries
+// take it) and, between amg_classical_chain_level and amg_classical_chain_fetch, the level built from it: S, the
+// splitting and P in `level`, R and the coarse operator C beside it.  The fetch moves C into A and drops the rest.
+enum { CHAIN_IDLE = 0, CHAIN_BUILT = 1, CHAIN_REFUSED = 2 };
+struct amg_classical_chain {
+    int n = 0, reversed = 0, state = CHAIN_IDLE;
+    long nnz = 0;
+    HbmCsr A;
+    double upload_ms = 0.0;         // of A_0: reported with the first level
+    amg_classical level;
+    int n_coarse = 0, c_facts = 0;
+    long c_nnz = 0;
+    DBuf Rp, Rj, Rx, Cp, Cj, Cx;
+    double times_ms[AMG_CHAIN_STAGES] = {0, 0, 0, 0, 0, 0, 0, 0};
+    void drop_level()
+    {
+        level = amg_classical{};
+        Rp.reset(); Rj.reset(); Rx.reset(); Cp.reset(); Cj.reset(); Cx.reset();
+        state = CHAIN_IDLE;
+    }
+};
+
+// One level from an operator that is already in HBM (A: n x n with a_nnz entries; dr: the n start values): strength, the
+// strength graph, the start weights, the splitting and the interpolation into h, h.times_ms[1 .. 4] from timer's laps.
+// amg_classical_level_build runs it on what it uploaded, the chain (below) on the product its last level left.
+static int classical_level_resident(int n, const HbmCsr &A, long a_nnz, double theta, int kind, int reversed, const DBuf &dr,
+                                    int interpolation, int max_per_row, amg_classical &h, int *rounds, LapClock &timer)
+{
+    const size_t vbytes = sizeof(int) * (size_t)n, pbytes = sizeof(int) * ((size_t)n + 1);
+    h.n = n;
+
+    // 1. strength
+    CHK(strength_device(n, theta, A, a_nnz, h.Sp, h.Sj, h.Sx, &h.s_nnz));
+    h.times_ms[1] = timer.lap();
+
+    // 2. G = S without its diagonal, the pattern of T = G^T and the in-degrees
+    DBuf count, indegree, cursor, Gp, Gj, Tp, Tj;
+    CHK(count.alloc(pbytes)); CHK(indegree.zero(pbytes)); CHK(cursor.zero(vbytes));
+    CHK(Gp.alloc(pbytes)); CHK(Tp.alloc(pbytes));
+    hipLaunchKernelGGL(graph_count_kernel, grid_for((long)n + 1), dim3(TB), 0, nullptr, n, (const int *)h.Sp.i(), (const int *)h.Sj.i(),
+                       count.i(), indegree.i());
+    LAUNCH_CHECK("classical level: graph count launch");
+    CHK(exclusive_scan(count.i(), Gp.i(), (size_t)n + 1));
+    CHK(exclusive_scan(indegree.i(), Tp.i(), (size_t)n + 1));
+    long g_nnz = 0, t_nnz = 0;
+    CHK(last_offset(Gp.i(), n, &g_nnz));
+    CHK(last_offset(Tp.i(), n, &t_nnz));
+    if (g_nnz < 0 || g_nnz > h.s_nnz || t_nnz != g_nnz) { set_error("classical level: the graph scans disagree"); return AMG_ESTATE; }
+    CHK(Gj.alloc(sizeof(int) * (size_t)g_nnz)); CHK(Tj.alloc(sizeof(int) * (size_t)g_nnz));
+    hipLaunchKernelGGL(graph_fill_kernel, grid_for(n), dim3(TB), 0, nullptr, n, (const int *)h.Sp.i(), (const int *)h.Sj.i(),
+                       (const int *)Gp.i(), Gj.i(), (const int *)Tp.i(), cursor.i(), Tj.i());
+    LAUNCH_CHECK("classical level: graph fill launch");
+
+    // 3. the start weights
+    DBuf weight;
+    CHK(weight.alloc(sizeof(double) * (size_t)n));
+    hipLaunchKernelGGL(start_weights_kernel, grid_for(n), dim3(TB), 0, nullptr, n, kind, (const int *)indegree.i(), (const double *)dr.d(),
+                       weight.d());
+    LAUNCH_CHECK("classical level: weight launch");
+    AMG_HIP(hipDeviceSynchronize());
+    h.times_ms[2] = timer.lap();
+
+    // 4. the splitting
+    CHK(h.splitting.alloc(vbytes));
+    int done = 0;
+    if (kind == KIND_PMIS) {
+        DBuf Up, Uj, flag;
+        CHK(Up.alloc(pbytes)); CHK(Uj.alloc(sizeof(int) * 2 * (size_t)g_nnz)); CHK(flag.alloc(sizeof(int)));
+        hipLaunchKernelGGL(union_offsets_kernel, grid_for((long)n + 1), dim3(TB), 0, nullptr, n, (const int *)Gp.i(), (const int *)Tp.i(),
+                           Up.i());
+        LAUNCH_CHECK("classical level: union offsets launch");
+        hipLaunchKernelGGL(union_fill_kernel, grid_for(n), dim3(TB), 0, nullptr, n, (const int *)Gp.i(), (const int *)Gj.i(),
+                           (const int *)Tp.i(), (const int *)Tj.i(), (const int *)Up.i(), Uj.i());
+        LAUNCH_CHECK("classical level: union fill launch");
+        hipLaunchKernelGGL(fill_kernel, grid_for(n), dim3(TB), 0, nullptr, (long)n, -1, h.splitting.i());
+        LAUNCH_CHECK("classical level: state launch");
+        CHK(mis_rounds_device(n, Up.i(), Uj.i(), weight.d(), -1, 1, 0, h.splitting.i(), flag.i(), &done));
+    } else {
+        CHK(cljp_passes_device(n, g_nnz, Gp.i(), Gj.i(), Tp.i(), Tj.i(), weight.d(), h.splitting.i(), &done));
+    }
+    AMG_HIP(hipDeviceSynchronize());
+    h.times_ms[3] = timer.lap();
+
+    // 5. interpolation on S's pattern: extended+i reads the pattern as the strength kernel stored it, direct
+    // interpolation also the values written beside it
+    if (interpolation == INTERP_EXTENDED_I) {
+        CHK(extended_interpolation_device(n, A, h.Sp.i(), h.Sj.i(), h.splitting.i(), max_per_row, h.Pp, h.Pj, h.Px, &h.p_nnz));
+    } else {
+        CHK(interpolation_offsets_device(n, h.Sp.i(), h.Sj.i(), h.splitting.i(), h.Pp, &h.p_nnz));
+        if (h.p_nnz < 0 || h.p_nnz > h.s_nnz + n) { set_error("classical level: the interpolation scan left the matrix"); return AMG_ESTATE; }
+        CHK(h.Pj.alloc(sizeof(int) * (size_t)h.p_nnz));
+        CHK(h.Px.alloc(sizeof(double) * (size_t)h.p_nnz));
+        CHK(interpolation_fill_device(n, A, h.Sp.i(), h.Sj.i(), h.Sx.d(), h.splitting.i(), h.Pp.i(), h.Pj.i(), h.Px.d(), reversed ? -1 : 1));
+    }
+    h.times_ms[4] = timer.lap();
+
+    *rounds = done;
+    return 0;
+}
 
 extern "C" {
 
@@ -1229,7 +1539,6 @@ int amg_classical_level_build(int n, const int *Ap, const int *Aj, const double 
     if (interpolation == INTERP_EXTENDED_I) CHK(check_unique_columns(who, n, Ap, Aj));
     CHK(require_device());
     LapClock timer;
-    const size_t vbytes = sizeof(int) * (size_t)n, pbytes = sizeof(int) * ((size_t)n + 1);
     HbmCsr A;
     CHK(A.upload(n, Ap, Aj, Ax));
     DBuf dr;
@@ -1241,73 +1550,9 @@ int amg_classical_level_build(int n, const int *Ap, const int *Aj, const double 
         ~Guard() { delete h; }
     } guard{new amg_classical};
     amg_classical &h = *guard.h;
-    h.n = n;
     h.times_ms[0] = timer.lap();
-
-    // 1. strength
-    CHK(strength_device(n, theta, A, Ap[n], h.Sp, h.Sj, h.Sx, &h.s_nnz));
-    h.times_ms[1] = timer.lap();
-
-    // 2. G = S without its diagonal, the pattern of T = G^T and the in-degrees
-    DBuf count, indegree, cursor, Gp, Gj, Tp, Tj;
-    CHK(count.alloc(pbytes)); CHK(indegree.zero(pbytes)); CHK(cursor.zero(vbytes));
-    CHK(Gp.alloc(pbytes)); CHK(Tp.alloc(pbytes));
-    hipLaunchKernelGGL(graph_count_kernel, grid_for((long)n + 1), dim3(TB), 0, nullptr, n, (const int *)h.Sp.i(), (const int *)h.Sj.i(),
-                       count.i(), indegree.i());
-    LAUNCH_CHECK("classical level: graph count launch");
-    CHK(exclusive_scan(count.i(), Gp.i(), (size_t)n + 1));
-    CHK(exclusive_scan(indegree.i(), Tp.i(), (size_t)n + 1));
-    long g_nnz = 0, t_nnz = 0;
-    CHK(last_offset(Gp.i(), n, &g_nnz));
-    CHK(last_offset(Tp.i(), n, &t_nnz));
-    if (g_nnz < 0 || g_nnz > h.s_nnz || t_nnz != g_nnz) { set_error("classical level: the graph scans disagree"); return AMG_ESTATE; }
-    CHK(Gj.alloc(sizeof(int) * (size_t)g_nnz)); CHK(Tj.alloc(sizeof(int) * (size_t)g_nnz));
-    hipLaunchKernelGGL(graph_fill_kernel, grid_for(n), dim3(TB), 0, nullptr, n, (const int *)h.Sp.i(), (const int *)h.Sj.i(),
-                       (const int *)Gp.i(), Gj.i(), (const int *)Tp.i(), cursor.i(), Tj.i());
-    LAUNCH_CHECK("classical level: graph fill launch");
-
-    // 3. the start weights
-    DBuf weight;
-    CHK(weight.alloc(sizeof(double) * (size_t)n));
-    hipLaunchKernelGGL(start_weights_kernel, grid_for(n), dim3(TB), 0, nullptr, n, kind, (const int *)indegree.i(), (const double *)dr.d(),
-                       weight.d());
-    LAUNCH_CHECK("classical level: weight launch");
-    AMG_HIP(hipDeviceSynchronize());
-    h.times_ms[2] = timer.lap();
-
-    // 4. the splitting
-    CHK(h.splitting.alloc(vbytes));
     int done = 0;
-    if (kind == KIND_PMIS) {
-        DBuf Up, Uj, flag;
-        CHK(Up.alloc(pbytes)); CHK(Uj.alloc(sizeof(int) * 2 * (size_t)g_nnz)); CHK(flag.alloc(sizeof(int)));
-        hipLaunchKernelGGL(union_offsets_kernel, grid_for((long)n + 1), dim3(TB), 0, nullptr, n, (const int *)Gp.i(), (const int *)Tp.i(),
-                           Up.i());
-        LAUNCH_CHECK("classical level: union offsets launch");
-        hipLaunchKernelGGL(union_fill_kernel, grid_for(n), dim3(TB), 0, nullptr, n, (const int *)Gp.i(), (const int *)Gj.i(),
-                           (const int *)Tp.i(), (const int *)Tj.i(), (const int *)Up.i(), Uj.i());
-        LAUNCH_CHECK("classical level: union fill launch");
-        hipLaunchKernelGGL(fill_kernel, grid_for(n), dim3(TB), 0, nullptr, (long)n, -1, h.splitting.i());
-        LAUNCH_CHECK("classical level: state launch");
-        CHK(mis_rounds_device(n, Up.i(), Uj.i(), weight.d(), -1, 1, 0, h.splitting.i(), flag.i(), &done));
-    } else {
-        CHK(cljp_passes_device(n, g_nnz, Gp.i(), Gj.i(), Tp.i(), Tj.i(), weight.d(), h.splitting.i(), &done));
-    }
-    AMG_HIP(hipDeviceSynchronize());
-    h.times_ms[3] = timer.lap();
-
-    // 5. interpolation on S's pattern: extended+i reads the pattern as the strength kernel stored it, direct
-    // interpolation also the values written beside it
-    if (interpolation == INTERP_EXTENDED_I) {
-        CHK(extended_interpolation_device(n, A, h.Sp.i(), h.Sj.i(), h.splitting.i(), max_per_row, h.Pp, h.Pj, h.Px, &h.p_nnz));
-    } else {
-        CHK(interpolation_offsets_device(n, h.Sp.i(), h.Sj.i(), h.splitting.i(), h.Pp, &h.p_nnz));
-        if (h.p_nnz < 0 || h.p_nnz > h.s_nnz + n) { set_error("classical level: the interpolation scan left the matrix"); return AMG_ESTATE; }
-        CHK(h.Pj.alloc(sizeof(int) * (size_t)h.p_nnz));
-        CHK(h.Px.alloc(sizeof(double) * (size_t)h.p_nnz));
-        CHK(interpolation_fill_device(n, A, h.Sp.i(), h.Sj.i(), h.Sx.d(), h.splitting.i(), h.Pp.i(), h.Pj.i(), h.Px.d(), reversed ? -1 : 1));
-    }
-    h.times_ms[4] = timer.lap();
+    CHK(classical_level_resident(n, A, Ap[n], theta, kind, reversed, dr, interpolation, max_per_row, h, &done, timer));
 
     sizes[0] = h.s_nnz;
     sizes[1] = h.p_nnz;
@@ -1347,5 +1592,251 @@ int amg_classical_level_fetch(amg_classical *h, int *splitting, int *Pp, int *Pj
     }
     return 0;
 }
+
+// ---- R = P^T as a flat entry: host arrays in, the offsets out at once, columns and values through a handle
+
+int amg_csr_transpose_device(int n_row, int n_col, const int *Pp, const int *Pj, const double *Px, int *Rp, amg_transpose **out)
+{
+    const char *who = "transpose";
+    if (!out || !Rp) return bad(who, "bad arguments");
+    *out = nullptr;
+    if (n_col < 0) return bad(who, "negative size");
+    CHK(check_csr_arrays(who, n_row, n_col, Pp, n_row + 1, Pj, 0x7fffffff, Px, 0x7fffffff));
+    last_transpose = TransposeRoute{};
+    struct Guard {
+        amg_transpose *h;
+        ~Guard() { delete h; }
+    } guard{new amg_transpose};
+    amg_transpose &h = *guard.h;
+    h.nnz = n_row > 0 ? Pp[n_row] : 0;
+    if (h.nnz == 0) {                       // no rows or no entries: the empty result, without a launch
+        std::fill(Rp, Rp + (size_t)n_col + 1, 0);
+        *out = guard.h;
+        guard.h = nullptr;
+        return 0;
+    }
+    CHK(require_device());
+    HbmCsr P;
+    DBuf dRp;
+    CHK(P.upload(n_row, Pp, Pj, Px));
+    CHK(transpose_device(n_row, n_col, h.nnz, P.p.i(), P.j.i(), P.x.d(), dRp, h.Rj, h.Rx));
+    CHK(dRp.to_host(Rp, sizeof(int) * ((size_t)n_col + 1)));
+    *out = guard.h;
+    guard.h = nullptr;
+    return 0;
+}
+
+int amg_csr_transpose_fetch(amg_transpose *h, int *Rj, double *Rx)
+{
+    if (!h) return AMG_EINVAL;
+    struct Guard {
+        amg_transpose *h;
+        ~Guard() { delete h; }
+    } guard{h};
+    if (h->nnz > 0 && (!Rj || !Rx)) return bad("transpose fetch", "null array");
+    if (h->nnz == 0) return 0;
+    CHK(h->Rj.to_host(Rj, sizeof(int) * (size_t)h->nnz));
+    return h->Rx.to_host(Rx, sizeof(double) * (size_t)h->nnz);
+}
+
+int amg_transpose_last_route(int *out, int n)
+{
+    const int f[AMG_TRANSPOSE_ROUTE_FIELDS] = {last_transpose.launched, last_transpose.lane_rows, last_transpose.lds_rows,
+                                               last_transpose.hbm_rows};
+    for (int q = 0; out && q < n && q < AMG_TRANSPOSE_ROUTE_FIELDS; ++q) out[q] = f[q];
+    return AMG_TRANSPOSE_ROUTE_FIELDS;
+}
+
+// ---- the chain: A_l, P_l, R_l, R_l A_l and A_{l+1} stay in HBM from the upload of A_0 on
+
+int amg_classical_chain_begin(int n, const int *Ap, const int *Aj, const double *Ax, int reversed, amg_classical_chain **out)
+{
+    const char *who = "classical chain";
+    if (!out) return bad(who, "bad arguments");
+    *out = nullptr;
+    if (n <= 0) return bad(who, "an empty operator");
+    CHK(check_csr_arrays(who, n, n, Ap, n + 1, Aj, 0x7fffffff, Ax, 0x7fffffff));
+    CHK(check_unique_columns(who, n, Ap, Aj));       // extended+i and the right-hand operand of R * A both need it
+    CHK(require_device());
+    LapClock timer;
+    struct Guard {
+        amg_classical_chain *c;
+        ~Guard() { delete c; }
+    } guard{new amg_classical_chain};
+    amg_classical_chain &c = *guard.c;
+    CHK(c.A.upload(n, Ap, Aj, Ax));
+    AMG_HIP(hipDeviceSynchronize());
+    c.n = n;
+    c.nnz = Ap[n];
+    c.reversed = reversed ? 1 : 0;
+    c.upload_ms = timer.lap();
+    *out = guard.c;
+    guard.c = nullptr;
+    return 0;
+}
+
+int amg_classical_chain_level(amg_classical_chain *c, double theta, int kind, const double *r, int interpolation, int max_per_row,
+                              long *sizes, int *flags, int *rounds, double *times_ms)
+{
+    const char *who = "classical chain";
+    if (!c || !sizes || !flags) return bad(who, "bad arguments");
+    if (kind != KIND_PMIS && kind != KIND_CLJP) return bad(who, "the splitting is 0 (PMIS) or 1 (CLJP)");
+    if (interpolation != INTERP_DIRECT && interpolation != INTERP_EXTENDED_I)
+        return bad(who, "the interpolation is 0 (direct) or 1 (extended+i)");
+    if (max_per_row < 0 || (max_per_row > 0 && interpolation == INTERP_DIRECT))
+        return bad(who, "max_per_row is 0, or positive with extended+i");
+    if (c->n <= 0 || !r) return bad(who, "no resident operator or no start values");
+    if (!(theta >= 0.0 && theta <= 1.0)) return bad(who, "expected theta in [0, 1]");
+    if (c->state != CHAIN_IDLE) { set_error("classical chain: the level built last has not been fetched"); return AMG_ESTATE; }
+    // The resident operator is not checked again.  A_0 passed begin's checks; a later one is a product of spgemm.hip,
+    // which stores one entry per column and drops exact zeros, so of what the host route vets only the row order and the
+    // finiteness of the values are open, and those came with the product's facts (below).
+    const int n = c->n;
+    LapClock timer;
+    DBuf dr;
+    CHK(dr.from_host(r, sizeof(double) * (size_t)n));
+    AMG_HIP(hipDeviceSynchronize());
+    // an early return leaves the chain without a level, its resident operator as it was
+    struct Drop {
+        amg_classical_chain *c;
+        ~Drop() { if (c) c->drop_level(); }
+    } drop{c};
+    amg_classical &h = c->level;
+    std::fill(c->times_ms, c->times_ms + AMG_CHAIN_STAGES, 0.0);
+    c->times_ms[0] = c->upload_ms + timer.lap();
+    c->upload_ms = 0.0;
+    int done = 0;
+    CHK(classical_level_resident(n, c->A, c->nnz, theta, kind, c->reversed, dr, interpolation, max_per_row, h, &done, timer));
+    std::copy(h.times_ms + 1, h.times_ms + 5, c->times_ms + 1);
+
+    // 6. R = P^T; the coarse size is the number of C points
+    DBuf total;
+    CHK(total.zero(sizeof(int)));
+    hipLaunchKernelGGL(count_ones_kernel, grid_for(n), dim3(TB), 0, nullptr, n, (const int *)h.splitting.i(), total.i());
+    LAUNCH_CHECK("classical chain: coarse size launch");
+    AMG_HIP(hipMemcpy(&c->n_coarse, total.p, sizeof(int), hipMemcpyDeviceToHost));
+    if (c->n_coarse < 0 || c->n_coarse > n) { set_error("classical chain: the coarse size left the level"); return AMG_ESTATE; }
+    CHK(transpose_device(n, c->n_coarse, h.p_nnz, h.Pp.i(), h.Pj.i(), h.Px.d(), c->Rp, c->Rj, c->Rx));
+    const TransposeRoute how = last_transpose;
+    c->times_ms[5] = timer.lap();
+
+    // 7. A_c = (R * A) * P by the routes of spgemm.hip; R * A goes when the second product has run
+    int tables[2] = {0, 0};
+    int rc = 0;
+    c->c_nnz = 0;
+    {
+        DevArr<long> Ap64, Rp64, Pp64, RAp, Cp64;
+        DevArr<int> RAj, Cj;
+        DevArr<double> RAx, Cx;
+        long ra_nnz = 0;
+        int route[AMG_SPGEMM_ROUTE_FIELDS];
+        CHK(widen_rowptr_device(n, c->A.p.i(), Ap64));
+        CHK(widen_rowptr_device(c->n_coarse, c->Rp.i(), Rp64));
+        CHK(widen_rowptr_device(n, h.Pp.i(), Pp64));
+        rc = spgemm_device(c->n_coarse, n, n, h.p_nnz, Rp64, c->Rj.i(), c->Rx.d(), c->nnz, Ap64, c->A.j.i(), c->A.x.d(), &ra_nnz, RAp, RAj,
+                           RAx);
+        amg_spgemm_last_route(route, AMG_SPGEMM_ROUTE_FIELDS);
+        tables[0] = route[3];
+        if (rc == 0) {
+            rc = spgemm_device(c->n_coarse, n, c->n_coarse, ra_nnz, RAp, RAj, RAx, h.p_nnz, Pp64, h.Pj.i(), h.Px.d(), &c->c_nnz, Cp64, Cj,
+                               Cx);
+            amg_spgemm_last_route(route, AMG_SPGEMM_ROUTE_FIELDS);
+            tables[1] = route[3];
+        }
+        if (rc != 0 && rc != AMG_EINVAL) return rc;
+        if (rc == 0) {
+            CHK(c->Cp.alloc(sizeof(int) * ((size_t)c->n_coarse + 1)));
+            CHK(narrow_rowptr_device(c->n_coarse, c->c_nnz, Cp64, c->Cp.i()));
+            static_cast<DevArr<void> &>(c->Cj) = DevArr<void>(std::move(Cj));
+            static_cast<DevArr<void> &>(c->Cx) = DevArr<void>(std::move(Cx));
+        }
+    }
+    c->c_facts = 0;
+    if (rc == 0) {
+        // the row order and the finiteness of A_c in one pass over it, where it lies
+        DBuf facts;
+        CHK(facts.zero(sizeof(int)));
+        hipLaunchKernelGGL(operator_facts_kernel, grid_for(c->n_coarse), dim3(TB), 0, nullptr, c->n_coarse, (const int *)c->Cp.i(),
+                           (const int *)c->Cj.i(), (const double *)c->Cx.d(), facts.i());
+        LAUNCH_CHECK("classical chain: operator facts launch");
+        AMG_HIP(hipMemcpy(&c->c_facts, facts.p, sizeof(int), hipMemcpyDeviceToHost));
+    }
+    c->times_ms[6] = timer.lap();
+
+    sizes[0] = h.s_nnz;
+    sizes[1] = h.p_nnz;
+    sizes[2] = h.p_nnz;
+    sizes[3] = c->c_nnz;
+    sizes[4] = c->n_coarse;
+    flags[0] = rc == 0 && !(c->c_facts & ROWS_UNSORTED);
+    flags[1] = rc == 0 && !(c->c_facts & VALUE_NOT_FINITE);
+    flags[2] = tables[0];
+    flags[3] = tables[1];
+    flags[4] = how.launched; flags[5] = how.lane_rows; flags[6] = how.lds_rows; flags[7] = how.hbm_rows;
+    if (rounds) *rounds = done;
+    if (times_ms) std::copy(c->times_ms, c->times_ms + AMG_CHAIN_STAGES - 1, times_ms);
+    c->state = rc == 0 ? CHAIN_BUILT : CHAIN_REFUSED;
+    drop.c = nullptr;
+    return rc == 0 ? 0 : AMG_CHAIN_PRODUCT_REFUSED;
+}
+
+int amg_classical_chain_fetch(amg_classical_chain *c, int *splitting, int *Pp, int *Pj, double *Px, int *Rp, int *Rj, double *Rx,
+                              int *Cp, int *Cj, double *Cx, int *Sp, int *Sj, double *Sx, double *times_ms)
+{
+    const char *who = "classical chain fetch";
+    if (!c) return AMG_EINVAL;
+    if (c->state == CHAIN_IDLE) { set_error("classical chain fetch: no level has been built"); return AMG_ESTATE; }
+    // the level's buffers go whatever happens below; A_c becomes the resident operator only after a complete fetch
+    struct Drop {
+        amg_classical_chain *c;
+        ~Drop() { c->drop_level(); }
+    } drop{c};
+    const bool whole = c->state == CHAIN_BUILT;
+    amg_classical &h = c->level;
+    if (!splitting || !Pp || (h.p_nnz > 0 && (!Pj || !Px))) return bad(who, "null array");
+    const bool want_R = whole && Rp, want_C = whole && Cp;      // a caller that finishes the level on the host wants neither
+    if ((want_R && h.p_nnz > 0 && (!Rj || !Rx)) || (want_C && c->c_nnz > 0 && (!Cj || !Cx))) return bad(who, "null array");
+    LapClock timer;
+    const size_t pbytes = sizeof(int) * ((size_t)h.n + 1), cbytes = sizeof(int) * ((size_t)c->n_coarse + 1);
+    CHK(h.splitting.to_host(splitting, sizeof(int) * (size_t)h.n));
+    CHK(h.Pp.to_host(Pp, pbytes));
+    CHK(h.Pj.to_host(Pj, sizeof(int) * (size_t)h.p_nnz));
+    CHK(h.Px.to_host(Px, sizeof(double) * (size_t)h.p_nnz));
+    if (want_R) {
+        CHK(c->Rp.to_host(Rp, cbytes));
+        CHK(c->Rj.to_host(Rj, sizeof(int) * (size_t)h.p_nnz));
+        CHK(c->Rx.to_host(Rx, sizeof(double) * (size_t)h.p_nnz));
+    }
+    if (want_C) {
+        CHK(c->Cp.to_host(Cp, cbytes));
+        CHK(c->Cj.to_host(Cj, sizeof(int) * (size_t)c->c_nnz));
+        CHK(c->Cx.to_host(Cx, sizeof(double) * (size_t)c->c_nnz));
+    }
+    if (Sp) {
+        if (h.s_nnz > 0 && (!Sj || !Sx)) return bad(who, "null array");
+        hipLaunchKernelGGL(scale_rows_kernel, grid_for(h.n), dim3(TB), 0, nullptr, h.n, (const int *)h.Sp.i(), h.Sx.d());
+        LAUNCH_CHECK("classical chain: scaling launch");
+        CHK(h.Sp.to_host(Sp, pbytes));
+        CHK(h.Sj.to_host(Sj, sizeof(int) * (size_t)h.s_nnz));
+        CHK(h.Sx.to_host(Sx, sizeof(double) * (size_t)h.s_nnz));
+    }
+    if (whole) {
+        c->A.p = std::move(c->Cp); c->A.j = std::move(c->Cj); c->A.x = std::move(c->Cx);
+        c->n = c->n_coarse;
+        c->nnz = c->c_nnz;
+        c->reversed = (c->c_facts & ROWS_UNSORTED) ? 1 : 0;
+    } else {                                // the product was refused: the chain ends here, its caller begins another
+        c->A = HbmCsr{};
+        c->n = 0;
+        c->nnz = 0;
+    }
+    if (times_ms) {
+        std::copy(c->times_ms, c->times_ms + AMG_CHAIN_STAGES - 1, times_ms);
+        times_ms[AMG_CHAIN_STAGES - 1] = timer.lap();
+    }
+    return 0;
+}
+
+void amg_classical_chain_free(amg_classical_chain *c) { delete c; }
 
 }   // extern "C"

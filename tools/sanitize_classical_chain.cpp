@@ -1,0 +1,87 @@
+// Host-side checks of the transpose and chain entries under AddressSanitizer and UBSan, on the CPU: the validation that
+// runs before any launch (check_csr_arrays, check_unique_columns), the empty results and the argument refusals, on heap
+// arrays of exactly the stated sizes so that a read past them is caught.  No GPU is used: every call here returns
+// before the first device call, or with AMG_ENODEV where there is no device.  Build and run from pyamg_amd/csrc after
+// `make` (split.hip instrumented, the other objects as they are):
+//
+//   hipcc -O1 -g -std=c++17 -fPIC -ffp-contract=off --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined \
+//         -c split.hip -o /tmp/split_san.o
+//   $(hipconfig -l)/clang++ -O1 -g -std=c++17 -fsanitize=address,undefined -c ../../tools/sanitize_classical_chain.cpp \
+//         -o /tmp/main_san.o
+//   hipcc --offload-arch=gfx950 -fsanitize=address,undefined /tmp/main_san.o /tmp/split_san.o \
+//         $(ls _obj/*.o | grep -v /split.o) -ldl -o /tmp/sanitize_classical_chain && /tmp/sanitize_classical_chain
+#include <cstdint>
+
+#include "../include/amgcore_hip.h"
+
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+static int failures = 0;
+#define EXPECT(cond)                                                        \
+    do {                                                                    \
+        if (!(cond)) { std::printf("FAILED line %d: %s\n", __LINE__, #cond); ++failures; } \
+    } while (0)
+
+int main()
+{
+    // P: 3 x 4, rows stored unsorted, one column twice
+    const std::vector<int> Pp{0, 2, 5, 6}, Pj{3, 0, 1, 1, 2, 0};
+    const std::vector<double> Px{1, 2, 3, 4, 5, 6};
+    std::vector<int> Rp(5, -7);
+    amg_transpose *t = nullptr;
+
+    auto transpose = [&](const std::vector<int> &p, const std::vector<int> &j, int n_row, int n_col) {
+        std::vector<int> hp(p), hj(j);                   // exact-size heap copies
+        std::vector<double> hx(Px.begin(), Px.begin() + (long)hj.size());
+        return amg_csr_transpose_device(n_row, n_col, hp.data(), hj.data(), hx.data(), Rp.data(), &t);
+    };
+    EXPECT(transpose({1, 2, 5, 6}, Pj, 3, 4) == AMG_EINVAL && !t);             // offsets do not start at 0
+    EXPECT(transpose({0, 3, 2, 6}, Pj, 3, 4) == AMG_EINVAL && !t);             // offsets decrease
+    EXPECT(transpose(Pp, {3, 0, 1, 4, 2, 0}, 3, 4) == AMG_EINVAL && !t);       // a column outside the matrix
+    EXPECT(transpose(Pp, {3, 0, -1, 1, 2, 0}, 3, 4) == AMG_EINVAL && !t);
+    EXPECT(transpose(Pp, Pj, 3, -1) == AMG_EINVAL && !t);
+    EXPECT(Rp[0] == -7 && Rp[4] == -7);                                        // refusals leave the offsets alone
+    EXPECT(amg_csr_transpose_device(3, 4, Pp.data(), Pj.data(), Px.data(), nullptr, &t) == AMG_EINVAL);
+    EXPECT(amg_csr_transpose_device(3, 4, Pp.data(), Pj.data(), Px.data(), Rp.data(), nullptr) == AMG_EINVAL);
+    // no rows / no entries: the empty result without a device
+    EXPECT(transpose({0}, {}, 0, 4) == 0 && t && Rp[0] == 0 && Rp[4] == 0);
+    EXPECT(amg_csr_transpose_fetch(t, nullptr, nullptr) == 0);
+    Rp.assign(5, -7);
+    EXPECT(transpose({0, 0, 0, 0}, {}, 3, 4) == 0 && t && Rp[2] == 0);
+    EXPECT(amg_csr_transpose_fetch(t, nullptr, nullptr) == 0);
+    EXPECT(amg_csr_transpose_fetch(nullptr, nullptr, nullptr) == AMG_EINVAL);
+    int route[AMG_TRANSPOSE_ROUTE_FIELDS] = {-1, -1, -1, -1};
+    EXPECT(amg_transpose_last_route(route, 2) == AMG_TRANSPOSE_ROUTE_FIELDS && route[0] == 0 && route[2] == -1);
+    // with entries the call goes on to the device: without one it is AMG_ENODEV, and nothing is held
+    const int rc = transpose(Pp, Pj, 3, 4);
+    EXPECT(rc == 0 || rc == AMG_ENODEV);
+    if (rc == 0) EXPECT(amg_csr_transpose_fetch(t, nullptr, nullptr) == AMG_EINVAL);
+
+    // the chain's begin: a square operator with a column twice, outside, bad offsets
+    amg_classical_chain *c = nullptr;
+    auto begin = [&](const std::vector<int> &p, const std::vector<int> &j, int n) {
+        std::vector<int> hp(p), hj(j);
+        std::vector<double> hx(hj.size(), 1.0);
+        return amg_classical_chain_begin(n, hp.data(), hj.data(), hx.data(), 0, &c);
+    };
+    EXPECT(begin({0, 2, 4}, {0, 1, 1, 1}, 2) == AMG_EINVAL && !c);             // a column twice in a row
+    EXPECT(begin({0, 2, 4}, {0, 1, 0, 2}, 2) == AMG_EINVAL && !c);             // outside
+    EXPECT(begin({0, 2, 1}, {0, 1, 0, 1}, 2) == AMG_EINVAL && !c);
+    EXPECT(begin({0}, {}, 0) == AMG_EINVAL && !c);
+    EXPECT(amg_classical_chain_begin(2, nullptr, nullptr, nullptr, 0, &c) == AMG_EINVAL);
+    long sizes[5];
+    int flags[AMG_CHAIN_FLAG_FIELDS];
+    double r[2] = {0.1, 0.2};
+    EXPECT(amg_classical_chain_level(nullptr, 0.25, 0, r, 0, 0, sizes, flags, nullptr, nullptr) == AMG_EINVAL);
+    EXPECT(amg_classical_chain_fetch(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                     nullptr, nullptr, nullptr, nullptr) == AMG_EINVAL);
+    amg_classical_chain_free(nullptr);
+    const int rb = begin({0, 2, 4}, {0, 1, 0, 1}, 2);
+    EXPECT(rb == 0 || rb == AMG_ENODEV);
+    if (rb == 0) amg_classical_chain_free(c);
+    if (failures) std::printf("%d check(s) failed\n", failures);
+    else std::printf("all checks passed\n");
+    return failures ? 1 : 0;
+}
