@@ -127,6 +127,39 @@ def norm_bound(n, sumsq):
     return (e / (1.0 + math.sqrt(1.0 - e)) + 2 * U) * math.sqrt(sumsq)
 
 
+# --------------------------------------------------------------------------- the multi-RHS engine's norm
+# csrc/hier_multi.hip, norm_partial_multi / norm_final_multi, restated from the comment above them: "per-column ||v||^2
+# in two stages over a FIXED grid: lane t of workgroup w adds rows w 256 + t, + 2048 256, ... in order, a binary tree
+# joins the lanes, then one workgroup joins the 2048 partial sums the same way and takes the roots.  Columns never
+# meet: the tree of a column depends on n only."
+MULTI_NORM_BLOCKS, MULTI_NORM_WG = 2048, 256
+MULTI_NORM_GRID = MULTI_NORM_BLOCKS * MULTI_NORM_WG          # 524288 rows: above it a lane adds more than one row
+
+
+def _multi_tree(a):
+    """the binary tree over the last axis (256 lanes): for w = 128, 64, .. 1, lane t < w takes s[t] + s[t + w]"""
+    w = a.shape[-1] // 2
+    while w > 0:
+        a = a[..., :w] + a[..., w:2 * w]
+        w //= 2
+    return a[..., 0]
+
+
+def multi_norm_model(v):
+    """||v||_2 of one column as the multi-RHS engine forms it"""
+    v = np.asarray(v, dtype=np.float64)
+    q = v * v
+    acc = np.zeros(MULTI_NORM_GRID)                    # lane w 256 + t, from 0.0
+    for lo in range(0, len(q), MULTI_NORM_GRID):
+        seg = q[lo:lo + MULTI_NORM_GRID]
+        acc[:len(seg)] = acc[:len(seg)] + seg
+    part = _multi_tree(acc.reshape(MULTI_NORM_BLOCKS, MULTI_NORM_WG))
+    lane = np.zeros(MULTI_NORM_WG)                     # lane t adds partial sums t, t + 256, ... from 0.0
+    for lo in range(0, MULTI_NORM_BLOCKS, MULTI_NORM_WG):
+        lane = lane + part[lo:lo + MULTI_NORM_WG]
+    return math.sqrt(float(_multi_tree(lane)))
+
+
 # --------------------------------------------------------------------------- elementwise, in the kernels' order
 def scale(c, x):                    # scale_kernel
     return np.multiply(c, x)
