@@ -745,6 +745,24 @@ int amg_mis_device(int n, const int *Ap, const int *Aj, const double *y, int act
 int amg_cljp_device(int n, const int *Sp, const int *Sj, const int *Tp, const int *Tj, const double *weight0, int *splitting,
                     int *passes, double *times_ms);
 
+/* The distance-k independent set and the MIS(2) aggregation (csrc/misagg.hpp); graphs as above.
+ *
+ * amg_mis_k_device: maximal_independent_set_k_parallel (amg_core/graph.h:501-589) on the graph as handed in, which need
+ * not be symmetric: x (n ints, written) is 1 for the members and 0 for the others after at most max_iters rounds (-1:
+ * until no vertex is active).  k >= 1; y: n finite weights, the larger index winning a tie.  AMG_ESTATE when more than
+ * n rounds leave work (weights at or below -1, on which the reference does not end either).
+ *
+ * amg_mis_aggregation_device: the aggregation of section 8l on a structurally symmetric graph (the caller's check): the
+ * set with k = 2, its members with an off-diagonal entry as roots, numbered in ascending order, and the two attachment
+ * rounds.  agg (n ints): the aggregate of every vertex, -1 for a vertex without off-diagonal entries; cpts (room for n
+ * ints): the *n_agg roots, ascending.
+ *
+ * *rounds (or NULL): rounds of the set.  times_ms (or NULL): milliseconds of the upload [0], of everything that runs in
+ * HBM [1] and of the download [2]. */
+int amg_mis_k_device(int n, const int *Ap, const int *Aj, int k, const double *y, int max_iters, int *x, int *rounds, double *times_ms);
+int amg_mis_aggregation_device(int n, const int *Ap, const int *Aj, const double *y, int *agg, int *cpts, int *n_agg, int *rounds,
+                               double *times_ms);
+
 /* One level of the classical setup in HBM from one upload of A (csrc/split.hip): classical
  * strength with theta, the strength graph without its diagonal with its transpose's pattern and the in-degrees, the start
  * weights, the splitting (kind 0: PMIS, Luby's rounds on S + S^T with double(in-degree) + r; kind 1: CLJP, r then + 1.0 per

@@ -64,6 +64,8 @@ def _signatures():
         # independent sets, colourings and the CLJP splitting (graph.py, classical.py)
         "amgsetup_mis_serial": (I, [I, i, i, I, I, I, i]),
         "amgsetup_mis_parallel": (I, [I, i, i, I, I, I, i, d, I]),
+        "amgsetup_mis_k_parallel": (I, [I, i, i, I, i, d, I]),
+        "amgsetup_mis_aggregation": (I, [I, i, i, d, i, i, i]),
         "amgsetup_vertex_coloring_mis": (I, [I, i, i, i]),
         "amgsetup_vertex_coloring_first_fit": (None, [I, i, i, i, I]),
         "amgsetup_vertex_coloring_jones_plassmann": (I, [I, i, i, i, d]),

@@ -203,6 +203,8 @@ def lib():
         "amg_energy_fetch": [V, V],
         "amg_mis_device": [I, V, V, V, I, I, I, V, c_int_p, c_dbl_p],
         "amg_cljp_device": [I, V, V, V, V, V, V, c_int_p, c_dbl_p],
+        "amg_mis_k_device": [I, V, V, I, V, I, V, c_int_p, c_dbl_p],
+        "amg_mis_aggregation_device": [I, V, V, V, V, V, c_int_p, c_int_p, c_dbl_p],
         "amg_classical_level_device": [I, V, V, V, D, I, I, V, C.POINTER(C.c_void_p), C.POINTER(C.c_long), c_int_p, c_dbl_p],
         "amg_classical_level_fetch": [V, V, V, V, V, V, V, V, c_dbl_p],
         "amg_classical_level_build": [I, V, V, V, D, I, I, V, I, I, C.POINTER(C.c_void_p), C.POINTER(C.c_long), c_int_p, c_dbl_p],

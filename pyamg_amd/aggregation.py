@@ -7,7 +7,8 @@ HBM by ``multilevel_solver``; nothing here runs inside the cycle.
 Supported subset (anything else raises NotImplementedError):
   strength   'symmetric' (any theta) | 'evolution' / 'ode' (one candidate, strength.py) | None |
              ('predefined', {'C': csr})
-  aggregate  'standard' | ('predefined', {'AggOp': csr})
+  aggregate  'standard' | 'mis' / ('mis', {'device'}) (MIS(2) aggregation) |
+             ('predefined', {'AggOp': csr})
   smooth     ('jacobi', {'omega', 'degree'}) | ('energy', {'krylov': 'cg', 'maxiter', 'tol', 'degree',
              'weighting': 'local' | 'diagonal', 'device'}) (smooth.py) | None
   symmetry   'hermitian' | 'symmetric'
@@ -26,14 +27,14 @@ import numpy as np
 import scipy.sparse as sparse
 from scipy.sparse import bsr_matrix, csr_matrix, isspmatrix_bsr, isspmatrix_csr
 
-from ._host import dp as _dp, host_lib, ip as _ip, lp as _lp
+from ._host import attempt, dp as _dp, f64 as _f64, host_lib, i32 as _i32, ip as _ip, lp as _lp, route
 from .multilevel import multilevel_solver
 from .smooth import energy_prolongation_smoother
 from .smoothing import change_smoothers
 from .util import (approximate_spectral_radius, approximate_spectral_radius_device, get_diagonal,
                    release_device_operator, scale_rows, use_device_for)
 
-__all__ = ["smoothed_aggregation_solver", "standard_aggregation", "fit_candidates",
+__all__ = ["smoothed_aggregation_solver", "standard_aggregation", "mis_aggregation", "fit_candidates",
            "symmetric_strength_of_connection", "jacobi_prolongation_smoother", "energy_prolongation_smoother"]
 
 
@@ -144,6 +145,72 @@ def standard_aggregation(Cm):
     Tp = np.arange(num_rows + 1, dtype=np.intc)
     Tx = np.ones(len(Tj), dtype="int8")
     return csr_matrix((Tx, Tj, Tp), shape=shape), Cpts
+
+
+# What device=None does for mis_aggregation when a GPU is present: the host route, whatever the measurement in
+# profiles/r21_mis_aggregation.txt shows.
+MIS_DEVICE_AUTO = False
+
+
+def _mis_aggregation_device(n, Ap, Aj, y, agg, cpts, times=None):
+    """amg_mis_aggregation_device; agg and cpts (int32, n each) are written.  Returns (aggregates, rounds of the set).
+    times: a list that receives (upload, rounds, fetch) in milliseconds."""
+    from . import _lib
+    from .graph import _finite_weights
+    _finite_weights(y)
+    n_agg, rounds = C.c_int(0), C.c_int(0)
+    ms = (C.c_double * 3)()
+    _lib.check(_lib.lib().amg_mis_aggregation_device(n, Ap.ctypes.data, Aj.ctypes.data, y.ctypes.data, agg.ctypes.data,
+                                                     cpts.ctypes.data, C.byref(n_agg), C.byref(rounds), ms))
+    if times is not None:
+        times.extend([ms[0], ms[1], ms[2]])
+    return n_agg.value, rounds.value
+
+
+def _mis_aggregation_host(n, Ap, Aj, y, agg, cpts):
+    from .graph import _no_end
+    rounds = C.c_int(0)
+    n_agg = _no_end(host_lib().amgsetup_mis_aggregation(n, _ip(Ap), _ip(Aj), _dp(y), _ip(agg), _ip(cpts), C.byref(rounds)))
+    return n_agg, rounds.value
+
+
+def mis_aggregation(Cm, y=None, device=None, times=None, rounds=None):
+    """MIS(2) aggregation -> (AggOp, Cpts), shaped and typed as standard_aggregation's.
+
+    Cm : square csr_matrix with a structurally symmetric pattern (ValueError otherwise); only the pattern is read.
+    y : one weight per vertex, None draws np.random.rand(n).  The roots are the members of the distance-2 independent
+    set on y that have an off-diagonal entry; a vertex next to a root joins it, and a vertex still unassigned joins,
+    among the aggregates of its neighbours, the one whose root has the largest (y[root], root).  Vertices without
+    off-diagonal entries get a zero row.
+    device : True = the device route (finite weights only), False or None = the host route (None: the device route
+    where MIS_DEVICE_AUTO and a GPU).
+    times, rounds : lists that receive the device route's (upload, rounds, fetch) milliseconds and the rounds of the
+    set."""
+    if not isspmatrix_csr(Cm):
+        raise TypeError("expected csr_matrix")
+    if Cm.shape[0] != Cm.shape[1]:
+        raise ValueError("expected square matrix")
+    n = Cm.shape[0]
+    Ap, Aj = _i32(Cm.indptr), _i32(Cm.indices)
+    if n and not host_lib().amgsetup_pattern_symmetric(n, _ip(Ap), _ip(Aj)):
+        raise ValueError("expected a structurally symmetric pattern")
+    y = _f64(np.random.rand(n) if y is None else y)
+    if y.shape != (n,):
+        raise ValueError("expected one weight per vertex")
+    agg = np.empty(n, dtype=np.intc)
+    Cpts = np.empty(n, dtype=np.intc)
+    n_agg, ran = 0, 0
+    if n:
+        n_agg, ran = attempt(route(device, MIS_DEVICE_AUTO), lambda: _mis_aggregation_device(n, Ap, Aj, y, agg, Cpts, times),
+                             lambda: _mis_aggregation_host(n, Ap, Aj, y, agg, Cpts))
+    if rounds is not None:
+        rounds.append(ran)
+    Cpts = Cpts[:n_agg].copy()
+    if n_agg == 0:
+        return csr_matrix((n, 1), dtype="int8"), Cpts
+    mask = agg != -1
+    Tp = np.concatenate(([0], np.cumsum(mask))).astype(np.intc)
+    return csr_matrix((np.ones(Tp[-1], dtype="int8"), agg[mask], Tp), shape=(n, n_agg)), Cpts
 
 
 # --------------------------------------------------------------------------- tentative prolongator
@@ -1006,6 +1073,8 @@ def extend_hierarchy(levels, strength, aggregate, smooth, improve_candidates, ke
     fn, kwargs = unpack_arg(aggregate[len(levels) - 1])
     if fn == "standard":
         AggOp = standard_aggregation(Cm, **kwargs)[0]
+    elif fn == "mis":
+        AggOp = mis_aggregation(Cm, **kwargs)[0]        # draws the level's rand(n) here, before the spectral radius does
     elif fn == "predefined":
         AggOp = kwargs["AggOp"].tocsr()
     else:

@@ -20,7 +20,7 @@ __all__ = ["gauss_seidel", "bsr_gauss_seidel", "jacobi", "bsr_jacobi", "gauss_se
            "csr_matvec", "bsr_matvec", "overlapping_schwarz_csr", "extract_subblocks",
            "incomplete_mat_mult_csr", "apply_distance_filter", "apply_absolute_distance_filter", "min_blocks",
            "incomplete_mat_mult_bsr", "satisfy_constraints_helper", "calc_BtB", "truncate_rows_csr",
-           "maximal_independent_set_parallel", "cljp_naive_splitting", "classical_strength_of_connection",
+           "maximal_independent_set_parallel", "maximal_independent_set_k_parallel", "cljp_naive_splitting", "classical_strength_of_connection",
            "maximum_row_value", "rs_direct_interpolation_pass1", "rs_direct_interpolation_pass2"]
 
 _INDEX = np.dtype(np.intc)
@@ -255,6 +255,26 @@ def maximal_independent_set_parallel(num_rows, Ap, Aj, active, C, F, x, y, max_i
     _lib.check(_lib.lib().amg_mis_device(num_rows, Ap.ctypes.data, Aj.ctypes.data, y.ctypes.data, int(active), int(C), int(F),
                                          x.ctypes.data, ctypes.byref(rounds), None))
     return int(np.count_nonzero(x[:num_rows] == C)) - before
+
+
+def maximal_independent_set_k_parallel(num_rows, Ap, Aj, k, x, y, max_iters):
+    """graph.h:501-589 on the host (csrc/setup_host.cpp; the device route is pyamg_amd.graph.maximal_independent_set_k):
+    x (int32) becomes 1 for the members of a distance-k independent set and 0 for the others, by at most max_iters
+    rounds (-1: until the set is maximal) on the weights y (float64), the larger index winning a tie.  The graph is
+    taken as handed in."""
+    from .graph import mis_k
+    n = "maximal_independent_set_k_parallel"
+    num_rows = int(num_rows)
+    _graph_arrays(n, num_rows, (Ap, Aj, x), (y,))
+    if int(k) < 1:
+        raise ValueError("%s: k must be at least 1" % n)
+    if len(Ap) < num_rows + 1 or len(x) < num_rows or len(y) < num_rows or (num_rows and len(Aj) < Ap[num_rows]):
+        raise ValueError("%s: arrays shorter than the graph" % n)
+    if num_rows and (Ap[0] != 0 or np.any(np.diff(Ap[:num_rows + 1]) < 0)
+                     or (Ap[num_rows] and (Aj[:Ap[num_rows]].min() < 0 or Aj[:Ap[num_rows]].max() >= num_rows))):
+        raise ValueError("%s: not a CSR graph of num_rows vertices" % n)
+    if num_rows:
+        mis_k(num_rows, Ap, Aj, int(k), x, y, int(max_iters), device=False)
 
 
 def cljp_naive_splitting(n, Sp, Sj, Tp, Tj, splitting, colorflag):

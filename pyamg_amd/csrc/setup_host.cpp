@@ -1458,6 +1458,110 @@ void amgsetup_cljp_naive_splitting(int n, const int *Sp, const int *Sj, const in
     amgsetup_cljp_select(n, Sp, Sj, Tp, Tj, weight.data(), splitting);
 }
 
+namespace {
+// graph.h:469-499, out of place: the (value, key) maximum over a vertex and the columns of its row, the larger key on
+// equal values
+void propagate_max(int n, const int *Ap, const int *Aj, const int *i_keys, int *o_keys, const double *i_vals, double *o_vals)
+{
+#pragma omp parallel for schedule(static)
+    for (int i = 0; i < n; ++i) {
+        int k_max = i_keys[i];
+        double v_max = i_vals[i];
+        for (int jj = Ap[i]; jj < Ap[i + 1]; ++jj) {
+            const int j = Aj[jj], k_j = i_keys[j];
+            const double v_j = i_vals[j];
+            if (k_j == k_max) continue;
+            if (v_j < v_max) continue;
+            if (v_j > v_max || k_j > k_max) { k_max = k_j; v_max = v_j; }
+        }
+        o_keys[i] = k_max;
+        o_vals[i] = v_max;
+    }
+}
+}  // namespace
+
+// graph.h:501-589: the distance-k maximal independent set by rounds of k max-propagations of (key, y) -- an active
+// vertex whose own key returns joins -- and k propagations of the membership, which retire every vertex they reach
+// (value -1).  x: 1 for the members, 0 for the others.  max_iters == -1: until nobody is active.  Returns the number
+// of rounds run, -1 when more than n rounds leave work (an active weight at or below a retired vertex's -1: the
+// reference does not end on such weights).
+int amgsetup_mis_k_parallel(int n, const int *Ap, const int *Aj, int k, int *x, const double *y, int max_iters)
+{
+    std::vector<char> active((size_t)n, 1);
+    std::vector<int> i_keys((size_t)n), o_keys((size_t)n);
+    std::vector<double> i_vals((size_t)n), o_vals((size_t)n);
+    for (int i = 0; i < n; ++i) { i_keys[i] = i; i_vals[i] = y[i]; x[i] = 0; }
+    int rounds = 0;
+    for (int iter = 0; max_iters == -1 || iter < max_iters; ++iter) {
+        if (rounds > n) return -1;
+        ++rounds;
+        for (int t = 0; t < k; ++t) {
+            propagate_max(n, Ap, Aj, i_keys.data(), o_keys.data(), i_vals.data(), o_vals.data());
+            i_keys.swap(o_keys);
+            i_vals.swap(o_vals);
+        }
+        for (int i = 0; i < n; ++i) {
+            if (i_keys[i] == i && active[i]) x[i] = 1;
+            i_keys[i] = i;
+            i_vals[i] = x[i];
+        }
+        for (int t = 0; t < k; ++t) {
+            propagate_max(n, Ap, Aj, i_keys.data(), o_keys.data(), i_vals.data(), o_vals.data());
+            i_keys.swap(o_keys);
+            i_vals.swap(o_vals);
+        }
+        bool work_left = false;
+        for (int i = 0; i < n; ++i) {
+            if (i_vals[i] == 1) { active[i] = 0; i_vals[i] = -1; }
+            else { i_vals[i] = y[i]; work_left = true; }
+            i_keys[i] = i;
+        }
+        if (!work_left) break;
+    }
+    return rounds;
+}
+
+// MIS(2) aggregation on a structurally symmetric pattern.  Roots: the members of the
+// distance-2 set on y that have an off-diagonal entry, numbered in ascending order (cpts).  Round 1: a vertex next to a
+// root joins it.  Round 2, from round 1's result into agg: a vertex still unassigned joins, among the aggregates of its
+// round-1 neighbours, the one whose root has the largest (y[root], root).  agg: -1 for vertices without off-diagonal
+// entries.  Returns the number of aggregates (-1 as amgsetup_mis_k_parallel); *rounds: rounds of the set.
+int amgsetup_mis_aggregation(int n, const int *Ap, const int *Aj, const double *y, int *agg, int *cpts, int *rounds)
+{
+    std::vector<int> mis((size_t)n), agg1((size_t)n);
+    *rounds = amgsetup_mis_k_parallel(n, Ap, Aj, 2, mis.data(), y, -1);
+    if (*rounds < 0) return -1;
+    int n_agg = 0;
+    for (int i = 0; i < n; ++i) {
+        bool off_diagonal = false;
+        for (int jj = Ap[i]; jj < Ap[i + 1] && !off_diagonal; ++jj) off_diagonal = Aj[jj] != i;
+        if (mis[i] && off_diagonal) { mis[i] = n_agg; cpts[n_agg++] = i; }
+        else mis[i] = -1;
+    }
+    const int *number = mis.data();         // the aggregate of a root, -1 for everybody else
+#pragma omp parallel for schedule(static)
+    for (int i = 0; i < n; ++i) {
+        int a = number[i];
+        for (int jj = Ap[i]; jj < Ap[i + 1] && a < 0; ++jj) a = number[Aj[jj]];
+        agg1[i] = a;
+    }
+#pragma omp parallel for schedule(static)
+    for (int i = 0; i < n; ++i) {
+        int a = agg1[i];
+        if (a < 0) {
+            int best = -1;
+            for (int jj = Ap[i]; jj < Ap[i + 1]; ++jj) {
+                const int aj = agg1[Aj[jj]];
+                if (aj < 0) continue;
+                const int r = cpts[aj];
+                if (best < 0 || y[r] > y[best] || (y[r] == y[best] && r > best)) { best = r; a = aj; }
+            }
+        }
+        agg[i] = a;
+    }
+    return n_agg;
+}
+
 // :497-600 direct interpolation.  pass 1: row pointer of P; pass 2: entries
 int amgsetup_rs_direct_interpolation_pass1(int n_nodes, const int *Sp, const int *Sj, const int *splitting, int *Bp)
 {

@@ -6,10 +6,8 @@
 // Below them, the stages that turn a splitting into a level: classical strength, direct and extended+i interpolation
 //  and the level chained in HBM, which runs the two loops above on buffers its earlier stages
 // left there.
-#include "flat.hpp"
+#include "graph_dev.hpp"
 #include "hier.hpp"
-
-#include <rocprim/device/device_scan.hpp>
 
 #include <cfloat>
 #include <string>
@@ -242,18 +240,6 @@ int cljp_passes_device(int n, long nnz, const int *Sp, const int *Sj, const int 
         ++done;
     }
     *passes = done;
-    return 0;
-}
-
-// n + 1 offsets from 0 up, never decreasing, every column inside the matrix: nothing is launched on less
-int check_graph(const char *who, int n, const int *p, const int *j)
-{
-    if (!p || p[0] != 0) { set_error(std::string(who) + ": offsets do not start at 0"); return AMG_EINVAL; }
-    for (int i = 0; i < n; ++i)
-        if (p[i + 1] < p[i]) { set_error(std::string(who) + ": offsets decrease"); return AMG_EINVAL; }
-    if (p[n] > 0 && !j) { set_error(std::string(who) + ": null index array"); return AMG_EINVAL; }
-    for (int e = 0; e < p[n]; ++e)
-        if (j[e] < 0 || j[e] >= n) { set_error(std::string(who) + ": column index outside the graph"); return AMG_EINVAL; }
     return 0;
 }
 
@@ -538,17 +524,6 @@ __global__ __launch_bounds__(TB) void scale_rows_kernel(int n, const int *Sp, do
     }
     if (m == 0.0) m = 1.0;
     for (long jj = lo; jj < hi; ++jj) Sx[jj] = fabs(Sx[jj]) / m;
-}
-
-// out[k] = in[0] + ... + in[k - 1] for k < count
-int exclusive_scan(const int *in, int *out, size_t count)
-{
-    size_t bytes = 0;
-    AMG_HIP(rocprim::exclusive_scan(nullptr, bytes, in, out, 0, count, rocprim::plus<int>(), nullptr));
-    DBuf tmp;
-    CHK(tmp.alloc(bytes));
-    AMG_HIP(rocprim::exclusive_scan(tmp.p, bytes, in, out, 0, count, rocprim::plus<int>(), nullptr));
-    return 0;
 }
 
 int last_offset(const int *offsets, int n, long *out)
@@ -1840,3 +1815,8 @@ int amg_classical_chain_fetch(amg_classical_chain *c, int *splitting, int *Pp, i
 void amg_classical_chain_free(amg_classical_chain *c) { delete c; }
 
 }   // extern "C"
+
+// ================================================================================================ MIS(2) aggregation
+// Third part of this translation unit, kept in a file of its own: the distance-k independent set and the MIS(2)
+// aggregation, amg_mis_k_device and amg_mis_aggregation_device.
+#include "misagg.hpp"

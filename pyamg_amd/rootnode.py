@@ -6,7 +6,8 @@ The setup differs from SA in its order: the candidates are improved AFTER streng
 
 Supported subset (anything else raises NotImplementedError before any level is built):
   strength   'symmetric' | 'evolution' / 'ode' (one candidate) | None | ('predefined', {'C': csr})
-  aggregate  'standard' | ('predefined', {'AggOp': csr, 'Cnodes': array})
+  aggregate  'standard' | 'mis' / ('mis', {'device'}) (the roots of the MIS(2) aggregation are the root nodes) |
+             ('predefined', {'AggOp': csr, 'Cnodes': array})
   smooth     'energy' / ('energy', {'krylov': 'cg', 'maxiter', 'tol', 'degree', 'weighting': 'local' | 'diagonal',
              'prefilter', 'postfilter', 'device'}) | None
   symmetry   'hermitian' | 'symmetric', real operators
@@ -15,8 +16,8 @@ import numpy as np
 from scipy.sparse import bsr_matrix, csr_matrix, isspmatrix_bsr, isspmatrix_csr
 
 from ._host import outside as _outside
-from .aggregation import (_improve, _levelize_sa, _levelize_smooth, blocksize, fit_candidates, standard_aggregation,
-                          symmetric_strength_of_connection, unpack_arg)
+from .aggregation import (_improve, _levelize_sa, _levelize_smooth, blocksize, fit_candidates, mis_aggregation,
+                          standard_aggregation, symmetric_strength_of_connection, unpack_arg)
 from .multilevel import multilevel_solver
 from .smooth import energy_prolongation_smoother
 from .smoothing import change_smoothers
@@ -25,7 +26,7 @@ from .util import get_Cpt_params, scale_T
 __all__ = ["rootnode_solver"]
 
 _STRENGTH = ("symmetric", "evolution", "ode", "predefined", None)
-_AGGREGATE = ("standard", "predefined")
+_AGGREGATE = ("standard", "mis", "predefined")
 _SMOOTH = ("energy", None)
 
 
@@ -136,6 +137,8 @@ def extend_hierarchy(levels, strength, aggregate, smooth, improve_candidates, ke
     fn, kwargs = unpack_arg(aggregate[li])
     if fn == "standard":
         AggOp, Cnodes = standard_aggregation(Cm, **kwargs)
+    elif fn == "mis":
+        AggOp, Cnodes = mis_aggregation(Cm, **kwargs)
     elif fn == "predefined":
         AggOp, Cnodes = kwargs["AggOp"].tocsr(), np.asarray(kwargs["Cnodes"])
     else:
