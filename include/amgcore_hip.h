@@ -183,7 +183,7 @@ int amgcore_calc_BtB_f64(int NullDim, int Nnodes, int ColsPerBlock, const double
  * its first len - k entries are set to 0.0, so that among equal magnitudes the reference's choice survives.  One lane
  * per row, an explicit stack of at most 32 ranges, no per-row buffer: rows of any length. */
 int amgcore_truncate_rows_csr_f64(int n_row, int k, const int Sp[], int Sp_size, int Sj[], int Sj_size, double Sx[], int Sx_size);
-/* The row-parallel stages of the classical setup (amg_core/ruge_stuben.h, csrc/split.hip), float64
+/* The row-parallel stages of the classical setup (amg_core/ruge_stuben.h, csrc/classical.hip), float64
  * only, one lane per row walking it in stored order:
  * classical_strength_of_connection (:46-93): Sp, Sj[:nnz], Sx[:nnz] as the reference leaves them (count, exclusive scan,
  *   stable fill).  The row maximum starts at DBL_MIN and a NaN never replaces it; the threshold is theta * max, the test >=;
@@ -648,6 +648,7 @@ void amg_set_tile_target(int t);
  * A is level `level` of a hierarchy handle that already holds it in HBM as CSR (the handle behind the setup-time
  * spectral-radius estimate); R, P are host CSR arrays with 64-bit row pointers.  Cp receives n_coarse + 1 offsets;
  * amg_galerkin_fetch copies the Cp[n_coarse] columns / values to the host and releases the product.
+ * A fetch of a product with entries into null arrays is AMG_EINVAL and releases it all the same.
  * AMG_EINVAL (nothing left allocated) when the operator is not held as CSR or the device tables would not fit: a row
  * that outgrows the tables in LDS and has more than 2^22 products (the memory guard of csrc/spgemm.hip). */
 typedef struct amg_galerkin amg_galerkin;
@@ -745,7 +746,7 @@ int amg_mis_device(int n, const int *Ap, const int *Aj, const double *y, int act
 int amg_cljp_device(int n, const int *Sp, const int *Sj, const int *Tp, const int *Tj, const double *weight0, int *splitting,
                     int *passes, double *times_ms);
 
-/* The distance-k independent set and the MIS(2) aggregation (csrc/misagg.hpp); graphs as above.
+/* The distance-k independent set and the MIS(2) aggregation (csrc/misagg.hip); graphs as above.
  *
  * amg_mis_k_device: maximal_independent_set_k_parallel (amg_core/graph.h:501-589) on the graph as handed in, which need
  * not be symmetric: x (n ints, written) is 1 for the members and 0 for the others after at most max_iters rounds (-1:
@@ -763,7 +764,7 @@ int amg_mis_k_device(int n, const int *Ap, const int *Aj, int k, const double *y
 int amg_mis_aggregation_device(int n, const int *Ap, const int *Aj, const double *y, int *agg, int *cpts, int *n_agg, int *rounds,
                                double *times_ms);
 
-/* One level of the classical setup in HBM from one upload of A (csrc/split.hip): classical
+/* One level of the classical setup in HBM from one upload of A (csrc/classical.hip): classical
  * strength with theta, the strength graph without its diagonal with its transpose's pattern and the in-degrees, the start
  * weights, the splitting (kind 0: PMIS, Luby's rounds on S + S^T with double(in-degree) + r; kind 1: CLJP, r then + 1.0 per
  * dependent), and direct interpolation on S's pattern with the values the strength stage wrote.  A: n x n CSR on the host,
@@ -789,7 +790,7 @@ int amg_classical_level_build(int n, const int *Ap, const int *Aj, const double 
                               double *times_ms);
 
 /* R = P^T for a float64 CSR matrix P (n_row x n_col, host arrays, 32-bit offsets) with the bits and the order of scipy's
- * P.T.tocsr() (csr_tocsc, DESIGN.md section 8k, csrc/split.hip): row c of R holds the entries of column c of P in the
+ * P.T.tocsr() (csr_tocsc, DESIGN.md section 8k, csrc/transpose.hip): row c of R holds the entries of column c of P in the
  * order in which a walk over P's stored arrays meets them -- ascending row of P, and within a row of P the stored order.
  * A column stored twice in a row stays two entries in that order; nothing is summed, dropped or sorted by value; values
  * are copied bit for bit; an empty column gives repeated offsets; the rows of P may be stored in any order.  On return
@@ -849,7 +850,7 @@ int amg_classical_chain_fetch(amg_classical_chain *chain, int *splitting, int *P
                               int *Cp, int *Cj, double *Cx, int *Sp, int *Sj, double *Sx, double *times_ms);
 void amg_classical_chain_free(amg_classical_chain *chain);
 
-/* Extended+i (distance-two) interpolation (csrc/split.hip) from a float64 CSR operator A, the
+/* Extended+i (distance-two) interpolation (csrc/classical.hip) from a float64 CSR operator A, the
  * pattern of a strength matrix S of A's shape and a C/F splitting (1 = C, 0 = F), all on the host with 32-bit offsets;
  * rows in any stored order.  An F row interpolates from C_hat, its strong C neighbours and those of its strong F
  * neighbours, with the sign-filtered row sums of section 8j; every sum in the order stated there, so the result has the

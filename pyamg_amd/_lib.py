@@ -6,6 +6,7 @@ call raises ``AmgDeviceError``.
 """
 import ctypes as C
 import os
+import time
 
 import numpy as np
 
@@ -75,7 +76,7 @@ FLAT_TABLE = {
     "satisfy_constraints_helper": ("iiiiVVVIIV", True),
     "calc_BtB": ("iiiViVII", True),
     "truncate_rows_csr": ("iiIIV", True),
-    # amg_core/ruge_stuben.h, the row-parallel stages of the classical setup (csrc/split.hip)
+    # amg_core/ruge_stuben.h, the row-parallel stages of the classical setup (csrc/classical.hip)
     "classical_strength_of_connection": ("iFIIVIIV", True),
     "maximum_row_value": ("iVIIV", True),
     "rs_direct_interpolation_pass1": ("iIIII", True),
@@ -420,6 +421,26 @@ def dp(a):
     return a.ctypes.data_as(c_dbl_p)
 
 
+def allocate(specs):
+    """One uninitialised array per (count or shape, dtype) of specs, None where specs holds None."""
+    return [None if s is None else np.empty(s[0], dtype=s[1]) for s in specs]
+
+
+def fetch_result(handle, fetch, specs, *tail):
+    """The second call of a device stage: `fetch` (an amg_*_fetch entry) downloads the arrays the handle holds and
+    releases it.  specs: the (count, dtype) of each array the entry takes, None for one that is not wanted; tail: what
+    the entry takes after the arrays.  Where the host arrays cannot be allocated the entry is called with null arrays,
+    which releases the result all the same, before the error goes on.  Returns (arrays, milliseconds of the fetch)."""
+    try:
+        arrays = allocate(specs)
+    except BaseException:
+        fetch(handle, *([None] * len(specs)), *tail)
+        raise
+    t0 = time.perf_counter()
+    check(fetch(handle, *(None if a is None else a.ctypes.data for a in arrays), *tail))
+    return arrays, (time.perf_counter() - t0) * 1e3
+
+
 def device_count():
     return lib().amg_device_count()
 
@@ -447,14 +468,14 @@ def spgemm_last_route():
 
 TRANSPOSE_ROUTE_FIELDS = ("launched", "lane_rows", "lds_rows", "hbm_rows")
 # a row of R of at most TRANSPOSE_LANE_MAX entries is ordered by one lane, of at most TRANSPOSE_LDS_MAX by one wave in LDS,
-# a longer one by one workgroup in HBM (TR_LANE_MAX, TR_LDS_MAX of csrc/split.hip)
+# a longer one by one workgroup in HBM (TR_LANE_MAX, TR_LDS_MAX of csrc/transpose.hip)
 TRANSPOSE_LANE_MAX, TRANSPOSE_LDS_MAX = 32, 2048
 CHAIN_PRODUCT_REFUSED = 1
 CHAIN_FLAG_FIELDS = 8
 
 
 def transpose_last_route():
-    """What this thread's most recent device transpose did (amg_transpose_last_route, csrc/split.hip): a dict of
+    """What this thread's most recent device transpose did (amg_transpose_last_route, csrc/transpose.hip): a dict of
     TRANSPOSE_ROUTE_FIELDS."""
     out = (C.c_int * len(TRANSPOSE_ROUTE_FIELDS))()
     n = lib().amg_transpose_last_route(out, len(TRANSPOSE_ROUTE_FIELDS))

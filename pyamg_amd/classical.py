@@ -6,7 +6,7 @@ Interpolation is the reference's direct interpolation or, beyond the reference, 
 ``ruge_stuben_solver(..., interpolation='extended_i')``): the distance-two formula of De Sterck, Falgout, Nolting and
 Yang (2008, eq. 4.10) with BoomerAMG's sign filter, optionally truncated to ``max_per_row`` entries per row.  It is
 what PMIS needs: an F row without a strong C neighbour interpolates from the C neighbours of its strong F neighbours.
-Its arithmetic is DESIGN.md section 8j, and its host route (csrc/setup_host.cpp) and device route (csrc/split.hip)
+Its arithmetic is DESIGN.md section 8j, and its host route (csrc/setup_host.cpp) and device route (csrc/classical.hip)
 return the same bits for an operator and a strength matrix stored in any row order without duplicate columns.
 
 C/F splittings (1 = C, 0 = F): ``RS`` (first pass of Ruge-Stuben, sequential by construction, host only) and the
@@ -16,7 +16,7 @@ same integers:
   host    the reference's sweeps restated in csrc/setup_host.cpp;
   device  Luby's rounds / the CLJP selection passes in HBM (csrc/split.hip); weights and colourings come from the host.
 
-Classical strength and direct interpolation have the same two routes with the same bits (csrc/split.hip, DESIGN.md
+Classical strength and direct interpolation have the same two routes with the same bits (csrc/classical.hip, DESIGN.md
 section 8i); their device route takes A as canonical CSR (sorted rows, no duplicate columns, no stored zeros, finite
 values).  ``ruge_stuben_solver(..., device=True)`` with classical strength and ``CF`` 'PMIS' or 'CLJP' builds the whole
 hierarchy in HBM from one upload of A_0: every level's strength, graph, weights, splitting and
@@ -396,24 +396,16 @@ def _extended_host(n, Ap, Aj, Ax, Sp, Sj, splitting, q):
 def _extended_device(n, Ap, Aj, Ax, Sp, Sj, splitting, q, times=None):
     """amg_extended_interpolation_device and its fetch.  times: a list that receives (upload, stages, fetch) in
     milliseconds."""
-    import time
-
     from . import _lib
     handle = C.c_void_p()
     ms = (C.c_double * 2)()
     Pp = np.empty(n + 1, dtype=np.intc)
     _lib.check(_lib.lib().amg_extended_interpolation_device(n, Ap.ctypes.data, Aj.ctypes.data, Ax.ctypes.data, Sp.ctypes.data,
                                                             Sj.ctypes.data, splitting.ctypes.data, q, Pp.ctypes.data, C.byref(handle), ms))
-    t0 = time.perf_counter()
-    try:
-        Pj = np.empty(int(Pp[-1]), dtype=np.intc)
-        Px = np.empty(int(Pp[-1]), dtype=np.float64)
-    except BaseException:
-        _lib.lib().amg_extended_interpolation_fetch(handle, None, None)     # releases the result
-        raise
-    _lib.check(_lib.lib().amg_extended_interpolation_fetch(handle, Pj.ctypes.data, Px.ctypes.data))
+    nnz = int(Pp[-1])
+    (Pj, Px), fetch_ms = _lib.fetch_result(handle, _lib.lib().amg_extended_interpolation_fetch, [(nnz, np.intc), (nnz, np.float64)])
     if times is not None:
-        times.extend([ms[0], ms[1], (time.perf_counter() - t0) * 1e3])
+        times.extend([ms[0], ms[1], fetch_ms])
     return Pp, Pj, Px
 
 
@@ -451,50 +443,54 @@ _CHAINED_SPLITTINGS = {"PMIS": 0, "CLJP": 1}
 LEVEL_STAGES = ("upload", "strength", "graph", "splitting", "interpolation", "fetch")
 
 
-def classical_level_device(A, theta, CF, keep=False, times=None, product_order=False, interpolation="direct"):
-    """One level in HBM from one upload of A (amg_classical_level_build): classical strength, the strength graph and
-    its transpose, the start weights, the PMIS or CLJP splitting and the interpolation chosen (ruge_stuben_solver's
-    ``interpolation``).  Returns (splitting, P, S);
-    S, the scaled strength matrix, only with keep (None otherwise).  The random start values are drawn on the host
-    where the host route draws them: rand(n) of the global numpy RNG for PMIS, glibc rand() after srand(2448422) for
-    CLJP.  times: a list that receives the milliseconds of LEVEL_STAGES.  product_order: _operator_order."""
-    from . import _lib
-    name, q = _interpolation_choice(interpolation)
-    reverse = _operator_order(A, "the device route of a classical level", product_order)
+def _level_arguments(A, theta, CF):
+    """What both device level builders check and look up before their first call: (n, kind, draw).  draw() returns the n
+    start values, drawn where the host route draws them: rand(n) of the global numpy RNG for PMIS, glibc rand() after
+    srand(2448422) for CLJP."""
     if theta < 0 or theta > 1:
         raise ValueError("expected theta in [0,1]")
     n = A.shape[0]
     if n == 0:
         raise outside("the device route of a classical level without rows")
     kind = _CHAINED_SPLITTINGS[CF]
-    Ap, Aj, Ax = _i32(A.indptr), _i32(A.indices), np.ascontiguousarray(A.data, dtype=np.float64)
-    if kind == 0:
-        r = np.ascontiguousarray(np.random.rand(n))
-    else:
+
+    def draw():
+        if kind == 0:
+            return np.ascontiguousarray(np.random.rand(n))
         r = np.empty(n, dtype=np.float64)
         host_lib().amgsetup_cljp_random(n, _dp(r))
+        return r
+    return n, kind, draw
+
+
+def _level_specs(n, p_nnz):
+    return [(n, np.intc), (n + 1, np.intc), (p_nnz, np.intc), (p_nnz, np.float64)]
+
+
+def _csr_specs(n, nnz, wanted=True):
+    return [(n + 1, np.intc), (nnz, np.intc), (nnz, np.float64)] if wanted else [None] * 3
+
+
+def classical_level_device(A, theta, CF, keep=False, times=None, product_order=False, interpolation="direct"):
+    """One level in HBM from one upload of A (amg_classical_level_build): classical strength, the strength graph and
+    its transpose, the start weights, the PMIS or CLJP splitting and the interpolation chosen (ruge_stuben_solver's
+    ``interpolation``).  Returns (splitting, P, S);
+    S, the scaled strength matrix, only with keep (None otherwise).  The random start values are drawn on the host
+    (_level_arguments).  times: a list that receives the milliseconds of LEVEL_STAGES.  product_order: _operator_order."""
+    from . import _lib
+    name, q = _interpolation_choice(interpolation)
+    reverse = _operator_order(A, "the device route of a classical level", product_order)
+    n, kind, draw = _level_arguments(A, theta, CF)
+    Ap, Aj, Ax = _i32(A.indptr), _i32(A.indices), np.ascontiguousarray(A.data, dtype=np.float64)
+    r = draw()
     handle = C.c_void_p()
     sizes = (C.c_long * 2)()
     ms = (C.c_double * 6)()
     _lib.check(_lib.lib().amg_classical_level_build(n, Ap.ctypes.data, Aj.ctypes.data, Ax.ctypes.data, float(theta), kind,
                                                     int(reverse), r.ctypes.data, _INTERPOLATIONS[name], q or 0, C.byref(handle),
                                                     sizes, None, ms))
-    ptr = lambda a: None if a is None else a.ctypes.data
-    try:
-        splitting = np.empty(n, dtype=np.intc)
-        Pp = np.empty(n + 1, dtype=np.intc)
-        Pj = np.empty(sizes[1], dtype=np.intc)
-        Px = np.empty(sizes[1], dtype=np.float64)
-        Sp = Sj = Sx = None
-        if keep:
-            Sp = np.empty(n + 1, dtype=np.intc)
-            Sj = np.empty(sizes[0], dtype=np.intc)
-            Sx = np.empty(sizes[0], dtype=np.float64)
-    except BaseException:
-        _lib.lib().amg_classical_level_fetch(handle, None, None, None, None, None, None, None, None)    # releases the result
-        raise
-    _lib.check(_lib.lib().amg_classical_level_fetch(handle, ptr(splitting), ptr(Pp), ptr(Pj), ptr(Px), ptr(Sp), ptr(Sj), ptr(Sx),
-                                                    ms))
+    (splitting, Pp, Pj, Px, Sp, Sj, Sx), _ = _lib.fetch_result(handle, _lib.lib().amg_classical_level_fetch,
+                                                               _level_specs(n, sizes[1]) + _csr_specs(n, sizes[0], keep), ms)
     if times is not None:
         times.extend(ms[k] for k in range(6))
     S = csr_matrix((Sx, Sj, Sp), shape=A.shape) if keep else None
@@ -630,13 +626,8 @@ def _transpose_device(P):
     handle = C.c_void_p()
     _lib.check(_lib.lib().amg_csr_transpose_device(n_row, n_col, Pp.ctypes.data, Pj.ctypes.data, Px.ctypes.data, Rp.ctypes.data,
                                                    C.byref(handle)))
-    try:
-        Rj = np.empty(int(Rp[-1]), dtype=np.intc)
-        Rx = np.empty(int(Rp[-1]), dtype=np.float64)
-    except BaseException:
-        _lib.lib().amg_csr_transpose_fetch(handle, None, None)      # releases the result
-        raise
-    _lib.check(_lib.lib().amg_csr_transpose_fetch(handle, Rj.ctypes.data, Rx.ctypes.data))
+    nnz = int(Rp[-1])
+    (Rj, Rx), _ = _lib.fetch_result(handle, _lib.lib().amg_csr_transpose_fetch, [(nnz, np.intc), (nnz, np.float64)])
     return _transposed(Rp, Rj, Rx, (n_col, n_row))
 
 
@@ -650,7 +641,7 @@ def _transposed(Rp, Rj, Rx, shape):
 def transpose(P, device=None):
     """R = P^T of a CSR matrix exactly as P.T.tocsr() returns it (scipy's csr_tocsc): row c of R holds the entries of
     column c of P by ascending row of P and, within a row of P, in stored order; duplicates stay, values keep their
-    bits.  device: the host route is P.T.tocsr(), the device route the kernels of csrc/split.hip (DESIGN.md section
+    bits.  device: the host route is P.T.tocsr(), the device route the kernels of csrc/transpose.hip (DESIGN.md section
     8k, float64 only); both return the same bits."""
     if not isspmatrix_csr(P):
         raise TypeError("expected csr_matrix")
@@ -698,12 +689,7 @@ def _chain_level(levels, chain, theta, CF, keep, interpolation):
         raise outside("%s of an operator with stored zeros or non-finite values" % what)
     else:
         reverse = bool(chain.reversed)
-    if theta < 0 or theta > 1:
-        raise ValueError("expected theta in [0,1]")
-    n = A.shape[0]
-    if n == 0:
-        raise outside("the device route of a classical level without rows")
-    kind = _CHAINED_SPLITTINGS[CF]
+    n, kind, draw = _level_arguments(A, theta, CF)
     if chain.handle is None:
         Ap, Aj, Ax = _i32(A.indptr), _i32(A.indices), np.ascontiguousarray(A.data, dtype=np.float64)
         handle = C.c_void_p()
@@ -711,30 +697,18 @@ def _chain_level(levels, chain, theta, CF, keep, interpolation):
                                                         C.byref(handle)))
         chain.handle, chain.reversed, chain.finite = handle, int(reverse), True
         LAST_BUILD["uploads"] += 1
-    if kind == 0:
-        r = np.ascontiguousarray(np.random.rand(n))
-    else:
-        r = np.empty(n, dtype=np.float64)
-        host_lib().amgsetup_cljp_random(n, _dp(r))
+    r = draw()
     sizes = (C.c_long * 5)()
     flags = (C.c_int * _lib.CHAIN_FLAG_FIELDS)()
     ms = (C.c_double * len(CHAIN_STAGES))()
     rc = _chain_level_call(chain.handle, theta, kind, r, _INTERPOLATIONS[name], q or 0, sizes, flags, ms)
     s_nnz, p_nnz, r_nnz, c_nnz, n_coarse = (int(v) for v in sizes)
     refused = rc == _lib.CHAIN_PRODUCT_REFUSED or c_nnz >= _PRODUCT_ENTRIES_LIMIT
-    ptr = lambda a: None if a is None else a.ctypes.data
-    splitting = np.empty(n, dtype=np.intc)
-    Pp = np.empty(n + 1, dtype=np.intc)
-    Pj = np.empty(p_nnz, dtype=np.intc)
-    Px = np.empty(p_nnz, dtype=np.float64)
-    Rp = Rj = Rx = Cp = Cj = Cx = Sp = Sj = Sx = None
-    if not refused:
-        Rp, Rj, Rx = np.empty(n_coarse + 1, dtype=np.intc), np.empty(r_nnz, dtype=np.intc), np.empty(r_nnz, dtype=np.float64)
-        Cp, Cj, Cx = np.empty(n_coarse + 1, dtype=np.intc), np.empty(c_nnz, dtype=np.intc), np.empty(c_nnz, dtype=np.float64)
-    if keep:
-        Sp, Sj, Sx = np.empty(n + 1, dtype=np.intc), np.empty(s_nnz, dtype=np.intc), np.empty(s_nnz, dtype=np.float64)
-    _lib.check(_lib.lib().amg_classical_chain_fetch(chain.handle, ptr(splitting), ptr(Pp), ptr(Pj), ptr(Px), ptr(Rp), ptr(Rj), ptr(Rx),
-                                                    ptr(Cp), ptr(Cj), ptr(Cx), ptr(Sp), ptr(Sj), ptr(Sx), ms))
+    # the handle is the chain, which _Chain.close frees: nothing to release where an allocation fails
+    arrays = _lib.allocate(_level_specs(n, p_nnz) + _csr_specs(n_coarse, r_nnz, not refused) + _csr_specs(n_coarse, c_nnz, not refused)
+                           + _csr_specs(n, s_nnz, keep))
+    splitting, Pp, Pj, Px, Rp, Rj, Rx, Cp, Cj, Cx, Sp, Sj, Sx = arrays
+    _lib.check(_lib.lib().amg_classical_chain_fetch(chain.handle, *(None if a is None else a.ctypes.data for a in arrays), ms))
     _record_level(chained=not refused, resident=True, reversed=int(reverse), times=dict(zip(CHAIN_STAGES, ms)),
                   products=(_lib.SPGEMM_TABLES[flags[2]], _lib.SPGEMM_TABLES[flags[3]]),
                   transpose=dict(zip(_lib.TRANSPOSE_ROUTE_FIELDS, (int(v) for v in flags[4:8]))))

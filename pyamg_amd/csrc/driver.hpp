@@ -78,6 +78,37 @@ template <class T> struct __attribute__((visibility("hidden"))) DevArr {
     template <class U> U *as() const { return (U *)p; }
 };
 
+// Untyped owner for the setup stages.  Every allocation reaches 128 bytes (PAD doubles) past what was asked for, so a
+// buffer of no bytes is still a valid pointer and a 16-byte load that starts inside the array ends inside the allocation.
+// One type for the whole library (hidden, not unit-local), so that a function that crosses units can take one.
+struct __attribute__((visibility("hidden"))) DBuf : DevArr<void> {
+    int alloc(size_t bytes)
+    {
+        hipError_t e = malloc_bytes(bytes + PAD * sizeof(double));
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc", __FILE__, __LINE__);
+        return 0;
+    }
+    int zero(size_t bytes)
+    {
+        CHK(alloc(bytes));
+        AMG_HIP(hipMemset(p, 0, bytes + PAD * sizeof(double)));
+        return 0;
+    }
+    int from_host(const void *src, size_t bytes)
+    {
+        CHK(alloc(bytes));
+        if (bytes) AMG_HIP(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
+        return 0;
+    }
+    int to_host(void *dst, size_t bytes) const
+    {
+        if (bytes) AMG_HIP(hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    double *d() const { return as<double>(); }
+    int *i() const { return as<int>(); }
+};
+
 }  // namespace amg
 
 // after a launch inside a function that returns a status: leave with the launch's error, if it has one
@@ -105,36 +136,6 @@ namespace {
 // one lane per item in workgroups of TB; an empty launch still gets one workgroup
 constexpr int TB = 256;
 inline dim3 grid_for(long work) { return dim3((unsigned)std::max<long>(1, (work + TB - 1) / TB)); }
-
-// Untyped owner for the setup stages.  Every allocation reaches 128 bytes (PAD doubles) past what was asked for, so a
-// buffer of no bytes is still a valid pointer and a 16-byte load that starts inside the array ends inside the allocation.
-struct DBuf : DevArr<void> {
-    int alloc(size_t bytes)
-    {
-        hipError_t e = malloc_bytes(bytes + PAD * sizeof(double));
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc", __FILE__, __LINE__);
-        return 0;
-    }
-    int zero(size_t bytes)
-    {
-        CHK(alloc(bytes));
-        AMG_HIP(hipMemset(p, 0, bytes + PAD * sizeof(double)));
-        return 0;
-    }
-    int from_host(const void *src, size_t bytes)
-    {
-        CHK(alloc(bytes));
-        if (bytes) AMG_HIP(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
-        return 0;
-    }
-    int to_host(void *dst, size_t bytes) const
-    {
-        if (bytes) AMG_HIP(hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost));
-        return 0;
-    }
-    double *d() const { return as<double>(); }
-    int *i() const { return as<int>(); }
-};
 
 // stage timer on the steady clock: lap() is the milliseconds since the previous lap (the first: since construction)
 struct LapClock {

@@ -17,6 +17,7 @@
 // quicksort sequence on an explicit stack.
 #include "flat.hpp"
 
+#include <memory>
 #include <string>
 
 using namespace amg;
@@ -312,7 +313,7 @@ __global__ __launch_bounds__(TB) void inner_product_level_kernel(const int *Sp, 
 
 }   // namespace
 
-struct amg_energy {
+struct __attribute__((visibility("hidden"))) amg_energy {
     DBuf T;
     long n_scalar = 0;
 };
@@ -620,23 +621,19 @@ static int energy_smooth(int n_brow, int n_bcol, int R, int Cc, int ND, const in
     CHK(s.Dinv.from_host(Dinv, sizeof(double) * (size_t)n_brow * R));
     if (root_row) { CHK(s.RootAt.from_host(root_at.data(), sizeof(int) * (size_t)n_bcol)); s.rooted = true; }
     if (Bf) { CHK(s.Bf.from_host(Bf, sizeof(double) * (size_t)n_brow * R * ND)); s.fit = true; }
-    amg_energy *h = new amg_energy;
+    std::unique_ptr<amg_energy> h(new amg_energy);
     h->n_scalar = s.n_scalar;
-    int rc = h->T.from_host(Tx, vbytes);
-    if (rc == 0) rc = s.Rx.alloc(vbytes);
-    if (rc == 0) rc = s.Zx.alloc(vbytes);
-    if (rc == 0) rc = s.Px.alloc(vbytes);
-    if (rc == 0) rc = s.APx.alloc(vbytes);
-    if (rc == 0) rc = s.UB.alloc(sizeof(double) * (size_t)n_brow * R * ND);
+    CHK(h->T.from_host(Tx, vbytes));
+    CHK(s.Rx.alloc(vbytes)); CHK(s.Zx.alloc(vbytes)); CHK(s.Px.alloc(vbytes)); CHK(s.APx.alloc(vbytes));
+    CHK(s.UB.alloc(sizeof(double) * (size_t)n_brow * R * ND));
     const size_t parts = 2 * sizeof(double) * (((size_t)n_brow + TB - 1) / TB);
-    if (rc == 0) rc = s.part0.alloc(parts);
-    if (rc == 0) rc = s.part1.alloc(parts);
-    if (rc == 0 && hipDeviceSynchronize() != hipSuccess) { set_error(name + ": upload failed"); rc = AMG_ENODEV; }
+    CHK(s.part0.alloc(parts)); CHK(s.part1.alloc(parts));
+    if (hipDeviceSynchronize() != hipSuccess) { set_error(name + ": upload failed"); return AMG_ENODEV; }
     const double upload_ms = timer.lap();
-    if (rc == 0) rc = s.run(h->T.d(), maxiter, tol, iterations, trace);
+    const int rc = s.run(h->T.d(), maxiter, tol, iterations, trace);
     if (times_ms) { times_ms[0] = upload_ms; times_ms[1] = timer.lap(); }
-    if (rc != 0) { delete h; return rc; }
-    *out = h;
+    CHK(rc);
+    *out = h.release();
     return 0;
 }
 
@@ -684,13 +681,12 @@ int amgcore_truncate_rows_csr_f64(int n_row, int k, const int Sp[], int Sp_size,
 int amg_energy_fetch(amg_energy *h, double *Tx)
 {
     if (!h) return AMG_EINVAL;
-    int rc = 0;
+    std::unique_ptr<amg_energy> own(h);
     if (!Tx || hipMemcpy(Tx, h->T.p, sizeof(double) * (size_t)h->n_scalar, hipMemcpyDeviceToHost) != hipSuccess) {
         set_error("energy smoothing: download failed");
-        rc = AMG_ENODEV;
+        return AMG_ENODEV;
     }
-    delete h;
-    return rc;
+    return 0;
 }
 
 }   // extern "C"

@@ -148,7 +148,7 @@ int spgemm_square_device(int n, long nnz, const long *Ap, const int *Aj, const d
                          DevArr<double> &Cx);
 int spgemm_device(int n_row, int n_inner, int n_col, long a_nnz, const long *Ap, const int *Aj, const double *Ax, long b_nnz,
                   const long *Bp, const int *Bj, const double *Bx, long *Cnnz, DevArr<long> &Cp, DevArr<int> &Cj, DevArr<double> &Cx);
-// between the 32-bit row pointers of the classical setup (split.hip) and the 64-bit ones of the products
+// between the 32-bit row pointers of the classical setup (classical.hip) and the 64-bit ones of the products
 int widen_rowptr_device(int n, const int *p32, DevArr<long> &p64);
 int narrow_rowptr_device(int n, long nnz, const long *p64, int *p32);
 // schwarz.hip

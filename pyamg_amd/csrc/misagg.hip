@@ -3,10 +3,6 @@
 // only from arrays the previous launch wrote and writes only its own vertex, so the integers are those of the
 // reference's sequential loops however the lanes are scheduled, and there is nothing for a stale read to change.
 // Offsets are widened to 64 bits inside the kernels.
-//
-// A header and not a translation unit of its own: split.hip, the file of the graph stages, includes it once at its end
-// and so compiles these kernels and exports the two C entries; nothing else may include it.
-#pragma once
 #include "graph_dev.hpp"
 
 namespace amg {

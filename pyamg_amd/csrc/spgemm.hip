@@ -26,6 +26,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <numeric>
 #include <type_traits>
 #include <vector>
@@ -583,7 +584,7 @@ int spgemm_square_device(int n, long nnz, const long *Ap, const int *Aj, const d
     return 0;
 }
 
-// C = A * B for operands already in HBM (the Galerkin products of the classical chain, split.hip): A is n_row x n_inner,
+// C = A * B for operands already in HBM (the Galerkin products of the classical chain, classical.hip): A is n_row x n_inner,
 // B n_inner x n_col, both with 64-bit row pointers.  Same ownership rule as above.  AMG_EINVAL, with nothing moved, where
 // matmat() refuses the product or C would hold 2^31 entries or more (C's columns and the callers' offsets are ints).
 int spgemm_device(int n_row, int n_inner, int n_col, long a_nnz, const long *Ap, const int *Aj, const double *Ax, long b_nnz,
@@ -614,7 +615,7 @@ int narrow_rowptr_device(int n, long nnz, const long *p64, int *p32)
 }
 }   // namespace amg
 
-struct amg_galerkin {
+struct __attribute__((visibility("hidden"))) amg_galerkin {
     DCsr C;
     DCsrT<c128> Cz;             // the product of the complex128 entries (is_c128)
     bool is_c128 = false;
@@ -651,18 +652,17 @@ int amg_hier_galerkin(amg_hier *h, int level, int n_coarse, const int64_t *Rp, c
     if (rc != 0) return rc;
     rc = upload_dcsr(P, n, n_coarse, (const long *)Pp, Pj, Px);
     lap("P to HBM");
-    amg_galerkin *g = new amg_galerkin;
+    std::unique_ptr<amg_galerkin> g(new amg_galerkin);
     if (rc == 0) rc = matmat(RA, P, g->C);
     lap("(R*A)*P");
     P = {};
     RA = {};
-    if (rc != 0) { delete g; return rc; }
+    CHK(rc);
     if (hipMemcpy(Cp, g->C.Ap, sizeof(long) * ((size_t)n_coarse + 1), hipMemcpyDeviceToHost) != hipSuccess) {
-        delete g;
         set_error("galerkin: row pointer download failed");
         return AMG_ENODEV;
     }
-    *out = g;
+    *out = g.release();
     return 0;
 }
 
@@ -670,16 +670,16 @@ int amg_galerkin_fetch(amg_galerkin *g, int *Cj, double *Cx)
 {
     if (!g) return AMG_EINVAL;
     if (g->is_c128) { set_error("galerkin: a complex128 product is fetched with amg_galerkin_fetch_c128"); return AMG_EINVAL; }
-    int rc = 0;
+    std::unique_ptr<amg_galerkin> own(g);
     if (g->C.nnz > 0) {
+        if (!Cj || !Cx) { set_error("galerkin fetch: null array"); return AMG_EINVAL; }
         if (hipMemcpy(Cj, g->C.Aj, sizeof(int) * (size_t)g->C.nnz, hipMemcpyDeviceToHost) != hipSuccess ||
             hipMemcpy(Cx, g->C.Ax, sizeof(double) * (size_t)g->C.nnz, hipMemcpyDeviceToHost) != hipSuccess) {
             set_error("galerkin: download failed");
-            rc = AMG_ENODEV;
+            return AMG_ENODEV;
         }
     }
-    delete g;
-    return rc;
+    return 0;
 }
 
 // C = A * B for host CSR operands through the device kernels (tests; same arithmetic as amg_hier_galerkin's products)
@@ -688,18 +688,16 @@ int amg_csr_matmat_device(int n_row, int n_inner, int n_col, const int64_t *Ap, 
 {
     if (!out) return AMG_EINVAL;
     DCsr A, B;
-    int rc = upload_dcsr(A, n_row, n_inner, (const long *)Ap, Aj, Ax);
-    if (rc == 0) rc = upload_dcsr(B, n_inner, n_col, (const long *)Bp, Bj, Bx);
-    amg_galerkin *g = new amg_galerkin;
-    if (rc == 0) rc = matmat(A, B, g->C);
+    CHK(upload_dcsr(A, n_row, n_inner, (const long *)Ap, Aj, Ax));
+    CHK(upload_dcsr(B, n_inner, n_col, (const long *)Bp, Bj, Bx));
+    std::unique_ptr<amg_galerkin> g(new amg_galerkin);
+    CHK(matmat(A, B, g->C));
     A = {}; B = {};
-    if (rc != 0) { delete g; return rc; }
     if (hipMemcpy(Cp, g->C.Ap, sizeof(long) * ((size_t)n_row + 1), hipMemcpyDeviceToHost) != hipSuccess) {
-        delete g;
         set_error("matmat: row pointer download failed");
         return AMG_ENODEV;
     }
-    *out = g;
+    *out = g.release();
     return 0;
 }
 
@@ -713,19 +711,17 @@ int amg_csr_matmat_device_c128(int n_row, int n_inner, int n_col, const int64_t 
 {
     if (!out || !Ap || !Bp || !Cp || n_row < 0 || n_inner < 0 || n_col < 0) { set_error("matmat: bad arguments"); return AMG_EINVAL; }
     DCsrT<c128> A, B;
-    int rc = upload_dcsr(A, n_row, n_inner, (const long *)Ap, Aj, (const c128 *)Ax);
-    if (rc == 0) rc = upload_dcsr(B, n_inner, n_col, (const long *)Bp, Bj, (const c128 *)Bx);
-    amg_galerkin *g = new amg_galerkin;
+    CHK(upload_dcsr(A, n_row, n_inner, (const long *)Ap, Aj, (const c128 *)Ax));
+    CHK(upload_dcsr(B, n_inner, n_col, (const long *)Bp, Bj, (const c128 *)Bx));
+    std::unique_ptr<amg_galerkin> g(new amg_galerkin);
     g->is_c128 = true;
-    if (rc == 0) rc = matmat(A, B, g->Cz);
+    CHK(matmat(A, B, g->Cz));
     A = {}; B = {};
-    if (rc != 0) { delete g; return rc; }
     if (hipMemcpy(Cp, g->Cz.Ap, sizeof(long) * ((size_t)n_row + 1), hipMemcpyDeviceToHost) != hipSuccess) {
-        delete g;
         set_error("matmat: row pointer download failed");
         return AMG_ENODEV;
     }
-    *out = g;
+    *out = g.release();
     return 0;
 }
 
@@ -749,22 +745,20 @@ int amg_galerkin_device_c128(int n_fine, int n_coarse, const int64_t *Rp, const 
     if (rc != 0) return rc;
     rc = upload_dcsr(P, n_fine, n_coarse, (const long *)Pp, Pj, (const c128 *)Px);
     lap("P to HBM");
-    amg_galerkin *g = new amg_galerkin;
+    std::unique_ptr<amg_galerkin> g(new amg_galerkin);
     g->is_c128 = true;
     if (rc == 0) rc = matmat(RA, P, g->Cz);
     lap("(R*A)*P");
     P = {}; RA = {};
-    if (rc != 0) { delete g; return rc; }
+    CHK(rc);
     if (hipMemcpy(Cp, g->Cz.Ap, sizeof(long) * ((size_t)n_coarse + 1), hipMemcpyDeviceToHost) != hipSuccess) {
-        delete g;
         set_error("galerkin: row pointer download failed");
         return AMG_ENODEV;
     }
-    *out = g;
+    *out = g.release();
     return 0;
 }
 
-// columns and interleaved values (Cp[n] entries each) of a complex128 product to the host; releases it
 int amg_spgemm_last_route(int *out, int n)
 {
     const int f[AMG_SPGEMM_ROUTE_FIELDS] = {last_route.cplx, last_route.g_first, last_route.g_final, last_route.where,
@@ -773,20 +767,21 @@ int amg_spgemm_last_route(int *out, int n)
     return AMG_SPGEMM_ROUTE_FIELDS;
 }
 
+// columns and interleaved values (Cp[n] entries each) of a complex128 product to the host; releases it
 int amg_galerkin_fetch_c128(amg_galerkin *g, int *Cj, void *Cx)
 {
     if (!g) return AMG_EINVAL;
     if (!g->is_c128) { set_error("galerkin: a float64 product is fetched with amg_galerkin_fetch"); return AMG_EINVAL; }
-    int rc = 0;
+    std::unique_ptr<amg_galerkin> own(g);
     if (g->Cz.nnz > 0) {
+        if (!Cj || !Cx) { set_error("galerkin fetch: null array"); return AMG_EINVAL; }
         if (hipMemcpy(Cj, g->Cz.Aj, sizeof(int) * (size_t)g->Cz.nnz, hipMemcpyDeviceToHost) != hipSuccess ||
             hipMemcpy(Cx, g->Cz.Ax, sizeof(c128) * (size_t)g->Cz.nnz, hipMemcpyDeviceToHost) != hipSuccess) {
             set_error("galerkin: download failed");
-            rc = AMG_ENODEV;
+            return AMG_ENODEV;
         }
     }
-    delete g;
-    return rc;
+    return 0;
 }
 
 }   // extern "C"

@@ -14,6 +14,7 @@
 #include <cfloat>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <utility>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -421,7 +422,7 @@ __global__ __launch_bounds__(TB) void invert_scale_kernel(int n, const long *Sp,
 
 }   // namespace
 
-struct amg_strength {
+struct __attribute__((visibility("hidden"))) amg_strength {
     DMat C;
 };
 
@@ -599,15 +600,15 @@ int amg_evolution_strength_device(int n, const int64_t *Ap, const int *Aj, const
     CHK(bd.from_host(b, sizeof(double) * (size_t)n));
     AMG_HIP(hipDeviceSynchronize());
     const double upload_ms = timer.lap();
-    amg_strength *s = new amg_strength;
+    std::unique_ptr<amg_strength> s(new amg_strength);
     int rc = run_pipeline(A, bd.d(), rho, epsilon, k, symmetrize, s->C);
     if (rc == 0 && hipMemcpy(Cp, s->C.p, sizeof(long) * ((size_t)n + 1), hipMemcpyDeviceToHost) != hipSuccess) {
         set_error("evolution strength: offset download failed");
         rc = AMG_ENODEV;
     }
     if (times_ms) { times_ms[0] = upload_ms; times_ms[1] = timer.lap(); }
-    if (rc != 0) { delete s; return rc; }
-    *out = s;
+    CHK(rc);
+    *out = s.release();
     return 0;
 }
 
@@ -615,16 +616,15 @@ int amg_evolution_strength_device(int n, const int64_t *Ap, const int *Aj, const
 int amg_strength_fetch(amg_strength *s, int *Cj, double *Cx)
 {
     if (!s) return AMG_EINVAL;
-    int rc = 0;
+    std::unique_ptr<amg_strength> own(s);
     if (s->C.nnz > 0) {
         if (!Cj || !Cx || hipMemcpy(Cj, s->C.j, sizeof(int) * (size_t)s->C.nnz, hipMemcpyDeviceToHost) != hipSuccess ||
             hipMemcpy(Cx, s->C.x, sizeof(double) * (size_t)s->C.nnz, hipMemcpyDeviceToHost) != hipSuccess) {
             set_error("evolution strength: download failed");
-            rc = AMG_ENODEV;
+            return AMG_ENODEV;
         }
     }
-    delete s;
-    return rc;
+    return 0;
 }
 
 }   // extern "C"

@@ -3,7 +3,7 @@ colourings, by one of two routes that return the same integers:
 
   host    the reference's sequential sweeps restated in csrc/setup_host.cpp (amg_core/graph.h:34-327, :455-589);
   device  Luby's rounds run to completion in HBM (csrc/split.hip, amg_mis_device), and the rounds of the distance-k
-          set (csrc/misagg.hpp, amg_mis_k_device).
+          set (csrc/misagg.hip, amg_mis_k_device).
 
 The device route takes what has ONE answer whatever the sweep order: Luby's algorithm without a
 sweep limit on a structurally symmetric graph, which also covers the greedy serial set (priority -i) and the 'MIS'

@@ -269,7 +269,6 @@ def _cg_host(p, maxiter, tol, trace=None):
 
 def _cg_device(p, maxiter, tol, trace=None, times=None):
     """the same iteration by csrc/energy.hip; times: a list that receives (upload, iterations, fetch) in milliseconds"""
-    import time
     L = _lib.lib()
     handle = C.c_void_p()
     ms = (C.c_double * 2)()
@@ -289,11 +288,9 @@ def _cg_device(p, maxiter, tol, trace=None, times=None):
                                                        p.root_row.ctypes.data, None if p.Bf is None else p.Bf.ctypes.data,
                                                        int(maxiter), float(tol), C.byref(handle), C.byref(its),
                                                        tr.ctypes.data, ms))
-    Tx = np.empty_like(p.Tx)
-    t0 = time.perf_counter()
-    _lib.check(L.amg_energy_fetch(handle, Tx.ctypes.data))
+    (Tx,), fetch_ms = _lib.fetch_result(handle, L.amg_energy_fetch, [(p.Tx.shape, p.Tx.dtype)])
     if times is not None:
-        times.extend([ms[0], ms[1], (time.perf_counter() - t0) * 1e3])
+        times.extend([ms[0], ms[1], fetch_ms])
     if trace is not None:
         started = min(maxiter, its.value + 1)
         trace.extend([float(tr[2 * q]), float(tr[2 * q + 1])] for q in range(started))

@@ -232,7 +232,6 @@ def _device_measure(A, b, rho, epsilon, k, symmetrize_measure, times=None):
     """the pipeline of csrc/strength.hip on a sorted CSR operator without stored zeros; None when the operator holds
     duplicate entries (the host path then does what scipy does with them).  times: a list that receives
     (upload, stages, fetch) in milliseconds."""
-    import time
     from . import _lib
     if not A.has_canonical_format:
         return None
@@ -249,12 +248,9 @@ def _device_measure(A, b, rho, epsilon, k, symmetrize_measure, times=None):
                                                float(rho), float(epsilon), int(k), int(bool(symmetrize_measure)),
                                                Cp.ctypes.data, C.byref(handle), ms))
     nnz = int(Cp[n])
-    Cj = np.empty(nnz, dtype=np.intc)
-    Cx = np.empty(nnz, dtype=np.float64)
-    t0 = time.perf_counter()
-    _lib.check(L.amg_strength_fetch(handle, Cj.ctypes.data, Cx.ctypes.data))
+    (Cj, Cx), fetch_ms = _lib.fetch_result(handle, L.amg_strength_fetch, [(nnz, np.intc), (nnz, np.float64)])
     if times is not None:
-        times.extend([ms[0], ms[1], (time.perf_counter() - t0) * 1e3])
+        times.extend([ms[0], ms[1], fetch_ms])
     if nnz >= 2 ** 31:
         raise ValueError("strength matrix exceeds int32 indices")
     return csr_matrix((Cx, Cj, Cp.astype(np.intc)), shape=A.shape)

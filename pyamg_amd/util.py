@@ -364,9 +364,7 @@ def galerkin_device(A, R, P, n_coarse):
         if rc != 0:
             return None
         nnz = int(Cp[n_coarse])
-        Cj = np.empty(nnz, dtype=np.intc)
-        Cx = np.empty(nnz, dtype=np.complex128)
-        _lib.check(L.amg_galerkin_fetch_c128(g, Cj.ctypes.data, Cx.ctypes.data))
+        (Cj, Cx), _ = _lib.fetch_result(g, L.amg_galerkin_fetch_c128, [(nnz, np.intc), (nnz, np.complex128)])
         return Cp, Cj, Cx
     op = getattr(A, "_amg_devop", None)
     if op is None or not getattr(op, "h", None):
@@ -381,9 +379,7 @@ def galerkin_device(A, R, P, n_coarse):
     if rc != 0:
         return None
     nnz = int(Cp[n_coarse])
-    Cj = np.empty(nnz, dtype=np.intc)
-    Cx = np.empty(nnz, dtype=np.float64)
-    _lib.check(L.amg_galerkin_fetch(g, Cj.ctypes.data, Cx.ctypes.data))
+    (Cj, Cx), _ = _lib.fetch_result(g, L.amg_galerkin_fetch, [(nnz, np.intc), (nnz, np.float64)])
     return Cp, Cj, Cx
 
 

@@ -1,4 +1,4 @@
-"""GPU: classical strength of connection and direct interpolation on the device (csrc/split.hip) -- the flat
+"""GPU: classical strength of connection and direct interpolation on the device (csrc/classical.hip) -- the flat
 amg_core entries against every recorded native call of the reference, the device routes of pyamg_amd.classical against
 its host routes, and whole PMIS / CLJP levels built in HBM against the host hierarchy and the reference's.  Everything
 is compared on the raw bytes."""

@@ -456,3 +456,72 @@ def test_flat_table_sweeps(live):
     x = x0.copy()
     amg_core.bsr_gauss_seidel(Ab.indptr, Ab.indices, np.ravel(Ab.data), x, b, 0, n // 2, 1, 2)
     assert live() == base and not np.array_equal(x, x0)
+
+
+def _small_operator():
+    """Poisson 6 x 6 (36 rows), a checkerboard splitting and a random 48-row R, A, P triple"""
+    from pyamg_amd.aggregation import poisson
+    A = sps.csr_matrix(poisson((6, 6)))
+    A.sort_indices()
+    i = np.arange(36)
+    splitting = ((i // 6 + i % 6) % 2).astype(np.intc)
+    rng = np.random.RandomState(7)
+    G = sps.random(48, 48, density=0.1, random_state=rng, format="csr")
+    G = sps.csr_matrix(G + G.T + 4.0 * sps.identity(48))
+    P = sps.csr_matrix((rng.rand(48), (np.arange(48), np.arange(48) % 12)), shape=(48, 12))
+    return A, splitting, sps.csr_matrix(P.T), G, P
+
+
+def _trip(M, dtype):
+    return (M.indptr.astype(np.int64), M.indices.astype(np.intc), M.data.astype(dtype))
+
+
+def _fetch_site(site):
+    """-> (call, cleanup): the Python fetch site `site` on the smallest case its own GPU tests build"""
+    import energy_io
+    from pyamg_amd import classical, util
+    from pyamg_amd.smooth import energy_prolongation_smoother
+    from pyamg_amd.strength import evolution_strength_of_connection
+    A, splitting, R, G, P = _small_operator()
+    if site == "extended":
+        S = classical.classical_strength_of_connection(A, 0.25, device=False)
+        return (lambda: classical.extended_interpolation(A, S, splitting, device=True)), None
+    if site == "level":
+        return (lambda: classical.classical_level_device(A, 0.25, "PMIS", keep=True)), None
+    if site == "transpose":
+        return (lambda: classical.transpose(P, device=True)), None
+    if site == "strength":
+        return (lambda: evolution_strength_of_connection(A, np.ones(36), epsilon=4.0, k=2, rho=2.0, device=True)), None
+    if site == "energy":
+        p = energy_io.problem("aniso_17x23")
+        return (lambda: energy_prolongation_smoother(p["A"], p["T"], p["Atilde"], p["Bc"], None, (False, {}), device=True)), None
+    if site == "galerkin":
+        util.device_operator(G)
+        return ((lambda: util.galerkin_device(G, _trip(R, np.float64), _trip(P, np.float64), 12)),
+                lambda: util.release_device_operator(G))
+    assert site == "galerkin_c128"
+    return (lambda: util.galerkin_device(_trip(G, np.complex128), _trip(R, np.complex128), _trip(P, np.complex128), 12)), None
+
+
+@pytest.mark.parametrize("site", ["extended", "level", "transpose", "strength", "energy", "galerkin", "galerkin_c128"])
+def test_a_failed_host_allocation_releases_the_device_result(live, monkeypatch, site):
+    """Between a device stage's call and its fetch the host arrays are allocated (_lib.fetch_result).  Where that raises,
+    the result the handle holds is released before the error reaches the caller: the count is back where it was."""
+    from pyamg_amd import _lib
+    call, cleanup = _fetch_site(site)
+    held = []
+
+    def no_memory(specs):
+        held.append(live())
+        raise MemoryError("no host memory for %d arrays" % len(specs))
+    try:
+        base = live()
+        monkeypatch.setattr(_lib, "allocate", no_memory)
+        with pytest.raises(MemoryError, match="no host memory"):
+            call()
+        monkeypatch.undo()
+        assert held and held[0] > base          # the device call had returned and its result was alive
+        assert live() == base
+    finally:
+        if cleanup:
+            cleanup()

@@ -1,4 +1,4 @@
-"""GPU: extended+i interpolation on the device (csrc/split.hip) -- the device route against the
+"""GPU: extended+i interpolation on the device (csrc/classical.hip) -- the device route against the
 host route and the model on every designed case of extended_io, with and without truncation; PMIS hierarchies built with
 device=True against device=False; the level chained in HBM against the stages one by one; and the argument errors of
 the C entry.  Everything is compared on the raw bytes."""

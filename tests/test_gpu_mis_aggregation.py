@@ -1,4 +1,4 @@
-"""The distance-k independent set and the MIS(2) aggregation on the device (csrc/misagg.hpp: amg_mis_k_device,
+"""The distance-k independent set and the MIS(2) aggregation on the device (csrc/misagg.hip: amg_mis_k_device,
 amg_mis_aggregation_device): the set against the reference's integers (tests/golden/mis_k/cases.npz), the aggregation
 and the solvers built on it against the host route, which tests/test_mis_k_host.py and
 tests/test_mis_aggregation_host.py pin.  Every comparison is exact equality.

@@ -1,4 +1,4 @@
-"""GPU: the device transpose (csrc/split.hip) -- the flat entry amg_csr_transpose_device and
+"""GPU: the device transpose (csrc/transpose.hip) -- the flat entry amg_csr_transpose_device and
 classical.transpose(device=True) against scipy's P.T.tocsr() on every designed operand of transpose_cases and on the
 prolongators of real hierarchies, each with the form its rows of R took; the argument errors of the C entry; and the
 device allocations, which every call leaves where they were.  Everything is compared on the raw bytes."""

@@ -1,4 +1,4 @@
-"""Designed operands of the device transpose (csrc/split.hip), a pure-Python model of its
+"""Designed operands of the device transpose (csrc/transpose.hip), a pure-Python model of its
 definition -- a walk over P's stored arrays that appends every entry to the list of its column -- and the operators of
 the classical chain's hierarchies with the sizes the host route gives them.
 
@@ -10,7 +10,7 @@ import scipy.sparse as sps
 import extended_io as xio
 import splitting_io as sio
 
-LANE_MAX, LDS_MAX = 32, 2048            # TR_LANE_MAX, TR_LDS_MAX of csrc/split.hip (_lib.TRANSPOSE_*_MAX)
+LANE_MAX, LDS_MAX = 32, 2048            # TR_LANE_MAX, TR_LDS_MAX of csrc/transpose.hip (_lib.TRANSPOSE_*_MAX)
 _cache = {}
 
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Classical AMG levels: the host route against the device route (pyamg_amd/classical.py, csrc/split.hip) on
+"""Classical AMG levels: the host route against the device route (pyamg_amd/classical.py, csrc/classical.hip) on
 Poisson 500 x 500 and 100^3 with theta = 0.25, the operators of tools/bench_splitting.py.
 
   stages   classical_strength_of_connection and direct_interpolation (on the host route's PMIS splitting), each with
@@ -150,7 +150,7 @@ def main():
     a = ap.parse_args()
     operators = (("poisson 500x500", poisson((500, 500), format="csr")), ("poisson 100^3", poisson((100, 100, 100), format="csr")))
     lines = ["classical AMG levels, theta = %.2f; milliseconds, median of %d runs after one warm-up" % (THETA, a.repeat),
-             "host: csrc/setup_host.cpp (one thread) and scipy; device: csrc/split.hip",
+             "host: csrc/setup_host.cpp (one thread) and scipy; device: csrc/classical.hip",
              "", "stages: the public call with device=False / device=True",
              "%-16s %-14s %9s %10s %9s %9s %6s" % ("operator", "stage", "rows", "nnz(A)", "host", "device", "ratio")]
 

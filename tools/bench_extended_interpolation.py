@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Extended+i interpolation: the host route against the device route (pyamg_amd/classical.py, csrc/setup_host.cpp,
-csrc/split.hip) on Poisson 100^3 with theta = 0.25 and the PMIS splitting.
+csrc/classical.hip) on Poisson 100^3 with theta = 0.25 and the PMIS splitting.
 
   stage   extended_interpolation (on the host route's PMIS splitting) with device=False and device=True, without
           truncation and with max_per_row = 4: the public call, argument checks, transfers and the Python around it
@@ -92,7 +92,7 @@ def main():
     lines = []
     head = ["extended+i interpolation on Poisson 100^3, theta = %.2f, PMIS (%d of %d points are C); milliseconds, median of %d runs "
              "after one warm-up" % (THETA, int(splitting.sum()), A.shape[0], a.repeat),
-             "host: csrc/setup_host.cpp on %d threads; device: csrc/split.hip" % _host.host_lib().amgsetup_num_threads(),
+             "host: csrc/setup_host.cpp on %d threads; device: csrc/classical.hip" % _host.host_lib().amgsetup_num_threads(),
              "", "stage: the public call with device=False / device=True; the device entry's own clock: upload stages fetch",
              "%-24s %9s %10s %10s %9s %9s %6s  %8s %8s %8s" % ("interpolation", "rows", "nnz(A)", "nnz(P)", "host", "device", "ratio",
                                                                "upload", "stages", "fetch")]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """MIS(2) aggregation: the host route against the device route (pyamg_amd/aggregation.py,
-csrc/setup_host.cpp, csrc/misagg.hpp) on the symmetric strength patterns (theta = 0) of Poisson 500 x 500 and 100^3,
+csrc/setup_host.cpp, csrc/misagg.hip) on the symmetric strength patterns (theta = 0) of Poisson 500 x 500 and 100^3,
 with the host's standard_aggregation beside them for scale.
 
 Every column is the public call -- argument checks, the symmetry check, transfers and the assembly of AggOp included --
@@ -83,7 +83,7 @@ def main():
         say(table())
         return
     say(["MIS(2) aggregation on symmetric strength patterns (theta = 0); milliseconds, median of %d runs after one warm-up" % a.repeat,
-         "host: csrc/setup_host.cpp on %d threads; device: csrc/misagg.hpp" % _host.host_lib().amgsetup_num_threads(),
+         "host: csrc/setup_host.cpp on %d threads; device: csrc/misagg.hip" % _host.host_lib().amgsetup_num_threads(),
          "standard / mis host / mis device: the public calls; upload rounds fetch: the device entry's own clock",
          "%-16s %9s %10s %9s %9s %6s %9s %9s %9s  %8s %8s %8s" % ("problem", "rows", "nnz(C)", "agg std", "agg mis", "rounds", "standard",
                                                                  "mis host", "mis dev", "upload", "rounds", "fetch")])

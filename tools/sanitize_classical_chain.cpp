@@ -2,14 +2,16 @@
 // runs before any launch (check_csr_arrays, check_unique_columns), the empty results and the argument refusals, on heap
 // arrays of exactly the stated sizes so that a read past them is caught.  No GPU is used: every call here returns
 // before the first device call, or with AMG_ENODEV where there is no device.  Build and run from pyamg_amd/csrc after
-// `make` (split.hip instrumented, the other objects as they are):
+// `make` (classical.hip and transpose.hip instrumented, the other objects as they are):
 //
-//   hipcc -O1 -g -std=c++17 -fPIC -ffp-contract=off --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined \
-//         -c split.hip -o /tmp/split_san.o
+//   for u in classical transpose; do
+//     hipcc -O1 -g -std=c++17 -fPIC -ffp-contract=off --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined \
+//           -c $u.hip -o /tmp/${u}_san.o; done
 //   $(hipconfig -l)/clang++ -O1 -g -std=c++17 -fsanitize=address,undefined -c ../../tools/sanitize_classical_chain.cpp \
 //         -o /tmp/main_san.o
-//   hipcc --offload-arch=gfx950 -fsanitize=address,undefined /tmp/main_san.o /tmp/split_san.o \
-//         $(ls _obj/*.o | grep -v /split.o) -ldl -o /tmp/sanitize_classical_chain && /tmp/sanitize_classical_chain
+//   hipcc --offload-arch=gfx950 -fsanitize=address,undefined /tmp/main_san.o /tmp/classical_san.o /tmp/transpose_san.o \
+//         $(ls _obj/*.o | grep -v -e /classical.o -e /transpose.o) -ldl -o /tmp/sanitize_classical_chain \
+//     && /tmp/sanitize_classical_chain
 #include <cstdint>
 
 #include "../include/amgcore_hip.h"
@@ -81,6 +83,22 @@ int main()
     const int rb = begin({0, 2, 4}, {0, 1, 0, 1}, 2);
     EXPECT(rb == 0 || rb == AMG_ENODEV);
     if (rb == 0) amg_classical_chain_free(c);
+
+    // extended+i without rows: the empty prolongator without a device, and its fetch releases it
+    {
+        std::vector<int> Ap0{0}, Sp0{0}, Pp0{-7};
+        amg_interpolation *e = nullptr;
+        EXPECT(amg_extended_interpolation_device(0, Ap0.data(), nullptr, nullptr, Sp0.data(), nullptr, nullptr, 0, Pp0.data(), &e,
+                                                 nullptr) == 0 && e && Pp0[0] == 0);
+        EXPECT(amg_extended_interpolation_fetch(e, nullptr, nullptr) == 0);
+    }
+    // every fetch refuses a null handle
+    EXPECT(amg_extended_interpolation_fetch(nullptr, nullptr, nullptr) == AMG_EINVAL);
+    EXPECT(amg_classical_level_fetch(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == AMG_EINVAL);
+    EXPECT(amg_strength_fetch(nullptr, nullptr, nullptr) == AMG_EINVAL);
+    EXPECT(amg_energy_fetch(nullptr, nullptr) == AMG_EINVAL);
+    EXPECT(amg_galerkin_fetch(nullptr, nullptr, nullptr) == AMG_EINVAL);
+    EXPECT(amg_galerkin_fetch_c128(nullptr, nullptr, nullptr) == AMG_EINVAL);
     if (failures) std::printf("%d check(s) failed\n", failures);
     else std::printf("all checks passed\n");
     return failures ? 1 : 0;
