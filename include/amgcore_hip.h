@@ -764,6 +764,42 @@ int amg_mis_k_device(int n, const int *Ap, const int *Aj, int k, const double *y
 int amg_mis_aggregation_device(int n, const int *Ap, const int *Aj, const double *y, int *agg, int *cpts, int *n_agg, int *rounds,
                                double *times_ms);
 
+/* The smoothed-aggregation stages around the aggregation (csrc/prolong.hpp), real float64; matrices
+ * are CSR on the host with 32-bit offsets from 0 and columns inside the matrix (AMG_EINVAL otherwise, before any launch).
+ *
+ * amg_symmetric_strength_device: symmetric_strength_of_connection of an n x n operator whose rows may be unsorted, hold
+ * a column more than once, lack a diagonal entry or be empty.  d_i: the sum of row i's diagonal entries in stored order;
+ * an entry is kept when it is on the diagonal or a*a >= ((theta*theta) * |d_i|) * |d_j|; the kept entries, in stored
+ * order, become magnitudes divided by the row's largest one (by 1 where that is 0).  Sp (n + 1 offsets) is filled and
+ * *out holds the columns and values; amg_symmetric_strength_fetch copies them (Sp[n] each) and releases the result, also
+ * when it fails.
+ *
+ * amg_fit_candidates_device: the tentative prolongator of fit_candidates (amg_core/smoothed_aggregation.h:323-452).
+ * Tp, Tj: AggOp (n_fine x n_coarse, at most one entry per row; a node without one is unaggregated); B: n_fine blocks of
+ * K1 x K2 candidates, row-major.  Per aggregate, modified Gram-Schmidt over the K1 rows of each of its members in
+ * ascending node order, every norm and dot product a sequential sum from zero, the threshold tol * norm taken before the
+ * orthogonalisation.  Tx (Tp[n_fine] blocks of K1 x K2, block k that of the node whose entry is number k of AggOp) and R
+ * (n_coarse blocks of K2 x K2) are written.
+ *
+ * amg_jacobi_prolongation_device: P = T, then `degree` times P <- P - W * P with W_ik = (S_ik * dinv_i) * w, the
+ * products by the routes of amg_csr_matmat_device, the difference with the entry order and the dropped zeros of scipy's
+ * csr_minus_csr.  S: n x n; T: n x n_coarse, no column twice in a row (AMG_EINVAL); dinv: n
+ * values.  AMG_ENOTIMPL where a product route refuses.  Pp (n + 1 offsets) is filled and *out holds the columns and
+ * values for amg_jacobi_prolongation_fetch (Pp[n] each), which releases the result, also when it fails.
+ *
+ * times_ms (or NULL, three doubles): milliseconds of the upload [0] and of everything that runs in HBM [1], written by
+ * the stage entry, and of the download [2], written by amg_fit_candidates_device itself and by the two fetch entries. */
+typedef struct amg_prolong amg_prolong;
+int amg_symmetric_strength_device(int n, const int *Ap, const int *Aj, const double *Ax, double theta, int *Sp, amg_prolong **out,
+                                  double *times_ms);
+int amg_symmetric_strength_fetch(amg_prolong *h, int *Sj, double *Sx, double *times_ms);
+int amg_fit_candidates_device(int n_fine, int n_coarse, int K1, int K2, const int *Tp, const int *Tj, const double *B, double tol,
+                              double *Tx, double *R, double *times_ms);
+int amg_jacobi_prolongation_device(int n, int n_coarse, const int *Sp, const int *Sj, const double *Sx, const double *dinv, double w,
+                                   int degree, const int *Tp, const int *Tj, const double *Tx, int *Pp, amg_prolong **out,
+                                   double *times_ms);
+int amg_jacobi_prolongation_fetch(amg_prolong *h, int *Pj, double *Px, double *times_ms);
+
 /* One level of the classical setup in HBM from one upload of A (csrc/classical.hip): classical
  * strength with theta, the strength graph without its diagonal with its transpose's pattern and the in-degrees, the start
  * weights, the splitting (kind 0: PMIS, Luby's rounds on S + S^T with double(in-degree) + r; kind 1: CLJP, r then + 1.0 per

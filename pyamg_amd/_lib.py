@@ -206,6 +206,11 @@ def lib():
         "amg_cljp_device": [I, V, V, V, V, V, V, c_int_p, c_dbl_p],
         "amg_mis_k_device": [I, V, V, I, V, I, V, c_int_p, c_dbl_p],
         "amg_mis_aggregation_device": [I, V, V, V, V, V, c_int_p, c_int_p, c_dbl_p],
+        "amg_symmetric_strength_device": [I, V, V, V, D, V, C.POINTER(C.c_void_p), c_dbl_p],
+        "amg_symmetric_strength_fetch": [V, V, V, c_dbl_p],
+        "amg_fit_candidates_device": [I, I, I, I, V, V, V, D, V, V, c_dbl_p],
+        "amg_jacobi_prolongation_device": [I, I, V, V, V, V, D, I, V, V, V, V, C.POINTER(C.c_void_p), c_dbl_p],
+        "amg_jacobi_prolongation_fetch": [V, V, V, c_dbl_p],
         "amg_classical_level_device": [I, V, V, V, D, I, I, V, C.POINTER(C.c_void_p), C.POINTER(C.c_long), c_int_p, c_dbl_p],
         "amg_classical_level_fetch": [V, V, V, V, V, V, V, V, c_dbl_p],
         "amg_classical_level_build": [I, V, V, V, D, I, I, V, I, I, C.POINTER(C.c_void_p), C.POINTER(C.c_long), c_int_p, c_dbl_p],

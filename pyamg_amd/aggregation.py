@@ -5,12 +5,14 @@ travel (the GPU box).  The hierarchy is built ONCE on the host and shipped to
 HBM by ``multilevel_solver``; nothing here runs inside the cycle.
 
 Supported subset (anything else raises NotImplementedError):
-  strength   'symmetric' (any theta) | 'evolution' / 'ode' (one candidate, strength.py) | None |
+  strength   'symmetric' / ('symmetric', {'theta', 'device'}) | 'evolution' / 'ode' (one candidate, strength.py) | None |
              ('predefined', {'C': csr})
   aggregate  'standard' | 'mis' / ('mis', {'device'}) (MIS(2) aggregation) |
              ('predefined', {'AggOp': csr})
-  smooth     ('jacobi', {'omega', 'degree'}) | ('energy', {'krylov': 'cg', 'maxiter', 'tol', 'degree',
-             'weighting': 'local' | 'diagonal', 'device'}) (smooth.py) | None
+  smooth     ('jacobi', {'omega', 'degree', 'weighting', 'device'}) | ('energy', {'krylov': 'cg', 'maxiter', 'tol',
+             'degree', 'weighting': 'local' | 'diagonal', 'device'}) (smooth.py) | None
+  device     True | False | None: the device routes of strength, MIS(2) aggregation, fit_candidates and Jacobi
+             smoothing on every level
   symmetry   'hermitian' | 'symmetric'
   improve_candidates  relaxation descriptors (run on the device) | None
 
@@ -27,7 +29,7 @@ import numpy as np
 import scipy.sparse as sparse
 from scipy.sparse import bsr_matrix, csr_matrix, isspmatrix_bsr, isspmatrix_csr
 
-from ._host import attempt, dp as _dp, f64 as _f64, host_lib, i32 as _i32, ip as _ip, lp as _lp, route
+from ._host import attempt, dp as _dp, f64 as _f64, host_lib, i32 as _i32, ip as _ip, lp as _lp, outside, route
 from .multilevel import multilevel_solver
 from .smooth import energy_prolongation_smoother
 from .smoothing import change_smoothers
@@ -68,47 +70,69 @@ def blocksize(A):
 
 
 # --------------------------------------------------------------------------- strength
-def symmetric_strength_of_connection(A, theta=0):
-    """pyamg/strength.py:213-318, amg_core/smoothed_aggregation.h:49-99:
-    keep a_ij with |a_ij|^2 >= theta^2 |a_ii| |a_jj| (the diagonal always), take
-    magnitudes and scale each row by its largest entry.  Complex operators: the
-    diagonal is summed as a complex number, |d| = sqrt(re^2 + im^2) (linalg.h mynorm)
-    and |a_ij|^2 = re^2 + im^2 (mynormsq)."""
-    if theta < 0:
-        raise ValueError("expected a positive theta")
-    if isspmatrix_csr(A):
-        A = csr_matrix(A)
-        n = A.shape[0]
-        rows = np.repeat(np.arange(n), np.diff(A.indptr))
-        isdiag = rows == A.indices
-        if A.dtype.kind == "c":
-            d = np.zeros(n, dtype=A.dtype)
-            np.add.at(d, rows[isdiag], A.data[isdiag])
-            diags = np.sqrt(d.real * d.real + d.imag * d.imag)
-            normsq = A.data.real * A.data.real + A.data.imag * A.data.imag
-        else:
-            d = np.zeros(n)
-            np.add.at(d, rows[isdiag], A.data[isdiag])
-            diags = np.abs(d)
-            normsq = A.data * A.data
-        eps = (theta * theta) * diags
-        keep = isdiag | (normsq >= eps[rows] * diags[A.indices])
-        Sp = np.concatenate(([0], np.cumsum(np.bincount(rows[keep], minlength=n)))).astype(A.indptr.dtype)
-        S = csr_matrix((A.data[keep], A.indices[keep], Sp), shape=A.shape)
-    elif isspmatrix_bsr(A):
-        M, N = A.shape
-        R, Cb = A.blocksize
-        if R != Cb:
-            raise ValueError("matrix must have square blocks")
-        if theta == 0:
-            data = np.ones(len(A.indices), dtype=A.dtype)
-            S = csr_matrix((data, A.indices.copy(), A.indptr.copy()), shape=(int(M / R), int(N / Cb)))
-        else:
-            data = (np.conjugate(A.data) * A.data).reshape(-1, R * Cb).sum(axis=1)
-            Ab = csr_matrix((data, A.indices, A.indptr), shape=(int(M / R), int(N / Cb)))
-            return symmetric_strength_of_connection(Ab, theta)
+# What device=None does for each of the three stages of DESIGN.md section 8m when a GPU is present: the host route,
+# whatever profiles/r22_sa_stages.txt shows.
+SYMMETRIC_STRENGTH_DEVICE_AUTO = False
+FIT_CANDIDATES_DEVICE_AUTO = False
+JACOBI_DEVICE_AUTO = False
+
+
+def _finite_f64(what, values):
+    """the refusals every float64 device route of section 8m shares, raised before the library is touched"""
+    if values.dtype.kind == "c":
+        raise outside("%s of complex values on the device" % what)
+    if values.dtype != np.float64:
+        raise outside("%s of %s values on the device" % (what, values.dtype))
+    if not np.isfinite(values).all():
+        raise outside("%s of values that are not finite on the device" % what)
+
+
+def _symmetric_strength_device(A, theta, times=None):
+    """amg_symmetric_strength_device and its fetch on a CSR float64 operator.  times: a list that receives (upload, in
+    HBM, fetch) in milliseconds."""
+    n = A.shape[0]
+    if A.shape[0] != A.shape[1]:
+        raise outside("symmetric strength of a matrix that is not square on the device")
+    nnz = int(A.indptr[-1]) if n else 0
+    _finite_f64("symmetric strength", A.data[:nnz])
+    if nnz >= 2 ** 31:
+        raise outside("symmetric strength of 2^31 entries or more on the device")
+    from . import _lib
+    L = _lib.lib()
+    Ap, Aj, Ax = _i32(A.indptr), _i32(A.indices), _f64(A.data)
+    Sp = np.empty(n + 1, dtype=np.intc)
+    handle = C.c_void_p()
+    ms = (C.c_double * 3)()
+    _lib.check(L.amg_symmetric_strength_device(n, Ap.ctypes.data, Aj.ctypes.data, Ax.ctypes.data, float(theta), Sp.ctypes.data,
+                                               C.byref(handle), ms))
+    kept = int(Sp[-1])
+    (Sj, Sx), _ = _lib.fetch_result(handle, L.amg_symmetric_strength_fetch, [(kept, np.intc), (kept, np.float64)], ms)
+    if times is not None:
+        times.extend([ms[0], ms[1], ms[2]])
+    return csr_matrix((Sx, Sj.astype(A.indices.dtype, copy=False), Sp.astype(A.indptr.dtype, copy=False)), shape=A.shape)
+
+
+def _symmetric_strength_host(A, theta):
+    n = A.shape[0]
+    rows = np.repeat(np.arange(n), np.diff(A.indptr))
+    isdiag = rows == A.indices
+    if A.dtype.kind == "c":
+        d = np.zeros(n, dtype=A.dtype)
+        np.add.at(d, rows[isdiag], A.data[isdiag])
+        diags = np.sqrt(d.real * d.real + d.imag * d.imag)
+        normsq = A.data.real * A.data.real + A.data.imag * A.data.imag
     else:
-        raise TypeError("expected csr_matrix or bsr_matrix")
+        d = np.zeros(n)
+        np.add.at(d, rows[isdiag], A.data[isdiag])
+        diags = np.abs(d)
+        normsq = A.data * A.data
+    eps = (theta * theta) * diags
+    keep = isdiag | (normsq >= eps[rows] * diags[A.indices])
+    Sp = np.concatenate(([0], np.cumsum(np.bincount(rows[keep], minlength=n)))).astype(A.indptr.dtype)
+    return _magnitudes_by_largest(csr_matrix((A.data[keep], A.indices[keep], Sp), shape=A.shape))
+
+
+def _magnitudes_by_largest(S):
     S.data = np.abs(S.data)
     # scale_rows_by_largest_entry (util/utils.py)
     largest = np.maximum.reduceat(S.data, S.indptr[:-1][np.diff(S.indptr) > 0]) if S.nnz else np.array([])
@@ -117,6 +141,37 @@ def symmetric_strength_of_connection(A, theta=0):
     scale[scale == 0] = 1.0
     S.data = S.data / np.repeat(scale, np.diff(S.indptr))
     return S
+
+
+def symmetric_strength_of_connection(A, theta=0, device=None, times=None):
+    """pyamg/strength.py:213-318, amg_core/smoothed_aggregation.h:49-99:
+    keep a_ij with |a_ij|^2 >= theta^2 |a_ii| |a_jj| (the diagonal always), take
+    magnitudes and scale each row by its largest entry.  Complex operators: the
+    diagonal is summed as a complex number, |d| = sqrt(re^2 + im^2) (linalg.h mynorm)
+    and |a_ij|^2 = re^2 + im^2 (mynormsq).
+
+    device : True = the device route (CSR, real float64, finite values), False or None = the host
+    route (None: the device route where SYMMETRIC_STRENGTH_DEVICE_AUTO and a GPU).  A BSR operator with theta != 0
+    is reduced to its block norms on the host and handed on as CSR; with theta == 0 it stays on the host.
+    times : a list that receives the device route's (upload, in HBM, fetch) milliseconds."""
+    if theta < 0:
+        raise ValueError("expected a positive theta")
+    if isspmatrix_csr(A):
+        A = csr_matrix(A)
+        return attempt(route(device, SYMMETRIC_STRENGTH_DEVICE_AUTO), lambda: _symmetric_strength_device(A, theta, times),
+                       lambda: _symmetric_strength_host(A, theta))
+    if isspmatrix_bsr(A):
+        M, N = A.shape
+        R, Cb = A.blocksize
+        if R != Cb:
+            raise ValueError("matrix must have square blocks")
+        if theta == 0:
+            data = np.ones(len(A.indices), dtype=A.dtype)
+            return _magnitudes_by_largest(csr_matrix((data, A.indices.copy(), A.indptr.copy()), shape=(int(M / R), int(N / Cb))))
+        data = (np.conjugate(A.data) * A.data).reshape(-1, R * Cb).sum(axis=1)
+        Ab = csr_matrix((data, A.indices, A.indptr), shape=(int(M / R), int(N / Cb)))
+        return symmetric_strength_of_connection(Ab, theta, device, times)
+    raise TypeError("expected csr_matrix or bsr_matrix")
 
 
 # --------------------------------------------------------------------------- aggregation
@@ -214,9 +269,40 @@ def mis_aggregation(Cm, y=None, device=None, times=None, rounds=None):
 
 
 # --------------------------------------------------------------------------- tentative prolongator
-def fit_candidates(AggOp, B, tol=1e-10):
+def _fit_candidates_device(AggOp, B, tol, times=None):
+    """amg_fit_candidates_device: T in the layout Q.T.tobsr() has on the host route (the offsets and columns of AggOp, node
+    i's K1 x K2 block) and B_coarse.  times: a list that receives (upload, in HBM, fetch) in milliseconds."""
+    _finite_f64("fit_candidates", B)
+    N_fine, N_coarse = AggOp.shape
+    K1, K2 = int(B.shape[0] / N_fine), B.shape[1]
+    if K2 < 1:
+        raise outside("fit_candidates without candidates on the device")
+    if N_fine and np.diff(AggOp.indptr).max() > 1:
+        raise outside("fit_candidates with a node in more than one aggregate on the device")
+    if AggOp.indptr.dtype != np.intc or AggOp.indices.dtype != np.intc:
+        raise outside("fit_candidates of an AggOp without 32-bit indices on the device")     # (T carries AggOp's arrays)
+    Tp, Tj = np.array(AggOp.indptr, dtype=np.intc), np.array(AggOp.indices[:AggOp.indptr[-1]], dtype=np.intc)
+    if len(Tj) and (Tj.min() < 0 or Tj.max() >= N_coarse):
+        raise ValueError("AggOp holds a column outside the matrix")
+    from . import _lib
+    Bc = _f64(B)
+    Tx = np.empty((len(Tj), K1, K2), dtype=np.float64)
+    R = np.zeros((N_coarse, K2, K2), dtype=np.float64)
+    ms = (C.c_double * 3)()
+    _lib.check(_lib.lib().amg_fit_candidates_device(N_fine, N_coarse, K1, K2, Tp.ctypes.data, Tj.ctypes.data, Bc.ctypes.data,
+                                                    float(tol), Tx.ctypes.data, R.ctypes.data, ms))
+    if times is not None:
+        times.extend([ms[0], ms[1], ms[2]])
+    return bsr_matrix((Tx, Tj, Tp), shape=(K1 * N_fine, K2 * N_coarse), blocksize=(K1, K2)), R.reshape(-1, K2)
+
+
+def fit_candidates(AggOp, B, tol=1e-10, device=None, times=None):
     """pyamg/aggregation/tentative.py:19-166 / amg_core/smoothed_aggregation.h:323-500:
-    per aggregate, modified Gram-Schmidt QR of the candidates restricted to it."""
+    per aggregate, modified Gram-Schmidt QR of the candidates restricted to it.
+
+    device : True = the device route (float64 candidates with finite values, any K1 and K2, at most
+    one aggregate per node), False or None = the host route (None: the device route where FIT_CANDIDATES_DEVICE_AUTO and
+    a GPU).  times : a list that receives the device route's (upload, in HBM, fetch) milliseconds."""
     if not isspmatrix_csr(AggOp):
         raise TypeError("expected csr_matrix for argument AggOp")
     B = np.asarray(B)
@@ -228,6 +314,11 @@ def fit_candidates(AggOp, B, tol=1e-10):
         raise ValueError("expected 2d array for argument B")
     if B.shape[0] % AggOp.shape[0] != 0:
         raise ValueError("dimensions of AggOp %s and B %s are incompatible" % (AggOp.shape, B.shape))
+    return attempt(route(device, FIT_CANDIDATES_DEVICE_AUTO), lambda: _fit_candidates_device(AggOp, B, tol, times),
+                   lambda: _fit_candidates_host(AggOp, B, tol))
+
+
+def _fit_candidates_host(AggOp, B, tol):
     N_fine, N_coarse = AggOp.shape
     K1 = int(B.shape[0] / N_fine)
     K2 = B.shape[1]
@@ -357,30 +448,108 @@ def _aggregate_qr_c128(Qx, Ap, N_coarse, K1, K2, tol):
 
 
 # --------------------------------------------------------------------------- prolongation smoothing
+def _jacobi_weights(S, omega, weighting):
+    """(D^-1 S, w) of the smoothing step P - (w * D^-1 S) P, and D^-1 as the vector that scaled the rows: everything
+    that both routes share, the in-place sort of S by get_diagonal and the one np.random draw of the spectral radius
+    included"""
+    if weighting == "diagonal":
+        D_inv = get_diagonal(S, inv=True)
+        D_inv_S = scale_rows(S, D_inv, copy=True)
+        return D_inv_S, omega / approximate_spectral_radius(D_inv_S), D_inv
+    D = np.abs(S) * np.ones((S.shape[0], 1), dtype=S.dtype)
+    D_inv = np.zeros_like(D)
+    D_inv[D != 0] = 1.0 / np.abs(D[D != 0])
+    return scale_rows(S, D_inv, copy=True), omega, D_inv
+
+
+def _scalar_blocks(M):
+    return isspmatrix_csr(M) or (isspmatrix_bsr(M) and M.blocksize == (1, 1))
+
+
+def _jacobi_device_refusals(S, T, B, filter, weighting):
+    """what puts a call outside the device route of jacobi_prolongation_smoother, raised before the library is touched
+    and before anything is drawn or sorted"""
+    what = "Jacobi prolongation smoothing"
+    if filter:
+        raise outside("filtered prolongation smoothing")
+    if weighting not in ("diagonal", "local", "block"):
+        raise outside("weighting=%r" % (weighting,))
+    for M in (S, T):
+        if not (isspmatrix_csr(M) or isspmatrix_bsr(M)):
+            raise outside("%s of operands that are neither CSR nor BSR on the device" % what)
+        if np.dtype(M.dtype).kind == "c":
+            raise outside("%s of complex operators on the device" % what)
+        if not _scalar_blocks(M):
+            raise outside("%s with blocks larger than 1 x 1 on the device" % what)
+        if M.dtype != np.float64 or M.indptr.dtype != np.intc or M.indices.dtype != np.intc:
+            raise outside("%s of operands other than float64 with 32-bit indices on the device" % what)
+    if B is not None and np.ndim(B) == 2 and np.shape(B)[1] > 1:
+        raise outside("%s with more than one candidate on the device" % what)
+    if S.shape[0] != S.shape[1] or S.shape[1] != T.shape[0]:
+        raise ValueError("dimensions of S %s and T %s are incompatible" % (S.shape, T.shape))
+    if not _columns_once(T):
+        raise outside("%s of a prolongator with a column twice in a row on the device" % what)
+
+
+def _jacobi_device(S, T, D_inv, w, degree, times=None):
+    """amg_jacobi_prolongation_device and its fetch: the smoothed prolongator in T's format.  times: a list that receives
+    (upload, in HBM, fetch) in milliseconds."""
+    from . import _lib
+    L = _lib.lib()
+    n, nc = T.shape
+    Sp, Sj, Sx = _i32(S.indptr), _i32(S.indices), _f64(np.ravel(S.data))
+    Tp, Tj, Tx = _i32(T.indptr), _i32(T.indices), _f64(np.ravel(T.data))
+    dinv = _f64(np.ravel(D_inv))
+    Pp = np.empty(n + 1, dtype=np.intc)
+    handle = C.c_void_p()
+    ms = (C.c_double * 3)()
+    _lib.check(L.amg_jacobi_prolongation_device(n, nc, Sp.ctypes.data, Sj.ctypes.data, Sx.ctypes.data, dinv.ctypes.data, float(w),
+                                                int(degree), Tp.ctypes.data, Tj.ctypes.data, Tx.ctypes.data, Pp.ctypes.data,
+                                                C.byref(handle), ms))
+    nnz = int(Pp[-1])
+    (Pj, Px), _ = _lib.fetch_result(handle, L.amg_jacobi_prolongation_fetch, [(nnz, np.intc), (nnz, np.float64)], ms)
+    if times is not None:
+        times.extend([ms[0], ms[1], ms[2]])
+    if isspmatrix_bsr(T):
+        return bsr_matrix((Px.reshape(-1, 1, 1), Pj, Pp), shape=T.shape)
+    return csr_matrix((Px, Pj, Pp), shape=T.shape)
+
+
 def jacobi_prolongation_smoother(S, T, Cm, B, omega=4.0 / 3.0, degree=1, filter=False,
-                                 weighting="diagonal"):
-    """pyamg/aggregation/smooth.py:67-210 (weighting 'diagonal' / 'local', no filtering)."""
+                                 weighting="diagonal", device=None, times=None):
+    """pyamg/aggregation/smooth.py:67-210 (weighting 'diagonal' / 'local', no filtering).
+
+    device : True = the device route (real float64 S and T with 1 x 1 blocks, one candidate, no
+    filtering; the diagonal, the spectral radius and the row sums of 'local' stay on the host, the weights, the products
+    and the differences run in HBM), False or None = the host route (None: the device route where JACOBI_DEVICE_AUTO
+    and a GPU).  times : a list that receives the device route's (upload, in HBM, fetch) milliseconds."""
+    way = route(device, JACOBI_DEVICE_AUTO)
+    if way is not False:
+        try:
+            _jacobi_device_refusals(S, T, B, filter, weighting)
+        except NotImplementedError:
+            if way is True:
+                raise
+            way = False
     if filter:
         raise NotImplementedError("filtered prolongation smoothing is outside the restated setup")
     if weighting == "block":
         if isspmatrix_csr(S) or (isspmatrix_bsr(S) and S.blocksize[0] == 1):
             weighting = "diagonal"
-    if weighting == "diagonal":
-        D_inv = get_diagonal(S, inv=True)
-        D_inv_S = scale_rows(S, D_inv, copy=True)
-        D_inv_S = (omega / approximate_spectral_radius(D_inv_S)) * D_inv_S
-    elif weighting == "local":
-        D = np.abs(S) * np.ones((S.shape[0], 1), dtype=S.dtype)
-        D_inv = np.zeros_like(D)
-        D_inv[D != 0] = 1.0 / np.abs(D[D != 0])
-        D_inv_S = scale_rows(S, D_inv, copy=True)
-        D_inv_S = omega * D_inv_S
-    else:
+    if weighting not in ("diagonal", "local"):
         raise NotImplementedError("weighting=%r" % weighting)
-    P = T
-    for i in range(degree):
-        P = P - (D_inv_S * P)
-    return P
+    D_inv_S, w, D_inv = _jacobi_weights(S, omega, weighting)
+    if degree <= 0:
+        return T                        # (after the weights, as ever: S is sorted and the estimate has drawn)
+
+    def on_host():
+        W = w * D_inv_S
+        P = T
+        for i in range(degree):
+            P = P - (W * P)
+        return P
+    # (a refusal of the library comes after the weights, so the host route that answers it draws nothing again)
+    return attempt(way, lambda: _jacobi_device(S, T, D_inv, w, degree, times), on_host)
 
 
 # --------------------------------------------------------------------------- driver
@@ -600,9 +769,14 @@ def smoothed_aggregation_solver(A, B=None, BH=None, symmetry="hermitian", streng
                                 improve_candidates=[("block_gauss_seidel", {"sweep": "symmetric",
                                                                             "iterations": 4}), None],
                                 max_levels=10, max_coarse=500, diagonal_dominance=False, keep=False,
-                                fast=True, **kwargs):
+                                fast=True, device=None, **kwargs):
     """Create a multilevel solver using Smoothed Aggregation (SA)
-    (pyamg/aggregation/aggregation.py:30-290); returns a pyamg_amd.multilevel_solver."""
+    (pyamg/aggregation/aggregation.py:30-290); returns a pyamg_amd.multilevel_solver.
+
+    device : None = every stage as its own options say.  True or False = the `device` option of symmetric strength,
+    MIS(2) aggregation, fit_candidates and Jacobi smoothing on every level that does not set its own; with True every
+    level takes the generic path of extend_hierarchy, and options that put one of these stages outside its device route
+     raise NotImplementedError before any level is built."""
     if not (isspmatrix_csr(A) or isspmatrix_bsr(A)):
         try:
             A = csr_matrix(A)
@@ -636,6 +810,13 @@ def smoothed_aggregation_solver(A, B=None, BH=None, symmetry="hermitian", streng
     improve_candidates = _levelize_smooth(list(improve_candidates) if isinstance(improve_candidates, list)
                                           else improve_candidates, max_levels)
     smooth = _levelize_smooth(smooth, max_levels)
+    if device is not None:
+        device = bool(device)
+        strength = _with_device(strength, ("symmetric",), device)
+        aggregate = _with_device(aggregate, ("mis",), device)
+        smooth = _with_device(smooth, ("jacobi",), device)
+        if device:
+            _device_setup_refusals(A, B, smooth)
 
     verbose = os.environ.get("AMG_SETUP_VERBOSE", "0") != "0"
     t0 = time.perf_counter()
@@ -643,7 +824,7 @@ def smoothed_aggregation_solver(A, B=None, BH=None, symmetry="hermitian", streng
     levels[-1].A = A
     levels[-1].B = B
     while len(levels) < max_levels and int(levels[-1].A.shape[0] / blocksize(levels[-1].A)) > max_coarse:
-        extend_hierarchy(levels, strength, aggregate, smooth, improve_candidates, keep or not fast)
+        extend_hierarchy(levels, strength, aggregate, smooth, improve_candidates, keep or not fast, device=device)
     t1 = time.perf_counter()
     ml = multilevel_solver(levels, **kwargs)
     t2 = time.perf_counter()
@@ -652,6 +833,36 @@ def smoothed_aggregation_solver(A, B=None, BH=None, symmetry="hermitian", streng
         print("[setup] levels %.2fs, multilevel_solver (coarse solver) %.2fs, smoothers %.2fs"
               % (t1 - t0, t2 - t1, time.perf_counter() - t2), flush=True)
     return ml
+
+
+def _with_device(levelized, stages, device):
+    """the per-level options with device=`device` added to every stage of `stages` that does not set its own"""
+    out = []
+    for entry in levelized:
+        fn, kw = unpack_arg(entry)
+        if fn in stages and "device" not in kw:
+            entry = (fn, dict(kw, device=device))
+        out.append(entry)
+    return out
+
+
+def _device_setup_refusals(A, B, smooth):
+    """smoothed_aggregation_solver(device=True): what puts a stage outside its device route on every level, raised
+    before any level is built"""
+    if A.dtype.kind == "c":
+        raise outside("smoothed aggregation of a complex operator on the device")
+    for entry in smooth:
+        fn, kw = unpack_arg(entry)
+        if fn != "jacobi" or not kw.get("device", False):
+            continue
+        if blocksize(A) != 1:
+            raise outside("Jacobi prolongation smoothing with blocks larger than 1 x 1 on the device")
+        if B.shape[1] > 1:
+            raise outside("Jacobi prolongation smoothing with more than one candidate on the device")
+        if kw.get("filter", False):
+            raise outside("filtered prolongation smoothing")
+        if kw.get("weighting", "diagonal") not in ("diagonal", "local", "block"):
+            raise outside("weighting=%r" % (kw.get("weighting"),))
 
 
 def poisson(grid, format="csr"):
@@ -735,13 +946,13 @@ def _default_options(B, strength_l, aggregate_l, smooth_l):
     if B.shape[1] != 1:
         return False
     fn, kw = unpack_arg(strength_l)
-    if fn != "symmetric" or kw.get("theta", 0) != 0:
+    if fn != "symmetric" or kw.get("theta", 0) != 0 or kw.get("device"):
         return False
     fn, kw = unpack_arg(aggregate_l)
     if fn != "standard" or kw:
         return False
     fn, kw = unpack_arg(smooth_l)
-    if fn != "jacobi" or kw.get("degree", 1) != 1 or kw.get("filter", False) or \
+    if fn != "jacobi" or kw.get("degree", 1) != 1 or kw.get("filter", False) or kw.get("device") or \
             kw.get("weighting", "diagonal") not in ("diagonal", "block"):
         return False
     return True
@@ -1024,8 +1235,9 @@ def _galerkin_c128_device(R, A, P):
     return _as_bsr11(Ac, (P.shape[1], P.shape[1]))
 
 
-def extend_hierarchy(levels, strength, aggregate, smooth, improve_candidates, keep=True, rho_fn=None):
-    """aggregation.py:293-435"""
+def extend_hierarchy(levels, strength, aggregate, smooth, improve_candidates, keep=True, rho_fn=None, device=None):
+    """aggregation.py:293-435.  device: fit_candidates' option (the other stages carry theirs in their keywords); True
+    also keeps the level on the generic path."""
     A = levels[-1].A
     B = levels[-1].B
 
@@ -1049,9 +1261,9 @@ def extend_hierarchy(levels, strength, aggregate, smooth, improve_candidates, ke
         levels[-1].B = B
         lap("candidate improvement")
 
-    if not keep and _scalar_fast_path_ok(A, B, strength[li], aggregate[li], smooth[li]):
+    if not keep and not device and _scalar_fast_path_ok(A, B, strength[li], aggregate[li], smooth[li]):
         return _extend_scalar(levels, smooth[li], keep, rho_fn or _rho_D_inv_A_host)
-    if not keep and _block_fast_path_ok(A, B, strength[li], aggregate[li], smooth[li]):
+    if not keep and not device and _block_fast_path_ok(A, B, strength[li], aggregate[li], smooth[li]):
         return _extend_block(levels, smooth[li], keep, rho_fn or _rho_D_inv_A_host)
 
     fn, kwargs = unpack_arg(strength[len(levels) - 1])
@@ -1081,7 +1293,7 @@ def extend_hierarchy(levels, strength, aggregate, smooth, improve_candidates, ke
         raise NotImplementedError("aggregate=%r is outside the restated setup" % (fn,))
     lap("strength, aggregation")
 
-    T, B = fit_candidates(AggOp, B)
+    T, B = fit_candidates(AggOp, B, device=device)
     lap("tentative prolongator")
 
     fn, kwargs = unpack_arg(smooth[len(levels) - 1])

@@ -924,8 +924,8 @@ int amg_extended_interpolation_device(int n, const int *Ap, const int *Aj, const
     CHK(check_csr_arrays(who, n, n, Ap, n + 1, Aj, 0x7fffffff, Ax, 0x7fffffff));
     CHK(check_csr_arrays(who, n, n, Sp, n + 1, Sj, 0x7fffffff, nullptr, -1));
     CHK(check_splitting(who, n, splitting, n));
-    CHK(check_unique_columns(who, n, Ap, Aj));
-    CHK(check_unique_columns(who, n, Sp, Sj));
+    CHK(check_unique_columns(who, n, n, Ap, Aj));
+    CHK(check_unique_columns(who, n, n, Sp, Sj));
     if (times_ms) times_ms[0] = times_ms[1] = 0.0;
     std::unique_ptr<amg_interpolation> h(new amg_interpolation);
     if (n == 0) {
@@ -974,7 +974,7 @@ int amg_classical_level_build(int n, const int *Ap, const int *Aj, const double 
     if (n <= 0) return bad(who, "an empty operator");
     CHK(check_level_options(who, kind, interpolation, max_per_row, theta, r));
     CHK(check_csr_arrays(who, n, n, Ap, n + 1, Aj, 0x7fffffff, Ax, 0x7fffffff));
-    if (interpolation == INTERP_EXTENDED_I) CHK(check_unique_columns(who, n, Ap, Aj));
+    if (interpolation == INTERP_EXTENDED_I) CHK(check_unique_columns(who, n, n, Ap, Aj));
     CHK(require_device());
     LapClock timer;
     HbmCsr A;
@@ -1022,7 +1022,7 @@ int amg_classical_chain_begin(int n, const int *Ap, const int *Aj, const double 
     *out = nullptr;
     if (n <= 0) return bad(who, "an empty operator");
     CHK(check_csr_arrays(who, n, n, Ap, n + 1, Aj, 0x7fffffff, Ax, 0x7fffffff));
-    CHK(check_unique_columns(who, n, Ap, Aj));       // extended+i and the right-hand operand of R * A both need it
+    CHK(check_unique_columns(who, n, n, Ap, Aj));       // extended+i and the right-hand operand of R * A both need it
     CHK(require_device());
     LapClock timer;
     std::unique_ptr<amg_classical_chain> c(new amg_classical_chain);

@@ -72,10 +72,10 @@ constexpr int F_NODE = 0, C_NODE = 1, U_NODE = 2;       // the states of a split
     return 0;
 }
 
-// no column twice in a row (host arrays that check_csr_arrays has passed)
-[[maybe_unused]] int check_unique_columns(const char *who, int n, const int *p, const int *j)
+// no column twice in a row of an n x n_col matrix (host arrays that check_csr_arrays has passed)
+[[maybe_unused]] int check_unique_columns(const char *who, int n, int n_col, const int *p, const int *j)
 {
-    std::vector<int> seen((size_t)n, -1);
+    std::vector<int> seen((size_t)std::max(n_col, 0), -1);
     for (int i = 0; i < n; ++i)
         for (int e = p[i]; e < p[i + 1]; ++e) {
             if (seen[(size_t)j[e]] == i) return bad(who, "a column is stored twice in a row");

@@ -269,3 +269,6 @@ int amg_mis_aggregation_device(int n, const int *Ap, const int *Aj, const double
 }
 
 }   // extern "C"
+
+// the smoothed-aggregation stages before and after the aggregation
+#include "prolong.hpp"
