@@ -764,7 +764,7 @@ int amg_mis_k_device(int n, const int *Ap, const int *Aj, int k, const double *y
 int amg_mis_aggregation_device(int n, const int *Ap, const int *Aj, const double *y, int *agg, int *cpts, int *n_agg, int *rounds,
                                double *times_ms);
 
-/* The smoothed-aggregation stages around the aggregation (csrc/prolong.hpp), real float64; matrices
+/* The smoothed-aggregation stages around the aggregation (csrc/prolong.hip), real float64; matrices
  * are CSR on the host with 32-bit offsets from 0 and columns inside the matrix (AMG_EINVAL otherwise, before any launch).
  *
  * amg_symmetric_strength_device: symmetric_strength_of_connection of an n x n operator whose rows may be unsorted, hold

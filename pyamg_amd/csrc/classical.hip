@@ -223,13 +223,10 @@ int strength_device(int n, double theta, const HbmCsr &A, long a_nnz, DBuf &Sp, 
     DBuf threshold, count;
     CHK(threshold.alloc(sizeof(double) * (size_t)n));
     CHK(count.alloc(sizeof(int) * ((size_t)n + 1)));
-    CHK(Sp.alloc(sizeof(int) * ((size_t)n + 1)));
     hipLaunchKernelGGL(strength_count_kernel, grid_for((long)n + 1), dim3(TB), 0, nullptr, n, theta, (const int *)A.p.i(), (const int *)A.j.i(),
                        (const double *)A.x.d(), threshold.d(), count.i());
     LAUNCH_CHECK("classical strength: count launch");
-    CHK(exclusive_scan(count.i(), Sp.i(), (size_t)n + 1));
-    CHK(last_offset(Sp.i(), n, nnz));
-    if (*nnz < 0 || *nnz > a_nnz) { set_error("classical strength: the scan left the matrix"); return AMG_ESTATE; }
+    CHK(offsets_from_counts("classical strength", n, count.i(), a_nnz, Sp, nnz));
     CHK(Sj.alloc(sizeof(int) * (size_t)*nnz));
     CHK(Sx.alloc(sizeof(double) * (size_t)*nnz));
     hipLaunchKernelGGL(strength_fill_kernel, grid_for(n), dim3(TB), 0, nullptr, n, (const int *)A.p.i(), (const int *)A.j.i(),
@@ -239,16 +236,14 @@ int strength_device(int n, double theta, const HbmCsr &A, long a_nnz, DBuf &Sp, 
     return 0;
 }
 
-// pass 1 and its scan: Bp (n + 1 offsets, allocated here); *nnz: entries of the prolongator
+// pass 1 and its scan: Bp (n + 1 offsets, allocated here); *nnz: the prolongator's entries, no bound (a lone C row stores one)
 int interpolation_offsets_device(int n, const int *Sp, const int *Sj, const int *splitting, DBuf &Bp, long *nnz)
 {
     DBuf count;
     CHK(count.alloc(sizeof(int) * ((size_t)n + 1)));
-    CHK(Bp.alloc(sizeof(int) * ((size_t)n + 1)));
     hipLaunchKernelGGL(interpolation_count_kernel, grid_for((long)n + 1), dim3(TB), 0, nullptr, n, Sp, Sj, splitting, count.i());
     LAUNCH_CHECK("direct interpolation: count launch");
-    CHK(exclusive_scan(count.i(), Bp.i(), (size_t)n + 1));
-    return last_offset(Bp.i(), n, nnz);
+    return offsets_from_counts("direct interpolation", n, count.i(), -1, Bp, nnz);
 }
 
 // the scan of splitting and pass 2 into Bj, Bx (device, Bp[n] entries each)
@@ -564,16 +559,6 @@ __global__ __launch_bounds__(TB) void truncate_fill_kernel(int n, int q, const i
         }
 }
 
-int exclusive_scan_long(const long *in, long *out, size_t count)
-{
-    size_t bytes = 0;
-    AMG_HIP(rocprim::exclusive_scan(nullptr, bytes, in, out, 0L, count, rocprim::plus<long>(), nullptr));
-    DBuf tmp;
-    CHK(tmp.alloc(bytes));
-    AMG_HIP(rocprim::exclusive_scan(tmp.p, bytes, in, out, 0L, count, rocprim::plus<long>(), nullptr));
-    return 0;
-}
-
 // Extended+i interpolation of A on the pattern of S (all on the device) into Pp (n + 1 offsets) and freshly allocated
 // Pj, Px, truncated to max_per_row entries per row where that is > 0; *nnz: entries of the prolongator
 int extended_interpolation_device(int n, const HbmCsr &A, const int *Sp, const int *Sj, const int *splitting, int max_per_row, DBuf &Pp,
@@ -589,9 +574,9 @@ int extended_interpolation_device(int n, const HbmCsr &A, const int *Sp, const i
     CHK(Pp.alloc(pbytes));
     hipLaunchKernelGGL(extended_bound_kernel, grid_for((long)n + 1), dim3(TB), 0, nullptr, n, Sp, Sj, splitting, big.as<long>());
     LAUNCH_CHECK("extended interpolation: bound launch");
-    CHK(exclusive_scan_long(big.as<long>(), Wp.as<long>(), (size_t)n + 1));
+    CHK(exclusive_scan(big.as<long>(), Wp.as<long>(), (size_t)n + 1));
     long wide = 0;
-    AMG_HIP(hipMemcpy(&wide, Wp.as<long>() + n, sizeof(long), hipMemcpyDeviceToHost));
+    CHK(last_offset(Wp.as<long>(), n, &wide));
     if (wide < 0) { set_error("extended interpolation: the workspace scan went negative"); return AMG_ESTATE; }
     CHK(wcand.alloc(sizeof(int) * (size_t)wide));
     hipLaunchKernelGGL(extended_count_kernel, dim3(wave_blocks), dim3(TB), 0, nullptr, n, Sp, Sj, splitting, (const long *)Wp.as<long>(),
@@ -620,13 +605,10 @@ int extended_interpolation_device(int n, const HbmCsr &A, const int *Sp, const i
     if (max_per_row > 0) {
         DBuf Tp, Tj, Tx;
         long kept = 0;
-        CHK(Tp.alloc(pbytes));
         hipLaunchKernelGGL(truncate_count_kernel, grid_for((long)n + 1), dim3(TB), 0, nullptr, n, max_per_row, (const int *)Pp.i(),
                            (const double *)Px.d(), count.i());
         LAUNCH_CHECK("extended interpolation: truncation count launch");
-        CHK(exclusive_scan(count.i(), Tp.i(), (size_t)n + 1));
-        CHK(last_offset(Tp.i(), n, &kept));
-        if (kept < 0 || kept > *nnz) { set_error("extended interpolation: the truncation scan left the prolongator"); return AMG_ESTATE; }
+        CHK(offsets_from_counts("extended interpolation: truncation", n, count.i(), *nnz, Tp, &kept));
         CHK(Tj.alloc(sizeof(int) * (size_t)kept));
         CHK(Tx.alloc(sizeof(double) * (size_t)kept));
         hipLaunchKernelGGL(truncate_fill_kernel, grid_for(n), dim3(TB), 0, nullptr, n, max_per_row, (const int *)Pp.i(), (const int *)Pj.i(),
@@ -926,7 +908,7 @@ int amg_extended_interpolation_device(int n, const int *Ap, const int *Aj, const
     CHK(check_splitting(who, n, splitting, n));
     CHK(check_unique_columns(who, n, n, Ap, Aj));
     CHK(check_unique_columns(who, n, n, Sp, Sj));
-    if (times_ms) times_ms[0] = times_ms[1] = 0.0;
+    clear_times(times_ms, 2);
     std::unique_ptr<amg_interpolation> h(new amg_interpolation);
     if (n == 0) {
         Pp[0] = 0;

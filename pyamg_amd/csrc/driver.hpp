@@ -149,5 +149,8 @@ struct LapClock {
     }
 };
 
+// the times a stage entry reports, before anything has run (a caller may pass none)
+inline void clear_times(double *times_ms, int count = 3) { if (times_ms) std::fill(times_ms, times_ms + count, 0.0); }
+
 }  // namespace
 }  // namespace amg

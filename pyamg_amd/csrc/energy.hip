@@ -15,7 +15,7 @@
 //
 // Part 3: the flat entry truncate_rows_csr (smoothed_aggregation.h:898-960): one lane per row runs the reference's
 // quicksort sequence on an explicit stack.
-#include "flat.hpp"
+#include "graph_dev.hpp"
 
 #include <memory>
 #include <string>
@@ -205,27 +205,6 @@ __global__ __launch_bounds__(TB) void calc_BtB_kernel(int ND, int n_node, int Cc
 }
 
 // ---------------------------------------------------------------------------------------------- argument checks
-int check_offsets(const std::string &name, const int *p, int p_size, int n, long j_size, long x_size, long per_block)
-{
-    if (!p || n < 0 || p_size < n + 1) { set_error(name + ": pointer array shorter than rows + 1"); return AMG_EINVAL; }
-    if (p[0] != 0) { set_error(name + ": offsets do not start at 0"); return AMG_EINVAL; }
-    for (int i = 0; i < n; ++i)
-        if (p[i + 1] < p[i]) { set_error(name + ": offsets decrease"); return AMG_EINVAL; }
-    if (p[n] > j_size || (x_size >= 0 && (long)p[n] * per_block > x_size)) {
-        set_error(name + ": index or value array shorter than the last offset");
-        return AMG_EINVAL;
-    }
-    return 0;
-}
-
-int check_columns(const std::string &name, const int *p, const int *j, int n, int n_col)
-{
-    if (p[n] > 0 && !j) { set_error(name + ": null array"); return AMG_EINVAL; }
-    for (int e = 0; e < p[n]; ++e)
-        if (j[e] < 0 || j[e] >= n_col) { set_error(name + ": column index outside the matrix"); return AMG_EINVAL; }
-    return 0;
-}
-
 bool rows_sorted_unique(const int *p, const int *j, int n)
 {
     for (int i = 0; i < n; ++i)
@@ -464,13 +443,13 @@ int amgcore_incomplete_mat_mult_bsr_f64(const int Ap[], int Ap_size, const int A
     if (n_brow < 0 || n_bcol < 0 || brow_A < 1 || bcol_A < 1 || bcol_B < 1) { set_error(name + ": bad sizes"); return AMG_EINVAL; }
     const long bsA = (long)brow_A * bcol_A, bsB = (long)bcol_A * bcol_B, bsS = (long)brow_A * bcol_B;
     const int n_brow_B = Bp_size - 1;
-    CHK(check_offsets(name + ": A", Ap, Ap_size, n_brow, Aj_size, Ax_size, bsA));
-    CHK(check_offsets(name + ": S", Sp, Sp_size, n_brow, Sj_size, Sx_size, bsS));
+    CHK(check_csr_offsets((name + ": A").c_str(), n_brow, Ap, Ap_size, Aj_size, Ax_size, bsA));
+    CHK(check_csr_offsets((name + ": S").c_str(), n_brow, Sp, Sp_size, Sj_size, Sx_size, bsS));
     if (n_brow == 0 || Sp[n_brow] == 0) return 0;
-    CHK(check_offsets(name + ": B", Bp, Bp_size, std::max(n_brow_B, 0), Bj_size, Bx_size, bsB));
-    CHK(check_columns(name + ": A", Ap, Aj, n_brow, n_brow_B));
-    CHK(check_columns(name + ": B", Bp, Bj, n_brow_B, n_bcol));
-    CHK(check_columns(name + ": S", Sp, Sj, n_brow, n_bcol));
+    CHK(check_csr_offsets((name + ": B").c_str(), std::max(n_brow_B, 0), Bp, Bp_size, Bj_size, Bx_size, bsB));
+    CHK(check_csr_columns((name + ": A").c_str(), n_brow, n_brow_B, Ap, Aj));
+    CHK(check_csr_columns((name + ": B").c_str(), n_brow_B, n_bcol, Bp, Bj));
+    CHK(check_csr_columns((name + ": S").c_str(), n_brow, n_bcol, Sp, Sj));
     const size_t na = (size_t)Ap[n_brow], nb = (size_t)Bp[n_brow_B], ns = (size_t)Sp[n_brow];
     if (!Sx || (na && !Ax) || (nb && !Bx)) { set_error(name + ": null array"); return AMG_EINVAL; }
     if ((long)ns * bsS >= 2147483647L) { set_error(name + ": S exceeds int32 indices"); return AMG_EINVAL; }
@@ -500,11 +479,11 @@ int amgcore_satisfy_constraints_helper_f64(int RowsPerBlock, int ColsPerBlock, i
     CHK(require_device());
     if (RowsPerBlock < 1 || ColsPerBlock < 1 || num_block_rows < 0 || NullDim < 1) { set_error(name + ": bad sizes"); return AMG_EINVAL; }
     const long bs = (long)RowsPerBlock * ColsPerBlock;
-    CHK(check_offsets(name + ": S", Sp, Sp_size, num_block_rows, Sj_size, Sx_size, bs));
+    CHK(check_csr_offsets((name + ": S").c_str(), num_block_rows, Sp, Sp_size, Sj_size, Sx_size, bs));
     if (num_block_rows == 0 || Sp[num_block_rows] == 0) return 0;
     const long per_col = (long)ColsPerBlock * NullDim;
     if (x_size < 0 || !x) { set_error(name + ": null array"); return AMG_EINVAL; }
-    CHK(check_columns(name + ": S", Sp, Sj, num_block_rows, (int)std::min<long>(x_size / per_col, 2147483647L)));
+    CHK(check_csr_columns((name + ": S").c_str(), num_block_rows, (int)std::min<long>(x_size / per_col, 2147483647L), Sp, Sj));
     if ((long)num_block_rows * RowsPerBlock * NullDim > y_size || (long)num_block_rows * NullDim * NullDim > z_size) {
         set_error(name + ": y or z shorter than the block rows need");
         return AMG_EINVAL;
@@ -538,12 +517,12 @@ int amgcore_calc_BtB_f64(int NullDim, int Nnodes, int ColsPerBlock, const double
         set_error(name + ": bad sizes (BsqCols must be NullDim (NullDim + 1) / 2)");
         return AMG_EINVAL;
     }
-    CHK(check_offsets(name + ": S", Sp, Sp_size, Nnodes, Sj_size, -1, 0));
+    CHK(check_csr_offsets((name + ": S").c_str(), Nnodes, Sp, Sp_size, Sj_size, -1, 0));
     const long n_out = (long)Nnodes * NullDim * NullDim;
     if (n_out > x_size) { set_error(name + ": x shorter than Nnodes * NullDim * NullDim"); return AMG_EINVAL; }
     if (Nnodes == 0) return 0;
     if (!x || b_size < 0 || (Sp[Nnodes] > 0 && !b)) { set_error(name + ": null array"); return AMG_EINVAL; }
-    CHK(check_columns(name + ": S", Sp, Sj, Nnodes, (int)std::min<long>(b_size / ((long)ColsPerBlock * BsqCols), 2147483647L)));
+    CHK(check_csr_columns((name + ": S").c_str(), Nnodes, (int)std::min<long>(b_size / ((long)ColsPerBlock * BsqCols), 2147483647L), Sp, Sj));
     const size_t ns = (size_t)Sp[Nnodes];
     DBuf db, dx, dSp, dSj;
     CHK(db.from_host(b, sizeof(double) * (size_t)b_size));
@@ -575,10 +554,10 @@ static int energy_smooth(int n_brow, int n_bcol, int R, int Cc, int ND, const in
 {
     const std::string name = "energy smoothing";
     if (!out || n_brow < 1 || n_bcol < 1 || R < 1 || Cc < 1 || ND < 1 || maxiter < 0) { set_error(name + ": bad arguments"); return AMG_EINVAL; }
-    CHK(check_offsets(name + ": A", Ap, n_brow + 1, n_brow, 2147483647L, -1, 0));
-    CHK(check_offsets(name + ": pattern", Sp, n_brow + 1, n_brow, 2147483647L, -1, 0));
-    CHK(check_columns(name + ": A", Ap, Aj, n_brow, n_brow));
-    CHK(check_columns(name + ": pattern", Sp, Sj, n_brow, n_bcol));
+    CHK(check_csr_offsets((name + ": A").c_str(), n_brow, Ap, n_brow + 1, 2147483647L, -1, 0));
+    CHK(check_csr_offsets((name + ": pattern").c_str(), n_brow, Sp, n_brow + 1, 2147483647L, -1, 0));
+    CHK(check_csr_columns((name + ": A").c_str(), n_brow, n_brow, Ap, Aj));
+    CHK(check_csr_columns((name + ": pattern").c_str(), n_brow, n_bcol, Sp, Sj));
     if (Sp[n_brow] == 0) { set_error(name + ": empty pattern"); return AMG_EINVAL; }
     if (!rows_sorted_unique(Sp, Sj, n_brow)) { set_error(name + ": the pattern's rows must hold sorted, unique columns"); return AMG_EINVAL; }
     if (!Ax || !Tx || !Bc || !BtBinv || !Dinv) { set_error(name + ": null array"); return AMG_EINVAL; }
@@ -662,7 +641,7 @@ int amgcore_truncate_rows_csr_f64(int n_row, int k, const int Sp[], int Sp_size,
     const std::string name = "truncate_rows_csr";
     CHK(require_device());
     if (n_row < 0 || k < 0) { set_error(name + ": bad sizes"); return AMG_EINVAL; }
-    CHK(check_offsets(name + ": S", Sp, Sp_size, n_row, std::min(Sj_size, Sx_size), -1, 0));
+    CHK(check_csr_offsets((name + ": S").c_str(), n_row, Sp, Sp_size, std::min(Sj_size, Sx_size), -1, 0));
     if (n_row == 0 || Sp[n_row] == 0) return 0;
     if (!Sj || !Sx) { set_error(name + ": null array"); return AMG_EINVAL; }
     const size_t nnz = (size_t)Sp[n_row];

@@ -1,7 +1,7 @@
-// The one internal header of the graph stages of the setup (split.hip, classical.hip, transpose.hip, misagg.hip): what
-// more than one of them needs on the host side of its drivers -- the checks every host array passes before anything is
-// launched on it, a CSR matrix in HBM, the int scan that numbers what a kernel flagged -- and the functions of one
-// unit that another one calls.
+// The one internal header of the graph stages of the setup (split, classical, transpose, misagg, prolong; strength and
+// energy for the scan and the checks): what more than one of them needs on the host side of its drivers -- the checks
+// every host array passes before anything is launched on it, a CSR matrix in HBM, the scan that numbers what a kernel
+// counted and the offsets it leaves -- and the functions of one unit that another one calls.
 #pragma once
 #include "flat.hpp"
 
@@ -40,22 +40,36 @@ constexpr int F_NODE = 0, C_NODE = 1, U_NODE = 2;       // the states of a split
     return AMG_EINVAL;
 }
 
-// n + 1 offsets from 0 up that never decrease, every column in [0, n_col), arrays as long as the offsets say (x_size < 0:
-// no values).  The last offset is an int, so nnz < 2^31.  Nothing is launched on less.
-[[maybe_unused]] int check_csr_arrays(const char *who, int n, int n_col, const int *p, int p_size, const int *j, int j_size, const void *x,
-                                      int x_size)
+// The checks of a CSR matrix in host arrays, in two halves; nothing is launched on less.  n + 1 offsets from 0 up that never
+// decrease, within j_size indices and x_size values at per_block an entry (x_size < 0: no values); an int, so nnz < 2^31.
+[[maybe_unused]] int check_csr_offsets(const char *who, int n, const int *p, int p_size, long j_size, long x_size, long per_block)
 {
     if (n < 0) return bad(who, "negative size");
     if (!p || p_size < n + 1) return bad(who, "offsets shorter than n + 1");
     if (p[0] != 0) return bad(who, "offsets do not start at 0");
     for (int i = 0; i < n; ++i)
         if (p[i + 1] < p[i]) return bad(who, "offsets decrease");
+    if (p[n] > j_size || (x_size >= 0 && (long)p[n] * per_block > x_size)) return bad(who, "arrays shorter than the last offset");
+    return 0;
+}
+
+// every column in [0, n_col), under offsets that check_csr_offsets has passed
+[[maybe_unused]] int check_csr_columns(const char *who, int n, int n_col, const int *p, const int *j)
+{
     const int nnz = p[n];
-    if (nnz > j_size || (x_size >= 0 && nnz > x_size)) return bad(who, "arrays shorter than the last offset");
-    if (nnz > 0 && (!j || (x_size >= 0 && !x))) return bad(who, "null array");
+    if (nnz > 0 && !j) return bad(who, "null array");
     for (int e = 0; e < nnz; ++e)
         if (j[e] < 0 || j[e] >= n_col) return bad(who, "column index outside the matrix");
     return 0;
+}
+
+// offsets, then columns, for scalar entries: arrays as long as the offsets say (x_size < 0: no values)
+[[maybe_unused]] int check_csr_arrays(const char *who, int n, int n_col, const int *p, int p_size, const int *j, int j_size, const void *x,
+                                      int x_size)
+{
+    CHK(check_csr_offsets(who, n, p, p_size, j_size, x_size, 1));
+    if (p[n] > 0 && x_size >= 0 && !x) return bad(who, "null array");
+    return check_csr_columns(who, n, n_col, p, j);
 }
 
 // the pattern of a graph of n vertices, its arrays as long as its offsets say
@@ -84,35 +98,49 @@ constexpr int F_NODE = 0, C_NODE = 1, U_NODE = 2;       // the states of a split
     return 0;
 }
 
-// A on the device
+// A on the device: 32-bit offsets, columns and (where the caller has any) values
 struct HbmCsr {
     DBuf p, j, x;
-    int upload(int n, const int *Ap, const int *Aj, const double *Ax)
+    // valued: x is allocated even where Ax is null, as it may be for a matrix without entries whose kernels are handed x
+    int upload(int n, const int *Ap, const int *Aj, const double *Ax, bool valued = false)
     {
         const size_t nnz = (size_t)Ap[n];
         CHK(p.from_host(Ap, sizeof(int) * ((size_t)n + 1)));
         CHK(j.from_host(Aj, sizeof(int) * nnz));
         if (Ax) CHK(x.from_host(Ax, sizeof(double) * nnz));
+        else if (valued) CHK(x.alloc(0));
         return 0;
     }
 };
 
-[[maybe_unused]] int last_offset(const int *offsets, int n, long *out)
+// out[k] = in[0] + ... + in[k - 1] for k < count
+template <class T> int exclusive_scan(const T *in, T *out, size_t count)
 {
-    int v = 0;
-    AMG_HIP(hipMemcpy(&v, offsets + n, sizeof(int), hipMemcpyDeviceToHost));
+    size_t bytes = 0;
+    AMG_HIP(rocprim::exclusive_scan(nullptr, bytes, in, out, T(0), count, rocprim::plus<T>(), nullptr));
+    DBuf tmp;
+    CHK(tmp.alloc(bytes));
+    AMG_HIP(rocprim::exclusive_scan(tmp.p, bytes, in, out, T(0), count, rocprim::plus<T>(), nullptr));
+    return 0;
+}
+
+template <class T> int last_offset(const T *offsets, int n, long *out)
+{
+    T v = 0;
+    AMG_HIP(hipMemcpy(&v, offsets + n, sizeof(T), hipMemcpyDeviceToHost));
     *out = v;
     return 0;
 }
 
-// out[k] = in[0] + ... + in[k - 1] for k < count
-[[maybe_unused]] int exclusive_scan(const int *in, int *out, size_t count)
+// The middle of count / scan / fill: n + 1 offsets, allocated here, from the counts a kernel wrote (count[n]: the
+// scan's last addend, 0), and their last one read back as *total.  A total outside [0, upper] is refused with
+// AMG_ESTATE before anything is allocated or filled by it; upper < 0: the caller has no bound.
+template <class T> int offsets_from_counts(const char *who, int n, const T *count, long upper, DBuf &offsets, long *total)
 {
-    size_t bytes = 0;
-    AMG_HIP(rocprim::exclusive_scan(nullptr, bytes, in, out, 0, count, rocprim::plus<int>(), nullptr));
-    DBuf tmp;
-    CHK(tmp.alloc(bytes));
-    AMG_HIP(rocprim::exclusive_scan(tmp.p, bytes, in, out, 0, count, rocprim::plus<int>(), nullptr));
+    CHK(offsets.alloc(sizeof(T) * ((size_t)n + 1)));
+    CHK(exclusive_scan(count, offsets.as<T>(), (size_t)n + 1));
+    CHK(last_offset(offsets.as<T>(), n, total));
+    if (upper >= 0 && (*total < 0 || *total > upper)) { set_error(std::string(who) + ": the scan left its bound"); return AMG_ESTATE; }
     return 0;
 }
 

@@ -183,16 +183,29 @@ __global__ __launch_bounds__(TB) void agg_round2_kernel(int n, const int *Ap, co
     agg2[i] = a;
 }
 
-struct HbmGraph {
-    DBuf p, j, y;
-    int upload(int n, const int *Ap, const int *Aj, const double *yv)
-    {
-        CHK(p.from_host(Ap, sizeof(int) * ((size_t)n + 1)));
-        CHK(j.from_host(Aj, sizeof(int) * (size_t)Ap[n]));
-        CHK(y.from_host(yv, sizeof(double) * (size_t)n));
-        return 0;
-    }
-};
+// The aggregation of a graph that is already in HBM (p, j: its n + 1 offsets and columns; y: the n weights) into freshly
+// allocated agg (n ints, -1: no aggregate) and cpts (the roots, *n_agg of them, ascending).  *rounds: rounds of the set.
+int mis_aggregation_resident(int n, const int *p, const int *j, const double *y, DBuf &agg, DBuf &cpts, int *n_agg, int *rounds)
+{
+    const size_t vbytes = sizeof(int) * (size_t)n;
+    DBuf dx, root, number, agg1;
+    CHK(dx.alloc(vbytes)); CHK(agg1.alloc(vbytes)); CHK(agg.alloc(vbytes)); CHK(cpts.alloc(vbytes));
+    CHK(root.alloc(vbytes + sizeof(int)));
+    CHK(mis_k_rounds_device(n, p, j, 2, y, -1, dx.i(), rounds));
+    hipLaunchKernelGGL(agg_root_kernel, grid_for((long)n + 1), dim3(TB), 0, nullptr, n, p, j, (const int *)dx.i(), root.i());
+    LAUNCH_CHECK("mis_aggregation: root launch");
+    long count = 0;
+    CHK(offsets_from_counts("mis_aggregation", n, root.i(), n, number, &count));
+    hipLaunchKernelGGL(agg_round1_kernel, grid_for(n), dim3(TB), 0, nullptr, n, p, j, (const int *)root.i(), (const int *)number.i(),
+                       agg1.i(), cpts.i());
+    LAUNCH_CHECK("mis_aggregation: round 1 launch");
+    hipLaunchKernelGGL(agg_round2_kernel, grid_for(n), dim3(TB), 0, nullptr, n, p, j, (const int *)agg1.i(), (const int *)cpts.i(), y,
+                       agg.i());
+    LAUNCH_CHECK("mis_aggregation: round 2 launch");
+    AMG_HIP(hipDeviceSynchronize());
+    *n_agg = (int)count;
+    return 0;
+}
 
 }   // namespace
 }   // namespace amg
@@ -204,19 +217,20 @@ int amg_mis_k_device(int n, const int *Ap, const int *Aj, int k, const double *y
     using namespace amg;
     if (n < 0 || k < 1 || (n > 0 && (!y || !x))) { set_error("mis_k: bad arguments"); return AMG_EINVAL; }
     if (rounds) *rounds = 0;
-    if (times_ms) times_ms[0] = times_ms[1] = times_ms[2] = 0.0;
+    clear_times(times_ms);
     if (n == 0) return 0;
     CHK(check_graph("mis_k", n, Ap, Aj));
     CHK(require_device());
     LapClock timer;
-    HbmGraph G;
-    DBuf dx;
-    CHK(G.upload(n, Ap, Aj, y));
+    HbmCsr G;
+    DBuf dy, dx;
+    CHK(G.upload(n, Ap, Aj, nullptr));
+    CHK(dy.from_host(y, sizeof(double) * (size_t)n));
     CHK(dx.alloc(sizeof(int) * (size_t)n));
     AMG_HIP(hipDeviceSynchronize());
     const double upload_ms = timer.lap();
     int done = 0;
-    CHK(mis_k_rounds_device(n, G.p.i(), G.j.i(), k, G.y.d(), max_iters, dx.i(), &done));
+    CHK(mis_k_rounds_device(n, G.p.i(), G.j.i(), k, dy.d(), max_iters, dx.i(), &done));
     AMG_HIP(hipDeviceSynchronize());
     const double rounds_ms = timer.lap();
     CHK(dx.to_host(x, sizeof(int) * (size_t)n));
@@ -232,35 +246,21 @@ int amg_mis_aggregation_device(int n, const int *Ap, const int *Aj, const double
     if (n < 0 || !n_agg || (n > 0 && (!y || !agg || !cpts))) { set_error("mis_aggregation: bad arguments"); return AMG_EINVAL; }
     *n_agg = 0;
     if (rounds) *rounds = 0;
-    if (times_ms) times_ms[0] = times_ms[1] = times_ms[2] = 0.0;
+    clear_times(times_ms);
     if (n == 0) return 0;
     CHK(check_graph("mis_aggregation", n, Ap, Aj));
     CHK(require_device());
     LapClock timer;
-    const size_t vbytes = sizeof(int) * (size_t)n;
-    HbmGraph G;
-    DBuf dx, root, number, agg1, agg2, dcpts;
-    CHK(G.upload(n, Ap, Aj, y));
-    CHK(dx.alloc(vbytes)); CHK(agg1.alloc(vbytes)); CHK(agg2.alloc(vbytes)); CHK(dcpts.alloc(vbytes));
-    CHK(root.alloc(vbytes + sizeof(int))); CHK(number.alloc(vbytes + sizeof(int)));
+    HbmCsr G;
+    DBuf dy, dagg, dcpts;
+    CHK(G.upload(n, Ap, Aj, nullptr));
+    CHK(dy.from_host(y, sizeof(double) * (size_t)n));
     AMG_HIP(hipDeviceSynchronize());
     const double upload_ms = timer.lap();
     int done = 0, count = 0;
-    const int *p = G.p.i(), *j = G.j.i();
-    CHK(mis_k_rounds_device(n, p, j, 2, G.y.d(), -1, dx.i(), &done));
-    hipLaunchKernelGGL(agg_root_kernel, grid_for((long)n + 1), dim3(TB), 0, nullptr, n, p, j, (const int *)dx.i(), root.i());
-    LAUNCH_CHECK("mis_aggregation: root launch");
-    CHK(exclusive_scan(root.i(), number.i(), (size_t)n + 1));
-    hipLaunchKernelGGL(agg_round1_kernel, grid_for(n), dim3(TB), 0, nullptr, n, p, j, (const int *)root.i(), (const int *)number.i(),
-                       agg1.i(), dcpts.i());
-    LAUNCH_CHECK("mis_aggregation: round 1 launch");
-    hipLaunchKernelGGL(agg_round2_kernel, grid_for(n), dim3(TB), 0, nullptr, n, p, j, (const int *)agg1.i(), (const int *)dcpts.i(),
-                       (const double *)G.y.d(), agg2.i());
-    LAUNCH_CHECK("mis_aggregation: round 2 launch");
-    AMG_HIP(hipMemcpy(&count, number.i() + n, sizeof(int), hipMemcpyDeviceToHost));
-    if (count < 0 || count > n) { set_error("mis_aggregation: the scan left the graph"); return AMG_ESTATE; }
+    CHK(mis_aggregation_resident(n, G.p.i(), G.j.i(), dy.d(), dagg, dcpts, &count, &done));
     const double rounds_ms = timer.lap();
-    CHK(agg2.to_host(agg, vbytes));
+    CHK(dagg.to_host(agg, sizeof(int) * (size_t)n));
     CHK(dcpts.to_host(cpts, sizeof(int) * (size_t)count));
     *n_agg = count;
     if (rounds) *rounds = done;
@@ -269,6 +269,3 @@ int amg_mis_aggregation_device(int n, const int *Ap, const int *Aj, const double
 }
 
 }   // extern "C"
-
-// the smoothed-aggregation stages before and after the aggregation
-#include "prolong.hpp"

@@ -6,16 +6,20 @@
 // contracted (-ffp-contract=off), square root and division are the correctly rounded ones.  Offsets are widened to 64
 // bits inside the kernels; every count fits an int because the sizes are checked before the first launch.  The products
 // of the smoothing are spgemm.hip's, the members of an aggregate come from transpose.hip.
-// Compiled as part of misagg.hip, the unit of the aggregation these stages surround: its only includer.
-#pragma once
+// Every stage is a core on buffers already in HBM (*_resident) inside a thin entry: checks, upload, core, copy back.
 #include "graph_dev.hpp"
 #include "hier.hpp"
 
 #include <memory>
 #include <string>
 
-using namespace amg;
+// the columns and values of a stage's result, held for its fetch (hidden, like classical.hip's handles)
+struct __attribute__((visibility("hidden"))) amg_prolong {
+    long nnz = 0;
+    amg::DBuf j, x;
+};
 
+namespace amg {
 namespace {
 
 // ------------------------------------------------------------------------------------------------ symmetric strength
@@ -76,6 +80,29 @@ __global__ __launch_bounds__(TB) void sym_fill_kernel(int n, double theta2, cons
     for (long e = lo; e < at; ++e) Sx[e] = Sx[e] / m;
 }
 
+// symmetric strength of A (device, with values) into freshly allocated S: S.p n + 1 offsets; *nnz: entries kept
+int symmetric_strength_resident(int n, double theta, const HbmCsr &A, long a_nnz, HbmCsr &S, long *nnz)
+{
+    const double theta2 = theta * theta;
+    const int *p = A.p.i(), *j = A.j.i();
+    const double *x = A.x.d();
+    DBuf diags, count;
+    CHK(diags.alloc(sizeof(double) * (size_t)n));
+    CHK(count.alloc(sizeof(int) * ((size_t)n + 1)));
+    hipLaunchKernelGGL(sym_diagonal_kernel, grid_for(n), dim3(TB), 0, nullptr, n, p, j, x, diags.d());
+    LAUNCH_CHECK("symmetric strength: diagonal launch");
+    hipLaunchKernelGGL(sym_count_kernel, grid_for((long)n + 1), dim3(TB), 0, nullptr, n, theta2, p, j, x, (const double *)diags.d(), count.i());
+    LAUNCH_CHECK("symmetric strength: count launch");
+    CHK(offsets_from_counts("symmetric strength", n, count.i(), a_nnz, S.p, nnz));
+    CHK(S.j.alloc(sizeof(int) * (size_t)*nnz));
+    CHK(S.x.alloc(sizeof(double) * (size_t)*nnz));
+    hipLaunchKernelGGL(sym_fill_kernel, grid_for(n), dim3(TB), 0, nullptr, n, theta2, p, j, x, (const double *)diags.d(), (const int *)S.p.i(),
+                       S.j.i(), S.x.d());
+    LAUNCH_CHECK("symmetric strength: fill launch");
+    AMG_HIP(hipDeviceSynchronize());
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------------ tentative prolongator
 // node i's K1 x K2 block of B into its block of T (a node has at most one aggregate, so its block is number Tp[i])
 __global__ __launch_bounds__(TB) void fit_copy_kernel(int n_fine, int bs, const int *Tp, const double *B, double *Tx)
@@ -132,6 +159,27 @@ __global__ __launch_bounds__(TB) void fit_mgs_kernel(int n_coarse, int K1, int K
             for (int r = 0; r < K1; ++r) q[r * K2 + bj] = q[r * K2 + bj] * scale;
         }
     }
+}
+
+// The tentative prolongator of AggOp (device: Tp, and Tj with nnz columns, at most one per row) and the candidates B
+// (device) into freshly allocated Tx (nnz blocks) and R (zero where an aggregate has no members); AggOp^T is formed here.
+int fit_candidates_resident(int n_fine, int n_coarse, int K1, int K2, const int *Tp, const int *Tj, long nnz, const double *B, double tol,
+                            DBuf &Tx, DBuf &R)
+{
+    const size_t bs = (size_t)K1 * (size_t)K2;
+    DBuf unused_values, Mp, Mj, Mx;
+    CHK(Tx.alloc(sizeof(double) * (size_t)nnz * bs));
+    CHK(R.zero(sizeof(double) * (size_t)n_coarse * (size_t)K2 * (size_t)K2));
+    CHK(unused_values.zero(sizeof(double) * (size_t)nnz));      // transpose_device moves values too; only Mp and Mj are read
+    TransposeRoute how;
+    CHK(transpose_device(n_fine, n_coarse, nnz, Tp, Tj, unused_values.d(), Mp, Mj, Mx, how));
+    hipLaunchKernelGGL(fit_copy_kernel, grid_for(n_fine), dim3(TB), 0, nullptr, n_fine, (int)bs, Tp, B, Tx.d());
+    LAUNCH_CHECK("fit_candidates: copy launch");
+    hipLaunchKernelGGL(fit_mgs_kernel, grid_for(n_coarse), dim3(TB), 0, nullptr, n_coarse, K1, K2, tol, (const int *)Mp.i(),
+                       (const int *)Mj.i(), Tp, Tx.d(), R.d());
+    LAUNCH_CHECK("fit_candidates: Gram-Schmidt launch");
+    AMG_HIP(hipDeviceSynchronize());
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------ Jacobi smoothing
@@ -204,22 +252,22 @@ __global__ __launch_bounds__(TB) void jacobi_subtract_kernel(int n, const int *P
     if (!FILL) count[i] = kept;
 }
 
-// P <- P - X in HBM: Pp (n + 1 ints), Pj, Px are replaced, *p_nnz updated
-int jacobi_subtract_device(int n, DBuf &Pp, DBuf &Pj, DBuf &Px, long *p_nnz, const long *Xp, const int *Xj, const double *Xx, long x_nnz)
+// P <- P - X in HBM: P's three arrays are replaced, *p_nnz updated
+int jacobi_subtract_device(int n, HbmCsr &P, long *p_nnz, const long *Xp, const int *Xj, const double *Xx, long x_nnz)
 {
     if (*p_nnz + x_nnz >= (1L << 31)) { set_error("jacobi smoothing: the difference may hold 2^31 entries or more"); return AMG_ENOTIMPL; }
-    DBuf flag, count, Op, Oj, Ox;
+    DBuf flag, count;
+    HbmCsr O;
     int canonical = 1;
     CHK(flag.from_host(&canonical, sizeof(int)));
-    hipLaunchKernelGGL(canonical_kernel<int>, grid_for(n), dim3(TB), 0, nullptr, n, (const int *)Pp.i(), (const int *)Pj.i(), flag.i());
+    hipLaunchKernelGGL(canonical_kernel<int>, grid_for(n), dim3(TB), 0, nullptr, n, (const int *)P.p.i(), (const int *)P.j.i(), flag.i());
     LAUNCH_CHECK("jacobi smoothing: canonical check of P");
     hipLaunchKernelGGL(canonical_kernel<long>, grid_for(n), dim3(TB), 0, nullptr, n, Xp, Xj, flag.i());
     LAUNCH_CHECK("jacobi smoothing: canonical check of X");
     CHK(flag.to_host(&canonical, sizeof(int)));
     CHK(count.alloc(sizeof(int) * ((size_t)n + 1)));
-    CHK(Op.alloc(sizeof(int) * ((size_t)n + 1)));
-    const int *pp = Pp.i(), *pj = Pj.i();
-    const double *px = Px.d();
+    const int *pp = P.p.i(), *pj = P.j.i();
+    const double *px = P.x.d();
     if (canonical)
         hipLaunchKernelGGL((jacobi_subtract_kernel<false, true>), grid_for((long)n + 1), dim3(TB), 0, nullptr, n, pp, pj, px, Xp, Xj, Xx,
                            (const int *)nullptr, (int *)nullptr, (double *)nullptr, count.i());
@@ -227,39 +275,56 @@ int jacobi_subtract_device(int n, DBuf &Pp, DBuf &Pj, DBuf &Px, long *p_nnz, con
         hipLaunchKernelGGL((jacobi_subtract_kernel<false, false>), grid_for((long)n + 1), dim3(TB), 0, nullptr, n, pp, pj, px, Xp, Xj, Xx,
                            (const int *)nullptr, (int *)nullptr, (double *)nullptr, count.i());
     LAUNCH_CHECK("jacobi smoothing: count launch");
-    CHK(exclusive_scan(count.i(), Op.i(), (size_t)n + 1));
     long nnz = 0;
-    CHK(last_offset(Op.i(), n, &nnz));
-    if (nnz < 0 || nnz > *p_nnz + x_nnz) { set_error("jacobi smoothing: the scan left the operands"); return AMG_ESTATE; }
-    CHK(Oj.alloc(sizeof(int) * (size_t)nnz));
-    CHK(Ox.alloc(sizeof(double) * (size_t)nnz));
+    CHK(offsets_from_counts("jacobi smoothing", n, count.i(), *p_nnz + x_nnz, O.p, &nnz));
+    CHK(O.j.alloc(sizeof(int) * (size_t)nnz));
+    CHK(O.x.alloc(sizeof(double) * (size_t)nnz));
     if (canonical)
         hipLaunchKernelGGL((jacobi_subtract_kernel<true, true>), grid_for(n), dim3(TB), 0, nullptr, n, pp, pj, px, Xp, Xj, Xx,
-                           (const int *)Op.i(), Oj.i(), Ox.d(), (int *)nullptr);
+                           (const int *)O.p.i(), O.j.i(), O.x.d(), (int *)nullptr);
     else
         hipLaunchKernelGGL((jacobi_subtract_kernel<true, false>), grid_for(n), dim3(TB), 0, nullptr, n, pp, pj, px, Xp, Xj, Xx,
-                           (const int *)Op.i(), Oj.i(), Ox.d(), (int *)nullptr);
+                           (const int *)O.p.i(), O.j.i(), O.x.d(), (int *)nullptr);
     LAUNCH_CHECK("jacobi smoothing: fill launch");
     AMG_HIP(hipDeviceSynchronize());
-    Pp = std::move(Op); Pj = std::move(Oj); Px = std::move(Ox);
+    P = std::move(O);
     *p_nnz = nnz;
     return 0;
 }
 
-void clear_times(double *times_ms)
+// Jacobi smoothing in HBM: P (n x n_coarse, *p_nnz entries, no column twice in a row) becomes P - W P, `degree` times,
+// W = w * (dinv (.)rows S) on the pattern of S (n x n, s_nnz entries).  P's arrays are replaced, *p_nnz updated.
+int jacobi_smoothing_resident(int n, int n_coarse, const HbmCsr &S, long s_nnz, const double *dinv, double w, int degree, HbmCsr &P,
+                              long *p_nnz)
 {
-    if (times_ms) times_ms[0] = times_ms[1] = times_ms[2] = 0.0;
+    DBuf Wx;
+    CHK(Wx.alloc(sizeof(double) * (size_t)s_nnz));
+    hipLaunchKernelGGL(jacobi_weight_kernel, grid_for(n), dim3(TB), 0, nullptr, n, w, (const int *)S.p.i(), (const double *)S.x.d(), dinv,
+                       Wx.d());
+    LAUNCH_CHECK("jacobi smoothing: weight launch");
+    DevArr<long> Wp64;
+    CHK(widen_rowptr_device(n, S.p.i(), Wp64));
+    for (int step = 0; step < degree; ++step) {
+        DevArr<long> Pp64, Xp;
+        DevArr<int> Xj;
+        DevArr<double> Xx;
+        long x_nnz = 0;
+        if (s_nnz > 0 && *p_nnz > 0) {
+            CHK(widen_rowptr_device(n, P.p.i(), Pp64));
+            const int rc = spgemm_device(n, n, n_coarse, s_nnz, Wp64, S.j.i(), Wx.d(), *p_nnz, Pp64, P.j.i(), P.x.d(), &x_nnz, Xp, Xj, Xx);
+            if (rc == AMG_EINVAL) return AMG_ENOTIMPL;      // the product routes' refusal: the caller's host route
+            CHK(rc);
+        } else {                                            // a product without entries: nothing to launch
+            AMG_HIP(Xp.malloc_bytes(sizeof(long) * ((size_t)n + 1)));
+            AMG_HIP(hipMemset(Xp.p, 0, sizeof(long) * ((size_t)n + 1)));
+        }
+        CHK(jacobi_subtract_device(n, P, p_nnz, Xp, Xj, Xx, x_nnz));
+    }
+    AMG_HIP(hipDeviceSynchronize());
+    return 0;
 }
 
-}   // namespace
-
-// the columns and values of a stage's result, held for its fetch
-struct __attribute__((visibility("hidden"))) amg_prolong {
-    long nnz = 0;
-    DBuf j, x;
-};
-
-static int fetch_prolong(const char *who, amg_prolong *h, int *j, double *x, double *times_ms)
+int fetch_prolong(const char *who, amg_prolong *h, int *j, double *x, double *times_ms)
 {
     if (!h) return AMG_EINVAL;
     std::unique_ptr<amg_prolong> own(h);
@@ -273,11 +338,15 @@ static int fetch_prolong(const char *who, amg_prolong *h, int *j, double *x, dou
     return 0;
 }
 
+}   // namespace
+}   // namespace amg
+
 extern "C" {
 
 int amg_symmetric_strength_device(int n, const int *Ap, const int *Aj, const double *Ax, double theta, int *Sp, amg_prolong **out,
                                   double *times_ms)
 {
+    using namespace amg;
     const char *who = "symmetric strength";
     if (!out || !Sp) return bad(who, "bad arguments");
     *out = nullptr;
@@ -292,34 +361,15 @@ int amg_symmetric_strength_device(int n, const int *Ap, const int *Aj, const dou
     }
     CHK(require_device());
     LapClock timer;
-    const long a_nnz = Ap[n];
-    const double theta2 = theta * theta;
-    HbmCsr A;
-    DBuf diags, count, dSp;
-    CHK(A.upload(n, Ap, Aj, Ax));
-    if (!A.x.p) CHK(A.x.alloc(0));
+    HbmCsr A, S;
+    CHK(A.upload(n, Ap, Aj, Ax, true));
     AMG_HIP(hipDeviceSynchronize());
     const double upload_ms = timer.lap();
-    const int *p = A.p.i(), *j = A.j.i();
-    const double *x = A.x.d();
-    CHK(diags.alloc(sizeof(double) * (size_t)n));
-    CHK(count.alloc(sizeof(int) * ((size_t)n + 1)));
-    CHK(dSp.alloc(sizeof(int) * ((size_t)n + 1)));
-    hipLaunchKernelGGL(sym_diagonal_kernel, grid_for(n), dim3(TB), 0, nullptr, n, p, j, x, diags.d());
-    LAUNCH_CHECK("symmetric strength: diagonal launch");
-    hipLaunchKernelGGL(sym_count_kernel, grid_for((long)n + 1), dim3(TB), 0, nullptr, n, theta2, p, j, x, (const double *)diags.d(), count.i());
-    LAUNCH_CHECK("symmetric strength: count launch");
-    CHK(exclusive_scan(count.i(), dSp.i(), (size_t)n + 1));
-    CHK(last_offset(dSp.i(), n, &h->nnz));
-    if (h->nnz < 0 || h->nnz > a_nnz) { set_error("symmetric strength: the scan left the matrix"); return AMG_ESTATE; }
-    CHK(h->j.alloc(sizeof(int) * (size_t)h->nnz));
-    CHK(h->x.alloc(sizeof(double) * (size_t)h->nnz));
-    hipLaunchKernelGGL(sym_fill_kernel, grid_for(n), dim3(TB), 0, nullptr, n, theta2, p, j, x, (const double *)diags.d(), (const int *)dSp.i(),
-                       h->j.i(), h->x.d());
-    LAUNCH_CHECK("symmetric strength: fill launch");
-    AMG_HIP(hipDeviceSynchronize());
+    CHK(symmetric_strength_resident(n, theta, A, Ap[n], S, &h->nnz));
     const double hbm_ms = timer.lap();
-    CHK(dSp.to_host(Sp, sizeof(int) * ((size_t)n + 1)));
+    CHK(S.p.to_host(Sp, sizeof(int) * ((size_t)n + 1)));
+    h->j = std::move(S.j);
+    h->x = std::move(S.x);
     if (times_ms) { times_ms[0] = upload_ms; times_ms[1] = hbm_ms; }
     *out = h.release();
     return 0;
@@ -327,12 +377,13 @@ int amg_symmetric_strength_device(int n, const int *Ap, const int *Aj, const dou
 
 int amg_symmetric_strength_fetch(amg_prolong *h, int *Sj, double *Sx, double *times_ms)
 {
-    return fetch_prolong("symmetric strength fetch", h, Sj, Sx, times_ms);
+    return amg::fetch_prolong("symmetric strength fetch", h, Sj, Sx, times_ms);
 }
 
 int amg_fit_candidates_device(int n_fine, int n_coarse, int K1, int K2, const int *Tp, const int *Tj, const double *B, double tol,
                               double *Tx, double *R, double *times_ms)
 {
+    using namespace amg;
     const char *who = "fit_candidates";
     clear_times(times_ms);
     if (n_coarse < 0 || K1 < 1 || K2 < 1) return bad(who, "bad sizes");
@@ -346,24 +397,13 @@ int amg_fit_candidates_device(int n_fine, int n_coarse, int K1, int K2, const in
     if (n_fine == 0 || r_count == 0) return 0;
     CHK(require_device());
     LapClock timer;
-    DBuf dTp, dTj, dB, dTx, dR, unused_values, Mp, Mj, Mx;
-    CHK(dTp.from_host(Tp, sizeof(int) * ((size_t)n_fine + 1)));
-    CHK(dTj.from_host(Tj, sizeof(int) * (size_t)nnz));
+    HbmCsr T;
+    DBuf dB, dTx, dR;
+    CHK(T.upload(n_fine, Tp, Tj, nullptr));
     CHK(dB.from_host(B, sizeof(double) * b_count));
     AMG_HIP(hipDeviceSynchronize());
     const double upload_ms = timer.lap();
-    CHK(dTx.alloc(sizeof(double) * t_count));
-    CHK(dR.zero(sizeof(double) * r_count));
-    CHK(unused_values.zero(sizeof(double) * (size_t)nnz));      // transpose_device moves values too; only Mp and Mj are read
-    TransposeRoute how;
-    CHK(transpose_device(n_fine, n_coarse, nnz, dTp.i(), dTj.i(), unused_values.d(), Mp, Mj, Mx, how));
-    hipLaunchKernelGGL(fit_copy_kernel, grid_for(n_fine), dim3(TB), 0, nullptr, n_fine, (int)bs, (const int *)dTp.i(), (const double *)dB.d(),
-                       dTx.d());
-    LAUNCH_CHECK("fit_candidates: copy launch");
-    hipLaunchKernelGGL(fit_mgs_kernel, grid_for(n_coarse), dim3(TB), 0, nullptr, n_coarse, K1, K2, tol, (const int *)Mp.i(),
-                       (const int *)Mj.i(), (const int *)dTp.i(), dTx.d(), dR.d());
-    LAUNCH_CHECK("fit_candidates: Gram-Schmidt launch");
-    AMG_HIP(hipDeviceSynchronize());
+    CHK(fit_candidates_resident(n_fine, n_coarse, K1, K2, T.p.i(), T.j.i(), nnz, dB.d(), tol, dTx, dR));
     const double hbm_ms = timer.lap();
     CHK(dTx.to_host(Tx, sizeof(double) * t_count));
     CHK(dR.to_host(R, sizeof(double) * r_count));
@@ -374,6 +414,7 @@ int amg_fit_candidates_device(int n_fine, int n_coarse, int K1, int K2, const in
 int amg_jacobi_prolongation_device(int n, int n_coarse, const int *Sp, const int *Sj, const double *Sx, const double *dinv, double w,
                                    int degree, const int *Tp, const int *Tj, const double *Tx, int *Pp, amg_prolong **out, double *times_ms)
 {
+    using namespace amg;
     const char *who = "jacobi smoothing";
     if (!out || !Pp) return bad(who, "bad arguments");
     *out = nullptr;
@@ -391,46 +432,19 @@ int amg_jacobi_prolongation_device(int n, int n_coarse, const int *Sp, const int
     }
     CHK(require_device());
     LapClock timer;
-    const long s_nnz = Sp[n];
-    long p_nnz = Tp[n];
-    HbmCsr S;
-    DBuf ddinv, dPp, dPj, dPx, Wx;
-    CHK(S.upload(n, Sp, Sj, Sx));
-    if (!S.x.p) CHK(S.x.alloc(0));
+    HbmCsr S, P;
+    DBuf ddinv;
+    CHK(S.upload(n, Sp, Sj, Sx, true));
     CHK(ddinv.from_host(dinv, sizeof(double) * (size_t)n));
-    CHK(dPp.from_host(Tp, sizeof(int) * ((size_t)n + 1)));
-    CHK(dPj.from_host(Tj, sizeof(int) * (size_t)p_nnz));
-    CHK(dPx.from_host(Tx, sizeof(double) * (size_t)p_nnz));
+    CHK(P.upload(n, Tp, Tj, Tx, true));
     AMG_HIP(hipDeviceSynchronize());
     const double upload_ms = timer.lap();
-    CHK(Wx.alloc(sizeof(double) * (size_t)s_nnz));
-    hipLaunchKernelGGL(jacobi_weight_kernel, grid_for(n), dim3(TB), 0, nullptr, n, w, (const int *)S.p.i(), (const double *)S.x.d(),
-                       (const double *)ddinv.d(), Wx.d());
-    LAUNCH_CHECK("jacobi smoothing: weight launch");
-    DevArr<long> Wp64;
-    CHK(widen_rowptr_device(n, S.p.i(), Wp64));
-    for (int step = 0; step < degree; ++step) {
-        DevArr<long> Pp64, Xp;
-        DevArr<int> Xj;
-        DevArr<double> Xx;
-        long x_nnz = 0;
-        if (s_nnz > 0 && p_nnz > 0) {
-            CHK(widen_rowptr_device(n, dPp.i(), Pp64));
-            const int rc = spgemm_device(n, n, n_coarse, s_nnz, Wp64, S.j.i(), Wx.d(), p_nnz, Pp64, dPj.i(), dPx.d(), &x_nnz, Xp, Xj, Xx);
-            if (rc == AMG_EINVAL) return AMG_ENOTIMPL;      // the product routes' refusal: the caller's host route
-            CHK(rc);
-        } else {                                            // a product without entries: nothing to launch
-            AMG_HIP(Xp.malloc_bytes(sizeof(long) * ((size_t)n + 1)));
-            AMG_HIP(hipMemset(Xp.p, 0, sizeof(long) * ((size_t)n + 1)));
-        }
-        CHK(jacobi_subtract_device(n, dPp, dPj, dPx, &p_nnz, Xp, Xj, Xx, x_nnz));
-    }
-    AMG_HIP(hipDeviceSynchronize());
+    h->nnz = Tp[n];
+    CHK(jacobi_smoothing_resident(n, n_coarse, S, Sp[n], ddinv.d(), w, degree, P, &h->nnz));
     const double hbm_ms = timer.lap();
-    CHK(dPp.to_host(Pp, sizeof(int) * ((size_t)n + 1)));
-    h->nnz = p_nnz;
-    h->j = std::move(dPj);
-    h->x = std::move(dPx);
+    CHK(P.p.to_host(Pp, sizeof(int) * ((size_t)n + 1)));
+    h->j = std::move(P.j);
+    h->x = std::move(P.x);
     if (times_ms) { times_ms[0] = upload_ms; times_ms[1] = hbm_ms; }
     *out = h.release();
     return 0;
@@ -438,7 +452,7 @@ int amg_jacobi_prolongation_device(int n, int n_coarse, const int *Sp, const int
 
 int amg_jacobi_prolongation_fetch(amg_prolong *h, int *Pj, double *Px, double *times_ms)
 {
-    return fetch_prolong("jacobi smoothing fetch", h, Pj, Px, times_ms);
+    return amg::fetch_prolong("jacobi smoothing fetch", h, Pj, Px, times_ms);
 }
 
 }   // extern "C"

@@ -245,7 +245,7 @@ int amg_mis_device(int n, const int *Ap, const int *Aj, const double *y, int act
     if (n < 0 || (n > 0 && (!y || !x))) { set_error("mis: bad arguments"); return AMG_EINVAL; }
     if (active == C || active == F) { set_error("mis: the active value must differ from C and F"); return AMG_EINVAL; }
     if (rounds) *rounds = 0;
-    if (times_ms) times_ms[0] = times_ms[1] = times_ms[2] = 0.0;
+    clear_times(times_ms);
     if (n == 0) return 0;
     CHK(check_graph("mis", n, Ap, Aj));
     CHK(require_device());
@@ -273,7 +273,7 @@ int amg_cljp_device(int n, const int *Sp, const int *Sj, const int *Tp, const in
 {
     if (n < 0 || (n > 0 && (!weight0 || !splitting))) { set_error("cljp: bad arguments"); return AMG_EINVAL; }
     if (passes) *passes = 0;
-    if (times_ms) times_ms[0] = times_ms[1] = times_ms[2] = 0.0;
+    clear_times(times_ms);
     if (n == 0) return 0;
     CHK(check_graph("cljp: S", n, Sp, Sj));
     CHK(check_graph("cljp: T", n, Tp, Tj));

@@ -9,7 +9,7 @@
 // entries by writing 0.0 and then calls eliminate_zeros(), so does the pipeline (count per row, scan, fill, order
 // kept).  Transposes and row sorts are one radix sort of (row, column) keys: indices are unique, so the order is
 // scipy's.  Only row counts and offsets travel to the host between upload and fetch.
-#include "flat.hpp"
+#include "graph_dev.hpp"
 
 #include <cfloat>
 #include <cmath>
@@ -18,7 +18,6 @@
 #include <utility>
 
 #include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 using namespace amg;
 
@@ -99,7 +98,8 @@ __global__ __launch_bounds__(TB) void min_blocks_kernel(int n_blocks, int blocks
     Tx[i] = m;
 }
 
-// a CSR pointer array of an entry's arguments: n + 1 offsets, from 0 up, never decreasing, within the arrays they index
+// a CSR pointer array of an entry's arguments: n + 1 offsets that never decrease, within the arrays they index.
+// Not graph_dev.hpp's pair: the amgcore_* entries accept a first offset above 0, as the reference's loops do.
 int check_offsets(const char *name, const int *p, int p_size, int n, int j_size, int x_size)
 {
     if (!p || n < 0 || p_size < n + 1) { set_error(std::string(name) + ": pointer array shorter than rows + 1"); return AMG_EINVAL; }
@@ -135,7 +135,9 @@ int filter_entry(int n_row, double epsilon, const int *Sp, int Sp_size, const in
 }
 
 // ---------------------------------------------------------------------------------------------- the pipeline
-struct DMat {                  // a square CSR matrix in HBM, 64-bit offsets (the layout of spgemm.hip's operands)
+// A square CSR matrix in HBM with 64-bit offsets in typed arrays, the layout of spgemm.hip's operands and results, which
+// are moved in and out of it.  Not graph_dev.hpp's HbmCsr, whose offsets are ints in untyped buffers.
+struct DMat {
     int n = 0;
     long nnz = 0;
     DevArr<long> p;
@@ -151,16 +153,11 @@ struct DMat {                  // a square CSR matrix in HBM, 64-bit offsets (th
     }
 };
 
-// offsets (n + 1) from per-row counts (count[n] = 0) by a device scan; the total comes back to the host
-int offsets_from_counts(int n, const long *count, long *offsets, long *total)
+// offsets (n + 1, a DMat's own: no DBuf, and no bound, for graph_dev.hpp's helper) from per-row counts (count[n] = 0)
+int scan_counts(int n, const long *count, long *offsets, long *total)
 {
-    size_t bytes = 0;
-    AMG_HIP(rocprim::exclusive_scan(nullptr, bytes, count, offsets, 0L, (size_t)n + 1, rocprim::plus<long>(), nullptr));
-    DBuf tmp;
-    CHK(tmp.alloc(bytes));
-    AMG_HIP(rocprim::exclusive_scan(tmp.p, bytes, count, offsets, 0L, (size_t)n + 1, rocprim::plus<long>(), nullptr));
-    AMG_HIP(hipMemcpy(total, offsets + n, sizeof(long), hipMemcpyDeviceToHost));
-    return 0;
+    CHK(exclusive_scan(count, offsets, (size_t)n + 1));
+    return last_offset(offsets, n, total);
 }
 
 // Every count/fill pair below is ONE device function instantiated twice, so both passes take the same decisions.
@@ -281,7 +278,7 @@ int reorder(const DMat &S, int transposed, DMat &T)
     hipLaunchKernelGGL(widen_kernel, grid_for((long)n + 1), dim3(TB), 0, nullptr, n, cnt32.as<int>(), cnt64.as<long>());
     LAUNCH_CHECK("strength: count widening launch");
     long total = 0;
-    CHK(offsets_from_counts(n, cnt64.as<long>(), T.p, &total));
+    CHK(scan_counts(n, cnt64.as<long>(), T.p, &total));
     if (total != nnz) { set_error("strength: reordered matrix lost entries"); return AMG_ESTATE; }
     return 0;
 }
@@ -298,7 +295,7 @@ int reorder(const DMat &S, int transposed, DMat &T)
                            (const long *)nullptr, (int *)nullptr, (double *)nullptr);                               \
         LAUNCH_CHECK(what " (count)");                                                                               \
         long total__ = 0;                                                                                            \
-        CHK(offsets_from_counts((NROWS), count__.as<long>(), (MAT).p, &total__));                                          \
+        CHK(scan_counts((NROWS), count__.as<long>(), (MAT).p, &total__));                                                  \
         CHK((MAT).alloc_entries(total__));                                                                             \
         hipLaunchKernelGGL(KFILL, grid_for((long)(NROWS) + 1), dim3(TB), 0, nullptr, __VA_ARGS__, (long *)nullptr,       \
                            (const long *)(MAT).p, (MAT).j, (MAT).x);                                                       \

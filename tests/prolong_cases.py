@@ -399,3 +399,66 @@ def model_jacobi(S, T, dinv, w, degree, steps=None):
     if T.format == "bsr":
         return sps.bsr_matrix((Px.reshape(-1, 1, 1), Pj, Pp), shape=T.shape)
     return sps.csr_matrix((Px, Pj, Pp), shape=T.shape)
+
+
+# -------------------------------------------------------------------------------------------------- degenerate sizes
+# Matrices without rows, without stored entries and of one row: the shapes at which an upload has no bytes, an
+# allocation no size and a branch nothing to launch.
+def _no_entries(shape, dtype=np.float64):
+    return sps.csr_matrix(shape, dtype=dtype)
+
+
+def degenerate_strength_names():
+    return ["%s_theta_%g" % (kind, theta) for theta in (0, 0.25) for kind in ("no_rows", "no_entries_3x3", "one_by_one")]
+
+
+@functools.lru_cache(maxsize=None)
+def degenerate_strength_cases():
+    """name -> (A, theta)"""
+    out = {}
+    for theta in (0, 0.25):
+        out["no_rows_theta_%g" % theta] = (_no_entries((0, 0)), theta)
+        out["no_entries_3x3_theta_%g" % theta] = (_no_entries((3, 3)), theta)
+        out["one_by_one_theta_%g" % theta] = (sps.csr_matrix(np.array([[2.0]])), theta)
+    return out
+
+
+def degenerate_fit_names():
+    return ["no_members_3x1", "second_aggregate_empty_3x2"]
+
+
+@functools.lru_cache(maxsize=None)
+def degenerate_fit_cases():
+    """name -> (AggOp, B), K1 = K2 = 1.  An aggregate without members leaves a zero in R and no block in T."""
+    B = np.array([[1.0], [2.0], [3.0]])
+    one = sps.csr_matrix((np.ones(1, dtype=np.int8), np.array([0], dtype=np.intc), np.array([0, 0, 1, 1], dtype=np.intc)), shape=(3, 2))
+    return {"no_members_3x1": (_no_entries((3, 1), np.int8), B), "second_aggregate_empty_3x2": (one, B)}
+
+
+def degenerate_jacobi_names():
+    return ["%s_degree%d" % (kind, degree) for kind in ("no_entries_in_T", "no_entries_in_S", "one_by_one") for degree in (1, 2)]
+
+
+@functools.lru_cache(maxsize=None)
+def degenerate_jacobi_cases():
+    """name -> dict(S, T, omega, degree, weighting), weighting 'local' (with 'diagonal' an S without entries has a zero
+    spectral radius, which the host route divides by)"""
+    tridiagonal = sps.diags([-1.0, 2.0, -1.0], [-1, 0, 1], shape=(3, 3), format="csr")
+    columns = sps.csr_matrix((np.ones(3), np.array([0, 0, 1], dtype=np.intc), np.arange(4, dtype=np.intc)), shape=(3, 2))
+    operands = {"no_entries_in_T": (tridiagonal, _no_entries((3, 2))), "no_entries_in_S": (_no_entries((3, 3)), columns),
+                "one_by_one": (sps.csr_matrix(np.array([[2.0]])), sps.csr_matrix(np.array([[1.0]])))}
+    return {"%s_degree%d" % (kind, degree): dict(S=S, T=T, omega=4.0 / 3.0, degree=degree, weighting="local")
+            for kind, (S, T) in operands.items() for degree in (1, 2)}
+
+
+def degenerate_graph_names():
+    return ["no_vertices", "three_isolated_vertices", "identity_3x3"]
+
+
+@functools.lru_cache(maxsize=None)
+def degenerate_graphs():
+    """name -> (Cm, y) for mis_aggregation.  A vertex without an off-diagonal entry is no root: the last two give zero
+    aggregates."""
+    return {"no_vertices": (_no_entries((0, 0), np.int8), np.zeros(0)),
+            "three_isolated_vertices": (_no_entries((3, 3), np.int8), np.array([0.5, 0.25, 0.75])),
+            "identity_3x3": (sps.identity(3, dtype=np.int8, format="csr"), np.array([0.5, 0.25, 0.75]))}

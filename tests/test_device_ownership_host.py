@@ -48,7 +48,7 @@ def test_library_loads_and_holds_nothing():
 
 
 def test_sources_are_there():
-    assert len(glob.glob(os.path.join(CSRC, "*.hip"))) == 20 and os.path.exists(os.path.join(CSRC, "driver.hpp"))
+    assert len(glob.glob(os.path.join(CSRC, "*.hip"))) == 21 and os.path.exists(os.path.join(CSRC, "driver.hpp"))
 
 
 def test_frees_only_in_the_owner_and_at_the_boundary():

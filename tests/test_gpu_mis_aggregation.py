@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import mis_cases as mc
+import prolong_cases as pc
 from pyamg_amd import _host, _lib, aggregation, graph, smoothed_aggregation_solver
 from pyamg_amd.aggregation import mis_aggregation, symmetric_strength_of_connection
 from pyamg_amd.gallery import poisson
@@ -66,6 +67,17 @@ def test_device_aggregation_equals_the_host_route_on_strength_patterns(grid):
     for y in (np.random.RandomState(0).rand(n), np.random.RandomState(1).randint(0, 4, n) / 4.0):
         AggOp, Cpts = _both_routes(Cm, y)
         assert AggOp.nnz == n and 0 < len(Cpts) < n / 4
+
+
+@pytest.mark.parametrize("name", pc.degenerate_graph_names())
+def test_device_aggregation_equals_the_host_route_on_degenerate_sizes(name):
+    Cm, y = pc.degenerate_graphs()[name]
+    live, rounds = _lib.live_buffers(), []
+    dev = mis_aggregation(Cm.copy(), y.copy(), device=True, rounds=rounds)
+    host = mis_aggregation(Cm.copy(), y.copy(), device=False, rounds=rounds)
+    assert pc.same_matrix(dev[0], host[0]) and dev[1].dtype == host[1].dtype and np.array_equal(dev[1], host[1])
+    assert dev[0].shape == (Cm.shape[0], 1) and dev[0].nnz == 0 and len(dev[1]) == 0     # no vertex has a neighbour: no root
+    assert rounds[0] == rounds[1] and _lib.live_buffers() == live
 
 
 @pytest.mark.parametrize("grid", [(40, 40), (12, 12, 12)], ids=["poisson_40x40", "poisson_12x12x12"])

@@ -1,4 +1,4 @@
-"""Symmetric strength, fit_candidates and Jacobi prolongation smoothing on the device (csrc/prolong.hpp, DESIGN.md section
+"""Symmetric strength, fit_candidates and Jacobi prolongation smoothing on the device (csrc/prolong.hip, DESIGN.md section
 8m) against their host routes, which tests/test_prolong_cases_host.py pins to the plain-Python models, on every designed
 case of tests/prolong_cases.py; then the solver option that sends every level through them.  Every comparison is exact
 equality of arrays, dtypes and format included.
@@ -68,6 +68,43 @@ def test_device_jacobi_equals_the_host_route(name):
     assert pc.same_matrix(dev[0], host[0]) and dev[0].format == c["T"].format
     assert pc.same_matrix(dev[1], host[1]) and dev[2] == host[2]        # the same sort of S, the same draws
     assert (_good_times(times) if c["degree"] else times == []) and _lib.live_buffers() == live
+
+
+# The degenerate sizes: no rows, no stored entries, one row.  An upload of no bytes, an allocation of no size and the
+# branches that launch nothing must give what the host route gives.
+@pytest.mark.parametrize("name", pc.degenerate_strength_names())
+def test_device_strength_equals_the_host_route_on_degenerate_sizes(name):
+    A, theta = pc.degenerate_strength_cases()[name]
+    live, times = _lib.live_buffers(), []
+    dev = symmetric_strength_of_connection(A.copy(), theta, device=True, times=times)
+    assert pc.same_matrix(dev, symmetric_strength_of_connection(A.copy(), theta, device=False))
+    assert _good_times(times) and _lib.live_buffers() == live
+
+
+@pytest.mark.parametrize("name", pc.degenerate_fit_names())
+def test_device_fit_candidates_equals_the_host_route_on_degenerate_sizes(name):
+    AggOp, B = pc.degenerate_fit_cases()[name]
+    live, times = _lib.live_buffers(), []
+    T, Bc = fit_candidates(AggOp.copy(), B.copy(), device=True, times=times)
+    Th, Bh = fit_candidates(AggOp.copy(), B.copy(), device=False)
+    assert pc.same_matrix(T, Th)
+    assert Bc.dtype == Bh.dtype and Bc.shape == Bh.shape and np.array_equal(Bc, Bh)
+    assert _good_times(times) and _lib.live_buffers() == live
+
+
+@pytest.mark.parametrize("name", pc.degenerate_jacobi_names())
+def test_device_jacobi_equals_the_host_route_on_degenerate_sizes(name):
+    c = pc.degenerate_jacobi_cases()[name]
+
+    def run(device, times=None):
+        S = c["S"].copy()
+        P = jacobi_prolongation_smoother(S, c["T"].copy(), None, None, omega=c["omega"], degree=c["degree"],
+                                         weighting=c["weighting"], device=device, times=times)
+        return P, S
+    live, times = _lib.live_buffers(), []
+    dev, host = run(True, times), run(False)
+    assert pc.same_matrix(dev[0], host[0]) and pc.same_matrix(dev[1], host[1])
+    assert _good_times(times) and _lib.live_buffers() == live
 
 
 def test_failed_and_refused_calls_leave_no_buffers():

@@ -163,6 +163,44 @@ def test_jacobi_cases_hold_what_they_are_designed_for():
         assert {c["T"].format for n, c in pc.jacobi_cases().items() if n.startswith(prefix)} == {"csr", "bsr"}
 
 
+# ------------------------------------------------------------------------------------------------- degenerate sizes
+@pytest.mark.parametrize("name", pc.degenerate_strength_names())
+def test_strength_host_route_equals_the_model_on_degenerate_sizes(name):
+    A, theta = pc.degenerate_strength_cases()[name]
+    Sp, Sj, Sx = pc.model_strength(A, theta)
+    got = symmetric_strength_of_connection(A.copy(), theta)
+    assert pc.same_matrix(got, sps.csr_matrix((Sx, Sj, Sp), shape=A.shape))
+    assert got.nnz == (1 if A.shape[0] == 1 else 0) and np.array_equal(got.data, np.ones(got.nnz))
+
+
+@pytest.mark.parametrize("name", pc.degenerate_fit_names())
+def test_fit_candidates_host_route_equals_the_model_on_degenerate_sizes(name):
+    AggOp, B = pc.degenerate_fit_cases()[name]
+    Tp, Tj, Tx, R = pc.model_fit(AggOp, B)
+    T, Bc = fit_candidates(AggOp.copy(), B.copy())
+    assert pc.same_matrix(T, sps.bsr_matrix((Tx, Tj, Tp), shape=AggOp.shape, blocksize=(1, 1)))
+    assert Bc.dtype == R.dtype and Bc.shape == R.shape and np.array_equal(Bc, R)
+    assert Bc[-1, 0] == 0.0 and T.nnz == AggOp.nnz      # the aggregate without members: a zero in R, no block in T
+
+
+@pytest.mark.parametrize("name", pc.degenerate_jacobi_names())
+def test_jacobi_host_route_equals_the_model_on_degenerate_sizes(name):
+    c = pc.degenerate_jacobi_cases()[name]
+    S, Sm = c["S"].copy(), c["S"].copy()
+    got = jacobi_prolongation_smoother(S, c["T"].copy(), None, None, omega=c["omega"], degree=c["degree"], weighting=c["weighting"])
+    dinv, w = pc.jacobi_weights(Sm, c["omega"], c["weighting"])
+    assert pc.same_matrix(Sm, S) and pc.same_matrix(got, pc.model_jacobi(Sm, c["T"], dinv, w, c["degree"]))
+    if name.startswith("no_entries"):
+        assert pc.same_matrix(got, c["T"])              # nothing to subtract: T itself
+
+
+def test_degenerate_names_are_the_cases():
+    assert pc.degenerate_strength_names() == list(pc.degenerate_strength_cases())
+    assert pc.degenerate_fit_names() == list(pc.degenerate_fit_cases())
+    assert pc.degenerate_jacobi_names() == list(pc.degenerate_jacobi_cases())
+    assert pc.degenerate_graph_names() == list(pc.degenerate_graphs())
+
+
 # ------------------------------------------------------------------------------------------------------- refusals
 def test_device_refusals_come_before_the_library(monkeypatch):
     A, _ = pc.strength_cases()["designed_theta_0.25"]

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The smoothed-aggregation stages of DESIGN.md section 8m -- symmetric strength (theta = 0.1), fit_candidates (one
 candidate, the aggregates of standard_aggregation) and Jacobi prolongation smoothing (degree 1, weighting 'diagonal') --
-by the host route and by the device route (pyamg_amd/aggregation.py, csrc/prolong.hpp) on Poisson 500 x 500 and 100^3.
+by the host route and by the device route (pyamg_amd/aggregation.py, csrc/prolong.hip) on Poisson 500 x 500 and 100^3.
 
 host / device: the public calls, argument checks, transfers and the assembly of the result included; for the smoothing
 also the part both routes keep on the host (the diagonal, the scaled copy of S and the spectral-radius estimate, which
@@ -81,7 +81,7 @@ def main():
             lines.append(line)
             print(line, flush=True)
     say(["smoothed-aggregation stages, host route against device route; milliseconds, median of %d runs after one warm-up" % a.repeat,
-         "host: numpy, scipy and csrc/setup_host.cpp on %d threads; device: csrc/prolong.hpp" % _host.host_lib().amgsetup_num_threads(),
+         "host: numpy, scipy and csrc/setup_host.cpp on %d threads; device: csrc/prolong.hip" % _host.host_lib().amgsetup_num_threads(),
          "host / device: the public calls; upload, in HBM, fetch: the device entry's own clock",
          "%-16s %-15s %9s %10s %9s %9s  %8s %8s %8s" % ("problem", "stage", "rows", "entries", "host", "device", "upload", "in HBM", "fetch")])
     for name, grid in (("poisson 500x500", (500, 500)), ("poisson 100^3", (100, 100, 100))):

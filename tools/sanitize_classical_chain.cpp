@@ -1,16 +1,17 @@
-// Host-side checks of the transpose and chain entries under AddressSanitizer and UBSan, on the CPU: the validation that
-// runs before any launch (check_csr_arrays, check_unique_columns), the empty results and the argument refusals, on heap
+// Host-side checks of the transpose, chain and prolong entries under AddressSanitizer and UBSan, on the CPU: the validation
+// that runs before any launch (check_csr_arrays, check_unique_columns), the empty results and the argument refusals, on heap
 // arrays of exactly the stated sizes so that a read past them is caught.  No GPU is used: every call here returns
 // before the first device call, or with AMG_ENODEV where there is no device.  Build and run from pyamg_amd/csrc after
-// `make` (classical.hip and transpose.hip instrumented, the other objects as they are):
+// `make` (classical.hip, transpose.hip and prolong.hip instrumented, the other objects as they are):
 //
-//   for u in classical transpose; do
+//   for u in classical transpose prolong; do
 //     hipcc -O1 -g -std=c++17 -fPIC -ffp-contract=off --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined \
 //           -c $u.hip -o /tmp/${u}_san.o; done
 //   $(hipconfig -l)/clang++ -O1 -g -std=c++17 -fsanitize=address,undefined -c ../../tools/sanitize_classical_chain.cpp \
 //         -o /tmp/main_san.o
 //   hipcc --offload-arch=gfx950 -fsanitize=address,undefined /tmp/main_san.o /tmp/classical_san.o /tmp/transpose_san.o \
-//         $(ls _obj/*.o | grep -v -e /classical.o -e /transpose.o) -ldl -o /tmp/sanitize_classical_chain \
+//         /tmp/prolong_san.o $(ls _obj/*.o | grep -v -e /classical.o -e /transpose.o -e /prolong.o) -ldl \
+//         -o /tmp/sanitize_classical_chain \
 //     && /tmp/sanitize_classical_chain
 #include <cstdint>
 
@@ -91,6 +92,41 @@ int main()
         EXPECT(amg_extended_interpolation_device(0, Ap0.data(), nullptr, nullptr, Sp0.data(), nullptr, nullptr, 0, Pp0.data(), &e,
                                                  nullptr) == 0 && e && Pp0[0] == 0);
         EXPECT(amg_extended_interpolation_fetch(e, nullptr, nullptr) == 0);
+    }
+    // the three prolong entries: what they refuse, and return for no rows, before any device call
+    {
+        const std::vector<int> Ap{0, 2, 3}, Aj{0, 1, 1}, outside{0, 2, 1};
+        const std::vector<double> Ax{2.0, -1.0, 2.0}, dinv{0.5, 0.5};
+        std::vector<int> Sp(3, -7);
+        amg_prolong *h = nullptr;
+        double ms[3] = {-1.0, -1.0, -1.0};
+        EXPECT(amg_symmetric_strength_device(2, Ap.data(), outside.data(), Ax.data(), 0.25, Sp.data(), &h, ms) == AMG_EINVAL && !h);
+        EXPECT(amg_symmetric_strength_device(2, Ap.data(), Aj.data(), Ax.data(), -0.5, Sp.data(), &h, ms) == AMG_EINVAL && !h);
+        EXPECT(Sp[0] == -7 && ms[0] == 0.0 && ms[1] == 0.0 && ms[2] == 0.0);
+        const std::vector<int> none{0};
+        EXPECT(amg_symmetric_strength_device(0, none.data(), nullptr, nullptr, 0.25, Sp.data(), &h, nullptr) == 0 && h && Sp[0] == 0);
+        EXPECT(amg_symmetric_strength_fetch(h, nullptr, nullptr, ms) == 0);
+        // AggOp 2 x 2 with node 0 in both aggregates; then no nodes
+        const std::vector<int> two_p{0, 2, 2}, two_j{0, 1};
+        const std::vector<double> B{1.0, 1.0};
+        std::vector<double> Tx(2, -7.0), R(2, -7.0);
+        EXPECT(amg_fit_candidates_device(2, 2, 1, 1, two_p.data(), two_j.data(), B.data(), 1e-10, Tx.data(), R.data(), ms) == AMG_EINVAL);
+        EXPECT(amg_fit_candidates_device(2, 2, 1, 0, Ap.data(), Aj.data(), B.data(), 1e-10, Tx.data(), R.data(), ms) == AMG_EINVAL);
+        EXPECT(amg_fit_candidates_device(0, 2, 1, 1, none.data(), nullptr, nullptr, 1e-10, nullptr, R.data(), ms) == 0);
+        EXPECT(Tx[0] == -7.0 && R[0] == -7.0);
+        // T 2 x 2 with column 1 twice in row 1; then a column of S outside; then no rows
+        const std::vector<int> twice_j{0, 1, 1}, Tp{0, 1, 3};
+        h = nullptr;
+        EXPECT(amg_jacobi_prolongation_device(2, 2, Ap.data(), Aj.data(), Ax.data(), dinv.data(), 1.0, 1, Tp.data(), twice_j.data(),
+                                              Ax.data(), Sp.data(), &h, ms) == AMG_EINVAL && !h);
+        EXPECT(amg_jacobi_prolongation_device(2, 2, Ap.data(), outside.data(), Ax.data(), dinv.data(), 1.0, 1, Ap.data(), Aj.data(),
+                                              Ax.data(), Sp.data(), &h, ms) == AMG_EINVAL && !h);
+        Sp[0] = -7;
+        EXPECT(amg_jacobi_prolongation_device(0, 2, none.data(), nullptr, nullptr, nullptr, 1.0, 1, none.data(), nullptr, nullptr,
+                                              Sp.data(), &h, ms) == 0 && h && Sp[0] == 0);
+        EXPECT(amg_jacobi_prolongation_fetch(h, nullptr, nullptr, ms) == 0);
+        EXPECT(amg_symmetric_strength_fetch(nullptr, nullptr, nullptr, nullptr) == AMG_EINVAL);
+        EXPECT(amg_jacobi_prolongation_fetch(nullptr, nullptr, nullptr, nullptr) == AMG_EINVAL);
     }
     // every fetch refuses a null handle
     EXPECT(amg_extended_interpolation_fetch(nullptr, nullptr, nullptr) == AMG_EINVAL);
