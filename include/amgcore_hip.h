@@ -886,6 +886,60 @@ int amg_classical_chain_fetch(amg_classical_chain *chain, int *splitting, int *P
                               int *Cp, int *Cj, double *Cx, int *Sp, int *Sj, double *Sx, double *times_ms);
 void amg_classical_chain_free(amg_classical_chain *chain);
 
+/* A chain of MIS(2) smoothed-aggregation levels that stays in HBM (csrc/prolong.hip): one upload
+ * of A_0 and of its one candidate B_0, then per level one call that builds it and one that downloads what the host
+ * hierarchy keeps.  Real float64, scalar unknowns, one candidate.
+ *
+ * amg_sa_chain_begin validates A_0 (n x n, n > 0, no column twice in a row: AMG_EINVAL; a value that is not finite:
+ * AMG_ENOTIMPL) and uploads it with B (n values) as the chain's resident operator and candidate.
+ *
+ * amg_sa_chain_level builds the level of the resident operator (n: its rows as the caller has them, the length of y,
+ * dinv and B; another size is AMG_EINVAL before anything is read): symmetric strength with theta on the operator as it is
+ * stored (strength_mode AMG_SA_STRENGTH_CSR: amg_symmetric_strength_device's; _SQUARED: the same on the values a*a, one
+ * rounding, what the host makes of a BSR operator with 1 x 1 blocks; _ONES: the whole pattern in stored order with every
+ * value 1.0, the host's answer for such an operator with theta == 0); a check that the pattern of S is structurally
+ * symmetric (AMG_EINVAL "expected a structurally symmetric pattern" otherwise); MIS(2) aggregation on y (n finite
+ * weights); AggOp from the aggregate of every vertex; the tentative prolongator T and the coarse candidate B_c with tol;
+ * the rows of the operator sorted by column, where they are not sorted already; `degree` Jacobi steps P <- P - W P with
+ * W_ik = (A_ik * dinv_i) * w on the sorted operator; R = P^T; R * A and A_c = (R * A) * P on the sorted operator; one
+ * pass over A_c for its facts.  B (or NULL): n values that replace the resident candidate first.
+ * sizes (5 longs): the entries of S [0], T [1], P [2] and A_c [3] and the coarse size [4].  flags
+ * (AMG_SA_CHAIN_FLAG_FIELDS ints): [0] 1 where every row of A_c is strictly ascending, [1] 1 where every value of A_c
+ * is finite, [2] 1 where the pattern of S is symmetric, [3] why the level stopped after the aggregation or in the
+ * smoothing (0: it did not, AMG_SA_NO_AGGREGATE: MIS(2) found no aggregate, AMG_SA_SMOOTHING_REFUSED: a product of the
+ * smoothing was refused), [4] and [5] the tables of R * A and of (R * A) * P, [6 .. 9] the fields of
+ * amg_transpose_last_route.  *rounds (or NULL): the rounds of the independent set.  times_ms (or NULL,
+ * AMG_SA_CHAIN_STAGES doubles): upload [0], strength [1], symmetry check, aggregation and AggOp [2], tentative
+ * prolongator [3], row sort [4] (exactly 0 where the rows were sorted already), smoothing [5], transpose [6], the two products and the pass over A_c [7]; the fetch
+ * writes the same eight and its own time [8].  Returns 0, or AMG_CHAIN_PRODUCT_REFUSED where a Galerkin product was
+ * refused: the level then holds P and B_c (and S, the aggregates and T for a caller that keeps them).  A second call
+ * before the fetch is AMG_ESTATE.  Any other return is an error and leaves the chain without a level, its resident
+ * operator and candidate as they were.
+ *
+ * amg_sa_chain_fetch copies the level to the host: Pp (n + 1), Pj, Px (sizes[2]), Rp (sizes[4] + 1), Rj, Rx (sizes[2]),
+ * Cp (sizes[4] + 1), Cj, Cx (sizes[3]), Bc (sizes[4]) and, where they are not NULL, Sp (n + 1), Sj, Sx (sizes[0]), agg
+ * (n, -1: no aggregate) and Tx (sizes[1]).  A_c (in the order of the product) and B_c then become the resident operator
+ * and candidate.  With Rp or Cp NULL a built level is fetched like one
+ * whose product was refused: its caller forms the coarse operator itself.  After AMG_CHAIN_PRODUCT_REFUSED the R and C arrays are not read; after a level that stopped
+ * (flags[3]) only Sp, Sj, Sx are, and they are required; either way the chain is left without an operator.  A failing
+ * fetch releases the level and keeps the operator the chain had.
+ *
+ * amg_sa_chain_free releases the chain with everything it holds (NULL: nothing). */
+typedef struct amg_sa_chain amg_sa_chain;
+#define AMG_SA_CHAIN_FLAG_FIELDS 10
+#define AMG_SA_CHAIN_STAGES 9
+#define AMG_SA_STRENGTH_CSR 0
+#define AMG_SA_STRENGTH_SQUARED 1
+#define AMG_SA_STRENGTH_ONES 2
+#define AMG_SA_NO_AGGREGATE 1
+#define AMG_SA_SMOOTHING_REFUSED 2
+int amg_sa_chain_begin(int n, const int *Ap, const int *Aj, const double *Ax, const double *B, amg_sa_chain **out);
+int amg_sa_chain_level(amg_sa_chain *chain, int n, double theta, int strength_mode, const double *y, const double *dinv, double w, int degree,
+                       const double *B, double tol, long *sizes, int *flags, int *rounds, double *times_ms);
+int amg_sa_chain_fetch(amg_sa_chain *chain, int *Pp, int *Pj, double *Px, int *Rp, int *Rj, double *Rx, int *Cp, int *Cj, double *Cx,
+                       double *Bc, int *Sp, int *Sj, double *Sx, int *agg, double *Tx, double *times_ms);
+void amg_sa_chain_free(amg_sa_chain *chain);
+
 /* Extended+i (distance-two) interpolation (csrc/classical.hip) from a float64 CSR operator A, the
  * pattern of a strength matrix S of A's shape and a C/F splitting (1 = C, 0 = F), all on the host with 32-bit offsets;
  * rows in any stored order.  An F row interpolates from C_hat, its strong C neighbours and those of its strong F

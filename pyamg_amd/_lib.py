@@ -220,6 +220,9 @@ def lib():
         "amg_classical_chain_begin": [I, V, V, V, I, C.POINTER(C.c_void_p)],
         "amg_classical_chain_level": [V, D, I, V, I, I, C.POINTER(C.c_long), c_int_p, c_int_p, c_dbl_p],
         "amg_classical_chain_fetch": [V] * 14 + [c_dbl_p],
+        "amg_sa_chain_begin": [I, V, V, V, V, C.POINTER(C.c_void_p)],
+        "amg_sa_chain_level": [V, I, D, I, V, V, D, I, V, D, C.POINTER(C.c_long), c_int_p, c_int_p, c_dbl_p],
+        "amg_sa_chain_fetch": [V] * 16 + [c_dbl_p],
         "amg_extended_interpolation_device": [I, V, V, V, V, V, V, I, V, C.POINTER(C.c_void_p), c_dbl_p],
         "amg_extended_interpolation_fetch": [V, V, V],
         "amg_hierx_create": [I, I, I, C.POINTER(C.c_void_p)],
@@ -271,6 +274,8 @@ def lib():
     L.amg_device_name.restype = C.c_char_p
     L.amg_classical_chain_free.argtypes = [V]
     L.amg_classical_chain_free.restype = None
+    L.amg_sa_chain_free.argtypes = [V]
+    L.amg_sa_chain_free.restype = None
     L.amg_hier_create.argtypes = [I, I]
     L.amg_hier_create.restype = V
     L.amg_hier_destroy.argtypes = [V]
@@ -477,6 +482,10 @@ TRANSPOSE_ROUTE_FIELDS = ("launched", "lane_rows", "lds_rows", "hbm_rows")
 TRANSPOSE_LANE_MAX, TRANSPOSE_LDS_MAX = 32, 2048
 CHAIN_PRODUCT_REFUSED = 1
 CHAIN_FLAG_FIELDS = 8
+# amg_sa_chain_level: the fields of its flags, its strength modes and why a level stopped (include/amgcore_hip.h)
+SA_CHAIN_FLAG_FIELDS = 10
+SA_STRENGTH_CSR, SA_STRENGTH_SQUARED, SA_STRENGTH_ONES = 0, 1, 2
+SA_NO_AGGREGATE, SA_SMOOTHING_REFUSED = 1, 2
 
 
 def transpose_last_route():

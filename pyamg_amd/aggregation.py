@@ -516,13 +516,15 @@ def _jacobi_device(S, T, D_inv, w, degree, times=None):
 
 
 def jacobi_prolongation_smoother(S, T, Cm, B, omega=4.0 / 3.0, degree=1, filter=False,
-                                 weighting="diagonal", device=None, times=None):
+                                 weighting="diagonal", device=None, times=None, weights=None):
     """pyamg/aggregation/smooth.py:67-210 (weighting 'diagonal' / 'local', no filtering).
 
     device : True = the device route (real float64 S and T with 1 x 1 blocks, one candidate, no
     filtering; the diagonal, the spectral radius and the row sums of 'local' stay on the host, the weights, the products
     and the differences run in HBM), False or None = the host route (None: the device route where JACOBI_DEVICE_AUTO
-    and a GPU).  times : a list that receives the device route's (upload, in HBM, fetch) milliseconds."""
+    and a GPU).  times : a list that receives the device route's (upload, in HBM, fetch) milliseconds.
+    weights : what _jacobi_weights(S, omega, weighting) returned to a caller that has already sorted S and drawn for
+    it (the resident chain, which hands a level it could not finish on); nothing is sorted or drawn again."""
     way = route(device, JACOBI_DEVICE_AUTO)
     if way is not False:
         try:
@@ -538,7 +540,7 @@ def jacobi_prolongation_smoother(S, T, Cm, B, omega=4.0 / 3.0, degree=1, filter=
             weighting = "diagonal"
     if weighting not in ("diagonal", "local"):
         raise NotImplementedError("weighting=%r" % weighting)
-    D_inv_S, w, D_inv = _jacobi_weights(S, omega, weighting)
+    D_inv_S, w, D_inv = _jacobi_weights(S, omega, weighting) if weights is None else weights
     if degree <= 0:
         return T                        # (after the weights, as ever: S is sorted and the estimate has drawn)
 
@@ -776,7 +778,10 @@ def smoothed_aggregation_solver(A, B=None, BH=None, symmetry="hermitian", streng
     device : None = every stage as its own options say.  True or False = the `device` option of symmetric strength,
     MIS(2) aggregation, fit_candidates and Jacobi smoothing on every level that does not set its own; with True every
     level takes the generic path of extend_hierarchy, and options that put one of these stages outside its device route
-     raise NotImplementedError before any level is built."""
+     raise NotImplementedError before any level is built.  Where all four stages of a level run
+    on the device and _chain_options takes it ('symmetric' strength, 'mis' aggregation, Jacobi smoothing, real float64,
+    one candidate), the levels are chained in HBM from one upload of A and B; the hierarchy is
+    the same, bit for bit.  LAST_BUILD records the route of the last build."""
     if not (isspmatrix_csr(A) or isspmatrix_bsr(A)):
         try:
             A = csr_matrix(A)
@@ -823,8 +828,14 @@ def smoothed_aggregation_solver(A, B=None, BH=None, symmetry="hermitian", streng
     levels = [multilevel_solver.level()]
     levels[-1].A = A
     levels[-1].B = B
-    while len(levels) < max_levels and int(levels[-1].A.shape[0] / blocksize(levels[-1].A)) > max_coarse:
-        extend_hierarchy(levels, strength, aggregate, smooth, improve_candidates, keep or not fast, device=device)
+    LAST_BUILD["uploads"] = 0
+    LAST_BUILD["levels"] = []
+    chain = _Chain()
+    try:
+        while len(levels) < max_levels and int(levels[-1].A.shape[0] / blocksize(levels[-1].A)) > max_coarse:
+            extend_hierarchy(levels, strength, aggregate, smooth, improve_candidates, keep or not fast, device=device, chain=chain)
+    finally:
+        chain.close()
     t1 = time.perf_counter()
     ml = multilevel_solver(levels, **kwargs)
     t2 = time.perf_counter()
@@ -1235,9 +1246,205 @@ def _galerkin_c128_device(R, A, P):
     return _as_bsr11(Ac, (P.shape[1], P.shape[1]))
 
 
-def extend_hierarchy(levels, strength, aggregate, smooth, improve_candidates, keep=True, rho_fn=None, device=None):
+# --------------------------------------------------------------------------- the resident chain
+# The route of the last smoothed_aggregation_solver build, for the tests and tools/bench_sa_hierarchy.py.  uploads:
+# operators sent to HBM by the chain (one per chain; the stage routes' own uploads are not counted).  levels: one record
+# per level built: chained (the whole level, its transpose and its Galerkin product ran in HBM on the chain's resident
+# operator), resident (the chain built the prolongator, whoever formed the product), strength_mode (what the chain was
+# told about the host's format of A_l; None off the chain), stopped (why the chain handed the level on: 'no aggregate',
+# 'smoothing refused' or None), times (milliseconds by CHAIN_STAGES), products (the tables of R * A and (R * A) * P,
+# _lib.SPGEMM_TABLES) and transpose (_lib.TRANSPOSE_ROUTE_FIELDS).
+LAST_BUILD = {"uploads": 0, "levels": []}
+CHAIN_STAGES = ("upload", "strength", "aggregation", "tentative", "sort", "smoothing", "transpose", "galerkin", "fetch")
+# What tools/bench_sa_hierarchy.py turns off to time the per-stage device route (every stage uploads its operands and
+# fetches its result, transpose and Galerkin product on the host); not an option of the setup.
+_RESIDENT_CHAIN = True
+# a coarse operator of this many entries or more does not fit the host's 32-bit index arrays: the level's product is
+# treated as refused, as the device library itself refuses it
+_PRODUCT_ENTRIES_LIMIT = 2 ** 31
+_STOPPED = {1: "no aggregate", 2: "smoothing refused"}
+
+
+def _record_level(chained=False, resident=False, strength_mode=None, stopped=None, times=None, products=None, transpose=None):
+    LAST_BUILD["levels"].append({"chained": chained, "resident": resident, "strength_mode": strength_mode, "stopped": stopped,
+                                 "times": times or {}, "products": products, "transpose": transpose})
+
+
+class _Chain:
+    """the resident chain of one smoothed_aggregation_solver call: the handle of amg_sa_chain_begin and what the last
+    level's flags said about the operator it left in HBM: its rows and whether its values are finite"""
+
+    def __init__(self):
+        self.handle = None
+        self.finite = True
+        self.n = 0
+
+    def close(self):
+        if self.handle is not None:
+            from . import _lib
+            handle, self.handle = self.handle, None
+            _lib.lib().amg_sa_chain_free(handle)
+
+
+def _chain_options(A, B, strength_l, aggregate_l, smooth_l, device):
+    """(theta, omega, degree, weighting) where the whole level runs in HBM, None otherwise: a real float64 operator
+    with scalar unknowns and one candidate; 'symmetric' strength with theta alone, 'mis' aggregation without weights of
+    its own and 'jacobi' smoothing without filtering, of one step or more, with weighting 'diagonal', 'local' or
+    'block'; none of the four stages sent to the host (`device` is fit_candidates' option, the others carry theirs)."""
+    if not (isspmatrix_csr(A) or (isspmatrix_bsr(A) and A.blocksize == (1, 1))) or A.dtype != np.float64:
+        return None
+    if np.ndim(B) != 2 or B.shape[1] != 1 or B.dtype != np.float64:
+        return None
+    if route(device, FIT_CANDIDATES_DEVICE_AUTO) is False:
+        return None
+    fn, kw = unpack_arg(strength_l)
+    if fn != "symmetric" or set(kw) - {"theta", "device"} or route(kw.get("device"), SYMMETRIC_STRENGTH_DEVICE_AUTO) is False:
+        return None
+    theta = kw.get("theta", 0)
+    if not theta >= 0:
+        return None
+    fn, kw = unpack_arg(aggregate_l)
+    if fn != "mis" or set(kw) - {"device"} or route(kw.get("device"), MIS_DEVICE_AUTO) is False:
+        return None
+    fn, kw = unpack_arg(smooth_l)
+    if fn != "jacobi" or set(kw) - {"omega", "degree", "weighting", "filter", "device"} \
+            or route(kw.get("device"), JACOBI_DEVICE_AUTO) is False:
+        return None
+    weighting = kw.get("weighting", "diagonal")
+    if kw.get("filter", False) or weighting not in ("diagonal", "local", "block") or kw.get("degree", 1) < 1:
+        return None
+    # ('block' on scalar unknowns is 'diagonal', as jacobi_prolongation_smoother has it)
+    return theta, kw.get("omega", 4.0 / 3.0), int(kw.get("degree", 1)), "diagonal" if weighting == "block" else weighting
+
+
+def _chain_strength_mode(A, theta):
+    """What symmetric_strength_of_connection makes of the host's A_l: a CSR operator's values as they are; of a BSR
+    operator with 1 x 1 blocks (every level that scipy's bsr * csr * bsr left) the squared values, and with theta == 0
+    the whole pattern with every value 1.0"""
+    from . import _lib
+    if isspmatrix_csr(A):
+        return _lib.SA_STRENGTH_CSR
+    return _lib.SA_STRENGTH_ONES if theta == 0 else _lib.SA_STRENGTH_SQUARED
+
+
+def _chain_level_call(handle, n, theta, mode, y, D_inv, w, degree, B, sizes, flags, ms):
+    """amg_sa_chain_level -> 0 or _lib.CHAIN_PRODUCT_REFUSED (the tests wrap it to see the calls).  n: the rows of the
+    host's A_l, which the entry compares with its resident operator's before it reads y, D_inv and B."""
+    from . import _lib
+    rc = _lib.lib().amg_sa_chain_level(handle, n, float(theta), mode, y.ctypes.data, D_inv.ctypes.data, float(w), degree,
+                                       None if B is None else B.ctypes.data, 1e-10, sizes, flags, None, ms)
+    if rc != _lib.CHAIN_PRODUCT_REFUSED:
+        _lib.check(rc)
+    return rc
+
+
+def _chain_level(levels, chain, options, keep, improved):
+    """One level on the chain's resident operator and candidate (amg_sa_chain_level / _fetch): strength, MIS(2)
+    aggregation, the tentative prolongator, Jacobi smoothing, R = P^T and R A P in HBM; the host hierarchy receives what
+    it keeps.  The first level of a chain vets and uploads A and B.  improved: B is new on the host (candidate
+    improvement) and replaces the resident one.  The host draws the weights of the set and then takes the diagonal and
+    the spectral radius, in the order of the stage route, before the call.
+
+    Returns None where the level is built, or what the stage route needs to finish a level that stopped (no aggregate,
+    or a refused product of the smoothing) without sorting or drawing again: {'C', 'y', 'weights'}.  Whatever is
+    outside the chain raises NotImplementedError before anything is drawn; one from the level entry, after the draws,
+    becomes a RuntimeError.  Where a Galerkin product is refused the
+    level is finished on the host from the fetched P, and the chain ends."""
+    from . import _lib
+    A, B = levels[-1].A, levels[-1].B
+    theta, omega, degree, weighting = options
+    n = A.shape[0]
+    what = "a chained smoothed-aggregation level"
+    if chain.handle is not None and chain.n != n:
+        chain.close()                       # not the operator the chain left: this level begins another
+    if chain.handle is None:
+        if A.indptr.dtype != np.intc or A.indices.dtype != np.intc:
+            raise outside("%s of an operator without 32-bit indices" % what)
+        if n == 0 or A.shape[0] != A.shape[1] or int(A.indptr[-1]) >= 2 ** 31:
+            raise outside("%s of an operator that is empty, not square or of 2^31 entries or more" % what)
+        if not _columns_once(A):
+            raise outside("%s of an operator with a column twice in a row" % what)
+    elif not chain.finite:
+        raise outside("%s of an operator with values that are not finite" % what)
+    _finite_f64(what, B)
+    Bv = _f64(np.ravel(B))
+    if chain.handle is None:
+        # (in the order its product left it: the host's copy is sorted only below; a value that is not finite is
+        # AMG_ENOTIMPL from the pass over the uploaded operator)
+        Ap, Aj, Ax = _i32(A.indptr), _i32(A.indices), _f64(np.ravel(A.data))
+        handle = C.c_void_p()
+        _lib.check(_lib.lib().amg_sa_chain_begin(n, Ap.ctypes.data, Aj.ctypes.data, Ax.ctypes.data, Bv.ctypes.data, C.byref(handle)))
+        chain.handle, chain.finite, chain.n = handle, True, n
+        LAST_BUILD["uploads"] += 1
+        improved = False
+    mode = _chain_strength_mode(A, theta)
+    y = _f64(np.random.rand(n))
+    weights = _jacobi_weights(A, omega, weighting)
+    D_inv = _f64(np.ravel(weights[2]))
+    sizes = (C.c_long * 5)()
+    flags = (C.c_int * _lib.SA_CHAIN_FLAG_FIELDS)()
+    ms = (C.c_double * len(CHAIN_STAGES))()
+    try:
+        rc = _chain_level_call(chain.handle, n, theta, mode, y, D_inv, weights[1], degree, Bv if improved else None, sizes, flags, ms)
+    except NotImplementedError as e:
+        # the weights are drawn and the host's A_l is sorted: a refusal now must not reach the stage route, which would
+        # draw and sort again (the entry reports what it cannot finish in its flags instead)
+        raise RuntimeError("a chained smoothed-aggregation level was refused after its draws: %s" % e) from e
+    s_nnz, t_nnz, p_nnz, c_nnz, n_coarse = (int(v) for v in sizes)
+    stopped = int(flags[3])
+    refused = rc == _lib.CHAIN_PRODUCT_REFUSED or c_nnz >= _PRODUCT_ENTRIES_LIMIT
+    # the handle is the chain, which _Chain.close frees: nothing to release where an allocation fails
+    built, whole = not stopped, not stopped and not refused
+    arrays = _lib.allocate(_csr_specs(n, p_nnz, built) + _csr_specs(n_coarse, p_nnz, whole) + _csr_specs(n_coarse, c_nnz, whole)
+                           + [(n_coarse, np.float64) if built else None] + _csr_specs(n, s_nnz, keep or stopped)
+                           + ([(n, np.intc), (t_nnz, np.float64)] if keep and built else [None, None]))
+    Pp, Pj, Px, Rp, Rj, Rx, Cp, Cj, Cx, Bc, Sp, Sj, Sx, agg, Tx = arrays
+    _lib.check(_lib.lib().amg_sa_chain_fetch(chain.handle, *(None if a is None else a.ctypes.data for a in arrays), ms))
+    _record_level(chained=whole, resident=built, strength_mode=mode, stopped=_STOPPED.get(stopped),
+                  times=dict(zip(CHAIN_STAGES, ms)), products=(_lib.SPGEMM_TABLES[flags[4]], _lib.SPGEMM_TABLES[flags[5]]),
+                  transpose=dict(zip(_lib.TRANSPOSE_ROUTE_FIELDS, (int(v) for v in flags[6:10]))))
+    Cm = None
+    if Sp is not None:
+        Cm = csr_matrix((Sx, Sj.astype(A.indices.dtype, copy=False), Sp.astype(A.indptr.dtype, copy=False)), shape=A.shape)
+    if stopped:
+        chain.close()
+        return {"C": Cm, "y": y, "weights": weights}
+    P = bsr_matrix((Px.reshape(-1, 1, 1), Pj, Pp), shape=(n, n_coarse))
+    symmetry = A.symmetry
+    if refused:
+        chain.close()
+        R = P.conj().T.asformat(P.format) if symmetry == "hermitian" else P.T.asformat(P.format)
+        Ac = R * A * P
+    else:
+        chain.finite, chain.n = bool(flags[1]), n_coarse
+        R = bsr_matrix((Rx.reshape(-1, 1, 1), Rj, Rp), shape=(n_coarse, n))
+        Ac = bsr_matrix((Cx.reshape(-1, 1, 1), Cj, Cp), shape=(n_coarse, n_coarse))
+    if keep:
+        mask = agg != -1
+        Tp = np.concatenate(([0], np.cumsum(mask))).astype(np.intc)
+        Tj = agg[mask]
+        levels[-1].C = Cm
+        levels[-1].AggOp = csr_matrix((np.ones(Tp[-1], dtype="int8"), Tj, Tp), shape=(n, n_coarse))
+        levels[-1].T = bsr_matrix((Tx.reshape(-1, 1, 1), Tj.copy(), Tp.copy()), shape=(n, n_coarse), blocksize=(1, 1))
+    levels[-1].P = P
+    levels[-1].R = R
+    levels.append(multilevel_solver.level())
+    Ac._amg_columns_once = True             # a csr_matmat result, from either path
+    Ac.symmetry = symmetry
+    levels[-1].A = Ac
+    levels[-1].B = Bc.reshape(-1, 1)
+    return None
+
+
+def _csr_specs(n_row, nnz, wanted=True):
+    """the (count, dtype) of the three arrays of a CSR matrix for _lib.allocate, None each where it is not wanted"""
+    return [(n_row + 1, np.intc), (nnz, np.intc), (nnz, np.float64)] if wanted else [None, None, None]
+
+
+def extend_hierarchy(levels, strength, aggregate, smooth, improve_candidates, keep=True, rho_fn=None, device=None, chain=None):
     """aggregation.py:293-435.  device: fit_candidates' option (the other stages carry theirs in their keywords); True
-    also keeps the level on the generic path."""
+    also keeps the level on the generic path.  chain: the resident chain of the calling smoothed_aggregation_solver
+    (_Chain); with it, a level that _chain_options takes is built, transposed and multiplied in HBM."""
     A = levels[-1].A
     B = levels[-1].B
 
@@ -1261,13 +1468,37 @@ def extend_hierarchy(levels, strength, aggregate, smooth, improve_candidates, ke
         levels[-1].B = B
         lap("candidate improvement")
 
+    # what the chain hands on where it stopped a level after its draws: C, the weights of the set, the Jacobi weights
+    handed = None
+    options = _chain_options(A, B, strength[li], aggregate[li], smooth[li], device) if chain is not None and _RESIDENT_CHAIN else None
+    if options is not None:
+        try:
+            handed = _chain_level(levels, chain, options, keep, fn is not None)
+            if handed is None:
+                return
+        except NotImplementedError:
+            # a refusal from before the level's draws (_chain_level turns a later one into an error): the stage routes
+            # answer, as they did
+            chain.close()
+        except BaseException:
+            chain.close()
+            raise
+    elif chain is not None:
+        # a level that is built elsewhere ends the chain: its resident operator is A_l, and the next level that the
+        # chain takes has to begin another one from the A_{l+1} this level leaves on the host
+        chain.close()
+    if chain is not None and handed is None:
+        _record_level()
+
     if not keep and not device and _scalar_fast_path_ok(A, B, strength[li], aggregate[li], smooth[li]):
         return _extend_scalar(levels, smooth[li], keep, rho_fn or _rho_D_inv_A_host)
     if not keep and not device and _block_fast_path_ok(A, B, strength[li], aggregate[li], smooth[li]):
         return _extend_block(levels, smooth[li], keep, rho_fn or _rho_D_inv_A_host)
 
     fn, kwargs = unpack_arg(strength[len(levels) - 1])
-    if fn == "symmetric":
+    if handed is not None:
+        Cm = handed["C"]
+    elif fn == "symmetric":
         Cm = symmetric_strength_of_connection(A, **kwargs)
     elif fn in ("ode", "evolution"):
         from .strength import evolution_strength_of_connection
@@ -1285,6 +1516,8 @@ def extend_hierarchy(levels, strength, aggregate, smooth, improve_candidates, ke
     fn, kwargs = unpack_arg(aggregate[len(levels) - 1])
     if fn == "standard":
         AggOp = standard_aggregation(Cm, **kwargs)[0]
+    elif fn == "mis" and handed is not None:
+        AggOp = mis_aggregation(Cm, y=handed["y"], **kwargs)[0]
     elif fn == "mis":
         AggOp = mis_aggregation(Cm, **kwargs)[0]        # draws the level's rand(n) here, before the spectral radius does
     elif fn == "predefined":
@@ -1298,7 +1531,7 @@ def extend_hierarchy(levels, strength, aggregate, smooth, improve_candidates, ke
 
     fn, kwargs = unpack_arg(smooth[len(levels) - 1])
     if fn == "jacobi":
-        P = jacobi_prolongation_smoother(A, T, Cm, B, **kwargs)
+        P = jacobi_prolongation_smoother(A, T, Cm, B, weights=None if handed is None else handed["weights"], **kwargs)
     elif fn == "energy":
         P = energy_prolongation_smoother(A, T, Cm, B, None, (False, {}), **kwargs)
     elif fn is None:

@@ -622,24 +622,7 @@ int extended_interpolation_device(int n, const HbmCsr &A, const int *Sp, const i
     return 0;
 }
 
-// One bit per fact about a CSR operator in HBM, by one lane per row: ROWS_UNSORTED where a row is not strictly
-// ascending, VALUE_NOT_FINITE where a value is an infinity or a NaN.  Integer atomics: the result does not depend on order.
-constexpr int ROWS_UNSORTED = 1, VALUE_NOT_FINITE = 2;
-
-__global__ __launch_bounds__(TB) void operator_facts_kernel(int n, const int *Ap, const int *Aj, const double *Ax, int *facts)
-{
-    const int i = blockIdx.x * TB + threadIdx.x;
-    int found = 0;
-    if (i < n) {
-        const long lo = Ap[i], hi = Ap[i + 1];
-        for (long jj = lo; jj < hi; ++jj) {
-            if (jj > lo && Aj[jj] <= Aj[jj - 1]) found |= ROWS_UNSORTED;
-            if (!isfinite(Ax[jj])) found |= VALUE_NOT_FINITE;
-        }
-    }
-    if (found) atomicOr(facts, found);
-}
-
+// (operator_facts_kernel, the pass over a product for its row order and its finiteness, is graph_dev.hpp's)
 __global__ __launch_bounds__(TB) void count_ones_kernel(int n, const int *splitting, int *total)
 {
     const int i = blockIdx.x * TB + threadIdx.x;

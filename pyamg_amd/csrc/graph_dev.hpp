@@ -25,6 +25,10 @@ __attribute__((visibility("hidden"))) int fill_int_device(const char *what, long
 // transpose.hip: R = P^T in HBM; how: what it did, as the calling thread's amg_transpose_last_route then reports it
 __attribute__((visibility("hidden"))) int transpose_device(int n_row, int n_col, long nnz, const int *Pp, const int *Pj, const double *Px,
                                                            DBuf &Rp, DBuf &Rj, DBuf &Rx, TransposeRoute &how);
+// misagg.hip: MIS(2) aggregation of a graph that is already in HBM (p, j: n + 1 offsets and columns; y: n weights) into
+// freshly allocated agg (n ints, -1: no aggregate) and cpts (the roots, *n_agg of them, ascending); *rounds: rounds of the set
+__attribute__((visibility("hidden"))) int mis_aggregation_resident(int n, const int *p, const int *j, const double *y, DBuf &agg,
+                                                                   DBuf &cpts, int *n_agg, int *rounds);
 
 namespace {
 
@@ -142,6 +146,24 @@ template <class T> int offsets_from_counts(const char *who, int n, const T *coun
     CHK(last_offset(offsets.as<T>(), n, total));
     if (upper >= 0 && (*total < 0 || *total > upper)) { set_error(std::string(who) + ": the scan left its bound"); return AMG_ESTATE; }
     return 0;
+}
+
+// One bit per fact about a CSR operator in HBM, by one lane per row: ROWS_UNSORTED where a row is not strictly
+// ascending, VALUE_NOT_FINITE where a value is an infinity or a NaN.  Integer atomics: the result does not depend on order.
+constexpr int ROWS_UNSORTED = 1, VALUE_NOT_FINITE = 2;
+
+[[maybe_unused]] __global__ __launch_bounds__(TB) void operator_facts_kernel(int n, const int *Ap, const int *Aj, const double *Ax, int *facts)
+{
+    const int i = blockIdx.x * TB + threadIdx.x;
+    int found = 0;
+    if (i < n) {
+        const long lo = Ap[i], hi = Ap[i + 1];
+        for (long jj = lo; jj < hi; ++jj) {
+            if (jj > lo && Aj[jj] <= Aj[jj - 1]) found |= ROWS_UNSORTED;
+            if (!isfinite(Ax[jj])) found |= VALUE_NOT_FINITE;
+        }
+    }
+    if (found) atomicOr(facts, found);
 }
 
 }  // namespace

@@ -183,8 +183,11 @@ __global__ __launch_bounds__(TB) void agg_round2_kernel(int n, const int *Ap, co
     agg2[i] = a;
 }
 
+}   // namespace
+
 // The aggregation of a graph that is already in HBM (p, j: its n + 1 offsets and columns; y: the n weights) into freshly
 // allocated agg (n ints, -1: no aggregate) and cpts (the roots, *n_agg of them, ascending).  *rounds: rounds of the set.
+// Crosses units (graph_dev.hpp): the smoothed-aggregation chain of prolong.hip calls it.
 int mis_aggregation_resident(int n, const int *p, const int *j, const double *y, DBuf &agg, DBuf &cpts, int *n_agg, int *rounds)
 {
     const size_t vbytes = sizeof(int) * (size_t)n;
@@ -207,7 +210,6 @@ int mis_aggregation_resident(int n, const int *p, const int *j, const double *y,
     return 0;
 }
 
-}   // namespace
 }   // namespace amg
 
 extern "C" {

@@ -19,11 +19,44 @@ struct __attribute__((visibility("hidden"))) amg_prolong {
     amg::DBuf j, x;
 };
 
+// A chain of smoothed-aggregation levels.  It owns the resident operator A (n x n, nnz entries,
+// in the order its product left it; `sorted` where that order is ascending in every row) with the candidate B and,
+// between amg_sa_chain_level and amg_sa_chain_fetch, the level built from them: S, the aggregates, T, the sorted copy
+// of A, P, R, the coarse operator C and the coarse candidate Bc.  The fetch moves C and Bc into A and B and drops the rest.
+enum { SA_IDLE = 0, SA_BUILT = 1, SA_REFUSED = 2, SA_STOPPED = 3 };
+struct __attribute__((visibility("hidden"))) amg_sa_chain {
+    int n = 0, sorted = 0, state = SA_IDLE;
+    long nnz = 0;
+    amg::HbmCsr A;
+    amg::DBuf B;
+    double upload_ms = 0.0;         // of A_0 and B_0: reported with the first level
+    int n_coarse = 0, c_facts = 0;
+    long s_nnz = 0, t_nnz = 0, p_nnz = 0, c_nnz = 0;
+    amg::HbmCsr S, T, Asorted, P;
+    amg::DBuf agg, Bc, Rp, Rj, Rx, Cp, Cj, Cx;
+    double times_ms[AMG_SA_CHAIN_STAGES] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    void drop_level()
+    {
+        S = amg::HbmCsr{}; T = amg::HbmCsr{}; Asorted = amg::HbmCsr{}; P = amg::HbmCsr{};
+        agg.reset(); Bc.reset(); Rp.reset(); Rj.reset(); Rx.reset(); Cp.reset(); Cj.reset(); Cx.reset();
+        state = SA_IDLE;
+    }
+};
+// the deleter of "drop the level on the way out": std::unique_ptr<amg_sa_chain, SaLevelDrop>
+struct SaLevelDrop {
+    void operator()(amg_sa_chain *c) const { c->drop_level(); }
+};
+
 namespace amg {
 namespace {
 
 // ------------------------------------------------------------------------------------------------ symmetric strength
+// The three kernels take the operator's values as they are stored (SQ = false) or squared, a * a in one rounding
+// (SQ = true): what the host hands on for a BSR operator with 1 x 1 blocks, the "norms" of its blocks.
+template <bool SQ> __device__ __forceinline__ double sym_value(double a) { return SQ ? a * a : a; }
+
 // diags[i] = |sum of the stored diagonal entries of row i, in stored order from zero|
+template <bool SQ>
 __global__ __launch_bounds__(TB) void sym_diagonal_kernel(int n, const int *Ap, const int *Aj, const double *Ax, double *diags)
 {
     const int i = blockIdx.x * TB + threadIdx.x;
@@ -31,7 +64,7 @@ __global__ __launch_bounds__(TB) void sym_diagonal_kernel(int n, const int *Ap, 
     double d = 0.0;
     const long hi = Ap[i + 1];
     for (long jj = Ap[i]; jj < hi; ++jj)
-        if (Aj[jj] == i) d = d + Ax[jj];
+        if (Aj[jj] == i) d = d + sym_value<SQ>(Ax[jj]);
     diags[i] = fabs(d);
 }
 
@@ -41,6 +74,7 @@ __device__ __forceinline__ bool sym_keeps(int i, int j, double a, double eps, co
 }
 
 // count pass: the entries row i keeps; lane n writes the scan's last addend
+template <bool SQ>
 __global__ __launch_bounds__(TB) void sym_count_kernel(int n, double theta2, const int *Ap, const int *Aj, const double *Ax,
                                                        const double *diags, int *count)
 {
@@ -51,12 +85,13 @@ __global__ __launch_bounds__(TB) void sym_count_kernel(int n, double theta2, con
     int kept = 0;
     const long hi = Ap[i + 1];
     for (long jj = Ap[i]; jj < hi; ++jj)
-        if (sym_keeps(i, Aj[jj], Ax[jj], eps, diags)) ++kept;
+        if (sym_keeps(i, Aj[jj], sym_value<SQ>(Ax[jj]), eps, diags)) ++kept;
     count[i] = kept;
 }
 
 // fill pass: the magnitudes of the kept entries from Sp[i] on, in stored order, then the row divided by its largest one
 // (by 1 where that is 0)
+template <bool SQ>
 __global__ __launch_bounds__(TB) void sym_fill_kernel(int n, double theta2, const int *Ap, const int *Aj, const double *Ax,
                                                       const double *diags, const int *Sp, int *Sj, double *Sx)
 {
@@ -68,7 +103,7 @@ __global__ __launch_bounds__(TB) void sym_fill_kernel(int n, double theta2, cons
     double m = 0.0;
     for (long jj = Ap[i]; jj < hi; ++jj) {
         const int j = Aj[jj];
-        const double a = Ax[jj];
+        const double a = sym_value<SQ>(Ax[jj]);
         if (!sym_keeps(i, j, a, eps, diags)) continue;
         const double v = fabs(a);
         if (m < v) m = v;
@@ -80,8 +115,15 @@ __global__ __launch_bounds__(TB) void sym_fill_kernel(int n, double theta2, cons
     for (long e = lo; e < at; ++e) Sx[e] = Sx[e] / m;
 }
 
+// out[e] = 1.0 for e < count
+__global__ __launch_bounds__(TB) void fill_ones_kernel(long count, double *out)
+{
+    const long e = (long)blockIdx.x * TB + threadIdx.x;
+    if (e < count) out[e] = 1.0;
+}
+
 // symmetric strength of A (device, with values) into freshly allocated S: S.p n + 1 offsets; *nnz: entries kept
-int symmetric_strength_resident(int n, double theta, const HbmCsr &A, long a_nnz, HbmCsr &S, long *nnz)
+template <bool SQ> int symmetric_strength_kernels(int n, double theta, const HbmCsr &A, long a_nnz, HbmCsr &S, long *nnz)
 {
     const double theta2 = theta * theta;
     const int *p = A.p.i(), *j = A.j.i();
@@ -89,17 +131,38 @@ int symmetric_strength_resident(int n, double theta, const HbmCsr &A, long a_nnz
     DBuf diags, count;
     CHK(diags.alloc(sizeof(double) * (size_t)n));
     CHK(count.alloc(sizeof(int) * ((size_t)n + 1)));
-    hipLaunchKernelGGL(sym_diagonal_kernel, grid_for(n), dim3(TB), 0, nullptr, n, p, j, x, diags.d());
+    hipLaunchKernelGGL(sym_diagonal_kernel<SQ>, grid_for(n), dim3(TB), 0, nullptr, n, p, j, x, diags.d());
     LAUNCH_CHECK("symmetric strength: diagonal launch");
-    hipLaunchKernelGGL(sym_count_kernel, grid_for((long)n + 1), dim3(TB), 0, nullptr, n, theta2, p, j, x, (const double *)diags.d(), count.i());
+    hipLaunchKernelGGL(sym_count_kernel<SQ>, grid_for((long)n + 1), dim3(TB), 0, nullptr, n, theta2, p, j, x, (const double *)diags.d(),
+                       count.i());
     LAUNCH_CHECK("symmetric strength: count launch");
     CHK(offsets_from_counts("symmetric strength", n, count.i(), a_nnz, S.p, nnz));
     CHK(S.j.alloc(sizeof(int) * (size_t)*nnz));
     CHK(S.x.alloc(sizeof(double) * (size_t)*nnz));
-    hipLaunchKernelGGL(sym_fill_kernel, grid_for(n), dim3(TB), 0, nullptr, n, theta2, p, j, x, (const double *)diags.d(), (const int *)S.p.i(),
-                       S.j.i(), S.x.d());
+    hipLaunchKernelGGL(sym_fill_kernel<SQ>, grid_for(n), dim3(TB), 0, nullptr, n, theta2, p, j, x, (const double *)diags.d(),
+                       (const int *)S.p.i(), S.j.i(), S.x.d());
     LAUNCH_CHECK("symmetric strength: fill launch");
     AMG_HIP(hipDeviceSynchronize());
+    return 0;
+}
+
+// mode AMG_SA_STRENGTH_CSR: the values as stored; _SQUARED: their squares; _ONES: the pattern of A, in stored order,
+// with every value 1.0 (what the host returns for a BSR operator with theta == 0, stored zeros included)
+int symmetric_strength_resident(int n, double theta, const HbmCsr &A, long a_nnz, HbmCsr &S, long *nnz, int mode = AMG_SA_STRENGTH_CSR)
+{
+    if (mode == AMG_SA_STRENGTH_CSR) return symmetric_strength_kernels<false>(n, theta, A, a_nnz, S, nnz);
+    if (mode == AMG_SA_STRENGTH_SQUARED) return symmetric_strength_kernels<true>(n, theta, A, a_nnz, S, nnz);
+    CHK(S.p.alloc(sizeof(int) * ((size_t)n + 1)));
+    CHK(S.j.alloc(sizeof(int) * (size_t)a_nnz));
+    CHK(S.x.alloc(sizeof(double) * (size_t)a_nnz));
+    AMG_HIP(hipMemcpy(S.p.p, A.p.p, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToDevice));
+    if (a_nnz > 0) {                        // (without entries S.j and S.x are the empty buffers just allocated)
+        AMG_HIP(hipMemcpy(S.j.p, A.j.p, sizeof(int) * (size_t)a_nnz, hipMemcpyDeviceToDevice));
+        hipLaunchKernelGGL(fill_ones_kernel, grid_for(a_nnz), dim3(TB), 0, nullptr, a_nnz, S.x.d());
+        LAUNCH_CHECK("symmetric strength: ones launch");
+    }
+    AMG_HIP(hipDeviceSynchronize());
+    *nnz = a_nnz;
     return 0;
 }
 
@@ -324,6 +387,113 @@ int jacobi_smoothing_resident(int n, int n_coarse, const HbmCsr &S, long s_nnz, 
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------ the chained level
+// *symmetric = 0 where a stored (i, j) has no stored (j, i): one lane per row, each entry walks row j
+__global__ __launch_bounds__(TB) void pattern_symmetric_kernel(int n, const int *Sp, const int *Sj, int *symmetric)
+{
+    const int i = blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    const long hi = Sp[i + 1];
+    for (long jj = Sp[i]; jj < hi; ++jj) {
+        const int j = Sj[jj];
+        if (j == i) continue;
+        bool back = false;
+        const long jhi = Sp[j + 1];
+        for (long e = Sp[j]; e < jhi && !back; ++e) back = Sj[e] == i;
+        if (!back) { *symmetric = 0; return; }
+    }
+}
+
+// AggOp from the aggregate of every vertex: a row holds its aggregate, or nothing where agg[i] is -1.  FILL = false
+// counts (lane n writes the scan's last addend), FILL = true writes the column at Tp[i].
+template <bool FILL>
+__global__ __launch_bounds__(TB) void aggop_kernel(int n, const int *agg, const int *Tp, int *Tj, int *count)
+{
+    const int i = blockIdx.x * TB + threadIdx.x;
+    if (!FILL && i == n) { count[n] = 0; return; }
+    if (i >= n) return;
+    const int a = agg[i];
+    if (!FILL) count[i] = a >= 0 ? 1 : 0;
+    else if (a >= 0) Tj[Tp[i]] = a;
+}
+
+// The rows of a CSR operator sorted by column, out of place: an entry goes to the position its rank gives it, the number
+// of columns of its row below its own.  No column is stored twice, so the ranks of a row are 0 .. length - 1, each once,
+// and the result is the one sorted row there is.  A row of at most SORT_LANE_MAX entries is ranked by one lane, a longer
+// one by one wave whose lanes take its entries side by side.
+constexpr int SORT_LANE_MAX = 32;
+
+__device__ __forceinline__ void sort_place(const int *Aj, const double *Ax, long lo, long hi, long e, int *Oj, double *Ox)
+{
+    const int j = Aj[e];
+    long rank = 0;
+    for (long k = lo; k < hi; ++k) rank += Aj[k] < j ? 1 : 0;
+    Oj[lo + rank] = j;
+    Ox[lo + rank] = Ax[e];
+}
+
+__global__ __launch_bounds__(TB) void sort_rows_lane_kernel(int n, const int *Ap, const int *Aj, const double *Ax, int *Oj, double *Ox,
+                                                            int *long_rows)
+{
+    const int i = blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    const long lo = Ap[i], hi = Ap[i + 1];
+    if (hi - lo > SORT_LANE_MAX) { *long_rows = 1; return; }       // left to the wave kernel, which then has to run
+    for (long e = lo; e < hi; ++e) sort_place(Aj, Ax, lo, hi, e, Oj, Ox);
+}
+
+__global__ __launch_bounds__(TB) void sort_rows_wave_kernel(int n, const int *Ap, const int *Aj, const double *Ax, int *Oj, double *Ox)
+{
+    const long i = (long)blockIdx.x * (TB / WAVE) + threadIdx.x / WAVE;
+    if (i >= n) return;
+    const long lo = Ap[i], hi = Ap[i + 1];
+    if (hi - lo <= SORT_LANE_MAX) return;
+    for (long e = lo + threadIdx.x % WAVE; e < hi; e += WAVE) sort_place(Aj, Ax, lo, hi, e, Oj, Ox);
+}
+
+// A (n rows, nnz entries, no column twice in a row) with its rows sorted by column into freshly allocated O
+int sort_rows_device(int n, long nnz, const HbmCsr &A, HbmCsr &O)
+{
+    CHK(O.p.alloc(sizeof(int) * ((size_t)n + 1)));
+    CHK(O.j.alloc(sizeof(int) * (size_t)nnz));
+    CHK(O.x.alloc(sizeof(double) * (size_t)nnz));
+    AMG_HIP(hipMemcpy(O.p.p, A.p.p, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToDevice));
+    int long_rows = 0;
+    DBuf flag;
+    CHK(flag.zero(sizeof(int)));
+    hipLaunchKernelGGL(sort_rows_lane_kernel, grid_for(n), dim3(TB), 0, nullptr, n, (const int *)A.p.i(), (const int *)A.j.i(),
+                       (const double *)A.x.d(), O.j.i(), O.x.d(), flag.i());
+    LAUNCH_CHECK("row sort: lane launch");
+    CHK(flag.to_host(&long_rows, sizeof(int)));
+    if (long_rows) {                        // (the lane kernel left at least one row: a wave per row over all of them)
+        hipLaunchKernelGGL(sort_rows_wave_kernel, grid_for((long)n * WAVE), dim3(TB), 0, nullptr, n, (const int *)A.p.i(),
+                           (const int *)A.j.i(), (const double *)A.x.d(), O.j.i(), O.x.d());
+        LAUNCH_CHECK("row sort: wave launch");
+    }
+    AMG_HIP(hipDeviceSynchronize());
+    return 0;
+}
+
+// a copy of `bytes` bytes of src in a freshly allocated dst
+int copy_device(const DBuf &src, size_t bytes, DBuf &dst)
+{
+    CHK(dst.alloc(bytes));
+    if (bytes) AMG_HIP(hipMemcpy(dst.p, src.p, bytes, hipMemcpyDeviceToDevice));
+    return 0;
+}
+
+// the facts (graph_dev.hpp) of an operator in HBM
+int operator_facts_device(const char *what, int n, const HbmCsr &A, int *facts)
+{
+    DBuf found;
+    CHK(found.zero(sizeof(int)));
+    hipLaunchKernelGGL(operator_facts_kernel, grid_for(n), dim3(TB), 0, nullptr, n, (const int *)A.p.i(), (const int *)A.j.i(),
+                       (const double *)A.x.d(), found.i());
+    LAUNCH_CHECK(what);
+    AMG_HIP(hipMemcpy(facts, found.p, sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int fetch_prolong(const char *who, amg_prolong *h, int *j, double *x, double *times_ms)
 {
     if (!h) return AMG_EINVAL;
@@ -454,5 +624,254 @@ int amg_jacobi_prolongation_fetch(amg_prolong *h, int *Pj, double *Px, double *t
 {
     return amg::fetch_prolong("jacobi smoothing fetch", h, Pj, Px, times_ms);
 }
+
+// ---- the chain: A_l, S_l, the aggregates, T_l, P_l, R_l, R_l A_l, A_{l+1} and B_{l+1} stay in HBM from the upload of A_0 on
+
+int amg_sa_chain_begin(int n, const int *Ap, const int *Aj, const double *Ax, const double *B, amg_sa_chain **out)
+{
+    using namespace amg;
+    const char *who = "sa chain";
+    if (!out) return bad(who, "bad arguments");
+    *out = nullptr;
+    if (n <= 0) return bad(who, "an empty operator");
+    if (!B) return bad(who, "null array");
+    CHK(check_csr_arrays(who, n, n, Ap, n + 1, Aj, 0x7fffffff, Ax, 0x7fffffff));
+    CHK(check_unique_columns(who, n, n, Ap, Aj));       // the row sort and the right-hand operand of R * A both need it
+    CHK(require_device());
+    LapClock timer;
+    std::unique_ptr<amg_sa_chain> c(new amg_sa_chain);
+    CHK(c->A.upload(n, Ap, Aj, Ax, true));
+    CHK(c->B.from_host(B, sizeof(double) * (size_t)n));
+    int facts = 0;
+    CHK(operator_facts_device("sa chain: operator facts launch", n, c->A, &facts));
+    if (facts & VALUE_NOT_FINITE) { set_error("sa chain: the operator holds a value that is not finite"); return AMG_ENOTIMPL; }
+    c->n = n;
+    c->nnz = Ap[n];
+    c->sorted = (facts & ROWS_UNSORTED) ? 0 : 1;
+    c->upload_ms = timer.lap();
+    *out = c.release();
+    return 0;
+}
+
+int amg_sa_chain_level(amg_sa_chain *c, int n_rows, double theta, int strength_mode, const double *y, const double *dinv, double w, int degree,
+                       const double *B, double tol, long *sizes, int *flags, int *rounds, double *times_ms)
+{
+    using namespace amg;
+    const char *who = "sa chain";
+    if (!c || !sizes || !flags || !y || !dinv) return bad(who, "bad arguments");
+    if (c->n <= 0) return bad(who, "no resident operator");
+    if (n_rows != c->n) return bad(who, "the caller's size is not the resident operator's");       // y, dinv and B are read by it
+    if (!(theta >= 0.0)) return bad(who, "expected a theta that is not negative");
+    if (strength_mode < AMG_SA_STRENGTH_CSR || strength_mode > AMG_SA_STRENGTH_ONES || degree < 0) return bad(who, "bad options");
+    if (c->state != SA_IDLE) { set_error("sa chain: the level built last has not been fetched"); return AMG_ESTATE; }
+    // The resident operator is not checked again.  A_0 passed begin's checks; a later one is a product of spgemm.hip,
+    // which stores one entry per column, and its row order and finiteness came with the product's facts.
+    const int n = c->n;
+    std::fill(sizes, sizes + 5, 0L);
+    std::fill(flags, flags + AMG_SA_CHAIN_FLAG_FIELDS, 0);
+    if (rounds) *rounds = 0;
+    LapClock timer;
+    DBuf dy, ddinv, newB;
+    CHK(dy.from_host(y, sizeof(double) * (size_t)n));
+    CHK(ddinv.from_host(dinv, sizeof(double) * (size_t)n));
+    if (B) CHK(newB.from_host(B, sizeof(double) * (size_t)n));
+    AMG_HIP(hipDeviceSynchronize());
+    // an early return leaves the chain without a level, its resident operator and candidate as they were
+    std::unique_ptr<amg_sa_chain, SaLevelDrop> drop(c);
+    const double *dB = B ? newB.d() : c->B.d();
+    std::fill(c->times_ms, c->times_ms + AMG_SA_CHAIN_STAGES, 0.0);
+    c->times_ms[0] = c->upload_ms + timer.lap();
+    c->s_nnz = c->t_nnz = c->p_nnz = c->c_nnz = 0;
+    c->n_coarse = 0;
+    c->c_facts = 0;
+
+    // 1. strength, on the operator in the order its product left it
+    CHK(symmetric_strength_resident(n, theta, c->A, c->nnz, c->S, &c->s_nnz, strength_mode));
+    c->times_ms[1] = timer.lap();
+
+    // 2. - 4. the pattern of S is symmetric; MIS(2) aggregation; AggOp
+    int symmetric = 1, done = 0;
+    {
+        DBuf flag;
+        CHK(flag.from_host(&symmetric, sizeof(int)));
+        hipLaunchKernelGGL(pattern_symmetric_kernel, grid_for(n), dim3(TB), 0, nullptr, n, (const int *)c->S.p.i(), (const int *)c->S.j.i(),
+                           flag.i());
+        LAUNCH_CHECK("sa chain: symmetry launch");
+        CHK(flag.to_host(&symmetric, sizeof(int)));
+    }
+    flags[2] = symmetric;
+    if (!symmetric) return bad(who, "expected a structurally symmetric pattern");
+    DBuf cpts;
+    CHK(mis_aggregation_resident(n, c->S.p.i(), c->S.j.i(), dy.d(), c->agg, cpts, &c->n_coarse, &done));
+    if (rounds) *rounds = done;
+    sizes[0] = c->s_nnz;
+    auto stopped = [&](int why) {
+        flags[3] = why;
+        if (B) c->B = std::move(newB);
+        c->upload_ms = 0.0;
+        if (times_ms) std::copy(c->times_ms, c->times_ms + AMG_SA_CHAIN_STAGES - 1, times_ms);
+        c->state = SA_STOPPED;
+        drop.release();
+        return 0;
+    };
+    if (c->n_coarse == 0) { c->times_ms[2] = timer.lap(); return stopped(AMG_SA_NO_AGGREGATE); }
+    {
+        DBuf count;
+        CHK(count.alloc(sizeof(int) * ((size_t)n + 1)));
+        hipLaunchKernelGGL(aggop_kernel<false>, grid_for((long)n + 1), dim3(TB), 0, nullptr, n, (const int *)c->agg.i(), (const int *)nullptr,
+                           (int *)nullptr, count.i());
+        LAUNCH_CHECK("sa chain: AggOp count launch");
+        CHK(offsets_from_counts(who, n, count.i(), n, c->T.p, &c->t_nnz));
+        CHK(c->T.j.alloc(sizeof(int) * (size_t)c->t_nnz));
+        hipLaunchKernelGGL(aggop_kernel<true>, grid_for(n), dim3(TB), 0, nullptr, n, (const int *)c->agg.i(), (const int *)c->T.p.i(),
+                           c->T.j.i(), (int *)nullptr);
+        LAUNCH_CHECK("sa chain: AggOp fill launch");
+    }
+    c->times_ms[2] = timer.lap();
+
+    // 5. the tentative prolongator and the coarse candidate
+    CHK(fit_candidates_resident(n, c->n_coarse, 1, 1, c->T.p.i(), c->T.j.i(), c->t_nnz, dB, tol, c->T.x, c->Bc));
+    c->times_ms[3] = timer.lap();
+
+    // 6. everything after the strength sees sorted rows (the host sorts its copy where it takes the diagonal)
+    if (!c->sorted) CHK(sort_rows_device(n, c->nnz, c->A, c->Asorted));
+    const HbmCsr &As = c->sorted ? c->A : c->Asorted;
+    if (!c->sorted) c->times_ms[4] = timer.lap();        // (exactly 0 where the facts said the rows are sorted)
+
+    // 7. P = T, then the Jacobi steps
+    const size_t tbytes = sizeof(int) * (size_t)c->t_nnz;
+    CHK(copy_device(c->T.p, sizeof(int) * ((size_t)n + 1), c->P.p));
+    CHK(copy_device(c->T.j, tbytes, c->P.j));
+    CHK(copy_device(c->T.x, sizeof(double) * (size_t)c->t_nnz, c->P.x));
+    c->p_nnz = c->t_nnz;
+    sizes[1] = c->t_nnz;
+    sizes[4] = c->n_coarse;
+    {
+        const int rc = jacobi_smoothing_resident(n, c->n_coarse, As, c->nnz, ddinv.d(), w, degree, c->P, &c->p_nnz);
+        c->times_ms[5] = timer.lap();
+        if (rc == AMG_ENOTIMPL) return stopped(AMG_SA_SMOOTHING_REFUSED);
+        CHK(rc);
+    }
+
+    // 8. R = P^T
+    TransposeRoute how;
+    CHK(transpose_device(n, c->n_coarse, c->p_nnz, c->P.p.i(), c->P.j.i(), c->P.x.d(), c->Rp, c->Rj, c->Rx, how));
+    c->times_ms[6] = timer.lap();
+
+    // 9. A_c = (R * A) * P by the routes of spgemm.hip; R * A goes when the second product has run
+    int tables[2] = {0, 0};
+    int rc = 0;
+    {
+        DevArr<long> Ap64, Rp64, Pp64, RAp, Cp64;
+        DevArr<int> RAj, Cj;
+        DevArr<double> RAx, Cx;
+        long ra_nnz = 0;
+        int route[AMG_SPGEMM_ROUTE_FIELDS];
+        CHK(widen_rowptr_device(n, As.p.i(), Ap64));
+        CHK(widen_rowptr_device(c->n_coarse, c->Rp.i(), Rp64));
+        CHK(widen_rowptr_device(n, c->P.p.i(), Pp64));
+        rc = spgemm_device(c->n_coarse, n, n, c->p_nnz, Rp64, c->Rj.i(), c->Rx.d(), c->nnz, Ap64, As.j.i(), As.x.d(), &ra_nnz, RAp, RAj, RAx);
+        amg_spgemm_last_route(route, AMG_SPGEMM_ROUTE_FIELDS);
+        tables[0] = route[3];
+        if (rc == 0) {
+            rc = spgemm_device(c->n_coarse, n, c->n_coarse, ra_nnz, RAp, RAj, RAx, c->p_nnz, Pp64, c->P.j.i(), c->P.x.d(), &c->c_nnz, Cp64, Cj,
+                               Cx);
+            amg_spgemm_last_route(route, AMG_SPGEMM_ROUTE_FIELDS);
+            tables[1] = route[3];
+        }
+        if (rc != 0 && rc != AMG_EINVAL) return rc;
+        if (rc == 0) {
+            CHK(c->Cp.alloc(sizeof(int) * ((size_t)c->n_coarse + 1)));
+            CHK(narrow_rowptr_device(c->n_coarse, c->c_nnz, Cp64, c->Cp.i()));
+            static_cast<DevArr<void> &>(c->Cj) = DevArr<void>(std::move(Cj));
+            static_cast<DevArr<void> &>(c->Cx) = DevArr<void>(std::move(Cx));
+        }
+    }
+    // 10. the row order and the finiteness of A_c in one pass over it, where it lies
+    if (rc == 0) {
+        DBuf facts;
+        CHK(facts.zero(sizeof(int)));
+        hipLaunchKernelGGL(operator_facts_kernel, grid_for(c->n_coarse), dim3(TB), 0, nullptr, c->n_coarse, (const int *)c->Cp.i(),
+                           (const int *)c->Cj.i(), (const double *)c->Cx.d(), facts.i());
+        LAUNCH_CHECK("sa chain: operator facts launch");
+        AMG_HIP(hipMemcpy(&c->c_facts, facts.p, sizeof(int), hipMemcpyDeviceToHost));
+    } else {
+        c->c_nnz = 0;
+    }
+    c->times_ms[7] = timer.lap();
+
+    sizes[2] = c->p_nnz;
+    sizes[3] = c->c_nnz;
+    flags[0] = rc == 0 && !(c->c_facts & ROWS_UNSORTED);
+    flags[1] = rc == 0 && !(c->c_facts & VALUE_NOT_FINITE);
+    flags[4] = tables[0];
+    flags[5] = tables[1];
+    flags[6] = how.launched; flags[7] = how.lane_rows; flags[8] = how.lds_rows; flags[9] = how.hbm_rows;
+    if (B) c->B = std::move(newB);
+    c->upload_ms = 0.0;
+    if (times_ms) std::copy(c->times_ms, c->times_ms + AMG_SA_CHAIN_STAGES - 1, times_ms);
+    c->state = rc == 0 ? SA_BUILT : SA_REFUSED;
+    drop.release();
+    return rc == 0 ? 0 : AMG_CHAIN_PRODUCT_REFUSED;
+}
+
+int amg_sa_chain_fetch(amg_sa_chain *c, int *Pp, int *Pj, double *Px, int *Rp, int *Rj, double *Rx, int *Cp, int *Cj, double *Cx,
+                       double *Bc, int *Sp, int *Sj, double *Sx, int *agg, double *Tx, double *times_ms)
+{
+    using namespace amg;
+    const char *who = "sa chain fetch";
+    if (!c) return AMG_EINVAL;
+    if (c->state == SA_IDLE) { set_error("sa chain fetch: no level has been built"); return AMG_ESTATE; }
+    // the level's buffers go whatever happens below; A_c becomes the resident operator only after a complete fetch
+    std::unique_ptr<amg_sa_chain, SaLevelDrop> drop(c);
+    const int n = c->n;
+    // whole: the level is built and its caller takes R and A_c; a caller that finishes a built level on the host (Rp or Cp
+    // NULL) is treated like a refused product, and the chain ends
+    const bool whole = c->state == SA_BUILT && Rp && Cp, stopped = c->state == SA_STOPPED;
+    if (stopped && !Sp) return bad(who, "null array");
+    if (!stopped && (!Pp || !Bc || (c->p_nnz > 0 && (!Pj || !Px)))) return bad(who, "null array");
+    if (whole && ((c->p_nnz > 0 && (!Rj || !Rx)) || (c->c_nnz > 0 && (!Cj || !Cx)))) return bad(who, "null array");
+    if (Sp && c->s_nnz > 0 && (!Sj || !Sx)) return bad(who, "null array");
+    LapClock timer;
+    if (Sp) {
+        CHK(c->S.p.to_host(Sp, sizeof(int) * ((size_t)n + 1)));
+        CHK(c->S.j.to_host(Sj, sizeof(int) * (size_t)c->s_nnz));
+        CHK(c->S.x.to_host(Sx, sizeof(double) * (size_t)c->s_nnz));
+    }
+    if (!stopped) {
+        if (agg) CHK(c->agg.to_host(agg, sizeof(int) * (size_t)n));
+        if (Tx) CHK(c->T.x.to_host(Tx, sizeof(double) * (size_t)c->t_nnz));
+        CHK(c->P.p.to_host(Pp, sizeof(int) * ((size_t)n + 1)));
+        CHK(c->P.j.to_host(Pj, sizeof(int) * (size_t)c->p_nnz));
+        CHK(c->P.x.to_host(Px, sizeof(double) * (size_t)c->p_nnz));
+        CHK(c->Bc.to_host(Bc, sizeof(double) * (size_t)c->n_coarse));
+    }
+    if (whole) {
+        const size_t cbytes = sizeof(int) * ((size_t)c->n_coarse + 1);
+        CHK(c->Rp.to_host(Rp, cbytes));
+        CHK(c->Rj.to_host(Rj, sizeof(int) * (size_t)c->p_nnz));
+        CHK(c->Rx.to_host(Rx, sizeof(double) * (size_t)c->p_nnz));
+        CHK(c->Cp.to_host(Cp, cbytes));
+        CHK(c->Cj.to_host(Cj, sizeof(int) * (size_t)c->c_nnz));
+        CHK(c->Cx.to_host(Cx, sizeof(double) * (size_t)c->c_nnz));
+        c->A.p = std::move(c->Cp); c->A.j = std::move(c->Cj); c->A.x = std::move(c->Cx);
+        c->B = std::move(c->Bc);
+        c->n = c->n_coarse;
+        c->nnz = c->c_nnz;
+        c->sorted = (c->c_facts & ROWS_UNSORTED) ? 0 : 1;
+    } else {                                // the level did not reach its coarse operator: the chain ends here
+        c->A = HbmCsr{};
+        c->B.reset();
+        c->n = 0;
+        c->nnz = 0;
+    }
+    if (times_ms) {
+        std::copy(c->times_ms, c->times_ms + AMG_SA_CHAIN_STAGES - 1, times_ms);
+        times_ms[AMG_SA_CHAIN_STAGES - 1] = timer.lap();
+    }
+    return 0;
+}
+
+void amg_sa_chain_free(amg_sa_chain *c) { delete c; }
 
 }   // extern "C"

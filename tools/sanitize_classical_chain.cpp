@@ -85,6 +85,44 @@ int main()
     EXPECT(rb == 0 || rb == AMG_ENODEV);
     if (rb == 0) amg_classical_chain_free(c);
 
+    // the smoothed-aggregation chain: the same refusals at its begin, and what its level and fetch refuse without a chain
+    {
+        amg_sa_chain *s = nullptr;
+        auto sa_begin = [&](const std::vector<int> &p, const std::vector<int> &j, int n, bool with_B = true) {
+            std::vector<int> hp(p), hj(j);
+            std::vector<double> hx(hj.size(), 1.0), hB((size_t)(n > 0 ? n : 0), 1.0);
+            return amg_sa_chain_begin(n, hp.data(), hj.data(), hx.data(), with_B ? hB.data() : nullptr, &s);
+        };
+        EXPECT(sa_begin({0, 2, 4}, {0, 1, 1, 1}, 2) == AMG_EINVAL && !s);          // a column twice in a row
+        EXPECT(sa_begin({0, 2, 4}, {0, 1, 0, 2}, 2) == AMG_EINVAL && !s);          // outside
+        EXPECT(sa_begin({0, 2, 1}, {0, 1, 0, 1}, 2) == AMG_EINVAL && !s);          // offsets decrease
+        EXPECT(sa_begin({0}, {}, 0) == AMG_EINVAL && !s);                          // an empty operator
+        EXPECT(sa_begin({0, 2, 4}, {0, 1, 0, 1}, 2, false) == AMG_EINVAL && !s);   // no candidate
+        EXPECT(amg_sa_chain_begin(2, nullptr, nullptr, nullptr, r, &s) == AMG_EINVAL);
+        EXPECT(amg_sa_chain_begin(2, nullptr, nullptr, nullptr, r, nullptr) == AMG_EINVAL);
+        int sa_flags[AMG_SA_CHAIN_FLAG_FIELDS];
+        EXPECT(amg_sa_chain_level(nullptr, 2, 0.25, AMG_SA_STRENGTH_CSR, r, r, 1.0, 1, nullptr, 1e-10, sizes, sa_flags, nullptr, nullptr)
+               == AMG_EINVAL);
+        EXPECT(amg_sa_chain_fetch(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                  nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == AMG_EINVAL);
+        amg_sa_chain_free(nullptr);
+        const int sb = sa_begin({0, 2, 4}, {0, 1, 0, 1}, 2);
+        EXPECT(sb == 0 || sb == AMG_ENODEV);
+        if (sb == 0) {
+            // with a chain: the options a level refuses before it touches the device, each leaving the chain as it was
+            EXPECT(amg_sa_chain_level(s, 2, -0.5, AMG_SA_STRENGTH_CSR, r, r, 1.0, 1, nullptr, 1e-10, sizes, sa_flags, nullptr, nullptr) == AMG_EINVAL);
+            EXPECT(amg_sa_chain_level(s, 2, 0.25, 3, r, r, 1.0, 1, nullptr, 1e-10, sizes, sa_flags, nullptr, nullptr) == AMG_EINVAL);
+            EXPECT(amg_sa_chain_level(s, 2, 0.25, AMG_SA_STRENGTH_CSR, r, r, 1.0, -1, nullptr, 1e-10, sizes, sa_flags, nullptr, nullptr) == AMG_EINVAL);
+            EXPECT(amg_sa_chain_level(s, 2, 0.25, AMG_SA_STRENGTH_CSR, nullptr, r, 1.0, 1, nullptr, 1e-10, sizes, sa_flags, nullptr, nullptr)
+                   == AMG_EINVAL);
+            EXPECT(amg_sa_chain_level(s, 3, 0.25, AMG_SA_STRENGTH_CSR, r, r, 1.0, 1, nullptr, 1e-10, sizes, sa_flags, nullptr, nullptr)
+                   == AMG_EINVAL);         // not the resident operator's size: refused before y is read
+            EXPECT(amg_sa_chain_fetch(s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                      nullptr, nullptr, nullptr, nullptr, nullptr) == AMG_ESTATE);
+            amg_sa_chain_free(s);
+        }
+    }
+
     // extended+i without rows: the empty prolongator without a device, and its fetch releases it
     {
         std::vector<int> Ap0{0}, Sp0{0}, Pp0{-7};
